@@ -7,15 +7,29 @@
 
 One "step" = one full training step of the hot path on a resident synthetic batch: encoder + decoder forward, fused
 weighted cross-entropy, hand-written backward, (N > 1: RCCL all-reduce of the flat gradient arena), fused AdamW.
-Prints ONE JSON line (rank 0).  ``value`` is whole-job train images/s; the same line carries greedy captions/s, the
-roofline of the dominant kernel (the bf16 MFMA GEMM, timed live with HIP events) and the CPU baseline (the fp32
-oracle port on the host cores, rank 0 at N = 1 only, bounded sample).
+Prints ONE JSON line (rank 0).  ``value`` is whole-job train images/s and ``ms_per_step`` the wall time of one timed step.
+A plain run sets up, warms up, times the steps and prints that line.  ``--full`` adds the other legs to the same line: greedy
+captions/s, the PCIe-inclusive rate, the roofline of the dominant kernel (the bf16 MFMA GEMM, timed live with HIP events), the
+fused cross-attention kernel at the reference's GPU-config width, and the CPU baseline (the fp32 oracle port on the host cores,
+rank 0 at N = 1 only, bounded sample).
+
+The last timed step starts again from the initial parameters and optimizer state, restored outside the timed window: from
+random init, training amplifies the last-bit noise of the backward's atomic accumulations from step to step, so a state reached
+after several steps differs from run to run.  The same arguments therefore give the same inputs and the same last step on every
+run, up to rounding.
+
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0), for output-for-output comparison of two builds:
+``loss.npy`` (float64) and ``grad.<name>.npy`` (float32), the gradient of every parameter that its backward handed to AdamW, in
+full up to 65536 elements and as a fixed seeded sample of 65536 elements above that.  (The parameters after the update are not
+written: AdamW's first step moves each one by about lr times the sign of its gradient, and where a gradient is zero in exact
+arithmetic -- the cross-attention key bias -- that sign is rounding noise.)
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 import torch
 
@@ -40,11 +54,18 @@ def parse():
     ap.add_argument('--decode-batch', type=int, default=4096, help='captions per GPU per greedy run')
     ap.add_argument('--decode-reps', type=int, default=3)
     ap.add_argument('--decode-streams', type=int, default=3, help='independent caption batches decoded concurrently')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-decode', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--gemm-breakdown', action='store_true', help='per-shape GEMM table on stderr (2 timed steps)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also run the decode, kernel-timing, PCIe and CPU-baseline legs (off: the '
+                                                          'timed training steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the last timed step\'s loss and gradients as '
+                                                                          'DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-decode', action='store_true', help='with --full: skip the greedy decode leg')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: skip the per-kernel and PCIe legs')
+    ap.add_argument('--gemm-breakdown', action='store_true', help='with --full: per-shape GEMM table on stderr (2 timed steps)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 class GemmTimer:
@@ -267,6 +288,24 @@ def xattn_width_leg(ops, dev, images=2048, d=1280, dropout=0.1, reps=20):
     return out
 
 
+DUMP_SAMPLE = 65536
+
+
+def dump_outputs(out_dir, loss, grads):
+    """The last timed step's outputs as .npy: its loss (float64) and the (name, gradient) pairs of ``grads`` (float32; a tensor
+    above DUMP_SAMPLE elements as a fixed sample, the positions seeded by the parameter's name)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([float(loss.detach())], dtype=np.float64))
+    for name, t in grads:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f'grad.{name}.npy'), flat.float().cpu().numpy())
+
+
 def main():
     args = parse()
     # stdout carries exactly one JSON line: libraries that write to fd 1 (RCCL prints a version banner when the first
@@ -342,20 +381,42 @@ def main():
     # ---- the north star's kernel on the reference's GPU-config decoder width, stand-alone (before the training phase: the same launch
     # measured after 20 steps at 190 GB resident ran ~10 % slower -- the chip's clock state, not the kernel)
     xattn_wide = None
-    if not args.no_kernel_timing and rank == 0:
+    if args.full and not args.no_kernel_timing and rank == 0:
         log('xattn: one cross-attention layer of the gpu/nano.yaml decoder (d = 1280, 2048 images)')
         xattn_wide = xattn_width_leg(ops, dev, dropout=args.dropout)
         torch.cuda.empty_cache()
+    # The last timed step starts again from the initial parameters and optimizer state (restored with the clock stopped): training
+    # from random init amplifies the rounding noise of the backward's atomic accumulations from step to step, so the state after a
+    # few steps -- and all the step computes from it -- differs from run to run; from a fixed state, one step is reproducible.
+    train_params = [p for p in wrapper.model.parameters() if p.requires_grad]
+    init_params = [p.detach().to('cpu', copy=True) for p in train_params]
+
+    def restart():
+        with torch.no_grad():
+            for p, p0 in zip(train_params, init_params):
+                p.copy_(p0)
+        if opt._arena is not None:          # the moments and the arena exist once the optimizer has stepped
+            opt._m.zero_()
+            opt._v.zero_()
+            opt._arena.refresh_shadow()     # the bf16 weight shadow of the restored values, cast here rather than in the timed step
+        opt._step = 0
+
     fence()
     log(f'train: batch {args.batch}/gpu, {args.warmup} warm-up + {args.steps} timed steps')
     for _ in range(args.warmup):
         loss = step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         loss = step()
     fence()
     elapsed = time.perf_counter() - t0
+    restart()
+    fence()
+    t0 = time.perf_counter()
+    loss = step()
+    fence()
+    elapsed += time.perf_counter() - t0
     final_loss = float(loss.detach())
     log(f'train: {1e3 * elapsed / args.steps:.2f} ms/step')
     red_dev = dev if pg_backend == 'nccl' else 'cpu'           # the timing reductions travel on the control plane
@@ -364,10 +425,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     img_s = world * args.batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # the step's zero_grad drops the .grad views only: the gradient arena keeps what the last backward wrote until the next one
+        arena = wrapper.model._engine.arena
+        grads = [(n, arena.G(n)) for n, p in wrapper.model.named_parameters() if p.requires_grad and arena.G(n) is not None]
+        dump_outputs(args.dump_outputs, loss, grads)
+        log(f'outputs of the last timed step written to {args.dump_outputs}')
 
     # ---- the same step with the batch handed over as HOST buffers (pinned): PCIe-inclusive rate, reported beside `value`
     pcie_img_s = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         h_images, h_labels = images.cpu().pin_memory(), labels.cpu().pin_memory()
         fence()
         t1 = time.perf_counter()
@@ -381,7 +448,7 @@ def main():
 
     # ---- per-kernel timing of the dominant kernel (bf16 MFMA GEMM) with HIP events, 2 extra steps
     gemm = xattn = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         with GemmTimer(ops) as gt, XattnTimer(ops) as xt:
             for _ in range(2):
                 step()
@@ -394,7 +461,7 @@ def main():
 
     # ---- greedy decode: B captions x 64 new tokens per run (encoder + KV-cache decode under hipGraph replay)
     cap_s = dec_attn = dec_gemm = None
-    if not args.no_decode:
+    if args.full and not args.no_decode:
         wrapper.eval()
         opt.zero_grad()
         torch.cuda.empty_cache()              # hand the training step's cached blocks back before the decode leg allocates its own
@@ -456,7 +523,7 @@ def main():
                        'parallelism': f'dp{world}', 'dropout': args.dropout, 'optimizer': 'AdamW lr 6e-4 betas (0.9,0.95)',
                        'weights': 'random init (reference distributions)'},
             'greedy_captions_per_sec': None if cap_s is None else round(cap_s, 2),
-            'greedy_config': {'captions_per_batch': (Bd if not args.no_decode else args.decode_batch), 'concurrent_batches_per_gpu': args.decode_streams,
+            'greedy_config': {'captions_per_batch': (Bd if cap_s is not None else args.decode_batch), 'concurrent_batches_per_gpu': args.decode_streams,
                               'new_tokens': 64, 'ngrams': [2, 3, 4, 5], 'includes': 'encoder forward + KV-cache decode (hipGraph replay)'},
             'final_loss': round(final_loss, 4),
             'host_input_images_per_sec': None if pcie_img_s is None else round(pcie_img_s, 1),     # H2D copy of the batch inside the step
@@ -512,7 +579,7 @@ def main():
                                            'gemm_ms_per_run': round(dec_gemm['total_ms'], 2),
                                            'share_of_timed_decode_kernels': round(dec_gemm['total_ms'] / (dec_gemm['total_ms'] + dec_attn['total_ms']), 3)
                                            if dec_attn is not None else None}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(dropout=args.dropout)
         print(json.dumps(out), file=json_out, flush=True)
     if dp is not None:

@@ -15,7 +15,7 @@ from image2text_amd import ops  # noqa: E402
 
 BF16, F32 = torch.bfloat16, torch.float32
 REPS = 3
-# (M, N, K, a_kmajor, b_kmajor, out f32, epilogue) -- the step's heaviest shapes (bench.py --gemm-breakdown, B = 3072)
+# (M, N, K, a_kmajor, b_kmajor, out f32, epilogue) -- the step's heaviest shapes (bench.py --full --gemm-breakdown, B = 3072)
 SHAPES = [
     (798720, 2048, 512, 0, 0, 0, 'gelu_dout'), (798720, 2048, 512, 0, 1, 0, 'mul_aux'), (798720, 512, 2048, 0, 0, 1, 'res'),
     (798720, 1536, 512, 0, 0, 0, ''), (798720, 512, 2048, 0, 1, 0, ''), (798720, 512, 1536, 0, 1, 0, ''), (798720, 512, 512, 0, 0, 1, 'res'),
