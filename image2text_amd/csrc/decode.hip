@@ -163,39 +163,49 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
     }
 }
 
-// HF NoRepeatNGramLogitsProcessor + argmax for one caption per workgroup
+// The n-gram ban of both greedy kernels: bit t of the workgroup's dynamic-LDS bitmap (ceil(V / 32) words) is set when token t
+// is banned -- no cap on the number of matches (a capped list of matches, duplicates included, overflowed at ~1000 cached
+// tokens with three n-gram sizes and silently unbanned the rest), and one bit test per column instead of a scan of the list.
+constexpr int BAN_LDS_MAX = 64 * 1024;          // dynamic LDS bytes a greedy kernel may request: V up to ~500 k tokens
+__device__ __forceinline__ void build_ban_bitmap(unsigned* bits, const int64_t* row, int len, const int* ngram_sizes, int n_sizes, int V,
+                                                 int nthreads) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < (V + 31) / 32; w += nthreads) bits[w] = 0u;
+    __syncthreads();
+    for (int si = 0; si < n_sizes; ++si) {
+        const int n = ngram_sizes[si];
+        if (n < 1 || len + 1 < n) continue;              // block-uniform
+        // candidate n-gram starts i in [0, len - n]; it repeats the current (n-1)-token tail iff ids[i+j] == ids[len-n+1+j]
+        for (int i = tid; i <= len - n; i += nthreads) {
+            bool same = true;
+            for (int j = 0; j < n - 1; ++j) same = same && (row[i + j] == row[len - n + 1 + j]);
+            if (same) {
+                const int64_t t = row[i + n - 1];
+                if (t >= 0 && t < V) atomicOr(&bits[(int)t >> 5], 1u << ((int)t & 31));
+            }
+        }
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ bool ban_bit(const unsigned* bits, int c) { return (bits[c >> 5] >> (c & 31)) & 1u; }     // 0 <= c < V
+
+// HF NoRepeatNGramLogitsProcessor + argmax for one caption per workgroup.  A row with no finite allowed column (all banned)
+// gets token 0, torch.argmax's answer for a row of -inf, and margin 0.
 constexpr int BAN_THREADS = 1024;
-constexpr int MAX_BANNED = 1024;
 template <bool F32>
 __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const void* __restrict__ logits, int ld,
                                                                        int64_t* __restrict__ ids, int ids_ld,
                                                                        const int* __restrict__ len_ptr,
                                                                        const int* __restrict__ ngram_sizes, int n_sizes,
                                                                        int V, float* __restrict__ margin_out) {
-    __shared__ int banned[MAX_BANNED];
-    __shared__ int n_banned;
+    extern __shared__ unsigned dyn_lds[];              // ban bitmap, ceil(V / 32) words
     __shared__ float rv[BAN_THREADS / 64], rv2[BAN_THREADS / 64];
     __shared__ int ri[BAN_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int len = *len_ptr;
     int64_t* row = ids + (size_t)b * ids_ld;
-    if (tid == 0) n_banned = 0;
-    __syncthreads();
-    for (int si = 0; si < n_sizes; ++si) {
-        const int n = ngram_sizes[si];
-        if (n < 1 || len + 1 < n) continue;              // block-uniform
-        // candidate n-gram starts i in [0, len - n]; it repeats the current (n-1)-token tail iff ids[i+j] == ids[len-n+1+j]
-        for (int i = tid; i <= len - n; i += BAN_THREADS) {
-            bool same = true;
-            for (int j = 0; j < n - 1; ++j) same = same && (row[i + j] == row[len - n + 1 + j]);
-            if (same) {
-                int slot = atomicAdd(&n_banned, 1);
-                if (slot < MAX_BANNED) banned[slot] = (int)row[i + n - 1];
-            }
-        }
-    }
-    __syncthreads();
-    const int nb = min(n_banned, MAX_BANNED);
+    unsigned* banbits = dyn_lds;
+    build_ban_bitmap(banbits, row, len, ngram_sizes, n_sizes, V, BAN_THREADS);
     float best = -INFINITY, second = -INFINITY;
     int bi = 0x7fffffff;
     // fp32 rows with ld % 4 == 0 (the decode path pads to 8): 16-byte loads, 4 consecutive columns per lane per step
@@ -204,12 +214,11 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
     const int vend = vec4 ? (V & ~3) : 0;
     for (int c4 = tid * 4; c4 < vend; c4 += BAN_THREADS * 4) {
         const f32x4 q = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(logits) + (size_t)b * ld + c4);
+        const unsigned nib = (banbits[c4 >> 5] >> (c4 & 31)) & 15u;     // c4 % 4 == 0: the 4 columns' bits share a word
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float v = q[e];
+            const float v = ((nib >> e) & 1u) ? -INFINITY : q[e];
             const int c = c4 + e;
-            for (int k = 0; k < nb; ++k)
-                if (banned[k] == c) v = -INFINITY;
             if (v > best) {
                 second = best;
                 best = v;
@@ -222,8 +231,7 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
     for (int c = vend + tid; c < V; c += BAN_THREADS) {
         float v = F32 ? reinterpret_cast<const float*>(logits)[(size_t)b * ld + c]
                       : bf16_to_f32(reinterpret_cast<const bf16_t*>(logits)[(size_t)b * ld + c]);
-        for (int k = 0; k < nb; ++k)
-            if (banned[k] == c) v = -INFINITY;
+        if (ban_bit(banbits, c)) v = -INFINITY;
         if (v > best) {                                   // strided ascending scan: first index wins ties
             second = best;
             best = v;
@@ -262,8 +270,9 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
                 second = fmaxf(second, rv[k]);
             }
         }
-        row[len] = bi;
-        if (margin_out) margin_out[b] = best - second;
+        const bool none = bi == 0x7fffffff;                  // every column banned or -inf
+        row[len] = none ? 0 : bi;
+        if (margin_out) margin_out[b] = none ? 0.f : best - second;
     }
 }
 
@@ -271,41 +280,25 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
 // row, value descending / column ascending) instead of the logits themselves: a segment whose best column is not banned contributes
 // it, one whose best is banned contributes its second, and one whose two best are BOTH banned (rare: two continuations of repeated
 // n-grams among 64 neighbouring token ids, both ahead of everything else there) is re-evaluated exactly here -- 64 dot products of
-// the hidden row with the head's rows, banned columns left out.  One caption per workgroup.
-constexpr int T2_THREADS = 256, T2_MAX_REDO = 64;
+// the hidden row with the head's rows, banned columns left out.  Such segments are marked in an LDS bitmap of ceil(nseg / 32) words
+// behind the ban bitmap, so however many there are, none is dropped; each wave re-evaluates the marked segments of every fourth word.
+// One caption per workgroup; a row with every column banned gets token 0.
+constexpr int T2_THREADS = 256;
 __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32x4* __restrict__ top2, int nseg, const bf16_t* __restrict__ hid,
                                                                         int ld_h, const bf16_t* __restrict__ W, int ldw, int d,
                                                                         int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
                                                                         const int* __restrict__ ngram_sizes, int n_sizes, int V) {
-    __shared__ int banned[MAX_BANNED];
-    __shared__ int n_banned, n_redo;
-    __shared__ int redo[T2_MAX_REDO];
+    extern __shared__ unsigned dyn_lds[];              // ban bitmap (ceil(V / 32) words), then the redo bitmap (ceil(nseg / 32) words)
     __shared__ float rv[T2_THREADS / 64];
     __shared__ int ri[T2_THREADS / 64];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int len = *len_ptr;
     int64_t* row = ids + (size_t)b * ids_ld;
-    if (tid == 0) n_banned = n_redo = 0;
-    __syncthreads();
-    for (int si = 0; si < n_sizes; ++si) {                  // (as ngram_ban_argmax_kernel)
-        const int n = ngram_sizes[si];
-        if (n < 1 || len + 1 < n) continue;
-        for (int i = tid; i <= len - n; i += T2_THREADS) {
-            bool same = true;
-            for (int j = 0; j < n - 1; ++j) same = same && (row[i + j] == row[len - n + 1 + j]);
-            if (same) {
-                int slot = atomicAdd(&n_banned, 1);
-                if (slot < MAX_BANNED) banned[slot] = (int)row[i + n - 1];
-            }
-        }
-    }
-    __syncthreads();
-    const int nb = min(n_banned, MAX_BANNED);
-    auto is_banned = [&](int c) {
-        bool hit = false;
-        for (int k = 0; k < nb; ++k) hit = hit || (banned[k] == c);
-        return hit;
-    };
+    unsigned* banbits = dyn_lds;
+    unsigned* redo = dyn_lds + (V + 31) / 32;
+    const int nrw = (nseg + 31) / 32;
+    for (int w = tid; w < nrw; w += T2_THREADS) redo[w] = 0u;
+    build_ban_bitmap(banbits, row, len, ngram_sizes, n_sizes, V, T2_THREADS);      // (its barriers also cover the redo clear)
     float best = -INFINITY;
     int bi = 0x7fffffff;
     auto offer = [&](float v, int c) {
@@ -318,21 +311,23 @@ __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32
         const f32x4 t = top2[(size_t)b * nseg + sgm];
         const int i1 = __float_as_int(t[1]), i2 = __float_as_int(t[3]);
         if (!(t[0] > -INFINITY)) continue;                  // nothing valid in the segment
-        if (!is_banned(i1)) {
+        if ((unsigned)i1 >= (unsigned)V) continue;          // (a column index outside the vocabulary: never from i2t_gemm_bf16_top2)
+        if (!ban_bit(banbits, i1)) {
             offer(t[0], i1);
-        } else if (t[2] > -INFINITY && !is_banned(i2)) {
+        } else if (t[2] > -INFINITY && (unsigned)i2 < (unsigned)V && !ban_bit(banbits, i2)) {
             offer(t[2], i2);
         } else if (t[2] > -INFINITY) {                      // both leaders banned: what is left of the segment is unknown
-            const int slot = atomicAdd(&n_redo, 1);
-            if (slot < T2_MAX_REDO) redo[slot] = sgm;
+            atomicOr(&redo[sgm >> 5], 1u << (sgm & 31));
         }
     }
     __syncthreads();
-    const int nr = min(n_redo, T2_MAX_REDO);
-    for (int r = 0; r < nr; ++r) {                          // exact re-evaluation of a segment, one column per thread of wave 0
-        if (tid < 64) {
-            const int c = redo[r] * 64 + tid;
-            if (c < V && !is_banned(c)) {
+    for (int w = wave; w < nrw; w += T2_THREADS / 64) {     // exact re-evaluation of a segment, one column per lane of the wave
+        unsigned m = redo[w];
+        while (m) {                                          // wave-uniform
+            const int sgm = w * 32 + __builtin_ctz(m);
+            m &= m - 1u;
+            const int c = sgm * 64 + lane;
+            if (c < V && !ban_bit(banbits, c)) {
                 const bf16_t* wr = W + (size_t)c * ldw;
                 const bf16_t* hr = hid + (size_t)b * ld_h;
                 float acc = 0.f;
@@ -351,14 +346,14 @@ __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32
         const int oi = __shfl_xor(bi, o, 64);
         offer(ov, oi);
     }
-    if ((tid & 63) == 0) {
-        rv[tid >> 6] = best;
-        ri[tid >> 6] = bi;
+    if (lane == 0) {
+        rv[wave] = best;
+        ri[wave] = bi;
     }
     __syncthreads();
     if (tid == 0) {
         for (int k = 1; k < T2_THREADS / 64; ++k) offer(rv[k], ri[k]);
-        row[len] = bi;
+        row[len] = bi == 0x7fffffff ? 0 : bi;               // every column banned or -inf: torch.argmax's 0
     }
 }
 
@@ -410,11 +405,13 @@ extern "C" int i2t_decode_attention(void* stream, const void* q, int q_rs, void*
 extern "C" int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, int logits_is_f32, int64_t* ids, int ids_ld,
                                     int* len_ptr, const int* ngram_sizes, int n_sizes, int B, int V, float* margin_out) {
     I2T_REQUIRE(logits && ids && len_ptr && B > 0 && V > 0 && (n_sizes == 0 || ngram_sizes), "i2t_ngram_ban_argmax: bad args");
+    const size_t lds = (size_t)(V + 31) / 32 * sizeof(unsigned);
+    I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_ngram_ban_argmax: vocabulary %d: the ban bitmap exceeds %d bytes of LDS", V, BAN_LDS_MAX);
     if (logits_is_f32)
-        hipLaunchKernelGGL(ngram_ban_argmax_kernel<true>, dim3(B), dim3(BAN_THREADS), 0, (hipStream_t)stream, logits, ld, ids,
+        hipLaunchKernelGGL(ngram_ban_argmax_kernel<true>, dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
                            ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out);
     else
-        hipLaunchKernelGGL(ngram_ban_argmax_kernel<false>, dim3(B), dim3(BAN_THREADS), 0, (hipStream_t)stream, logits, ld, ids,
+        hipLaunchKernelGGL(ngram_ban_argmax_kernel<false>, dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
                            ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out);
     I2T_CHECK_LAUNCH("i2t_ngram_ban_argmax");
     return I2T_OK;
@@ -426,7 +423,9 @@ extern "C" int i2t_top2_ngram_argmax(void* stream, const float* top2, int nseg, 
                 "i2t_top2_ngram_argmax: bad args (nseg must be ceil(V / 64))");
     I2T_REQUIRE(d % 8 == 0 && (ld_hidden & 7) == 0 && (ld_w & 7) == 0 && ALIGNED16(top2) && ALIGNED16(hidden) && ALIGNED16(w_head),
                 "i2t_top2_ngram_argmax: hidden / head rows must be 16-byte aligned, d %% 8 == 0");
-    hipLaunchKernelGGL(top2_ngram_argmax_kernel, dim3(B), dim3(T2_THREADS), 0, (hipStream_t)stream, (const f32x4*)top2, nseg,
+    const size_t lds = ((size_t)(V + 31) / 32 + (nseg + 31) / 32) * sizeof(unsigned);
+    I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_top2_ngram_argmax: vocabulary %d: the ban bitmaps exceed %d bytes of LDS", V, BAN_LDS_MAX);
+    hipLaunchKernelGGL(top2_ngram_argmax_kernel, dim3(B), dim3(T2_THREADS), lds, (hipStream_t)stream, (const f32x4*)top2, nseg,
                        (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, V);
     I2T_CHECK_LAUNCH("i2t_top2_ngram_argmax");
     return I2T_OK;

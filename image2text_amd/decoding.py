@@ -44,6 +44,21 @@ class Sampling(NamedTuple):
         return (float(self.temperature), int(self.top_k or 0), None if self.nucleus_p is None else float(self.nucleus_p))
 
 
+# i2t_decode_attention and i2t_gq_decode_attention keep the scores of at most this many keys per caption in LDS; neither reads a key
+# count from the device against it, so the cache the step attends over is never allocated longer
+DECODE_MAX_KEYS = 1024
+
+
+def text_window(block: int, off: int, prefix: int) -> int:
+    """Text positions of the decode step's self-attention cache: the decoder's block less the soft-prompt offset ``off``, capped so
+    that ``prefix`` cached prompt rows + the text fit in DECODE_MAX_KEYS keys."""
+    tmax = min(block - off, DECODE_MAX_KEYS - prefix)
+    if tmax < 1:
+        raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
+                         f'no room for text (block {block}, soft-prompt offset {off})')
+    return tmax
+
+
 class GreedyDecoder:
     """KV-cache decoder; greedy by default, ``generate(..., sampling=Sampling(...))`` draws tokens on the device instead."""
 
@@ -60,12 +75,10 @@ class GreedyDecoder:
         cfg = self.model.config
         ncls = eng.enc.ncls
         off = ncls if cfg.use_soft_prompting else 0
-        tmax = dc.block - off
         d, ff = dc.d, dc.ff
-        if dc.llama is not None:        # i2t_gq_decode_attention walks at most 1024 cached keys per caption (prompt rows included)
-            tmax = min(tmax, 1024 - min(ncls, dc.block))
         # Hugging Face decoder + soft prompt (engine.decode_prefixed): the encoder outputs are the first cache positions of every caption
         prefix = min(ncls, dc.block) if dc.prefixed else 0
+        tmax = text_window(dc.block, off, prefix)
         st = SimpleNamespace(B=B, ids_ld=ids_ld, off=off, tmax=tmax, arena=a, sparse_epoch=eng.sparse_epoch, prefix=prefix,
                              clen=tmax + prefix)
         e = lambda *s, dtype=BF16: torch.zeros(*s, dtype=dtype, device=dev)

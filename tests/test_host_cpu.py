@@ -713,3 +713,18 @@ def test_every_shipped_pretrained_vit_preset_builds(preset, monkeypatch):
         last = kw['n_cls'] - 1
         assert enc.state_dict()[f'proj.models.{last}.model.2.weight'].shape == (kw['n_embd_out_vit'], kw['gate_sizes'][0])
         assert (f'proj.models.{last}.residual_connector.weight' in keys) == (kw['n_embd_out_vit'] != 768)
+
+
+def test_decode_text_window_keeps_the_attention_key_bound():
+    """The KV-cache decode step attends over at most 1024 keys per caption (the kernels' LDS score rows): the text window is capped
+    for every decoder path, and a cached prompt that leaves no room is refused before any buffer is made."""
+    from image2text_amd.decoding import DECODE_MAX_KEYS, text_window
+    assert DECODE_MAX_KEYS == 1024
+    assert text_window(1024, 0, 0) == 1024
+    assert text_window(1024, 197, 0) == 827                  # soft prompt: positions shift, the cache holds text only
+    assert text_window(4096, 0, 0) == 1024                   # a longer block is capped
+    assert text_window(4096, 197, 197) == 1024 - 197          # cached prompt rows count against the bound
+    assert text_window(64, 8, 8) == 56
+    for block, off, prefix in ((2048, 1024, 1024), (4096, 1100, 1100)):
+        with pytest.raises(ValueError, match='at most 1024 keys'):
+            text_window(block, off, prefix)
