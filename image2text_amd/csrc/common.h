@@ -169,6 +169,33 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
+// The n-gram ban of the greedy and beam kernels (decode.hip, beam.hip): bit t of the workgroup's dynamic-LDS bitmap (ceil(V / 32)
+// words) is set when token t is banned -- no cap on the number of matches (a capped list of matches, duplicates included, overflowed
+// at ~1000 cached tokens with three n-gram sizes and silently unbanned the rest), and one bit test per column instead of a scan of
+// the list.
+constexpr int BAN_LDS_MAX = 64 * 1024;          // dynamic LDS bytes a greedy kernel may request: V up to ~500 k tokens
+__device__ __forceinline__ void build_ban_bitmap(unsigned* bits, const int64_t* row, int len, const int* ngram_sizes, int n_sizes, int V,
+                                                 int nthreads) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < (V + 31) / 32; w += nthreads) bits[w] = 0u;
+    __syncthreads();
+    for (int si = 0; si < n_sizes; ++si) {
+        const int n = ngram_sizes[si];
+        if (n < 1 || len + 1 < n) continue;              // block-uniform
+        // candidate n-gram starts i in [0, len - n]; it repeats the current (n-1)-token tail iff ids[i+j] == ids[len-n+1+j]
+        for (int i = tid; i <= len - n; i += nthreads) {
+            bool same = true;
+            for (int j = 0; j < n - 1; ++j) same = same && (row[i + j] == row[len - n + 1 + j]);
+            if (same) {
+                const int64_t t = row[i + n - 1];
+                if (t >= 0 && t < V) atomicOr(&bits[(int)t >> 5], 1u << ((int)t & 31));
+            }
+        }
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ bool ban_bit(const unsigned* bits, int c) { return (bits[c >> 5] >> (c & 31)) & 1u; }     // 0 <= c < V
+
 // LDS transposed read: 4 rows x 16 cols block of 16-bit elements per 16-lane group, delivered column-major
 // (cdna_hip_programming.md T10).  EXEC must be all ones at the call site.
 __device__ __forceinline__ s16x4 lds_read_tr16(const void* lds_ptr) {

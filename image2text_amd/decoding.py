@@ -68,7 +68,9 @@ class GreedyDecoder:
         self._state = None
 
     # ------------------------------------------------------------------------------------------------ buffers
-    def _build(self, B: int, ids_ld: int):
+    def _build(self, B: int, ids_ld: int, mem_rows: Optional[int] = None):
+        """Buffers of a step over B rows; the cross-attention memory holds ``mem_rows`` (default B) rows -- the images, when the B
+        rows are beams of them (BeamDecoder)."""
         eng, a = self.eng, self.eng.arena
         dc = eng.dec
         dev = a.device
@@ -106,7 +108,9 @@ class GreedyDecoder:
             st.kc = [e(B, st.clen, d) for _ in range(dc.L)]
             st.vc = [e(B, st.clen, d) for _ in range(dc.L)]
         S = ncls
-        st.cross_kv = {l: (e(B, S, 2 * d), S) for l in self._cross_layers()}
+        st.cross_kv = {l: (e(mem_rows or B, S, 2 * d), S) for l in self._cross_layers()}
+        st.hist = None                      # beam search: int32 [B][clen] history table (BeamDecoder), None: row b's keys are row b's
+        st.mem_div = 1                      # rows per cross-attention memory row
         if dc.fam is not None:
             self._build_family(st, e)
         if dc.advpos:
@@ -188,14 +192,22 @@ class GreedyDecoder:
             else:
                 ops.gemm(st.ln, a.W(f'{p}.attn.c_attn.weight'), st.qkv, B, 3 * d, d, bias=a.P(f'{p}.attn.c_attn.bias'), workspace=st.ws)
                 qv, kn, vn, out_name = st.qkv[:, :d], st.qkv[:, d:2 * d], st.qkv[:, 2 * d:], 'attn.c_proj'
-            ops.gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd)
+            if st.hist is None:
+                ops.gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd)
+            else:
+                ops.beam_gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd,
+                                             hist=st.hist)
             ops.gemm(st.ao, a.W(f'{p}.{out_name}.weight'), xo, B, d, d, bias=a.P(f'{p}.{out_name}.bias'), residual=st.x, workspace=st.ws)
             if l in st.cross_kv:
                 kv, S = st.cross_kv[l]
                 win, bin_ = a.W(f'{p}.cross_attn.in_proj_weight'), a.P(f'{p}.cross_attn.in_proj_bias')
                 ops.layernorm_fwd(xo, a.P(f'{p}.ln_3.weight'), a.P(f'{p}.ln_3.bias'), st.ln, None, None, B, d)
                 ops.gemm(st.ln, win[:d], st.q, B, d, d, bias=bin_[:d], workspace=st.ws)
-                ops.gq_decode_attention(st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, hd)
+                if st.mem_div == 1:
+                    ops.gq_decode_attention(st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, hd)
+                else:
+                    ops.beam_gq_decode_attention(st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, hd,
+                                                 rows_per_mem=st.mem_div)
                 ops.gemm(st.ao, a.W(f'{p}.cross_attn.out_proj.weight'), xo, B, d, d, bias=a.P(f'{p}.cross_attn.out_proj.bias'), residual=xo, workspace=st.ws)
             ops.layernorm_fwd(xo, a.P(f'{p}.ln_2.weight'), a.P(f'{p}.ln_2.bias'), st.ln, None, None, B, d)
             if sp.moe is not None:
@@ -219,7 +231,30 @@ class GreedyDecoder:
         """Consume the token at ids[:, pos]; when with_head also choose ids[:, len] (argmax after the n-gram ban, or a draw from
         the filtered distribution when ``sampling`` is given); then advance pos and len."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
-        B, d, ff, H = st.B, dc.d, dc.ff, dc.H
+        B, d = st.B, dc.d
+        len_ptr = st.counters[1:2]
+        self._body(st)
+        if with_head:
+            self._final_norm(st)
+            if top2 and sampling is None:
+                # greedy, nobody asked for margins: the lm_head leaves the two largest logits of every 64-column segment of a row
+                # instead of the row (51 MB instead of 823 MB written and read back at 4096 captions), the ban + argmax merges them
+                ops.gemm_top2(st.hid, a.W(eng.n_head), st.top2, B, dc.V, d)
+                ops.top2_ngram_argmax(st.top2, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, d)
+                ops.advance(st.counters, 1)
+                return
+            ops.gemm(st.hid, a.W(eng.n_head), st.logits, B, dc.V, d, workspace=st.ws)
+            if sampling is None:
+                ops.ngram_ban_argmax(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, st.margin)
+            else:
+                ops.sample_token(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V,
+                                 sampling.temperature, sampling.top_k, sampling.nucleus_p, st.seed, dist_out=st.dist)
+        ops.advance(st.counters, 1)                            # pos and len together
+
+    def _body(self, st):
+        """Embedding of the token at ids[:, len - 1] and the decoder blocks at position pos: st.x holds the new hidden rows."""
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        B, d = st.B, dc.d
         pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
         dp = eng.dp
         ops.embed_step(st.ids, st.ids_ld, len_ptr, a.P(eng.n_wte),
@@ -241,28 +276,18 @@ class GreedyDecoder:
             self._layers_family(st)
         else:
             self._layers_dense(st)
-        if with_head:
-            if dc.llama is not None and dc.llama.arch == 'falcon':
-                wn = dp + dc.llama.norm_f
-                ops.layernorm_fwd(st.x, a.P(wn + '.weight'), a.P(wn + '.bias'), st.hid, None, None, B, d, eps=dc.llama.eps)
-            elif dc.llama is not None:
-                ops.rmsnorm_fwd(st.x, a.P(dp + dc.llama.norm_f + '.weight'), st.hid, None, B, d, dc.llama.eps)
-            else:
-                ops.layernorm_fwd(st.x, a.P(f'{dp}transformer.ln_f.weight'), a.P(f'{dp}transformer.ln_f.bias'), st.hid, None, None, B, d)
-            if top2 and sampling is None:
-                # greedy, nobody asked for margins: the lm_head leaves the two largest logits of every 64-column segment of a row
-                # instead of the row (51 MB instead of 823 MB written and read back at 4096 captions), the ban + argmax merges them
-                ops.gemm_top2(st.hid, a.W(eng.n_head), st.top2, B, dc.V, d)
-                ops.top2_ngram_argmax(st.top2, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, d)
-                ops.advance(st.counters, 1)
-                return
-            ops.gemm(st.hid, a.W(eng.n_head), st.logits, B, dc.V, d, workspace=st.ws)
-            if sampling is None:
-                ops.ngram_ban_argmax(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, st.margin)
-            else:
-                ops.sample_token(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V,
-                                 sampling.temperature, sampling.top_k, sampling.nucleus_p, st.seed, dist_out=st.dist)
-        ops.advance(st.counters, 1)                            # pos and len together
+
+    def _final_norm(self, st):
+        """st.hid = the final norm of st.x (the lm_head's input)."""
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        B, d, dp = st.B, dc.d, eng.dp
+        if dc.llama is not None and dc.llama.arch == 'falcon':
+            wn = dp + dc.llama.norm_f
+            ops.layernorm_fwd(st.x, a.P(wn + '.weight'), a.P(wn + '.bias'), st.hid, None, None, B, d, eps=dc.llama.eps)
+        elif dc.llama is not None:
+            ops.rmsnorm_fwd(st.x, a.P(dp + dc.llama.norm_f + '.weight'), st.hid, None, B, d, dc.llama.eps)
+        else:
+            ops.layernorm_fwd(st.x, a.P(f'{dp}transformer.ln_f.weight'), a.P(f'{dp}transformer.ln_f.bias'), st.hid, None, None, B, d)
 
     def _w(self, l: int, site: str, name: str, rows=None):
         """bf16 weight of a decoder linear for the decode step: the arena's shadow, or -- under a LoRA adapter -- the merged
@@ -284,15 +309,22 @@ class GreedyDecoder:
             ops.layernorm_fwd(st.x, a.P(f'{p}.ln_1.weight'), a.P(f'{p}.ln_1.bias'), st.ln, None, None, B, d)
             ops.gemm(st.ln, self._w(l, 'attn_c_attn', f'{p}.attn.c_attn.weight'), st.qkv, B, 3 * d, d, bias=a.P(f'{p}.attn.c_attn.bias'),
                      workspace=st.ws)
-            ops.decode_attention(st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, H, append_dm=d,
-                                 cache_hs=st.clen * 64)           # head-major self-attention cache [B][H][prefix + tmax][64]
+            if st.hist is None:
+                ops.decode_attention(st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, H, append_dm=d,
+                                     cache_hs=st.clen * 64)       # head-major self-attention cache [B][H][prefix + tmax][64]
+            else:
+                ops.beam_decode_attention(st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, H, hist=st.hist,
+                                          append_dm=d, cache_hs=st.clen * 64)
             ops.gemm(st.ao, a.W(f'{p}.attn.c_proj.weight'), st.x, B, d, d, bias=a.P(f'{p}.attn.c_proj.bias'), residual=st.x, workspace=st.ws)
             if l in st.cross_kv:
                 kv, S = st.cross_kv[l]
                 win, bin_ = a.W(f'{p}.cross_attn.in_proj_weight'), a.P(f'{p}.cross_attn.in_proj_bias')
                 ops.layernorm_fwd(st.x, a.P(f'{p}.ln_3.weight'), a.P(f'{p}.ln_3.bias'), st.ln, None, None, B, d)
                 ops.gemm(st.ln, win[:d], st.q, B, d, d, bias=bin_[:d], workspace=st.ws)
-                ops.decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H)
+                if st.mem_div == 1:
+                    ops.decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H)
+                else:
+                    ops.beam_decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H, rows_per_mem=st.mem_div)
                 ops.gemm(st.ao, a.W(f'{p}.cross_attn.out_proj.weight'), st.x, B, d, d,
                          bias=a.P(f'{p}.cross_attn.out_proj.bias'), residual=st.x, workspace=st.ws)
             ops.layernorm_fwd(st.x, a.P(f'{p}.ln_2.weight'), a.P(f'{p}.ln_2.bias'), st.ln, None, None, B, d)
@@ -318,8 +350,7 @@ class GreedyDecoder:
                 ops.layernorm_fwd(st.x, v.n1, v.b1, st.ln, None, None, B, d, eps=ls.eps)
                 ops.gemm(st.ln, v.Wqkv, st.qkv, B, v.nq, d, workspace=st.ws)
                 ops.rope(st.qkv, v.nq, 0, H + G, hd, cs, B, pos_ptr=pos_ptr)
-                ops.gq_decode_attention(st.qkv[:, :H * hd], st.qkv[:, H * hd:(H + G) * hd], st.qkv[:, (H + G) * hd:], st.kc[l], st.vc[l],
-                                        st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd)
+                self._gq_self_attention(st, l, H, G, hd)
                 ops.gemm(st.ao, v.Wo, st.x, B, d, H * hd, residual=st.x, workspace=st.ws)
                 ops.gemm(st.ln, v.Wgu, st.h, B, ff, d, act=ops.ACT_GELU_ERF)
                 ops.gemm(st.h, v.Wdn, st.x, B, d, ff, residual=st.x, workspace=st.ws)
@@ -327,44 +358,31 @@ class GreedyDecoder:
             ops.rmsnorm_fwd(st.x, v.n1, st.ln, None, B, d, ls.eps)
             ops.gemm(st.ln, v.Wqkv, st.qkv, B, v.nq, d, bias=v.bqkv, workspace=st.ws)
             ops.rope(st.qkv, v.nq, 0, H + G, hd, cs, B, pos_ptr=pos_ptr)
-            ops.gq_decode_attention(st.qkv[:, :H * hd], st.qkv[:, H * hd:(H + G) * hd], st.qkv[:, (H + G) * hd:], st.kc[l], st.vc[l],
-                                    st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd)
+            self._gq_self_attention(st, l, H, G, hd)
             ops.gemm(st.ao, v.Wo, st.x, B, d, H * hd, residual=st.x, workspace=st.ws)
             ops.rmsnorm_fwd(st.x, v.n2, st.ln, None, B, d, ls.eps)
             ops.gemm(st.ln, v.Wgu, st.gu, B, 2 * ff, d, workspace=st.ws)
             ops.swiglu_fwd(st.gu, st.h, B, ff)
             ops.gemm(st.h, v.Wdn, st.x, B, d, ff, residual=st.x, workspace=st.ws)
 
-    def _capture(self, st, with_head: bool, sampling: Optional[Sampling] = None, top2: bool = False):
-        side = torch.cuda.Stream(device=st.arena.device)
-        side.wait_stream(torch.cuda.current_stream())
-        g = ops.Graph()
-        with torch.cuda.stream(side):
-            g.begin()
-            self._step(st, with_head, sampling, top2)
-            g.end()
-        torch.cuda.current_stream().wait_stream(side)
-        return g
+    def _gq_self_attention(self, st, l: int, H: int, G: int, hd: int):
+        """Self-attention of a Llama-2 / Qwen2 / Falcon decode step over the row-major cache [B][slot][G hd] (packed q | k | v rows)."""
+        B, pos_ptr = st.B, st.counters[0:1]
+        q, k, v = st.qkv[:, :H * hd], st.qkv[:, H * hd:(H + G) * hd], st.qkv[:, (H + G) * hd:]
+        if st.hist is None:
+            ops.gq_decode_attention(q, k, v, st.kc[l], st.vc[l], st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd)
+        else:
+            ops.beam_gq_decode_attention(q, k, v, st.kc[l], st.vc[l], st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd,
+                                         hist=st.hist)
 
-    # ------------------------------------------------------------------------------------------------ public
-    @torch.no_grad()
-    def generate(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, return_margins: bool = False,
-                 use_graph: bool = True, sampling: Optional[Sampling] = None, return_dists: bool = False):
-        """-> ids (B, P + max_new_tokens) [, margins (B, N) greedy only] [, dists (B, N, V) sampling only: the filtered,
-        renormalised distribution every token was drawn from]."""
-        eng = self.eng
-        if not eng.dec.causal:      # nothing to cache under bidirectional attention: the reference's re-evaluation loop
-            assert not return_margins and not return_dists, 'margins / distributions are recorded on the KV-cache path only'
-            return generate_by_recompute(self.model, images, prompt_ids, max_new_tokens, sampling)
-        a = eng.prepare(False)
-        dc = eng.dec
-        B, P = prompt_ids.shape
-        total = P + max_new_tokens
-        st = self._state
-        if st is None or st.B != B or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch:
-            st = self._state = self._build(B, max(total, dc.block))
-        assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
-        assert not (return_margins and sampling is not None) and not (return_dists and sampling is None)
+    def _capture(self, st, with_head: bool, sampling: Optional[Sampling] = None, top2: bool = False):
+        return _capture_launches(st.arena.device, lambda: self._step(st, with_head, sampling, top2))
+
+    def _prepare_inputs(self, st, images, B: int, W: int = 1):
+        """Everything a step reads besides the ids: the encoder output of the B images, the per-layer cross K/V (B rows), the
+        soft-prompt rows' K/V at the head of the cache (copied to the W rows b * W .. b * W + W - 1 of every image) and the packed
+        expert weights."""
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         # encoder + per-layer cross K/V (once per image)
         # (in slices of ENC_CHUNK images -- 4096: +1.4 % captions/s over 1024 -- every image is independent in the encoder, and its activations -- ~20 MB per
         # image in eval mode -- would otherwise set the memory footprint of a large caption batch)
@@ -388,14 +406,15 @@ class GreedyDecoder:
                 ops.gemm(mem, self._w(l, 'xattn_c_attn', f'{p}.in_proj_weight', slice(dc.d, 3 * dc.d)), kv.view(B * S, 2 * dc.d), B * S,
                          2 * dc.d, dc.d, bias=a.P(f'{p}.in_proj_bias')[dc.d:])
         if st.prefix:       # the prompt rows' keys and values (one causal pass over the encoder outputs) open every caption's cache
+                            # (every one of its W rows)
             n_p = st.prefix
             if dc.llama is not None:          # row-major cache [B][slot][Hkv hd]; the saved keys already carry their rotation.  Each layer's
                 ls = dc.llama                 # K / V go into the cache as the layer finishes (a 7-B model's 32 saves would not fit beside it)
 
                 def take_kv(l, sv):
                     qkv = sv.qkv.view(B, n_p, -1)
-                    st.kc[l][:, :n_p].copy_(qkv[..., ls.H * ls.hd:(ls.H + ls.Hkv) * ls.hd])
-                    st.vc[l][:, :n_p].copy_(qkv[..., (ls.H + ls.Hkv) * ls.hd:])
+                    st.kc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(qkv[..., ls.H * ls.hd:(ls.H + ls.Hkv) * ls.hd].unsqueeze(1))
+                    st.vc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(qkv[..., (ls.H + ls.Hkv) * ls.hd:].unsqueeze(1))
                 eng._layer_sink = take_kv
             try:
                 _, _, pctx = eng.decode_segment(B, n_p, eng._mem_bf16(enc_out) if eng.cross_inputs else None, S, True,
@@ -404,14 +423,35 @@ class GreedyDecoder:
                 eng._layer_sink = None
             for l in range(dc.L if dc.llama is None else 0):
                 qkv = pctx.saves[l].qkv.view(B, n_p, 3, dc.H, 64)
-                st.kc[l].view(B, dc.H, st.clen, 64)[:, :, :n_p].copy_(qkv[:, :, 1].transpose(1, 2))
-                st.vc[l].view(B, dc.H, st.clen, 64)[:, :, :n_p].copy_(qkv[:, :, 2].transpose(1, 2))
+                st.kc[l].view(B, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(qkv[:, :, 1].transpose(1, 2).unsqueeze(1))
+                st.vc[l].view(B, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(qkv[:, :, 2].transpose(1, 2).unsqueeze(1))
             del pctx
         if dc.fam is not None and dc.fam.moe is not None:       # the packed expert output weights follow the current parameters
             for l in range(dc.L):
                 for part in ('c_fc', 'c_proj'):
                     mv = eng._moe_views(f'{eng.dp}transformer.h.{l}.mlp.{part}', dc.fam.moe)
                     ops.moe_pack_w2(mv.l2w, mv.l2b, mv.W2aug, mv.out_f, dc.fam.moe.E, dc.fam.moe.P)
+
+    # ------------------------------------------------------------------------------------------------ public
+    @torch.no_grad()
+    def generate(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, return_margins: bool = False,
+                 use_graph: bool = True, sampling: Optional[Sampling] = None, return_dists: bool = False):
+        """-> ids (B, P + max_new_tokens) [, margins (B, N) greedy only] [, dists (B, N, V) sampling only: the filtered,
+        renormalised distribution every token was drawn from]."""
+        eng = self.eng
+        if not eng.dec.causal:      # nothing to cache under bidirectional attention: the reference's re-evaluation loop
+            assert not return_margins and not return_dists, 'margins / distributions are recorded on the KV-cache path only'
+            return generate_by_recompute(self.model, images, prompt_ids, max_new_tokens, sampling)
+        a = eng.prepare(False)
+        dc = eng.dec
+        B, P = prompt_ids.shape
+        total = P + max_new_tokens
+        st = self._state
+        if st is None or st.B != B or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch:
+            st = self._state = self._build(B, max(total, dc.block))
+        assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
+        assert not (return_margins and sampling is not None) and not (return_dists and sampling is None)
+        self._prepare_inputs(st, images, B)
         if sampling is not None:
             seed = sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
             lo, hi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
@@ -456,6 +496,149 @@ class GreedyDecoder:
         if return_dists:
             return out, dists.transpose(0, 1).contiguous()
         return out
+
+
+class BeamSpec(NamedTuple):
+    """Arguments of a beam search (BeamSearchTokenGenerator's, models/generation_utils.py); eos None: no EOS rule."""
+    beam_width: int = 3
+    expansion: int = 4
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    consolidation_temperature: float = 1.0
+    eos: Optional[int] = None
+    log_boost: float = 0.0
+    ngram_sizes: tuple = (2, 3, 4)
+
+    def key(self):
+        return (int(self.beam_width), int(self.expansion), float(self.temperature), int(self.top_k or 0),
+                float(self.consolidation_temperature), -1 if self.eos is None else int(self.eos), float(self.log_boost),
+                tuple(int(n) for n in self.ngram_sizes))
+
+
+class BeamDecoder(GreedyDecoder):
+    """Beam search on the static KV cache: R = B * W rows (batch-major, r = b * W + w) through GreedyDecoder's buffers and layer
+    sequence, one captured hipGraph replay per token.  The step's head is the fp32 lm_head, then on the device (csrc/beam.hip):
+    i2t_beam_candidates (ban, crop, E candidates, EOS rule) -> i2t_beam_consolidate (W survivors per caption, ids and history rows
+    moved to the children) -> i2t_beam_advance.  Survivors copy no K/V: the history table st.hist[r][t] names the cache row that
+    holds key t of beam r, and the attention kernels read through it.  The encoder and the cross K/V run once per image
+    (rows_per_mem = W); the prompt is prefilled for all R rows under the identity table.  Once every beam of every caption holds
+    EOS the remaining replays do nothing, so the host launches them all and reads the final length once."""
+
+    def _build_beam(self, B: int, spec: BeamSpec, ids_ld: int, record: bool):
+        W, E = spec.beam_width, spec.expansion
+        R = B * W
+        st = self._build(R, ids_ld, mem_rows=B)
+        dev = st.arena.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        st.W, st.images = W, B
+        st.mem_div = W
+        st.hist = torch.zeros(R, st.clen, **i32)
+        st.hist_init = torch.arange(R, **i32).unsqueeze(1).expand(R, st.clen).contiguous()
+        st.cand_tok, st.cand_lp = torch.zeros(R, E, **i32), torch.zeros(R, E, dtype=F32, device=dev)
+        st.scores = torch.zeros(R, dtype=F32, device=dev)
+        st.has_eos, st.parent = torch.zeros(R, **i32), torch.zeros(R, **i32)
+        st.ctrl = torch.zeros(2, **i32)                         # [done, unfinished captions]
+        st.raw_tok = torch.zeros(R, E, **i32) if record else None
+        st.raw_pick = torch.zeros(R, **i32) if record else None
+        st.spec = spec
+        st.beam_ngrams = torch.tensor(list(spec.ngram_sizes), **i32)
+        return st
+
+    def _beam_step(self, st):
+        eng, a, dc, sp = self.eng, self.eng.arena, self.eng.dec, st.spec
+        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
+        self._body(st)
+        self._final_norm(st)
+        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        ops.beam_candidates(st.logits, st.ids, len_ptr, st.ctrl, st.beam_ngrams, st.B, dc.V, sp.expansion, sp.temperature, sp.top_k,
+                            sp.eos, sp.log_boost, st.seed, st.cand_tok, st.cand_lp, st.raw_tok)
+        ops.beam_consolidate(st.cand_tok, st.cand_lp, st.scores, st.ids, st.hist, st.has_eos, st.parent, pos_ptr, len_ptr, st.ctrl,
+                             st.images, st.W, sp.expansion, sp.consolidation_temperature, sp.eos, st.seed, st.raw_pick)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    @torch.no_grad()
+    def search(self, images, prompt_ids: torch.Tensor, max_len: int, spec: BeamSpec, seed: Optional[int] = None, use_graph: bool = True,
+               record: bool = False):
+        """-> ids (B, W, L), cumulative log scores (B, W) [, draws: per step the raw candidate draws (B * W, E) before the EOS rule
+        and the flat picks (B, W) of consolidation, when ``record``].  Steps run while the length is below ``max_len`` and some
+        caption still has a beam without EOS (BeamSearchTokenGenerator's loop test); ``seed`` (64-bit) keys the draws."""
+        eng = self.eng
+        dc = eng.dec
+        if not dc.causal:
+            raise ValueError('BeamDecoder needs a causal decoder')
+        if dc.fam is not None and dc.fam.sparse:
+            raise NotImplementedError('beam search on the KV cache does not cover sparse decoder blocks: a sparse layer caches its kept '
+                                      'positions only, at slots that the per-beam history table does not address')
+        W, E = spec.beam_width, spec.expansion
+        if spec.temperature > 0 and spec.top_k is not None and 0 < spec.top_k < E:
+            raise ValueError(f'top_k = {spec.top_k} leaves fewer than beam_expansion_factor = {E} tokens to draw without replacement')
+        a = eng.prepare(False)
+        prompt_ids = prompt_ids.to(a.device)
+        B, P = prompt_ids.shape
+        R = B * W
+        total = max(P, max_len)
+        n_steps = total - P
+        st = self._state
+        if (st is None or st.B != R or getattr(st, 'W', None) != W or st.arena is not a or st.ids_ld < total
+                or st.sparse_epoch != eng.sparse_epoch or st.spec.key() != spec.key() or (st.raw_tok is not None) != record):
+            self._state = None
+            st = self._state = self._build_beam(B, spec, max(total, dc.block), record)
+        assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
+        prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
+        if spec.eos is not None and bool((prompt_ids == spec.eos).any(dim=-1).all()):
+            ids = prompt_rows.view(B, W, P).clone()          # every beam already holds EOS: nothing to do
+            return (ids, torch.zeros(B, W, device=a.device)) + (([],) if record else ())
+        self._prepare_inputs(st, images, B, W)
+        _set_seed(st.seed, seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+
+        def reset():
+            st.ids.zero_()
+            st.ids[:, :P] = prompt_rows
+            st.counters.copy_(st.counters_init)
+            st.hist.copy_(st.hist_init)
+            st.scores.zero_()
+            st.ctrl.zero_()
+            if spec.eos is None:
+                st.has_eos.zero_()
+            else:
+                st.has_eos.copy_((prompt_rows == spec.eos).any(dim=-1))
+        reset()
+        if use_graph and 'beam' not in st.graphs:
+            self._step(st, False)                             # warm up eagerly once (code objects load before capture)
+            self._beam_step(st)
+            st.graphs[None] = self._capture(st, False)
+            st.graphs['beam'] = _capture_launches(a.device, lambda: self._beam_step(st))
+            reset()
+        for _ in range(P - 1):                                # prompt tokens before the last: fill the cache only
+            st.graphs[None].launch() if use_graph else self._step(st, False)
+        draws = []
+        for _ in range(n_steps):
+            st.graphs['beam'].launch() if use_graph else self._beam_step(st)
+            if record:
+                draws.append((st.raw_tok.clone(), st.raw_pick.view(B, W).clone()))
+        L = int(st.counters[1].item())                        # the one host sync of the search
+        ids = st.ids[:, :L].reshape(B, W, L).clone()
+        scores = st.scores.view(B, W).clone()
+        return (ids, scores, draws[:L - P]) if record else (ids, scores)
+
+
+def _set_seed(buf: torch.Tensor, seed: int):
+    """the two 32-bit words of a 64-bit seed into an int32 device buffer"""
+    lo, hi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    buf.copy_(torch.tensor([lo - (1 << 32) if lo >= (1 << 31) else lo, hi - (1 << 32) if hi >= (1 << 31) else hi], dtype=torch.int32))
+
+
+def _capture_launches(device, fn):
+    """hipGraph of the launches ``fn`` issues, captured on a side stream."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    g = ops.Graph()
+    with torch.cuda.stream(side):
+        g.begin()
+        fn()
+        g.end()
+    torch.cuda.current_stream().wait_stream(side)
+    return g
 
 
 @torch.no_grad()

@@ -14,8 +14,15 @@ length boost added.  Consolidation (reference :95-148): of the W x E candidates 
 cumulative score (``consolidation_temperature <= 0``, sorted) or sampled from softmax(cumulative / temperature).
 The loop ends at ``max_new_tokens`` or when every beam contains an EOS anywhere -- with ``prompt = BOS = EOS`` that is
 true before the first step (reference behaviour), so pass ``eos_token_id=None`` or a distinct BOS.
+
+``kv_cache=True`` (``None``: the environment variable ``I2T_BEAM_KV_CACHE``, off by default) runs the same search on the static KV
+cache instead (``decoding.BeamDecoder``): B x W rows, one hipGraph replay per token, candidates and consolidation on the device,
+no host sync per token.  Draws without replacement are Gumbel-top-k over a counter-based uniform keyed by ``seed`` (``None``: drawn
+from torch's CPU generator once per call, so ``torch.manual_seed`` reproduces a run) -- the same distribution as the sequential
+draws of ``torch.multinomial``, not the same stream.  Non-causal decoders keep the path above; sparse nano-mini blocks raise.
 """
 import math
+import os
 from typing import Optional
 
 import torch
@@ -33,7 +40,9 @@ class BeamSearchTokenGenerator:
                  beam_expansion_factor: int = 4,
                  eos_token_id: Optional[int] = None,
                  consolidation_temperature: float = 1.0,
-                 length_boost: float = 1.0):
+                 length_boost: float = 1.0,
+                 kv_cache: Optional[bool] = None,
+                 seed: Optional[int] = None):
         self.model = model
         self.beam_width = beam_width
         self.beam_expansion_factor = beam_expansion_factor
@@ -44,10 +53,25 @@ class BeamSearchTokenGenerator:
         self.eos_token_id = eos_token_id
         self.length_boost = math.log(length_boost)
         self.processor = LogitsProcessorList([NoRepeatNGramLogitsProcessor(ngram_size=n) for n in no_repeat_n_grams])
+        self.no_repeat_n_grams = tuple(no_repeat_n_grams)
+        self.kv_cache = kv_cache
+        self.seed = seed
+        self._decoder = None
+
+    def uses_kv_cache(self) -> bool:
+        on = self.kv_cache if self.kv_cache is not None else os.environ.get('I2T_BEAM_KV_CACHE', '0') not in ('', '0')
+        return bool(on) and self.model._engine.dec.causal          # nothing to cache under bidirectional attention
+
+    def beam_spec(self):
+        from ..decoding import BeamSpec
+        return BeamSpec(self.beam_width, self.beam_expansion_factor, self.temperature, self.top_k, self.consolidation_temperature,
+                        self.eos_token_id, self.length_boost, self.no_repeat_n_grams)
 
     @torch.no_grad()
     def __call__(self, inputs, decoded_ids):
         self.model.eval()
+        if self.uses_kv_cache():
+            return self.search_cached(inputs, decoded_ids)[:2]
         W = self.beam_width
         mem = self.model.encoder(inputs)                                        # (B, n_cls, d), once
         B = mem.size(0)
@@ -59,6 +83,16 @@ class BeamSearchTokenGenerator:
             cand_ids, cand_lp = self.decode_next(mem, beams)                    # (B, W, E) each
             beams, scores = self.consolidate_candidates(beams, scores, cand_ids, cand_lp)
         return beams, scores
+
+    @torch.no_grad()
+    def search_cached(self, inputs, decoded_ids, use_graph: bool = True, record: bool = False):
+        """The KV-cache search (decoding.BeamDecoder.search): -> ids (B, W, L), scores (B, W) [, per-step raw draws if ``record``]."""
+        from ..decoding import BeamDecoder
+        self.model.eval()
+        if self._decoder is None:
+            self._decoder = BeamDecoder(self.model)
+        max_len = self.max_new_tokens + decoded_ids.size(-1) - 1
+        return self._decoder.search(inputs, decoded_ids, max_len, self.beam_spec(), seed=self.seed, use_graph=use_graph, record=record)
 
     def _all_ended(self, beams) -> bool:
         if self.eos_token_id is None:

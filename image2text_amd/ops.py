@@ -354,6 +354,56 @@ def gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out
     return out
 
 
+def beam_decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, o, o_rs, pos, n_keys_fixed, R, H, hist=None, rows_per_mem=1,
+                          append_dm=0, cache_hs=64):
+    """decode_attention with key t of row r read from cache row hist[r][t] (hist None: row r // rows_per_mem) -- include/i2t.h::
+    i2t_beam_decode_attention"""
+    _need_cuda(q, kcache, vcache, o, hist)
+    assert hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1)
+    _l.check(_lib().i2t_beam_decode_attention(_stream(), _p(q), q_rs, _p(kcache), _p(vcache), cache_bs, cache_rs, cache_hs, _p(o), o_rs,
+                                              _p(pos), n_keys_fixed, append_dm, _p(hist), 0 if hist is None else hist.stride(0),
+                                              rows_per_mem, R, H), 'i2t_beam_decode_attention')
+
+
+def beam_gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, R, H, Hkv, hd,
+                             hist=None, rows_per_mem=1):
+    """gq_decode_attention with the same history indirection (include/i2t.h::i2t_beam_gq_decode_attention)"""
+    _need_cuda(q, kcache, vcache, out, hist)
+    assert hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1)
+    kv_rs = k_new.stride(0) if k_new is not None else 0
+    _l.check(_lib().i2t_beam_gq_decode_attention(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
+                                                 cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, _p(hist),
+                                                 0 if hist is None else hist.stride(0), rows_per_mem, R, H, Hkv, hd),
+             'i2t_beam_gq_decode_attention')
+    return out
+
+
+def beam_candidates(logits, ids, len_ptr, ctrl, ngram_sizes, R, V, E, temperature, top_k, eos, log_boost, seed, cand_tok, cand_lp,
+                    raw_tok=None):
+    """E candidates per beam row after ban / crop / EOS rule (include/i2t.h::i2t_beam_candidates); top_k None/0 = no crop, eos None/-1
+    = no EOS rule"""
+    _need_cuda(logits, ids, len_ptr, ctrl, seed, cand_tok, cand_lp)
+    assert logits.dtype == F32 and cand_tok.dtype == torch.int32 and cand_lp.dtype == F32 and seed.dtype == torch.int32
+    _l.check(_lib().i2t_beam_candidates(_stream(), _p(logits), logits.stride(0), _p(ids), ids.stride(0), _p(len_ptr), _p(ctrl),
+                                        _p(ngram_sizes), 0 if ngram_sizes is None else ngram_sizes.numel(), R, V, E, float(temperature),
+                                        int(top_k or 0), -1 if eos is None else int(eos), float(log_boost), _p(seed), _p(cand_tok),
+                                        _p(cand_lp), _p(raw_tok)), 'i2t_beam_candidates')
+
+
+def beam_consolidate(cand_tok, cand_lp, scores, ids, hist, has_eos, parent, pos_ptr, len_ptr, ctrl, B, W, E, temperature, eos, seed,
+                     raw_pick=None):
+    """W survivors per caption, ids / history rows moved to the children (include/i2t.h::i2t_beam_consolidate)"""
+    _need_cuda(cand_tok, cand_lp, scores, ids, hist, has_eos, parent, ctrl, seed)
+    assert hist.dtype == torch.int32 and scores.dtype == F32 and ids.dtype == torch.long
+    _l.check(_lib().i2t_beam_consolidate(_stream(), _p(cand_tok), _p(cand_lp), _p(scores), _p(ids), ids.stride(0), _p(hist), hist.stride(0),
+                                         _p(has_eos), _p(parent), _p(pos_ptr), _p(len_ptr), _p(ctrl), B, W, E, float(temperature),
+                                         -1 if eos is None else int(eos), _p(seed), _p(raw_pick)), 'i2t_beam_consolidate')
+
+
+def beam_advance(counters, ctrl):
+    _l.check(_lib().i2t_beam_advance(_stream(), _p(counters), _p(ctrl)), 'i2t_beam_advance')
+
+
 def sparse_step_setup(pos_ptr, rank, member, lpos, lmem, L, tmax):
     _need_cuda(pos_ptr, rank, member, lpos, lmem)
     _l.check(_lib().i2t_sparse_step_setup(_stream(), _p(pos_ptr), _p(rank), _p(member), _p(lpos), _p(lmem), L, tmax), 'i2t_sparse_step_setup')

@@ -50,6 +50,21 @@ def sample_uniform(seed: int, step: int, row: int) -> float:
     return (h >> 8) / 16777216.0
 
 
+def beam_uniform(seed: int, step: int, row: int, index, salt: int = 0) -> torch.Tensor:
+    """Host replica of the beam kernels' uniforms (csrc/beam.hip::beam_uniform): u in (0, 1) on a grid of 2^-23 (float64, equal to the kernels' fp32 value), a pure function of
+    the 64-bit ``seed``, the position being written (``step`` = current length of the id rows), the ``row`` and ``index`` (an int or
+    a tensor of them).  salt 0: candidate draws (beam row, token id); salt 1: consolidation (caption, flat candidate w * E + e)."""
+    lo, hi = seed & M32, (seed >> 32) & M32
+    h2 = lowbias32((lowbias32(lo ^ ((row * 0x9E3779B9) & M32)) + hi + step * 0x85EBCA6B + salt * 0x27D4EB2F) & M32)
+    x = (torch.as_tensor(index, dtype=torch.int64) * 0x165667B1 + h2) & M32
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & M32
+    x ^= x >> 16
+    return ((x >> 9).to(torch.float64) + 0.5) / 8388608.0
+
+
 def mlm_draws(seed: int, n: int):
     """Host replica of the three per-token draws of csrc/elementwise.hip::lm_inputs_kernel for elements 0 .. n-1 of the label
     tensor: (u_mask float32 in [0, 1), u_rand float32 in [0, 1), random id numerator uint32 -- id = (numerator * vocab) >> 32)."""

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 2
+#define I2T_ABI_VERSION 3
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -452,6 +452,40 @@ int i2t_moe_unpack_dw2(void* stream, const float* dW, float* gw, float* gb, int 
 int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
                             void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
                             int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd);
+/* Beam-search step over the static KV cache (reference models/generation_utils.py:10-148, BeamSearchTokenGenerator; csrc/beam.hip).
+ * R = B * W rows, batch-major (row r = b * W + w).  *len_ptr, *pos_ptr and ctrl = [done, unfinished] (int32) live in device memory,
+ * so one captured hipGraph replays the step per token; once ctrl[0] is set, candidates / consolidate / advance do nothing.
+ *   beam_candidates: logits f32 [R][ld] (ld % 4 == 0, 16-byte aligned) of the last position -> no-repeat-n-gram ban over
+ *     ids[r][0 .. len) (prompt included) -> top-k crop (top_k <= 0: none; ties at the k-th value stay) -> E candidates: temperature
+ *     <= 0 the E largest scores (descending, lower id first on ties) with log_softmax(scores); else E draws without replacement from
+ *     softmax(scores / T) (Gumbel-top-E over uniform(seed, len, r, token, 0): image2text_amd/rng.py::beam_uniform) with
+ *     log_softmax(scores / T).  EOS rule (eos >= 0 only): a row whose last token is eos re-emits eos at 0 where lp + log_boost < 0,
+ *     every other candidate gets + log_boost.  Writes cand_tok int [R][E], cand_lp f32 [R][E]; raw_tok (optional, [R][E]): the
+ *     draws before the EOS rule.  E <= 16.
+ *   beam_consolidate: per caption the W survivors of the W * E totals scores[r] + cand_lp (temperature <= 0: the top W, descending,
+ *     lower flat index w * E + e first on ties; else W draws without replacement from softmax(total / T) over uniform(seed, len, b,
+ *     flat, 1)).  Child b * W + k gets the parent's ids [0 .. len) and history [0 .. pos), ids[child][len] = token, hist[child][pos] =
+ *     parent, the new score, parent[child] and has_eos[child] (int [R]: the row holds eos anywhere); ctrl[1] counts the captions
+ *     with a beam that has no eos (every caption when eos < 0).  raw_pick (optional, int [R]): the flat index each child was made
+ *     from.  W <= 16, W * E <= 1024.
+ *   beam_advance: while ctrl[0] is clear: pos += 1, len += 1, and ctrl[0] = (ctrl[1] == 0); then ctrl[1] = 0.
+ *   beam_decode_attention / beam_gq_decode_attention: i2t_decode_attention / i2t_gq_decode_attention with key t of row r read from
+ *     cache row hist[r][t] (int32 [R][hist_ld]; the new token's key / value are written to the row's own slot *pos); hist NULL: row
+ *     r / rows_per_mem for every key (cross-attention over a memory stored once per image).  Same loads and reduction order: with
+ *     an identity table the outputs are bit-equal to the plain kernels'. */
+int i2t_beam_candidates(void* stream, const float* logits, int ld, const int64_t* ids, int ids_ld, const int* len_ptr, const int* ctrl,
+                        const int* ngram_sizes, int n_sizes, int R, int V, int E, float temperature, int top_k, int eos, float log_boost,
+                        const unsigned* seed, int* cand_tok, float* cand_lp, int* raw_tok);
+int i2t_beam_consolidate(void* stream, const int* cand_tok, const float* cand_lp, float* scores, int64_t* ids, int ids_ld, int* hist,
+                         int hist_ld, int* has_eos, int* parent, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int E,
+                         float temperature, int eos, const unsigned* seed, int* raw_pick);
+int i2t_beam_advance(void* stream, int* counters, int* ctrl);
+int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, void* kcache, void* vcache, long cache_bs, int cache_rs,
+                              long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed, int append_dm, const int* hist,
+                              int hist_ld, int rows_per_mem, int R, int H);
+int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
+                                 void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr, int n_keys_fixed,
+                                 int max_keys, const int* hist, int hist_ld, int rows_per_mem, int R, int H, int Hkv, int hd);
 /* Sparse blocks in the decode step: a layer's cache holds only its kept positions, so the token at text position *pos_ptr uses
  * slot rank[l][pos] (= kept positions before it) and runs the block only when member[l][pos]; both tables int [L][tmax] on the
  * device.  setup writes lpos[l] / lmem[l] for the current position; i2t_select_rows picks the block's or the null connector's
