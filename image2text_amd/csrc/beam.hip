@@ -4,7 +4,9 @@
 //   decoder blocks (beam attention below) -> lm_head (fp32 logits) -> i2t_beam_candidates -> i2t_beam_consolidate -> i2t_beam_advance.
 // Survivors never copy K/V: a history table hist[R][T] (int32) names the physical cache row that holds key t of beam r.  The step
 // writes its new K/V at physical (r, pos); consolidation sets hist[child][t] = hist[parent][t] for t < pos and hist[child][pos] =
-// parent.  Each position of each physical row is written once, so no entry a live beam points at is ever overwritten.
+// parent.  Each position of each physical row is written once, so no entry a live beam points at is ever overwritten.  A sparse
+// layer caches its kept positions only (slot = rank among them): key s of beam r is at (hist[r][slot_pos[s]], s), and a slot
+// written again before a kept token lands there is named by no history.
 #include "common.h"
 
 namespace {
@@ -395,7 +397,9 @@ __global__ __launch_bounds__(64 * WPB) void beam_decode_attention_kernel(const b
     }
 }
 
-// family.hip::gq_decode_attention_kernel with the same history indirection (row-major cache [R][T][Hkv hd])
+// family.hip::gq_decode_attention_kernel with the same history indirection (row-major cache [R][T][Hkv hd]).  slot_pos (sparse
+// layers, nullable): slot s holds the layer's s-th kept text position, so key s of row r is read from row hist[r][slot_pos[s]]; the
+// table row is the only thing it changes, null keeps the kernel as it was.
 constexpr int GDEC_MAX_KEYS = 1024;
 template <int HD>
 __global__ __launch_bounds__(64) void beam_gq_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
@@ -403,7 +407,7 @@ __global__ __launch_bounds__(64) void beam_gq_decode_attention_kernel(const bf16
                                                                       bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
                                                                       bf16_t* __restrict__ o, int o_rs, const int* __restrict__ pos_ptr,
                                                                       int n_keys_fixed, int G, float scale, const int* __restrict__ hist,
-                                                                      int hist_ld, int rows_per_mem) {
+                                                                      int hist_ld, const int* __restrict__ slot_pos, int rows_per_mem) {
     constexpr int LPK = HD / 8, KPP = 64 / LPK;
     __shared__ float qs[HD], kn[HD], vn[HD];
     __shared__ float ps[GDEC_MAX_KEYS];
@@ -414,7 +418,8 @@ __global__ __launch_bounds__(64) void beam_gq_decode_attention_kernel(const bf16
     const int n_cached = append ? n - 1 : n;
     bf16_t* kh = kc + hk * HD;
     bf16_t* vh = vc + hk * HD;
-    for (int t = lane; t < n_cached; t += 64) hs[t] = hist ? hist[(size_t)b * hist_ld + t] : b / rows_per_mem;
+    for (int t = lane; t < n_cached; t += 64)
+        hs[t] = hist ? hist[(size_t)b * hist_ld + (slot_pos ? slot_pos[t] : t)] : b / rows_per_mem;
     for (int i = lane; i < HD; i += 64) {
         qs[i] = bf16_to_f32(q[(size_t)b * q_rs + h * HD + i]);
         if (append) {
@@ -560,7 +565,7 @@ extern "C" int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, 
 extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
                                             void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
                                             const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld,
-                                            int rows_per_mem, int R, int H, int Hkv, int hd) {
+                                            const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
     I2T_REQUIRE(q && kcache && vcache && out && R > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && rows_per_mem >= 1,
                 "i2t_beam_gq_decode_attention: bad args");
     I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "i2t_beam_gq_decode_attention: head_dim %d (16, 32, 64 or 128)", hd);
@@ -568,6 +573,7 @@ extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_r
     I2T_REQUIRE(max_keys > 0 && max_keys <= GDEC_MAX_KEYS && n_keys_fixed <= max_keys, "i2t_beam_gq_decode_attention: at most %d keys",
                 GDEC_MAX_KEYS);
     I2T_REQUIRE(!hist || hist_ld >= max_keys, "i2t_beam_gq_decode_attention: history rows shorter than max_keys");
+    I2T_REQUIRE(!slot_pos || hist, "i2t_beam_gq_decode_attention: slot_pos needs a history table");
     I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
                 "i2t_beam_gq_decode_attention: cache / output rows must be 16-byte aligned");
     const float scale = 1.0f / sqrtf((float)hd);
@@ -576,7 +582,7 @@ extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_r
 #define BGDEC_LAUNCH(HD)                                                                                                             \
     hipLaunchKernelGGL(beam_gq_decode_attention_kernel<HD>, grid, dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,        \
                        (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr, \
-                       n_keys_fixed, H / Hkv, scale, hist, hist_ld, rows_per_mem)
+                       n_keys_fixed, H / Hkv, scale, hist, hist_ld, slot_pos, rows_per_mem)
     if (hd == 16) BGDEC_LAUNCH(16);
     else if (hd == 32) BGDEC_LAUNCH(32);
     else if (hd == 64) BGDEC_LAUNCH(64);

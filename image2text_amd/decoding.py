@@ -23,6 +23,7 @@ import os
 from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -57,6 +58,18 @@ def text_window(block: int, off: int, prefix: int) -> int:
         raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
                          f'no room for text (block {block}, soft-prompt offset {off})')
     return tmax
+
+
+def slot_positions(member: np.ndarray) -> np.ndarray:
+    """int32 [L][slots] from a sparse decoder's membership table (int [L][tmax], 1 where layer l keeps text position p): row l lists
+    the text positions layer l keeps, in order, zero-padded -- the position whose K/V sit at each cache slot (slot = rank of the
+    position among the kept ones); slots = the largest count, at least 1."""
+    member = np.asarray(member) != 0
+    kpos = np.zeros((member.shape[0], max(int(member.sum(axis=1).max(initial=0)), 1)), dtype=np.int32)
+    for l, row in enumerate(member):
+        kept = np.flatnonzero(row)
+        kpos[l, :kept.size] = kept
+    return kpos
 
 
 class GreedyDecoder:
@@ -125,7 +138,6 @@ class GreedyDecoder:
         """Buffers of the nano-mini family's decode step (engine_family.py): a K/V cache of Hkv heads per layer that, in a sparse
         layer, holds the kept positions only (slot = number of kept positions before the token), the per-layer slot / membership
         tables, and the MoE routing workspaces."""
-        import numpy as np
         eng, dc = self.eng, self.eng.dec
         sp, dev = dc.fam, st.arena.device
         B, d, hd, tmax, off = st.B, dc.d, sp.hd, st.tmax, st.off
@@ -146,8 +158,12 @@ class GreedyDecoder:
                 text[idx[idx < off + tmax]] = 1
                 member[l] = text[off:]
                 rank[l] = np.cumsum(member[l]) - member[l]
-            st.slots = max(int(member.sum(axis=1).max()), 1)
+            kpos = slot_positions(member)
+            st.slots = kpos.shape[1]
+            # beam search reads key s of a sparse layer from row hist[r][kpos[l][s]] (i2t_beam_gq_decode_attention's slot_pos)
+            assert int(kpos.max()) < st.clen, 'a kept position lies beyond the beam history table'
             st.rank, st.member = torch.from_numpy(rank).to(dev), torch.from_numpy(member).to(dev)
+            st.kpos = torch.from_numpy(kpos).to(dev)
             st.lpos = torch.zeros(dc.L, dtype=torch.int32, device=dev)
             st.lmem = torch.zeros(dc.L, dtype=torch.int32, device=dev)
             st.xb, st.xn, st.xnb = e(B, d, dtype=F32), e(B, d, dtype=F32), e(B, d)
@@ -196,7 +212,7 @@ class GreedyDecoder:
                 ops.gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd)
             else:
                 ops.beam_gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd,
-                                             hist=st.hist)
+                                             hist=st.hist, slot_pos=st.kpos[l] if st.sparse else None)
             ops.gemm(st.ao, a.W(f'{p}.{out_name}.weight'), xo, B, d, d, bias=a.P(f'{p}.{out_name}.bias'), residual=st.x, workspace=st.ws)
             if l in st.cross_kv:
                 kv, S = st.cross_kv[l]
@@ -520,7 +536,8 @@ class BeamDecoder(GreedyDecoder):
     sequence, one captured hipGraph replay per token.  The step's head is the fp32 lm_head, then on the device (csrc/beam.hip):
     i2t_beam_candidates (ban, crop, E candidates, EOS rule) -> i2t_beam_consolidate (W survivors per caption, ids and history rows
     moved to the children) -> i2t_beam_advance.  Survivors copy no K/V: the history table st.hist[r][t] names the cache row that
-    holds key t of beam r, and the attention kernels read through it.  The encoder and the cross K/V run once per image
+    holds key t of beam r, and the attention kernels read through it (a sparse layer's slot s through hist[r][st.kpos[l][s]], the
+    text position the slot holds).  The encoder and the cross K/V run once per image
     (rows_per_mem = W); the prompt is prefilled for all R rows under the identity table.  Once every beam of every caption holds
     EOS the remaining replays do nothing, so the host launches them all and reads the final length once."""
 
@@ -566,9 +583,6 @@ class BeamDecoder(GreedyDecoder):
         dc = eng.dec
         if not dc.causal:
             raise ValueError('BeamDecoder needs a causal decoder')
-        if dc.fam is not None and dc.fam.sparse:
-            raise NotImplementedError('beam search on the KV cache does not cover sparse decoder blocks: a sparse layer caches its kept '
-                                      'positions only, at slots that the per-beam history table does not address')
         W, E = spec.beam_width, spec.expansion
         if spec.temperature > 0 and spec.top_k is not None and 0 < spec.top_k < E:
             raise ValueError(f'top_k = {spec.top_k} leaves fewer than beam_expansion_factor = {E} tokens to draw without replacement')

@@ -82,7 +82,7 @@ SIGNATURES = {
     'i2t_beam_consolidate': [P, P, P, P, P, I, P, I, P, P, P, P, P, I, I, I, F, I, P, P],
     'i2t_beam_advance': [P, P, P],
     'i2t_beam_decode_attention': [P, P, I, P, P, L, I, L, P, I, P, I, I, P, I, I, I, I],
-    'i2t_beam_gq_decode_attention': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, P, I, I, I, I, I, I],
+    'i2t_beam_gq_decode_attention': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, P, I, P, I, I, I, I, I],
     'i2t_sparse_step_setup': [P, P, P, P, P, P, I, I],
     'i2t_select_rows': [P, P, P, P, P, L],
     'i2t_grouped_gemm': [P, I, P, I, P, I, L, P, I, L, I, P, L, I, P, P, I, P, I, I, P, I, I, P, I, I, I],
@@ -128,7 +128,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 _lib = None
 
 

@@ -19,7 +19,9 @@ true before the first step (reference behaviour), so pass ``eos
 cache instead (``decoding.BeamDecoder``): B x W rows, one hipGraph replay per token, candidates and consolidation on the device,
 no host sync per token.  Draws without replacement are Gumbel-top-k over a counter-based uniform keyed by ``seed`` (``None``: drawn
 from torch's CPU generator once per call, so ``torch.manual_seed`` reproduces a run) -- the same distribution as the sequential
-draws of ``torch.multinomial``, not the same stream.  Non-causal decoders keep the path above; sparse nano-mini blocks raise.
+draws of ``torch.multinomial``, not the same stream.  Non-causal decoders keep the path above.  Sparse nano-mini decoder blocks
+run on the cache too: a sparse layer caches its kept positions only, and reads slot s through the history entry of the text
+position that slot holds.
 """
 import math
 import os

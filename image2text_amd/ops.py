@@ -366,14 +366,17 @@ def beam_decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, o, o_rs, 
 
 
 def beam_gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, R, H, Hkv, hd,
-                             hist=None, rows_per_mem=1):
-    """gq_decode_attention with the same history indirection (include/i2t.h::i2t_beam_gq_decode_attention)"""
-    _need_cuda(q, kcache, vcache, out, hist)
+                             hist=None, rows_per_mem=1, slot_pos=None):
+    """gq_decode_attention with the same history indirection (include/i2t.h::i2t_beam_gq_decode_attention); slot_pos (int32
+    [max_keys], sparse layers): key s of row r is read from cache row hist[r][slot_pos[s]]"""
+    _need_cuda(q, kcache, vcache, out, hist, slot_pos)
     assert hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1)
+    assert slot_pos is None or (hist is not None and slot_pos.dtype == torch.int32 and slot_pos.is_contiguous()
+                                and slot_pos.numel() >= max_keys)
     kv_rs = k_new.stride(0) if k_new is not None else 0
     _l.check(_lib().i2t_beam_gq_decode_attention(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
                                                  cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, _p(hist),
-                                                 0 if hist is None else hist.stride(0), rows_per_mem, R, H, Hkv, hd),
+                                                 0 if hist is None else hist.stride(0), _p(slot_pos), rows_per_mem, R, H, Hkv, hd),
              'i2t_beam_gq_decode_attention')
     return out
 

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 3
+#define I2T_ABI_VERSION 4
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -472,7 +472,9 @@ int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k
  *   beam_decode_attention / beam_gq_decode_attention: i2t_decode_attention / i2t_gq_decode_attention with key t of row r read from
  *     cache row hist[r][t] (int32 [R][hist_ld]; the new token's key / value are written to the row's own slot *pos); hist NULL: row
  *     r / rows_per_mem for every key (cross-attention over a memory stored once per image).  Same loads and reduction order: with
- *     an identity table the outputs are bit-equal to the plain kernels'. */
+ *     an identity table the outputs are bit-equal to the plain kernels'.  beam_gq_decode_attention's slot_pos (int32 [max_keys],
+ *     NULL: slot = position; needs hist): the cache of a sparse layer holds its kept positions only, slot s the text position
+ *     slot_pos[s], so key s of row r is read from row hist[r][slot_pos[s]]; every entry must be below hist_ld. */
 int i2t_beam_candidates(void* stream, const float* logits, int ld, const int64_t* ids, int ids_ld, const int* len_ptr, const int* ctrl,
                         const int* ngram_sizes, int n_sizes, int R, int V, int E, float temperature, int top_k, int eos, float log_boost,
                         const unsigned* seed, int* cand_tok, float* cand_lp, int* raw_tok);
@@ -485,7 +487,8 @@ int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, void* kcach
                               int hist_ld, int rows_per_mem, int R, int H);
 int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
                                  void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr, int n_keys_fixed,
-                                 int max_keys, const int* hist, int hist_ld, int rows_per_mem, int R, int H, int Hkv, int hd);
+                                 int max_keys, const int* hist, int hist_ld, const int* slot_pos, int rows_per_mem, int R, int H,
+                                 int Hkv, int hd);
 /* Sparse blocks in the decode step: a layer's cache holds only its kept positions, so the token at text position *pos_ptr uses
  * slot rank[l][pos] (= kept positions before it) and runs the block only when member[l][pos]; both tables int [L][tmax] on the
  * device.  setup writes lpos[l] / lmem[l] for the current position; i2t_select_rows picks the block's or the null connector's
