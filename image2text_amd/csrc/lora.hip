@@ -60,11 +60,13 @@ __global__ __launch_bounds__(256) void lora_stage_kernel(const bf16_t* __restric
             bool k0[4], k1[4];
             dropout_keep4(key, (unsigned)(i * 8), thr, k0);
             dropout_keep4(key, (unsigned)(i * 8 + 4), thr, k1);
+            // (x * 0 for a dropped element, as i2t_dropout_apply writes it: the two forms of the masked copy are bit-equal, sign of zero included)
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { f[e] = k0[e] ? scale : 0.f; f[4 + e] = k1[e] ? scale : 0.f; }
             u32x4 o;
-            o[0] = pack_bf16x2(k0[0] ? bf16lo(v[0]) * scale : 0.f, k0[1] ? bf16hi(v[0]) * scale : 0.f);
-            o[1] = pack_bf16x2(k0[2] ? bf16lo(v[1]) * scale : 0.f, k0[3] ? bf16hi(v[1]) * scale : 0.f);
-            o[2] = pack_bf16x2(k1[0] ? bf16lo(v[2]) * scale : 0.f, k1[1] ? bf16hi(v[2]) * scale : 0.f);
-            o[3] = pack_bf16x2(k1[2] ? bf16lo(v[3]) * scale : 0.f, k1[3] ? bf16hi(v[3]) * scale : 0.f);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(bf16lo(v[e]) * f[2 * e], bf16hi(v[e]) * f[2 * e + 1]);
             *reinterpret_cast<u32x4*>(xd + i * 8) = o;
         }
     }
