@@ -127,7 +127,7 @@ class VisionTransformerEncoderConfig(EncoderConfig):
 
 class PretrainedViTConfig(EncoderConfig):
     """torchvision ViT-B/16 backbone + heads (reference configs/models.py:91-96): ``models/encoder.py::PretrainedViT`` on
-    ``engine_vit.ViTEncoder`` (slot-MLP / PEER / LSH heads; learnable LSH projections are refused)."""
+    ``engine_vit.ViTEncoder`` (slot-MLP / PEER / LSH heads, the LSH head with fixed or learnable projections)."""
     refine_base_model: bool = True
     n_embd_out_vit: int
     peer_config: Optional[PeerConfig] = None

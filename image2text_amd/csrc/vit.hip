@@ -380,6 +380,164 @@ __global__ __launch_bounds__(256) void lsh_embed_bwd_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ learnable LSH
+// L2 rows of matrices that sit apart in the parameter arena (the CosineLinear weights of every (slot, resolution)): row r of group
+// g is x + goff[g] + r d; the normalised rows come out contiguous, [(g, r)][d].  Same arithmetic as l2norm_fwd / _bwd above.
+__global__ __launch_bounds__(256) void l2norm_groups_fwd_kernel(const float* __restrict__ x, const long* __restrict__ goff, float* __restrict__ y,
+                                                                float* __restrict__ inv, int M, int rows, int d) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float* xr = x + goff[row / rows] + (size_t)(row % rows) * d;
+    float s = 0.f;
+    for (int c = lane * 4; c < d; c += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c);
+        s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+    }
+    s = wave_sum(s);
+    const float r = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+    if (lane == 0) inv[row] = r;
+    for (int c = lane * 4; c < d; c += 256) *reinterpret_cast<f32x4*>(y + (size_t)row * d + c) = *reinterpret_cast<const f32x4*>(xr + c) * r;
+}
+
+__global__ __launch_bounds__(256) void l2norm_groups_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const long* __restrict__ goff,
+                                                                const float* __restrict__ inv, float* __restrict__ dx, int accumulate, int M,
+                                                                int rows, int d) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const size_t o = (size_t)goff[row / rows] + (size_t)(row % rows) * d;
+    const float* xr = x + o;
+    const float* gr = dy + (size_t)row * d;
+    const float r = inv[row];
+    float s = 0.f;
+    for (int c = lane * 4; c < d; c += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c), g = *reinterpret_cast<const f32x4*>(gr + c);
+        s += v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3];
+    }
+    s = wave_sum(s) * r * r;
+    if (r >= 1e12f) s = 0.f;
+    for (int c = lane * 4; c < d; c += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xr + c), g = *reinterpret_cast<const f32x4*>(gr + c);
+        f32x4 w = (g - v * s) * r;
+        float* dst = dx + o + c;
+        if (accumulate) w += *reinterpret_cast<const f32x4*>(dst);
+        *reinterpret_cast<f32x4*>(dst) = w;
+    }
+}
+
+// LearnableCosineVectorEmbedding.gaussian_kernel (models/layers.py:183-191, top_k None) for every (image b, slot s, resolution k,
+// projection j): a_i = exp(-(c - mean_i)^2 / (2 sigma2_k)), sigma2_k = (2 / nb_k)^2, z = a / max(||a||_2, 1e-12).  c fp32
+// [B][n_cls nK n_proj]; mean of (s, k) = par + s slot_stride + moff[k], fp32 [n_proj][nb_k]; z leaves as the bf16 A operand of the
+// slot-grouped GEMM: row s B + b, column koff[k] + j nb_k + i (koff[nK] = Ktot).  All arithmetic fp32; any nb_k >= 1.
+constexpr int SOFT_MAXU = 1024;                                  // nK * n_proj units of one row held in LDS
+__device__ __forceinline__ float soft_scale(int nb) {            // -log2(e) / (2 sigma2)
+    const float res = 2.0f / (float)nb;
+    return -0.5f * 1.4426950408889634f / (res * res);
+}
+// column of a slot's K axis -> (k, j, i)
+__device__ __forceinline__ void soft_locate(int col, const int* __restrict__ koff, const int* __restrict__ nbins, int nK, int& k, int& j, int& i, int& nb) {
+    k = 0;
+    while (k + 1 < nK && col >= koff[k + 1]) ++k;
+    nb = nbins[k];
+    const int q = col - koff[k];
+    j = q / nb;
+    i = q - j * nb;
+}
+
+// one workgroup per slot-major row (s, b)
+__global__ __launch_bounds__(256) void lsh_soft_fwd_kernel(const float* __restrict__ c, const float* __restrict__ par, long slot_stride,
+                                                           const long* __restrict__ moff, const int* __restrict__ nbins, const int* __restrict__ koff,
+                                                           bf16_t* __restrict__ z, float* __restrict__ inv, int B, int n_cls, int nK, int n_proj,
+                                                           int Ktot) {
+    __shared__ float cs[SOFT_MAXU], rs[SOFT_MAXU];
+    const int s = blockIdx.x / B, b = blockIdx.x % B, tid = threadIdx.x, nU = nK * n_proj;
+    const size_t crow = ((size_t)b * n_cls + s) * nU;
+    const float* ps = par + (size_t)s * slot_stride;
+    for (int u = tid; u < nU; u += 256) {                        // the norm of every (k, j) unit
+        const int k = u / n_proj, j = u - k * n_proj, nb = nbins[k];
+        const float cv = c[crow + u], sc = soft_scale(nb);
+        const float* mu = ps + moff[k] + (size_t)j * nb;
+        float ss = 0.f;
+        for (int i = 0; i < nb; ++i) {
+            const float dlt = cv - mu[i], a = __builtin_amdgcn_exp2f(sc * dlt * dlt);
+            ss += a * a;
+        }
+        const float r = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+        cs[u] = cv;
+        rs[u] = r;
+        inv[crow + u] = r;
+    }
+    __syncthreads();
+    bf16_t* zr = z + (size_t)blockIdx.x * Ktot;
+    for (int col = tid * 2; col < Ktot; col += 512) {            // two columns per thread: 4-byte stores, consecutive across the wave
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            int k, j, i, nb;
+            soft_locate(col + e, koff, nbins, nK, k, j, i, nb);
+            const int u = k * n_proj + j;
+            const float dlt = cs[u] - ps[moff[k] + (size_t)j * nb + i];
+            v[e] = __builtin_amdgcn_exp2f(soft_scale(nb) * dlt * dlt) * rs[u];
+        }
+        *reinterpret_cast<unsigned*>(zr + col) = pack_bf16x2(v[0], v[1]);
+    }
+}
+
+// Backward, first half: per unit t = <dz, z> and dc = sum_i dd_i with da_i = inv (dz_i - z_i t), dd_i = da_i a_i (mean_i - c) / sigma2
+// (d a_i / d c; d a_i / d mean_i = -that).  dz fp32 [n_cls B][Ktot] slot-major; dc, t fp32 [B][n_cls nK n_proj].
+__global__ __launch_bounds__(256) void lsh_soft_bwd_dc_kernel(const float* __restrict__ dz, const float* __restrict__ c, const float* __restrict__ inv,
+                                                              const float* __restrict__ par, long slot_stride, const long* __restrict__ moff,
+                                                              const int* __restrict__ nbins, const int* __restrict__ koff, float* __restrict__ dc,
+                                                              float* __restrict__ tws, int B, int n_cls, int nK, int n_proj, int Ktot) {
+    const int s = blockIdx.x / B, b = blockIdx.x % B, nU = nK * n_proj;
+    const size_t crow = ((size_t)b * n_cls + s) * nU;
+    const float* ps = par + (size_t)s * slot_stride;
+    const float* gr = dz + (size_t)blockIdx.x * Ktot;
+    for (int u = threadIdx.x; u < nU; u += 256) {
+        const int k = u / n_proj, j = u - k * n_proj, nb = nbins[k];
+        const float cv = c[crow + u], r = inv[crow + u], sc = soft_scale(nb);
+        const float* mu = ps + moff[k] + (size_t)j * nb;
+        const float* g = gr + koff[k] + (size_t)j * nb;
+        float t = 0.f;
+        for (int i = 0; i < nb; ++i) {
+            const float dlt = cv - mu[i];
+            t += g[i] * (__builtin_amdgcn_exp2f(sc * dlt * dlt) * r);
+        }
+        if (r >= 1e12f) t = 0.f;                                 // the 1e-12 floor was active: the divisor is a constant there
+        const float sl = 2.0f * sc * 0.6931471805599453f;        // -1 / sigma2
+        float acc = 0.f;
+        for (int i = 0; i < nb; ++i) {
+            const float dlt = cv - mu[i], a = __builtin_amdgcn_exp2f(sc * dlt * dlt);
+            acc += r * (g[i] - a * r * t) * a * (sl * dlt);
+        }
+        dc[crow + u] = acc;
+        tws[crow + u] = t;
+    }
+}
+
+// Backward, second half: dmean[s][k][j][i] (+)= -sum_b dd_i.  One thread per mean element of slot blockIdx.y, the batch cut into
+// gridDim.z chunks that meet in fp32 atomics; deterministic mode launches ONE chunk, so that every element is a fixed-order sum.
+__global__ __launch_bounds__(256) void lsh_soft_bwd_mean_kernel(const float* __restrict__ dz, const float* __restrict__ c, const float* __restrict__ inv,
+                                                                const float* __restrict__ tws, const float* __restrict__ par, float* __restrict__ gpar,
+                                                                long slot_stride, const long* __restrict__ moff, const int* __restrict__ nbins,
+                                                                const int* __restrict__ koff, int B, int n_cls, int nK, int n_proj, int Ktot, int chunk) {
+    const int col = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (col >= Ktot) return;
+    int k, j, i, nb;
+    soft_locate(col, koff, nbins, nK, k, j, i, nb);
+    const size_t po = (size_t)s * slot_stride + moff[k] + (size_t)j * nb + i;
+    const float mu = par[po], sc = soft_scale(nb), sl = 2.0f * sc * 0.6931471805599453f;
+    const int u = (s * nK + k) * n_proj + j, nU = n_cls * nK * n_proj;
+    const int b0 = blockIdx.z * chunk, b1 = min(B, b0 + chunk);
+    float acc = 0.f;
+    for (int b = b0; b < b1; ++b) {
+        const float cv = c[(size_t)b * nU + u], r = inv[(size_t)b * nU + u], t = tws[(size_t)b * nU + u];
+        const float dlt = cv - mu, a = __builtin_amdgcn_exp2f(sc * dlt * dlt);
+        acc -= r * (dz[((size_t)s * B + b) * Ktot + col] - a * r * t) * a * (sl * dlt);
+    }
+    if (gridDim.z == 1) gpar[po] += acc;
+    else atomicAdd(gpar + po, acc);
+}
+
 inline unsigned grid_for(long n) {
     const long blocks = (n + 255) / 256;
     return (unsigned)(blocks < 65536 ? blocks : 65536);
@@ -480,5 +638,54 @@ extern "C" int i2t_lsh_embed_bwd(void* stream, const float* dy, const int* rows,
     hipLaunchKernelGGL(lsh_embed_bwd_kernel, dim3(i2t_det() ? 1 : B * n_cls), dim3(256), 0, (hipStream_t)stream, dy, rows, g_tables, slot_stride,
                        tab_off, n_cls, nK, n_proj, dout, B * n_cls);
     I2T_CHECK_LAUNCH("i2t_lsh_embed_bwd");
+    return I2T_OK;
+}
+
+extern "C" int i2t_l2norm_groups_fwd(void* stream, const float* x, const long* group_off, float* y, float* inv_norm, int G, int rows, int d) {
+    I2T_REQUIRE(x && group_off && y && inv_norm && G > 0 && rows > 0 && d > 0 && d % 4 == 0 && ALIGNED16(x) && ALIGNED16(y),
+                "i2t_l2norm_groups_fwd: bad args (d=%d must be a multiple of 4)", d);
+    const int M = G * rows;
+    hipLaunchKernelGGL(l2norm_groups_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, group_off, y, inv_norm, M, rows, d);
+    I2T_CHECK_LAUNCH("i2t_l2norm_groups_fwd");
+    return I2T_OK;
+}
+
+extern "C" int i2t_l2norm_groups_bwd(void* stream, const float* dy, const float* x, const long* group_off, const float* inv_norm, float* dx,
+                                     int accumulate, int G, int rows, int d) {
+    I2T_REQUIRE(dy && x && group_off && inv_norm && dx && G > 0 && rows > 0 && d > 0 && d % 4 == 0 && ALIGNED16(dy) && ALIGNED16(x) && ALIGNED16(dx),
+                "i2t_l2norm_groups_bwd: bad args (d=%d must be a multiple of 4)", d);
+    const int M = G * rows;
+    hipLaunchKernelGGL(l2norm_groups_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, group_off, inv_norm, dx, accumulate, M,
+                       rows, d);
+    I2T_CHECK_LAUNCH("i2t_l2norm_groups_bwd");
+    return I2T_OK;
+}
+
+extern "C" int i2t_lsh_soft_fwd(void* stream, const float* c, const float* params, long slot_stride, const long* mean_off, const int* nbins,
+                                const int* col_off, void* z_bf16, float* inv_norm, int B, int n_cls, int nK, int n_proj, int Ktot) {
+    I2T_REQUIRE(c && params && mean_off && nbins && col_off && z_bf16 && inv_norm && B > 0 && n_cls > 0 && nK > 0 && n_proj > 0 &&
+                    nK * n_proj <= SOFT_MAXU && Ktot > 0 && Ktot % 2 == 0 && ALIGNED16(z_bf16),
+                "i2t_lsh_soft_fwd: bad args (nK * n_proj = %d <= %d, Ktot=%d even)", nK * n_proj, SOFT_MAXU, Ktot);
+    hipLaunchKernelGGL(lsh_soft_fwd_kernel, dim3(B * n_cls), dim3(256), 0, (hipStream_t)stream, c, params, slot_stride, mean_off, nbins, col_off,
+                       (bf16_t*)z_bf16, inv_norm, B, n_cls, nK, n_proj, Ktot);
+    I2T_CHECK_LAUNCH("i2t_lsh_soft_fwd");
+    return I2T_OK;
+}
+
+extern "C" int i2t_lsh_soft_bwd(void* stream, const float* dz, const float* c, const float* inv_norm, const float* params, float* g_params,
+                                long slot_stride, const long* mean_off, const int* nbins, const int* col_off, float* dc, float* t_ws, int B,
+                                int n_cls, int nK, int n_proj, int Ktot) {
+    I2T_REQUIRE(dz && c && inv_norm && params && mean_off && nbins && col_off && dc && t_ws && B > 0 && n_cls > 0 && nK > 0 && n_proj > 0 && Ktot > 0,
+                "i2t_lsh_soft_bwd: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(lsh_soft_bwd_dc_kernel, dim3(B * n_cls), dim3(256), 0, s, dz, c, inv_norm, params, slot_stride, mean_off, nbins, col_off, dc,
+                       t_ws, B, n_cls, nK, n_proj, Ktot);
+    I2T_CHECK_LAUNCH("i2t_lsh_soft_bwd");
+    if (g_params) {                                              // null = the means are frozen
+        const int chunk = i2t_det() ? B : 32;
+        hipLaunchKernelGGL(lsh_soft_bwd_mean_kernel, dim3((Ktot + 255) / 256, n_cls, (B + chunk - 1) / chunk), dim3(256), 0, s, dz, c, inv_norm, t_ws,
+                           params, g_params, slot_stride, mean_off, nbins, col_off, B, n_cls, nK, n_proj, Ktot, chunk);
+        I2T_CHECK_LAUNCH("i2t_lsh_soft_bwd");
+    }
     return I2T_OK;
 }

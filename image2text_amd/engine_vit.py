@@ -22,6 +22,9 @@ Heads
                ``peer_proj_wt``, the four linear maps as GEMMs, then ``i2t_peer_lookup_fwd`` (top-k / softmax / expert gathers).
     LSH        (encoder.py:117, layers.py:112-143,190-219)  fp32 projections (``i2t_gemm_f32``: bucket boundaries are discontinuities,
                bf16 operands would move rows across them), ``i2t_lsh_embed_fwd``; gradients reach the embedding tables only.
+    LSH, learnable (layers.py:147-191)  ``lsh_config.learnable``: cosines against the row-normalised ``proj.weight`` of every (slot,
+               resolution) in fp32 (one ``i2t_gemm_f32``), ``i2t_lsh_soft_fwd`` (Gaussian bins, normalised, bf16, slot-major),
+               ``emb.weight`` as ``i2t_grouped_gemm`` with group = slot (one call per resolution over column slices of the same rows).
 """
 from types import SimpleNamespace
 
@@ -40,14 +43,14 @@ class ViTEncoder:
         enc_mod = model.encoder[0] if model.has_bridge else model.encoder
         spec = enc_mod.model.spec
         d, p, img = spec['hidden_dim'], spec['patch_size'], spec['image_size']
-        head = 'peer' if enc_mod.use_peer else ('lsh' if enc_mod.use_lsh else 'mlp')
+        head = 'peer' if enc_mod.use_peer else ('mlp' if not enc_mod.use_lsh else ('lsh_soft' if ecfg.lsh_config.learnable else 'lsh'))
         self.enc = SimpleNamespace(kind='vit', ncls=ecfg.n_cls, d=d, out=ecfg.n_embd_out_vit, L=spec['num_layers'], H=spec['num_heads'],
                                    ff=spec['mlp_dim'], p=p, img=img, P2=(img // p) ** 2, T=(img // p) ** 2 + 1, dropout=0.0,
                                    attn_dropout=0.0, fam=None, causal=False, refine=bool(enc_mod.refine), head=head, module=enc_mod)
         if head == 'peer':
             pc = ecfg.peer_config
             self.enc.peer = SimpleNamespace(nq=pc.num_units_sqrt, topk=pc.topk, nh=pc.nhead, qd=enc_mod.peer.query_dim)
-        if head == 'lsh':
+        if head in ('lsh', 'lsh_soft'):
             lc = ecfg.lsh_config
             self.enc.lsh = SimpleNamespace(bins=tuple(lc.num_bins), n_proj=lc.num_proj, cache=None)
         self.conv, self.conv_mfma, self.cls_only_last = [], False, False
@@ -378,13 +381,94 @@ class ViTEncoder:
         ops.lsh_embed_bwd(denc, ctx.rows, a.g32[t.base:], t.stride, t.toff, B, e.ncls, t.nK, lc.n_proj, e.out)
         return None                                            # bucketize passes no gradient (and LSH forces refine off)
 
+    # ------------------------------------------------------------------------------------------------ learnable LSH head
+    def _lsh_soft_tables(self):
+        """Where the LearnableCosineVectorEmbeddings of the slots sit in the arena: slot s = slot 0 + s * stride for each of the three
+        parameter kinds, resolution k at its own offset inside a slot; the column ranges of a slot's K axis."""
+        a, e, lc = self.arena, self.enc, self.enc.lsh
+        if lc.cache is not None and lc.cache.version == a.p32.data_ptr():
+            return lc.cache
+        dev, nK, n = a.device, len(lc.bins), e.ncls
+        off = lambda s, k, leaf: a.entries[f'{self.ep}lsh_emb.{s}.emb.{k}.{leaf}'][0]
+        stride = off(1, 0, 'mean') - off(0, 0, 'mean') if n > 1 else 0
+        for s in range(n):
+            for k in range(nK):
+                q = f'{self.ep}lsh_emb.{s}.emb.{k}.'
+                assert tuple(a.entries[q + 'mean'][2]) == (1, 1, lc.n_proj, lc.bins[k])
+                assert tuple(a.entries[q + 'proj.weight'][2]) == (lc.n_proj, e.d)
+                assert tuple(a.entries[q + 'emb.weight'][2]) == (e.out, lc.n_proj * lc.bins[k])
+                for leaf in ('mean', 'proj.weight', 'emb.weight'):      # the constant-stride layout the kernels and the grouped GEMMs rely on
+                    assert off(s, k, leaf) == off(0, k, leaf) + s * stride, (s, k, leaf)
+        koff = np.concatenate(([0], np.cumsum([lc.n_proj * nb for nb in lc.bins]))).astype(np.int32)
+        lc.cache = SimpleNamespace(
+            version=a.p32.data_ptr(), nK=nK, stride=stride, Ktot=int(koff[-1]), koff_host=[int(v) for v in koff],
+            koff=torch.from_numpy(koff).to(dev), nbins=torch.tensor(lc.bins, dtype=torch.int32, device=dev),
+            moff=torch.tensor([off(0, k, 'mean') for k in range(nK)], dtype=torch.int64, device=dev),
+            poff=torch.tensor([off(s, k, 'proj.weight') for s in range(n) for k in range(nK)], dtype=torch.int64, device=dev),
+            eoff=[off(0, k, 'emb.weight') for k in range(nK)])
+        return lc.cache
+
+    def _vit_head_lsh_soft_fwd(self, feat, B: int, save: bool):
+        a, e, lc = self.arena, self.enc, self.enc.lsh
+        t = self._lsh_soft_tables()
+        d, n, M, G = e.d, e.ncls, e.ncls * B, e.ncls * t.nK
+        ncol = G * lc.n_proj
+        plan = self._pos_plan(B, n, None)                      # slot-major row order of a [B, n_cls] batch
+        xn = self._empty(B, d)
+        ops.l2norm_fwd(feat, xn, None, None, B, d)
+        # the cosines stay fp32 (i2t_gemm_f32): with sigma = 2 / nb an error delta in c is a relative error |c - mean| delta / sigma^2 in a
+        # bin's activation (x 100 at 20 bins), and this GEMM is 0.3 GFLOP at the shipped sizes
+        wn, winv = self._empty(ncol, d), self._empty(ncol)
+        ops.l2norm_groups_fwd(a.p32, t.poff, wn, winv, G, lc.n_proj, d)
+        wt = self._empty(d, ncol)
+        ops.transpose_last2(wn, wt, None, 1, ncol, d)
+        c = self._empty(B, ncol)
+        ops.gemm_f32(xn, wt, c, B, ncol, d)
+        z, rn = self._empty(M, t.Ktot, dtype=BF16), self._empty(B, ncol)
+        ops.lsh_soft_fwd(c, a.p32, t.stride, t.moff, t.nbins, t.koff, z, rn, B, n, t.nK, lc.n_proj, t.Ktot)
+        y = self._empty(M, e.out)
+        for k in range(t.nK):                                  # y_s = sum_k z[:, cols of k] . emb_k^T: one grouped GEMM per resolution
+            k0, Kk = t.koff_host[k], t.koff_host[k + 1] - t.koff_host[k]
+            ops.grouped_gemm(0, z[:, k0:k0 + Kk], a.pbf[t.eoff[k]:][:e.out * Kk].view(e.out, Kk), y, e.out, Kk, b_group_stride=t.stride,
+                             accumulate=k > 0, seg=plan.seg, n_groups=n, max_rows=B, group0=0)
+        enc_out = self._empty(M, e.out)
+        ops.scatter_rows(y, plan.rows, enc_out, M, e.out)      # slot-major -> (image, slot)
+        self.lsh_trace = SimpleNamespace(c=c)
+        ctx = SimpleNamespace(plan=plan, xn=xn, winv=winv, c=c, z=z, rn=rn) if save else None
+        return enc_out, ctx
+
+    def _vit_head_lsh_soft_bwd(self, ctx, denc, B: int):
+        """denc fp32 [B * n_cls, out] -> gradients of every emb.weight, mean and proj.weight; no feature gradient (LSH forces refine off)."""
+        a, e, lc = self.arena, self.enc, self.enc.lsh
+        t = self._lsh_soft_tables()
+        d, n, M, G, plan = e.d, e.ncls, e.ncls * B, e.ncls * t.nK, ctx.plan
+        ncol = G * lc.n_proj
+        g = self._empty(M, e.out, dtype=BF16)
+        ops.gather_rows(denc, plan.rows, M, e.out, out_bf16=g)
+        dz = self._empty(M, t.Ktot)
+        kw = dict(seg=plan.seg, n_groups=n, max_rows=B, group0=0)
+        for k in range(t.nK):
+            k0, Kk = t.koff_host[k], t.koff_host[k + 1] - t.koff_host[k]
+            zk = ctx.z[:, k0:k0 + Kk]
+            ops.grouped_gemm(2, g, zk, a.g32[t.eoff[k]:][:e.out * Kk].view(e.out, Kk), e.out, Kk, c_group_stride=t.stride, accumulate=True, **kw)
+            ops.grouped_gemm(1, g, a.pbf[t.eoff[k]:][:e.out * Kk].view(e.out, Kk), dz[:, k0:k0 + Kk], e.out, Kk, b_group_stride=t.stride, **kw)
+        dc, tws = self._empty(B, ncol), self._empty(B, ncol)
+        ops.lsh_soft_bwd(dz, ctx.c, ctx.rn, a.p32, a.g32, t.stride, t.moff, t.nbins, t.koff, dc, tws, B, n, t.nK, lc.n_proj, t.Ktot)
+        dct = self._empty(ncol, B)
+        ops.transpose_last2(dc, dct, None, 1, B, ncol)
+        dwn = self._empty(ncol, d)
+        ops.gemm_f32(dct, ctx.xn, dwn, ncol, d, B)             # d/d(normalised rows) = dc^T . normalised features, fp32 like the forward
+        ops.l2norm_groups_bwd(dwn, a.p32, t.poff, ctx.winv, a.g32, G, lc.n_proj, d, accumulate=True)
+        return None
+
     # ------------------------------------------------------------------------------------------------ encoder entry points
     def vit_encode(self, images: torch.Tensor, save: bool):
         a, e = self.arena, self.enc
         images = images.to(device=a.device, dtype=F32).contiguous()
         B = images.shape[0]
         feat, bctx = self.vit_backbone_fwd(images, save and e.refine)
-        head_fwd = {'mlp': self._vit_head_mlp_fwd, 'peer': self._vit_head_peer_fwd, 'lsh': self._vit_head_lsh_fwd}[e.head]
+        head_fwd = {'mlp': self._vit_head_mlp_fwd, 'peer': self._vit_head_peer_fwd, 'lsh': self._vit_head_lsh_fwd,
+                    'lsh_soft': self._vit_head_lsh_soft_fwd}[e.head]
         y, hctx = head_fwd(feat, B, save)
         yb = None
         if self.has_bridge:
@@ -408,7 +492,8 @@ class ViTEncoder:
             dy = self._empty(M, e.out)
             self._linear_bwd(dencb, M, self.dec.d, e.out, ctx.yb, 'encoder.1.weight', None, dx_out=dy)
             denc = dy
-        head_bwd = {'mlp': self._vit_head_mlp_bwd, 'peer': self._vit_head_peer_bwd, 'lsh': self._vit_head_lsh_bwd}[e.head]
+        head_bwd = {'mlp': self._vit_head_mlp_bwd, 'peer': self._vit_head_peer_bwd, 'lsh': self._vit_head_lsh_bwd,
+                    'lsh_soft': self._vit_head_lsh_soft_bwd}[e.head]
         dfeat = head_bwd(ctx.hctx, denc, B)
         if e.refine and dfeat is not None:
             self.vit_backbone_bwd(ctx.bctx, dfeat, B)

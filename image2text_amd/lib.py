@@ -108,6 +108,10 @@ SIGNATURES = {
     'i2t_gemm_f32': [P, P, P, P, I, I, I],
     'i2t_lsh_embed_fwd': [P, P, P, L, P, P, P, P, P, P, I, I, I, I, I],
     'i2t_lsh_embed_bwd': [P, P, P, P, L, P, I, I, I, I, I],
+    'i2t_l2norm_groups_fwd': [P, P, P, P, P, I, I, I],
+    'i2t_l2norm_groups_bwd': [P, P, P, P, P, P, I, I, I, I],
+    'i2t_lsh_soft_fwd': [P, P, P, L, P, P, P, P, P, I, I, I, I, I],
+    'i2t_lsh_soft_bwd': [P, P, P, P, P, P, L, P, P, P, P, P, I, I, I, I, I],
     'i2t_quant_rows_fp8': [P, P, I, I, P, I, P, I, I],
     'i2t_quant_cols_fp8': [P, P, I, P, I, P, I, I],
     'i2t_rmsnorm_fwd_fp8': [P, P, P, P, I, P, P, I, I, F, P],
@@ -128,7 +132,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 _lib = None
 
 

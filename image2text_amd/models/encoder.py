@@ -157,8 +157,9 @@ def _load_backbone_weights(model: TorchvisionViT):
 class PretrainedViT(Encoder):
     """torchvision ViT-B/16 backbone (class-token feature, 768 wide) + one of three heads that turn it into ``n_cls`` encoder
     outputs (reference encoder.py:56-127): a private MLP per slot between two L2 normalisations (default), a PEER product-key
-    lookup behind a learned (768, 768, n_cls) expansion (``peer_config``), or LSH cosine-bucket embeddings (``lsh_config``;
-    forces the backbone frozen).  ``backbone_spec`` exists for tests (fewer layers); checkpoints need ``VIT_B16``."""
+    lookup behind a learned (768, 768, n_cls) expansion (``peer_config``), or LSH cosine embeddings (``lsh_config``: fixed random
+    projections into buckets, or -- ``learnable`` -- learned projections into Gaussian bins; forces the backbone frozen).
+    ``backbone_spec`` exists for tests (fewer layers); checkpoints need ``VIT_B16``."""
     backbone_spec = VIT_B16
 
     def __init__(self, config: PretrainedViTConfig):
@@ -200,6 +201,12 @@ class PretrainedViT(Encoder):
                                           'num_units_sqrt <= 1024, widths multiples of 8)')
         if self.use_lsh and config.n_embd_out_vit % 4:
             raise NotImplementedError('n_embd_out_vit must be a multiple of 4 for the LSH embedding kernels')
+        if self.use_lsh and config.lsh_config.learnable:
+            lc = config.lsh_config
+            widths = [config.n_embd_out_vit] + [lc.num_proj * nb for nb in lc.num_bins]
+            if any(w % 32 for w in widths) or min(lc.num_bins) < 1 or len(lc.num_bins) * lc.num_proj > 1024:
+                raise NotImplementedError(f'learnable LSH head: n_embd_out_vit and every num_proj * num_bins {widths} must be multiples of 32 '
+                                          '(grouped MFMA GEMM tiles), with at most 1024 projections per slot')
 
     def forward(self, images: torch.Tensor):
         from .vision_encoder_decoder import run_encoder_standalone

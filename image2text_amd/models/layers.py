@@ -164,15 +164,40 @@ class CosineVectorEmbedding(_Container):
         self.emb_dim, self.n_proj, self.num_bins = emb_dim, n_proj, num_bins
 
 
+class CosineLinear(_Container):
+    """weight (out, in) of a cosine projection: normalize(x) @ normalize(weight, dim=-1).T (reference layers.py:147-153)."""
+
+    def __init__(self, inp_dim, out_dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.randn((out_dim, inp_dim)) / math.sqrt(inp_dim))
+
+
+class LearnableCosineVectorEmbedding(_Container):
+    """Learned cosine projections -> Gaussian activations around learned bin centres (width 2 / num_bins), L2-normalised over the
+    bins -> Linear(n_proj * num_bins -> emb_dim, no bias) (reference layers.py:156-191; arithmetic: engine_vit / csrc/vit.hip)."""
+
+    def __init__(self, inp_dim: int, emb_dim: int, n_proj: int = 16, num_bins: int = 20, sigma_inflation_factor: float = 1.0,
+                 top_k: Optional[int] = None):
+        super().__init__()
+        if top_k is not None:       # the reference's compression switch (layers.py:187-190); CompositeCosineVectorEmbedding never sets it
+            raise NotImplementedError('LearnableCosineVectorEmbedding(top_k=...) is outside the HIP hot path: the top-k crop of the '
+                                      'activations is reachable from no config, only top_k=None runs')
+        self.emb_dim, self.n_proj, self.num_bins = emb_dim, n_proj, num_bins
+        self.top_k = None
+        self.sigma2 = (sigma_inflation_factor * 2.0 / num_bins) ** 2
+        self.proj = CosineLinear(inp_dim, n_proj)
+        self.mean = nn.Parameter(2 * torch.rand((1, 1, n_proj, num_bins)) - 1)
+        self.emb = nn.Linear(self.n_proj * self.num_bins, emb_dim, bias=False)
+
+
 class CompositeCosineVectorEmbedding(_Container):
-    """Sum of CosineVectorEmbeddings at several bin resolutions (reference layers.py:190-219)."""
+    """Sum of CosineVectorEmbeddings (or, ``learnable``, LearnableCosineVectorEmbeddings) at several bin resolutions (reference
+    layers.py:194-219)."""
 
     def __init__(self, inp_dim: int, emb_dim: int, num_bins: Tuple[int, ...], n_proj: int, learnable: bool):
         super().__init__()
-        if learnable:
-            raise NotImplementedError('LearnableCosineVectorEmbedding (lsh_config.learnable: True; no shipped yaml uses it) is outside '
-                                      'the HIP hot path')
-        self.emb = nn.ModuleList([CosineVectorEmbedding(inp_dim=inp_dim, emb_dim=emb_dim, n_proj=n_proj, num_bins=k) for k in num_bins])
+        lsh_clazz = LearnableCosineVectorEmbedding if learnable else CosineVectorEmbedding
+        self.emb = nn.ModuleList([lsh_clazz(inp_dim=inp_dim, emb_dim=emb_dim, n_proj=n_proj, num_bins=k) for k in num_bins])
 
 
 class _MoEUnit(_Container):

@@ -838,6 +838,44 @@ def lsh_embed_bwd(dy, rows, g_tables, slot_stride, tab_off, B, n_cls, nK, n_proj
              'i2t_lsh_embed_bwd')
 
 
+def l2norm_groups_fwd(x, group_off, y, inv_norm, G, rows, d):
+    """l2norm_fwd over G matrices of ``rows`` rows at x + group_off[g] (int64 element offsets); y / inv_norm contiguous"""
+    _need_cuda(x, group_off, y, inv_norm)
+    assert x.dtype == F32 and y.dtype == F32 and group_off.dtype == torch.int64 and group_off.numel() >= G and y.is_contiguous()
+    _l.check(_lib().i2t_l2norm_groups_fwd(_stream(), _p(x), _p(group_off), _p(y), _p(inv_norm), G, rows, d), 'i2t_l2norm_groups_fwd')
+    return y
+
+
+def l2norm_groups_bwd(dy, x, group_off, inv_norm, dx, G, rows, d, accumulate=False):
+    _need_cuda(dy, x, group_off, inv_norm, dx)
+    assert dy.dtype == F32 and x.dtype == F32 and dx.dtype == F32 and group_off.dtype == torch.int64 and group_off.numel() >= G and dy.is_contiguous()
+    _l.check(_lib().i2t_l2norm_groups_bwd(_stream(), _p(dy), _p(x), _p(group_off), _p(inv_norm), _p(dx), int(accumulate), G, rows, d),
+             'i2t_l2norm_groups_bwd')
+    return dx
+
+
+def lsh_soft_fwd(c, params, slot_stride, mean_off, nbins, col_off, z, inv_norm, B, n_cls, nK, n_proj, Ktot):
+    """Gaussian-kernel activations of the learnable LSH head, normalised, bf16, slot-major (include/i2t.h::i2t_lsh_soft_fwd)"""
+    _need_cuda(c, params, mean_off, nbins, col_off, z, inv_norm)
+    assert c.dtype == F32 and params.dtype == F32 and z.dtype == BF16 and inv_norm.dtype == F32 and c.is_contiguous() and z.is_contiguous()
+    assert mean_off.dtype == torch.int64 and nbins.dtype == torch.int32 and col_off.dtype == torch.int32 and col_off.numel() == nK + 1
+    assert c.numel() == B * n_cls * nK * n_proj == inv_norm.numel() and z.numel() == B * n_cls * Ktot
+    _l.check(_lib().i2t_lsh_soft_fwd(_stream(), _p(c), _p(params), int(slot_stride), _p(mean_off), _p(nbins), _p(col_off), _p(z), _p(inv_norm),
+                                     B, n_cls, nK, n_proj, Ktot), 'i2t_lsh_soft_fwd')
+    return z
+
+
+def lsh_soft_bwd(dz, c, inv_norm, params, g_params, slot_stride, mean_off, nbins, col_off, dc, t_ws, B, n_cls, nK, n_proj, Ktot):
+    """dz f32 [n_cls B, Ktot] -> dc (c's layout) and g_params (+)= d/d(mean) (None: frozen); include/i2t.h::i2t_lsh_soft_bwd"""
+    _need_cuda(dz, c, inv_norm, params, g_params, mean_off, nbins, col_off, dc, t_ws)
+    assert dz.dtype == F32 and dz.is_contiguous() and dz.numel() == B * n_cls * Ktot and dc.dtype == F32 and t_ws.dtype == F32
+    assert c.numel() == B * n_cls * nK * n_proj == inv_norm.numel() == dc.numel() == t_ws.numel()
+    assert mean_off.dtype == torch.int64 and nbins.dtype == torch.int32 and col_off.dtype == torch.int32 and col_off.numel() == nK + 1
+    _l.check(_lib().i2t_lsh_soft_bwd(_stream(), _p(dz), _p(c), _p(inv_norm), _p(params), _p(g_params), int(slot_stride), _p(mean_off), _p(nbins),
+                                     _p(col_off), _p(dc), _p(t_ws), B, n_cls, nK, n_proj, Ktot), 'i2t_lsh_soft_bwd')
+    return dc
+
+
 # ---- fp8 (e4m3) operand path for frozen weights (csrc/fp8.hip)
 def quant_rows_fp8(x, out, scale, M, K):
     """x bf16 / f32 [M, >= K] -> out uint8 [M, ld_out] (e4m3 bytes, zero pad), scale f32 [M] (amax / 448)."""

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 4
+#define I2T_ABI_VERSION 5
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -578,6 +578,16 @@ int i2t_graph_destroy(void* graph_exec);
  *     -> bucket = #(grid points < z) -> mean over projections of table rows, summed over the nK resolutions; table k of slot s =
  *     tables + s slot_stride + tab_off[k] (f32 [(nbins[k] + 1) n_proj][dout]); grid k = grids + grid_off[k]; rows int [B][n_cls][nK][n_proj]
  *     saved; bwd scatters dy / n_proj into the tables' gradients (atomics).
+ *   i2t_l2norm_groups_fwd / _bwd: the same normalisation for G matrices of `rows` rows that sit apart in one arena (the CosineLinear
+ *     weights of the learnable LSH head, models/layers.py:147-153): row r of group g = x + group_off[g] + r d (offsets in elements,
+ *     multiples of 4); y f32 [(g, r)][d] and inv_norm [G rows] come out contiguous; bwd writes dx (+)= at the same offsets of `dx`.
+ *   i2t_lsh_soft_fwd / _bwd: LearnableCosineVectorEmbedding.gaussian_kernel (models/layers.py:183-191, top_k None) per (image b, slot s,
+ *     resolution k, projection j): a_i = exp(-(c - mean_i)^2 / (2 (2 / nb_k)^2)), z = a / max(||a||_2, 1e-12), fp32 arithmetic, any
+ *     nb_k >= 1.  c f32 [B][n_cls nK n_proj]; mean of (s, k) = params + s slot_stride + mean_off[k] (f32 [n_proj][nb_k]); z bf16
+ *     [n_cls B][Ktot], row s B + b, column col_off[k] + j nb_k + i (col_off int [nK + 1], col_off[nK] = Ktot): the A operand of
+ *     i2t_grouped_gemm with group = slot; inv_norm f32 [B][n_cls nK n_proj] saved.  bwd: dz f32 [n_cls B][Ktot] -> dc f32 (c's layout;
+ *     t_ws = workspace of the same size) and g_params (+)= the means' gradient at the means' offsets (null = frozen): a sum over the
+ *     batch, chunks of it meeting in fp32 atomics -- ONE fixed-order sum per element in deterministic mode.
  * --------------------------------------------------------------------------------------------------------- */
 int i2t_patchify(void* stream, const float* images, void* out, int B, int C, int H, int W, int p);
 int i2t_vit_tokens(void* stream, const float* proj, const float* cls, const float* pos, float* x, int B, int T, int d);
@@ -595,6 +605,14 @@ int i2t_lsh_embed_fwd(void* stream, const float* z, const float* tables, long sl
                       const float* grids, const int* grid_off, float* out, int* rows, int B, int n_cls, int nK, int n_proj, int dout);
 int i2t_lsh_embed_bwd(void* stream, const float* dy, const int* rows, float* g_tables, long slot_stride, const long* tab_off, int B,
                       int n_cls, int nK, int n_proj, int dout);
+int i2t_l2norm_groups_fwd(void* stream, const float* x, const long* group_off, float* y, float* inv_norm, int G, int rows, int d);
+int i2t_l2norm_groups_bwd(void* stream, const float* dy, const float* x, const long* group_off, const float* inv_norm, float* dx,
+                          int accumulate, int G, int rows, int d);
+int i2t_lsh_soft_fwd(void* stream, const float* c, const float* params, long slot_stride, const long* mean_off, const int* nbins,
+                     const int* col_off, void* z_bf16, float* inv_norm, int B, int n_cls, int nK, int n_proj, int Ktot);
+int i2t_lsh_soft_bwd(void* stream, const float* dz, const float* c, const float* inv_norm, const float* params, float* g_params,
+                     long slot_stride, const long* mean_off, const int* nbins, const int* col_off, float* dc, float* t_ws, int B,
+                     int n_cls, int nK, int n_proj, int Ktot);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange (replaces accelerate's DDP wrap, reference trainer.py:108-114,173-174):
