@@ -47,6 +47,9 @@ from .lib import I2TError
 BF16, F32 = torch.bfloat16, torch.float32
 # I2T_GELU_DOUT=0: the MLP's first GEMM keeps the pre-activation and the backward re-evaluates GELU' (A/B runs, bit-compatible with round 3)
 GELU_KEEPS_DERIVATIVE = os.environ.get('I2T_GELU_DOUT', '1') != '0'
+# the dense block's linears a LoRA adapter may ride on (engine_lora._lora_site): site -> (weight, bias) under the block's prefix
+_BLOCK_SITES = {'attn_c_attn': ('attn.c_attn.weight', 'attn.c_attn.bias'), 'xattn_c_attn': ('cross_attn.in_proj_weight', 'cross_attn.in_proj_bias'),
+                'mlp_c_fc': ('mlp.c_fc.weight', 'mlp.c_fc.bias'), 'mlp_c_proj': ('mlp.c_proj.weight', 'mlp.c_proj.bias')}
 # I2T_FOLD_NORMALISER=0: every block runs its own grad_normalize pass over the incoming gradient (A/B runs)
 NORMALISER_FOLDED = os.environ.get('I2T_FOLD_NORMALISER', '1') != '0'
 # the embedding dropouts applied by the producers of the embedded rows (forward) and by the lowest block's last LayerNorm backward
@@ -379,7 +382,7 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         # mixed into every training forward's dropout seed: a second model stepped at the same cadence (the momentum twin,
         # reference wrapper.py:68-71,197-198: forward_m draws fresh torch RNG) must not repeat this model's masks
         self.seed_salt = 0
-        # fp8 (e4m3) operands for the GEMMs of FROZEN decoder weights (engine_llama._lin; BASELINE.json configs[4]); off unless I2T_FP8=1
+        # fp8 (e4m3) operands for the GEMMs of FROZEN decoder weights (engine_lora.linear_path; BASELINE.json configs[4]); off unless I2T_FP8=1
         self.fp8 = os.environ.get('I2T_FP8', '0') not in ('', '0') or bool(getattr(model.decoder, 'fp8_request', False))
         self.fp8_fuse = os.environ.get('I2T_FP8_FUSE', '1') != '0'      # producers emit the e4m3 operand themselves (engine_llama, csrc/fp8.hip)
         # a frozen PretrainedViT backbone on e4m3 operands is its OWN opt-in (I2T_FP8_VIT=1): `fp8` above covers decoder weights only, as the
@@ -490,15 +493,11 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         ln1, m1, r1 = self._empty(M, d, dtype=BF16), self._empty(M), self._empty(M)
         ops.layernorm_fwd(x, a.P(f'{pfx}.ln_1.weight'), a.P(f'{pfx}.ln_1.bias'), ln1, m1, r1, M, d)
         qkv = self._empty(M, 3 * d, dtype=BF16)
-        ldrop = (lambda site: plan.get(layer, f'lora_{site}') if plan is not None else None)
-        lo = {site: self._lora_site(layer, site) for site in ('attn_c_attn', 'xattn_c_attn', 'mlp_c_fc', 'mlp_c_proj')} \
+        # the four linears a LoRA adapter may ride on (in the GEMM's K panel: engine_lora.py) go through their site records
+        sv.lo_drop = {site: plan.get(layer, f'lora_{site}') if plan is not None else None for site in _BLOCK_SITES} \
             if (pfx.startswith(self.dp) and getattr(self.dec, 'lora', None) is not None) else {}
-        sv.lo, sv.lo_drop = {}, {site: ldrop(site) for site in lo}
-        if lo.get('attn_c_attn') is not None:      # LoRA: the adapter rides in the GEMM's K panel (engine_lora.py)
-            sv.lo['attn_c_attn'] = self._lora_gemm(lo['attn_c_attn'], ln1, a.W(f'{pfx}.attn.c_attn.weight'), qkv, M, ldrop('attn_c_attn'), save,
-                                                   bias=a.P(f'{pfx}.attn.c_attn.bias'), drop=dr['qkv'])
-        else:
-            ops.gemm(ln1, a.W(f'{pfx}.attn.c_attn.weight'), qkv, M, 3 * d, d, bias=a.P(f'{pfx}.attn.c_attn.bias'), drop=dr['qkv'])
+        lo = {'attn_c_attn': self._site_fwd(self._block_site(pfx, layer, 'attn_c_attn', 3 * d, d), ln1, qkv, M, sv.lo_drop.get('attn_c_attn'), save,
+                                            drop=dr['qkv'])}
         ao, lse = self._empty(M, d, dtype=BF16), self._empty(H * M)
         q3 = v3(qkv, 3 * d)
         ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], v3(ao, d), lse, B, H, T, T, causal, drop=dr['sdpa'],
@@ -518,9 +517,9 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
             ops.gemm(ln3, win[:d], q, M, d, d, bias=bin_[:d])
             kv = self._empty(B, S, 2 * d, dtype=BF16)
             co, lse_c = self._empty(M, d, dtype=BF16), self._empty(H * M)
-            if lo.get('xattn_c_attn') is not None:      # adapted K/V projection: the un-fused form
-                sv.lo['xattn_c_attn'] = self._lora_gemm(lo['xattn_c_attn'], mem_bf, win[d:], kv.view(B * S, 2 * d), B * S, ldrop('xattn_c_attn'),
-                                                        save, bias=bin_[d:])
+            s_kv = self._block_site(pfx, layer, 'xattn_c_attn', 2 * d, d, rows=(d, 3 * d))
+            if s_kv.lora is not None:      # adapted K/V projection: the un-fused form
+                lo['xattn_c_attn'] = self._site_fwd(s_kv, mem_bf, kv.view(B * S, 2 * d), B * S, sv.lo_drop.get('xattn_c_attn'), save)
                 ops.attention_fwd(v3(q, d), kv[..., :d], kv[..., d:], v3(co, d), lse_c, B, H, T, S, False, drop=dr['xattn'],
                                   cu_q=cu, total_q=M)
             elif self.xattn_fused and S == 64 and H % 2 == 0 and d == 64 * H and not ops.precise():
@@ -540,40 +539,35 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         ops.layernorm_fwd(x2, a.P(f'{pfx}.ln_2.weight'), a.P(f'{pfx}.ln_2.bias'), ln2, m2, r2, M, d)
         h = self._empty(M, ff, dtype=BF16)
         pre = self._empty(M, ff, dtype=BF16) if save else None
-        if lo.get('mlp_c_fc') is not None:
-            sv.lo['mlp_c_fc'] = self._lora_gemm(lo['mlp_c_fc'], ln2, a.W(f'{pfx}.mlp.c_fc.weight'), h, M, ldrop('mlp_c_fc'), save,
-                                                bias=a.P(f'{pfx}.mlp.c_fc.bias'), act=1, aux_out=pre)
-        else:
-            # the second output of a step that will be differentiated is GELU'(pre), not pre: the backward GEMM's epilogue is then one
-            # multiply per element (ops.ACT_MUL_AUX) instead of re-evaluating exp + rcp; the LoRA forms keep the pre-activation
-            dout = save and GELU_KEEPS_DERIVATIVE and lo.get('mlp_c_proj') is None
-            ops.gemm(ln2, a.W(f'{pfx}.mlp.c_fc.weight'), h, M, ff, d, bias=a.P(f'{pfx}.mlp.c_fc.bias'),
-                     act=ops.ACT_GELU_DOUT if dout else 1, aux_out=pre)
+        s_fc, s_proj = self._block_site(pfx, layer, 'mlp_c_fc', ff, d), self._block_site(pfx, layer, 'mlp_c_proj', d, ff)
+        # the second output of a step that will be differentiated is GELU'(pre), not pre: the backward GEMM's epilogue is then one
+        # multiply per element (ops.ACT_MUL_AUX) instead of re-evaluating exp + rcp; the LoRA forms keep the pre-activation
+        dout = save and GELU_KEEPS_DERIVATIVE and s_fc.lora is None and s_proj.lora is None
+        lo['mlp_c_fc'] = self._site_fwd(s_fc, ln2, h, M, sv.lo_drop.get('mlp_c_fc'), save, act=ops.ACT_GELU_DOUT if dout else 1, aux_out=pre)
+        if s_fc.lora is None:
             sv.pre_is_grad = dout
         x3 = self._empty(M, d)
-        if lo.get('mlp_c_proj') is not None:
-            sv.lo['mlp_c_proj'] = self._lora_gemm(lo['mlp_c_proj'], h, a.W(f'{pfx}.mlp.c_proj.weight'), x3, M, ldrop('mlp_c_proj'), save,
-                                                  bias=a.P(f'{pfx}.mlp.c_proj.bias'), residual=x2, drop=dr['mlp'])
-        else:
-            ops.gemm(h, a.W(f'{pfx}.mlp.c_proj.weight'), x3, M, d, ff, bias=a.P(f'{pfx}.mlp.c_proj.bias'), residual=x2,
-                     drop=dr['mlp'])
+        lo['mlp_c_proj'] = self._site_fwd(s_proj, h, x3, M, sv.lo_drop.get('mlp_c_proj'), save, residual=x2, drop=dr['mlp'])
         sv.x2, sv.ln2, sv.m2, sv.r2, sv.h, sv.pre = x2, ln2, m2, r2, h, pre
+        sv.lo = {site: r for site, r in lo.items() if r is not None}
         sv.layer = layer
         return x3, (sv if save else None)
 
+    def _block_site(self, pfx: str, layer: int, site: str, N: int, K: int, rows=None):
+        """The site record (engine_lora._site) of one of a dense block's four adaptable linears; adapters sit on decoder blocks only
+        (their spec is fixed per arena: looked up when the record is made)."""
+        key = ('block_site', pfx, site, id(self.arena))
+        s = self._sub_cache.get(key)
+        if s is None:
+            w, b = _BLOCK_SITES[site]
+            s = self._sub_cache[key] = self._site(f'{pfx}.{w}', N, K, f'{pfx}.{b}', lora=self._lora_site(layer, site) if pfx.startswith(self.dp) else None,
+                                                  rows=rows)
+        return s
+
     def _linear_bwd(self, dyb, M, N, K, x_bf, wname: str, bname: Optional[str], dx_out=None, dy_sumsq=None, **dx_kw):
-        """y = x W^T + b with y [M,N], x [M,K], W [N,K]: accumulates dW, db; returns/fills dX when requested.
-        dy_sumsq (1-float device tensor): dyb is an UN-normalised gradient whose normaliser 1 / (sqrt(dy_sumsq) + 1e-6) the three
-        consumers apply themselves (ops.gemm alpha_sumsq): no pass over dyb exists just to rescale it."""
-        a = self.arena
-        gb = a.Gt(bname) if bname else None
-        if gb is not None:
-            ops.colsum(dyb, gb, M, N, accumulate=True, alpha_sumsq=dy_sumsq)
-        if a.trainable(wname):
-            ops.gemm(dyb, x_bf, a.G(wname), N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True, alpha_sumsq=dy_sumsq)
-        if dx_out is not None:
-            ops.gemm(dyb, a.W(wname), dx_out, M, K, N, b_kmajor=True, alpha_sumsq=dy_sumsq, **dx_kw)
-        return dx_out
+        """y = x W^T + b with y [M,N], x [M,K], W [N,K]: accumulates dW, db; returns/fills dX when requested -- the plain branch of
+        engine_lora._site_bwd (dy_sumsq: see there): its record has no adapter and no fp8 switch, whatever other site shares the weight."""
+        return self._site_bwd(self._site(wname, N, K, bname), None, dyb, x_bf, M, dx_out=dx_out, dy_sumsq=dy_sumsq, **dx_kw)
 
     def block_bwd(self, pfx: str, sv, dx, dxb, B, T, d, H, ff, causal, S, dmem, emit_last_bf16: bool, vl=None, sumsq_out=None,
                   dx_pre=None, dxb_sumsq=None, last_bf16_drop=None, dx_mask=None):
@@ -590,26 +584,15 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         # ---- MLP: x3 = x2 + drop(c_proj(gelu(c_fc(ln_2 x2)))).  dxb arrives already masked with the MLP dropout (the
         # producer of the bf16 copy applies it: the branch sees the masked gradient, dx -- the residual path -- does not)
         dpre = self._empty(M, ff, dtype=BF16)
-        svlo = getattr(sv, 'lo', None) or {}
-        lsite = (lambda site: self._lora_site(sv.layer, site))
-        ldrop = (lambda site: sv.lo_drop.get(site))          # the adapter's input-dropout mask of the forward pass
-        if svlo.get('mlp_c_proj') is not None:        # LoRA (engine_lora.py): fp32 dh = dY . W + dropout(du . A), then the GELU derivative
-            dh32 = self._lora_bwd(lsite('mlp_c_proj'), svlo['mlp_c_proj'], dxb, sv.h, a.W(f'{pfx}.mlp.c_proj.weight'),
-                                  a.Gt(f'{pfx}.mlp.c_proj.weight'), a.Gt(f'{pfx}.mlp.c_proj.bias'), M, ldrop('mlp_c_proj'))
-            ops.dgelu_mul(dh32, sv.pre, dpre)
-        else:
-            # dxb_sumsq: dxb is the block-output gradient as the layer above left it -- masked, NOT normalised; mlp.c_proj's three
-            # backward launches apply 1 / (||dx|| + 1e-6) in their epilogues (no grad_normalize pass ran for this block)
-            self._linear_bwd(dxb, M, d, ff, sv.h, f'{pfx}.mlp.c_proj.weight', f'{pfx}.mlp.c_proj.bias' if a.G(f'{pfx}.mlp.c_proj.bias') is not None else None,
-                             dx_out=dpre, act=ops.ACT_MUL_AUX if getattr(sv, 'pre_is_grad', False) else 2, aux_in=sv.pre, dy_sumsq=dxb_sumsq)
+        # (the four adaptable linears: engine_lora._site_bwd -- sv.lo / sv.lo_drop: the adapters' save records and the input-dropout
+        # masks of the forward pass; an adapted site returns its own fp32 dx = dY . W + dropout(du . A), the LayerNorm backward takes either)
+        svlo, ldrop = sv.lo, sv.lo_drop
+        # dxb_sumsq: dxb is the block-output gradient as the layer above left it -- masked, NOT normalised; mlp.c_proj's three
+        # backward launches apply 1 / (||dx|| + 1e-6) in their epilogues (no grad_normalize pass ran for this block)
+        self._site_bwd(self._block_site(pfx, sv.layer, 'mlp_c_proj', d, ff), svlo.get('mlp_c_proj'), dxb, sv.h, M, ldrop.get('mlp_c_proj'), dx_out=dpre,
+                       act=ops.ACT_MUL_AUX if getattr(sv, 'pre_is_grad', False) else 2, aux_in=sv.pre, dy_sumsq=dxb_sumsq)
         dln = self._empty(M, d, dtype=BF16)
-        dln2 = dln
-        if svlo.get('mlp_c_fc') is not None:
-            dln2 = self._lora_bwd(lsite('mlp_c_fc'), svlo['mlp_c_fc'], dpre, sv.ln2, a.W(f'{pfx}.mlp.c_fc.weight'),
-                                  a.Gt(f'{pfx}.mlp.c_fc.weight'), a.Gt(f'{pfx}.mlp.c_fc.bias'), M, ldrop('mlp_c_fc'))
-        else:
-            self._linear_bwd(dpre, M, ff, d, sv.ln2, f'{pfx}.mlp.c_fc.weight', f'{pfx}.mlp.c_fc.bias' if a.G(f'{pfx}.mlp.c_fc.bias') is not None else None,
-                             dx_out=dln)
+        dln2 = self._site_bwd(self._block_site(pfx, sv.layer, 'mlp_c_fc', ff, d), svlo.get('mlp_c_fc'), dpre, sv.ln2, M, ldrop.get('mlp_c_fc'), dx_out=dln)
         ops.layernorm_bwd(dln2, sv.x2, a.P(f'{pfx}.ln_2.weight'), sv.m2, sv.r2, dx, a.Gt(f'{pfx}.ln_2.weight'),
                           a.Gt(f'{pfx}.ln_2.bias'), M, d, dx_accumulate=True, dx_bf16=dxb,
                           bf16_drop=dr.get('xresid') if sv.cross else dr['resid'],      # next consumer of dxb: the (cross-)attention output projection's backward
@@ -631,16 +614,10 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
             if train_in:
                 ops.gemm(dqf, sv.ln3, gin[:d], d, d, M, a_kmajor=True, b_kmajor=True, accumulate=True)
             ops.gemm(dqf, win[:d], dln, M, d, d, b_kmajor=True)
-            if svlo.get('xattn_c_attn') is not None:
-                dmem32 = self._lora_bwd(lsite('xattn_c_attn'), svlo['xattn_c_attn'], dkvf, sv.mem, win[d:], gin[d:] if train_in else None,
-                                        gbin[d:] if train_inb else None, B * S, ldrop('xattn_c_attn'))
+            dmem32 = self._site_bwd(self._block_site(pfx, sv.layer, 'xattn_c_attn', 2 * d, d, rows=(d, 3 * d)), svlo.get('xattn_c_attn'), dkvf, sv.mem,
+                                    B * S, ldrop.get('xattn_c_attn'), dx_out=dmem, accumulate=True)
+            if dmem32 is not dmem:
                 ops.add_(dmem, dmem32)
-            else:
-                if train_inb:
-                    ops.colsum(dkvf, gbin[d:], B * S, 2 * d, accumulate=True)
-                if train_in:
-                    ops.gemm(dkvf, sv.mem, gin[d:], 2 * d, d, B * S, a_kmajor=True, b_kmajor=True, accumulate=True)
-                ops.gemm(dkvf, win[d:], dmem, B * S, d, 2 * d, b_kmajor=True, accumulate=True)
             ops.layernorm_bwd(dln, sv.x1, a.P(f'{pfx}.ln_3.weight'), sv.m3, sv.r3, dx, a.Gt(f'{pfx}.ln_3.weight'),
                               a.Gt(f'{pfx}.ln_3.bias'), M, d, dx_accumulate=True, dx_bf16=dxb, bf16_drop=dr['resid'])
         # ---- self attention: x1 = x + drop(c_proj(attn(mult * c_attn(ln_1 x)))); dxb carries the resid-dropout mask
@@ -652,13 +629,8 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         ops.attention_bwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], v3(sv.ao, d), v3(dao, d), sv.lse, ws, g3[..., :d],
                           g3[..., d:2 * d], g3[..., 2 * d:], B, H, T, T, causal, drop=dr['sdpa'], cu_q=cu, cu_k=cu, total_q=M,
                           out_drop=dr['qkv'])                  # gradient w.r.t. the un-multiplied q/k/v
-        dln1 = dln
-        if svlo.get('attn_c_attn') is not None:
-            dln1 = self._lora_bwd(lsite('attn_c_attn'), svlo['attn_c_attn'], dqkv, sv.ln1, a.W(f'{pfx}.attn.c_attn.weight'),
-                                  a.Gt(f'{pfx}.attn.c_attn.weight'), a.Gt(f'{pfx}.attn.c_attn.bias'), M, ldrop('attn_c_attn'))
-        else:
-            self._linear_bwd(dqkv, M, 3 * d, d, sv.ln1, f'{pfx}.attn.c_attn.weight',
-                             f'{pfx}.attn.c_attn.bias' if a.G(f'{pfx}.attn.c_attn.bias') is not None else None, dx_out=dln)
+        dln1 = self._site_bwd(self._block_site(pfx, sv.layer, 'attn_c_attn', 3 * d, d), svlo.get('attn_c_attn'), dqkv, sv.ln1, M, ldrop.get('attn_c_attn'),
+                              dx_out=dln)
         # last writer of dx in this block: it also leaves sum(dx^2) for the next block's gradient normaliser
         # (emit_last_bf16 with last_bf16_drop: the bf16 copy is the NEXT block's incoming gradient, already masked for ITS mlp.c_proj)
         ops.layernorm_bwd(dln1, sv.x, a.P(f'{pfx}.ln_1.weight'), sv.m1, sv.r1, dx, a.Gt(f'{pfx}.ln_1.weight'),

@@ -22,8 +22,153 @@ BF16, F32 = torch.bfloat16, torch.float32
 LPAD = 128
 
 
+def _f8pad(k: int) -> int:
+    return (k + 255) // 256 * 256
+
+
+def fuse_guard(fp8_fuse: bool, d: int = 0, ff: int = 0) -> bool:
+    """May a row producer emit the e4m3 operand itself?  The fused row kernels (csrc/fp8.hip) keep a whole row in registers: model width
+    up to 8192, MLP width up to 12288 (pass the widths the producer at hand works on)."""
+    return bool(fp8_fuse) and d <= 8192 and ff <= 12288
+
+
+def linear_path(adapter: bool, trainable: bool, switch, fp8: bool, fp8_vit: bool, fuse: bool = False):
+    """How one linear runs -- THE place where that is decided (no tensors: tests/test_host_cpu.py enumerates it).
+    adapter: a LoRA adapter rides on the site; trainable: any of its base weights takes gradient steps; switch: which engine switch
+    governs the site ('fp8': decoder, 'fp8_vit': ViT backbone, None: never e4m3) and the switches' values; fuse: the producer of the
+    input row may emit the e4m3 operand itself (``fuse_guard``).
+    -> (path: 'bf16' | 'fp8' | 'lora' | 'lora_fp8',  producer form: 'bf16' | 'e4m3' | 'both' rows)"""
+    e4m3 = not trainable and {'fp8': fp8, 'fp8_vit': fp8_vit, None: False}[switch]      # a frozen matrix has no dW: both its GEMMs can take e4m3
+    path = ('lora_fp8' if e4m3 else 'lora') if adapter else ('fp8' if e4m3 else 'bf16')
+    return path, ('bf16' if not (e4m3 and fuse) else 'both' if adapter else 'e4m3')      # (the adapter's u = dropout(x) A^T reads the bf16 row)
+
+
 class LoraAdapters:
-    """Mixin of engine.HotPath."""
+    """Mixin of engine.HotPath: the linear sites (plain / frozen-on-e4m3 / LoRA-adapted: ``_site`` + ``_site_fwd`` / ``_site_bwd``
+    own the choice between the three) and the adapters' machinery."""
+
+    def _site(self, names, N: int, K: int, bias=None, lora=None, switch=None, rows=None):
+        """The cached record of one linear y = x W^T (+ b), W [N, K]: names = its arena entry (several ADJACENT entries: a fused
+        projection); bias likewise or None; rows = (r0, r1): a row block of the entry; lora: the adapter's spec or None; switch: see
+        ``linear_path``.  The policy (switch, adapter) is part of the record's identity: a caller never gets a record another caller
+        made with another policy for the same weight (``engine._linear_bwd``'s plain sites beside the ViT backbone's fp8_vit ones).  The
+        adapter spec is fixed per arena (``dec.lora`` is set once, in HotPath.__init__)."""
+        key = ('site', names if isinstance(names, str) else tuple(names), rows, switch, None if lora is None else lora.nA, id(self.arena))
+        s = self._sub_cache.get(key)          # (the hit is on the host path of every step: nothing is normalised before it)
+        if s is not None:
+            assert s.N == N and s.K == K and s.lora is lora, (names, (s.N, s.K), (N, K))
+        else:
+            a = self.arena
+            names, bias = ((names,) if isinstance(names, str) else tuple(names)), ((bias,) if isinstance(bias, str) else tuple(bias or ()))
+            bias = bias if bias and bias[0] in a.entries else ()
+            view = (lambda kind, nn, shape: None if not nn else getattr(a, kind)(nn[0]) if len(nn) == 1 else a.span(kind, list(nn), shape))
+            W, G, b, gb = view('W', names, (N, K)), view('G', names, (N, K)), view('P', bias, (N,)), view('G', bias, (N,))
+            if rows is not None:
+                W, G, b, gb = (t if t is None else t[rows[0]:rows[1]] for t in (W, G, b, gb))
+            s = self._sub_cache[key] = SimpleNamespace(names=names, bnames=bias, W=W, G=G, b=b, gb=gb, N=N, K=K, lora=lora, switch=switch)
+        return s
+
+    def _site_path(self, s, fuse: bool = False):
+        return linear_path(s.lora is not None, any(self.arena.trainable(n) for n in s.names), s.switch, self.fp8, self.fp8_vit, fuse)
+
+    def _site_e4m3(self, s) -> bool:
+        """Does this call run the site's base product on e4m3 operands?  (once per forward / backward helper call)"""
+        if s.switch is None:
+            return False
+        on = 'fp8' in self._site_path(s)[0]
+        if not on and getattr(self, s.switch):
+            # a weight that trains (again): the optimizer writes it through the arena without moving its version counter, so an e4m3 image
+            # kept from an earlier frozen phase would be stale if the weight is frozen once more
+            self._sub_cache.pop(('fp8w', s.names, id(self.arena)), None)
+        return on
+
+    # ---- fp8 operands for FROZEN weights (I2T_FP8=1 / I2T_FP8_VIT=1; csrc/fp8.hip, BASELINE.json configs[4]): a frozen matrix has no dW,
+    # so both GEMMs that touch it -- y = x W^T and dx = dy W -- run on the block-scaled e4m3 MFMA; W is quantised once per parameter
+    # version in both orientations (per-output-row scales for the forward, per-input-row scales for the backward), activations per call
+    def _fp8_weight(self, s):
+        key = ('fp8w', s.names, id(self.arena))
+        ent = self._sub_cache.get(key)
+        # a frozen parameter is skipped by the fused optimizers (arena.generation moves every step, these values do not): the image
+        # is rebuilt only when torch-side code wrote the parameter (load_state_dict, a manual edit -> its version counter moves)
+        version = tuple(self.arena.params[n]._version for n in s.names)
+        if ent is None or ent.generation != version:
+            self.arena.refresh_shadow()
+            N, K, dev = s.N, s.K, s.W.device
+            # rows zero-padded to a multiple of 256 bytes: the GEMM then runs K' = the padded length (zeros contribute nothing) and every
+            # projection is eligible for the persistent fp8 kernel (K % 256 == 0; Falcon-7B: 4544 -> 4608)
+            ent = SimpleNamespace(generation=version,
+                                  w8=torch.empty(N, _f8pad(K), dtype=torch.uint8, device=dev), sw=torch.empty(N, dtype=F32, device=dev),
+                                  wt8=torch.empty(K, _f8pad(N), dtype=torch.uint8, device=dev), swt=torch.empty(K, dtype=F32, device=dev))
+            ops.quant_rows_fp8(s.W, ent.w8, ent.sw, N, K)
+            ops.quant_cols_fp8(s.W, ent.wt8, ent.swt, N, K)
+            self._sub_cache[key] = ent
+        return ent
+
+    def _fp8_rows(self, x_bf, M: int, K: int):
+        x8 = torch.empty(M, _f8pad(K), dtype=torch.uint8, device=x_bf.device)
+        sx = self._empty(M)
+        ops.quant_rows_fp8(x_bf, x8, sx, M, K)
+        return x8, sx
+
+    def _operand_rows(self, s, M: int, n: int, fuse: bool):
+        """Buffers for the row a fused producer (RMSNorm, SwiGLU forward / backward: engine_llama) hands to site ``s``: (bf16 [M, n] or
+        None, (e4m3 [M, pad n], scale [M]) or None) -- the e4m3 row when the site takes fp8 operands, the bf16 one unless nothing reads it"""
+        form = self._site_path(s, fuse)[1]
+        row = self._empty(M, n, dtype=BF16) if form != 'e4m3' else None
+        return row, ((torch.empty(M, _f8pad(n), dtype=torch.uint8, device=self.arena.device), self._empty(M)) if form != 'bf16' else None)
+
+    def _site_fwd(self, s, x_bf, out, M: int, drop_l=None, save: bool = False, xq=None, **ep):
+        """out = epilogue(x W^T (+ b)) on the site's path.  xq = (x8, scale): the producer already emitted the e4m3 operand (x_bf may
+        then be None on the plain fp8 path); drop_l: the adapter's input-dropout entry; ep: ops.gemm's epilogue keywords -- ``aux_out``
+        (even None) asks for the pre-activation beside ``act``, which the fp8 classes cannot write: product -> pre-activation, one more
+        pass applies the GELU.  Returns the adapter's save record (``_lora_bwd`` takes it) or None."""
+        e4m3 = self._site_e4m3(s)
+        if s.lora is not None:
+            return (self._lora_gemm_fp8 if e4m3 else self._lora_gemm)(s, x_bf, out, M, drop_l, save, xq=xq, bias=s.b, **ep)
+        if not e4m3:
+            ops.gemm(x_bf, s.W, out, M, s.N, s.K, bias=s.b, **ep)
+            return None
+        e = self._fp8_weight(s)
+        x8, sx = xq if xq is not None else self._fp8_rows(x_bf, M, s.K)
+        if 'aux_out' in ep:
+            act, pre = ep.pop('act'), ep.pop('aux_out')
+            tgt = pre if pre is not None else out
+            ops.gemm_fp8(x8, sx, e.w8, e.sw, tgt, M, s.N, _f8pad(s.K), bias=s.b, **ep)
+            ops.gelu_fwd(tgt, out, erf=(act == ops.ACT_GELU_ERF))
+        else:
+            ops.gemm_fp8(x8, sx, e.w8, e.sw, out, M, s.N, _f8pad(s.K), bias=s.b, **ep)
+        return None
+
+    def _site_bwd(self, s, sv_l, dY, x_bf, M: int, drop_l=None, dq=None, dx_out=None, dy_sumsq=None, act=0, aux_in=None, **dx_kw):
+        """Backward of ``_site_fwd``: dY bf16 [M, N] (dq = (dy8, scale): its e4m3 image from a fused producer), x_bf the saved input,
+        sv_l the adapter's save record.  Accumulates db / dW (trainable ones only) and the adapter's gradients, then dx [M, K] = dY . W:
+        the plain and fp8 paths fill ``dx_out`` (dx_kw: the dx GEMM's keywords, e.g. residual / accumulate) and return it, the LoRA path
+        returns its own fp32 tensor.  act / aux_in: the activation derivative behind dx (the bf16 GEMM's epilogue; one more pass over the
+        fp32 dx on the other paths) -- dx_out then holds the result on every path.
+        dy_sumsq (1-float device tensor): dY is an UN-normalised gradient whose normaliser 1 / (sqrt(dy_sumsq) + 1e-6) the three
+        consumers apply themselves (ops.gemm alpha_sumsq): no pass over dY exists just to rescale it."""
+        a, N, K = self.arena, s.N, s.K
+        gW = s.G if all(a.trainable(n) for n in s.names) else None
+        gb = s.gb if s.gb is not None and all(a.trainable(n) for n in s.bnames) else None
+        e4m3 = self._site_e4m3(s)
+        if s.lora is not None:
+            assert act in (0, ops.ACT_DGELU, ops.ACT_DGELU_ERF), act
+            dx32 = self._lora_bwd(s, sv_l, dY, x_bf, gW, gb, M, drop_l, e4m3, dq)
+        else:
+            if gb is not None:
+                ops.colsum(dY, gb, M, N, accumulate=True, alpha_sumsq=dy_sumsq)
+            if gW is not None:
+                ops.gemm(dY, x_bf, gW, N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True, alpha_sumsq=dy_sumsq)
+            if dx_out is None:
+                return None
+            if not e4m3:
+                return ops.gemm(dY, s.W, dx_out, M, K, N, b_kmajor=True, alpha_sumsq=dy_sumsq, act=act, aux_in=aux_in, **dx_kw)
+            assert act in (0, ops.ACT_DGELU, ops.ACT_DGELU_ERF), act          # (a GELU derivative is the only epilogue restated below)
+            dx32 = self._empty(M, K) if act else dx_out
+            e = self._fp8_weight(s)
+            d8, sd = dq if dq is not None else self._fp8_rows(dY, M, N)
+            ops.gemm_fp8(d8, sd, e.wt8, e.swt, dx32, M, K, _f8pad(N), **dx_kw)
+        return ops.dgelu_mul(dx32, aux_in, dx_out, erf=(act == ops.ACT_DGELU_ERF)) if act else dx32
 
     def _lora_site(self, l: int, site: str):
         lo = getattr(self.dec, 'lora', None)
@@ -60,13 +205,11 @@ class LoraAdapters:
             panel[row0:row0 + nrows, col0:col0 + B.shape[1]].copy_(B * ls.scale)
         return panel
 
-    def _lora_gemm(self, ls, x, W, out, M: int, drop_l, save: bool, **epilogue):
-        """out = epilogue([x | u] . [W | s B | 0]^T), u = dropout(x) . A^T.  x bf16 [M, K] contiguous, W bf16 [N, K].  Returns what
-        the backward needs (u and s B, both [*, LPAD] bf16) when save."""
-        K, N = ls.K, ls.N
-        if getattr(ls, 'wnames', None) is not None and self._fp8_on(ls.wnames) and epilogue.get('act', 0) in (0, ops.ACT_GELU, ops.ACT_GELU_ERF):
-            return self._lora_gemm_fp8(ls, x, W, out, M, drop_l, save, **epilogue)
-        epilogue.pop('xq', None)
+    def _lora_gemm(self, st, x, out, M: int, drop_l, save: bool, xq=None, **epilogue):
+        """out = epilogue([x | u] . [W | s B | 0]^T), u = dropout(x) . A^T.  st: the adapted site (``_site``), x bf16 [M, K] contiguous.
+        Returns what the backward needs (u and s B, both [*, LPAD] bf16) when save.  xq (an e4m3 image of x from a fused producer) is
+        accepted for ``_site_fwd``'s uniform call and ignored on purpose: this form reads bf16 operands only."""
+        ls, W, K, N = st.lora, st.W, st.K, st.N
         xcat = torch.empty(M, K + LPAD, dtype=BF16, device=x.device)
         xd = torch.empty(M, K, dtype=BF16, device=x.device) if drop_l is not None else None
         ops.lora_stage(x, xcat, xd, M, K, drop_l)                    # one pass: x into the concatenated operand + its masked copy
@@ -80,15 +223,15 @@ class LoraAdapters:
         # (the masked copy of x is kept for dA = du^T dropout(x): re-making it in backward cost two more passes over [M, K])
         return SimpleNamespace(u=u, sB=wcat[:, K:].contiguous(), xd=xd) if save else None
 
-    def _lora_gemm_fp8(self, ls, x, W, out, M: int, drop_l, save: bool, bias=None, residual=None, act=0, aux_out=None, xq=None, **_):
-        """The same layer with its FROZEN base weight on fp8 operands (I2T_FP8=1; engine_llama._fp8_*): the base product runs
+    def _lora_gemm_fp8(self, st, x, out, M: int, drop_l, save: bool, bias=None, residual=None, act=0, aux_out=None, xq=None):
+        """The same layer with its FROZEN base weight on fp8 operands (I2T_FP8=1; ``_fp8_weight``): the base product runs
         at the fp8 MFMA rate, so the adapter leaves the K panel -- out = fp8(x) . fp8(W)^T (+ bias) (+ residual) + u . (s B)^T, the
         rank-128 product added by a second, thin GEMM (in place on an fp32 output; ahead of the base GEMM, as its fp32 residual, when
         the output is bf16).  No K-concatenated copies of x and W; one quantisation pass over x instead."""
-        K, N = ls.K, ls.N
+        ls, K, N = st.lora, st.K, st.N
         if act:          # GELU behind the layer (Falcon's dense_h_to_4h): the product goes to the pre-activation buffer, one more pass applies it
             pre = aux_out if aux_out is not None else torch.empty(M, N, dtype=BF16, device=x.device)
-            sv = self._lora_gemm_fp8(ls, x, W, pre, M, drop_l, save, bias=bias, residual=residual, xq=xq)
+            sv = self._lora_gemm_fp8(st, x, pre, M, drop_l, save, bias=bias, residual=residual, xq=xq)
             ops.gelu_fwd(pre, out, erf=(act == ops.ACT_GELU_ERF))
             return sv
         xd = None
@@ -98,7 +241,7 @@ class LoraAdapters:
         u = torch.empty(M, LPAD, dtype=BF16, device=x.device)
         self._rank_gemm(xd if xd is not None else x, ls.A, u, M, K)
         panel = self._lora_panel(ls)
-        e = self._fp8_weight(ls.wnames, W)
+        e = self._fp8_weight(st)
         x8, sx = xq if xq is not None else self._fp8_rows(x, M, K)          # (xq: the producer of x emitted the e4m3 row beside the bf16 one)
         if out.dtype == F32:
             ops.gemm_fp8(x8, sx, e.w8, e.sw, out, M, N, x8.shape[1], bias=bias, residual=residual)      # (K' = the zero-padded row length)
@@ -109,10 +252,10 @@ class LoraAdapters:
             ops.gemm_fp8(x8, sx, e.w8, e.sw, out, M, N, x8.shape[1], bias=bias, residual=tmp)
         return SimpleNamespace(u=u, sB=panel, xd=xd) if save else None
 
-    def _lora_bwd(self, ls, sv_l, dY, x, W, gW, gb, M: int, drop_l, dq=None):
+    def _lora_bwd(self, st, sv_l, dY, x, gW, gb, M: int, drop_l, e4m3: bool = False, dq=None):
         """dY bf16 [M, N]: gradient w.r.t. the adapted linear's pre-epilogue output.  gW / gb: gradient views of the base weight /
         bias or None (frozen).  Accumulates every parameter gradient; returns dx fp32 [M, K] = dY . W + dropout(du . A)."""
-        K, N = ls.K, ls.N
+        ls, W, K, N = st.lora, st.W, st.K, st.N
         if gb is not None:
             ops.colsum(dY, gb, M, N, accumulate=True)
         if gW is not None:
@@ -126,8 +269,8 @@ class LoraAdapters:
         xd = sv_l.xd if sv_l.xd is not None else x
         ops.gemm(du, xd, ls.GA, LPAD, K, M, a_kmajor=True, b_kmajor=True, accumulate=True)
         dx = torch.empty(M, K, dtype=F32, device=dY.device)
-        if getattr(ls, 'wnames', None) is not None and self._fp8_on(ls.wnames):      # frozen base weight: dx on fp8 operands too
-            e = self._fp8_weight(ls.wnames, W)
+        if e4m3:      # frozen base weight: dx on fp8 operands too
+            e = self._fp8_weight(st)
             d8, sd = dq if dq is not None else self._fp8_rows(dY, M, N)
             ops.gemm_fp8(d8, sd, e.wt8, e.swt, dx, M, K, d8.shape[1])
         else:

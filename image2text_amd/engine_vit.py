@@ -62,30 +62,23 @@ class ViTEncoder:
         return {n for n in self.arena.entries if n.startswith(f'{self.ep}model.')}
 
     # ------------------------------------------------------------------------------------------------ backbone
-    def _vit_lin(self, x_bf, W, names, out, M, N, K, **kw):
-        """A backbone GEMM: e4m3 operands only under the backbone's own switch (``fp8_vit``, I2T_FP8_VIT=1) and only for frozen weights;
-        the decoder's switch (``fp8``: I2T_FP8 / a load_in_4bit request) never reaches the encoder."""
-        if self.fp8_vit and all(not self.arena.trainable(n) for n in ([names] if isinstance(names, str) else names)):
-            fp8, self.fp8 = self.fp8, True
-            try:
-                return self._lin(x_bf, W, names, out, M, N, K, **kw)
-            finally:
-                self.fp8 = fp8
-        return ops.gemm(x_bf, W, out, M, N, K, **kw)
+    def _vit_site(self, name: str, N: int, K: int, bias: str):
+        """A backbone linear: e4m3 operands only under the backbone's own switch (``fp8_vit``, I2T_FP8_VIT=1) and only for frozen weights
+        (engine_lora.linear_path); the decoder's switch (``fp8``: I2T_FP8 / a load_in_4bit request) never reaches the encoder."""
+        return self._site(name, N, K, bias, switch='fp8_vit')
 
     def _vit_block_fwd(self, q: str, x, B, T, d, H, ff, save: bool):
         a, M = self.arena, B * T
         ln1, m1, r1 = self._empty(M, d, dtype=BF16), self._empty(M), self._empty(M)
         ops.layernorm_fwd(x, a.P(q + 'ln_1.weight'), a.P(q + 'ln_1.bias'), ln1, m1, r1, M, d, eps=VIT_EPS)
         qkv = self._empty(M, 3 * d, dtype=BF16)
-        # (self._vit_lin: e4m3 operands when the backbone is frozen and I2T_FP8_VIT=1 -- forward-only GEMMs of weights that never change, DESIGN 4h)
-        lin = (lambda x_, name, out, N_, K_, **kw: self._vit_lin(x_, a.W(name), name, out, M, N_, K_, **kw))
-        lin(ln1, q + 'self_attention.in_proj_weight', qkv, 3 * d, d, bias=a.P(q + 'self_attention.in_proj_bias'))
+        # (self._vit_site: e4m3 operands when the backbone is frozen and I2T_FP8_VIT=1 -- forward-only GEMMs of weights that never change, DESIGN 4h)
+        self._site_fwd(self._vit_site(q + 'self_attention.in_proj_weight', 3 * d, d, q + 'self_attention.in_proj_bias'), ln1, qkv, M)
         q3 = qkv.view(B, T, 3 * d)
         ao, lse = self._empty(B, T, d, dtype=BF16), self._empty(H * M)
         ops.attention_fwd(q3[..., :d], q3[..., d:2 * d], q3[..., 2 * d:], ao, lse, B, H, T, T, False)
         x1 = self._empty(M, d)
-        lin(ao.view(M, d), q + 'self_attention.out_proj.weight', x1, d, d, bias=a.P(q + 'self_attention.out_proj.bias'), residual=x)
+        self._site_fwd(self._vit_site(q + 'self_attention.out_proj.weight', d, d, q + 'self_attention.out_proj.bias'), ao.view(M, d), x1, M, residual=x)
         ln2, m2, r2 = self._empty(M, d, dtype=BF16), self._empty(M), self._empty(M)
         ops.layernorm_fwd(x1, a.P(q + 'ln_2.weight'), a.P(q + 'ln_2.bias'), ln2, m2, r2, M, d, eps=VIT_EPS)
         h = self._empty(M, ff, dtype=BF16)
@@ -93,9 +86,9 @@ class ViTEncoder:
         if save:
             ops.gemm(ln2, a.W(q + 'mlp.0.weight'), h, M, ff, d, bias=a.P(q + 'mlp.0.bias'), act=ops.ACT_GELU_ERF, aux_out=pre)
         else:
-            lin(ln2, q + 'mlp.0.weight', h, ff, d, bias=a.P(q + 'mlp.0.bias'), act=ops.ACT_GELU_ERF)
+            self._site_fwd(self._vit_site(q + 'mlp.0.weight', ff, d, q + 'mlp.0.bias'), ln2, h, M, act=ops.ACT_GELU_ERF)
         x2 = self._empty(M, d)
-        lin(h, q + 'mlp.3.weight', x2, d, ff, bias=a.P(q + 'mlp.3.bias'), residual=x1)
+        self._site_fwd(self._vit_site(q + 'mlp.3.weight', d, ff, q + 'mlp.3.bias'), h, x2, M, residual=x1)
         sv = SimpleNamespace(x=x, ln1=ln1, m1=m1, r1=r1, qkv=qkv, ao=ao, lse=lse, x1=x1, ln2=ln2, m2=m2, r2=r2, h=h, pre=pre) if save else None
         return x2, sv
 
@@ -129,7 +122,7 @@ class ViTEncoder:
         patches = self._empty(B * e.P2, K0, dtype=BF16)
         ops.patchify(images, patches, B, 3, e.img, e.img, e.p)
         proj = self._empty(B * e.P2, d)
-        self._vit_lin(patches, a.W(m + 'conv_proj.weight').view(d, K0), m + 'conv_proj.weight', proj, B * e.P2, d, K0, bias=a.P(m + 'conv_proj.bias'))
+        self._site_fwd(self._vit_site(m + 'conv_proj.weight', d, K0, m + 'conv_proj.bias'), patches, proj, B * e.P2)      # (the [d, 3, p, p] kernel: rows of K0)
         x = self._empty(B * T, d)
         ops.vit_tokens(proj, a.P(m + 'class_token'), a.P(m + 'encoder.pos_embedding'), x, B, T, d)
         saves = []

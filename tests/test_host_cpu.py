@@ -578,6 +578,43 @@ def test_falcon_huggingface_decoder_plugin(tmp_path, monkeypatch):
         Decoder.from_config(_hf_decoder_config(name=name, vocab_size=vocab))
 
 
+def test_linear_site_path_decision():
+    """engine_lora.linear_path: how a linear site runs, as a pure function of (adapter present, trainable, governing switch and the two
+    switches' values, producer may fuse), and engine_lora.fuse_guard, the width guards behind that last input.  The expected outcome
+    of every combination is written out: (adapter, frozen weight AND its own switch on, fuse) -> (path, rows the producer emits)."""
+    import itertools
+    from image2text_amd.engine_lora import fuse_guard, linear_path
+    table = {(False, False, False): ('bf16', 'bf16'), (False, False, True): ('bf16', 'bf16'),
+             (False, True, False): ('fp8', 'bf16'), (False, True, True): ('fp8', 'e4m3'),
+             (True, False, False): ('lora', 'bf16'), (True, False, True): ('lora', 'bf16'),
+             (True, True, False): ('lora_fp8', 'bf16'), (True, True, True): ('lora_fp8', 'both')}
+    # which (switch, fp8, fp8_vit) have the site's OWN switch on: the decoder's never counts for a backbone site, nor the reverse
+    own_on = {('fp8', True, False), ('fp8', True, True), ('fp8_vit', False, True), ('fp8_vit', True, True)}
+    n = 0
+    for adapter, trainable, switch, fp8, fp8_vit, fuse in itertools.product((False, True), (False, True), ('fp8', 'fp8_vit', None),
+                                                                            (False, True), (False, True), (False, True)):
+        e4m3 = (switch, fp8, fp8_vit) in own_on and not trainable
+        assert linear_path(adapter, trainable, switch, fp8, fp8_vit, fuse) == table[(adapter, e4m3, fuse)], (adapter, trainable, switch, fp8, fp8_vit, fuse)
+        n += 1
+    assert n == 2 * 2 * 3 * 2 * 2 * 2
+    both = (True, True)
+    # a trainable weight never takes fp8, whatever is switched on, and its producer writes the bf16 row only
+    assert all(linear_path(ad, True, sw, *both, fuse=True) == ('lora' if ad else 'bf16', 'bf16') for ad in (False, True) for sw in ('fp8', 'fp8_vit', None))
+    # the backbone's switch never enables a decoder site, and the reverse; a site without a switch never takes fp8
+    assert linear_path(False, False, 'fp8', False, True, True) == ('bf16', 'bf16')
+    assert linear_path(False, False, 'fp8_vit', True, False, True) == ('bf16', 'bf16')
+    assert linear_path(False, False, None, True, True, True) == ('bf16', 'bf16')
+    assert linear_path(False, False, 'fp8_vit', False, True) == ('fp8', 'bf16') and linear_path(False, False, 'fp8', True, False, True) == ('fp8', 'e4m3')
+    # a LoRA site on a frozen fp8 base asks the producer for both rows; outside the fuse guards for the bf16 row alone (it quantises itself)
+    assert linear_path(True, False, 'fp8', True, False, True) == ('lora_fp8', 'both')
+    assert linear_path(True, False, 'fp8', True, False, False) == ('lora_fp8', 'bf16')
+    # the guards: model width <= 8192 and MLP width <= 12288, only with fp8_fuse on; the backward's SwiGLU producer passes ff alone
+    assert fuse_guard(True, 8192, 12288) and fuse_guard(True, ff=12288) and fuse_guard(True, 4096, 11008)
+    assert not fuse_guard(True, 8193, 12288) and not fuse_guard(True, 8192, 12289) and not fuse_guard(True, ff=12289)
+    assert not fuse_guard(False, 256, 512) and not fuse_guard(False)
+    assert linear_path(False, False, 'fp8', True, False, fuse_guard(True, 8192, 12289)) == ('fp8', 'bf16')
+
+
 def test_llama_qwen2_huggingface_decoder_lora(tmp_path, monkeypatch):
     """lora_spec on the Llama-2 / Qwen2 plugins (reference gpu/llama2-13b.yaml:35-39; decoder.py:133-134 -> models/utils.py:46-65): adapters
     on the block linears peft's suffix rule selects, the adapters of a fused projection stacked in one lora_A parameter, everything else
