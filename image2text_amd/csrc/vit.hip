@@ -230,10 +230,14 @@ __global__ __launch_bounds__(256) void peer_lookup_bwd_kernel(const float* __res
                                                               const int* __restrict__ sv_unit, const int* __restrict__ sv_lr,
                                                               const float* __restrict__ sv_score, const float* __restrict__ sv_dot,
                                                               float* __restrict__ dS, bf16_t* __restrict__ dip, float* __restrict__ g_in,
-                                                              float* __restrict__ g_out, int nh, int nq, int k, int din, int dout_w, int M) {
-    __shared__ float dfw[PEER_MAXK], dt[PEER_MAXK];
+                                                              float* __restrict__ g_out, int nh, int nq, int k, int din, int dout_w, int M,
+                                                              int det) {
+    __shared__ float dfw[PEER_MAXK], dt[PEER_MAXK], fwv[PEER_MAXK];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // (deterministic mode launches ONE workgroup that walks the rows in order: the table gradients are then summed in a fixed order)
+    // (deterministic mode launches ONE workgroup that walks the rows in order: the table gradients are then summed in a fixed order.
+    // unit = l k + r lets two candidates j of one (row, head) name the same unit, and candidate j belongs to wave j % 4, so there the
+    // g_out adds of the first phase would race between waves: det moves them to a phase in which a thread owns its columns and
+    // walks j in order, as the g_in phase does)
     for (int row = blockIdx.x; row < M; row += gridDim.x) {
     const float* g = dout + (size_t)row * dout_w;
     for (int h = 0; h < nh; ++h) {
@@ -248,15 +252,25 @@ __global__ __launch_bounds__(256) void peer_lookup_bwd_kernel(const float* __res
                 const u32x2 v = *reinterpret_cast<const u32x2*>(e + c);
                 const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c);
                 acc += bf16lo(v[0]) * gg[0] + bf16hi(v[0]) * gg[1] + bf16lo(v[1]) * gg[2] + bf16hi(v[1]) * gg[3];
-                if (g_out) {
+                if (g_out && !det) {
                     float* go = g_out + (size_t)u * dout_w + c;
                     atomicAdd(go, fwj * gg[0]); atomicAdd(go + 1, fwj * gg[1]); atomicAdd(go + 2, fwj * gg[2]); atomicAdd(go + 3, fwj * gg[3]);
                 }
             }
             acc = wave_sum(acc);
-            if (lane == 0) dfw[j] = acc;
+            if (lane == 0) { dfw[j] = acc; fwv[j] = fwj; }
         }
         __syncthreads();
+        if (g_out && det) {
+            for (int c = tid * 4; c < dout_w; c += 1024) {
+                const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c);
+                for (int j = 0; j < k; ++j) {
+                    float* go = g_out + (size_t)sv_unit[base + j] * dout_w + c;
+                    const float fwj = fwv[j];
+                    atomicAdd(go, fwj * gg[0]); atomicAdd(go + 1, fwj * gg[1]); atomicAdd(go + 2, fwj * gg[2]); atomicAdd(go + 3, fwj * gg[3]);
+                }
+            }
+        }
         if (tid == 0) {                                         // softmax / GELU backward over the k candidates, scatter into dS
             float dot_sd = 0.f, ds[PEER_MAXK];
             for (int j = 0; j < k; ++j) {
@@ -605,11 +619,14 @@ extern "C" int i2t_peer_lookup_bwd(void* stream, const float* dout, const void* 
                                    const int* sv_unit, const int* sv_lr, const float* sv_score, const float* sv_dot, float* dscores,
                                    void* dinp_proj, float* g_emb_in, float* g_emb_out, int M, int nhead, int nq, int topk, int din, int dout_w) {
     I2T_REQUIRE(dout && inp_proj && emb_in && emb_out && sv_unit && sv_lr && sv_score && sv_dot && dscores && dinp_proj && M > 0 && nhead > 0 &&
-                    nq <= PEER_MAXQ && topk >= 1 && topk <= PEER_MAXK && din % 8 == 0 && dout_w % 4 == 0 && ALIGNED16(dout) && ALIGNED16(emb_out),
-                "i2t_peer_lookup_bwd: bad args");
-    hipLaunchKernelGGL(peer_lookup_bwd_kernel, dim3(i2t_det() ? 1 : M), dim3(256), 0, (hipStream_t)stream, dout, (const bf16_t*)inp_proj,
+                    nq >= topk && nq <= PEER_MAXQ && topk >= 1 && topk <= PEER_MAXK && din % 8 == 0 && dout_w % 4 == 0 && dout_w <= 8192 &&
+                    ALIGNED16(dout) && ALIGNED16(inp_proj) && ALIGNED16(emb_in) && ALIGNED16(emb_out) && ALIGNED16(dinp_proj),
+                "i2t_peer_lookup_bwd: bad args (nq=%d <= %d, topk=%d <= min(nq, %d), din=%d %% 8, dout=%d %% 4 and <= 8192, dinp_proj %p 16-byte aligned)",
+                nq, PEER_MAXQ, topk, PEER_MAXK, din, dout_w, dinp_proj);
+    const int det = i2t_det() ? 1 : 0;
+    hipLaunchKernelGGL(peer_lookup_bwd_kernel, dim3(det ? 1 : M), dim3(256), 0, (hipStream_t)stream, dout, (const bf16_t*)inp_proj,
                        (const bf16_t*)emb_in, (const bf16_t*)emb_out, sv_unit, sv_lr, sv_score, sv_dot, dscores, (bf16_t*)dinp_proj, g_emb_in, g_emb_out,
-                       nhead, nq, topk, din, dout_w, M);
+                       nhead, nq, topk, din, dout_w, M, det);
     I2T_CHECK_LAUNCH("i2t_peer_lookup_bwd");
     return I2T_OK;
 }
@@ -634,7 +651,9 @@ extern "C" int i2t_lsh_embed_fwd(void* stream, const float* z, const float* tabl
 
 extern "C" int i2t_lsh_embed_bwd(void* stream, const float* dy, const int* rows, float* g_tables, long slot_stride, const long* tab_off, int B,
                                  int n_cls, int nK, int n_proj, int dout) {
-    I2T_REQUIRE(dy && rows && g_tables && tab_off && B > 0 && n_cls > 0 && nK > 0 && n_proj > 0, "i2t_lsh_embed_bwd: bad args");
+    I2T_REQUIRE(dy && rows && g_tables && tab_off && B > 0 && n_cls > 0 && nK > 0 && n_proj > 0 && nK * n_proj <= 1024 && dout % 4 == 0 &&
+                    slot_stride % 4 == 0,
+                "i2t_lsh_embed_bwd: bad args (nK * n_proj = %d <= 1024, dout=%d %% 4, slot_stride=%ld %% 4)", nK * n_proj, dout, slot_stride);
     hipLaunchKernelGGL(lsh_embed_bwd_kernel, dim3(i2t_det() ? 1 : B * n_cls), dim3(256), 0, (hipStream_t)stream, dy, rows, g_tables, slot_stride,
                        tab_off, n_cls, nK, n_proj, dout, B * n_cls);
     I2T_CHECK_LAUNCH("i2t_lsh_embed_bwd");

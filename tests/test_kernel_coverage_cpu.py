@@ -8,9 +8,8 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# entry point -> why no test calls a wrapper of it directly.  Only: graph capture and communicator calls, ABI / error / workspace /
-# mode queries, and the four PEER / LSH kernels (fixture-backed head tests in tests/test_vit_gpu.py; a faithful fp64 restatement
-# of them is a piece of work of its own).
+# entry point -> why no test calls a wrapper of it directly.  Only: graph capture and communicator calls and ABI / error / workspace /
+# mode queries.
 NO_DIRECT_TEST = {
     'i2t_abi_version': 'query: checked on every load (lib.load) and in tests/test_abi.py',
     'i2t_last_error': 'query: read through lib.last_error by every refusal test',
@@ -27,12 +26,8 @@ NO_DIRECT_TEST = {
     'i2t_comm_init': 'communicator',
     'i2t_comm_allreduce': 'communicator',
     'i2t_comm_destroy': 'communicator',
-    'i2t_peer_lookup_fwd': 'PEER head: fixture-backed in tests/test_vit_gpu.py',
-    'i2t_peer_lookup_bwd': 'PEER head: fixture-backed in tests/test_vit_gpu.py',
-    'i2t_lsh_embed_fwd': 'LSH head: fixture-backed in tests/test_vit_gpu.py',
-    'i2t_lsh_embed_bwd': 'LSH head: fixture-backed in tests/test_vit_gpu.py',
 }
-ALLOWED_PREFIXES = ('i2t_graph_', 'i2t_comm_', 'i2t_peer_lookup_', 'i2t_lsh_embed_')
+ALLOWED_PREFIXES = ('i2t_graph_', 'i2t_comm_')
 ALLOWED_QUERIES = {'i2t_abi_version', 'i2t_last_error', 'i2t_workspace_bytes', 'i2t_deterministic', 'i2t_gemm_reserved_cus',
                    'i2t_moe_gate_bwd_blocks'}
 VARIANT = re.compile(r'_(ex|eps|drop)$')
@@ -100,4 +95,4 @@ def test_the_exemption_table_stays_narrow():
     for entry, reason in NO_DIRECT_TEST.items():
         assert entry in names, f'{entry} is not an entry point any more: drop its row'
         assert reason.strip(), entry
-        assert entry.startswith(ALLOWED_PREFIXES) or entry in ALLOWED_QUERIES, f'{entry}: only capture / communicator calls, queries and the PEER / LSH kernels may go untested'
+        assert entry.startswith(ALLOWED_PREFIXES) or entry in ALLOWED_QUERIES, f'{entry}: only capture / communicator calls and queries may go untested'
