@@ -62,6 +62,7 @@ struct GemmParams {
     int g2_dbg;               // experiment (I2T_G256_DBG): 1 = epilogue without its global stores, 2 = no epilogue at all
     const float* scale_a = nullptr;   // class 9 (fp8 operands, i2t_gemm_fp8): per-row scales of A [M] and of B [N] applied to the accumulators
     const float* scale_b = nullptr;
+    float* colsum_out = nullptr;      // class 13 (split-K dW with the bias gradient as a by-product): colsum_out[m] += sum_k A[k][m] / (sqrt(*alpha_sumsq) + 1e-6)
     int g2_stagger, g2_stagger_groups;   // experiment: start delay (units of s_sleep 127) x (workgroup index within its XCD mod groups)
     // fused cross-attention (epilogue class 8, see xattn_epilogue): queries, outputs and shapes
     const bf16_t* xq; long xq_bs; int xq_rs;      // Q [B, T, >= 64 H] (batch stride used when xcu is null) or packed [rows, >= 64 H]
@@ -1041,7 +1042,7 @@ struct G2Tile {                       // wave-uniform description of one output 
     int m0, n0, t0;                   // t0: first K-tile of this work item's K slice
 };
 
-template <bool A_KMAJOR, bool B_KMAJOR, bool UNSWAP = false, bool XA = false>
+template <bool A_KMAJOR, bool B_KMAJOR, bool UNSWAP = false, bool XA = false, bool CS = false>
 struct G2 {
     static constexpr bool PK = A_KMAJOR && B_KMAJOR;
     static constexpr int FA = A_KMAJOR ? 2 : 1, FB = B_KMAJOR ? 2 : 1;      // LGKM ops per fragment read
@@ -1058,6 +1059,58 @@ struct G2 {
     unsigned step_a, step_b;         // bytes per K-tile
     unsigned lds0;                   // LDS byte address of smem
     G2Tile cur, nxt;                 // the tile being computed and the one whose first units are already being staged
+    // CS: the row sums of the A panel (= the column sums of dY, the bias gradient) as a by-product.  One more MFMA of an A fragment the
+    // wave already holds against an all-ones operand gives the 16 row sums of that fragment.  The four waves of a wave row hold the same
+    // eight A fragments: wave column wc takes fragment wc of either 64-row subtile (two accumulators), and the column tiles of one row
+    // tile share the K-tiles (tile column j takes those with t % tiles_n == j), so every workgroup of the launch pays the same
+    // 1 / tiles_n of one extra MFMA per phase of sixteen and the launch stays balanced.
+    f32x4 cs0, cs1;                  // row sums of rows wr*128 + wc*16 + (lane & 15) and of those 64 rows further on
+    int cs_c, cs_t, cs_j, cs_n;      // K-tile counter mod cs_n = tiles_n: the next tile's and the current one's; this work item's tile column
+    u32x4 cs_ones;                   // eight bf16 1.0
+    __device__ __forceinline__ void cs_begin(const GemmParams& p, int n0) {
+        cs0 = cs1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        cs_ones = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+        asm volatile("" : "+v"(cs_ones));      // kept in registers: re-made from constants next to the MFMA it would be a VALU write the asm below cannot see
+        cs_c = 0; cs_j = n0 >> 8; cs_n = p.tiles_n;
+    }
+    __device__ __forceinline__ void cs_tile() {
+        cs_t = cs_c;
+        cs_c = cs_c + 1 == cs_n ? 0 : cs_c + 1;
+    }
+    // Ones as the A operand: C[i][j] = sum_k fragment[j][k] for every i -- lane j of the first sixteen ends up with row j's sum.
+    // One asm block holds the whole step: skip unless the K-tile is this work item's, pick fragment wc (wave-uniform branches; EXEC is not
+    // touched), accumulate IN PLACE.  Through the builtin, and again with one asm MFMA per compiler-visible branch, hipcc gave the result
+    // fresh registers and copied it back at the join: a VALU read of an MFMA result one instruction old -- a drain of the matrix pipe in
+    // every such phase at best, and from asm without the wait states that read needs.  The leading s_nop covers a VALU write of an operand
+    // just ahead of the block; the accumulator is next touched a K-tile later, and the kernel pads the result latency before its epilogue
+    // reads cs0 / cs1.
+    template <int SUBA, int KS>
+    __device__ __forceinline__ void cs_mma(const bf16x8 (&ra)[8]) {
+        asm volatile("s_cmp_lg_u32 %[t], %[j]\n\t"
+                     "s_cbranch_scc1 .Lcs_end_%=\n\t"
+                     "s_nop 1\n\t"
+                     "s_cmp_lt_u32 %[wc], 2\n\t"
+                     "s_cbranch_scc0 .Lcs_hi_%=\n\t"
+                     "s_cmp_eq_u32 %[wc], 0\n\t"
+                     "s_cbranch_scc0 .Lcs_1_%=\n\t"
+                     "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[f0], %[c]\n\t"
+                     "s_branch .Lcs_end_%=\n"
+                     ".Lcs_1_%=:\n\t"
+                     "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[f1], %[c]\n\t"
+                     "s_branch .Lcs_end_%=\n"
+                     ".Lcs_hi_%=:\n\t"
+                     "s_cmp_eq_u32 %[wc], 2\n\t"
+                     "s_cbranch_scc0 .Lcs_3_%=\n\t"
+                     "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[f2], %[c]\n\t"
+                     "s_branch .Lcs_end_%=\n"
+                     ".Lcs_3_%=:\n\t"
+                     "v_mfma_f32_16x16x32_bf16 %[c], %[o], %[f3], %[c]\n"
+                     ".Lcs_end_%=:"
+                     : [c] "+v"(SUBA ? cs1 : cs0)
+                     : [o] "v"(cs_ones), [f0] "v"(ra[KS * 4 + 0]), [f1] "v"(ra[KS * 4 + 1]), [f2] "v"(ra[KS * 4 + 2]), [f3] "v"(ra[KS * 4 + 3]),
+                       [t] "s"(cs_t), [j] "s"(cs_j), [wc] "s"(wc)
+                     : "scc");
+    }
 
     __device__ __forceinline__ static G2Tile tile_desc(const GemmParams& p, int idx, int ntiles) {
         G2Tile d;
@@ -1216,6 +1269,7 @@ struct G2 {
                     (UNSWAP || (XA && SUBA == 0)) ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra[KS * 4 + i], rb[KS * 2 + j], acc[SUBA * 4 + i][SUBB * 2 + j], 0, 0, 0)
                            : __builtin_amdgcn_mfma_f32_16x16x32_bf16(rb[KS * 2 + j], ra[KS * 4 + i], acc[SUBA * 4 + i][SUBB * 2 + j], 0, 0, 0);
         if (G2_SETPRIO) __builtin_amdgcn_s_setprio(0);
+        if constexpr (CS && KS == SUBB) cs_mma<SUBA, KS>(ra);      // each (subtile, k half) of a K-tile meets KS == SUBB in exactly one phase
     }
     template <int LG>
     __device__ __forceinline__ void fence() {     // my part of unit P+2 landed, my reads of phase P-2 retired; then everyone's
@@ -1229,6 +1283,7 @@ struct G2 {
     template <bool LAST>
     __device__ __forceinline__ void two_tiles(int t, f32x4 (&acc)[8][4], bf16x8 (&ra)[8], bf16x8 (&rb0)[4], bf16x8 (&rb1)[4]) {
         // ---- even tile: B-first = sub 0 (rb0), B-second = sub 1 (rb1)
+        if constexpr (CS) cs_tile();
         fence<LG3>();  read_a<0, 1>(ra);  read_b<2>(rb1);  stage<1, 2>(t + 1);
         mma<0, 0, 0>(acc, ra, rb0);  mma<0, 0, 1>(acc, ra, rb0);
         fence<LG0>();  stage<1, 3>(t + 1);
@@ -1238,6 +1293,7 @@ struct G2 {
         fence<LG2>();  read_b<5>(rb1);  stage<0, 1>(t + 2);
         mma<1, 0, 0>(acc, ra, rb0);  read_a<4, 0>(ra);  mma<1, 0, 1>(acc, ra, rb0);
         // ---- odd tile: B-first = sub 1 (rb1), B-second = sub 0 (rb0)
+        if constexpr (CS) cs_tile();
         fence<LG3>();  read_a<4, 1>(ra);  read_b<6>(rb0);  stage<0, 2>(t + 2);
         mma<0, 1, 0>(acc, ra, rb1);  mma<0, 1, 1>(acc, ra, rb1);
         fence<LG0>();  stage<0, 3>(t + 2);
@@ -1395,7 +1451,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         const int k = ((bid >> 3) % p.g2_stagger_groups) * p.g2_stagger;
         for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
     }
-    G2<A_KMAJOR, B_KMAJOR, EPI == 6, EPI == 8> g;
+    G2<A_KMAJOR, B_KMAJOR, EPI == 6 || EPI == 13, EPI == 8, EPI == 13> g;
     g.init(p, smem, tid);
     g.cur = g.tile_desc(p, first, ntiles);
     g.nxt = g.tile_desc(p, first + G, ntiles);
@@ -1445,6 +1501,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (EPI == 13) g.cs_begin(p, g.cur.n0);
         for (int t = 0; t < g.nk - 2; t += 2) g.template two_tiles<false>(t, acc, ra, rb0, rb1);
         g.template two_tiles<true>(g.nk - 2, acc, ra, rb0, rb1);
         const int m0 = g.cur.m0, n0 = g.cur.n0;
@@ -1458,7 +1515,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
             top2_epilogue(*epilogue_params(), acc, m0 + g.wr * 128, n0 + g.wc * 64, lane_e);
-        } else if constexpr (EPI == 6) {        // split-K partial: fp32 atomics, one wave-instruction = 4 rows x 64 contiguous bytes
+        } else if constexpr (EPI == 6 || EPI == 13) {        // split-K partial: fp32 atomics, one wave-instruction = 4 rows x 64 contiguous bytes
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
             float* C = reinterpret_cast<float*>(p.C);
@@ -1473,6 +1530,13 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
                         const int m = mb + i * 16 + r, n = n_ + j * 16;
                         if (m < p.M && n < p.N && !(p.g2_dbg & 2)) atomicAdd(C + (size_t)m * p.ldc + n, acc[i][j][r] * alpha);
                     }
+            if constexpr (EPI == 13) {          // this item's share of the A panel's row sums: 2 x 16 rows per wave, one atomic each
+                asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(g.cs0), "+v"(g.cs1));      // (the last ones-MFMA's result: issued from asm, see cs_mma)
+                const float norm = p.alpha_sumsq ? 1.0f / (sqrtf(*p.alpha_sumsq) + 1e-6f) : 1.0f;      // (as colsum_kernel: the normaliser, not alpha)
+                const int m = m0 + g.wr * 128 + g.wc * 16 + lane_e;
+                if (lane_e < 16 && m < p.M) atomicAdd(p.colsum_out + m, g.cs0[0] * norm);
+                if (lane_e < 16 && m + 64 < p.M) atomicAdd(p.colsum_out + m + 64, g.cs1[0] * norm);
+            }
         } else {
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
@@ -1917,7 +1981,11 @@ namespace {
 // dW = A^T . B accumulated into an fp32 C (both operands k-major): K slices spread over the CUs when the output has too
 // few 256^2 tiles, partial tiles combined with float atomics (C already holds the value to accumulate onto); with enough
 // tiles (the tied lm_head / embedding gradient) one slice and a plain read-add-write epilogue.
-bool launch_g256_dw(hipStream_t s, GemmParams p) {
+void launch_colsum(hipStream_t s, const bf16_t* X, int ld, int M, int N, float* out, const float* alpha_sumsq);
+
+// p.colsum_out (or null): the row sums of the A panel are added to it as well -- inside the split-K kernel (class 13) unless the
+// caller set fold_colsum to false, by a column-sum launch of their own next to the one-slice form.
+bool launch_g256_dw(hipStream_t s, GemmParams p, bool fold_colsum = true) {
     const int n_cu = g256_cus();
     p.tiles_m = (p.M + 255) / 256; p.tiles_n = (p.N + 255) / 256;
     const int tiles = p.tiles_m * p.tiles_n, nk_all = (p.K + 63) >> 6;
@@ -1926,6 +1994,7 @@ bool launch_g256_dw(hipStream_t s, GemmParams p) {
         // one tile per workgroup on the persistent kernel still beats the 128^2 fallback it used to take, 711 TF)
         if (g256_epilogue_class(p) != 5) return false;
         p.g2_splits = 1; p.g2_nk = (nk_all + 1) & ~1;
+        if (p.colsum_out) launch_colsum(s, p.A, p.lda, p.K, p.M, p.colsum_out, p.alpha_sumsq);
         hipLaunchKernelGGL((gemm256_kernel<true, true, 5>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, s, p);
         return true;
     }
@@ -1937,7 +2006,12 @@ bool launch_g256_dw(hipStream_t s, GemmParams p) {
     if (splits < 2) return false;
     p.g2_splits = splits; p.g2_nk = per;
     const int items = tiles * splits;
-    hipLaunchKernelGGL((gemm256_kernel<true, true, 6>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
+    if (p.colsum_out && !fold_colsum) {
+        launch_colsum(s, p.A, p.lda, p.K, p.M, p.colsum_out, p.alpha_sumsq);
+        p.colsum_out = nullptr;
+    }
+    if (p.colsum_out) hipLaunchKernelGGL((gemm256_kernel<true, true, 13>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
+    else hipLaunchKernelGGL((gemm256_kernel<true, true, 6>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
     return true;
 }
 
@@ -1986,6 +2060,15 @@ __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ 
         const int n = blockIdx.x * 512 + c;
         if (n < N) atomicAdd(out + n, (part[0][c] + part[1][c] + part[2][c] + part[3][c]) * (alpha_sumsq ? 1.0f / (sqrtf(*alpha_sumsq) + 1e-6f) : 1.0f));
     }
+}
+
+void launch_colsum(hipStream_t s, const bf16_t* X, int ld, int M, int N, float* out, const float* alpha_sumsq) {
+    const int col_blocks = (N + 511) / 512;
+    int splits = (M + 63) / 64;                       // >= 64 rows per workgroup
+    const int want = 512 / col_blocks;                // ~2 workgroups per CU overall
+    if (splits > want) splits = want;
+    if (splits < 1 || i2t_det()) splits = 1;           // (deterministic mode: one workgroup per column block = one add per column)
+    hipLaunchKernelGGL(colsum_kernel, dim3(col_blocks, splits), dim3(256), 0, s, X, ld, M, N, out, alpha_sumsq);
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -2099,11 +2182,35 @@ extern "C" int i2t_gemm_bf16(void* stream, const void* A, int lda, int a_kmajor,
                             ld_aux_out, residual, ldr, accumulate, drop_mode, drop_key, drop_thr, drop_scale, nullptr);
 }
 
+static int gemm_bf16_impl(void* stream, const void* A, int lda, int a_kmajor, const void* B, int ldb,
+                          int b_kmajor, void* C, int ldc, int c_is_f32, int M, int N, int K, float alpha,
+                          const float* bias, int act, const void* aux_in, int ld_aux_in, void* aux_out,
+                          int ld_aux_out, const float* residual, int ldr, int accumulate, int drop_mode,
+                          unsigned drop_key, unsigned drop_thr, float drop_scale, const float* alpha_sumsq, float* colsum_out);
+
 extern "C" int i2t_gemm_bf16_ex(void* stream, const void* A, int lda, int a_kmajor, const void* B, int ldb,
                                 int b_kmajor, void* C, int ldc, int c_is_f32, int M, int N, int K, float alpha,
                                 const float* bias, int act, const void* aux_in, int ld_aux_in, void* aux_out,
                                 int ld_aux_out, const float* residual, int ldr, int accumulate, int drop_mode,
                                 unsigned drop_key, unsigned drop_thr, float drop_scale, const float* alpha_sumsq) {
+    return gemm_bf16_impl(stream, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, c_is_f32, M, N, K, alpha, bias, act, aux_in, ld_aux_in, aux_out,
+                          ld_aux_out, residual, ldr, accumulate, drop_mode, drop_key, drop_thr, drop_scale, alpha_sumsq, nullptr);
+}
+
+extern "C" int i2t_gemm_dw_colsum_bf16(void* stream, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K,
+                                       float alpha, const float* alpha_sumsq, float* colsum_out) {
+    I2T_REQUIRE(((uintptr_t)colsum_out & 3) == 0, "i2t_gemm_dw_colsum_bf16: colsum_out misaligned");
+    return gemm_bf16_impl(stream, A, lda, 1, B, ldb, 1, C, ldc, 1, M, N, K, alpha, nullptr, I2T_ACT_NONE, nullptr, 0, nullptr, 0, nullptr, 0, 1, 0,
+                          0u, 0u, 1.0f, alpha_sumsq, colsum_out);
+}
+
+// colsum_out (i2t_gemm_dw_colsum_bf16 only: both operands k-major, accumulate, plain epilogue): the A panel's row sums, folded into the
+// split-K dW kernel where the call takes it, a colsum_kernel launch ahead of every other route.
+static int gemm_bf16_impl(void* stream, const void* A, int lda, int a_kmajor, const void* B, int ldb,
+                          int b_kmajor, void* C, int ldc, int c_is_f32, int M, int N, int K, float alpha,
+                          const float* bias, int act, const void* aux_in, int ld_aux_in, void* aux_out,
+                          int ld_aux_out, const float* residual, int ldr, int accumulate, int drop_mode,
+                          unsigned drop_key, unsigned drop_thr, float drop_scale, const float* alpha_sumsq, float* colsum_out) {
     I2T_REQUIRE(A && B && C, "i2t_gemm_bf16: null operand");
     I2T_REQUIRE(M > 0 && N > 0 && K > 0, "i2t_gemm_bf16: empty problem M=%d N=%d K=%d", M, N, K);
     // K need not be a multiple of 8, but an operand whose reduction index is contiguous is then read up to the
@@ -2160,6 +2267,9 @@ extern "C" int i2t_gemm_bf16_ex(void* stream, const void* A, int lda, int a_kmaj
     }
     static const char* sel = getenv("I2T_GEMM");
     static const bool no_g256 = sel && !strcmp(sel, "v1");
+    // I2T_FOLD_COLSUM=0 (read per call: a test flips it): the bias gradient by its own colsum_kernel launch, as before the fold
+    const char* fold_env = getenv("I2T_FOLD_COLSUM");
+    const bool fold_colsum = !(fold_env && fold_env[0] == '0');
     if (!no_g256 && a_kmajor && b_kmajor && accumulate && c_is_f32 && !bias && act == I2T_ACT_NONE && !aux_out && !residual &&
         !drop_mode && M >= 256 && N >= 256 && (ldc & 3) == 0 && (N & 3) == 0) {
         // The k-major panels are addressed through 32-bit buffer offsets: (K + 512) rows x ld x 2 bytes must stay below 4 GiB.
@@ -2176,7 +2286,8 @@ extern "C" int i2t_gemm_bf16_ex(void* stream, const void* A, int lda, int a_kmaj
                 q.A = p.A + (size_t)k0 * lda;
                 q.B = p.B + (size_t)k0 * ldb;
                 q.K = (int)((K - k0 < kc) ? (K - k0) : kc);
-                ok = launch_g256_dw(s, q);
+                q.colsum_out = colsum_out;
+                ok = launch_g256_dw(s, q, fold_colsum);
                 if (!ok && k0 > 0) { i2t_set_error("i2t_gemm_bf16: K chunk %ld of a chunked dW GEMM has no large-tile form", k0); return I2T_EINVAL; }
             }
             if (ok) {
@@ -2185,6 +2296,7 @@ extern "C" int i2t_gemm_bf16_ex(void* stream, const void* A, int lda, int a_kmaj
             }
         }
     }
+    if (colsum_out) launch_colsum(s, p.A, lda, K, M, colsum_out, alpha_sumsq);      // (no large-tile split-K form for this call: its own launch)
     dim3 grid(p.tiles_m * p.tiles_n), block(256);
     // split-K for accumulate-into-fp32 problems whose tile grid cannot fill the 256 CUs (the dW = dY^T.X GEMMs: small
     // M x N, very long K): enough slices to reach ~2 workgroups per CU, each slice at least 4 K-steps long
@@ -2361,12 +2473,7 @@ extern "C" int i2t_colsum_bf16_ex(void* stream, const void* X, int ld, int M, in
         hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)N, s);
         if (e != hipSuccess) { i2t_set_error("i2t_colsum_bf16: memset: %s", hipGetErrorString(e)); return I2T_EHIP; }
     }
-    const int col_blocks = (N + 511) / 512;
-    int splits = (M + 63) / 64;                       // >= 64 rows per workgroup
-    const int want = 512 / col_blocks;                // ~2 workgroups per CU overall
-    if (splits > want) splits = want;
-    if (splits < 1 || i2t_det()) splits = 1;           // (deterministic mode: one workgroup per column block = one add per column)
-    hipLaunchKernelGGL(colsum_kernel, dim3(col_blocks, splits), dim3(256), 0, s, (const bf16_t*)X, ld, M, N, out, alpha_sumsq);
+    launch_colsum(s, (const bf16_t*)X, ld, M, N, out, alpha_sumsq);
     I2T_CHECK_LAUNCH("i2t_colsum_bf16");
     return I2T_OK;
 }

@@ -609,10 +609,10 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
                               dkv[..., :d], dkv[..., d:], B, H, T, S, False, drop=dr['xattn'], cu_q=cu, total_q=M)
             dqf, dkvf = dq, dkv.view(B * S, 2 * d)
             train_in, train_inb = a.trainable(f'{pfx}.cross_attn.in_proj_weight'), a.trainable(f'{pfx}.cross_attn.in_proj_bias')
-            if train_inb:
-                ops.colsum(dqf, gbin[:d], M, d, accumulate=True)
             if train_in:
-                ops.gemm(dqf, sv.ln3, gin[:d], d, d, M, a_kmajor=True, b_kmajor=True, accumulate=True)
+                ops.gemm(dqf, sv.ln3, gin[:d], d, d, M, a_kmajor=True, b_kmajor=True, accumulate=True, colsum_out=gbin[:d] if train_inb else None)
+            elif train_inb:
+                ops.colsum(dqf, gbin[:d], M, d, accumulate=True)
             ops.gemm(dqf, win[:d], dln, M, d, d, b_kmajor=True)
             dmem32 = self._site_bwd(self._block_site(pfx, sv.layer, 'xattn_c_attn', 2 * d, d, rows=(d, 3 * d)), svlo.get('xattn_c_attn'), dkvf, sv.mem,
                                     B * S, ldrop.get('xattn_c_attn'), dx_out=dmem, accumulate=True)

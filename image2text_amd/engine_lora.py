@@ -155,10 +155,10 @@ class LoraAdapters:
             assert act in (0, ops.ACT_DGELU, ops.ACT_DGELU_ERF), act
             dx32 = self._lora_bwd(s, sv_l, dY, x_bf, gW, gb, M, drop_l, e4m3, dq)
         else:
-            if gb is not None:
+            if gW is not None:          # (db rides on the dW launch: dY is not read a third time just to sum its columns)
+                ops.gemm(dY, x_bf, gW, N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True, alpha_sumsq=dy_sumsq, colsum_out=gb)
+            elif gb is not None:
                 ops.colsum(dY, gb, M, N, accumulate=True, alpha_sumsq=dy_sumsq)
-            if gW is not None:
-                ops.gemm(dY, x_bf, gW, N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True, alpha_sumsq=dy_sumsq)
             if dx_out is None:
                 return None
             if not e4m3:
@@ -256,10 +256,10 @@ class LoraAdapters:
         """dY bf16 [M, N]: gradient w.r.t. the adapted linear's pre-epilogue output.  gW / gb: gradient views of the base weight /
         bias or None (frozen).  Accumulates every parameter gradient; returns dx fp32 [M, K] = dY . W + dropout(du . A)."""
         ls, W, K, N = st.lora, st.W, st.K, st.N
-        if gb is not None:
-            ops.colsum(dY, gb, M, N, accumulate=True)
         if gW is not None:
-            ops.gemm(dY, x, gW, N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True)
+            ops.gemm(dY, x, gW, N, K, M, a_kmajor=True, b_kmajor=True, accumulate=True, colsum_out=gb)
+        elif gb is not None:
+            ops.colsum(dY, gb, M, N, accumulate=True)
         tmp = torch.zeros(N, LPAD, dtype=F32, device=dY.device)
         ops.gemm(dY, sv_l.u, tmp, N, LPAD, M, a_kmajor=True, b_kmajor=True, accumulate=True)
         for row0, nrows, col0, B, GB in ls.parts:             # (a fused projection: only the diagonal blocks are parameters)

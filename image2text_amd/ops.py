@@ -117,11 +117,15 @@ def _gemm_precise(a, b, out, M, N, K, *, a_kmajor, b_kmajor, lda, ldb, ldc, alph
 
 def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, *, a_kmajor=False, b_kmajor=False,
          lda=None, ldb=None, ldc=None, alpha=1.0, bias=None, act=0, aux_in=None, aux_out=None, residual=None,
-         ldr=None, accumulate=False, drop=None, workspace=None, alpha_sumsq=None):
+         ldr=None, accumulate=False, drop=None, workspace=None, alpha_sumsq=None, colsum_out=None):
     """out[M,N] = epilogue(alpha * op(a) . op(b)); see include/i2t.h::i2t_gemm_bf16.  workspace (fp32, decode steps): the
     deterministic split-K form i2t_gemm_bf16_ws when the problem has few tiles and a long K.  alpha_sumsq (1-float device tensor):
     alpha is further divided by sqrt(alpha_sumsq) + 1e-6 on the device (i2t_gemm_bf16_ex: a folded gradient normaliser).
-    Under I2T_PRECISE=1: the three-product form of the parity mode (above)."""
+    colsum_out (fp32 [M], the dW form a_kmajor = b_kmajor = accumulate only): the bias gradient beside the weight gradient, see
+    ``gemm_dw_colsum``.  Under I2T_PRECISE=1: the three-product form of the parity mode (above)."""
+    if colsum_out is not None:
+        assert a_kmajor and b_kmajor and accumulate and bias is None and not act and aux_out is None and residual is None and drop is None
+        return gemm_dw_colsum(a, b, out, colsum_out, M, N, K, alpha=alpha, alpha_sumsq=alpha_sumsq, lda=lda, ldb=ldb, ldc=ldc)
     if precise():
         return _gemm_precise(a, b, out, M, N, K, a_kmajor=a_kmajor, b_kmajor=b_kmajor, lda=lda, ldb=ldb, ldc=ldc, alpha=alpha, bias=bias,
                              act=act, aux_in=aux_in, aux_out=aux_out, residual=residual, ldr=ldr, accumulate=accumulate, drop=drop,
@@ -181,6 +185,23 @@ def colsum(x: torch.Tensor, out: torch.Tensor, M: int, N: int, ld=None, accumula
     _l.check(_lib().i2t_colsum_bf16_ex(_stream(), _p(x), x.stride(0) if ld is None else ld, M, N, _p(out), int(accumulate), _p(alpha_sumsq)),
              'i2t_colsum_bf16_ex')
     return out
+
+
+def gemm_dw_colsum(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb, N: int, K: int, M: int, *, alpha=1.0, alpha_sumsq=None,
+                   lda=None, ldb=None, ldc=None):
+    """gw[N, K] += alpha f dy^T . x and gb[N] += f sum_rows(dy) (f: the folded gradient normaliser of ``gemm`` / ``colsum``) for dy bf16
+    [M, N], x bf16 [M, K]: a linear layer's weight and bias gradients from one read of dy (include/i2t.h::i2t_gemm_dw_colsum_bf16;
+    I2T_FOLD_COLSUM=0: the two launches it replaces).  gb None: the GEMM alone.  Under I2T_PRECISE=1: the separate calls."""
+    if precise():
+        if gb is not None:
+            colsum(dy, gb, M, N, ld=lda, accumulate=True, alpha_sumsq=alpha_sumsq)
+        return gemm(dy, x, gw, N, K, M, a_kmajor=True, b_kmajor=True, lda=lda, ldb=ldb, ldc=ldc, alpha=alpha, accumulate=True, alpha_sumsq=alpha_sumsq)
+    _need_cuda(dy, x, gw)
+    assert dy.dtype == BF16 and x.dtype == BF16 and gw.dtype == F32 and (gb is None or gb.dtype == F32)
+    _l.check(_lib().i2t_gemm_dw_colsum_bf16(_stream(), _p(dy), dy.stride(0) if lda is None else lda, _p(x), x.stride(0) if ldb is None else ldb,
+                                            _p(gw), gw.stride(0) if ldc is None else ldc, N, K, M, float(alpha), _p(alpha_sumsq), _p(gb)),
+             'i2t_gemm_dw_colsum_bf16')
+    return gw
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, M, d, eps=None):

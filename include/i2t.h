@@ -123,6 +123,15 @@ int i2t_colsum_bf16(void* stream, const void* X, int ld, int M, int N, float* ou
 /* out[n] (+)= (sum_m X[m][n]) / (sqrt(*alpha_sumsq) + 1e-6)  (alpha_sumsq NULL: plain sums): the bias gradient of a linear layer whose
  * output gradient X is kept un-normalised (see i2t_gemm_bf16_ex) */
 int i2t_colsum_bf16_ex(void* stream, const void* X, int ld, int M, int N, float* out, int accumulate, const float* alpha_sumsq);
+/* A weight gradient and its bias gradient from one read of dY:
+ *   C[M][N] += alpha f A^T . B        colsum_out[m] += f sum_k A[k][m]        f = 1 / (sqrt(*alpha_sumsq) + 1e-6), or 1 when alpha_sumsq is NULL
+ * A = dY bf16 [K][lda], B = x bf16 [K][ldb] (both k-major: M is the layer's N, N the layer's K, K the rows), C f32.  The same call as
+ * i2t_gemm_bf16_ex(a_kmajor = b_kmajor = accumulate = 1) followed by i2t_colsum_bf16_ex(accumulate = 1) on A; where the GEMM runs as K
+ * slices on the persistent kernel the sums are a by-product of that launch (the A fragments a wave holds, once more against an all-ones
+ * operand) and A is not read a second time.  Every other route, deterministic mode and I2T_FOLD_COLSUM=0 launch the column-sum kernel.
+ * colsum_out NULL: the GEMM alone. */
+int i2t_gemm_dw_colsum_bf16(void* stream, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K,
+                            float alpha, const float* alpha_sumsq, float* colsum_out);
 
 /* ---------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim (layers.py:349-358, F.layer_norm eps 1e-5, optional bias)
