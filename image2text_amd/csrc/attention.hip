@@ -1579,7 +1579,7 @@ extern "C" int i2t_attention_bwd_ex(void* stream, const void* q, long q_bs, int 
                 "i2t_attention_bwd_ex: out_drop_q_seq=%d is offered by the one-pass resident kernel only (dense, Tk <= %d)", out_drop_q_seq, V2_MAXROWS);
     if (bmode == 3 && v2_applies(Tq, Tk, causal, cu_q, cu_k, drop_thr) && Tq <= V2_MAXROWS) {
         // 9 waves whenever 8 would leave a wave with a third key block (I2T_ATTN_BWD3_WAVES = 8 | 9 forces one: A/B runs)
-        static const char* we = getenv("I2T_ATTN_BWD3_WAVES");
+        const char* we = getenv("I2T_ATTN_BWD3_WAVES");
         const int nkb = (Tk + 15) >> 4;
         const bool nine = we && atoi(we) == 9;      // measured (B = 1024, T = 260, dropout): 1295 us against 1228 for 8 waves -- the third register-limited
         // wave of a SIMD and its spills cost more than wave 0's third block: off unless asked for
