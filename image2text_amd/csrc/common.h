@@ -60,6 +60,15 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
+// ---- online softmax: (mx, se) = (max, sum of exp(. - mx)) of one set of values, merged with those of another set.  A set without
+// a member is {-inf, 0}: its factor is 0, not exp(-inf - -inf).
+__device__ __forceinline__ void lse_merge(float& mx, float& se, float omx, float ose) {
+    const float m = fmaxf(mx, omx);
+    const float fa = mx > -INFINITY ? __expf(mx - m) : 0.f, fb = omx > -INFINITY ? __expf(omx - m) : 0.f;
+    se = se * fa + ose * fb;
+    mx = m;
+}
+
 // ---- GELU(tanh): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3), evaluated as x * sigmoid(2u): one v_exp_f32 and
 // one v_rcp_f32 (1 ulp each) instead of an IEEE division -- the epilogue VALU work of a K = 512 GEMM rivals its MFMA work,
 // so every instruction here is paid per output element.

@@ -331,6 +331,48 @@ __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32
     }
 }
 
+// Caption scoring: log p(label | row) from the lm_head's SEGMENT statistics (i2t_gemm_bf16_lse: (max, sum exp) of every 64-column
+// segment of a row of scale . hidden . W^T).  One wave per row: lane l merges segments l, l + 64, ... in ascending order, the 64
+// partial pairs are merged by a fixed xor tree (no atomics: bit-reproducible), lse = mx + log(se); the label's own logit is
+// re-evaluated here in fp32 from the bf16 operands (as top2_ngram_argmax_kernel re-evaluates a segment), so the GEMM needs no labels.
+constexpr int LSE_WAVES = 4;
+__global__ __launch_bounds__(64 * LSE_WAVES) void lse_token_logprob_kernel(const float* __restrict__ stats, int nseg, const bf16_t* __restrict__ hid,
+                                                                           int ld_h, const bf16_t* __restrict__ W, int ldw, int d, float scale,
+                                                                           const int64_t* __restrict__ labels, int64_t ignore_index,
+                                                                           float* __restrict__ lse, float* __restrict__ logprob, int M, int V) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
+    if (m >= M) return;                                      // wave-uniform
+    const f32x2* row = reinterpret_cast<const f32x2*>(stats) + (size_t)m * nseg;
+    float mx = -INFINITY, se = 0.f;
+    for (int sgm = lane; sgm < nseg; sgm += 64) {
+        const f32x2 t = row[sgm];
+        lse_merge(mx, se, t[0], t[1]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+    const float l = mx + logf(se);
+    const int64_t lab = labels[m];
+    const bool live = lab != ignore_index && lab >= 0 && lab < (int64_t)V;      // wave-uniform
+    float z = 0.f;
+    if (live) {
+        const bf16_t* wr = W + (size_t)lab * ldw;
+        const bf16_t* hr = hid + (size_t)m * ld_h;
+        for (int k = 8 * lane; k < d; k += 8 * 64) {
+            const u32x4 wv = *reinterpret_cast<const u32x4*>(wr + k), hv = *reinterpret_cast<const u32x4*>(hr + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z += bf16lo(wv[e]) * bf16lo(hv[e]) + bf16hi(wv[e]) * bf16hi(hv[e]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+    }
+    if (lane == 0) {
+        lse[m] = l;
+        logprob[m] = live ? scale * z - l : 0.f;
+    }
+}
+
 __global__ void advance_kernel(int* counters, int n, int delta) {
     if ((int)threadIdx.x < n) counters[threadIdx.x] += delta;
 }
@@ -402,6 +444,19 @@ extern "C" int i2t_top2_ngram_argmax(void* stream, const float* top2, int nseg, 
     hipLaunchKernelGGL(top2_ngram_argmax_kernel, dim3(B), dim3(T2_THREADS), lds, (hipStream_t)stream, (const f32x4*)top2, nseg,
                        (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, V);
     I2T_CHECK_LAUNCH("i2t_top2_ngram_argmax");
+    return I2T_OK;
+}
+
+extern "C" int i2t_lse_token_logprob(void* stream, const float* stats, int nseg, const void* hidden, int ld_hidden, const void* w_head, int ld_w,
+                                     int d, float scale, const int64_t* labels, int64_t ignore_index, float* lse, float* logprob, int M, int V) {
+    I2T_REQUIRE(stats && hidden && w_head && labels && lse && logprob && M > 0 && V > 0 && d > 0 && nseg == (V + 63) / 64,
+                "i2t_lse_token_logprob: bad args (nseg must be ceil(V / 64))");
+    I2T_REQUIRE(d % 8 == 0 && (ld_hidden & 7) == 0 && (ld_w & 7) == 0 && ld_hidden >= d && ld_w >= d && ALIGNED16(hidden) && ALIGNED16(w_head) &&
+                    (((uintptr_t)stats) & 7) == 0,
+                "i2t_lse_token_logprob: hidden / head rows must be 16-byte aligned, d %% 8 == 0, stats 8-byte aligned");
+    hipLaunchKernelGGL(lse_token_logprob_kernel, dim3((M + LSE_WAVES - 1) / LSE_WAVES), dim3(64 * LSE_WAVES), 0, (hipStream_t)stream, stats, nseg,
+                       (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, scale, labels, ignore_index, lse, logprob, M, V);
+    I2T_CHECK_LAUNCH("i2t_lse_token_logprob");
     return I2T_OK;
 }
 

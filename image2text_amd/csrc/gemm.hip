@@ -1428,6 +1428,39 @@ __device__ __forceinline__ void top2_epilogue(const GemmParams& p, f32x4 (&acc)[
     }
 }
 
+// Epilogue class 14 (i2t_gemm_bf16_lse: the lm_head of caption scoring).  The output tile is NOT stored either: every 64-column segment
+// of a row leaves the two numbers an online softmax carries -- C[row][segment] = {mx, se}, mx = max_c alpha z[row][c] and
+// se = sum_c exp(alpha z[row][c] - mx) over the segment's columns c < N -- 8 bytes instead of 256 (fp32) or 128 (bf16).  The maximum is
+// subtracted before every exp, so se >= 1 and nothing overflows; i2t_lse_token_logprob (decode.hip) merges the segments in order.
+// Register layout and reduction as top2_epilogue: a lane's 16 values first, then the lanes lane ^ 16, lane ^ 32.  No atomics.
+__device__ __forceinline__ void lse_epilogue(const GemmParams& p, f32x4 (&acc)[8][4], int mbase, int nbase, int lane) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    const int g = lane >> 4, li = lane & 15;
+    const int seg = nbase >> 6;
+    if (seg >= p.ldc) return;                          // wave-uniform: a segment wholly past N
+    f32x2* out = reinterpret_cast<f32x2*>(p.C);
+    const float scale = p.alpha;
+    const int n_valid = p.N - nbase - 4 * g;           // column 16 j + r of this lane is valid when 16 j + r < n_valid
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        float mx = -INFINITY, se = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (16 * j + r < n_valid) mx = fmaxf(mx, __fmul_rn(scale, acc[i][j][r]));      // (rounded product: the same value in both passes)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) se += 16 * j + r < n_valid ? __expf(__fmul_rn(scale, acc[i][j][r]) - mx) : 0.f;
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1)             // the four lanes that hold a row's other columns
+            lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+        const int m = mbase + 16 * i + li;
+        if (g == 0 && m < p.M) out[(size_t)m * p.ldc + seg] = f32x2{mx, se};
+    }
+}
+
 // The kernel's own argument block (GemmParams is the only argument: offset 0 of the kernarg segment), through a pointer the
 // compiler cannot connect to the argument `p`: loads through it are scalar loads issued where they are used.
 __device__ __forceinline__ const GemmParams* epilogue_params() {
@@ -1515,6 +1548,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
             top2_epilogue(*epilogue_params(), acc, m0 + g.wr * 128, n0 + g.wc * 64, lane_e);
+        } else if constexpr (EPI == 14) {       // (max, sum exp) of every 64-column row segment instead of the tile (caption scoring's lm_head)
+            int lane_e = tid & 63;
+            asm volatile("" : "+v"(lane_e));
+            lse_epilogue(*epilogue_params(), acc, m0 + g.wr * 128, n0 + g.wc * 64, lane_e);
         } else if constexpr (EPI == 6 || EPI == 13) {        // split-K partial: fp32 atomics, one wave-instruction = 4 rows x 64 contiguous bytes
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
@@ -2380,6 +2417,27 @@ extern "C" int i2t_gemm_bf16_top2(void* stream, const void* A, int lda, const vo
     const int tiles = p.tiles_m * p.tiles_n;
     hipLaunchKernelGGL((gemm256_kernel<false, false, 12>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
     I2T_CHECK_LAUNCH("i2t_gemm_bf16_top2");
+    return I2T_OK;
+}
+
+extern "C" int i2t_gemm_bf16_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float scale, float* stats, int nseg) {
+    I2T_REQUIRE(A && B && stats && M > 0 && N > 0 && K > 0 && nseg == (N + 63) / 64, "i2t_gemm_bf16_lse: bad args (nseg must be ceil(N / 64))");
+    I2T_REQUIRE(K % 128 == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && lda >= K && ldb >= K && ALIGNED16(A) && ALIGNED16(B) && ALIGNED16(stats),
+                "i2t_gemm_bf16_lse: K=%d must be a multiple of 128, operands 16-byte aligned with leading dimensions %% 8 == 0", K);
+    I2T_REQUIRE((size_t)256 * lda * 2 < (1ull << 32) && (size_t)256 * ldb * 2 < (1ull << 32), "i2t_gemm_bf16_lse: rows too long");
+    I2T_REQUIRE(scale == scale && scale - scale == 0.f, "i2t_gemm_bf16_lse: scale must be finite");
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = stats;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = nseg;
+    p.alpha = scale; p.c_is_f32 = 1;
+    { static const char* e = getenv("I2T_G256_GN"); static const int gn = e ? atoi(e) : 8; p.g2_gn = gn > 0 ? gn : 8; }
+    const int n_cu = g256_cus();
+    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
+    p.g2_splits = 1; p.g2_nk = (((K + 63) >> 6) + 1) & ~1;
+    const int tiles = p.tiles_m * p.tiles_n;
+    hipLaunchKernelGGL((gemm256_kernel<false, false, 14>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
+    I2T_CHECK_LAUNCH("i2t_gemm_bf16_lse");
     return I2T_OK;
 }
 

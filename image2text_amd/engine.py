@@ -1042,6 +1042,60 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         ops.gemm(hb, self.arena.W(self.n_head), buf, M, self.dec.V, self.dec.d)
         return buf
 
+    SCORE_WS_BYTES = 256 << 20      # cap of the scoring workspace (segment statistics, or the fallback's bf16 logits chunk)
+
+    def _score_ws(self, kind: str, rows: int, cols: int, dtype):
+        """cached [rows, cols] scratch of token_logprobs (grown, never shrunk; dropped with the arena)"""
+        dev = self.arena.device
+        cache = getattr(self, '_score_cache', None)
+        if cache is None or cache.get('device') != dev:
+            cache = self._score_cache = {'device': dev}
+        buf = cache.get(kind)
+        if buf is None or buf.shape[0] < rows or buf.shape[1] != cols or buf.dtype != dtype:
+            cache[kind] = None
+            buf = cache[kind] = torch.zeros(rows, cols, dtype=dtype, device=dev)
+        return buf
+
+    def token_logprobs(self, hb: torch.Tensor, labels: torch.Tensor, M: int, inv_temp: float = 1.0, ignore_index: int = -100):
+        """log p(labels[m] | row m) under softmax(inv_temp . hb . W_head^T), and the rows' logsumexp: (logprob f32 [M], lse f32 [M]).
+        A row whose label is ignore_index or outside [0, V) gets logprob 0; its lse is still computed.
+
+        d % 128 == 0 (the persistent GEMM kernel's K rule, as decoding.py's segment-maxima head): the head runs as ops.gemm_lse and
+        leaves 8 bytes per 64 columns; ops.lse_token_logprob merges them and re-evaluates the label's logit -- no logits buffer.
+        Otherwise: bf16 logits + ops.ce_fwd for the lse and a gather of the label's column.  Both forms walk the rows in chunks
+        whose scratch stays within SCORE_WS_BYTES."""
+        a, dc = self.arena, self.dec
+        W = a.W(self.n_head)
+        labels = labels.to(device=a.device, dtype=torch.long).contiguous().view(-1)
+        assert labels.numel() == M and hb.shape[0] >= M and hb.dtype == BF16
+        logprob, lse = self._empty(M), self._empty(M)
+        if M == 0:
+            return logprob, lse
+        if dc.d % 128 == 0:
+            nseg = (dc.V + 63) // 64
+            chunk = max(256, self.SCORE_WS_BYTES // (nseg * 8) // 256 * 256)
+            stats = self._score_ws('stats', min(chunk, M), nseg * 2, F32)
+            for r0 in range(0, M, chunk):
+                n = min(chunk, M - r0)
+                st = stats[:n].view(n, nseg, 2)
+                ops.gemm_lse(hb[r0:r0 + n], W, st, n, dc.V, dc.d, scale=inv_temp)
+                ops.lse_token_logprob(st, hb[r0:r0 + n], W, labels[r0:r0 + n], lse[r0:r0 + n], logprob[r0:r0 + n], n, dc.V, dc.d,
+                                      scale=inv_temp, ignore_index=ignore_index)
+            return logprob, lse
+        chunk = max(256, self.SCORE_WS_BYTES // (dc.Vp * 2) // 256 * 256)
+        buf = self._score_ws('logits', min(chunk, M), dc.Vp, BF16)          # (pad columns zero and never written, as logits_bf16's)
+        live = (labels != ignore_index) & (labels >= 0) & (labels < dc.V)
+        col = torch.where(live, labels, torch.zeros_like(labels))
+        every = torch.zeros_like(labels)                                     # ce_fwd skips ignored rows: label 0 on every row, nothing ignored
+        ones, loss = torch.ones(min(chunk, M), dtype=F32, device=a.device), torch.zeros(1, dtype=F32, device=a.device)
+        for r0 in range(0, M, chunk):
+            n = min(chunk, M - r0)
+            ops.gemm(hb[r0:r0 + n], W, buf[:n], n, dc.V, dc.d)
+            ops.ce_fwd(buf[:n], dc.Vp, every[r0:r0 + n], ones[:n], inv_temp, -1, lse[r0:r0 + n], loss, n, dc.V)
+            z = buf[:n].gather(1, col[r0:r0 + n, None])[:, 0].float() * inv_temp
+            logprob[r0:r0 + n] = torch.where(live[r0:r0 + n], z - lse[r0:r0 + n], torch.zeros_like(z))
+        return logprob, lse
+
     @staticmethod
     def _lockstep(*gens):
         """Run backward generators side by side.  Each yields (key, its sum(g^2) part) at a gradient-normaliser site (keys

@@ -65,6 +65,8 @@ SIGNATURES = {
     'i2t_gemm_bf16_top2': [P, P, I, P, I, I, I, I, P, I],
     'i2t_top2_ngram_argmax': [P, P, I, P, I, P, I, I, P, I, P, P, I, I, I],
     'i2t_sample_token': [P, P, I, P, I, P, P, I, I, I, F, I, F, P, P, I],
+    'i2t_gemm_bf16_lse': [P, P, I, P, I, I, I, I, F, P, I],
+    'i2t_lse_token_logprob': [P, P, I, P, I, P, I, I, F, P, I64, P, P, I, I],
     'i2t_embed_step': [P, P, I, P, P, P, P, I, I, I, I],
     'i2t_advance': [P, P, I, I],
     'i2t_gq_attention_fwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, I, U, U, F, P, P, I, I],
@@ -133,7 +135,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 _lib = None
 
 

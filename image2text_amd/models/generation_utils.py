@@ -142,3 +142,37 @@ class BeamSearchTokenGenerator:
         new_ids = cand_ids.flatten(1).gather(1, flat_idx).unsqueeze(-1)
         new_lp = cand_lp.flatten(1).gather(1, flat_idx)
         return torch.cat((kept, new_ids), dim=-1), scores.gather(1, beam_idx) + new_lp
+
+
+def post_eos_positions(ids: torch.Tensor, eos: Optional[int], prompt_len: int = 1) -> torch.Tensor:
+    """bool [N, L]: the columns after a row's first ``eos``.  The first ``prompt_len`` columns are the prompt and are not searched
+    (a GPT-2 tokenizer's BOS is its EOS); ``eos=None``: nothing."""
+    if eos is None:
+        return torch.zeros_like(ids, dtype=torch.bool)
+    is_eos = ids == eos
+    is_eos[:, :prompt_len] = False
+    return (is_eos.cumsum(dim=1) - is_eos.long()) > 0
+
+
+def rerank_labels(ids: torch.Tensor, eos: Optional[int], prompt_len: int = 1, ignore_index: int = -100) -> torch.Tensor:
+    """Next-token labels of candidate captions [N, L]: a token inside the prompt or after the row's first ``eos`` is not scored"""
+    from .vision_encoder_decoder import next_token_labels
+    labels = next_token_labels(ids, ignore_index)
+    skip = post_eos_positions(ids, eos, prompt_len)
+    skip[:, :prompt_len] = True
+    labels[:, :-1][skip[:, 1:]] = ignore_index
+    return labels
+
+
+@torch.no_grad()
+def rerank(model, images, candidates: torch.Tensor, eos: Optional[int] = None, prompt_len: int = 1, temperature: float = 1.0):
+    """Order W candidate captions per image by their log-likelihood (an addition: the reference has no such call).
+    candidates (B, W, L) -> (order (B, W): candidate indices, best first; logprob (B, W): sum of log p(token | image, predecessors)
+    over each candidate's tokens after the prompt, up to and including its first ``eos``).  The encoder runs once per image."""
+    B, W, L = candidates.shape
+    enc = model.encode(images)                                                  # (B, n_cls, d), once
+    enc = enc.unsqueeze(1).expand(B, W, *enc.shape[1:]).reshape(B * W, *enc.shape[1:]).contiguous()
+    flat = candidates.to(enc.device).reshape(B * W, L)
+    scores = model.score(None, flat, labels=rerank_labels(flat, eos, prompt_len), encoder_output=enc, temperature=temperature)
+    logprob = scores.logprob.view(B, W)
+    return torch.argsort(logprob, dim=1, descending=True, stable=True), logprob

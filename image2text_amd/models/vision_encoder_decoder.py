@@ -14,10 +14,17 @@ import torch.nn as nn
 from ..configs.models import VisionEncoderDecoderConfig
 from ..engine import BF16, F32, HotPath
 from ..lib import I2TError
-from ..object_models import VisionEncoderDecoderModelOutput
+from ..object_models import CaptionScores, VisionEncoderDecoderModelOutput
 from .decoder import Decoder
 from .encoder import Encoder
 from .utils import update_state_dict_from_partial_checkpoint
+
+
+def next_token_labels(ids: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    """labels[:, t] = ids[:, t + 1]; the last column, which has no successor, is ignore_index"""
+    labels = torch.full_like(ids, ignore_index)
+    labels[:, :-1] = ids[:, 1:]
+    return labels
 
 
 class _BridgedEncoder(nn.Sequential):
@@ -223,6 +230,39 @@ class VisionEncoderDecoder(nn.Module):
         if top_k == 1 and nucleus_p is None:
             return self._greedy.generate(images, prompt_ids, max_new_tokens)
         return self._greedy.generate(images, prompt_ids, max_new_tokens, sampling=Sampling(temperature, top_k, nucleus_p))
+
+
+    @torch.no_grad()
+    def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:
+        """Log-likelihood of given captions (no counterpart in the reference): ``token_logprobs[b, t]`` is
+        ``log_softmax(self(images, ids).logits[b, t].float() / temperature)[labels[b, t]]`` and 0 where ``labels[b, t]`` is
+        ``ignore_index`` (or no token id); ``labels=None`` scores every token given its predecessors (``next_token_labels``).
+        Same decoder calls and block-size crop as ``forward``; the encoder runs once, or not at all when ``encoder_output`` is given.
+        The logits are not materialised when the decoder width allows (``HotPath.token_logprobs``)."""
+        dev = next(self.parameters()).device
+        ids = ids.to(dev)
+        labels = next_token_labels(ids, ignore_index) if labels is None else labels.to(dev)
+        if labels.shape != ids.shape:
+            raise ValueError(f'labels of shape {tuple(labels.shape)} for ids of shape {tuple(ids.shape)}')
+        eng: HotPath = self._engine
+        eng.prepare(False)
+        B, L = ids.shape
+        if encoder_output is None:
+            enc_out, _ = eng.encode(images, False)
+        else:
+            enc_out = encoder_output.to(device=dev, dtype=F32).contiguous()
+        ncls = enc_out.shape[1]
+        mem = eng._mem_bf16(enc_out) if eng.cross_inputs else None
+        off = ncls if self.config.use_soft_prompting else 0
+        T = min(L, eng.dec.block - off)                       # the reference crops inputs to block_size (:88)
+        if eng.dec.prefixed:
+            _, hb, _ = eng.decode_prefixed(B, T, enc_out, mem, False, ids)
+        else:
+            _, hb, _ = eng.decode_segment(B, T, mem, ncls, False, ids=ids[:, :T], pos_offset=off)
+        T = hb.shape[0] // B
+        lp, lse = eng.token_logprobs(hb, labels[:, :T].contiguous().view(B * T), B * T, 1.0 / temperature, ignore_index)
+        lp = lp.view(B, T)
+        return CaptionScores(token_logprobs=lp, lse=lse.view(B, T), logprob=lp.sum(dim=1))
 
 
 def _owner_of(module):

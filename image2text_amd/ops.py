@@ -760,6 +760,30 @@ def advance(counters, delta=1):
     _l.check(_lib().i2t_advance(_stream(), _p(counters), counters.numel(), delta), 'i2t_advance')
 
 
+def gemm_lse(a, b, stats, M, N, K, scale=1.0):
+    """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
+    _need_cuda(a, b, stats)
+    assert a.dtype == BF16 and b.dtype == BF16 and stats.dtype == F32 and stats.is_contiguous()
+    assert stats.shape[-1] == 2 and stats.shape[-2] == (N + 63) // 64 and stats.numel() >= M * stats.shape[-2] * 2
+    assert a.stride(-1) == 1 and b.stride(-1) == 1 and a.shape[0] >= M and b.shape[0] >= N
+    _l.check(_lib().i2t_gemm_bf16_lse(_stream(), _p(a), a.stride(0), _p(b), b.stride(0), M, N, K, float(scale), _p(stats), (N + 63) // 64),
+             'i2t_gemm_bf16_lse')
+    return stats
+
+
+def lse_token_logprob(stats, hidden, w_head, labels, lse, logprob, M, V, d, scale=1.0, ignore_index=-100):
+    """lse[m] and logprob[m] = scale . hidden[m] . w_head[labels[m]] - lse[m] from gemm_lse's segments (include/i2t.h::i2t_lse_token_logprob)"""
+    _need_cuda(stats, hidden, w_head, labels, lse, logprob)
+    assert hidden.dtype == BF16 and w_head.dtype == BF16 and stats.dtype == F32 and lse.dtype == F32 and logprob.dtype == F32
+    assert labels.dtype == torch.long and labels.is_contiguous() and lse.is_contiguous() and logprob.is_contiguous() and stats.is_contiguous()
+    assert stats.shape[-1] == 2 and stats.shape[-2] == (V + 63) // 64 and stats.numel() >= M * stats.shape[-2] * 2
+    assert hidden.stride(-1) == 1 and w_head.stride(-1) == 1 and hidden.shape[0] >= M and w_head.shape[0] >= V
+    assert labels.numel() >= M and lse.numel() >= M and logprob.numel() >= M
+    _l.check(_lib().i2t_lse_token_logprob(_stream(), _p(stats), (V + 63) // 64, _p(hidden), hidden.stride(0), _p(w_head), w_head.stride(0), d,
+                                          float(scale), _p(labels), int(ignore_index), _p(lse), _p(logprob), M, V), 'i2t_lse_token_logprob')
+    return logprob, lse
+
+
 class Graph:
     """hipGraph captured from the launches issued between ``begin()`` and ``end()`` on the current stream."""
 

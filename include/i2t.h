@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 5
+#define I2T_ABI_VERSION 6
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -389,6 +389,16 @@ int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, int logits_is
 int i2t_gemm_bf16_top2(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float* top2, int nseg);
 int i2t_top2_ngram_argmax(void* stream, const float* top2, int nseg, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d,
                           int64_t* ids, int ids_ld, int* len_ptr, const int* ngram_sizes, int n_sizes, int B, int V);
+/* Caption scoring without the logits (an addition: the reference has no such call; it is log_softmax(logits / T) gathered at given
+ * labels).  i2t_gemm_bf16_lse runs z = scale . A [M][lda] . B^T (B = the head's rows [N][ldb], bf16, K % 128 == 0) on the persistent GEMM
+ * kernel as i2t_gemm_bf16_top2 does and leaves, for every 64-column segment of a row, stats[M][nseg][2] = {mx, se}: mx = max_c z[m][c],
+ * se = sum_c exp(z[m][c] - mx) over the segment's columns c < N, nseg = ceil(N / 64) -- 8 bytes per 64 columns, no atomics, bit-
+ * reproducible.  i2t_lse_token_logprob merges a row's segments in a fixed order into lse[m] = log sum_c exp(z[m][c]), re-evaluates
+ * the label's logit z_t = scale . hidden[m] . w_head[label] in fp32 from the bf16 operands and writes logprob[m] = z_t - lse[m];
+ * a row whose label is ignore_index or outside [0, V) gets logprob 0 exactly (its lse is still written). */
+int i2t_gemm_bf16_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float scale, float* stats, int nseg);
+int i2t_lse_token_logprob(void* stream, const float* stats, int nseg, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d,
+                          float scale, const int64_t* labels, int64_t ignore_index, float* lse, float* logprob, int M, int V);
 int i2t_embed_step(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* wte,
                    const float* wpe, float* x, int B, int d, int pos_offset, int vocab);
 /* One sampling step of generate() for B captions (reference models/vision_encoder_decoder.py:150-180, the non-greedy modes; the
