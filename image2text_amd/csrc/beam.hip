@@ -1,7 +1,7 @@
 // Beam-search step kernels over the static KV cache (reference models/generation_utils.py:10-148, BeamSearchTokenGenerator).
 // R = B * W rows, batch-major (row r = b * W + w).  Every position-dependent input (pos, len, the "all beams ended" flag) lives in
 // device memory, so one captured hipGraph replays the whole step once per token with no host round trip:
-//   decoder blocks (beam attention below) -> lm_head (fp32 logits) -> i2t_beam_candidates -> i2t_beam_consolidate -> i2t_beam_advance.
+//   decoder blocks (the HIST attention kernels of decode.hip / family.hip) -> lm_head (fp32 logits) -> i2t_beam_candidates -> i2t_beam_consolidate -> i2t_beam_advance.
 // Survivors never copy K/V: a history table hist[R][T] (int32) names the physical cache row that holds key t of beam r.  The step
 // writes its new K/V at physical (r, pos); consolidation sets hist[child][t] = hist[parent][t] for t < pos and hist[child][pos] =
 // parent.  Each position of each physical row is written once, so no entry a live beam points at is ever overwritten.  A sparse
@@ -273,236 +273,6 @@ __global__ void beam_advance_kernel(int* counters, int* ctrl) {
     ctrl[1] = 0;
 }
 
-// decode.hip::decode_attention_kernel with key t of row r read from cache row hist[r][t] (hist null: row r / rows_per_mem for
-// every key, the per-image cross-attention memory).  Same loads, same lanes, same reduction order: with an identity table the
-// output is bit-equal to decode_attention's.
-constexpr int DEC_MAX_KEYS = 1024;
-template <int WPB>
-__global__ __launch_bounds__(64 * WPB) void beam_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs,
-                                                                         bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
-                                                                         long cache_bs, int cache_rs, long cache_hs, bf16_t* __restrict__ o,
-                                                                         int o_rs, const int* __restrict__ pos_ptr, int n_keys_fixed,
-                                                                         int append_dm, const int* __restrict__ hist, int hist_ld,
-                                                                         int rows_per_mem) {
-    __shared__ float qs_[WPB][64], kn_[WPB][64], vn_[WPB][64];
-    __shared__ float ps_[WPB][DEC_MAX_KEYS];
-    __shared__ int hs[DEC_MAX_KEYS];
-    const int wv = threadIdx.x >> 6;
-    float* qs = qs_[wv];
-    float* kn = kn_[wv];
-    float* vn = vn_[wv];
-    float* ps = ps_[wv];
-    const int h = blockIdx.x * WPB + wv, b = blockIdx.y, lane = threadIdx.x & 63;
-    const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
-    const bf16_t* qrow = q + (size_t)b * q_rs + h * 64 + lane;
-    qs[lane] = bf16_to_f32(qrow[0]);
-    const int n_cached = append_dm > 0 ? n - 1 : n;
-    for (int t = threadIdx.x; t < n_cached; t += 64 * WPB) hs[t] = hist ? hist[(size_t)b * hist_ld + t] : b / rows_per_mem;
-    bf16_t* kh = kc + (size_t)h * cache_hs;                  // head h of cache row 0; row x adds x * cache_bs
-    bf16_t* vh = vc + (size_t)h * cache_hs;
-    if (append_dm > 0) {
-        const bf16_t kv = qrow[append_dm], vv = qrow[2 * append_dm];
-        kn[lane] = bf16_to_f32(kv);
-        vn[lane] = bf16_to_f32(vv);
-        kh[(size_t)b * cache_bs + (size_t)(n - 1) * cache_rs + lane] = kv;
-        vh[(size_t)b * cache_bs + (size_t)(n - 1) * cache_rs + lane] = vv;
-    }
-    __syncthreads();
-    const int kg = lane >> 3, c = lane & 7;
-    float qv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qv[e] = qs[c * 8 + e];
-    float mx = -INFINITY;
-    if (append_dm > 0 && lane == 0) {
-        float s = 0.f;
-        for (int e = 0; e < 64; ++e) s += kn[e] * qs[e];
-        s *= 0.125f;
-        ps[n - 1] = s;
-        mx = s;
-    }
-    for (int k0 = 0; k0 < n_cached; k0 += 32) {
-        u32x4 kk[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + kg;
-            kk[u] = u32x4{0u, 0u, 0u, 0u};
-            if (key < n_cached)
-                kk[u] = *reinterpret_cast<const u32x4*>(kh + (size_t)hs[key] * cache_bs + (size_t)key * cache_rs + c * 8);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + kg;
-            float s = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s += bf16lo(kk[u][e]) * qv[2 * e] + bf16hi(kk[u][e]) * qv[2 * e + 1];
-            s += __shfl_xor(s, 1, 64);
-            s += __shfl_xor(s, 2, 64);
-            s += __shfl_xor(s, 4, 64);
-            s *= 0.125f;
-            if (key < n_cached) {
-                if (c == 0) ps[key] = s;
-                mx = fmaxf(mx, s);
-            }
-        }
-    }
-    mx = wave_max(mx);
-    __syncthreads();
-    float sum = 0.f;
-    for (int key = lane; key < n; key += 64) {
-        float p = __expf(ps[key] - mx);
-        ps[key] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    for (int k0 = 0; k0 < n_cached; k0 += 32) {
-        u32x4 vv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + kg;
-            vv[u] = u32x4{0u, 0u, 0u, 0u};
-            if (key < n_cached)
-                vv[u] = *reinterpret_cast<const u32x4*>(vh + (size_t)hs[key] * cache_bs + (size_t)key * cache_rs + c * 8);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int key = k0 + 8 * u + kg;
-            const float p = key < n_cached ? ps[key] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[2 * e] += p * bf16lo(vv[u][e]);
-                acc[2 * e + 1] += p * bf16hi(vv[u][e]);
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        acc[e] += __shfl_xor(acc[e], 8, 64);
-        acc[e] += __shfl_xor(acc[e], 16, 64);
-        acc[e] += __shfl_xor(acc[e], 32, 64);
-    }
-    if (kg == 0) {
-        const float inv = 1.0f / sum;
-        if (append_dm > 0) {
-            const float pn = ps[n - 1];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += pn * vn[c * 8 + e];
-        }
-        const u32x4 pk = {pack_bf16x2(acc[0] * inv, acc[1] * inv), pack_bf16x2(acc[2] * inv, acc[3] * inv),
-                          pack_bf16x2(acc[4] * inv, acc[5] * inv), pack_bf16x2(acc[6] * inv, acc[7] * inv)};
-        *reinterpret_cast<u32x4*>(o + (size_t)b * o_rs + h * 64 + c * 8) = pk;
-    }
-}
-
-// family.hip::gq_decode_attention_kernel with the same history indirection (row-major cache [R][T][Hkv hd]).  slot_pos (sparse
-// layers, nullable): slot s holds the layer's s-th kept text position, so key s of row r is read from row hist[r][slot_pos[s]]; the
-// table row is the only thing it changes, null keeps the kernel as it was.
-constexpr int GDEC_MAX_KEYS = 1024;
-template <int HD>
-__global__ __launch_bounds__(64) void beam_gq_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
-                                                                      const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
-                                                                      bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
-                                                                      bf16_t* __restrict__ o, int o_rs, const int* __restrict__ pos_ptr,
-                                                                      int n_keys_fixed, int G, float scale, const int* __restrict__ hist,
-                                                                      int hist_ld, const int* __restrict__ slot_pos, int rows_per_mem) {
-    constexpr int LPK = HD / 8, KPP = 64 / LPK;
-    __shared__ float qs[HD], kn[HD], vn[HD];
-    __shared__ float ps[GDEC_MAX_KEYS];
-    __shared__ int hs[GDEC_MAX_KEYS];
-    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, hk = h / G;
-    const bool append = k_new != nullptr;
-    const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
-    const int n_cached = append ? n - 1 : n;
-    bf16_t* kh = kc + hk * HD;
-    bf16_t* vh = vc + hk * HD;
-    for (int t = lane; t < n_cached; t += 64)
-        hs[t] = hist ? hist[(size_t)b * hist_ld + (slot_pos ? slot_pos[t] : t)] : b / rows_per_mem;
-    for (int i = lane; i < HD; i += 64) {
-        qs[i] = bf16_to_f32(q[(size_t)b * q_rs + h * HD + i]);
-        if (append) {
-            const bf16_t kv = k_new[(size_t)b * kv_rs + hk * HD + i], vv = v_new[(size_t)b * kv_rs + hk * HD + i];
-            kn[i] = bf16_to_f32(kv);
-            vn[i] = bf16_to_f32(vv);
-            if (h % G == 0) {
-                kh[(size_t)b * cache_bs + (size_t)(n - 1) * cache_rs + i] = kv;
-                vh[(size_t)b * cache_bs + (size_t)(n - 1) * cache_rs + i] = vv;
-            }
-        }
-    }
-    __syncthreads();
-    const int kg = lane / LPK, c = lane % LPK;
-    float qv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qv[e] = qs[c * 8 + e];
-    float mx = -INFINITY;
-    if (append && lane == 0) {
-        float s = 0.f;
-        for (int e = 0; e < HD; ++e) s += kn[e] * qs[e];
-        s *= scale;
-        ps[n - 1] = s;
-        mx = s;
-    }
-    for (int k0 = 0; k0 < n_cached; k0 += KPP) {
-        const int key = k0 + kg;
-        float s = 0.f;
-        if (key < n_cached) {
-            const u32x4 kk = *reinterpret_cast<const u32x4*>(kh + (size_t)hs[key] * cache_bs + (size_t)key * cache_rs + c * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s += bf16lo(kk[e]) * qv[2 * e] + bf16hi(kk[e]) * qv[2 * e + 1];
-        }
-#pragma unroll
-        for (int o_ = 1; o_ < LPK; o_ <<= 1) s += __shfl_xor(s, o_, 64);
-        s *= scale;
-        if (key < n_cached) {
-            if (c == 0) ps[key] = s;
-            mx = fmaxf(mx, s);
-        }
-    }
-    mx = wave_max(mx);
-    __syncthreads();
-    float sum = 0.f;
-    for (int key = lane; key < n; key += 64) {
-        const float p = __expf(ps[key] - mx);
-        ps[key] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    for (int k0 = 0; k0 < n_cached; k0 += KPP) {
-        const int key = k0 + kg;
-        if (key < n_cached) {
-            const u32x4 vv = *reinterpret_cast<const u32x4*>(vh + (size_t)hs[key] * cache_bs + (size_t)key * cache_rs + c * 8);
-            const float p = ps[key];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[2 * e] += p * bf16lo(vv[e]);
-                acc[2 * e + 1] += p * bf16hi(vv[e]);
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-#pragma unroll
-        for (int o_ = LPK; o_ < 64; o_ <<= 1) acc[e] += __shfl_xor(acc[e], o_, 64);
-    if (kg == 0) {
-        const float inv = 1.0f / sum;
-        if (append) {
-            const float pn = ps[n - 1];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += pn * vn[c * 8 + e];
-        }
-        const u32x4 pk = {pack_bf16x2(acc[0] * inv, acc[1] * inv), pack_bf16x2(acc[2] * inv, acc[3] * inv),
-                          pack_bf16x2(acc[4] * inv, acc[5] * inv), pack_bf16x2(acc[6] * inv, acc[7] * inv)};
-        *reinterpret_cast<u32x4*>(o + (size_t)b * o_rs + h * HD + c * 8) = pk;
-    }
-}
-
 }  // namespace
 
 extern "C" int i2t_beam_candidates(void* stream, const float* logits, int ld, const int64_t* ids, int ids_ld, const int* len_ptr,
@@ -537,57 +307,5 @@ extern "C" int i2t_beam_advance(void* stream, int* counters, int* ctrl) {
     I2T_REQUIRE(counters && ctrl, "i2t_beam_advance: bad args");
     hipLaunchKernelGGL(beam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counters, ctrl);
     I2T_CHECK_LAUNCH("i2t_beam_advance");
-    return I2T_OK;
-}
-
-extern "C" int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, void* kcache, void* vcache, long cache_bs, int cache_rs,
-                                         long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed, int append_dm,
-                                         const int* hist, int hist_ld, int rows_per_mem, int R, int H) {
-    I2T_REQUIRE(cache_hs >= 64 && cache_hs % 8 == 0, "i2t_beam_decode_attention: head stride %ld", cache_hs);
-    I2T_REQUIRE(append_dm == 0 || (pos_ptr && append_dm == 64 * H), "i2t_beam_decode_attention: append needs pos_ptr and a packed qkv row");
-    I2T_REQUIRE(q && kcache && vcache && o && R > 0 && H > 0 && rows_per_mem >= 1, "i2t_beam_decode_attention: bad args");
-    I2T_REQUIRE(pos_ptr || (n_keys_fixed > 0 && n_keys_fixed <= DEC_MAX_KEYS), "i2t_beam_decode_attention: key count out of range");
-    I2T_REQUIRE(!hist || hist_ld >= (pos_ptr ? 1 : n_keys_fixed), "i2t_beam_decode_attention: history rows shorter than the keys");
-    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache), "i2t_beam_decode_attention: cache misaligned");
-    I2T_REQUIRE(o_rs % 8 == 0 && ALIGNED16(o), "i2t_beam_decode_attention: output rows must be 16-byte aligned");
-    if (H % 4 == 0)
-        hipLaunchKernelGGL(beam_decode_attention_kernel<4>, dim3(H / 4, R), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs,
-                           (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, (bf16_t*)o, o_rs, pos_ptr, n_keys_fixed, append_dm,
-                           hist, hist_ld, rows_per_mem);
-    else
-        hipLaunchKernelGGL(beam_decode_attention_kernel<1>, dim3(H, R), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs,
-                           (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, (bf16_t*)o, o_rs, pos_ptr, n_keys_fixed, append_dm,
-                           hist, hist_ld, rows_per_mem);
-    I2T_CHECK_LAUNCH("i2t_beam_decode_attention");
-    return I2T_OK;
-}
-
-extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
-                                            void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
-                                            const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld,
-                                            const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
-    I2T_REQUIRE(q && kcache && vcache && out && R > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && rows_per_mem >= 1,
-                "i2t_beam_gq_decode_attention: bad args");
-    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "i2t_beam_gq_decode_attention: head_dim %d (16, 32, 64 or 128)", hd);
-    I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "i2t_beam_gq_decode_attention: no key count");
-    I2T_REQUIRE(max_keys > 0 && max_keys <= GDEC_MAX_KEYS && n_keys_fixed <= max_keys, "i2t_beam_gq_decode_attention: at most %d keys",
-                GDEC_MAX_KEYS);
-    I2T_REQUIRE(!hist || hist_ld >= max_keys, "i2t_beam_gq_decode_attention: history rows shorter than max_keys");
-    I2T_REQUIRE(!slot_pos || hist, "i2t_beam_gq_decode_attention: slot_pos needs a history table");
-    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
-                "i2t_beam_gq_decode_attention: cache / output rows must be 16-byte aligned");
-    const float scale = 1.0f / sqrtf((float)hd);
-    dim3 grid(H, R);
-    hipStream_t s = (hipStream_t)stream;
-#define BGDEC_LAUNCH(HD)                                                                                                             \
-    hipLaunchKernelGGL(beam_gq_decode_attention_kernel<HD>, grid, dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,        \
-                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr, \
-                       n_keys_fixed, H / Hkv, scale, hist, hist_ld, slot_pos, rows_per_mem)
-    if (hd == 16) BGDEC_LAUNCH(16);
-    else if (hd == 32) BGDEC_LAUNCH(32);
-    else if (hd == 64) BGDEC_LAUNCH(64);
-    else BGDEC_LAUNCH(128);
-#undef BGDEC_LAUNCH
-    I2T_CHECK_LAUNCH("i2t_beam_gq_decode_attention");
     return I2T_OK;
 }

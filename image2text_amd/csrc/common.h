@@ -205,6 +205,17 @@ __device__ __forceinline__ void build_ban_bitmap(unsigned* bits, const int64_t* 
 }
 __device__ __forceinline__ bool ban_bit(const unsigned* bits, int c) { return (bits[c >> 5] >> (c & 31)) & 1u; }     // 0 <= c < V
 
+// ---- KV-cache decode attention (decode.hip: 64-wide heads; family.hip: grouped-query).  The kernels keep the scores of at most this
+// many keys per row in LDS (decoding.DECODE_MAX_KEYS is the host's copy).  key_row: the cache row of key `key`, counted from the row
+// the kernel's base pointers address -- row b itself, so 0; or (HIST, beam search) row 0, so the row that hs[], the workgroup's
+// LDS copy of row b's history, names for the key.
+constexpr int DECODE_MAX_KEYS = 1024;
+template <bool HIST>
+__device__ __forceinline__ int key_row(const int* hs, int key) {
+    if constexpr (HIST) return hs[key];
+    else return 0;
+}
+
 // LDS transposed read: 4 rows x 16 cols block of 16-bit elements per 16-lane group, delivered column-major
 // (cdna_hip_programming.md T10).  EXEC must be all ones at the call site.
 __device__ __forceinline__ s16x4 lds_read_tr16(const void* lds_ptr) {

@@ -43,17 +43,22 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
 // lane-per-key form issued 8 loads that each touched 64 lines).  Scores: per-lane partial dot over its 8 dims, 3 xor
 // shuffles inside the 8-lane group.  Output: per-lane partial sum over its key stripe for its 8 dims, 3 xor shuffles
 // across the 8 stripes.  The step is HBM-bound on the K/V cache (B x H x t x 256 B per call).
-constexpr int DEC_MAX_KEYS = 1024;
 // append_dm > 0: q points at a packed [q | k | v] row of width 3*append_dm; the new token's k/v (this head's 64
 // columns) are written into the cache at *pos by this workgroup and attended to from LDS (fused kv_append).
-template <int WPB>         // waves (= heads) per workgroup: 49 152 one-wave workgroups per launch were dispatch-rate bound
+// HIST (beam search, i2t_beam_decode_attention): key t of row b is read from cache row hist[b][t] (hist null: row
+// b / rows_per_mem for every key, the per-image cross-attention memory) through the LDS copy hs[] of the table row; the
+// new token still lands in row b.  The table row is all that HIST changes -- same loads, same lanes, same reduction order:
+// with an identity table the output is bit-equal.  HIST = false reads neither hs[] (no LDS for it) nor the last three arguments.
+template <int WPB, bool HIST>         // waves (= heads) per workgroup: 49 152 one-wave workgroups per launch were dispatch-rate bound
 __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs,
                                                                     bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
                                                                     long cache_bs, int cache_rs, long cache_hs, bf16_t* __restrict__ o,
                                                                     int o_rs, const int* __restrict__ pos_ptr, int n_keys_fixed,
-                                                                    int append_dm) {
+                                                                    int append_dm, const int* __restrict__ hist, int hist_ld,
+                                                                    int rows_per_mem) {
     __shared__ float qs_[WPB][64], kn_[WPB][64], vn_[WPB][64];
-    __shared__ float ps_[WPB][DEC_MAX_KEYS];
+    __shared__ float ps_[WPB][DECODE_MAX_KEYS];
+    __shared__ int hs[HIST ? DECODE_MAX_KEYS : 1];
     const int wv = threadIdx.x >> 6;
     float* qs = qs_[wv];
     float* kn = kn_[wv];
@@ -63,15 +68,19 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
     const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
     const bf16_t* qrow = q + (size_t)b * q_rs + h * 64 + lane;
     qs[lane] = bf16_to_f32(qrow[0]);
-    bf16_t* kb = kc + (size_t)b * cache_bs + (size_t)h * cache_hs;      // cache_hs = 64: token-major rows [t][H][64];
-    bf16_t* vb = vc + (size_t)b * cache_bs + (size_t)h * cache_hs;      // cache_hs = tmax * 64 (cache_rs = 64): head-major [H][t][64]
+    // the cache row kb / vb address is row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
+    const int own = HIST ? b : 0;
+    bf16_t* kb = kc + (size_t)(b - own) * cache_bs + (size_t)h * cache_hs;      // cache_hs = 64: token-major rows [t][H][64];
+    bf16_t* vb = vc + (size_t)(b - own) * cache_bs + (size_t)h * cache_hs;      // cache_hs = tmax * 64 (cache_rs = 64): head-major [H][t][64]
     const int n_cached = append_dm > 0 ? n - 1 : n;          // keys read back from the cache
+    if constexpr (HIST)
+        for (int t = threadIdx.x; t < n_cached; t += 64 * WPB) hs[t] = hist ? hist[(size_t)b * hist_ld + t] : b / rows_per_mem;
     if (append_dm > 0) {
         const bf16_t kv = qrow[append_dm], vv = qrow[2 * append_dm];
         kn[lane] = bf16_to_f32(kv);
         vn[lane] = bf16_to_f32(vv);
-        kb[(size_t)(n - 1) * cache_rs + lane] = kv;
-        vb[(size_t)(n - 1) * cache_rs + lane] = vv;
+        kb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + lane] = kv;
+        vb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + lane] = vv;
     }
     __syncthreads();
     const int kg = lane >> 3, c = lane & 7;                  // key within a group of 8, 16-byte chunk of the head
@@ -94,7 +103,8 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
         for (int u = 0; u < 4; ++u) {
             const int key = k0 + 8 * u + kg;
             kk[u] = u32x4{0u, 0u, 0u, 0u};
-            if (key < n_cached) kk[u] = *reinterpret_cast<const u32x4*>(kb + (size_t)key * cache_rs + c * 8);
+            if (key < n_cached)
+                kk[u] = *reinterpret_cast<const u32x4*>(kb + (size_t)key_row<HIST>(hs, key) * cache_bs + (size_t)key * cache_rs + c * 8);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -131,7 +141,8 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
         for (int u = 0; u < 4; ++u) {
             const int key = k0 + 8 * u + kg;
             vv[u] = u32x4{0u, 0u, 0u, 0u};
-            if (key < n_cached) vv[u] = *reinterpret_cast<const u32x4*>(vb + (size_t)key * cache_rs + c * 8);
+            if (key < n_cached)
+                vv[u] = *reinterpret_cast<const u32x4*>(vb + (size_t)key_row<HIST>(hs, key) * cache_bs + (size_t)key * cache_rs + c * 8);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -399,23 +410,39 @@ extern "C" int i2t_kv_append(void* stream, const void* qkv, int qkv_rs, void* kc
     return I2T_OK;
 }
 
+// i2t_decode_attention and i2t_beam_decode_attention (fn: the entry point the messages name): one set of checks, one launch
+static int decode_attention(const char* fn, bool beam, void* stream, const void* q, int q_rs, void* kcache, void* vcache, long cache_bs,
+                            int cache_rs, long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed, int append_dm,
+                            const int* hist, int hist_ld, int rows_per_mem, int B, int H) {
+    I2T_REQUIRE(cache_hs >= 64 && cache_hs % 8 == 0, "%s: head stride %ld", fn, cache_hs);
+    I2T_REQUIRE(append_dm == 0 || (pos_ptr && append_dm == 64 * H), "%s: append needs pos_ptr and a packed qkv row", fn);
+    I2T_REQUIRE(q && kcache && vcache && o && B > 0 && H > 0 && (!beam || rows_per_mem >= 1), "%s: bad args", fn);
+    I2T_REQUIRE(pos_ptr || (n_keys_fixed > 0 && n_keys_fixed <= DECODE_MAX_KEYS), "%s: key count out of range", fn);
+    I2T_REQUIRE(!beam || !hist || hist_ld >= (pos_ptr ? 1 : n_keys_fixed), "%s: history rows shorter than the keys", fn);
+    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache), "%s: cache misaligned", fn);
+    I2T_REQUIRE(o_rs % 8 == 0 && ALIGNED16(o), "%s: output rows must be 16-byte aligned", fn);
+    const bool w4 = H % 4 == 0;
+    const auto kernel = w4 ? (beam ? decode_attention_kernel<4, true> : decode_attention_kernel<4, false>)
+                           : (beam ? decode_attention_kernel<1, true> : decode_attention_kernel<1, false>);
+    hipLaunchKernelGGL(kernel, w4 ? dim3(H / 4, B) : dim3(H, B), dim3(w4 ? 256 : 64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs,
+                       (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, (bf16_t*)o, o_rs, pos_ptr, n_keys_fixed, append_dm,
+                       hist, hist_ld, rows_per_mem);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
+}
+
 extern "C" int i2t_decode_attention(void* stream, const void* q, int q_rs, void* kcache, void* vcache,
                                     long cache_bs, int cache_rs, long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed,
                                     int append_dm, int B, int H) {
-    I2T_REQUIRE(cache_hs >= 64 && cache_hs % 8 == 0, "i2t_decode_attention: head stride %ld", cache_hs);
-    I2T_REQUIRE(append_dm == 0 || (pos_ptr && append_dm == 64 * H), "i2t_decode_attention: append needs pos_ptr and a packed qkv row");
-    I2T_REQUIRE(q && kcache && vcache && o && B > 0 && H > 0, "i2t_decode_attention: bad args");
-    I2T_REQUIRE(pos_ptr || (n_keys_fixed > 0 && n_keys_fixed <= DEC_MAX_KEYS), "i2t_decode_attention: key count out of range");
-    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache), "i2t_decode_attention: cache misaligned");
-    I2T_REQUIRE(o_rs % 8 == 0 && ALIGNED16(o), "i2t_decode_attention: output rows must be 16-byte aligned");
-    if (H % 4 == 0)
-        hipLaunchKernelGGL(decode_attention_kernel<4>, dim3(H / 4, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs,
-                           (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, (bf16_t*)o, o_rs, pos_ptr, n_keys_fixed, append_dm);
-    else
-        hipLaunchKernelGGL(decode_attention_kernel<1>, dim3(H, B), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs,
-                           (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, (bf16_t*)o, o_rs, pos_ptr, n_keys_fixed, append_dm);
-    I2T_CHECK_LAUNCH("i2t_decode_attention");
-    return I2T_OK;
+    return decode_attention("i2t_decode_attention", false, stream, q, q_rs, kcache, vcache, cache_bs, cache_rs, cache_hs, o, o_rs, pos_ptr,
+                            n_keys_fixed, append_dm, nullptr, 0, 1, B, H);
+}
+
+extern "C" int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, void* kcache, void* vcache, long cache_bs, int cache_rs,
+                                         long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed, int append_dm,
+                                         const int* hist, int hist_ld, int rows_per_mem, int R, int H) {
+    return decode_attention("i2t_beam_decode_attention", true, stream, q, q_rs, kcache, vcache, cache_bs, cache_rs, cache_hs, o, o_rs,
+                            pos_ptr, n_keys_fixed, append_dm, hist, hist_ld, rows_per_mem, R, H);
 }
 
 extern "C" int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, int logits_is_f32, int64_t* ids, int ids_ld,

@@ -267,21 +267,32 @@ __global__ __launch_bounds__(256) void moe_unpack_dw2_kernel(const float* __rest
 // the query heads of a group reading one shared K/V head (multi-query: the cache is H times smaller than the multi-head one, and
 // the step is HBM-bound on exactly that cache).  k_new / v_new: this token's key / value rows (appended to the cache at slot
 // *pos_ptr by the group's first head, and attended to from LDS by all of them); null for a fixed memory of n_keys_fixed keys.
-constexpr int GDEC_MAX_KEYS = 1024;
-template <int HD>
+// HIST (beam search, i2t_beam_gq_decode_attention): the history indirection of decode_attention_kernel on the row-major cache
+// [R][T][Hkv hd] -- key s of row b is read from cache row hist[b][s] (hist null: row b / rows_per_mem) through the LDS copy hs[].
+// slot_pos (sparse layers, nullable): slot s holds the layer's s-th kept text position, so its row is hist[b][slot_pos[s]].  The
+// table row is all that HIST changes: with an identity table the output is bit-equal.  HIST = false reads neither hs[] (no LDS
+// for it) nor the last four arguments.
+template <int HD, bool HIST>
 __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
                                                                  const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
                                                                  bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
                                                                  bf16_t* __restrict__ o, int o_rs, const int* __restrict__ pos_ptr,
-                                                                 int n_keys_fixed, int G, float scale) {
+                                                                 int n_keys_fixed, int G, float scale, const int* __restrict__ hist,
+                                                                 int hist_ld, const int* __restrict__ slot_pos, int rows_per_mem) {
     constexpr int LPK = HD / 8, KPP = 64 / LPK;             // lanes per key, keys per pass
     __shared__ float qs[HD], kn[HD], vn[HD];
-    __shared__ float ps[GDEC_MAX_KEYS];
+    __shared__ float ps[DECODE_MAX_KEYS];
+    __shared__ int hs[HIST ? DECODE_MAX_KEYS : 1];
     const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, hk = h / G;
     const bool append = k_new != nullptr;
     const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
-    bf16_t* kb = kc + (size_t)b * cache_bs + hk * HD;
-    bf16_t* vb = vc + (size_t)b * cache_bs + hk * HD;
+    // the cache row kb / vb address is row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
+    const int own = HIST ? b : 0;
+    bf16_t* kb = kc + (size_t)(b - own) * cache_bs + hk * HD;
+    bf16_t* vb = vc + (size_t)(b - own) * cache_bs + hk * HD;
+    if constexpr (HIST)
+        for (int t = lane; t < (append ? n - 1 : n); t += 64)
+            hs[t] = hist ? hist[(size_t)b * hist_ld + (slot_pos ? slot_pos[t] : t)] : b / rows_per_mem;
     for (int i = lane; i < HD; i += 64) {
         qs[i] = bf16_to_f32(q[(size_t)b * q_rs + h * HD + i]);
         if (append) {
@@ -289,13 +300,14 @@ __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* _
             kn[i] = bf16_to_f32(kv);
             vn[i] = bf16_to_f32(vv);
             if (h % G == 0) {
-                kb[(size_t)(n - 1) * cache_rs + i] = kv;
-                vb[(size_t)(n - 1) * cache_rs + i] = vv;
+                kb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + i] = kv;
+                vb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + i] = vv;
             }
         }
     }
     __syncthreads();
-    const int n_cached = append ? n - 1 : n;
+    const int n_cached = append ? n - 1 : n;                // keys read back from the cache (named here, not above the barrier: the
+                                                            // compiler's prologue follows the source order, and this one is measured)
     const int kg = lane / LPK, c = lane % LPK;
     float qv[8];
 #pragma unroll
@@ -312,7 +324,8 @@ __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* _
         const int key = k0 + kg;
         float s = 0.f;
         if (key < n_cached) {
-            const u32x4 kk = *reinterpret_cast<const u32x4*>(kb + (size_t)key * cache_rs + c * 8);
+            const u32x4 kk =
+                *reinterpret_cast<const u32x4*>(kb + (size_t)key_row<HIST>(hs, key) * cache_bs + (size_t)key * cache_rs + c * 8);
 #pragma unroll
             for (int e = 0; e < 4; ++e) s += bf16lo(kk[e]) * qv[2 * e] + bf16hi(kk[e]) * qv[2 * e + 1];
         }
@@ -340,7 +353,8 @@ __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* _
     for (int k0 = 0; k0 < n_cached; k0 += KPP) {
         const int key = k0 + kg;
         if (key < n_cached) {
-            const u32x4 vv = *reinterpret_cast<const u32x4*>(vb + (size_t)key * cache_rs + c * 8);
+            const u32x4 vv =
+                *reinterpret_cast<const u32x4*>(vb + (size_t)key_row<HIST>(hs, key) * cache_bs + (size_t)key * cache_rs + c * 8);
             const float p = ps[key];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -476,29 +490,43 @@ extern "C" int i2t_moe_unpack_dw2(void* stream, const float* dW, float* gw, floa
     return I2T_OK;
 }
 
+// i2t_gq_decode_attention and i2t_beam_gq_decode_attention (fn: the entry point the messages name): one set of checks, one launch
+static int gq_decode_attention(const char* fn, bool beam, void* stream, const void* q, int q_rs, const void* k_new, const void* v_new,
+                               int kv_rs, void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                               const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, const int* slot_pos,
+                               int rows_per_mem, int B, int H, int Hkv, int hd) {
+    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && (!beam || rows_per_mem >= 1), "%s: bad args", fn);
+    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", fn, hd);
+    I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "%s: no key count", fn);
+    I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_MAX_KEYS && n_keys_fixed <= max_keys, "%s: at most %d keys", fn, DECODE_MAX_KEYS);
+    I2T_REQUIRE(!beam || !hist || hist_ld >= max_keys, "%s: history rows shorter than max_keys", fn);
+    I2T_REQUIRE(!beam || !slot_pos || hist, "%s: slot_pos needs a history table", fn);
+    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
+                "%s: cache / output rows must be 16-byte aligned", fn);
+    const float scale = 1.0f / sqrtf((float)hd);
+#define GDEC_KERNEL(HD) (beam ? gq_decode_attention_kernel<HD, true> : gq_decode_attention_kernel<HD, false>)
+    const auto kernel = hd == 16 ? GDEC_KERNEL(16) : hd == 32 ? GDEC_KERNEL(32) : hd == 64 ? GDEC_KERNEL(64) : GDEC_KERNEL(128);
+#undef GDEC_KERNEL
+    hipLaunchKernelGGL(kernel, dim3(H, B), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,
+                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr,
+                       n_keys_fixed, H / Hkv, scale, hist, hist_ld, slot_pos, rows_per_mem);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
+}
+
 extern "C" int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
                                        void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
                                        int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd) {
-    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "i2t_gq_decode_attention: bad args");
-    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "i2t_gq_decode_attention: head_dim %d (16, 32, 64 or 128)", hd);
-    I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "i2t_gq_decode_attention: no key count");
-    I2T_REQUIRE(max_keys > 0 && max_keys <= GDEC_MAX_KEYS && n_keys_fixed <= max_keys, "i2t_gq_decode_attention: at most %d keys", GDEC_MAX_KEYS);
-    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
-                "i2t_gq_decode_attention: cache / output rows must be 16-byte aligned");
-    const float scale = 1.0f / sqrtf((float)hd);
-    dim3 grid(H, B);
-    hipStream_t s = (hipStream_t)stream;
-#define GDEC_LAUNCH(HD)                                                                                                              \
-    hipLaunchKernelGGL(gq_decode_attention_kernel<HD>, grid, dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,             \
-                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr, \
-                       n_keys_fixed, H / Hkv, scale)
-    if (hd == 16) GDEC_LAUNCH(16);
-    else if (hd == 32) GDEC_LAUNCH(32);
-    else if (hd == 64) GDEC_LAUNCH(64);
-    else GDEC_LAUNCH(128);
-#undef GDEC_LAUNCH
-    I2T_CHECK_LAUNCH("i2t_gq_decode_attention");
-    return I2T_OK;
+    return gq_decode_attention("i2t_gq_decode_attention", false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs,
+                               out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, nullptr, 1, B, H, Hkv, hd);
+}
+
+extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
+                                            void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                                            const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld,
+                                            const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
+    return gq_decode_attention("i2t_beam_gq_decode_attention", true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, slot_pos, rows_per_mem, R, H, Hkv, hd);
 }
 
 extern "C" int i2t_sparse_step_setup(void* stream, const int* pos_ptr, const int* rank, const int* member, int* lpos, int* lmem, int L,

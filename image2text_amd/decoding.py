@@ -45,8 +45,8 @@ class Sampling(NamedTuple):
         return (float(self.temperature), int(self.top_k or 0), None if self.nucleus_p is None else float(self.nucleus_p))
 
 
-# i2t_decode_attention and i2t_gq_decode_attention keep the scores of at most this many keys per caption in LDS; neither reads a key
-# count from the device against it, so the cache the step attends over is never allocated longer
+# i2t_decode_attention and i2t_gq_decode_attention (csrc/common.h::DECODE_MAX_KEYS) keep the scores of at most this many keys per caption
+# in LDS; neither reads a key count from the device against it, so the cache the step attends over is never allocated longer
 DECODE_MAX_KEYS = 1024
 
 
@@ -208,22 +208,13 @@ class GreedyDecoder:
             else:
                 ops.gemm(st.ln, a.W(f'{p}.attn.c_attn.weight'), st.qkv, B, 3 * d, d, bias=a.P(f'{p}.attn.c_attn.bias'), workspace=st.ws)
                 qv, kn, vn, out_name = st.qkv[:, :d], st.qkv[:, d:2 * d], st.qkv[:, 2 * d:], 'attn.c_proj'
-            if st.hist is None:
-                ops.gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd)
-            else:
-                ops.beam_gq_decode_attention(qv, kn, vn, st.kc[l], st.vc[l], st.slots * w, w, st.ao, pos_ptr, 0, st.slots, B, H, Hkv, hd,
-                                             hist=st.hist, slot_pos=st.kpos[l] if st.sparse else None)
+            self._self_attention(st, l, pos_ptr, (qv, kn, vn, H, Hkv, hd, st.slots), slot_pos=st.kpos[l] if st.sparse else None)
             ops.gemm(st.ao, a.W(f'{p}.{out_name}.weight'), xo, B, d, d, bias=a.P(f'{p}.{out_name}.bias'), residual=st.x, workspace=st.ws)
             if l in st.cross_kv:
-                kv, S = st.cross_kv[l]
                 win, bin_ = a.W(f'{p}.cross_attn.in_proj_weight'), a.P(f'{p}.cross_attn.in_proj_bias')
                 ops.layernorm_fwd(xo, a.P(f'{p}.ln_3.weight'), a.P(f'{p}.ln_3.bias'), st.ln, None, None, B, d)
                 ops.gemm(st.ln, win[:d], st.q, B, d, d, bias=bin_[:d], workspace=st.ws)
-                if st.mem_div == 1:
-                    ops.gq_decode_attention(st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, hd)
-                else:
-                    ops.beam_gq_decode_attention(st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, hd,
-                                                 rows_per_mem=st.mem_div)
+                self._cross_attention(st, l, hd)
                 ops.gemm(st.ao, a.W(f'{p}.cross_attn.out_proj.weight'), xo, B, d, d, bias=a.P(f'{p}.cross_attn.out_proj.bias'), residual=xo, workspace=st.ws)
             ops.layernorm_fwd(xo, a.P(f'{p}.ln_2.weight'), a.P(f'{p}.ln_2.bias'), st.ln, None, None, B, d)
             if sp.moe is not None:
@@ -325,22 +316,13 @@ class GreedyDecoder:
             ops.layernorm_fwd(st.x, a.P(f'{p}.ln_1.weight'), a.P(f'{p}.ln_1.bias'), st.ln, None, None, B, d)
             ops.gemm(st.ln, self._w(l, 'attn_c_attn', f'{p}.attn.c_attn.weight'), st.qkv, B, 3 * d, d, bias=a.P(f'{p}.attn.c_attn.bias'),
                      workspace=st.ws)
-            if st.hist is None:
-                ops.decode_attention(st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, H, append_dm=d,
-                                     cache_hs=st.clen * 64)       # head-major self-attention cache [B][H][prefix + tmax][64]
-            else:
-                ops.beam_decode_attention(st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, H, hist=st.hist,
-                                          append_dm=d, cache_hs=st.clen * 64)
+            self._self_attention(st, l, pos_ptr)
             ops.gemm(st.ao, a.W(f'{p}.attn.c_proj.weight'), st.x, B, d, d, bias=a.P(f'{p}.attn.c_proj.bias'), residual=st.x, workspace=st.ws)
             if l in st.cross_kv:
-                kv, S = st.cross_kv[l]
                 win, bin_ = a.W(f'{p}.cross_attn.in_proj_weight'), a.P(f'{p}.cross_attn.in_proj_bias')
                 ops.layernorm_fwd(st.x, a.P(f'{p}.ln_3.weight'), a.P(f'{p}.ln_3.bias'), st.ln, None, None, B, d)
                 ops.gemm(st.ln, win[:d], st.q, B, d, d, bias=bin_[:d], workspace=st.ws)
-                if st.mem_div == 1:
-                    ops.decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H)
-                else:
-                    ops.beam_decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H, rows_per_mem=st.mem_div)
+                self._cross_attention(st, l)
                 ops.gemm(st.ao, a.W(f'{p}.cross_attn.out_proj.weight'), st.x, B, d, d,
                          bias=a.P(f'{p}.cross_attn.out_proj.bias'), residual=st.x, workspace=st.ws)
             ops.layernorm_fwd(st.x, a.P(f'{p}.ln_2.weight'), a.P(f'{p}.ln_2.bias'), st.ln, None, None, B, d)
@@ -383,13 +365,36 @@ class GreedyDecoder:
 
     def _gq_self_attention(self, st, l: int, H: int, G: int, hd: int):
         """Self-attention of a Llama-2 / Qwen2 / Falcon decode step over the row-major cache [B][slot][G hd] (packed q | k | v rows)."""
-        B, pos_ptr = st.B, st.counters[0:1]
         q, k, v = st.qkv[:, :H * hd], st.qkv[:, H * hd:(H + G) * hd], st.qkv[:, (H + G) * hd:]
-        if st.hist is None:
-            ops.gq_decode_attention(q, k, v, st.kc[l], st.vc[l], st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd)
+        self._self_attention(st, l, st.counters[0:1], (q, k, v, H, G, hd, st.clen))
+
+    def _self_attention(self, st, l: int, pos_ptr, gq=None, slot_pos=None):
+        """st.ao = layer l's new query over its self-attention cache, the token's K/V appended at *pos_ptr.  gq = (q, k, v, H, Hkv, hd,
+        slots): the row-major cache [B][slots][Hkv hd]; None: the dense model's packed st.qkv row and head-major cache
+        [B][H][prefix + tmax][64].  Beam search (st.hist) reads the keys through its history table, a sparse layer's through slot_pos."""
+        B, d = st.B, self.eng.dec.d
+        if gq is None:
+            args = (st.qkv, 3 * d, st.kc[l], st.vc[l], st.clen * d, 64, st.ao, d, pos_ptr, 0, B, self.eng.dec.H)
+            kw = dict(append_dm=d, cache_hs=st.clen * 64)
+            ops.decode_attention(*args, **kw) if st.hist is None else ops.beam_decode_attention(*args, hist=st.hist, **kw)
         else:
-            ops.beam_gq_decode_attention(q, k, v, st.kc[l], st.vc[l], st.clen * G * hd, G * hd, st.ao, pos_ptr, 0, st.clen, B, H, G, hd,
-                                         hist=st.hist)
+            q, k, v, H, Hkv, hd, slots = gq
+            w = Hkv * hd
+            args = (q, k, v, st.kc[l], st.vc[l], slots * w, w, st.ao, pos_ptr, 0, slots, B, H, Hkv, hd)
+            ops.gq_decode_attention(*args) if st.hist is None else ops.beam_gq_decode_attention(*args, hist=st.hist, slot_pos=slot_pos)
+
+    def _cross_attention(self, st, l: int, gq_hd: Optional[int] = None):
+        """st.ao = st.q over layer l's cross-attention memory (every head its own K/V; gq_hd: head width, through the grouped-query
+        kernel; None: 64, the dense model's).  Under beam search the st.mem_div rows of an image share its memory row."""
+        B, d, H = st.B, self.eng.dec.d, self.eng.dec.H
+        kv, S = st.cross_kv[l]
+        kw = {} if st.mem_div == 1 else dict(rows_per_mem=st.mem_div)
+        if gq_hd is None:
+            args = (st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H)
+            ops.beam_decode_attention(*args, **kw) if kw else ops.decode_attention(*args)
+        else:
+            args = (st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, gq_hd)
+            ops.beam_gq_decode_attention(*args, **kw) if kw else ops.gq_decode_attention(*args)
 
     def _capture(self, st, with_head: bool, sampling: Optional[Sampling] = None, top2: bool = False):
         return _capture_launches(st.arena.device, lambda: self._step(st, with_head, sampling, top2))
@@ -469,10 +474,7 @@ class GreedyDecoder:
         assert not (return_margins and sampling is not None) and not (return_dists and sampling is None)
         self._prepare_inputs(st, images, B)
         if sampling is not None:
-            seed = sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-            lo, hi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-            st.seed.copy_(torch.tensor([lo - (1 << 32) if lo >= (1 << 31) else lo, hi - (1 << 32) if hi >= (1 << 31) else hi],
-                                       dtype=torch.int32))
+            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
             if return_dists != (st.dist is not None):         # captured sampling steps bake the dist pointer (or its absence)
                 st.dist = torch.zeros(B, dc.V, dtype=F32, device=a.device) if return_dists else None
                 st.graphs = {k: g for k, g in st.graphs.items() if k in (None, 'greedy', 'greedy_top2')}
@@ -679,9 +681,7 @@ def generate_by_recompute(model, images, prompt_ids: torch.Tensor, max_new_token
     margin = torch.zeros(B, dtype=F32, device=dev)
     seed = torch.zeros(2, dtype=torch.int32, device=dev)
     if sampling is not None:
-        sd = sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        lo, hi = sd & 0xFFFFFFFF, (sd >> 32) & 0xFFFFFFFF
-        seed.copy_(torch.tensor([lo - (1 << 32) if lo >= (1 << 31) else lo, hi - (1 << 32) if hi >= (1 << 31) else hi], dtype=torch.int32))
+        _set_seed(seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
     for t in range(P, total):
         cond = ids[:, :t] if t <= blk else ids[:, t - blk:t]                     # the reference crops the conditioning to the block
         Tc = cond.shape[1]

@@ -471,7 +471,8 @@ int i2t_moe_unpack_dw2(void* stream, const float* dW, float* gw, float* gb, int 
 int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
                             void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
                             int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd);
-/* Beam-search step over the static KV cache (reference models/generation_utils.py:10-148, BeamSearchTokenGenerator; csrc/beam.hip).
+/* Beam-search step over the static KV cache (reference models/generation_utils.py:10-148, BeamSearchTokenGenerator; csrc/beam.hip,
+ * the two attention entry points beside their greedy twins in csrc/decode.hip and csrc/family.hip).
  * R = B * W rows, batch-major (row r = b * W + w).  *len_ptr, *pos_ptr and ctrl = [done, unfinished] (int32) live in device memory,
  * so one captured hipGraph replays the step per token; once ctrl[0] is set, candidates / consolidate / advance do nothing.
  *   beam_candidates: logits f32 [R][ld] (ld % 4 == 0, 16-byte aligned) of the last position -> no-repeat-n-gram ban over
