@@ -177,22 +177,39 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
 // HF NoRepeatNGramLogitsProcessor + argmax for one caption per workgroup.  A row with no finite allowed column (all banned)
 // gets token 0, torch.argmax's answer for a row of -inf, and margin 0.
 constexpr int BAN_THREADS = 1024;
-template <bool F32>
+// one more column for a thread's running (max, sum exp): the online-softmax update
+__device__ __forceinline__ void lse_add(float& mx, float& se, float v) {
+    if (v > mx) {
+        se = se * __expf(mx - v) + 1.f;                 // (mx = -inf: se is 0 and stays 0 through the product)
+        mx = v;
+    } else if (v > -INFINITY) {
+        se += __expf(v - mx);
+    }
+}
+// LP (i2t_ngram_ban_argmax_lp, a caption step): the same choice, and tok_lp[b][len] = z[chosen] - logsumexp(z[b][:V]) over the RAW
+// row -- the ban does not enter -- from an online (max, sum exp) pass folded into the scan: per thread in its scan order, the
+// lanes by a fixed xor tree, the waves in order.  Nothing is written once *done is set.
+template <bool F32, bool LP>
 __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const void* __restrict__ logits, int ld,
                                                                        int64_t* __restrict__ ids, int ids_ld,
                                                                        const int* __restrict__ len_ptr,
                                                                        const int* __restrict__ ngram_sizes, int n_sizes,
-                                                                       int V, float* __restrict__ margin_out) {
+                                                                       int V, float* __restrict__ margin_out,
+                                                                       const int* __restrict__ done, float* __restrict__ tok_lp, int lp_ld) {
     extern __shared__ unsigned dyn_lds[];              // ban bitmap, ceil(V / 32) words
     __shared__ float rv[BAN_THREADS / 64], rv2[BAN_THREADS / 64];
     __shared__ int ri[BAN_THREADS / 64];
+    __shared__ float rmx[LP ? BAN_THREADS / 64 : 1], rse[LP ? BAN_THREADS / 64 : 1];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (LP)
+        if (*done) return;                              // block-uniform, before any barrier
     const int len = *len_ptr;
     int64_t* row = ids + (size_t)b * ids_ld;
     unsigned* banbits = dyn_lds;
     build_ban_bitmap(banbits, row, len, ngram_sizes, n_sizes, V, BAN_THREADS);
     float best = -INFINITY, second = -INFINITY;
     int bi = 0x7fffffff;
+    float mx = -INFINITY, se = 0.f;                     // (LP) the raw row's online softmax pair
     // fp32 rows with ld % 4 == 0 (the decode path pads to 8): 16-byte loads, 4 consecutive columns per lane per step
     // (the scalar scan ran at ~2.3 TB/s).  Per lane the columns are still visited in ascending order: first index wins ties.
     const bool vec4 = F32 && (ld & 3) == 0 && ((uintptr_t)logits & 15) == 0;
@@ -204,6 +221,7 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
         for (int e = 0; e < 4; ++e) {
             const float v = ((nib >> e) & 1u) ? -INFINITY : q[e];
             const int c = c4 + e;
+            if constexpr (LP) lse_add(mx, se, q[e]);
             if (v > best) {
                 second = best;
                 best = v;
@@ -216,6 +234,7 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
     for (int c = vend + tid; c < V; c += BAN_THREADS) {
         float v = F32 ? reinterpret_cast<const float*>(logits)[(size_t)b * ld + c]
                       : bf16_to_f32(reinterpret_cast<const bf16_t*>(logits)[(size_t)b * ld + c]);
+        if constexpr (LP) lse_add(mx, se, v);
         if (ban_bit(banbits, c)) v = -INFINITY;
         if (v > best) {                                   // strided ascending scan: first index wins ties
             second = best;
@@ -239,6 +258,14 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
         }
     }
     const int w = tid >> 6;
+    if constexpr (LP) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+        if ((tid & 63) == 0) {
+            rmx[w] = mx;
+            rse[w] = se;
+        }
+    }
     if ((tid & 63) == 0) {
         rv[w] = best;
         rv2[w] = second;
@@ -258,6 +285,13 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
         const bool none = bi == 0x7fffffff;                  // every column banned or -inf
         row[len] = none ? 0 : bi;
         if (margin_out) margin_out[b] = none ? 0.f : best - second;
+        if constexpr (LP) {
+            for (int k = 1; k < BAN_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
+            const int tok = none ? 0 : bi;
+            const float z = F32 ? reinterpret_cast<const float*>(logits)[(size_t)b * ld + tok]
+                                : bf16_to_f32(reinterpret_cast<const bf16_t*>(logits)[(size_t)b * ld + tok]);
+            tok_lp[(size_t)b * lp_ld + len] = z - (mx + logf(se));
+        }
     }
 }
 
@@ -268,15 +302,24 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
 // the hidden row with the head's rows, banned columns left out.  Such segments are marked in an LDS bitmap of ceil(nseg / 32) words
 // behind the ban bitmap, so however many there are, none is dropped; each wave re-evaluates the marked segments of every fourth word.
 // One caption per workgroup; a row with every column banned gets token 0.
+// LP (i2t_top2_ngram_argmax_lp, a caption step after i2t_gemm_bf16_top2_lse): the same choice, and tok_lp[b][len] = z[chosen] - lse with
+// lse from the segments' (v1, se) pairs -- one wave, lane l merges segments l, l + 64, ... in ascending order, then a fixed xor tree, as
+// lse_token_logprob_kernel below -- and z[chosen] re-evaluated in fp32 from the bf16 operands (the chosen column may be token 0 of a
+// row with everything banned, of which the segments hold nothing).  The ban does not enter the lse.  Nothing is written once *done is set.
 constexpr int T2_THREADS = 256;
+template <bool LP>
 __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32x4* __restrict__ top2, int nseg, const bf16_t* __restrict__ hid,
                                                                         int ld_h, const bf16_t* __restrict__ W, int ldw, int d,
                                                                         int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
-                                                                        const int* __restrict__ ngram_sizes, int n_sizes, int V) {
+                                                                        const int* __restrict__ ngram_sizes, int n_sizes, int V,
+                                                                        const float* __restrict__ seg_se, const int* __restrict__ done,
+                                                                        float* __restrict__ tok_lp, int lp_ld) {
     extern __shared__ unsigned dyn_lds[];              // ban bitmap (ceil(V / 32) words), then the redo bitmap (ceil(nseg / 32) words)
     __shared__ float rv[T2_THREADS / 64];
     __shared__ int ri[T2_THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (LP)
+        if (*done) return;                              // block-uniform, before any barrier
     const int len = *len_ptr;
     int64_t* row = ids + (size_t)b * ids_ld;
     unsigned* banbits = dyn_lds;
@@ -339,6 +382,27 @@ __global__ __launch_bounds__(T2_THREADS) void top2_ngram_argmax_kernel(const f32
     if (tid == 0) {
         for (int k = 1; k < T2_THREADS / 64; ++k) offer(rv[k], ri[k]);
         row[len] = bi == 0x7fffffff ? 0 : bi;               // every column banned or -inf: torch.argmax's 0
+        if constexpr (LP) ri[0] = bi == 0x7fffffff ? 0 : bi;
+    }
+    if constexpr (LP) {
+        __syncthreads();
+        if (wave != 0) return;
+        const int tok = ri[0];
+        float mx = -INFINITY, se = 0.f;
+        for (int sgm = lane; sgm < nseg; sgm += 64) lse_merge(mx, se, top2[(size_t)b * nseg + sgm][0], seg_se[(size_t)b * nseg + sgm]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+        const bf16_t* wr = W + (size_t)tok * ldw;
+        const bf16_t* hr = hid + (size_t)b * ld_h;
+        float z = 0.f;
+        for (int k = 8 * lane; k < d; k += 8 * 64) {
+            const u32x4 wv = *reinterpret_cast<const u32x4*>(wr + k), hv = *reinterpret_cast<const u32x4*>(hr + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) z += bf16lo(wv[e]) * bf16lo(hv[e]) + bf16hi(wv[e]) * bf16hi(hv[e]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+        if (lane == 0) tok_lp[(size_t)b * lp_ld + len] = z - (mx + logf(se));
     }
 }
 
@@ -381,6 +445,39 @@ __global__ __launch_bounds__(64 * LSE_WAVES) void lse_token_logprob_kernel(const
     if (lane == 0) {
         lse[m] = l;
         logprob[m] = live ? scale * z - l : 0.f;
+    }
+}
+
+// The finish rule of a caption step, after the step's token landed at ids[r][len]: a row that finished earlier gets the
+// pad id and log-prob 0 there; a row whose new token is EOS is finished, its length len + 1 (the EOS kept).  ctrl[1] = rows still
+// unfinished (i2t_beam_advance raises ctrl[0] when it is 0).  One workgroup, block reduction, no atomics.
+constexpr int FIN_THREADS = 1024;
+__global__ __launch_bounds__(FIN_THREADS) void caption_finish_kernel(int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
+                                                                     int eos, int64_t pad, int* __restrict__ finished, int* __restrict__ lengths,
+                                                                     float* __restrict__ tok_lp, int lp_ld, int* __restrict__ ctrl, int R) {
+    __shared__ int red[FIN_THREADS / 64];
+    if (ctrl[0]) return;                                 // block-uniform: no thread writes ctrl[0]
+    const int len = *len_ptr, tid = threadIdx.x;
+    int live = 0;
+    for (int r = tid; r < R; r += FIN_THREADS) {
+        if (finished[r]) {
+            ids[(size_t)r * ids_ld + len] = pad;
+            tok_lp[(size_t)r * lp_ld + len] = 0.f;
+        } else if (eos >= 0 && ids[(size_t)r * ids_ld + len] == (int64_t)eos) {
+            finished[r] = 1;
+            lengths[r] = len + 1;
+        } else {
+            ++live;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = live;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int k = 0; k < FIN_THREADS / 64; ++k) t += red[k];
+        ctrl[1] = eos < 0 ? R : t;
     }
 }
 
@@ -451,12 +548,24 @@ extern "C" int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, in
     const size_t lds = (size_t)(V + 31) / 32 * sizeof(unsigned);
     I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_ngram_ban_argmax: vocabulary %d: the ban bitmap exceeds %d bytes of LDS", V, BAN_LDS_MAX);
     if (logits_is_f32)
-        hipLaunchKernelGGL(ngram_ban_argmax_kernel<true>, dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
-                           ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out);
+        hipLaunchKernelGGL((ngram_ban_argmax_kernel<true, false>), dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
+                           ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out, nullptr, nullptr, 0);
     else
-        hipLaunchKernelGGL(ngram_ban_argmax_kernel<false>, dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
-                           ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out);
+        hipLaunchKernelGGL((ngram_ban_argmax_kernel<false, false>), dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids,
+                           ids_ld, len_ptr, ngram_sizes, n_sizes, V, margin_out, nullptr, nullptr, 0);
     I2T_CHECK_LAUNCH("i2t_ngram_ban_argmax");
+    return I2T_OK;
+}
+
+extern "C" int i2t_ngram_ban_argmax_lp(void* stream, const float* logits, int ld, int64_t* ids, int ids_ld, const int* len_ptr,
+                                       const int* ngram_sizes, int n_sizes, int B, int V, const int* done, float* tok_lp, int lp_ld) {
+    I2T_REQUIRE(logits && ids && len_ptr && done && tok_lp && B > 0 && V > 0 && ld >= V && (n_sizes == 0 || ngram_sizes),
+                "i2t_ngram_ban_argmax_lp: bad args");
+    const size_t lds = (size_t)(V + 31) / 32 * sizeof(unsigned);
+    I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_ngram_ban_argmax_lp: vocabulary %d: the ban bitmap exceeds %d bytes of LDS", V, BAN_LDS_MAX);
+    hipLaunchKernelGGL((ngram_ban_argmax_kernel<true, true>), dim3(B), dim3(BAN_THREADS), lds, (hipStream_t)stream, logits, ld, ids, ids_ld,
+                       len_ptr, ngram_sizes, n_sizes, V, nullptr, done, tok_lp, lp_ld);
+    I2T_CHECK_LAUNCH("i2t_ngram_ban_argmax_lp");
     return I2T_OK;
 }
 
@@ -468,9 +577,37 @@ extern "C" int i2t_top2_ngram_argmax(void* stream, const float* top2, int nseg, 
                 "i2t_top2_ngram_argmax: hidden / head rows must be 16-byte aligned, d %% 8 == 0");
     const size_t lds = ((size_t)(V + 31) / 32 + (nseg + 31) / 32) * sizeof(unsigned);
     I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_top2_ngram_argmax: vocabulary %d: the ban bitmaps exceed %d bytes of LDS", V, BAN_LDS_MAX);
-    hipLaunchKernelGGL(top2_ngram_argmax_kernel, dim3(B), dim3(T2_THREADS), lds, (hipStream_t)stream, (const f32x4*)top2, nseg,
-                       (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, V);
+    hipLaunchKernelGGL(top2_ngram_argmax_kernel<false>, dim3(B), dim3(T2_THREADS), lds, (hipStream_t)stream, (const f32x4*)top2, nseg,
+                       (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, V,
+                       nullptr, nullptr, nullptr, 0);
     I2T_CHECK_LAUNCH("i2t_top2_ngram_argmax");
+    return I2T_OK;
+}
+
+extern "C" int i2t_top2_ngram_argmax_lp(void* stream, const float* top2, const float* se, int nseg, const void* hidden, int ld_hidden,
+                                        const void* w_head, int ld_w, int d, int64_t* ids, int ids_ld, const int* len_ptr, const int* ngram_sizes,
+                                        int n_sizes, int B, int V, const int* done, float* tok_lp, int lp_ld) {
+    I2T_REQUIRE(top2 && se && hidden && w_head && ids && len_ptr && done && tok_lp && B > 0 && V > 0 && nseg == (V + 63) / 64 &&
+                    (n_sizes == 0 || ngram_sizes),
+                "i2t_top2_ngram_argmax_lp: bad args (nseg must be ceil(V / 64))");
+    I2T_REQUIRE(d > 0 && d % 8 == 0 && (ld_hidden & 7) == 0 && (ld_w & 7) == 0 && ld_hidden >= d && ld_w >= d && ALIGNED16(top2) &&
+                    ALIGNED16(hidden) && ALIGNED16(w_head),
+                "i2t_top2_ngram_argmax_lp: hidden / head rows must be 16-byte aligned, d %% 8 == 0");
+    const size_t lds = ((size_t)(V + 31) / 32 + (nseg + 31) / 32) * sizeof(unsigned);
+    I2T_REQUIRE(lds <= BAN_LDS_MAX, "i2t_top2_ngram_argmax_lp: vocabulary %d: the ban bitmaps exceed %d bytes of LDS", V, BAN_LDS_MAX);
+    hipLaunchKernelGGL(top2_ngram_argmax_kernel<true>, dim3(B), dim3(T2_THREADS), lds, (hipStream_t)stream, (const f32x4*)top2, nseg,
+                       (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, V, se, done,
+                       tok_lp, lp_ld);
+    I2T_CHECK_LAUNCH("i2t_top2_ngram_argmax_lp");
+    return I2T_OK;
+}
+
+extern "C" int i2t_caption_finish(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, int eos, int64_t pad, int* finished, int* lengths,
+                                  float* tok_lp, int lp_ld, int* ctrl, int R) {
+    I2T_REQUIRE(ids && len_ptr && finished && lengths && tok_lp && ctrl && R > 0 && ids_ld > 0 && lp_ld > 0, "i2t_caption_finish: bad args");
+    hipLaunchKernelGGL(caption_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr, eos, pad, finished,
+                       lengths, tok_lp, lp_ld, ctrl, R);
+    I2T_CHECK_LAUNCH("i2t_caption_finish");
     return I2T_OK;
 }
 

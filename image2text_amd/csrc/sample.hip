@@ -44,11 +44,16 @@ __device__ __forceinline__ int block_sum_i(int v, int* red) {
     return t;
 }
 
-template <int EPT>
+// LP (i2t_sample_token_lp, a caption step): the same draw, and tok_lp[b][len] = z[drawn] - logsumexp(z[b][:V]) of the RAW row -- no
+// temperature, ban, crop or nucleus -- whose maximum and sum of exp's are taken while the row is loaded, before the filters transform
+// the registers: a thread's online pair, then two block reductions (the maximum; the rescaled sums).  Nothing is written once *done
+// is set.
+template <int EPT, bool LP>
 __global__ __launch_bounds__(ST) void sample_kernel(const float* __restrict__ logits, int ld, int64_t* __restrict__ ids, int ids_ld,
                                                     const int* __restrict__ len_ptr, const int* __restrict__ ngram_sizes,
                                                     int n_sizes, int V, float temperature, int top_k, float nucleus_p,
-                                                    const unsigned* __restrict__ seed, float* __restrict__ dist_out, int dist_ld) {
+                                                    const unsigned* __restrict__ seed, float* __restrict__ dist_out, int dist_ld,
+                                                    const int* __restrict__ done, float* __restrict__ tok_lp, int lp_ld) {
     __shared__ unsigned banbits[EPT * ST / 32];
     __shared__ float redf[SW];
     __shared__ int redi[SW];
@@ -57,6 +62,8 @@ __global__ __launch_bounds__(ST) void sample_kernel(const float* __restrict__ lo
     __shared__ float sh_target;
     __shared__ int sh_slot, sh_tok;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (LP)
+        if (*done) return;                              // block-uniform, before any barrier
     const int len = *len_ptr;
     int64_t* row = ids + (size_t)b * ids_ld;
 
@@ -80,15 +87,31 @@ __global__ __launch_bounds__(ST) void sample_kernel(const float* __restrict__ lo
     // ---- the row: element i = k * ST + tid (coalesced), scaled by 1 / temperature, banned / out-of-range -> -inf
     float x[EPT];
     const float* src = logits + (size_t)b * ld;
+    float raw_mx = -INFINITY, raw_se = 0.f;                  // (LP) this thread's online (max, sum exp) of the raw logits
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
         const int i = k * ST + tid;
         float v = -INFINITY;
         if (i < V) {
-            v = src[i] / temperature;
+            const float raw = src[i];
+            if constexpr (LP) {
+                if (raw > raw_mx) {
+                    raw_se = raw_se * __expf(raw_mx - raw) + 1.f;
+                    raw_mx = raw;
+                } else if (raw > -INFINITY) {
+                    raw_se += __expf(raw - raw_mx);
+                }
+            }
+            v = raw / temperature;
             if ((banbits[i >> 5] >> (i & 31)) & 1u) v = -INFINITY;
         }
         x[k] = v;
+    }
+    float raw_lse = 0.f;
+    if constexpr (LP) {
+        const float M = block_max(raw_mx, redf);
+        const float S = block_sum(raw_mx > -INFINITY ? raw_se * __expf(raw_mx - M) : 0.f, redf);
+        raw_lse = M + logf(S);
     }
 
     // ---- top-k: k-th largest value by bisection on the key bits; everything below it is cropped.  The row is turned into its
@@ -267,14 +290,19 @@ __global__ __launch_bounds__(ST) void sample_kernel(const float* __restrict__ lo
         __syncthreads();
         tok = sh_tok;
     }
-    if (tid == 0) row[len] = (int64_t)(tok < 0 ? 0 : tok);
+    if (tid == 0) {
+        row[len] = (int64_t)(tok < 0 ? 0 : tok);
+        if constexpr (LP) tok_lp[(size_t)b * lp_ld + len] = src[tok < 0 ? 0 : tok] - raw_lse;
+    }
 }
 
 }  // namespace
 
-#define LAUNCH_SAMPLE(E)                                                                                                        \
-    hipLaunchKernelGGL(sample_kernel<E>, dim3(B), dim3(ST), 0, (hipStream_t)stream, logits, ld, ids, ids_ld, len_ptr, ngram_sizes, \
-                       n_sizes, V, temperature, top_k, nucleus_p, seed, dist_out, dist_ld)
+#define LAUNCH_SAMPLE_(E, LP, DONE, TOK_LP, LP_LD)                                                                                          \
+    hipLaunchKernelGGL((sample_kernel<E, LP>), dim3(B), dim3(ST), 0, (hipStream_t)stream, logits, ld, ids, ids_ld, len_ptr, ngram_sizes, \
+                       n_sizes, V, temperature, top_k, nucleus_p, seed, dist_out, dist_ld, DONE, TOK_LP, LP_LD)
+#define LAUNCH_SAMPLE(E) LAUNCH_SAMPLE_(E, false, nullptr, nullptr, 0)
+#define LAUNCH_SAMPLE_LP(E) LAUNCH_SAMPLE_(E, true, done, tok_lp, lp_ld)
 
 extern "C" int i2t_sample_token(void* stream, const float* logits, int ld, int64_t* ids, int ids_ld, const int* len_ptr,
                                 const int* ngram_sizes, int n_sizes, int B, int V, float temperature, int top_k, float nucleus_p,
@@ -290,5 +318,23 @@ extern "C" int i2t_sample_token(void* stream, const float* logits, int ld, int64
     else if (ept <= 100) LAUNCH_SAMPLE(100);
     else LAUNCH_SAMPLE(128);
     I2T_CHECK_LAUNCH("i2t_sample_token");
+    return I2T_OK;
+}
+
+extern "C" int i2t_sample_token_lp(void* stream, const float* logits, int ld, int64_t* ids, int ids_ld, const int* len_ptr,
+                                   const int* ngram_sizes, int n_sizes, int B, int V, float temperature, int top_k, float nucleus_p,
+                                   const unsigned* seed, float* dist_out, int dist_ld, const int* done, float* tok_lp, int lp_ld) {
+    I2T_REQUIRE(logits && ids && len_ptr && seed && done && tok_lp && B > 0 && V > 0 && (n_sizes == 0 || ngram_sizes),
+                "i2t_sample_token_lp: bad args");
+    I2T_REQUIRE(temperature > 0.f, "i2t_sample_token_lp: temperature must be positive");
+    I2T_REQUIRE(V <= 128 * ST, "i2t_sample_token_lp: vocabulary %d exceeds the register-resident row (%d)", V, 128 * ST);
+    I2T_REQUIRE(!dist_out || dist_ld >= V, "i2t_sample_token_lp: dist_ld < V");
+    const int ept = (V + ST - 1) / ST;
+    if (ept <= 2) LAUNCH_SAMPLE_LP(2);
+    else if (ept <= 16) LAUNCH_SAMPLE_LP(16);
+    else if (ept <= 64) LAUNCH_SAMPLE_LP(64);
+    else if (ept <= 100) LAUNCH_SAMPLE_LP(100);
+    else LAUNCH_SAMPLE_LP(128);
+    I2T_CHECK_LAUNCH("i2t_sample_token_lp");
     return I2T_OK;
 }

@@ -638,6 +638,167 @@ class BeamDecoder(GreedyDecoder):
         return (ids, scores, draws[:L - P]) if record else (ids, scores)
 
 
+class GeneratedCaptions(NamedTuple):
+    """What ``generate_captions`` returns; rows are batch-major (caption n of image b)."""
+    ids: torch.Tensor                   # int64 [B, N, L]: prompt, new tokens up to and including the first emitted EOS, then the pad id
+    lengths: torch.Tensor               # int32 [B, N]: prompt + new tokens up to and including that EOS (P + max_new_tokens without one)
+    token_logprobs: torch.Tensor        # fp32 [B, N, L - P]: log_softmax of the step's raw logits at the chosen token; 0.0 past the EOS
+    logprob: torch.Tensor               # fp32 [B, N]: the row sums
+
+
+def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional[int] = None, token_logprobs: Optional[np.ndarray] = None):
+    """The finish rule of ``generate_captions`` on the host (numpy): what i2t_caption_finish does step by step on the device, applied to
+    whole rows.  ``ids`` [R, P + T]: the prompt and the T tokens a chooser emitted for every row (it goes on emitting after an EOS).  A row
+    is finished once it has EMITTED ``eos`` -- an EOS inside the prompt does not count --, that EOS is kept, later columns hold ``pad``
+    (default: the EOS id) and log-prob 0.0, a row without one has length P + T; ``eos`` None: no rule.  The steps end once every row has
+    finished, so L = lengths.max().  -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - P] or None)"""
+    ids = np.array(ids)
+    R, total = ids.shape
+    lengths = np.full(R, total, dtype=np.int32)
+    if eos is not None:
+        pad = eos if pad is None else pad
+        for r in range(R):
+            hit = np.flatnonzero(ids[r, P:] == eos)
+            if hit.size:
+                lengths[r] = P + int(hit[0]) + 1
+    L = int(lengths.max()) if R else total
+    ids = ids[:, :L]
+    lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - P]
+    for r in range(R if eos is not None else 0):
+        ids[r, lengths[r]:] = pad
+        if lp is not None:
+            lp[r, lengths[r] - P:] = 0.0
+    return ids, lengths, lp
+
+
+class CaptionDecoder(GreedyDecoder):
+    """``generate_captions`` on the static KV cache: R = B * N rows (batch-major, r = b * N + n) through GreedyDecoder's buffers and layer
+    sequence, one captured hipGraph replay per token.  The encoder and the cross K/V run once per image (rows_per_mem = N); the
+    self-attention cache is the identity one (no history table).  A step is _body -> _final_norm -> head and choice with the token's
+    log-prob (i2t_gemm_bf16_top2_lse + i2t_top2_ngram_argmax_lp; or fp32 logits + i2t_ngram_ban_argmax_lp / i2t_sample_token_lp) ->
+    i2t_caption_finish -> i2t_beam_advance.  Once every row has emitted EOS the device raises ctrl[0]; from then on no kernel of a
+    replay writes ids, tok_lp, finished or lengths, and the host, which reads that word every ``poll_every`` steps,
+    stops launching.  The decoder keeps its own state and graphs: nothing here touches what ``generate`` uses."""
+
+    last_replays = 0                    # full-step replays the last call launched (tests, tools)
+
+    def _build_captions(self, B: int, N: int, ids_ld: int):
+        R = B * N
+        st = self._build(R, ids_ld, mem_rows=B)
+        dev = st.arena.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        st.N, st.images = N, B
+        st.mem_div = N
+        st.ctrl = torch.zeros(2, **i32)                         # [done, unfinished rows]
+        st.finished, st.lengths = torch.zeros(R, **i32), torch.zeros(R, **i32)
+        st.tok_lp = torch.zeros(R, ids_ld, dtype=F32, device=dev)
+        st.top2 = st.seg_se = None
+        return st
+
+    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int):
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        R, d = st.B, dc.d
+        len_ptr, done = st.counters[1:2], st.ctrl[0:1]
+        nn = st.ngrams.numel()
+        self._body(st)
+        self._final_norm(st)
+        if top2:
+            ops.gemm_top2_lse(st.hid, a.W(eng.n_head), st.top2, st.seg_se, R, dc.V, d)
+            ops.top2_ngram_argmax_lp(st.top2, st.seg_se, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, d, done,
+                                     st.tok_lp)
+        else:
+            ops.gemm(st.hid, a.W(eng.n_head), st.logits, R, dc.V, d, workspace=st.ws)
+            if sampling is None:
+                ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
+            else:
+                ops.sample_token_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, sampling.temperature,
+                                    sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
+        ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    @torch.no_grad()
+    def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
+                          num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
+                          use_graph: bool = True) -> GeneratedCaptions:
+        eng = self.eng
+        dc = eng.dec
+        N = int(num_return_sequences)
+        check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
+        if not dc.causal:
+            raise ValueError('CaptionDecoder needs a causal decoder')
+        a = eng.prepare(False)
+        prompt_ids = prompt_ids.to(a.device)
+        B, P = prompt_ids.shape
+        R, total = B * N, P + max_new_tokens
+        pad = (0 if eos is None else eos) if pad is None else pad
+        st = self._state
+        if (st is None or st.B != R or st.N != N or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch):
+            self._state = None
+            st = self._state = self._build_captions(B, N, max(total, dc.block))
+        if total > st.tmax:
+            raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({st.tmax})')
+        self._prepare_inputs(st, images, B, N)
+        if sampling is not None:
+            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+        top2 = sampling is None and TOP2_HEAD and dc.d % 128 == 0          # as generate() chooses the form of the greedy head
+        if top2 and st.top2 is None:
+            nseg = (dc.V + 63) // 64
+            st.top2 = torch.zeros(R, nseg, 4, dtype=F32, device=a.device)
+            st.seg_se = torch.zeros(R, nseg, dtype=F32, device=a.device)
+        # eos and pad are kernel arguments: a captured step holds them
+        full_key = (('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key(), eos, pad)
+        prompt_rows = prompt_ids.repeat_interleave(N, dim=0) if N > 1 else prompt_ids
+
+        def reset():
+            st.ids.zero_()
+            st.ids[:, :P] = prompt_rows
+            st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
+            st.ctrl.zero_()
+            st.finished.zero_()
+            st.lengths.fill_(total)
+            st.tok_lp.zero_()
+        reset()
+        if use_graph and (full_key not in st.graphs or None not in st.graphs):
+            self._caption_step(st, sampling, top2, eos, pad)  # warm up eagerly once (code objects load before capture)
+            self._step(st, False)
+            if full_key not in st.graphs:
+                st.graphs[full_key] = _capture_launches(a.device, lambda: self._caption_step(st, sampling, top2, eos, pad))
+            if None not in st.graphs:
+                st.graphs[None] = self._capture(st, False)
+            reset()
+        for _ in range(P - 1):                                # prompt tokens before the last: fill the cache only
+            st.graphs[None].launch() if use_graph else self._step(st, False)
+        replays = 0
+        for i in range(max_new_tokens):
+            st.graphs[full_key].launch() if use_graph else self._caption_step(st, sampling, top2, eos, pad)
+            replays += 1
+            if eos is not None and poll_every and replays % poll_every == 0 and replays < max_new_tokens:
+                if int(st.ctrl[0:1].item()):                  # one 4-byte copy: every row has emitted EOS
+                    break
+        self.last_replays = replays
+        lengths = st.lengths.clone()
+        L = int(lengths.max().item()) if max_new_tokens else P          # the final host sync
+        ids = st.ids[:, :L].reshape(B, N, L).clone()
+        tok_lp = st.tok_lp[:, P:L].reshape(B, N, L - P).clone()
+        return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1))
+
+
+def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int):
+    """the refusals of generate_captions that need no device"""
+    if N < 1:
+        raise ValueError(f'num_return_sequences = {N}: at least one caption per image')
+    if sampling is None and N > 1:
+        raise ValueError(f'greedy decoding with num_return_sequences = {N}: the {N} rows of an image would be identical; sample instead')
+    if sampling is not None and not sampling.temperature > 0:
+        raise ValueError('sampling needs a positive temperature')
+    if eos is not None and eos < 0:
+        raise ValueError(f'eos_token_id = {eos}')
+    if pad is not None and pad < 0:
+        raise ValueError(f'pad_token_id = {pad}')
+    if poll_every < 0 or max_new_tokens < 0:
+        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+
+
 def _set_seed(buf: torch.Tensor, seed: int):
     """the two 32-bit words of a 64-bit seed into an int32 device buffer"""
     lo, hi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF

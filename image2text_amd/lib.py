@@ -69,6 +69,11 @@ SIGNATURES = {
     'i2t_lse_token_logprob': [P, P, I, P, I, P, I, I, F, P, I64, P, P, I, I],
     'i2t_embed_step': [P, P, I, P, P, P, P, I, I, I, I],
     'i2t_advance': [P, P, I, I],
+    'i2t_gemm_bf16_top2_lse': [P, P, I, P, I, I, I, I, P, P, I],
+    'i2t_top2_ngram_argmax_lp': [P, P, P, I, P, I, P, I, I, P, I, P, P, I, I, I, P, P, I],
+    'i2t_ngram_ban_argmax_lp': [P, P, I, P, I, P, P, I, I, I, P, P, I],
+    'i2t_sample_token_lp': [P, P, I, P, I, P, P, I, I, I, F, I, F, P, P, I, P, P, I],
+    'i2t_caption_finish': [P, P, I, P, I, I64, P, P, P, I, P, I],
     'i2t_gq_attention_fwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, I, U, U, F, P, P, I, I],
     'i2t_gq_attention_bwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, L, I, P, P, P, L, I, P, L, I, P, L, I, I, I, I, I, I, I, I, U, U, F, P, P, I,
                              U, U, F],
@@ -135,7 +140,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 

@@ -150,6 +150,7 @@ class VisionEncoderDecoder(nn.Module):
         object.__setattr__(self, '_engine', HotPath(self))
         object.__setattr__(self, '_hook', None)
         object.__setattr__(self, '_greedy', None)
+        object.__setattr__(self, '_captioner', None)
         if config.chkpt_path is not None:
             update_state_dict_from_partial_checkpoint(self, config.chkpt_path, map_location=None)
 
@@ -230,6 +231,50 @@ class VisionEncoderDecoder(nn.Module):
         if top_k == 1 and nucleus_p is None:
             return self._greedy.generate(images, prompt_ids, max_new_tokens)
         return self._greedy.generate(images, prompt_ids, max_new_tokens, sampling=Sampling(temperature, top_k, nucleus_p))
+
+    @torch.no_grad()
+    def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
+                          temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8):
+        """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
+        counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
+        logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
+        ``top_k == 1`` without a nucleus is greedy, as in ``generate`` (with N > 1: ValueError, the rows would be identical); anything
+        else samples (``decoding.Sampling``; ``seed`` None: drawn under ``torch.manual_seed`` as ``generate`` draws it).  A row is
+        finished once it has EMITTED ``eos_token_id``: the EOS is kept with its log-prob, ``lengths`` counts the prompt and the new tokens
+        up to and including it, later columns hold ``pad_token_id`` (default: the EOS id) and log-prob exactly 0.0; a row without one
+        has length P + max_new_tokens, and so has every row when ``eos_token_id`` is None; L = lengths.max().
+        ``token_logprobs`` is ``score``'s quantity at temperature 1 -- log_softmax of the step's logits over the whole vocabulary at the
+        chosen token: n-gram ban, crop, nucleus and sampling temperature do not enter --, ``logprob`` its row sum.
+        The encoder and the cross-attention K/V run once per image whatever N.  The decode loop stops launching steps once every row
+        has finished: the host reads one device word every ``poll_every`` steps (0: never, all steps are launched), its only
+        synchronisation besides the final read of the lengths.
+        A NON-causal decoder has no cache: this is then TWO passes -- ``generate_by_recompute`` over N-times repeated images with the
+        finish rule applied on the host, then ``score`` on the result for the log-probs."""
+        from ..decoding import CaptionDecoder, Sampling, apply_finish_rule, check_caption_args, generate_by_recompute
+        N = int(num_return_sequences)
+        sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
+        check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+        B, P = prompt_ids.shape
+        blk_size = self.decoder.block_size - self.space_for_prompt
+        if P + max_new_tokens > blk_size:
+            raise ValueError(f'prompt + new tokens ({P + max_new_tokens}) exceed the text window ({blk_size})')
+        dev = next(self.parameters()).device
+        prompt_ids = prompt_ids.to(dev)
+        if self._engine.dec.causal:
+            if self._captioner is None:
+                object.__setattr__(self, '_captioner', CaptionDecoder(self))
+            return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every)
+        from ..decoding import GeneratedCaptions
+        images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
+        raw = generate_by_recompute(self, images_rep, prompt_ids.repeat_interleave(N, dim=0), max_new_tokens, sampling)
+        ids, lengths, _ = apply_finish_rule(raw.cpu().numpy(), P, eos_token_id, pad_token_id)
+        ids, lengths = torch.from_numpy(ids).to(dev), torch.from_numpy(lengths).to(dev)
+        L = ids.shape[1]
+        labels = next_token_labels(ids, -100)
+        labels[torch.arange(L, device=dev)[None, :] >= (lengths[:, None] - 1)] = -100            # nothing follows a row's last token
+        lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, P - 1:L - 1] if L > P else torch.zeros(B * N, 0, device=dev)
+        lp = lp.reshape(B, N, L - P).contiguous()
+        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1))
 
 
     @torch.no_grad()

@@ -760,6 +760,65 @@ def advance(counters, delta=1):
     _l.check(_lib().i2t_advance(_stream(), _p(counters), counters.numel(), delta), 'i2t_advance')
 
 
+def gemm_top2_lse(a, b, top2, se, M, N, K):
+    """gemm_top2 that also leaves se f32 [M, ceil(N/64)]: the segment's sum of exp(z - v1) (include/i2t.h::i2t_gemm_bf16_top2_lse)"""
+    _need_cuda(a, b, top2, se)
+    nseg = (N + 63) // 64
+    assert a.dtype == BF16 and b.dtype == BF16 and top2.dtype == F32 and se.dtype == F32 and top2.is_contiguous() and se.is_contiguous()
+    assert top2.shape[-1] == 4 and top2.shape[-2] == nseg and top2.numel() >= M * nseg * 4 and se.shape[-1] == nseg and se.numel() >= M * nseg
+    assert a.stride(-1) == 1 and b.stride(-1) == 1 and a.shape[0] >= M and b.shape[0] >= N
+    _l.check(_lib().i2t_gemm_bf16_top2_lse(_stream(), _p(a), a.stride(0), _p(b), b.stride(0), M, N, K, _p(top2), _p(se), nseg),
+             'i2t_gemm_bf16_top2_lse')
+    return top2, se
+
+
+def _lp_args(ids, ids_ld, done, tok_lp, B):
+    """the shared checks of the caption-step choosers: tok_lp f32 rows addressed like the id rows, done an int32 device word"""
+    _need_cuda(ids, done, tok_lp)
+    assert ids.dtype == torch.long and tok_lp.dtype == F32 and done.dtype == torch.int32 and done.numel() >= 1
+    assert tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= B and tok_lp.shape[1] >= ids_ld
+
+
+def top2_ngram_argmax_lp(top2, se, hidden, w_head, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, d, done, tok_lp):
+    """top2_ngram_argmax + tok_lp[b][len] = log-prob of the chosen token; no write once *done (include/i2t.h::i2t_top2_ngram_argmax_lp)"""
+    _need_cuda(top2, se, hidden, w_head)
+    _lp_args(ids, ids_ld, done, tok_lp, B)
+    assert top2.dtype == F32 and se.dtype == F32 and hidden.dtype == BF16 and w_head.dtype == BF16
+    _l.check(_lib().i2t_top2_ngram_argmax_lp(_stream(), _p(top2), _p(se), (V + 63) // 64, _p(hidden), hidden.stride(0), _p(w_head),
+                                             w_head.stride(0), d, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V, _p(done),
+                                             _p(tok_lp), tok_lp.stride(0)), 'i2t_top2_ngram_argmax_lp')
+
+
+def ngram_ban_argmax_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, done, tok_lp):
+    """ngram_ban_argmax over fp32 logits + tok_lp[b][len]; no write once *done (include/i2t.h::i2t_ngram_ban_argmax_lp)"""
+    _need_cuda(logits)
+    _lp_args(ids, ids_ld, done, tok_lp, B)
+    assert logits.dtype == F32
+    _l.check(_lib().i2t_ngram_ban_argmax_lp(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V, _p(done),
+                                            _p(tok_lp), tok_lp.stride(0)), 'i2t_ngram_ban_argmax_lp')
+
+
+def sample_token_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, temperature, top_k, nucleus_p, seed, done, tok_lp,
+                    dist_out=None):
+    """sample_token + tok_lp[b][len] = log-prob of the drawn token under the RAW row; no write once *done (i2t_sample_token_lp)"""
+    _need_cuda(logits, seed)
+    _lp_args(ids, ids_ld, done, tok_lp, B)
+    assert logits.dtype == F32 and seed.dtype == torch.int32 and seed.numel() >= 2
+    _l.check(_lib().i2t_sample_token_lp(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V,
+                                        float(temperature), int(top_k or 0), float(-1.0 if nucleus_p is None else nucleus_p), _p(seed),
+                                        _p(dist_out), 0 if dist_out is None else dist_out.stride(0), _p(done), _p(tok_lp), tok_lp.stride(0)),
+             'i2t_sample_token_lp')
+
+
+def caption_finish(ids, ids_ld, len_ptr, eos, pad, finished, lengths, tok_lp, ctrl, R):
+    """the finish rule of a caption step (include/i2t.h::i2t_caption_finish); eos None/-1 = no rule"""
+    _need_cuda(ids, len_ptr, finished, lengths, tok_lp, ctrl)
+    assert ids.dtype == torch.long and finished.dtype == torch.int32 and lengths.dtype == torch.int32 and ctrl.dtype == torch.int32
+    assert tok_lp.dtype == F32 and tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
+    _l.check(_lib().i2t_caption_finish(_stream(), _p(ids), ids_ld, _p(len_ptr), -1 if eos is None else int(eos), int(pad), _p(finished),
+                                       _p(lengths), _p(tok_lp), tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish')
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     _need_cuda(a, b, stats)

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 6
+#define I2T_ABI_VERSION 7
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -412,6 +412,30 @@ int i2t_sample_token(void* stream, const float* logits, int ld, int64_t* ids, in
                      const int* ngram_sizes, int n_sizes, int B, int V, float temperature, int top_k, float nucleus_p,
                      const unsigned* seed, float* dist_out, int dist_ld);
 int i2t_advance(void* stream, int* counters, int n, int delta);   /* counters[0..n) += delta */
+/* The caption step (VisionEncoderDecoder.generate_captions, an addition next to generate()): the three token choosers
+ * above in a form that also records the log-probability of the token they choose, and the finish rule.  tok_lp[b][*len_ptr] =
+ * z[chosen] - log sum_c exp(z[b][c]) over the whole vocabulary of the step's RAW logits: ban, temperature, crop and nucleus do not
+ * enter.  Each takes `done` (a device word) and writes NOTHING once *done is non-zero.  On the same inputs the chosen ids are those of
+ * the plain forms, bit for bit.
+ *   i2t_gemm_bf16_top2_lse: i2t_gemm_bf16_top2 (top2 bit-equal) that also leaves se[M][nseg], se = sum_c exp(z[m][c] - v1) over the
+ *     segment's columns c < N (v1 = the segment's maximum), reduced as i2t_gemm_bf16_lse reduces it; no atomics.
+ *   i2t_top2_ngram_argmax_lp: merges a row's (v1, se) pairs in a fixed order into the lse, re-evaluates the chosen logit in fp32.
+ *   i2t_ngram_ban_argmax_lp: fp32 logits [B][ld]; the lse is an online pass over the unbanned row.
+ *   i2t_sample_token_lp: the raw row's maximum and sum of exp's are taken before the filters.
+ *   i2t_caption_finish (after a chooser, before i2t_beam_advance(counters, ctrl)): returns at once if ctrl[0]; a row that finished
+ *     earlier gets ids[r][len] = pad and tok_lp[r][len] = 0; else a row with ids[r][len] == eos gets finished[r] = 1 and
+ *     lengths[r] = len + 1; ctrl[1] = the number of rows not finished (R when eos < 0: no rule).  One workgroup, no atomics. */
+int i2t_gemm_bf16_top2_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float* top2, float* se, int nseg);
+int i2t_top2_ngram_argmax_lp(void* stream, const float* top2, const float* se, int nseg, const void* hidden, int ld_hidden,
+                             const void* w_head, int ld_w, int d, int64_t* ids, int ids_ld, const int* len_ptr, const int* ngram_sizes,
+                             int n_sizes, int B, int V, const int* done, float* tok_lp, int lp_ld);
+int i2t_ngram_ban_argmax_lp(void* stream, const float* logits, int ld, int64_t* ids, int ids_ld, const int* len_ptr,
+                            const int* ngram_sizes, int n_sizes, int B, int V, const int* done, float* tok_lp, int lp_ld);
+int i2t_sample_token_lp(void* stream, const float* logits, int ld, int64_t* ids, int ids_ld, const int* len_ptr,
+                        const int* ngram_sizes, int n_sizes, int B, int V, float temperature, int top_k, float nucleus_p,
+                        const unsigned* seed, float* dist_out, int dist_ld, const int* done, float* tok_lp, int lp_ld);
+int i2t_caption_finish(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, int eos, int64_t pad, int* finished, int* lengths,
+                       float* tok_lp, int lp_ld, int* ctrl, int R);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).

@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""generate() for 64 tokens against generate_captions() with an EOS id at which the rows end, on a nano-224-shaped model with random
+weights.
+
+    python tools/bench_generate_captions.py [--batch 256] [--rounds 3] [--new 64]
+
+Two comparisons, each alternating its two forms ROUNDS times in one process after a warm-up of both:
+  N = 1   generate(images, 64 tokens, greedy)                      vs  generate_captions(images, eos, greedy)
+  N = 4   generate(images repeated 4 times, 64 tokens, sampling)   vs  generate_captions(images, eos, N = 4, sampling)
+The EOS id is taken from a free run: the token whose first emission, over all rows, comes earliest at the latest row -- the rows of
+random weights do end, if late.  Prints wall time per call (median [min .. max] ms, synchronised), the replays launched, the mean
+length, and the rise of the allocator's peak across a call of each form (decoder state included: measured on a fresh model)."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from image2text_amd.models.vision_encoder_decoder import VisionEncoderDecoder  # noqa: E402
+from image2text_amd.synth import det_init_, nano224_config  # noqa: E402
+
+SAMPLING = dict(temperature=0.7, top_k=None, nucleus_p=0.6)
+
+
+def fresh(B):
+    m = VisionEncoderDecoder(nano224_config())
+    det_init_(m, seed=0)
+    m = m.to('cuda').eval()
+    g = torch.Generator().manual_seed(0)
+    images = torch.randn(B, 3, 224, 224, generator=g).to('cuda')
+    prompt = torch.full((B, 1), 50256, dtype=torch.long, device='cuda')
+    return m, images, prompt
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def peak_rise(B, call):
+    m, images, prompt = fresh(B)
+    m._engine.prepare(False)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    call(m, images, prompt)
+    torch.cuda.synchronize()
+    rise = torch.cuda.max_memory_allocated() - base
+    del m
+    torch.cuda.empty_cache()
+    return rise / 2 ** 20
+
+
+def pick_eos(ids, P):
+    """the token whose first emission comes earliest at the latest row; -> (id, that step)"""
+    new = ids[:, P:]
+    best, best_step = None, new.shape[1] + 1
+    for tok in new[0].unique().tolist():
+        hit = new == tok
+        if not bool(hit.any(dim=1).all()):
+            continue
+        step = int(hit.float().argmax(dim=1).max()) + 1
+        if step < best_step:
+            best, best_step = tok, step
+    return best, best_step
+
+
+def fmt(ts):
+    return f'{statistics.median(ts):8.1f} [{min(ts):.1f} .. {max(ts):.1f}] ms'
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--new', type=int, default=64)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'bench_generate_captions.py measures on the MI355X; there is nothing to report without one'
+    B, T = a.batch, a.new
+    print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {T} new tokens, {a.rounds} alternating rounds',
+          flush=True)
+    m, images, prompt = fresh(B)
+    for N, mode in ((1, dict(top_k=1)), (4, SAMPLING)):
+        rep_i, rep_p = (images.repeat_interleave(N, dim=0), prompt.repeat_interleave(N, dim=0)) if N > 1 else (images, prompt)
+        free = m.generate_captions(images, prompt, max_new_tokens=T, num_return_sequences=N, seed=3, **mode)
+        eos, step = pick_eos(free.ids.reshape(B * N, -1), 1)
+        if eos is None:
+            print(f'N = {N}: no token is emitted by every row within {T} steps; generate_captions runs all {T} steps', flush=True)
+        forms = {'generate': lambda: m.generate(rep_i, rep_p, max_new_tokens=T, **mode),
+                 'generate_captions': lambda: m.generate_captions(images, prompt, max_new_tokens=T, eos_token_id=eos, num_return_sequences=N,
+                                                                  seed=3, **mode)}
+        for fn in forms.values():
+            fn()
+        ts = {k: [] for k in forms}
+        for _ in range(a.rounds):
+            for k, fn in forms.items():
+                t, out = wall(fn)
+                ts[k].append(t)
+        print(f'N = {N} ({"greedy" if N == 1 else "sampling T 0.7 / p 0.6"}), eos id {eos} (every row has emitted it by step {step}):', flush=True)
+        print(f'  generate, {B * N} rows x {T} tokens      {fmt(ts["generate"])}', flush=True)
+        print(f'  generate_captions                   {fmt(ts["generate_captions"])}   replays {m._captioner.last_replays}, '
+              f'mean length {float(out.lengths.float().mean()):.1f}, L {out.ids.shape[-1]}', flush=True)
+        torch.cuda.empty_cache()
+        r_gen = peak_rise(B, lambda mm, im, pr: mm.generate(im.repeat_interleave(N, dim=0) if N > 1 else im,
+                                                            pr.repeat_interleave(N, dim=0) if N > 1 else pr, max_new_tokens=T, **mode))
+        r_cap = peak_rise(B, lambda mm, im, pr: mm.generate_captions(im, pr, max_new_tokens=T, eos_token_id=eos, num_return_sequences=N, seed=3,
+                                                                     **mode))
+        print(f'  peak memory rise: generate {r_gen:.0f} MiB, generate_captions {r_cap:.0f} MiB', flush=True)
+
+
+if __name__ == '__main__':
+    main()
