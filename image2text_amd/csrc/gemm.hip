@@ -71,6 +71,7 @@ struct GemmParams {
     bf16_t* xo; long xo_bs; int xo_rs;            // attention output, same layout convention as Q
     float* xlse;                                  // [H][total_q] (packed) or [B][H][TqMax]
     int x_total_q, x_TqMax, x_H, x_d, x_B;
+    int x_S;                                      // class 16 (xattn_small_epilogue): memory tokens per image, 8 / 16 / 32
 };
 
 // Tile order inside an XCD's contiguous chunk of the grid.  PMC (round 1, B = 256): with M fastest the GEMM family moved
@@ -880,6 +881,243 @@ __device__ __forceinline__ void xattn_epilogue(const GemmParams& p, f32x4 (&acc)
     }
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// Fused cross-attention for S = 8 / 16 / 32 memory tokens per image (epilogue class 16): the same GEMM tiling and the same two
+// accumulator forms as class 8, but a wave's 64 consecutive memory rows (first row n0 + 64 wc, a multiple of 64) are 64 / S WHOLE
+// images  b = (n0 + 64 wc) / S + u,  u < 64 / S  -- no image straddles two waves.  Bias and the K/V stores work as in class 8 (full
+// 128-byte lines through the wave's LDS pad, V transposed on the matrix pipe), addressed by memory row and predicated by
+// row < B S: a wave may be partly live, and what the loader leaves for rows at or past N (zeros: its buffer loads are bounded
+// by the operand) is neither stored nor attended.  Then every image u attends with its own query rows, over the key blocks it owns:
+//     S = 32: score blocks 2u, 2u+1 and the packed P pair u                    (4 + 4 MFMAs per 16 queries)
+//     S = 16: score block u; P pair u >> 1 with the other tile zero             (2 + 4)
+//     S =  8: half of score block u >> 1: the lanes g >> 1 != (u & 1) hold the neighbouring image's keys and are set to -inf
+//             before the row maximum -- probability exactly 0: out of the denominator and out of P V        (2 + 4)
+// Dropout index: ((b H + h) TqMax + q) S + key in image -- i2t_attention_fwd's with Tk = S (a multiple of 4 per lane).
+// Queries: two 16-row blocks of an image are in flight; image u + 1's are requested before image u's math (class 8's four blocks
+// of ONE image would be 2 - 8 images' worth here: 32 VGPRs either way).
+// Bias, the K/V stores and the operand packing do not depend on S and exist once (xattn_small_epilogue); only the attention loop
+// is specialised (xattn_small_attend<S>): three copies of the whole epilogue in one kernel spilled 61 VGPRs, this form none.
+
+// class 8's K/V store phase for a wave whose first `live` (<= 64) memory rows exist: kvw = the wave's first row, its head's columns
+__device__ __forceinline__ void xa_store_kv_rows(const GemmParams& p, f32x4 (&acc)[8][4], const bf16x8 (&va_)[4][2], bf16_t* kvw, int live,
+                                                 int g, int li, unsigned char* pad) {
+    bf16x8 sel[2];                                                      // (the selection matrices of xattn_epilogue)
+    {
+        const int e = li - 4 * g;
+        s16x8 s0 = {0, 0, 0, 0, 0, 0, 0, 0}, s1 = s0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            s0[q] = (e == q) ? (short)0x3F80 : (short)0;
+            s1[4 + q] = (e == q) ? (short)0x3F80 : (short)0;
+        }
+        sel[0] = __builtin_bit_cast(bf16x8, s0);
+        sel[1] = __builtin_bit_cast(bf16x8, s1);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (16 * j >= live) break;                                      // wave-uniform: the block holds no live row
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u32x2 k2 = {pack_bf16x2(acc[i][j][0], acc[i][j][1]), pack_bf16x2(acc[i][j][2], acc[i][j][3])};
+            *reinterpret_cast<u32x2*>(pad + li * 256 + (((2 * i + (g >> 1)) ^ li) << 4) + (g & 1) * 8) = k2;       // row = key li
+            const f32x4 vt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va_[i][j >> 1], sel[j & 1], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const u32x2 v2 = {pack_bf16x2(vt[0], vt[1]), pack_bf16x2(vt[2], vt[3])};
+            *reinterpret_cast<u32x2*>(pad + li * 256 + (((8 + 2 * i + (g >> 1)) ^ li) << 4) + (g & 1) * 8) = v2;   // row = key li, V part
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int row = 4 * it + g;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(pad + row * 256 + ((li ^ row) << 4));
+            bf16_t* dst = kvw + (size_t)(16 * j + row) * p.ldc + (li < 8 ? li * 8 : p.x_d + (li - 8) * 8);
+            if (16 * j + row < live) G2_STORE(reinterpret_cast<u32x4*>(dst), v);
+        }
+    }
+}
+
+// queries of image b: row count and first row -- of the packed arrays, or of the image's own [TqMax] rows (dense); the Q / O / lse
+// offsets are derived where they are used (two scalars per image stay live, not seven)
+struct XaImage {
+    int Tq, s0, b;
+};
+__device__ __forceinline__ XaImage xa_image(const GemmParams& p, int b) {
+    XaImage im = {p.x_TqMax, 0, b};
+    if (p.xcu) {
+        im.s0 = p.xcu[b];
+        im.Tq = p.xcu[b + 1] - im.s0;
+    }
+    return im;
+}
+__device__ __forceinline__ size_t xa_qoff(const GemmParams& p, const XaImage& im) { return p.xcu ? (size_t)im.s0 * p.xq_rs : (size_t)im.b * p.xq_bs; }
+__device__ __forceinline__ size_t xa_ooff(const GemmParams& p, const XaImage& im) { return p.xcu ? (size_t)im.s0 * p.xo_rs : (size_t)im.b * p.xo_bs; }
+__device__ __forceinline__ size_t xa_stat(const GemmParams& p, const XaImage& im, int h) {
+    return p.xcu ? (size_t)h * p.x_total_q + im.s0 : ((size_t)im.b * p.x_H + h) * p.x_TqMax;
+}
+// query blocks qblk0, qblk0 + 1 of an image as Q^T B-operands (the fragment form of xattn_epilogue's load_q); zeros past its rows
+__device__ __forceinline__ void xa_load_q2(const GemmParams& p, const XaImage& im, int h, int qblk0, int g, int li, u32x4 (&qf)[2][2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        qf[t][0] = qf[t][1] = u32x4{0u, 0u, 0u, 0u};
+        if (16 * (qblk0 + t) < im.Tq) {
+            const bf16_t* qp = p.xq + h * 64 + xa_qoff(p, im) + (size_t)min(16 * (qblk0 + t) + li, im.Tq - 1) * p.xq_rs + 4 * g;
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const u32x2 lo = *reinterpret_cast<const u32x2*>(qp + 32 * s2), hi = *reinterpret_cast<const u32x2*>(qp + 32 * s2 + 16);
+                qf[t][s2] = u32x4{lo[0], lo[1], hi[0], hi[1]};
+            }
+        }
+    }
+}
+
+// xa_quad_max / xa_quad_sum with the lane index handed in (the epilogue's laundered one): __shfl_xor reads __lane_id(), which the
+// compiler hoists above the persistent loop -- one more VGPR live across the K loop, and class 16 spilled exactly that one
+__device__ __forceinline__ float xa_lane_xor(float v, int lane, int m) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ m) << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ float xa_quad_max_at(float v, int lane) {
+    v = fmaxf(v, xa_lane_xor(v, lane, 16));
+    return fmaxf(v, xa_lane_xor(v, lane, 32));
+}
+__device__ __forceinline__ float xa_quad_sum_at(float v, int lane) {
+    v += xa_lane_xor(v, lane, 16);
+    return v + xa_lane_xor(v, lane, 32);
+}
+
+// the attention of the wave's nimg (<= 64 / S) live images, first image b0 (whose first two query blocks are in qfa), out of the
+// packed K^T (ka) and V (va_) fragments
+template <int S>
+__device__ __forceinline__ void xattn_small_attend(const GemmParams& p, const bf16x8 (&ka)[2][4], const bf16x8 (&va_)[4][2], u32x4 (&qfa)[2][2],
+                                                   XaImage im, int b0, int nimg, int h, int lane) {
+    static_assert(S == 8 || S == 16 || S == 32, "whole images per wave");
+    constexpr int NI = 64 / S, NB = S == 32 ? 2 : 1;                    // images per wave; 16-key score blocks per image
+    const int g = lane >> 4, li = lane & 15;
+    constexpr float kScale = 0.125f * 1.4426950408889634f;             // 1 / sqrt(64) x log2(e)
+    const bool drop = p.drop_thr != 0;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < NI; ++u) {
+        if (u >= nimg) break;                                           // wave-uniform: images at or past B
+        const int b = b0 + u;
+        // the next image's first queries are requested before this image's math
+        XaImage imn = {0, 0, 0};
+        u32x4 qfn[2][2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) qfn[t][0] = qfn[t][1] = u32x4{0u, 0u, 0u, 0u};
+        if (u + 1 < NI && u + 1 < nimg) {
+            imn = xa_image(p, b + 1);
+            xa_load_q2(p, imn, h, 0, g, li, qfn);
+        }
+        const int Tq = im.Tq;
+        const int j0 = S == 32 ? 2 * u : S == 16 ? u : u >> 1;          // first score block of the image; its P pair is j0 >> 1
+        // S = 8: the lanes g >> 1 != (u & 1) hold the neighbouring image's 4 keys of the block: their scores start from -inf and stay
+        // there.  (The constant goes through a laundered scalar: as a literal it was hoisted into a VGPR that then lived across the
+        // K loop, where no register is free -- the kernel spilled.)
+        f32x4 sc0 = zero4;
+        if (S == 8) {
+            unsigned ninf = 0xff800000u;
+            asm volatile("" : "+s"(ninf));
+            const float s0 = (g >> 1) != (u & 1) ? __builtin_bit_cast(float, ninf) : 0.f;
+            sc0 = f32x4{s0, s0, s0, s0};
+        }
+        const int nqb = (Tq + 15) >> 4;                                 // (an image may have no query row)
+        for (int qg = 0; qg < nqb; qg += 2) {
+            if (qg > 0) xa_load_q2(p, im, h, qg, g, li, qfa);
+#pragma unroll
+            for (int q2 = 0; q2 < 2; ++q2) {
+                const int qblk = qg + q2;
+                if (qblk >= nqb) break;                                 // wave-uniform
+                const bf16x8 q0 = __builtin_bit_cast(bf16x8, qfa[q2][0]), q1 = __builtin_bit_cast(bf16x8, qfa[q2][1]);
+                const int qrow = 16 * qblk + li;
+                f32x4 sc[NB];
+                float mx = -INFINITY;
+#pragma unroll
+                for (int jj = 0; jj < NB; ++jj) {
+                    f32x4 a = sc0;
+                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[0][j0 + jj], q0, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[1][j0 + jj], q1, a, 0, 0, 0);
+                    mx = fmaxf(fmaxf(mx, fmaxf(a[0], a[1])), fmaxf(a[2], a[3]));
+                    sc[jj] = a;
+                }
+                mx = xa_quad_max_at(mx, lane) * kScale;
+                float rs = 0.f;
+                const unsigned drow = (((unsigned)b * p.x_H + h) * (unsigned)p.x_TqMax + (unsigned)min(qrow, Tq - 1)) * (unsigned)S;
+#pragma unroll
+                for (int jj = 0; jj < NB; ++jj) {
+                    bool keep[4] = {true, true, true, true};
+                    if (drop) dropout_keep4_even(p.drop_key, drow + 16 * jj + (S == 8 ? 4 * (g & 1) : 4 * g), p.drop_thr, keep);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float pr = __builtin_amdgcn_exp2f(sc[jj][r] * kScale - mx);      // a foreign key: exp2(-inf) = 0 exactly
+                        rs += pr;                                       // the softmax denominator is dropout-free
+                        sc[jj][r] = keep[r] ? pr : 0.f;
+                    }
+                }
+                const float l = xa_quad_sum_at(rs, lane);
+                // P pair j0 >> 1: both tiles the image's (S = 32), or its one tile and zeros in the neighbour's place
+                const bf16x8 pp = S == 32 ? xa_pack(sc[0], sc[NB - 1]) : (j0 & 1) ? xa_pack(zero4, sc[0]) : xa_pack(sc[0], zero4);
+                const float inv = (drop ? p.drop_scale : 1.0f) / l;
+                u32x2 ob[4];                                            // (MFMAs stay outside the per-lane row predicate)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va_[i][j0 >> 1], pp, zero4, 0, 0, 0);
+                    ob[i] = u32x2{pack_bf16x2(o[0] * inv, o[1] * inv), pack_bf16x2(o[2] * inv, o[3] * inv)};
+                }
+                if (qrow < Tq) {
+                    bf16_t* op = p.xo + xa_ooff(p, im) + (size_t)qrow * p.xo_rs + h * 64 + 4 * g;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x2*>(op + 16 * i) = ob[i];
+                    if (g == 0 && p.xlse) p.xlse[xa_stat(p, im, h) + qrow] = (mx + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;      // (1 <= l <= S: the bare v_log_f32)
+                }
+            }
+        }
+        im = imn;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) { qfa[t][0] = qfn[t][0]; qfa[t][1] = qfn[t][1]; }
+    }
+}
+
+// Bias, the K/V stores and the operand packing do not depend on S: one copy; only the attention loop is specialised.
+__device__ __forceinline__ void xattn_small_epilogue(const GemmParams& p, f32x4 (&acc)[8][4], int tile_m, int n0, int wr, int wc, int lane,
+                                                     unsigned char* pad) {
+    const int g = lane >> 4, li = lane & 15;
+    const int h = 2 * tile_m + wr, row0 = n0 + 64 * wc, d = p.x_d;
+    if (row0 >= p.N || h >= p.x_H) return;                              // wave-uniform (no workgroup barrier in this epilogue); p.N = B S
+    const int S = p.x_S, live = min(64, p.N - row0);                    // live memory rows of this wave: live / S whole images
+    const int b0 = row0 >> (S == 32 ? 5 : S == 16 ? 4 : 3);
+    const XaImage im = xa_image(p, b0);
+    u32x4 qfa[2][2];
+    xa_load_q2(p, im, h, 0, g, li, qfa);                                // the first image's queries: ahead of the store phase
+    // ---- bias (as in xattn_epilogue)
+    {
+        const float* bk = p.bias + h * 64;
+        const float* bv = p.bias + d + h * 64;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 k4 = *reinterpret_cast<const f32x4*>(bk + 16 * i + 4 * g);
+            const float v1 = bv[16 * i + li];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[i][j] += k4;
+                acc[4 + i][j] += f32x4{v1, v1, v1, v1};
+            }
+        }
+    }
+    bf16x8 va_[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) va_[i][s2] = xa_pack(acc[4 + i][2 * s2], acc[4 + i][2 * s2 + 1]);
+    // ---- K and V of the live memory rows -> kv[row][0:d | d:2d]
+    xa_store_kv_rows(p, acc, va_, reinterpret_cast<bf16_t*>(p.C) + (size_t)row0 * p.ldc + h * 64, live, g, li, pad);
+    bf16x8 ka[2][4];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ka[s2][j] = xa_pack(acc[2 * s2][j], acc[2 * s2 + 1][j]);
+    if (S == 32) xattn_small_attend<32>(p, ka, va_, qfa, im, b0, live >> 5, h, lane);
+    else if (S == 16) xattn_small_attend<16>(p, ka, va_, qfa, im, b0, live >> 4, h, lane);
+    else xattn_small_attend<8>(p, ka, va_, qfa, im, b0, live >> 3, h, lane);
+}
+
 // SPLITK: gridDim.y slices of the reduction; every slice adds its partial tile into the fp32 C with float atomics
 // (C must already hold the value to accumulate onto -- the gradient arena does).  The MFMA is issued un-swapped
 // there so that one atomic wave-instruction covers 4 rows x 64 contiguous bytes instead of 16 rows x 4 scattered
@@ -1536,7 +1774,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
         const int k = ((bid >> 3) % p.g2_stagger_groups) * p.g2_stagger;
         for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
     }
-    G2<A_KMAJOR, B_KMAJOR, EPI == 6 || EPI == 13, EPI == 8, EPI == 13> g;
+    G2<A_KMAJOR, B_KMAJOR, EPI == 6 || EPI == 13, EPI == 8 || EPI == 16, EPI == 13> g;
     g.init(p, smem, tid);
     g.cur = g.tile_desc(p, first, ntiles);
     g.nxt = g.tile_desc(p, first + G, ntiles);
@@ -1596,6 +1834,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p) {
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
             xattn_epilogue(*epilogue_params(), acc, m0 >> 8, n0, g.wr, g.wc, lane_e, smem + 8 * G2_UNIT + (g.wave_off << 2));
+        } else if constexpr (EPI == 16) {       // fused cross-attention, 8 / 16 / 32 memory tokens per image: the wave's 64 / S images x its head
+            int lane_e = tid & 63;
+            asm volatile("" : "+v"(lane_e));
+            xattn_small_epilogue(*epilogue_params(), acc, m0 >> 8, n0, g.wr, g.wc, lane_e, smem + 8 * G2_UNIT + (g.wave_off << 2));
         } else if constexpr (EPI == 12) {       // the two largest of every 64-column row segment instead of the tile (greedy decode's lm_head)
             int lane_e = tid & 63;
             asm volatile("" : "+v"(lane_e));
@@ -2561,14 +2803,15 @@ extern "C" int i2t_xattn_kv_fused(void* stream, const void* mem, int ld_mem, con
                                   unsigned drop_thr, float drop_scale) {
     const int d = 64 * H;
     I2T_REQUIRE(mem && w_kv && bias_kv && q && kv && o && B > 0 && H > 0 && Tq > 0, "i2t_xattn_kv_fused: bad args");
-    I2T_REQUIRE(S == 64 && (H & 1) == 0, "i2t_xattn_kv_fused: needs 64 memory tokens per image and an even head count (S=%d H=%d)", S, H);
+    I2T_REQUIRE((S == 8 || S == 16 || S == 32 || S == 64) && (H & 1) == 0,
+                "i2t_xattn_kv_fused: needs 8, 16, 32 or 64 memory tokens per image and an even head count (S=%d H=%d)", S, H);
     I2T_REQUIRE((ld_mem & 7) == 0 && (ld_w & 7) == 0 && ld_mem >= d && ld_w >= d && ALIGNED16(mem) && ALIGNED16(w_kv),
                 "i2t_xattn_kv_fused: mem / w_kv must be 16-byte aligned with leading dimensions >= d, %% 8 == 0");
     I2T_REQUIRE((ld_kv & 7) == 0 && ld_kv >= 2 * d && ALIGNED16(kv), "i2t_xattn_kv_fused: kv rows must hold [K | V] (2 d), 16-byte aligned");
     I2T_REQUIRE(((uintptr_t)q & 7) == 0 && ((uintptr_t)o & 7) == 0 && (q_rs & 3) == 0 && (o_rs & 3) == 0 && (q_bs & 3) == 0 && (o_bs & 3) == 0 &&
                     q_rs >= d && o_rs >= d, "i2t_xattn_kv_fused: q / o must be 8-byte aligned with strides %% 4 == 0");
     I2T_REQUIRE(!cu_q || total_q > 0, "i2t_xattn_kv_fused: packed queries need total_q");
-    I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * 64 < 4294967296.0, "i2t_xattn_kv_fused: dropout index overflows 32 bits");
+    I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * S < 4294967296.0, "i2t_xattn_kv_fused: dropout index overflows 32 bits");
     I2T_REQUIRE((double)(d + 128) * ld_w * 2 < 4294967296.0 && (double)B * S * ld_mem * 2 < 1.8e19, "i2t_xattn_kv_fused: operand too large");
     GemmParams p;
     memset(&p, 0, sizeof(p));
@@ -2580,12 +2823,13 @@ extern "C" int i2t_xattn_kv_fused(void* stream, const void* mem, int ld_mem, con
     p.drop_key = drop_key; p.drop_thr = drop_thr; p.drop_scale = drop_scale;
     p.xq = (const bf16_t*)q; p.xq_bs = q_bs; p.xq_rs = q_rs; p.xcu = cu_q;
     p.xo = (bf16_t*)o; p.xo_bs = o_bs; p.xo_rs = o_rs; p.xlse = lse;
-    p.x_total_q = total_q; p.x_TqMax = Tq; p.x_H = H; p.x_d = d; p.x_B = B;
+    p.x_total_q = total_q; p.x_TqMax = Tq; p.x_H = H; p.x_d = d; p.x_B = B; p.x_S = S;
     p.g2_gn = 8;
     p.tiles_m = H / 2; p.tiles_n = (p.N + 255) / 256;
     p.g2_splits = 1; p.g2_nk = (((p.K + 63) >> 6) + 1) & ~1;
     const int n_cu = g256_cus(), tiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm256_kernel<false, false, 8>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
+    if (S == 64) hipLaunchKernelGGL((gemm256_kernel<false, false, 8>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((gemm256_kernel<false, false, 16>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);      // 64 / S images per wave
     I2T_CHECK_LAUNCH("i2t_xattn_kv_fused");
     return I2T_OK;
 }

@@ -116,6 +116,18 @@ class DropPlan:
         return e
 
 
+def xattn_route(S: int, H: int, d: int, fused: bool, small: bool, lora: bool, precise: bool) -> str:
+    """Which cross-attention forward a decoder block takes: 'lora' (adapted K/V projection: the un-fused form through the site
+    helper), 'fused' (ops.xattn_kv_fused: K/V projection + attention in one launch) or 'unfused' (ops.gemm + ops.attention_fwd).
+    S memory tokens per image, H heads of width d / H.  The fused kernel needs heads of 64, an even head count and 64 memory
+    tokens per image -- or, with ``small`` (I2T_XATTN_FUSED_SMALL=1), 8 / 16 / 32 (64 / S whole images per wave)."""
+    if lora:
+        return 'lora'
+    if fused and (S == 64 or (small and S in (8, 16, 32))) and H % 2 == 0 and d == 64 * H and not precise:
+        return 'fused'
+    return 'unfused'
+
+
 _ARENAS = weakref.WeakSet()
 
 
@@ -376,6 +388,8 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
                           for l in range(dcfg.n_layer)]
         # fused cross-attention forward (K/V projection + attention in one launch) when the shapes allow; I2T_XATTN_FUSED=0: A/B runs
         self.xattn_fused = os.environ.get('I2T_XATTN_FUSED') != '0'
+        # opt-in: 8 / 16 / 32 memory tokens per image take the fused launch too (xattn_route); unset, they keep the un-fused pair
+        self.xattn_fused_small = os.environ.get('I2T_XATTN_FUSED_SMALL') == '1'
         self._logits_cache: Dict[int, torch.Tensor] = {}
         self._ws = None
         self.grad_ready_hooks = []      # callables(which: 'begin' | 'decoder' | 'encoder'), e.g. the data-parallel exchange
@@ -518,11 +532,12 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
             kv = self._empty(B, S, 2 * d, dtype=BF16)
             co, lse_c = self._empty(M, d, dtype=BF16), self._empty(H * M)
             s_kv = self._block_site(pfx, layer, 'xattn_c_attn', 2 * d, d, rows=(d, 3 * d))
-            if s_kv.lora is not None:      # adapted K/V projection: the un-fused form
+            route = xattn_route(S, H, d, self.xattn_fused, self.xattn_fused_small, s_kv.lora is not None, ops.precise())
+            if route == 'lora':            # adapted K/V projection: the un-fused form
                 lo['xattn_c_attn'] = self._site_fwd(s_kv, mem_bf, kv.view(B * S, 2 * d), B * S, sv.lo_drop.get('xattn_c_attn'), save)
                 ops.attention_fwd(v3(q, d), kv[..., :d], kv[..., d:], v3(co, d), lse_c, B, H, T, S, False, drop=dr['xattn'],
                                   cu_q=cu, total_q=M)
-            elif self.xattn_fused and S == 64 and H % 2 == 0 and d == 64 * H and not ops.precise():
+            elif route == 'fused':
                 # ONE launch: K/V projection GEMM whose waves run the attention of their (image, head) out of the accumulators
                 # (K and V are written once for the backward pass and never read back here)
                 ops.xattn_kv_fused(mem_bf, win[d:], bin_[d:], v3(q, d), kv, v3(co, d), lse_c, B, S, H, T, drop=dr['xattn'],

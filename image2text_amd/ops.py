@@ -459,7 +459,8 @@ def grouped_colsum(x, seg, n_groups, out, out_group_stride, group0, N):
 
 def xattn_kv_fused(mem, w_kv, bias_kv, q, kv, o, lse, B, S, H, Tq, drop=None, cu_q=None, total_q=0):
     """Fused cross-attention forward (include/i2t.h::i2t_xattn_kv_fused): kv = mem . w_kv^T + bias written once, attention of every
-    (image, head) out of the projection's accumulators.  q / o: [B, Tq, >= 64 H] views or packed [rows, >= 64 H] with cu_q."""
+    (image, head) out of the projection's accumulators.  q / o: [B, Tq, >= 64 H] views or packed [rows, >= 64 H] with cu_q.
+    S (memory tokens per image) is 64, or 8 / 16 / 32 (64 / S whole images per wave); H even; any other S raises I2TError."""
     _need_cuda(mem, w_kv, q, kv, o)
     qb, qr = _bs_rs(q); ob, orr = _bs_rs(o)
     assert mem.dtype == BF16 and w_kv.dtype == BF16 and q.dtype == BF16 and kv.dtype == BF16 and o.dtype == BF16

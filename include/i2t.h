@@ -91,9 +91,12 @@ int i2t_gemm_bf16_ex(void* stream,
  * in ONE launch: the K/V projection is the persistent 256 x 256 MFMA GEMM, tiled so that a wave ends its K loop holding K_h(b)^T and
  * V_h(b) of one (image, head) in its accumulators, and that wave runs the image's attention straight out of those registers
  * (csrc/gemm.hip::xattn_epilogue) -- K and V are never read back from HBM in the forward.
- * mem bf16 [B*S][ld_mem] (S must be 64), w_kv = in_proj_weight rows d..3d (bf16 [2d][ld_w], d = 64 H, H even), bias_kv f32 [2d];
+ * S (memory tokens per image) is 64, or 8 / 16 / 32: a wave's 64 memory rows are then 64 / S whole images, each attended with its own
+ * query rows over the key blocks it owns (csrc/gemm.hip::xattn_small_epilogue, epilogue class 16; B S need not fill a tile).  Any
+ * other S is refused.
+ * mem bf16 [B*S][ld_mem], w_kv = in_proj_weight rows d..3d (bf16 [2d][ld_w], d = 64 H, H even), bias_kv f32 [2d];
  * q / o bf16: [B][Tq] views (batch / row strides) or, with cu_q (device int[B+1]), packed rows (batch strides unused, Tq = max);
- * dropout on the probabilities: same index space and rule as i2t_attention_fwd (drop_thr 0 = off), so i2t_attention_bwd on the
+ * dropout on the probabilities: same index space and rule as i2t_attention_fwd with Tk = S (drop_thr 0 = off; B H Tq S < 2^32), so i2t_attention_bwd on the
  * stored q / kv / o / lse is its backward. */
 int i2t_xattn_kv_fused(void* stream, const void* mem, int ld_mem, const void* w_kv, int ld_w, const float* bias_kv,
                        const void* q, long q_bs, int q_rs, const int* cu_q, int total_q, void* kv, int ld_kv, void* o,
