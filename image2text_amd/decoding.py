@@ -638,12 +638,25 @@ class BeamDecoder(GreedyDecoder):
         return (ids, scores, draws[:L - P]) if record else (ids, scores)
 
 
-class GeneratedCaptions(NamedTuple):
-    """What ``generate_captions`` returns; rows are batch-major (caption n of image b)."""
+class _CaptionFields(NamedTuple):
     ids: torch.Tensor                   # int64 [B, N, L]: prompt, new tokens up to and including the first emitted EOS, then the pad id
     lengths: torch.Tensor               # int32 [B, N]: prompt + new tokens up to and including that EOS (P + max_new_tokens without one)
     token_logprobs: torch.Tensor        # fp32 [B, N, L - P]: log_softmax of the step's raw logits at the chosen token; 0.0 past the EOS
     logprob: torch.Tensor               # fp32 [B, N]: the row sums
+
+
+class GeneratedCaptions(_CaptionFields):
+    """What ``generate_captions`` returns; rows are batch-major (caption n of image b).  The four fields above are the tuple: it
+    unpacks into four and ``_fields`` names four, as before ``prompt_lengths`` existed.  ``prompt_lengths`` (int32 [B], or None when
+    every row's prompt fills all P columns) is the optional fifth argument and an attribute beside them; with it ``lengths`` counts
+    from p_b and ``token_logprobs`` is [B, N, L - Pmin], entry t belonging to column Pmin + t.  ``_replace`` and
+    ``_make`` build the four fields only."""
+    prompt_lengths: Optional[torch.Tensor] = None
+
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None):
+        self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
+        self.prompt_lengths = prompt_lengths
+        return self
 
 
 def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional[int] = None, token_logprobs: Optional[np.ndarray] = None):
@@ -671,6 +684,38 @@ def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional
     return ids, lengths, lp
 
 
+def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[int], pad: Optional[int] = None,
+                             token_logprobs: Optional[np.ndarray] = None):
+    """``apply_finish_rule`` for rows whose prompts differ in length: what i2t_caption_finish_ragged does step by step on the device.
+    ``ids`` [R, Pmax + max_new]: row r holds its prompt in columns < plen[r] and the tokens a chooser emitted from column plen[r] on
+    (columns at or past plen[r] + max_new are not read); ``token_logprobs`` [R, Pmax + max_new - Pmin] is aligned by COLUMN, entry t
+    belonging to column Pmin + t.  A row is finished once it has EMITTED ``eos`` (an EOS inside its prompt does not count; ``eos``
+    None: never) or ``max_new`` tokens; ``lengths[r]`` = plen[r] + the emitted tokens up to and including that EOS; later columns hold
+    ``pad`` (default: the EOS id, 0 without one) and log-prob 0.0, and so do a row's prompt columns (nothing was chosen there).
+    L = lengths.max().  With every plen[r] = P this is ``apply_finish_rule(ids, P, eos, pad, token_logprobs)``.
+    -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - Pmin] or None)"""
+    ids = np.array(ids)
+    plen = np.asarray(plen, dtype=np.int64).reshape(-1)
+    R, total = ids.shape
+    assert plen.shape == (R,) and R >= 1 and max_new >= 0 and int(plen.min()) >= 1 and int(plen.max()) + max_new == total
+    pmin = int(plen.min())
+    pad = (0 if eos is None else eos) if pad is None else pad
+    lengths = (plen + max_new).astype(np.int32)
+    for r in range(R if eos is not None else 0):
+        hit = np.flatnonzero(ids[r, plen[r]:plen[r] + max_new] == eos)
+        if hit.size:
+            lengths[r] = plen[r] + int(hit[0]) + 1
+    L = int(lengths.max())
+    ids = ids[:, :L]
+    lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - pmin]
+    for r in range(R):
+        ids[r, lengths[r]:] = pad
+        if lp is not None:
+            lp[r, :plen[r] - pmin] = 0.0
+            lp[r, lengths[r] - pmin:] = 0.0
+    return ids, lengths, lp
+
+
 class CaptionDecoder(GreedyDecoder):
     """``generate_captions`` on the static KV cache: R = B * N rows (batch-major, r = b * N + n) through GreedyDecoder's buffers and layer
     sequence, one captured hipGraph replay per token.  The encoder and the cross K/V run once per image (rows_per_mem = N); the
@@ -678,7 +723,10 @@ class CaptionDecoder(GreedyDecoder):
     log-prob (i2t_gemm_bf16_top2_lse + i2t_top2_ngram_argmax_lp; or fp32 logits + i2t_ngram_ban_argmax_lp / i2t_sample_token_lp) ->
     i2t_caption_finish -> i2t_beam_advance.  Once every row has emitted EOS the device raises ctrl[0]; from then on no kernel of a
     replay writes ids, tok_lp, finished or lengths, and the host, which reads that word every ``poll_every`` steps,
-    stops launching.  The decoder keeps its own state and graphs: nothing here touches what ``generate`` uses."""
+    stops launching.  The decoder keeps its own state and graphs: nothing here touches what ``generate`` uses.
+    With ``prompt_lengths`` the rows' prompts differ in length: the same state and buffers, Pmin - 1 prefill replays,
+    then full steps that end in i2t_caption_finish_ragged, which puts a row's next prompt token over the chooser's while the column
+    is below the row's prompt length and counts max_new_tokens per row; those steps have graph keys of their own."""
 
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
 
@@ -693,6 +741,7 @@ class CaptionDecoder(GreedyDecoder):
         st.finished, st.lengths = torch.zeros(R, **i32), torch.zeros(R, **i32)
         st.tok_lp = torch.zeros(R, ids_ld, dtype=F32, device=dev)
         st.top2 = st.seg_se = None
+        st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
         return st
 
     def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int):
@@ -719,7 +768,10 @@ class CaptionDecoder(GreedyDecoder):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
-                          use_graph: bool = True) -> GeneratedCaptions:
+                          use_graph: bool = True, prompt_lengths=None) -> GeneratedCaptions:
+        if prompt_lengths is not None:
+            return self._generate_captions_ragged(images, prompt_ids, prompt_lengths, max_new_tokens, eos, pad, int(num_return_sequences),
+                                                  sampling, poll_every, use_graph)
         eng = self.eng
         dc = eng.dec
         N = int(num_return_sequences)
@@ -783,6 +835,113 @@ class CaptionDecoder(GreedyDecoder):
         return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1))
 
 
+    def _caption_step_ragged(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, max_new: int):
+        """_caption_step with i2t_caption_finish_ragged as its finish rule: the choosers run as they are, on every row; what they
+        wrote at a forced column is replaced after them"""
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        R, d = st.B, dc.d
+        len_ptr, done = st.counters[1:2], st.ctrl[0:1]
+        nn = st.ngrams.numel()
+        self._body(st)
+        self._final_norm(st)
+        if top2:
+            ops.gemm_top2_lse(st.hid, a.W(eng.n_head), st.top2, st.seg_se, R, dc.V, d)
+            ops.top2_ngram_argmax_lp(st.top2, st.seg_se, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, d, done,
+                                     st.tok_lp)
+        else:
+            ops.gemm(st.hid, a.W(eng.n_head), st.logits, R, dc.V, d, workspace=st.ws)
+            if sampling is None:
+                ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
+            else:
+                ops.sample_token_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, sampling.temperature,
+                                    sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
+        ops.caption_finish_ragged(st.ids, st.ids_ld, len_ptr, st.rag_prompt, st.rag_plen, st.N, max_new, eos, pad, st.finished, st.lengths,
+                                  st.tok_lp, st.ctrl, R)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    def _generate_captions_ragged(self, images, prompt_ids: torch.Tensor, prompt_lengths, max_new_tokens: int, eos: Optional[int],
+                                  pad: Optional[int], N: int, sampling: Optional[Sampling], poll_every: int, use_graph: bool):
+        """generate_captions(prompt_lengths=...): row (b, n) is prompt_ids[b, :p_b] and up to max_new_tokens emitted tokens.  All rows
+        share the step's column counter; a row whose prompt reaches past the column is forced on the device."""
+        eng = self.eng
+        dc = eng.dec
+        B, P = prompt_ids.shape
+        plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens)
+        if not dc.causal:
+            raise ValueError('CaptionDecoder needs a causal decoder')
+        a = eng.prepare(False)
+        pmin, pmax = int(plen.min()), int(plen.max())
+        R, total = B * N, pmax + max_new_tokens
+        pad = (0 if eos is None else eos) if pad is None else pad
+        st = self._state
+        if (st is None or st.B != R or st.N != N or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch):
+            self._state = None
+            st = self._state = self._build_captions(B, N, max(total, dc.block))
+        if total > st.tmax:
+            raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({st.tmax})')
+        if st.rag_prompt is None:                               # persistent: the captured steps bake their pointers
+            st.rag_prompt = torch.zeros(B, st.ids_ld, dtype=torch.long, device=a.device)
+            st.rag_plen = torch.ones(B, dtype=torch.int32, device=a.device)
+        plen_dev = torch.from_numpy(plen).to(a.device)
+        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
+        keep = torch.arange(pmax, device=a.device)[None, :] < plen_dev[:, None]
+        prompt = torch.where(keep, prompt_ids[:, :pmax].to(a.device), torch.zeros((), dtype=torch.long, device=a.device))
+        st.rag_prompt.zero_()
+        st.rag_prompt[:, :pmax] = prompt
+        st.rag_plen.copy_(plen_dev)
+        prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
+        len_rows = (plen_dev.repeat_interleave(N) if N > 1 else plen_dev) + max_new_tokens
+        if max_new_tokens == 0:                               # nothing to emit: the prompts, padded
+            ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
+            self.last_replays = 0
+            zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
+            return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev)
+        self._prepare_inputs(st, images, B, N)
+        if sampling is not None:
+            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+        top2 = sampling is None and TOP2_HEAD and dc.d % 128 == 0
+        if top2 and st.top2 is None:
+            nseg = (dc.V + 63) // 64
+            st.top2 = torch.zeros(R, nseg, 4, dtype=F32, device=a.device)
+            st.seg_se = torch.zeros(R, nseg, dtype=F32, device=a.device)
+        # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key)
+        full_key = ('ragged', ('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key(), eos, pad, max_new_tokens)
+
+        def reset():
+            st.ids.zero_()
+            st.ids[:, :pmax] = prompt_rows
+            st.counters.copy_(st.counters_init)
+            st.ctrl.zero_()
+            st.finished.zero_()
+            st.lengths.copy_(len_rows)                          # what a row without an EOS ends with: p_b + max_new_tokens
+            st.tok_lp.zero_()
+        reset()
+        if use_graph and (full_key not in st.graphs or None not in st.graphs):
+            self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens)          # eagerly once: code objects load before capture
+            self._step(st, False)
+            if full_key not in st.graphs:
+                st.graphs[full_key] = _capture_launches(a.device, lambda: self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens))
+            if None not in st.graphs:
+                st.graphs[None] = self._capture(st, False)
+            reset()
+        for _ in range(pmin - 1):                               # columns every row holds a prompt token in: fill the cache only
+            st.graphs[None].launch() if use_graph else self._step(st, False)
+        n_full = pmax - pmin + max_new_tokens                   # the longest prompt's row emits its last token in step n_full
+        replays = 0
+        for i in range(n_full):
+            st.graphs[full_key].launch() if use_graph else self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens)
+            replays += 1
+            if eos is not None and poll_every and replays % poll_every == 0 and replays < n_full:
+                if int(st.ctrl[0:1].item()):
+                    break
+        self.last_replays = replays
+        lengths = st.lengths.clone()
+        L = int(lengths.max().item())
+        ids = st.ids[:, :L].reshape(B, N, L).clone()
+        tok_lp = st.tok_lp[:, pmin:L].reshape(B, N, L - pmin).clone()
+        return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev)
+
+
 def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int):
     """the refusals of generate_captions that need no device"""
     if N < 1:
@@ -797,6 +956,28 @@ def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_ever
         raise ValueError(f'pad_token_id = {pad}')
     if poll_every < 0 or max_new_tokens < 0:
         raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+
+
+def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: Optional[Sampling], eos, pad, poll_every: int,
+                              max_new_tokens: int) -> np.ndarray:
+    """check_caption_args, and the refusals of ``prompt_lengths`` (read on the host, before anything moves to the device): one integer
+    per image, 1 <= p_b <= P  -> the lengths, int32 [B]"""
+    check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
+    if isinstance(prompt_lengths, torch.Tensor):
+        if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
+            raise ValueError(f'prompt_lengths of dtype {prompt_lengths.dtype}: integers are needed')
+        plen = prompt_lengths.detach().cpu().numpy()
+    else:
+        plen = np.asarray(prompt_lengths)
+        if plen.size and not np.issubdtype(plen.dtype, np.integer):
+            raise ValueError(f'prompt_lengths of type {plen.dtype}: integers are needed')
+    if plen.shape != (B,):
+        raise ValueError(f'prompt_lengths of shape {tuple(plen.shape)} for prompt_ids of {B} rows: one length per image, shape ({B},)')
+    if B and int(plen.min()) < 1:
+        raise ValueError(f'prompt_lengths[{int(plen.argmin())}] = {int(plen.min())}: every row needs at least one prompt token')
+    if B and int(plen.max()) > P:
+        raise ValueError(f'prompt_lengths[{int(plen.argmax())}] = {int(plen.max())} exceeds the {P} columns of prompt_ids')
+    return plen.astype(np.int32)
 
 
 def _set_seed(buf: torch.Tensor, seed: int):

@@ -74,6 +74,7 @@ SIGNATURES = {
     'i2t_ngram_ban_argmax_lp': [P, P, I, P, I, P, P, I, I, I, P, P, I],
     'i2t_sample_token_lp': [P, P, I, P, I, P, P, I, I, I, F, I, F, P, P, I, P, P, I],
     'i2t_caption_finish': [P, P, I, P, I, I64, P, P, P, I, P, I],
+    'i2t_caption_finish_ragged': [P, P, I, P, P, I, P, I, I, I, I64, P, P, P, I, P, I],
     'i2t_gq_attention_fwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, I, U, U, F, P, P, I, I],
     'i2t_gq_attention_bwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, L, I, P, P, P, L, I, P, L, I, P, L, I, I, I, I, I, I, I, I, U, U, F, P, P, I,
                              U, U, F],
@@ -140,7 +141,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

@@ -234,7 +234,7 @@ class VisionEncoderDecoder(nn.Module):
 
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
-                          temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8):
+                          temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -249,10 +249,24 @@ class VisionEncoderDecoder(nn.Module):
         has finished: the host reads one device word every ``poll_every`` steps (0: never, all steps are launched), its only
         synchronisation besides the final read of the lengths.
         A NON-causal decoder has no cache: this is then TWO passes -- ``generate_by_recompute`` over N-times repeated images with the
-        finish rule applied on the host, then ``score`` on the result for the log-probs."""
+        finish rule applied on the host, then ``score`` on the result for the log-probs.
+        ``prompt_lengths`` (int tensor or sequence [B], 1 <= p_b <= P) gives every image a prompt of its own length in
+        ONE call: row (b, n) is ``prompt_ids[b, :p_b]`` followed by up to ``max_new_tokens`` emitted tokens; columns of ``prompt_ids``
+        at or past p_b are ignored, whatever they hold.  Every row starts at text position 0 -- nothing is padded or masked: while the
+        step's column is below p_b the row's next token is taken from its prompt on the device instead of from the chooser.  The
+        finish rule counts per row: ``lengths[b, n]`` = p_b + the emitted tokens up to and including the EOS (p_b + max_new_tokens
+        without one), an EOS inside the prompt does not count, L = lengths.max().  With Pmin / Pmax the extremes of the lengths,
+        Pmax + max_new_tokens must fit the text window, and ``token_logprobs`` is [B, N, L - Pmin] aligned by COLUMN: entry t belongs
+        to column Pmin + t and is exactly 0.0 at a row's prompt columns and past its end.  The result carries ``prompt_lengths``
+        (int32 [B]; None without the argument).  None (the default) is the path above, unchanged.  For a NON-causal decoder this is
+        ``generate_by_recompute`` once per distinct length over the rows of that length, then the host rule and ``score``: it exists
+        for completeness, not for speed."""
         from ..decoding import CaptionDecoder, Sampling, apply_finish_rule, check_caption_args, generate_by_recompute
         N = int(num_return_sequences)
         sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
+        if prompt_lengths is not None:
+            return self._generate_captions_ragged(images, prompt_ids, prompt_lengths, max_new_tokens, eos_token_id, pad_token_id, N, sampling,
+                                                  poll_every)
         check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
         B, P = prompt_ids.shape
         blk_size = self.decoder.block_size - self.space_for_prompt
@@ -275,6 +289,46 @@ class VisionEncoderDecoder(nn.Module):
         lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, P - 1:L - 1] if L > P else torch.zeros(B * N, 0, device=dev)
         lp = lp.reshape(B, N, L - P).contiguous()
         return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1))
+
+    def _generate_captions_ragged(self, images, prompt_ids, prompt_lengths, max_new_tokens, eos_token_id, pad_token_id, N, sampling,
+                                  poll_every):
+        """generate_captions with ``prompt_lengths``: the host-side checks, then CaptionDecoder; for a non-causal decoder one
+        ``generate_by_recompute`` per distinct length, the host rule and ``score``"""
+        import numpy as np
+        from ..decoding import (CaptionDecoder, GeneratedCaptions, apply_finish_rule_ragged, check_ragged_caption_args,
+                                generate_by_recompute)
+        B, P = prompt_ids.shape
+        plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+        pmin, pmax = int(plen.min()), int(plen.max())
+        blk_size = self.decoder.block_size - self.space_for_prompt
+        if pmax + max_new_tokens > blk_size:
+            raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({blk_size})')
+        dev = next(self.parameters()).device
+        prompt_ids = prompt_ids.to(dev)
+        if self._engine.dec.causal:
+            if self._captioner is None:
+                object.__setattr__(self, '_captioner', CaptionDecoder(self))
+            return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
+                                                     prompt_lengths=plen)
+        rows = np.repeat(plen, N)
+        table = np.zeros((B * N, pmax + max_new_tokens), dtype=np.int64)
+        for p in sorted(set(plen.tolist())):
+            of_p = torch.from_numpy(np.flatnonzero(plen == p)).to(dev)
+            raw = generate_by_recompute(self, images[of_p].repeat_interleave(N, dim=0), prompt_ids[of_p, :p].repeat_interleave(N, dim=0),
+                                        max_new_tokens, sampling)
+            table[rows == p, :p + max_new_tokens] = raw.cpu().numpy()
+        ids, lengths, _ = apply_finish_rule_ragged(table, rows, max_new_tokens, eos_token_id, pad_token_id)
+        ids, lengths = torch.from_numpy(ids).to(dev), torch.from_numpy(lengths).to(dev)
+        L = ids.shape[1]
+        col = torch.arange(L, device=dev)[None, :]
+        labels = next_token_labels(ids, -100)
+        # the label at column c is the token at c + 1: scored from a row's first emitted token to its last
+        rows_dev = torch.from_numpy(rows).to(dev)
+        labels[(col >= lengths[:, None] - 1) | (col < rows_dev[:, None] - 1)] = -100
+        images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
+        lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, pmin - 1:L - 1] if L > pmin else torch.zeros(B * N, 0, device=dev)
+        lp = lp.reshape(B, N, L - pmin).contiguous()
+        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), torch.from_numpy(plen).to(dev))
 
 
     @torch.no_grad()

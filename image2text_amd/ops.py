@@ -820,6 +820,19 @@ def caption_finish(ids, ids_ld, len_ptr, eos, pad, finished, lengths, tok_lp, ct
                                        _p(lengths), _p(tok_lp), tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish')
 
 
+def caption_finish_ragged(ids, ids_ld, len_ptr, prompt, plen, N, max_new, eos, pad, finished, lengths, tok_lp, ctrl, R):
+    """the finish rule of a caption step whose rows have prompts of different lengths: forced while len < plen[r // N], the budget
+    of max_new emitted tokens counted per row (include/i2t.h::i2t_caption_finish_ragged); prompt int64 [B, ld], plen int32 [B]"""
+    _need_cuda(ids, len_ptr, prompt, plen, finished, lengths, tok_lp, ctrl)
+    assert ids.dtype == torch.long and finished.dtype == torch.int32 and lengths.dtype == torch.int32 and ctrl.dtype == torch.int32
+    assert tok_lp.dtype == F32 and tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
+    assert prompt.dtype == torch.long and prompt.dim() == 2 and prompt.stride(-1) == 1 and plen.dtype == torch.int32 and plen.is_contiguous()
+    assert N >= 1 and R % N == 0 and prompt.shape[0] >= R // N and plen.numel() >= R // N
+    _l.check(_lib().i2t_caption_finish_ragged(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(prompt), prompt.stride(0), _p(plen), N, int(max_new),
+                                              -1 if eos is None else int(eos), int(pad), _p(finished), _p(lengths), _p(tok_lp),
+                                              tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish_ragged')
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     _need_cuda(a, b, stats)

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 7
+#define I2T_ABI_VERSION 8
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -427,7 +427,12 @@ int i2t_advance(void* stream, int* counters, int n, int delta);   /* counters[0.
  *   i2t_sample_token_lp: the raw row's maximum and sum of exp's are taken before the filters.
  *   i2t_caption_finish (after a chooser, before i2t_beam_advance(counters, ctrl)): returns at once if ctrl[0]; a row that finished
  *     earlier gets ids[r][len] = pad and tok_lp[r][len] = 0; else a row with ids[r][len] == eos gets finished[r] = 1 and
- *     lengths[r] = len + 1; ctrl[1] = the number of rows not finished (R when eos < 0: no rule).  One workgroup, no atomics. */
+ *     lengths[r] = len + 1; ctrl[1] = the number of rows not finished (R when eos < 0: no rule).  One workgroup, no atomics.
+ *   i2t_caption_finish_ragged (in its place when the rows' prompts differ in length): row r belongs to image b = r / N
+ *     whose prompt is prompt[b][0 .. plen[b]) (prompt int64 [B][prompt_ld], plen int32 [B], both device memory).  While len < plen[b]
+ *     the column is FORCED: ids[r][len] = prompt[b][len] over whatever the chooser wrote, tok_lp[r][len] = 0, the row stays unfinished.
+ *     From len = plen[b] on the row emits: the rules above, and the row also finishes (lengths[r] = len + 1) with its max_new-th
+ *     emitted token, len + 1 - plen[b] >= max_new, whether or not eos >= 0.  ctrl[1] = the rows not finished, forced ones included. */
 int i2t_gemm_bf16_top2_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float* top2, float* se, int nseg);
 int i2t_top2_ngram_argmax_lp(void* stream, const float* top2, const float* se, int nseg, const void* hidden, int ld_hidden,
                              const void* w_head, int ld_w, int d, int64_t* ids, int ids_ld, const int* len_ptr, const int* ngram_sizes,
@@ -439,6 +444,9 @@ int i2t_sample_token_lp(void* stream, const float* logits, int ld, int64_t* ids,
                         const unsigned* seed, float* dist_out, int dist_ld, const int* done, float* tok_lp, int lp_ld);
 int i2t_caption_finish(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, int eos, int64_t pad, int* finished, int* lengths,
                        float* tok_lp, int lp_ld, int* ctrl, int R);
+int i2t_caption_finish_ragged(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, const int64_t* prompt, int prompt_ld,
+                              const int* plen, int N, int max_new, int eos, int64_t pad, int* finished, int* lengths, float* tok_lp,
+                              int lp_ld, int* ctrl, int R);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).
