@@ -450,63 +450,45 @@ __global__ __launch_bounds__(64 * LSE_WAVES) void lse_token_logprob_kernel(const
 
 // The finish rule of a caption step, after the step's token landed at ids[r][len]: a row that finished earlier gets the
 // pad id and log-prob 0 there; a row whose new token is EOS is finished, its length len + 1 (the EOS kept).  ctrl[1] = rows still
-// unfinished (i2t_beam_advance raises ctrl[0] when it is 0).  One workgroup, block reduction, no atomics.
+// unfinished (i2t_beam_advance raises ctrl[0] when it is 0); without an EOS id the equal-length form keeps it at R.
+// RAGGED: rows whose prompts differ in length.  Row r of image b = r / N is forced to its prompt while len < plen[b]
+// (whatever the chooser wrote there is replaced, log-prob 0, the row counts as unfinished) and emits from plen[b] on, where the rule
+// above holds and the max_new-th emitted token finishes the row as well.  A column outside the id / log-prob rows is not touched
+// (ctrl[1] then stays 0 and i2t_beam_advance ends the steps).  The equal-length form reads neither prompt nor plen (both null).
+// One workgroup, block reduction, no atomics.
 constexpr int FIN_THREADS = 1024;
+template <bool RAGGED>
 __global__ __launch_bounds__(FIN_THREADS) void caption_finish_kernel(int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
-                                                                     int eos, int64_t pad, int* __restrict__ finished, int* __restrict__ lengths,
+                                                                     const int64_t* __restrict__ prompt, int prompt_ld,
+                                                                     const int* __restrict__ plen, int N, int max_new, int eos, int64_t pad,
+                                                                     int* __restrict__ finished, int* __restrict__ lengths,
                                                                      float* __restrict__ tok_lp, int lp_ld, int* __restrict__ ctrl, int R) {
     __shared__ int red[FIN_THREADS / 64];
     if (ctrl[0]) return;                                 // block-uniform: no thread writes ctrl[0]
     const int len = *len_ptr, tid = threadIdx.x;
+    if constexpr (RAGGED) {
+        if (len < 0 || len >= ids_ld || len >= lp_ld) return;
+    }
     int live = 0;
     for (int r = tid; r < R; r += FIN_THREADS) {
-        if (finished[r]) {
-            ids[(size_t)r * ids_ld + len] = pad;
-            tok_lp[(size_t)r * lp_ld + len] = 0.f;
-        } else if (eos >= 0 && ids[(size_t)r * ids_ld + len] == (int64_t)eos) {
-            finished[r] = 1;
-            lengths[r] = len + 1;
-        } else {
-            ++live;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = live;
-    __syncthreads();
-    if (tid == 0) {
-        int t = 0;
-        for (int k = 0; k < FIN_THREADS / 64; ++k) t += red[k];
-        ctrl[1] = eos < 0 ? R : t;
-    }
-}
-
-// The finish rule for rows whose prompts differ in length: row r of image b = r / N is forced to its prompt while
-// len < plen[b] (whatever the chooser wrote there is replaced, log-prob 0, the row counts as unfinished) and emits from plen[b] on,
-// where caption_finish_kernel's rule holds and the max_new-th emitted token finishes the row as well.  A column outside the id /
-// log-prob rows is not touched (ctrl[1] then stays 0 and i2t_beam_advance ends the steps).  One workgroup, no atomics.
-__global__ __launch_bounds__(FIN_THREADS) void caption_finish_ragged_kernel(int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
-                                                                            const int64_t* __restrict__ prompt, int prompt_ld,
-                                                                            const int* __restrict__ plen, int N, int max_new, int eos, int64_t pad,
-                                                                            int* __restrict__ finished, int* __restrict__ lengths,
-                                                                            float* __restrict__ tok_lp, int lp_ld, int* __restrict__ ctrl, int R) {
-    __shared__ int red[FIN_THREADS / 64];
-    if (ctrl[0]) return;                                 // block-uniform: no thread writes ctrl[0]
-    const int len = *len_ptr, tid = threadIdx.x;
-    if (len < 0 || len >= ids_ld || len >= lp_ld) return;
-    int live = 0;
-    for (int r = tid; r < R; r += FIN_THREADS) {
-        const int b = r / N, p = plen[b];
         int64_t* id = ids + (size_t)r * ids_ld + len;
         float* lp = tok_lp + (size_t)r * lp_ld + len;
-        if (len < p && len < prompt_ld) {
+        int b = 0, p = 0;
+        bool forced = false, spent = false;
+        if constexpr (RAGGED) {
+            b = r / N;
+            p = plen[b];
+            forced = len < p && len < prompt_ld;
+            spent = len + 1 - p >= max_new;
+        }
+        if (forced) {
             *id = prompt[(size_t)b * prompt_ld + len];
             *lp = 0.f;
             ++live;
         } else if (finished[r]) {
             *id = pad;
             *lp = 0.f;
-        } else if ((eos >= 0 && *id == (int64_t)eos) || len + 1 - p >= max_new) {
+        } else if ((eos >= 0 && *id == (int64_t)eos) || spent) {
             finished[r] = 1;
             lengths[r] = len + 1;
         } else {
@@ -520,7 +502,7 @@ __global__ __launch_bounds__(FIN_THREADS) void caption_finish_ragged_kernel(int6
     if (tid == 0) {
         int t = 0;
         for (int k = 0; k < FIN_THREADS / 64; ++k) t += red[k];
-        ctrl[1] = t;
+        ctrl[1] = !RAGGED && eos < 0 ? R : t;
     }
 }
 
@@ -648,8 +630,8 @@ extern "C" int i2t_top2_ngram_argmax_lp(void* stream, const float* top2, const f
 extern "C" int i2t_caption_finish(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, int eos, int64_t pad, int* finished, int* lengths,
                                   float* tok_lp, int lp_ld, int* ctrl, int R) {
     I2T_REQUIRE(ids && len_ptr && finished && lengths && tok_lp && ctrl && R > 0 && ids_ld > 0 && lp_ld > 0, "i2t_caption_finish: bad args");
-    hipLaunchKernelGGL(caption_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr, eos, pad, finished,
-                       lengths, tok_lp, lp_ld, ctrl, R);
+    hipLaunchKernelGGL(caption_finish_kernel<false>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr,
+                       (const int64_t*)nullptr, 0, (const int*)nullptr, 1, 0, eos, pad, finished, lengths, tok_lp, lp_ld, ctrl, R);
     I2T_CHECK_LAUNCH("i2t_caption_finish");
     return I2T_OK;
 }
@@ -660,7 +642,7 @@ extern "C" int i2t_caption_finish_ragged(void* stream, int64_t* ids, int ids_ld,
     I2T_REQUIRE(ids && len_ptr && prompt && plen && finished && lengths && tok_lp && ctrl && R > 0 && ids_ld > 0 && lp_ld > 0 && prompt_ld > 0,
                 "i2t_caption_finish_ragged: bad args");
     I2T_REQUIRE(N >= 1 && R % N == 0 && max_new >= 1, "i2t_caption_finish_ragged: %d rows in groups of %d, max_new %d", R, N, max_new);
-    hipLaunchKernelGGL(caption_finish_ragged_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr, prompt, prompt_ld,
+    hipLaunchKernelGGL(caption_finish_kernel<true>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr, prompt, prompt_ld,
                        plen, N, max_new, eos, pad, finished, lengths, tok_lp, lp_ld, ctrl, R);
     I2T_CHECK_LAUNCH("i2t_caption_finish_ragged");
     return I2T_OK;

@@ -396,8 +396,55 @@ class GreedyDecoder:
             args = (st.q, None, None, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, None, S, S, B, H, H, gq_hd)
             ops.beam_gq_decode_attention(*args, **kw) if kw else ops.gq_decode_attention(*args)
 
-    def _capture(self, st, with_head: bool, sampling: Optional[Sampling] = None, top2: bool = False):
-        return _capture_launches(st.arena.device, lambda: self._step(st, with_head, sampling, top2))
+    def _reusable(self, st, rows: int, total: int, extra=None) -> bool:
+        """Whether the cached state ``st`` serves a call over ``rows`` rows and ``total`` id columns on the current arena and sparse
+        tables; ``extra(st)``: what else the mode needs of it."""
+        eng = self.eng
+        return (st is not None and st.B == rows and st.arena is eng.arena and st.ids_ld >= total and st.sparse_epoch == eng.sparse_epoch
+                and (extra is None or extra(st)))
+
+    def _greedy_head(self, st, sampling: Optional[Sampling], logits: bool = False, lse: bool = False):
+        """-> (top2, the first element of the full step's graph key).  top2: a greedy step whose head takes the segment-maxima form
+        (nobody needs the ``logits``; d % 128 == 0: the persistent GEMM kernel's K rule; I2T_DECODE_TOP2=0: the logits form); its
+        buffers are made at the first such call, with the segment sums beside them when the step takes the token's log-prob (``lse``)."""
+        dc = self.eng.dec
+        top2 = sampling is None and not logits and TOP2_HEAD and dc.d % 128 == 0
+        if top2 and getattr(st, 'top2', None) is None:
+            nseg = (dc.V + 63) // 64
+            st.top2 = torch.zeros(st.B, nseg, 4, dtype=F32, device=st.arena.device)
+            if lse:
+                st.seg_se = torch.zeros(st.B, nseg, dtype=F32, device=st.arena.device)
+        return top2, ('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key()
+
+    def _replay(self, st, full_key, full_step, reset, n_prefill: int, n_full: int, use_graph: bool, each=None, poll_every: int = 0,
+                prefill_first: bool = False) -> int:
+        """The decode loop of every mode: ``reset()``, then ``n_prefill`` prefill steps (a prompt token into the cache, no head; graph
+        key None) and up to ``n_full`` full steps (``full_step()`` issues their launches; graph key ``full_key``), each one hipGraph
+        replay under ``use_graph``.  A step kind without a graph is captured first: both kinds run eagerly once (code objects must be
+        loaded before capture; ``prefill_first``: in which order), the missing ones are captured, and ``reset()`` undoes it.
+        ``each(i)`` runs after full step i.  ``poll_every`` > 0: every so many full steps the host reads st.ctrl[0:1] -- one 4-byte copy
+        -- and stops once it is raised.  -> the full steps launched."""
+        prefill = lambda: self._step(st, False)
+        reset()
+        if use_graph and (full_key not in st.graphs or None not in st.graphs):
+            kinds = ((None, prefill), (full_key, full_step)) if prefill_first else ((full_key, full_step), (None, prefill))
+            for _, fn in kinds:
+                fn()
+            for key, fn in kinds:
+                if key not in st.graphs:
+                    st.graphs[key] = _capture_launches(st.arena.device, fn)
+            reset()
+        for _ in range(n_prefill):                              # prompt tokens before the last: fill the cache only
+            st.graphs[None].launch() if use_graph else prefill()
+        replays = 0
+        while replays < n_full:
+            st.graphs[full_key].launch() if use_graph else full_step()
+            replays += 1
+            if each is not None:
+                each(replays - 1)
+            if poll_every and replays % poll_every == 0 and replays < n_full and int(st.ctrl[0:1].item()):
+                break
+        return replays
 
     def _prepare_inputs(self, st, images, B: int, W: int = 1):
         """Everything a step reads besides the ids: the encoder output of the B images, the per-layer cross K/V (B rows), the
@@ -468,46 +515,26 @@ class GreedyDecoder:
         B, P = prompt_ids.shape
         total = P + max_new_tokens
         st = self._state
-        if st is None or st.B != B or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch:
+        if not self._reusable(st, B, total):
             st = self._state = self._build(B, max(total, dc.block))
         assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
         assert not (return_margins and sampling is not None) and not (return_dists and sampling is None)
         self._prepare_inputs(st, images, B)
         if sampling is not None:
-            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+            _draw_seed(st.seed, sampling.seed)
             if return_dists != (st.dist is not None):         # captured sampling steps bake the dist pointer (or its absence)
                 st.dist = torch.zeros(B, dc.V, dtype=F32, device=a.device) if return_dists else None
                 st.graphs = {k: g for k, g in st.graphs.items() if k in (None, 'greedy', 'greedy_top2')}
-        # greedy without margins: the head in its segment-maxima form (d % 128 == 0: the persistent GEMM kernel's K rule; I2T_DECODE_TOP2=0: the logits form)
-        top2 = sampling is None and not return_margins and TOP2_HEAD and dc.d % 128 == 0
-        if top2 and getattr(st, 'top2', None) is None:
-            st.top2 = torch.zeros(B, (dc.V + 63) // 64, 4, dtype=F32, device=a.device)
-        full_key = ('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key()
+        top2, full_key = self._greedy_head(st, sampling, logits=return_margins)
 
         def reset():
             st.ids.zero_()
             st.ids[:, :P] = prompt_ids
             st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
-        reset()
         margins = torch.zeros(max_new_tokens, B, dtype=F32, device=a.device) if return_margins else None
         dists = torch.zeros(max_new_tokens, B, dc.V, dtype=F32, device=a.device) if return_dists else None
-        if use_graph and (full_key not in st.graphs or None not in st.graphs):
-            # warm up eagerly once (code objects must be loaded before capture), then capture the step kinds that are missing
-            self._step(st, True, sampling, top2)
-            self._step(st, False)
-            if full_key not in st.graphs:
-                st.graphs[full_key] = self._capture(st, True, sampling, top2)
-            if None not in st.graphs:
-                st.graphs[None] = self._capture(st, False)
-            reset()
-        for _ in range(P - 1):                                  # prompt tokens before the last: fill the cache only
-            st.graphs[None].launch() if use_graph else self._step(st, False)
-        for i in range(max_new_tokens):
-            st.graphs[full_key].launch() if use_graph else self._step(st, True, sampling, top2)
-            if return_margins:
-                margins[i].copy_(st.margin)
-            if return_dists:
-                dists[i].copy_(st.dist)
+        keep = (lambda i: margins[i].copy_(st.margin)) if return_margins else (lambda i: dists[i].copy_(st.dist)) if return_dists else None
+        self._replay(st, full_key, lambda: self._step(st, True, sampling, top2), reset, P - 1, max_new_tokens, use_graph, each=keep)
         out = st.ids[:, :total].clone()
         if return_margins:
             return out, margins.t().contiguous()
@@ -535,7 +562,7 @@ class BeamSpec(NamedTuple):
 
 class BeamDecoder(GreedyDecoder):
     """Beam search on the static KV cache: R = B * W rows (batch-major, r = b * W + w) through GreedyDecoder's buffers and layer
-    sequence, one captured hipGraph replay per token.  The step's head is the fp32 lm_head, then on the device (csrc/beam.hip):
+    sequence, under GreedyDecoder._replay (no poll).  The step's head is the fp32 lm_head, then on the device (csrc/beam.hip):
     i2t_beam_candidates (ban, crop, E candidates, EOS rule) -> i2t_beam_consolidate (W survivors per caption, ids and history rows
     moved to the children) -> i2t_beam_advance.  Survivors copy no K/V: the history table st.hist[r][t] names the cache row that
     holds key t of beam r, and the attention kernels read through it (a sparse layer's slot s through hist[r][st.kpos[l][s]], the
@@ -595,8 +622,8 @@ class BeamDecoder(GreedyDecoder):
         total = max(P, max_len)
         n_steps = total - P
         st = self._state
-        if (st is None or st.B != R or getattr(st, 'W', None) != W or st.arena is not a or st.ids_ld < total
-                or st.sparse_epoch != eng.sparse_epoch or st.spec.key() != spec.key() or (st.raw_tok is not None) != record):
+        if not self._reusable(st, R, total, lambda st: (getattr(st, 'W', None) == W and st.spec.key() == spec.key()
+                                                         and (st.raw_tok is not None) == record)):
             self._state = None
             st = self._state = self._build_beam(B, spec, max(total, dc.block), record)
         assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
@@ -605,7 +632,7 @@ class BeamDecoder(GreedyDecoder):
             ids = prompt_rows.view(B, W, P).clone()          # every beam already holds EOS: nothing to do
             return (ids, torch.zeros(B, W, device=a.device)) + (([],) if record else ())
         self._prepare_inputs(st, images, B, W)
-        _set_seed(st.seed, seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+        _draw_seed(st.seed, seed)
 
         def reset():
             st.ids.zero_()
@@ -618,20 +645,9 @@ class BeamDecoder(GreedyDecoder):
                 st.has_eos.zero_()
             else:
                 st.has_eos.copy_((prompt_rows == spec.eos).any(dim=-1))
-        reset()
-        if use_graph and 'beam' not in st.graphs:
-            self._step(st, False)                             # warm up eagerly once (code objects load before capture)
-            self._beam_step(st)
-            st.graphs[None] = self._capture(st, False)
-            st.graphs['beam'] = _capture_launches(a.device, lambda: self._beam_step(st))
-            reset()
-        for _ in range(P - 1):                                # prompt tokens before the last: fill the cache only
-            st.graphs[None].launch() if use_graph else self._step(st, False)
         draws = []
-        for _ in range(n_steps):
-            st.graphs['beam'].launch() if use_graph else self._beam_step(st)
-            if record:
-                draws.append((st.raw_tok.clone(), st.raw_pick.view(B, W).clone()))
+        self._replay(st, 'beam', lambda: self._beam_step(st), reset, P - 1, n_steps, use_graph, prefill_first=True,
+                     each=(lambda i: draws.append((st.raw_tok.clone(), st.raw_pick.view(B, W).clone()))) if record else None)
         L = int(st.counters[1].item())                        # the one host sync of the search
         ids = st.ids[:, :L].reshape(B, W, L).clone()
         scores = st.scores.view(B, W).clone()
@@ -664,24 +680,10 @@ def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional
     whole rows.  ``ids`` [R, P + T]: the prompt and the T tokens a chooser emitted for every row (it goes on emitting after an EOS).  A row
     is finished once it has EMITTED ``eos`` -- an EOS inside the prompt does not count --, that EOS is kept, later columns hold ``pad``
     (default: the EOS id) and log-prob 0.0, a row without one has length P + T; ``eos`` None: no rule.  The steps end once every row has
-    finished, so L = lengths.max().  -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - P] or None)"""
+    finished, so L = lengths.max().  This is ``apply_finish_rule_ragged`` with every prompt P long, less its refusals (no rows, or an
+    empty prompt, pass).  -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - P] or None)"""
     ids = np.array(ids)
-    R, total = ids.shape
-    lengths = np.full(R, total, dtype=np.int32)
-    if eos is not None:
-        pad = eos if pad is None else pad
-        for r in range(R):
-            hit = np.flatnonzero(ids[r, P:] == eos)
-            if hit.size:
-                lengths[r] = P + int(hit[0]) + 1
-    L = int(lengths.max()) if R else total
-    ids = ids[:, :L]
-    lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - P]
-    for r in range(R if eos is not None else 0):
-        ids[r, lengths[r]:] = pad
-        if lp is not None:
-            lp[r, lengths[r] - P:] = 0.0
-    return ids, lengths, lp
+    return _finish_rows(ids, np.full(ids.shape[0], P, dtype=np.int64), P, ids.shape[1] - P, eos, pad, token_logprobs)
 
 
 def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[int], pad: Optional[int] = None,
@@ -698,14 +700,19 @@ def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[
     plen = np.asarray(plen, dtype=np.int64).reshape(-1)
     R, total = ids.shape
     assert plen.shape == (R,) and R >= 1 and max_new >= 0 and int(plen.min()) >= 1 and int(plen.max()) + max_new == total
-    pmin = int(plen.min())
+    return _finish_rows(ids, plen, int(plen.min()), max_new, eos, pad, token_logprobs)
+
+
+def _finish_rows(ids: np.ndarray, plen: np.ndarray, pmin: int, max_new: int, eos, pad, token_logprobs):
+    """the rule both ``apply_finish_rule`` forms state; ``ids`` is the caller's copy and is written"""
+    R, total = ids.shape
     pad = (0 if eos is None else eos) if pad is None else pad
     lengths = (plen + max_new).astype(np.int32)
     for r in range(R if eos is not None else 0):
         hit = np.flatnonzero(ids[r, plen[r]:plen[r] + max_new] == eos)
         if hit.size:
             lengths[r] = plen[r] + int(hit[0]) + 1
-    L = int(lengths.max())
+    L = int(lengths.max()) if R else total
     ids = ids[:, :L]
     lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - pmin]
     for r in range(R):
@@ -718,11 +725,11 @@ def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[
 
 class CaptionDecoder(GreedyDecoder):
     """``generate_captions`` on the static KV cache: R = B * N rows (batch-major, r = b * N + n) through GreedyDecoder's buffers and layer
-    sequence, one captured hipGraph replay per token.  The encoder and the cross K/V run once per image (rows_per_mem = N); the
+    sequence, under GreedyDecoder._replay.  The encoder and the cross K/V run once per image (rows_per_mem = N); the
     self-attention cache is the identity one (no history table).  A step is _body -> _final_norm -> head and choice with the token's
     log-prob (i2t_gemm_bf16_top2_lse + i2t_top2_ngram_argmax_lp; or fp32 logits + i2t_ngram_ban_argmax_lp / i2t_sample_token_lp) ->
     i2t_caption_finish -> i2t_beam_advance.  Once every row has emitted EOS the device raises ctrl[0]; from then on no kernel of a
-    replay writes ids, tok_lp, finished or lengths, and the host, which reads that word every ``poll_every`` steps,
+    replay writes ids, tok_lp, finished or lengths, and the driver, which polls that word every ``poll_every`` steps,
     stops launching.  The decoder keeps its own state and graphs: nothing here touches what ``generate`` uses.
     With ``prompt_lengths`` the rows' prompts differ in length: the same state and buffers, Pmin - 1 prefill replays,
     then full steps that end in i2t_caption_finish_ragged, which puts a row's next prompt token over the chooser's while the column
@@ -744,7 +751,10 @@ class CaptionDecoder(GreedyDecoder):
         st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
         return st
 
-    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int):
+    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None):
+        """The launches of a full step.  ``forced``: None, or (prompt, plen, max_new) of a ``prompt_lengths`` call -- the finish rule is
+        then i2t_caption_finish_ragged; the choosers run as they are, on every row, and what they wrote at a forced column is replaced
+        after them."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
@@ -762,181 +772,85 @@ class CaptionDecoder(GreedyDecoder):
             else:
                 ops.sample_token_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, sampling.temperature,
                                     sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
-        ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
+        if forced is None:
+            ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
+        else:
+            prompt, plen, max_new = forced
+            ops.caption_finish_ragged(st.ids, st.ids_ld, len_ptr, prompt, plen, st.N, max_new, eos, pad, st.finished, st.lengths, st.tok_lp,
+                                      st.ctrl, R)
         ops.beam_advance(st.counters, st.ctrl)
 
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
                           use_graph: bool = True, prompt_lengths=None) -> GeneratedCaptions:
-        if prompt_lengths is not None:
-            return self._generate_captions_ragged(images, prompt_ids, prompt_lengths, max_new_tokens, eos, pad, int(num_return_sequences),
-                                                  sampling, poll_every, use_graph)
+        """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
+        rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
+        None is the case Pmin = Pmax = P, which needs no forcing table."""
         eng = self.eng
         dc = eng.dec
         N = int(num_return_sequences)
-        check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
-        if not dc.causal:
-            raise ValueError('CaptionDecoder needs a causal decoder')
-        a = eng.prepare(False)
-        prompt_ids = prompt_ids.to(a.device)
         B, P = prompt_ids.shape
-        R, total = B * N, P + max_new_tokens
-        pad = (0 if eos is None else eos) if pad is None else pad
-        st = self._state
-        if (st is None or st.B != R or st.N != N or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch):
-            self._state = None
-            st = self._state = self._build_captions(B, N, max(total, dc.block))
-        if total > st.tmax:
-            raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({st.tmax})')
-        self._prepare_inputs(st, images, B, N)
-        if sampling is not None:
-            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
-        top2 = sampling is None and TOP2_HEAD and dc.d % 128 == 0          # as generate() chooses the form of the greedy head
-        if top2 and st.top2 is None:
-            nseg = (dc.V + 63) // 64
-            st.top2 = torch.zeros(R, nseg, 4, dtype=F32, device=a.device)
-            st.seg_se = torch.zeros(R, nseg, dtype=F32, device=a.device)
-        # eos and pad are kernel arguments: a captured step holds them
-        full_key = (('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key(), eos, pad)
-        prompt_rows = prompt_ids.repeat_interleave(N, dim=0) if N > 1 else prompt_ids
-
-        def reset():
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_rows
-            st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
-            st.ctrl.zero_()
-            st.finished.zero_()
-            st.lengths.fill_(total)
-            st.tok_lp.zero_()
-        reset()
-        if use_graph and (full_key not in st.graphs or None not in st.graphs):
-            self._caption_step(st, sampling, top2, eos, pad)  # warm up eagerly once (code objects load before capture)
-            self._step(st, False)
-            if full_key not in st.graphs:
-                st.graphs[full_key] = _capture_launches(a.device, lambda: self._caption_step(st, sampling, top2, eos, pad))
-            if None not in st.graphs:
-                st.graphs[None] = self._capture(st, False)
-            reset()
-        for _ in range(P - 1):                                # prompt tokens before the last: fill the cache only
-            st.graphs[None].launch() if use_graph else self._step(st, False)
-        replays = 0
-        for i in range(max_new_tokens):
-            st.graphs[full_key].launch() if use_graph else self._caption_step(st, sampling, top2, eos, pad)
-            replays += 1
-            if eos is not None and poll_every and replays % poll_every == 0 and replays < max_new_tokens:
-                if int(st.ctrl[0:1].item()):                  # one 4-byte copy: every row has emitted EOS
-                    break
-        self.last_replays = replays
-        lengths = st.lengths.clone()
-        L = int(lengths.max().item()) if max_new_tokens else P          # the final host sync
-        ids = st.ids[:, :L].reshape(B, N, L).clone()
-        tok_lp = st.tok_lp[:, P:L].reshape(B, N, L - P).clone()
-        return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1))
-
-
-    def _caption_step_ragged(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, max_new: int):
-        """_caption_step with i2t_caption_finish_ragged as its finish rule: the choosers run as they are, on every row; what they
-        wrote at a forced column is replaced after them"""
-        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
-        R, d = st.B, dc.d
-        len_ptr, done = st.counters[1:2], st.ctrl[0:1]
-        nn = st.ngrams.numel()
-        self._body(st)
-        self._final_norm(st)
-        if top2:
-            ops.gemm_top2_lse(st.hid, a.W(eng.n_head), st.top2, st.seg_se, R, dc.V, d)
-            ops.top2_ngram_argmax_lp(st.top2, st.seg_se, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, d, done,
-                                     st.tok_lp)
+        ragged = prompt_lengths is not None
+        if ragged:
+            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens)
+            pmin, pmax = int(plen.min()), int(plen.max())
         else:
-            ops.gemm(st.hid, a.W(eng.n_head), st.logits, R, dc.V, d, workspace=st.ws)
-            if sampling is None:
-                ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
-            else:
-                ops.sample_token_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, sampling.temperature,
-                                    sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
-        ops.caption_finish_ragged(st.ids, st.ids_ld, len_ptr, st.rag_prompt, st.rag_plen, st.N, max_new, eos, pad, st.finished, st.lengths,
-                                  st.tok_lp, st.ctrl, R)
-        ops.beam_advance(st.counters, st.ctrl)
-
-    def _generate_captions_ragged(self, images, prompt_ids: torch.Tensor, prompt_lengths, max_new_tokens: int, eos: Optional[int],
-                                  pad: Optional[int], N: int, sampling: Optional[Sampling], poll_every: int, use_graph: bool):
-        """generate_captions(prompt_lengths=...): row (b, n) is prompt_ids[b, :p_b] and up to max_new_tokens emitted tokens.  All rows
-        share the step's column counter; a row whose prompt reaches past the column is forced on the device."""
-        eng = self.eng
-        dc = eng.dec
-        B, P = prompt_ids.shape
-        plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens)
+            check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
+            pmin = pmax = P
         if not dc.causal:
             raise ValueError('CaptionDecoder needs a causal decoder')
         a = eng.prepare(False)
-        pmin, pmax = int(plen.min()), int(plen.max())
         R, total = B * N, pmax + max_new_tokens
         pad = (0 if eos is None else eos) if pad is None else pad
         st = self._state
-        if (st is None or st.B != R or st.N != N or st.arena is not a or st.ids_ld < total or st.sparse_epoch != eng.sparse_epoch):
+        if not self._reusable(st, R, total, lambda st: st.N == N):
             self._state = None
             st = self._state = self._build_captions(B, N, max(total, dc.block))
         if total > st.tmax:
             raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({st.tmax})')
-        if st.rag_prompt is None:                               # persistent: the captured steps bake their pointers
-            st.rag_prompt = torch.zeros(B, st.ids_ld, dtype=torch.long, device=a.device)
-            st.rag_plen = torch.ones(B, dtype=torch.int32, device=a.device)
-        plen_dev = torch.from_numpy(plen).to(a.device)
-        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
-        keep = torch.arange(pmax, device=a.device)[None, :] < plen_dev[:, None]
-        prompt = torch.where(keep, prompt_ids[:, :pmax].to(a.device), torch.zeros((), dtype=torch.long, device=a.device))
-        st.rag_prompt.zero_()
-        st.rag_prompt[:, :pmax] = prompt
-        st.rag_plen.copy_(plen_dev)
-        prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
-        len_rows = (plen_dev.repeat_interleave(N) if N > 1 else plen_dev) + max_new_tokens
-        if max_new_tokens == 0:                               # nothing to emit: the prompts, padded
-            ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
-            self.last_replays = 0
-            zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
-            return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev)
+        prompt = prompt_ids[:, :pmax].to(a.device)
+        plen_dev = forced = None
+        if ragged:
+            if st.rag_prompt is None:                           # persistent: the captured steps bake their pointers
+                st.rag_prompt = torch.zeros(B, st.ids_ld, dtype=torch.long, device=a.device)
+                st.rag_plen = torch.ones(B, dtype=torch.int32, device=a.device)
+            plen_dev = torch.from_numpy(plen).to(a.device)
+            # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
+            keep = torch.arange(pmax, device=a.device)[None, :] < plen_dev[:, None]
+            prompt = torch.where(keep, prompt, torch.zeros((), dtype=torch.long, device=a.device))
+            st.rag_prompt.zero_()
+            st.rag_prompt[:, :pmax] = prompt
+            st.rag_plen.copy_(plen_dev)
+            len_rows = (plen_dev.repeat_interleave(N) if N > 1 else plen_dev) + max_new_tokens
+            if max_new_tokens == 0:                           # nothing to emit: the prompts, padded
+                ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
+                self.last_replays = 0
+                zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
+                return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev)
+            forced = (st.rag_prompt, st.rag_plen, max_new_tokens)
         self._prepare_inputs(st, images, B, N)
         if sampling is not None:
-            _set_seed(st.seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
-        top2 = sampling is None and TOP2_HEAD and dc.d % 128 == 0
-        if top2 and st.top2 is None:
-            nseg = (dc.V + 63) // 64
-            st.top2 = torch.zeros(R, nseg, 4, dtype=F32, device=a.device)
-            st.seg_se = torch.zeros(R, nseg, dtype=F32, device=a.device)
+            _draw_seed(st.seed, sampling.seed)
+        top2, head = self._greedy_head(st, sampling, lse=True)
         # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key)
-        full_key = ('ragged', ('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key(), eos, pad, max_new_tokens)
+        full_key = ('ragged', head, eos, pad, max_new_tokens) if ragged else (head, eos, pad)
+        prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
             st.ids.zero_()
             st.ids[:, :pmax] = prompt_rows
-            st.counters.copy_(st.counters_init)
+            st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
             st.ctrl.zero_()
             st.finished.zero_()
-            st.lengths.copy_(len_rows)                          # what a row without an EOS ends with: p_b + max_new_tokens
+            # what a row without an EOS ends with: p_b + max_new_tokens
+            st.lengths.copy_(len_rows) if ragged else st.lengths.fill_(total)
             st.tok_lp.zero_()
-        reset()
-        if use_graph and (full_key not in st.graphs or None not in st.graphs):
-            self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens)          # eagerly once: code objects load before capture
-            self._step(st, False)
-            if full_key not in st.graphs:
-                st.graphs[full_key] = _capture_launches(a.device, lambda: self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens))
-            if None not in st.graphs:
-                st.graphs[None] = self._capture(st, False)
-            reset()
-        for _ in range(pmin - 1):                               # columns every row holds a prompt token in: fill the cache only
-            st.graphs[None].launch() if use_graph else self._step(st, False)
-        n_full = pmax - pmin + max_new_tokens                   # the longest prompt's row emits its last token in step n_full
-        replays = 0
-        for i in range(n_full):
-            st.graphs[full_key].launch() if use_graph else self._caption_step_ragged(st, sampling, top2, eos, pad, max_new_tokens)
-            replays += 1
-            if eos is not None and poll_every and replays % poll_every == 0 and replays < n_full:
-                if int(st.ctrl[0:1].item()):
-                    break
-        self.last_replays = replays
+        # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
+        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced), reset, pmin - 1,
+                                         pmax - pmin + max_new_tokens, use_graph, poll_every=poll_every if eos is not None else 0)
         lengths = st.lengths.clone()
-        L = int(lengths.max().item())
+        L = int(lengths.max().item()) if max_new_tokens else pmax       # the final host sync
         ids = st.ids[:, :L].reshape(B, N, L).clone()
         tok_lp = st.tok_lp[:, pmin:L].reshape(B, N, L - pmin).clone()
         return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev)
@@ -978,6 +892,11 @@ def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: 
     if B and int(plen.max()) > P:
         raise ValueError(f'prompt_lengths[{int(plen.argmax())}] = {int(plen.max())} exceeds the {P} columns of prompt_ids')
     return plen.astype(np.int32)
+
+
+def _draw_seed(buf: torch.Tensor, seed: Optional[int]):
+    """``seed`` into ``buf``; None: one draw from torch's CPU generator, so ``torch.manual_seed`` reproduces the call"""
+    _set_seed(buf, seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
 
 
 def _set_seed(buf: torch.Tensor, seed: int):
@@ -1023,7 +942,7 @@ def generate_by_recompute(model, images, prompt_ids: torch.Tensor, max_new_token
     margin = torch.zeros(B, dtype=F32, device=dev)
     seed = torch.zeros(2, dtype=torch.int32, device=dev)
     if sampling is not None:
-        _set_seed(seed, sampling.seed if sampling.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
+        _draw_seed(seed, sampling.seed)
     for t in range(P, total):
         cond = ids[:, :t] if t <= blk else ids[:, t - blk:t]                     # the reference crops the conditioning to the block
         Tc = cond.shape[1]

@@ -261,45 +261,18 @@ class VisionEncoderDecoder(nn.Module):
         (int32 [B]; None without the argument).  None (the default) is the path above, unchanged.  For a NON-causal decoder this is
         ``generate_by_recompute`` once per distinct length over the rows of that length, then the host rule and ``score``: it exists
         for completeness, not for speed."""
-        from ..decoding import CaptionDecoder, Sampling, apply_finish_rule, check_caption_args, generate_by_recompute
+        import numpy as np
+        from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, check_caption_args,
+                                check_ragged_caption_args, generate_by_recompute)
         N = int(num_return_sequences)
         sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
-        if prompt_lengths is not None:
-            return self._generate_captions_ragged(images, prompt_ids, prompt_lengths, max_new_tokens, eos_token_id, pad_token_id, N, sampling,
-                                                  poll_every)
-        check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
         B, P = prompt_ids.shape
-        blk_size = self.decoder.block_size - self.space_for_prompt
-        if P + max_new_tokens > blk_size:
-            raise ValueError(f'prompt + new tokens ({P + max_new_tokens}) exceed the text window ({blk_size})')
-        dev = next(self.parameters()).device
-        prompt_ids = prompt_ids.to(dev)
-        if self._engine.dec.causal:
-            if self._captioner is None:
-                object.__setattr__(self, '_captioner', CaptionDecoder(self))
-            return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every)
-        from ..decoding import GeneratedCaptions
-        images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
-        raw = generate_by_recompute(self, images_rep, prompt_ids.repeat_interleave(N, dim=0), max_new_tokens, sampling)
-        ids, lengths, _ = apply_finish_rule(raw.cpu().numpy(), P, eos_token_id, pad_token_id)
-        ids, lengths = torch.from_numpy(ids).to(dev), torch.from_numpy(lengths).to(dev)
-        L = ids.shape[1]
-        labels = next_token_labels(ids, -100)
-        labels[torch.arange(L, device=dev)[None, :] >= (lengths[:, None] - 1)] = -100            # nothing follows a row's last token
-        lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, P - 1:L - 1] if L > P else torch.zeros(B * N, 0, device=dev)
-        lp = lp.reshape(B, N, L - P).contiguous()
-        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1))
-
-    def _generate_captions_ragged(self, images, prompt_ids, prompt_lengths, max_new_tokens, eos_token_id, pad_token_id, N, sampling,
-                                  poll_every):
-        """generate_captions with ``prompt_lengths``: the host-side checks, then CaptionDecoder; for a non-causal decoder one
-        ``generate_by_recompute`` per distinct length, the host rule and ``score``"""
-        import numpy as np
-        from ..decoding import (CaptionDecoder, GeneratedCaptions, apply_finish_rule_ragged, check_ragged_caption_args,
-                                generate_by_recompute)
-        B, P = prompt_ids.shape
-        plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
-        pmin, pmax = int(plen.min()), int(plen.max())
+        if prompt_lengths is None:
+            check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+            plen, pmin, pmax = None, P, P
+        else:
+            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+            pmin, pmax = int(plen.min()), int(plen.max())
         blk_size = self.decoder.block_size - self.space_for_prompt
         if pmax + max_new_tokens > blk_size:
             raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({blk_size})')
@@ -310,12 +283,14 @@ class VisionEncoderDecoder(nn.Module):
                 object.__setattr__(self, '_captioner', CaptionDecoder(self))
             return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
                                                      prompt_lengths=plen)
-        rows = np.repeat(plen, N)
+        # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
+        images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
+        prompt_rep = prompt_ids.repeat_interleave(N, dim=0)
+        rows = np.repeat(np.full(B, P, dtype=np.int32) if plen is None else plen, N)
         table = np.zeros((B * N, pmax + max_new_tokens), dtype=np.int64)
-        for p in sorted(set(plen.tolist())):
-            of_p = torch.from_numpy(np.flatnonzero(plen == p)).to(dev)
-            raw = generate_by_recompute(self, images[of_p].repeat_interleave(N, dim=0), prompt_ids[of_p, :p].repeat_interleave(N, dim=0),
-                                        max_new_tokens, sampling)
+        for p in sorted(set(rows.tolist())):
+            of_p = torch.from_numpy(np.flatnonzero(rows == p)).to(dev)
+            raw = generate_by_recompute(self, images_rep[of_p], prompt_rep[of_p, :p], max_new_tokens, sampling)
             table[rows == p, :p + max_new_tokens] = raw.cpu().numpy()
         ids, lengths, _ = apply_finish_rule_ragged(table, rows, max_new_tokens, eos_token_id, pad_token_id)
         ids, lengths = torch.from_numpy(ids).to(dev), torch.from_numpy(lengths).to(dev)
@@ -323,13 +298,10 @@ class VisionEncoderDecoder(nn.Module):
         col = torch.arange(L, device=dev)[None, :]
         labels = next_token_labels(ids, -100)
         # the label at column c is the token at c + 1: scored from a row's first emitted token to its last
-        rows_dev = torch.from_numpy(rows).to(dev)
-        labels[(col >= lengths[:, None] - 1) | (col < rows_dev[:, None] - 1)] = -100
-        images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
+        labels[(col >= lengths[:, None] - 1) | (col < torch.from_numpy(rows).to(dev)[:, None] - 1)] = -100
         lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, pmin - 1:L - 1] if L > pmin else torch.zeros(B * N, 0, device=dev)
         lp = lp.reshape(B, N, L - pmin).contiguous()
-        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), torch.from_numpy(plen).to(dev))
-
+        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), None if plen is None else torch.from_numpy(plen).to(dev))
 
     @torch.no_grad()
     def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:
