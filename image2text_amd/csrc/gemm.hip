@@ -2,7 +2,7 @@
 //
 //   C[M,N] = epilogue(alpha * op(A)[M,K] . op(B)[K,N])
 //
-// Three kernels behind one entry point (i2t_gemm_bf16 picks by shape; routing at the bottom of the file):
+// Three kernels behind one entry point (i2t_gemm_bf16 picks by shape: the rule is gemm_route.h::gemm_route, this file launches what it says):
 //   gemm256_kernel   persistent 256 x 256 x 64 tiles, 8 waves, LDS-DMA staging with counted waits -- every problem with
 //                    >= 40 such tiles and every dW = dY^T.X problem (K slices + atomics): the workhorse, see its header;
 //   gemm_bf16_kernel 128 x 128 x 64 tiles, 4 waves (2 x 2, 64 x 64 each), register-staged double buffer, one barrier per
@@ -21,9 +21,12 @@
 // Block -> tile maps are XCD-aware (8 XCDs, private L2s) and N-fastest inside groups of column tiles, so an activation row
 // panel is fetched once per group and a weight group stays in one L2.
 #include "common.h"
+#include "gemm_route.h"
 #include <stdlib.h>
 #include <string.h>
 #include <utility>
+
+using namespace i2t;
 
 namespace {
 
@@ -61,9 +64,9 @@ struct GemmParams {
     int g2_splits, g2_nk;     // 256^2 kernel: K slices per output tile and K-tiles per slice (even)
     int g2_gn;                // 256^2 kernel: column tiles per group of the tile order
     int g2_dbg;               // experiment (I2T_G256_DBG): 1 = epilogue without its global stores, 2 = no epilogue at all
-    const float* scale_a = nullptr;   // class 9 (fp8 operands, i2t_gemm_fp8): per-row scales of A [M] and of B [N] applied to the accumulators
-    const float* scale_b = nullptr;
-    float* colsum_out = nullptr;      // class 13 (split-K dW with the bias gradient as a by-product): colsum_out[m] += sum_k A[k][m] / (sqrt(*alpha_sumsq) + 1e-6)
+    const float* scale_a;             // class 9 (fp8 operands, i2t_gemm_fp8): per-row scales of A [M] and of B [N] applied to the accumulators
+    const float* scale_b;
+    float* colsum_out;                // class 13 (split-K dW with the bias gradient as a by-product): colsum_out[m] += sum_k A[k][m] / (sqrt(*alpha_sumsq) + 1e-6)
     int g2_stagger, g2_stagger_groups;   // experiment: start delay (units of s_sleep 127) x (workgroup index within its XCD mod groups)
     // fused cross-attention (epilogue class 8, see xattn_epilogue): queries, outputs and shapes
     const bf16_t* xq; long xq_bs; int xq_rs;      // Q [B, T, >= 64 H] (batch stride used when xcu is null) or packed [rows, >= 64 H]
@@ -175,9 +178,9 @@ __device__ __forceinline__ bf16x8 frag_read(const unsigned char* lds, int r0, in
 }
 
 template <int N, class F, int... Is>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
+__host__ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
+__host__ __device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
 
 // Epilogue shared by the GEMM kernels.  SPLITK: un-swapped accumulators, float atomics; else fused bias / GELU /
 // GELU' / residual / accumulate with 8-/16-byte vector stores.
@@ -2211,23 +2214,6 @@ __global__ __launch_bounds__(512) void gemm3_kernel(GemmParams p) {
     }
 }
 
-int g256_epilogue_class(const GemmParams& p) {
-    const bool fast4 = (p.ldc & 3) == 0 && (!p.residual || (p.ldr & 3) == 0) && (!p.aux_in || (p.ld_aux_in & 3) == 0) &&
-                       (!p.aux_out || (p.ld_aux_out & 3) == 0);
-    const bool none = p.act == I2T_ACT_NONE && !p.aux_out;
-    // bias-free only: a straddling quad would read bias[N .. N+2]
-    if (fast4 && (p.N & 3) != 0 && none && !p.bias && !p.residual && !p.accumulate && !p.drop_mode) return 7;
-    if (!fast4 || (p.N & 3) != 0) return 0;
-    if (!p.c_is_f32 && none && !p.residual && !p.accumulate && p.drop_mode != 1) return 1;
-    if (!p.c_is_f32 && p.act == I2T_ACT_GELU && !p.drop_mode && !p.residual && !p.accumulate) return 2;
-    if (!p.c_is_f32 && p.act == I2T_ACT_GELU_DOUT && !p.drop_mode && !p.residual && !p.accumulate) return 10;
-    if (!p.c_is_f32 && p.act == I2T_ACT_MUL_AUX && !p.bias && !p.aux_out && !p.drop_mode && !p.residual && !p.accumulate) return 11;
-    if (p.c_is_f32 && none && !p.accumulate && p.drop_mode != 2 && (p.residual || p.bias || p.drop_mode)) return 3;
-    if (!p.c_is_f32 && p.act == I2T_ACT_DGELU && !p.bias && !p.aux_out && !p.drop_mode && !p.residual && !p.accumulate) return 4;
-    if (p.c_is_f32 && none && !p.bias && !p.residual && !p.drop_mode) return 5;
-    return 0;
-}
-
 // CUs the persistent kernels may occupy: all of them, unless i2t_gemm_set_cu_limit reserved some (see include/i2t.h)
 int g_cu_reserve = 0;
 int g256_cus() {
@@ -2241,13 +2227,65 @@ int g256_cus() {
     return (r > 0 && r < n_cu - 8) ? n_cu - r : n_cu;
 }
 
-void launch_g3(hipStream_t s, GemmParams p, bool overlap) {
+// Every I2T_* variable the GEMM host code reads, read here and nowhere else.  Once per process: I2T_GEMM, I2T_G256_NARROW,
+// I2T_G256_GN, I2T_G256_STAGGER, I2T_G256_DBG, I2T_GEMM_LOG.  Per call (tests flip them inside one process): the rest.
+GemmKnobs gemm_knobs() {
+    static const GemmKnobs once = [] {
+        GemmKnobs k{};
+        const char* e = getenv("I2T_GEMM");
+        k.no_g256 = e && !strcmp(e, "v1");
+        e = getenv("I2T_G256_NARROW");
+        k.narrow_256 = e && e[0] == '1';
+        e = getenv("I2T_G256_GN");
+        k.gn = e ? atoi(e) : 8;
+        if (k.gn <= 0) k.gn = 8;
+        e = getenv("I2T_G256_STAGGER");                   // "units[,groups]"
+        k.stagger = e ? atoi(e) : 0;
+        k.stagger_groups = (e && strchr(e, ',')) ? atoi(strchr(e, ',') + 1) : 2;
+        if (k.stagger_groups < 2) k.stagger_groups = 2;
+        e = getenv("I2T_G256_DBG");
+        k.g256_dbg = e ? atoi(e) : 0;
+        k.log = getenv("I2T_GEMM_LOG") != nullptr;
+        return k;
+    }();
+    GemmKnobs k = once;
+    const char* e = getenv("I2T_G256_MIN_TILES");
+    k.min_tiles = e ? atol(e) : 40;
+    e = getenv("I2T_GEMM3");
+    k.gemm3 = e ? atoi(e) : 0;
+    k.skinny_ksplit = getenv("I2T_SKINNY_KSPLIT") != nullptr;
+    e = getenv("I2T_FOLD_COLSUM");
+    k.fold_colsum = !(e && e[0] == '0');
+    e = getenv("I2T_DW_SPLITS");                          // experiments
+    k.dw_splits = e ? atoi(e) : 0;
+    e = getenv("I2T_G3_DBG");
+    k.g3_dbg = e ? atoi(e) : 0;
+    e = getenv("I2T_FP8_G256");
+    k.fp8_g256 = !(e && e[0] == '0');
+    return k;
+}
+
+// Every launch of the persistent 256^2 kernel.  One 8-wave workgroup per CU (fewer when there is less to do) walks
+// tiles_m x ceil(N / 256) output tiles x `splits` K slices of `nk` K-tiles (an even number) each; `gn` = column tiles per group of the
+// tile order.  The usual values are rows256(M), 1, even_ktiles(K) and I2T_G256_GN; what a caller passes instead is its own business
+// and stands at the call.
+constexpr int rows256(int M) { return (M + 255) / 256; }
+constexpr int even_ktiles(int K) { return (((K + 63) >> 6) + 1) & ~1; }
+
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI>
+void launch_persistent(hipStream_t s, GemmParams p, int tiles_m, int splits, int nk, int gn) {
+    p.tiles_m = tiles_m; p.tiles_n = (p.N + 255) / 256;
+    p.g2_splits = splits; p.g2_nk = nk; p.g2_gn = gn;
+    const int items = p.tiles_m * p.tiles_n * splits, n_cu = g256_cus();
+    hipLaunchKernelGGL((gemm256_kernel<A_KMAJOR, B_KMAJOR, EPI>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
+}
+
+void launch_g3(hipStream_t s, GemmParams p, int cls, bool overlap, int g3_dbg) {
     const int n_cu = g256_cus();
-    { const char* e = getenv("I2T_G3_DBG"); p.g2_stagger = e ? atoi(e) : 0; }
+    p.g2_stagger = g3_dbg;
     p.tiles_m = (p.M + 255) / 256; p.tiles_n = (p.N + 127) / 128;
     const int tiles = p.tiles_m * p.tiles_n;
     const dim3 grid(tiles < n_cu ? tiles : n_cu), block(512);
-    const int cls = g256_epilogue_class(p);
     if (cls == 2) {
         if (overlap) hipLaunchKernelGGL((gemm3_kernel<2, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((gemm3_kernel<2, false>), grid, block, 0, s, p);
@@ -2257,32 +2295,20 @@ void launch_g3(hipStream_t s, GemmParams p, bool overlap) {
     }
 }
 
+// cls: what gemm_route chose -- classes 2, 3, 7, 10 are built for the B^T form only, 4 and 11 for the B form only (NO fall-through
+// between cases: a wrong class dereferences a null epilogue operand)
 template <bool B_KMAJOR>
-void launch_g256(hipStream_t s, GemmParams p) {
-    const int n_cu = g256_cus();
-    p.tiles_m = (p.M + 255) / 256; p.tiles_n = (p.N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = (((p.K + 63) >> 6) + 1) & ~1;
-    const int tiles = p.tiles_m * p.tiles_n;
-    const dim3 grid(tiles < n_cu ? tiles : n_cu), block(512);
-    // forward GEMMs (B^T form) meet classes 1-3, the dX GEMMs (B form) classes 1, 4, 5; anything else runs the generic one
-    static const bool log_cls = getenv("I2T_GEMM_LOG") != nullptr;
-    if (log_cls)
-        fprintf(stderr, "[g256] class %d bk=%d M=%d N=%d K=%d f32=%d bias=%d act=%d auxo=%d auxi=%d res=%d acc=%d drop=%d ldc=%d\n",
-                g256_epilogue_class(p), (int)B_KMAJOR, p.M, p.N, p.K, p.c_is_f32, p.bias != nullptr, p.act, p.aux_out != nullptr,
-                p.aux_in != nullptr, p.residual != nullptr, p.accumulate, p.drop_mode, p.ldc);
-    // forward GEMMs (B^T form) meet classes 1, 2, 3, 5, 7, the dX GEMMs (B form) classes 1, 4, 5; a class that is not built for
-    // the layout runs the generic kernel (NO fall-through between cases: a wrong class dereferences a null epilogue operand)
-    int cls = g256_epilogue_class(p);
-    if (B_KMAJOR ? (cls == 2 || cls == 3 || cls == 7 || cls == 10) : (cls == 4 || cls == 11)) cls = 0;
-    if (cls == 1) hipLaunchKernelGGL((gemm256_kernel<false, B_KMAJOR, 1>), grid, block, 0, s, p);
-    else if (cls == 5) hipLaunchKernelGGL((gemm256_kernel<false, B_KMAJOR, 5>), grid, block, 0, s, p);
-    else if (cls == 2) hipLaunchKernelGGL((gemm256_kernel<false, false, 2>), grid, block, 0, s, p);
-    else if (cls == 3) hipLaunchKernelGGL((gemm256_kernel<false, false, 3>), grid, block, 0, s, p);
-    else if (cls == 7) hipLaunchKernelGGL((gemm256_kernel<false, false, 7>), grid, block, 0, s, p);
-    else if (cls == 4) hipLaunchKernelGGL((gemm256_kernel<false, true, 4>), grid, block, 0, s, p);
-    else if (cls == 10) hipLaunchKernelGGL((gemm256_kernel<false, false, 10>), grid, block, 0, s, p);
-    else if (cls == 11) hipLaunchKernelGGL((gemm256_kernel<false, true, 11>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<false, B_KMAJOR, 0>), grid, block, 0, s, p);
+void launch_g256(hipStream_t s, const GemmParams& p, int cls) {
+    const int tm = rows256(p.M), nk = even_ktiles(p.K), gn = p.g2_gn;
+    if (cls == 1) launch_persistent<false, B_KMAJOR, 1>(s, p, tm, 1, nk, gn);
+    else if (cls == 5) launch_persistent<false, B_KMAJOR, 5>(s, p, tm, 1, nk, gn);
+    else if (cls == 2) launch_persistent<false, false, 2>(s, p, tm, 1, nk, gn);
+    else if (cls == 3) launch_persistent<false, false, 3>(s, p, tm, 1, nk, gn);
+    else if (cls == 7) launch_persistent<false, false, 7>(s, p, tm, 1, nk, gn);
+    else if (cls == 4) launch_persistent<false, true, 4>(s, p, tm, 1, nk, gn);
+    else if (cls == 10) launch_persistent<false, false, 10>(s, p, tm, 1, nk, gn);
+    else if (cls == 11) launch_persistent<false, true, 11>(s, p, tm, 1, nk, gn);
+    else launch_persistent<false, B_KMAJOR, 0>(s, p, tm, 1, nk, gn);
 }
 
 }  // namespace
@@ -2291,63 +2317,31 @@ void launch_g256(hipStream_t s, GemmParams p) {
 // K-tile).  False = not eligible (the caller keeps its own 128 x 128 kernel): K % 256, alignment, fewer tiles than the hand-over point.
 bool i2t_g256_fp8_try(hipStream_t s, const void* A8, int lda, const float* sa, const void* B8, int ldb, const float* sb, void* C, int ldc,
                       int c_is_f32, int M, int N, int K, const float* bias, int act, const float* residual, int ldr) {
-    const char* off = getenv("I2T_FP8_G256");
-    if (off && off[0] == '0') return false;
+    if (!gemm_knobs().fp8_g256) return false;
     if (K % 256 != 0 || (lda & 15) || (ldb & 15) || (N & 3) || (ldc & 3) || (residual && (ldr & 3)) || !ALIGNED16(A8) || !ALIGNED16(B8) || !ALIGNED16(C) ||
         (bias && !ALIGNED16(bias)) || !ALIGNED16(sb) || (size_t)M * lda >= (1ull << 32) || (size_t)N * ldb >= (1ull << 32))
         return false;
     if ((long)((M + 255) / 256) * ((N + 255) / 256) < 40) return false;
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
+    GemmParams p{};
     p.A = (const bf16_t*)A8; p.B = (const bf16_t*)B8; p.C = C;
     p.M = M; p.N = N; p.K = K / 2; p.lda = lda / 2; p.ldb = ldb / 2; p.ldc = ldc;
     p.alpha = 1.0f; p.bias = bias; p.act = act; p.residual = residual; p.ldr = ldr; p.c_is_f32 = c_is_f32;
     p.scale_a = sa; p.scale_b = sb;
-    p.g2_gn = 8;
-    const int n_cu = g256_cus();
-    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = p.K >> 6;                               // K % 256 == 0: an even number of 128-byte K-tiles
-    const int tiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm256_kernel<false, false, 9>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, s, p);
+    launch_persistent<false, false, 9>(s, p, rows256(M), 1, p.K >> 6, 8);      // K % 256 == 0: an even number of 128-byte K-tiles
     return true;
 }
 namespace {
 
-// dW = A^T . B accumulated into an fp32 C (both operands k-major): K slices spread over the CUs when the output has too
-// few 256^2 tiles, partial tiles combined with float atomics (C already holds the value to accumulate onto); with enough
-// tiles (the tied lm_head / embedding gradient) one slice and a plain read-add-write epilogue.
 void launch_colsum(hipStream_t s, const bf16_t* X, int ld, int M, int N, float* out, const float* alpha_sumsq);
 
-// p.colsum_out (or null): the row sums of the A panel are added to it as well -- inside the split-K kernel (class 13) unless the
-// caller set fold_colsum to false, by a column-sum launch of their own next to the one-slice form.
-bool launch_g256_dw(hipStream_t s, GemmParams p, bool fold_colsum = true) {
-    const int n_cu = g256_cus();
-    p.tiles_m = (p.M + 255) / 256; p.tiles_n = (p.N + 255) / 256;
-    const int tiles = p.tiles_m * p.tiles_n, nk_all = (p.K + 63) >> 6;
-    if (tiles >= n_cu || n_cu / tiles < 2 || i2t_det()) {      // (deterministic mode: one K slice, no atomics)
-        // (more than half a round of tiles but less than one -- a Qwen2-1.5B down_proj dW, 1536 x 8960 = 210 tiles -- cannot be split:
-        // one tile per workgroup on the persistent kernel still beats the 128^2 fallback it used to take, 711 TF)
-        if (g256_epilogue_class(p) != 5) return false;
-        p.g2_splits = 1; p.g2_nk = (nk_all + 1) & ~1;
-        if (p.colsum_out) launch_colsum(s, p.A, p.lda, p.K, p.M, p.colsum_out, p.alpha_sumsq);
-        hipLaunchKernelGGL((gemm256_kernel<true, true, 5>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, s, p);
-        return true;
-    }
-    int splits = n_cu / tiles;
-    if (const char* e = getenv("I2T_DW_SPLITS")) splits = atoi(e);      // experiments
-    int per = ((nk_all + splits - 1) / splits + 1) & ~1;          // even number of K-tiles per slice
-    if (per < 8) per = 8;
-    splits = (nk_all + per - 1) / per;
-    if (splits < 2) return false;
-    p.g2_splits = splits; p.g2_nk = per;
-    const int items = tiles * splits;
-    if (p.colsum_out && !fold_colsum) {
-        launch_colsum(s, p.A, p.lda, p.K, p.M, p.colsum_out, p.alpha_sumsq);
-        p.colsum_out = nullptr;
-    }
-    if (p.colsum_out) hipLaunchKernelGGL((gemm256_kernel<true, true, 13>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<true, true, 6>), dim3(items < n_cu ? items : n_cu), dim3(512), 0, s, p);
-    return true;
+// One K chunk of a dW GEMM as gemm_route.h::dw_plan laid it out; p.colsum_out reaches the kernel only where the column sum is folded in.
+void launch_g256_dw(hipStream_t s, GemmParams p, const DwPlan& plan) {
+    if (plan.colsum == Colsum::Before) launch_colsum(s, p.A, p.lda, p.K, p.M, p.colsum_out, p.alpha_sumsq);
+    if (plan.colsum != Colsum::Folded) p.colsum_out = nullptr;
+    const int tm = rows256(p.M), gn = p.g2_gn;
+    if (plan.cls == 5) launch_persistent<true, true, 5>(s, p, tm, 1, plan.per, gn);
+    else if (plan.cls == 13) launch_persistent<true, true, 13>(s, p, tm, plan.splits, plan.per, gn);
+    else launch_persistent<true, true, 6>(s, p, tm, plan.splits, plan.per, gn);
 }
 
 // out[n] (+)= sum_m X[m][n]: 16-byte loads (8 columns per lane, 512 columns per wave-row), the 4 waves of a
@@ -2500,10 +2494,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p, int sp
     epilogue_quad(p, a, m, n4, vec_ok);
 }
 
-template <int MT>
-void launch_skinny(hipStream_t s, const GemmParams& p, int ksplit) {
-    dim3 grid((p.N + 15) / 16, ksplit);
-    hipLaunchKernelGGL(gemm_skinny_kernel<MT>, grid, dim3(256), 0, s, p);
+void launch_skinny(hipStream_t s, const GemmParams& p, int mt, int ksplit) {
+    const dim3 grid((p.N + 15) / 16, ksplit);
+    static_for<4>([&](auto i) {
+        constexpr int MT = decltype(i)::value + 1;
+        if (mt == MT) hipLaunchKernelGGL(gemm_skinny_kernel<MT>, grid, dim3(256), 0, s, p);
+    });
+}
+
+// gemm_bf16_kernel<a_kmajor, b_kmajor, splits > 1>: a workgroup per 128^2 tile and K slice
+void launch_g128(hipStream_t s, const GemmParams& p, bool a_kmajor, bool b_kmajor, int splits) {
+    const dim3 grid(p.tiles_m * p.tiles_n, splits), block(256);
+    const int which = (a_kmajor ? 4 : 0) | (b_kmajor ? 2 : 0) | (splits > 1 ? 1 : 0);
+    static_for<8>([&](auto i) {
+        constexpr int I = decltype(i)::value;
+        if (which == I) hipLaunchKernelGGL((gemm_bf16_kernel<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0>), grid, block, 0, s, p);
+    });
 }
 
 }  // namespace
@@ -2539,6 +2545,7 @@ extern "C" int i2t_gemm_dw_colsum_bf16(void* stream, const void* A, int lda, con
                           0u, 0u, 1.0f, alpha_sumsq, colsum_out);
 }
 
+// Validate, fill GemmParams, ask gemm_route.h::gemm_route which kernel the call reaches, launch it.
 // colsum_out (i2t_gemm_dw_colsum_bf16 only: both operands k-major, accumulate, plain epilogue): the A panel's row sums, folded into the
 // split-K dW kernel where the call takes it, a colsum_kernel launch ahead of every other route.
 static int gemm_bf16_impl(void* stream, const void* A, int lda, int a_kmajor, const void* B, int ldb,
@@ -2559,7 +2566,8 @@ static int gemm_bf16_impl(void* stream, const void* A, int lda, int a_kmajor, co
     I2T_REQUIRE((act != I2T_ACT_DGELU && act != I2T_ACT_DGELU_ERF && act != I2T_ACT_MUL_AUX) || aux_in, "i2t_gemm_bf16: DGELU / MUL_AUX need aux_in");
     I2T_REQUIRE(act >= I2T_ACT_NONE && act <= I2T_ACT_MUL_AUX, "i2t_gemm_bf16: unknown act %d", act);
     I2T_REQUIRE(((uintptr_t)C & (c_is_f32 ? 15 : 7)) == 0, "i2t_gemm_bf16: C misaligned");
-    GemmParams p;
+    const GemmKnobs knobs = gemm_knobs();
+    GemmParams p{};
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.alpha = alpha; p.alpha_sumsq = alpha_sumsq; p.bias = bias; p.act = act;
@@ -2567,199 +2575,94 @@ static int gemm_bf16_impl(void* stream, const void* A, int lda, int a_kmajor, co
     p.aux_out = (bf16_t*)aux_out; p.ld_aux_out = ld_aux_out;
     p.residual = residual; p.ldr = ldr; p.c_is_f32 = c_is_f32; p.accumulate = accumulate;
     p.drop_mode = drop_mode; p.drop_key = drop_key; p.drop_thr = drop_thr; p.drop_scale = drop_scale;
-    p.g2_splits = 1; p.g2_nk = 0; p.ws = nullptr;
-    { static const char* e = getenv("I2T_G256_GN"); static const int gn = e ? atoi(e) : 8; p.g2_gn = gn > 0 ? gn : 8; }
-    {
-        static const char* e = getenv("I2T_G256_STAGGER");                   // "units[,groups]"
-        static const int su = e ? atoi(e) : 0;
-        static const int sg = (e && strchr(e, ',')) ? atoi(strchr(e, ',') + 1) : 2;
-        p.g2_stagger = su; p.g2_stagger_groups = sg > 1 ? sg : 2;
-        static const char* d = getenv("I2T_G256_DBG");
-        static const int dbg = d ? atoi(d) : 0;
-        p.g2_dbg = dbg;
-    }
+    p.g2_splits = 1; p.g2_gn = knobs.gn;
+    p.g2_stagger = knobs.stagger; p.g2_stagger_groups = knobs.stagger_groups; p.g2_dbg = knobs.g256_dbg;
     I2T_REQUIRE(drop_mode == 0 || (drop_mode == 1 && (long)M * N < (1L << 32)) || (drop_mode == 2 && N % 12 == 0),
                 "i2t_gemm_bf16: dropout mode %d unsupported for M=%d N=%d", drop_mode, M, N);
     p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
+
+    GemmCall c{};
+    c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldb = ldb; c.ldc = ldc;
+    c.a_kmajor = a_kmajor != 0; c.b_kmajor = b_kmajor != 0;
+    c.c_is_f32 = c_is_f32; c.accumulate = accumulate; c.act = act; c.drop_mode = drop_mode;
+    c.bias = bias != nullptr; c.aux_in = aux_in != nullptr; c.aux_out = aux_out != nullptr; c.residual = residual != nullptr;
+    c.ld_aux_in = ld_aux_in; c.ld_aux_out = ld_aux_out; c.ldr = ldr;
+    c.alpha_one = alpha == 1.0f; c.alpha_sumsq = alpha_sumsq != nullptr; c.colsum_out = colsum_out != nullptr;
+    c.c_aligned16 = ALIGNED16(C); c.aux_out_aligned16 = ALIGNED16(aux_out); c.residual_is_c = residual == (const float*)C;
+    const GemmRoute r = gemm_route(c, knobs, g256_cus(), i2t_det());
+
     hipStream_t s = (hipStream_t)stream;
-    if (M <= 64 && !a_kmajor && !b_kmajor && !aux_out && act <= I2T_ACT_GELU && !accumulate && !drop_mode) {
-        // decode-step shape: weight-streaming kernel.  In-place residual form (C is fp32 and IS the residual) may also
-        // split K across workgroups when there are too few column tiles to pull HBM bandwidth from every CU.
-        int ksplit = 1;
-        const int ntiles = (N + 15) / 16;
-        // NOTE: the cross-workgroup split is OFF by default: float atomics make the sum order, hence the last bits of
-        // the logits, vary from run to run, and greedy decoding must be token-exact reproducible.  The N = 768
-        // projections then run on 48 workgroups; they are launch-latency-sized anyway (1.2 - 4.7 MB of weights).
-        if (getenv("I2T_SKINNY_KSPLIT") && c_is_f32 && residual == (const float*)C && ldr == ldc && act == I2T_ACT_NONE && !accumulate)
-            while (ntiles * ksplit < 256 && (K / 64) / (ksplit * 2) >= 2 && ksplit < 16) ksplit *= 2;
-        const int mt = (M + 15) / 16;
-        if (mt == 1) launch_skinny<1>(s, p, ksplit);
-        else if (mt == 2) launch_skinny<2>(s, p, ksplit);
-        else if (mt == 3) launch_skinny<3>(s, p, ksplit);
-        else launch_skinny<4>(s, p, ksplit);
+    if (r.colsum == Colsum::Before) launch_colsum(s, p.A, lda, K, M, colsum_out, alpha_sumsq);
+    switch (r.kind) {
+    case RouteKind::Skinny:
+        launch_skinny(s, p, r.mt, r.ksplit);
         I2T_CHECK_LAUNCH("i2t_gemm_bf16(skinny)");
-        return I2T_OK;
-    }
-    static const char* sel = getenv("I2T_GEMM");
-    static const bool no_g256 = sel && !strcmp(sel, "v1");
-    // I2T_FOLD_COLSUM=0 (read per call: a test flips it): the bias gradient by its own colsum_kernel launch, as before the fold
-    const char* fold_env = getenv("I2T_FOLD_COLSUM");
-    const bool fold_colsum = !(fold_env && fold_env[0] == '0');
-    if (!no_g256 && a_kmajor && b_kmajor && accumulate && c_is_f32 && !bias && act == I2T_ACT_NONE && !aux_out && !residual &&
-        !drop_mode && M >= 256 && N >= 256 && (ldc & 3) == 0 && (N & 3) == 0) {
-        // The k-major panels are addressed through 32-bit buffer offsets: (K + 512) rows x ld x 2 bytes must stay below 4 GiB.
-        // A longer reduction (B = 2048: the tied lm_head's dW reads 74 k rows of 50 264 logits, the projector's 401 k rows of
-        // 8192) runs as consecutive K chunks that accumulate into the same C -- it used to fall back to the 128^2 kernel
-        // (731 / 789 TF instead of ~1.1 / 1.3 PF).
-        const size_t ld_max = (size_t)(lda > ldb ? lda : ldb);
-        const long k_fit = (long)((1ull << 32) / (2 * ld_max)) - 512;
-        if (k_fit >= 1024) {
-            const long kc = (K <= k_fit) ? K : (k_fit / 128) * 128;
-            bool ok = true;
-            for (long k0 = 0; k0 < K && ok; k0 += kc) {
-                GemmParams q = p;
-                q.A = p.A + (size_t)k0 * lda;
-                q.B = p.B + (size_t)k0 * ldb;
-                q.K = (int)((K - k0 < kc) ? (K - k0) : kc);
-                q.colsum_out = colsum_out;
-                ok = launch_g256_dw(s, q, fold_colsum);
-                if (!ok && k0 > 0) { i2t_set_error("i2t_gemm_bf16: K chunk %ld of a chunked dW GEMM has no large-tile form", k0); return I2T_EINVAL; }
-            }
-            if (ok) {
-                I2T_CHECK_LAUNCH("i2t_gemm_bf16(256 dW)");
-                return I2T_OK;
-            }
+        break;
+    case RouteKind::DW:
+        for (int i = 0; i < r.chunks; ++i) {
+            const long k0 = i * r.kc;
+            GemmParams q = p;
+            q.A = p.A + (size_t)k0 * lda;
+            q.B = p.B + (size_t)k0 * ldb;
+            q.K = (int)((K - k0 < r.kc) ? (K - k0) : r.kc);
+            q.colsum_out = colsum_out;
+            launch_g256_dw(s, q, q.K == r.kc ? r.full : r.tail);
         }
-    }
-    if (colsum_out) launch_colsum(s, p.A, lda, K, M, colsum_out, alpha_sumsq);      // (no large-tile split-K form for this call: its own launch)
-    dim3 grid(p.tiles_m * p.tiles_n), block(256);
-    // split-K for accumulate-into-fp32 problems whose tile grid cannot fill the 256 CUs (the dW = dY^T.X GEMMs: small
-    // M x N, very long K): enough slices to reach ~2 workgroups per CU, each slice at least 4 K-steps long
-    int splits = 1;
-    const int plain_epilogue = !bias && act == I2T_ACT_NONE && !aux_out && !residual && !drop_mode;
-    if (accumulate && c_is_f32 && plain_epilogue) {
-        const int tiles = p.tiles_m * p.tiles_n, nk_all = (K + BK - 1) / BK;
-        while (tiles * splits < 384 && nk_all / (splits * 2) >= 4 && splits < 64) splits *= 2;
-        if (i2t_det()) splits = 1;            // deterministic mode: one K slice per tile, plain read-add-write epilogue
-    }
-    // large-tile kernel for the non-split problems with enough 256^2 tiles to occupy the chip (I2T_GEMM=v1 keeps the 128^2 one)
-    // K % 128 == 0: K-tiles run in pairs and the DMA stream chains output tiles; k-major panels must fit a 32-bit byte offset
-    // K % 128 == 0 (K-tiles run in pairs), or any K when B is k-major: the range check then returns B rows >= K as zeros, so
-    // whatever finite values a row-major A delivers past K (its zero pads, then the head of the next row) contribute nothing
-    const bool g256_ok = (K % 128 == 0 || b_kmajor) && (!a_kmajor || (size_t)(K + 512) * lda * 2 < (1ull << 32)) &&
-                         (!b_kmajor || (size_t)(K + 512) * ldb * 2 < (1ull << 32));
-    // I2T_G256_MIN_TILES (read per call so that a test can flip it): tile count from which the large-tile kernel takes over
-    const char* mt_env = getenv("I2T_G256_MIN_TILES");
-    const long min_tiles = mt_env ? atol(mt_env) : 40;
-    {   // gemm3 (256 x 128 tiles, the previous tile's epilogue inside the K loop): bit-equal to the 256^2 kernel; measured on MI355X
-        // (tools/bench_gemm3.py) +8.5 % at K = 512 (class 1: 865 vs 797 TF), a tie at K = 768 (993 vs 979, 963 vs 953, 1026 vs 1058)
-        // and -14 % at K = 2048 (its K loop moves 1.33x the LDS bytes per MFMA and is LDS-bound); the GELU class LOSES (458 vs 704 TF:
-        // a 64-value GELU step per wave outlasts the MFMA block it is meant to hide behind).  Default: class 1 with K <= 512 only ...
-        // I2T_GEMM3 = 0 never | 1 always, epilogue after the K loop | 2 always, overlapped | unset: the default rule.
-        const char* e3 = getenv("I2T_GEMM3");          // (read per call: a test flips it)
-        // ... and only without the per-row dropout multipliers and up to ~4e5 rows: at the benchmark's M = 798 720 (B = 3072) the
-        // 256^2 kernel is the faster one (1363 vs 1654 us with dropout, 1417 vs 1528 without), and with dropout gemm3 does not win
-        // at M = 266 240 either (515 vs 513 us)
-        // Round 3 re-measurement (tools/ab_gemm_classes.py, M = 99 840, K = 512, class 1): since the 256^2 kernel's stores became
-        // non-temporal it is the faster one here too -- 843 / 850 TF against gemm3's 775 / 798 (N = 2048 / 1536) -- so the default
-        // rule is OFF; gemm3 stays reachable through I2T_GEMM3 for the record of the overlap experiment.
-        const int g3 = e3 ? atoi(e3) : 0;
-        const int cls3 = g256_epilogue_class(p);
-        if (g3 && splits == 1 && !a_kmajor && !b_kmajor && K % 64 == 0 && alpha == 1.0f && !alpha_sumsq && (N & 7) == 0 && (ldc & 7) == 0 && ALIGNED16(C) &&
-            ((cls3 == 1 && K >= 5 * 64) || (cls3 == 2 && K >= 8 * 64 && (!aux_out || ((ld_aux_out & 7) == 0 && ALIGNED16(aux_out))))) &&
-            (long)((M + 255) / 256) * ((N + 127) / 128) >= 2 * min_tiles) {
-            launch_g3(s, p, g3 == 2);
-            I2T_CHECK_LAUNCH("i2t_gemm_bf16(g3)");
-            return I2T_OK;
-        }
-    }
-    // N <= 128 (the LoRA adapters' rank-padded products u = x A^T, du = dY (s B)): a 256-column tile is half empty and M / 256 row tiles
-    // leave most CUs idle -- the 128^2 kernel runs twice the workgroups on full tiles (I2T_G256_NARROW=1: the old routing, for A/B)
-    static const bool narrow_256 = getenv("I2T_G256_NARROW") && getenv("I2T_G256_NARROW")[0] == '1';
-    if (splits == 1 && !no_g256 && g256_ok && !a_kmajor && (N > 128 || narrow_256) && (long)((M + 255) / 256) * ((N + 255) / 256) >= min_tiles) {
-        if (b_kmajor) launch_g256<true>(s, p);
-        else launch_g256<false>(s, p);
+        if (r.chunk_error) { i2t_set_error("i2t_gemm_bf16: K chunk %ld of a chunked dW GEMM has no large-tile form", r.chunks * r.kc); return I2T_EINVAL; }
+        I2T_CHECK_LAUNCH("i2t_gemm_bf16(256 dW)");
+        break;
+    case RouteKind::Gemm3:
+        launch_g3(s, p, r.cls, r.overlap, knobs.g3_dbg);
+        I2T_CHECK_LAUNCH("i2t_gemm_bf16(g3)");
+        break;
+    case RouteKind::G256:
+        if (knobs.log)
+            fprintf(stderr, "[g256] class %d bk=%d M=%d N=%d K=%d f32=%d bias=%d act=%d auxo=%d auxi=%d res=%d acc=%d drop=%d ldc=%d\n",
+                    g256_epilogue_class(c), (int)c.b_kmajor, p.M, p.N, p.K, p.c_is_f32, p.bias != nullptr, p.act, p.aux_out != nullptr,
+                    p.aux_in != nullptr, p.residual != nullptr, p.accumulate, p.drop_mode, p.ldc);
+        if (b_kmajor) launch_g256<true>(s, p, r.cls);
+        else launch_g256<false>(s, p, r.cls);
         I2T_CHECK_LAUNCH("i2t_gemm_bf16(256)");
-        return I2T_OK;
+        break;
+    case RouteKind::G128:
+        launch_g128(s, p, c.a_kmajor, c.b_kmajor, r.splits);
+        I2T_CHECK_LAUNCH("i2t_gemm_bf16");
+        break;
     }
-    if (splits > 1) {
-        grid.y = splits;
-        if (!a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<false, false, true>), grid, block, 0, s, p);
-        else if (!a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<false, true, true>), grid, block, 0, s, p);
-        else if (a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<true, false, true>), grid, block, 0, s, p);
-    } else {
-        if (!a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<false, false, false>), grid, block, 0, s, p);
-        else if (!a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<false, true, false>), grid, block, 0, s, p);
-        else if (a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_bf16_kernel<true, true, false>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<true, false, false>), grid, block, 0, s, p);
-    }
-    I2T_CHECK_LAUNCH("i2t_gemm_bf16");
+    return I2T_OK;
+}
+
+// i2t_gemm_bf16_top2 (EPI 12), i2t_gemm_bf16_top2_lse (15: `se` = the [M][nseg] segment sums of exp's) and i2t_gemm_bf16_lse (14: alpha =
+// the caller's scale): the 256^2 kernel leaves per-segment statistics of the logits in `out` instead of the logits.
+template <int EPI>
+static int gemm_seg_stats(const char* fn, void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float alpha, float* out,
+                          float* se, int nseg) {
+    I2T_REQUIRE(A && B && out && (EPI != 15 || se) && M > 0 && N > 0 && K > 0 && nseg == (N + 63) / 64, "%s: bad args (nseg must be ceil(N / 64))", fn);
+    I2T_REQUIRE(K % 128 == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && lda >= K && ldb >= K && ALIGNED16(A) && ALIGNED16(B) && ALIGNED16(out) &&
+                    (((uintptr_t)se) & 3) == 0,
+                "%s: K=%d must be a multiple of 128, operands 16-byte aligned with leading dimensions %% 8 == 0", fn, K);
+    I2T_REQUIRE((size_t)256 * lda * 2 < (1ull << 32) && (size_t)256 * ldb * 2 < (1ull << 32), "%s: rows too long", fn);
+    I2T_REQUIRE(alpha == alpha && alpha - alpha == 0.f, "%s: scale must be finite", fn);
+    GemmParams p{};
+    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = out; p.ws = se;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = nseg;
+    p.alpha = alpha; p.c_is_f32 = 1;
+    launch_persistent<false, false, EPI>((hipStream_t)stream, p, rows256(M), 1, even_ktiles(K), gemm_knobs().gn);
+    I2T_CHECK_LAUNCH(fn);
     return I2T_OK;
 }
 
 extern "C" int i2t_gemm_bf16_top2(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float* top2, int nseg) {
-    I2T_REQUIRE(A && B && top2 && M > 0 && N > 0 && K > 0 && nseg == (N + 63) / 64, "i2t_gemm_bf16_top2: bad args (nseg must be ceil(N / 64))");
-    I2T_REQUIRE(K % 128 == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && lda >= K && ldb >= K && ALIGNED16(A) && ALIGNED16(B) && ALIGNED16(top2),
-                "i2t_gemm_bf16_top2: K=%d must be a multiple of 128, operands 16-byte aligned with leading dimensions %% 8 == 0", K);
-    I2T_REQUIRE((size_t)256 * lda * 2 < (1ull << 32) && (size_t)256 * ldb * 2 < (1ull << 32), "i2t_gemm_bf16_top2: rows too long");
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = top2;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = nseg;
-    p.alpha = 1.0f; p.c_is_f32 = 1;
-    { static const char* e = getenv("I2T_G256_GN"); static const int gn = e ? atoi(e) : 8; p.g2_gn = gn > 0 ? gn : 8; }
-    const int n_cu = g256_cus();
-    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = (((K + 63) >> 6) + 1) & ~1;
-    const int tiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm256_kernel<false, false, 12>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
-    I2T_CHECK_LAUNCH("i2t_gemm_bf16_top2");
-    return I2T_OK;
+    return gemm_seg_stats<12>("i2t_gemm_bf16_top2", stream, A, lda, B, ldb, M, N, K, 1.0f, top2, nullptr, nseg);
 }
 
 extern "C" int i2t_gemm_bf16_top2_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float* top2, float* se,
                                       int nseg) {
-    I2T_REQUIRE(A && B && top2 && se && M > 0 && N > 0 && K > 0 && nseg == (N + 63) / 64,
-                "i2t_gemm_bf16_top2_lse: bad args (nseg must be ceil(N / 64))");
-    I2T_REQUIRE(K % 128 == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && lda >= K && ldb >= K && ALIGNED16(A) && ALIGNED16(B) && ALIGNED16(top2) &&
-                    (((uintptr_t)se) & 3) == 0,
-                "i2t_gemm_bf16_top2_lse: K=%d must be a multiple of 128, operands 16-byte aligned with leading dimensions %% 8 == 0", K);
-    I2T_REQUIRE((size_t)256 * lda * 2 < (1ull << 32) && (size_t)256 * ldb * 2 < (1ull << 32), "i2t_gemm_bf16_top2_lse: rows too long");
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = top2; p.ws = se;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = nseg;
-    p.alpha = 1.0f; p.c_is_f32 = 1;
-    { static const char* e = getenv("I2T_G256_GN"); static const int gn = e ? atoi(e) : 8; p.g2_gn = gn > 0 ? gn : 8; }
-    const int n_cu = g256_cus();
-    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = (((K + 63) >> 6) + 1) & ~1;
-    const int tiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm256_kernel<false, false, 15>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
-    I2T_CHECK_LAUNCH("i2t_gemm_bf16_top2_lse");
-    return I2T_OK;
+    return gemm_seg_stats<15>("i2t_gemm_bf16_top2_lse", stream, A, lda, B, ldb, M, N, K, 1.0f, top2, se, nseg);
 }
 
 extern "C" int i2t_gemm_bf16_lse(void* stream, const void* A, int lda, const void* B, int ldb, int M, int N, int K, float scale, float* stats, int nseg) {
-    I2T_REQUIRE(A && B && stats && M > 0 && N > 0 && K > 0 && nseg == (N + 63) / 64, "i2t_gemm_bf16_lse: bad args (nseg must be ceil(N / 64))");
-    I2T_REQUIRE(K % 128 == 0 && (lda & 7) == 0 && (ldb & 7) == 0 && lda >= K && ldb >= K && ALIGNED16(A) && ALIGNED16(B) && ALIGNED16(stats),
-                "i2t_gemm_bf16_lse: K=%d must be a multiple of 128, operands 16-byte aligned with leading dimensions %% 8 == 0", K);
-    I2T_REQUIRE((size_t)256 * lda * 2 < (1ull << 32) && (size_t)256 * ldb * 2 < (1ull << 32), "i2t_gemm_bf16_lse: rows too long");
-    I2T_REQUIRE(scale == scale && scale - scale == 0.f, "i2t_gemm_bf16_lse: scale must be finite");
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = stats;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = nseg;
-    p.alpha = scale; p.c_is_f32 = 1;
-    { static const char* e = getenv("I2T_G256_GN"); static const int gn = e ? atoi(e) : 8; p.g2_gn = gn > 0 ? gn : 8; }
-    const int n_cu = g256_cus();
-    p.tiles_m = (M + 255) / 256; p.tiles_n = (N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = (((K + 63) >> 6) + 1) & ~1;
-    const int tiles = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm256_kernel<false, false, 14>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
-    I2T_CHECK_LAUNCH("i2t_gemm_bf16_lse");
-    return I2T_OK;
+    return gemm_seg_stats<14>("i2t_gemm_bf16_lse", stream, A, lda, B, ldb, M, N, K, scale, stats, nullptr, nseg);
 }
 
 extern "C" int i2t_gemm_bf16_ws(void* stream, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int c_is_f32, int M,
@@ -2783,7 +2686,7 @@ extern "C" int i2t_gemm_bf16_ws(void* stream, const void* A, int lda, const void
     I2T_REQUIRE((lda & 7) == 0 && (ldb & 7) == 0 && ALIGNED16(A) && ALIGNED16(B) && lda >= ((K + 7) & ~7) && ldb >= ((K + 7) & ~7) && ldc >= N,
                 "i2t_gemm_bf16_ws: operand layout (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
     I2T_REQUIRE(((uintptr_t)C & (c_is_f32 ? 15 : 7)) == 0 && ALIGNED16(workspace), "i2t_gemm_bf16_ws: C / workspace misaligned");
-    GemmParams p = {};
+    GemmParams p{};
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.alpha = 1.0f; p.bias = bias; p.act = act; p.residual = residual; p.ldr = ldr; p.c_is_f32 = c_is_f32;
@@ -2813,8 +2716,7 @@ extern "C" int i2t_xattn_kv_fused(void* stream, const void* mem, int ld_mem, con
     I2T_REQUIRE(!cu_q || total_q > 0, "i2t_xattn_kv_fused: packed queries need total_q");
     I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * S < 4294967296.0, "i2t_xattn_kv_fused: dropout index overflows 32 bits");
     I2T_REQUIRE((double)(d + 128) * ld_w * 2 < 4294967296.0 && (double)B * S * ld_mem * 2 < 1.8e19, "i2t_xattn_kv_fused: operand too large");
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
+    GemmParams p{};
     p.A = (const bf16_t*)w_kv; p.lda = ld_w;                  // "A" = the weight rows: [K_h | V_h] per wave tile
     p.B = (const bf16_t*)mem; p.ldb = ld_mem;                 // "B" = 256 memory rows = 4 images per workgroup tile
     p.C = kv; p.ldc = ld_kv;
@@ -2824,12 +2726,9 @@ extern "C" int i2t_xattn_kv_fused(void* stream, const void* mem, int ld_mem, con
     p.xq = (const bf16_t*)q; p.xq_bs = q_bs; p.xq_rs = q_rs; p.xcu = cu_q;
     p.xo = (bf16_t*)o; p.xo_bs = o_bs; p.xo_rs = o_rs; p.xlse = lse;
     p.x_total_q = total_q; p.x_TqMax = Tq; p.x_H = H; p.x_d = d; p.x_B = B; p.x_S = S;
-    p.g2_gn = 8;
-    p.tiles_m = H / 2; p.tiles_n = (p.N + 255) / 256;
-    p.g2_splits = 1; p.g2_nk = (((p.K + 63) >> 6) + 1) & ~1;
-    const int n_cu = g256_cus(), tiles = p.tiles_m * p.tiles_n;
-    if (S == 64) hipLaunchKernelGGL((gemm256_kernel<false, false, 8>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((gemm256_kernel<false, false, 16>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, (hipStream_t)stream, p);      // 64 / S images per wave
+    // a row tile = one pair of heads' [K_h | V_h] weight rows: H / 2 of them, not ceil(M / 256)
+    if (S == 64) launch_persistent<false, false, 8>((hipStream_t)stream, p, H / 2, 1, even_ktiles(p.K), 8);
+    else launch_persistent<false, false, 16>((hipStream_t)stream, p, H / 2, 1, even_ktiles(p.K), 8);      // 64 / S images per wave
     I2T_CHECK_LAUNCH("i2t_xattn_kv_fused");
     return I2T_OK;
 }

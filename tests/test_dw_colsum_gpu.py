@@ -7,7 +7,7 @@ Tolerance (the per-element rule of tests/test_row_kernels_gpu.py, fp32 outputs):
 ``terms``: the value the output held before the call and every addend of the sum (products a b f for C, a f for the column sums).
 ``k``: the addends on the longest fp32 path -- the K steps (64 rows each: the MFMA adds a step's exact products in fp32) of one
 workgroup's K slice, then one float atomic per slice onto the value already there: k = steps per slice + slices, both restated from the
-launch rule of csrc/gemm.hip::launch_g256_dw.  Outputs start from a non-zero pattern (the calls accumulate); the floats behind
+launch rule of csrc/gemm_route.h::dw_plan.  Outputs start from a non-zero pattern (the calls accumulate); the floats behind
 colsum[M], the pad columns of C and the pad columns of dY hold sentinels / junk: what must not be written is compared bit for bit."""
 import os
 from types import SimpleNamespace
@@ -49,7 +49,7 @@ def check(name, got, ref, tol):
 
 
 def path_len(M, N, K):
-    """(K steps of one slice) + (slices): launch_g256_dw's split of ceil(K / 64) K-tiles over the CUs the output tiles leave idle"""
+    """(K steps of one slice) + (slices): dw_plan's split of ceil(K / 64) K-tiles over the CUs the output tiles leave idle"""
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
     tiles, nk_all = ((M + 255) // 256) * ((N + 255) // 256), (K + 63) // 64
     per = max(8, ((nk_all + n_cu // tiles - 1) // (n_cu // tiles) + 1) & ~1)
