@@ -510,6 +510,34 @@ __global__ void advance_kernel(int* counters, int n, int delta) {
     if ((int)threadIdx.x < n) counters[threadIdx.x] += delta;
 }
 
+// Prompt prefill: the K and V rows a forward pass saved for m tokens of B images go to cache slots slot0 .. slot0 + m - 1 of the N
+// cache rows b * N .. b * N + N - 1 of every image.  One thread per 16-byte chunk of a source row's K (and the chunk of its V at the
+// same column): chunk index fastest, so a wave reads 1 KB runs of a source row, and its stores go out as groups of hd / 8 lanes
+// that each fill one head's hd * 2 bytes of a cache slot -- 8 lanes x 16 B = one whole 128-byte line in the head-major layout
+// [R][H][clen][64], where (head, slot) rows are exactly one line; in the row-major layout [R][clen][w] the wave's stores are one
+// contiguous run of the slot's row.  The two chunks are loaded once and stored N times: nothing else depends on N.
+// Element (row r, head h, slot s, column c) of a cache is at r * cache_bs + h * cache_hs + s * cache_rs + c, as
+// decode_attention_kernel (kb / vb) and gq_decode_attention address it.
+__global__ __launch_bounds__(256) void kv_prefill_kernel(const bf16_t* __restrict__ src, int src_ld, int k_off, int v_off, int src_T,
+                                                         int src_t0, int m, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, long cache_bs,
+                                                         int cache_rs, long cache_hs, int hd, int w8, int slot0, long total, int N) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int ch = (int)(idx % w8);                          // 16-byte chunk of the w = 8 * w8 K (or V) columns
+    const long bt = idx / w8;
+    const int t = (int)(bt % m);
+    const long b = bt / m;
+    const int col = ch * 8, h = col / hd, c = col - h * hd;
+    const bf16_t* s = src + (size_t)(b * src_T + src_t0 + t) * src_ld + col;
+    const u32x4 kk = *reinterpret_cast<const u32x4*>(s + k_off);
+    const u32x4 vv = *reinterpret_cast<const u32x4*>(s + v_off);
+    const size_t at = (size_t)(b * N) * cache_bs + (size_t)h * cache_hs + (size_t)(slot0 + t) * cache_rs + c;
+    for (int n = 0; n < N; ++n) {
+        *reinterpret_cast<u32x4*>(kc + at + (size_t)n * cache_bs) = kk;
+        *reinterpret_cast<u32x4*>(vc + at + (size_t)n * cache_bs) = vv;
+    }
+}
+
 }  // namespace
 
 extern "C" int i2t_embed_step(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* wte,
@@ -529,6 +557,36 @@ extern "C" int i2t_kv_append(void* stream, const void* qkv, int qkv_rs, void* kc
     hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)qkv, qkv_rs,
                        (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, pos_ptr, d);
     I2T_CHECK_LAUNCH("i2t_kv_append");
+    return I2T_OK;
+}
+
+extern "C" int i2t_kv_prefill(void* stream, const void* src, int src_ld, int k_off, int v_off, int src_T, int src_t0, int m, void* kcache,
+                              void* vcache, long cache_bs, int cache_rs, long cache_hs, int hd, int w, int slot0, int B, int N) {
+    I2T_REQUIRE(src && kcache && vcache, "i2t_kv_prefill: null pointer");
+    I2T_REQUIRE(w > 0 && w % 8 == 0, "i2t_kv_prefill: w = %d: the K / V width must be a positive multiple of 8", w);
+    I2T_REQUIRE(hd > 0 && hd % 8 == 0 && w % hd == 0, "i2t_kv_prefill: hd = %d: the head width must be a multiple of 8 that divides w = %d", hd, w);
+    I2T_REQUIRE(src_ld > 0 && src_ld % 8 == 0, "i2t_kv_prefill: src_ld = %d: source rows must be a multiple of 8 elements apart", src_ld);
+    I2T_REQUIRE(k_off >= 0 && v_off >= 0 && k_off % 8 == 0 && v_off % 8 == 0 && k_off + w <= src_ld && v_off + w <= src_ld,
+                "i2t_kv_prefill: k_off = %d, v_off = %d: column offsets must be multiples of 8 with w = %d columns inside src_ld = %d", k_off,
+                v_off, w, src_ld);
+    I2T_REQUIRE(ALIGNED16(src) && ALIGNED16(kcache) && ALIGNED16(vcache), "i2t_kv_prefill: misaligned base pointer (16 bytes)");
+    I2T_REQUIRE(cache_bs > 0 && cache_rs > 0 && cache_hs > 0 && cache_bs % 8 == 0 && cache_rs % 8 == 0 && cache_hs % 8 == 0,
+                "i2t_kv_prefill: cache strides (%ld, %d, %ld) must be positive multiples of 8", cache_bs, cache_rs, cache_hs);
+    I2T_REQUIRE(B >= 1 && N >= 1, "i2t_kv_prefill: B = %d images, N = %d rows per image", B, N);
+    I2T_REQUIRE(m >= 1, "i2t_kv_prefill: m = %d: at least one token", m);
+    I2T_REQUIRE(src_t0 >= 0 && (long)src_t0 + m <= src_T, "i2t_kv_prefill: src_t0 + m = %d + %d exceeds src_T = %d", src_t0, m, src_T);
+    const long Hkv = w / hd, end = (long)slot0 + m;
+    // row-major [R][clen][w]: heads are hd apart inside a slot's row; head-major [R][Hkv][clen][hd-wide rows]: slots inside a head's run
+    const bool row_major = cache_hs == hd && cache_rs >= w;
+    const bool fits = row_major ? end * cache_rs <= cache_bs : (cache_rs >= hd && end * cache_rs <= cache_hs && Hkv * cache_hs <= cache_bs);
+    I2T_REQUIRE(slot0 >= 0 && fits, "i2t_kv_prefill: slot0 + m = %d + %d exceeds the slots a cache row holds (strides %ld, %d, %ld)", slot0, m,
+                cache_bs, cache_rs, cache_hs);
+    const int w8 = w / 8;
+    const long total = (long)B * m * w8, blocks = (total + 255) / 256;
+    I2T_REQUIRE(blocks <= 0x7fffffffL, "i2t_kv_prefill: %ld chunks exceed one grid", total);
+    hipLaunchKernelGGL(kv_prefill_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, src_ld, k_off, v_off,
+                       src_T, src_t0, m, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, cache_hs, hd, w8, slot0, total, N);
+    I2T_CHECK_LAUNCH("i2t_kv_prefill");
     return I2T_OK;
 }
 

@@ -34,6 +34,9 @@ ENC_CHUNK = int(os.environ.get('I2T_DECODE_ENC_CHUNK', '4096'))      # images pe
 TOP2_HEAD = os.environ.get('I2T_DECODE_TOP2', '1') not in ('', '0')    # greedy steps: lm_head + argmax through segment maxima (ops.gemm_top2)
 
 
+PREFILL_ROWS = int(os.environ.get('I2T_PREFILL_ROWS', '8192'))       # token rows per forward pass of prompt_prefill='pass' 
+
+
 class Sampling(NamedTuple):
     """How the next token is chosen when it is not the argmax (arguments of the reference's generate, :136-137)."""
     temperature: float = 1.0
@@ -58,6 +61,47 @@ def text_window(block: int, off: int, prefix: int) -> int:
         raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
                          f'no room for text (block {block}, soft-prompt offset {off})')
     return tmax
+
+
+PROMPT_PREFILL_MODES = ('steps', 'pass')
+
+
+def prefill_plan(mode: str, pmin: int, prefix: int, fam, causal: bool):
+    """How ``generate_captions`` fills the cache with the prompt columns every row shares -> (m, (pos, len)): the first m
+    prompt columns go through ONE forward pass, the counters start at (pos, len) -- the cache slot and the id column of the first
+    step -- and pmin - 1 - m prefill replays follow.  'steps': m = 0, the counters (prefix, 1), pmin - 1 replays: every prompt token a
+    decode step.  'pass': m = pmin - 1 and the counters (prefix + m, 1 + m): no prefill replay; pmin = 1 leaves m = 0, which IS
+    'steps'.  ``prefix``: the soft-prompt rows at the head of the cache; ``fam``: the nano-mini family's spec (None: a dense or
+    Llama-family decoder), refused under 'pass'; a non-causal decoder has no cache and nothing to plan: the mode is checked and ignored."""
+    if mode not in PROMPT_PREFILL_MODES:
+        raise ValueError(f'prompt_prefill = {mode!r}: one of {PROMPT_PREFILL_MODES}')
+    if pmin < 1 or prefix < 0:
+        raise ValueError(f'pmin = {pmin}, prefix = {prefix}: every row needs a prompt token, and a prefix cannot be negative')
+    if mode == 'steps' or not causal:
+        return 0, (prefix, 1)
+    if fam is not None:
+        raise NotImplementedError("prompt_prefill='pass' is not available for the nano-mini decoder family: a sparse layer caches the "
+                                  "positions it keeps by slot, not by position, which the one-pass scatter does not map; use 'steps'")
+    m = pmin - 1
+    return m, (prefix + m, 1 + m)
+
+
+def kv_prefill_host(src: np.ndarray, k_off: int, v_off: int, src_T: int, src_t0: int, m: int, kcache: np.ndarray, vcache: np.ndarray,
+                    cache_bs: int, cache_rs: int, cache_hs: int, hd: int, w: int, slot0: int, B: int, N: int):
+    """What i2t_kv_prefill does, on the host (numpy): ``src`` [rows, src_ld] holds K at columns k_off .. k_off + w - 1 and V at v_off ..;
+    token t < m of image b is source row b * src_T + src_t0 + t and goes to slot slot0 + t of cache rows b * N .. b * N + N - 1.
+    ``kcache`` / ``vcache`` are FLAT arrays, element (row, head, slot, column) at row * cache_bs + head * cache_hs + slot * cache_rs +
+    column (head-major [R][H][clen][64]: cache_rs = 64, cache_hs = clen * 64; row-major [R][clen][w]: cache_rs = w, cache_hs = hd).
+    Written in place; nothing else is touched."""
+    assert kcache.ndim == 1 and vcache.ndim == 1 and w % hd == 0 and src_t0 + m <= src_T
+    for b in range(B):
+        for t in range(m):
+            row = src[b * src_T + src_t0 + t]
+            for n in range(N):
+                for h in range(w // hd):
+                    at = (b * N + n) * cache_bs + h * cache_hs + (slot0 + t) * cache_rs
+                    kcache[at:at + hd] = row[k_off + h * hd:k_off + (h + 1) * hd]
+                    vcache[at:at + hd] = row[v_off + h * hd:v_off + (h + 1) * hd]
 
 
 def slot_positions(member: np.ndarray) -> np.ndarray:
@@ -446,10 +490,11 @@ class GreedyDecoder:
                 break
         return replays
 
-    def _prepare_inputs(self, st, images, B: int, W: int = 1):
+    def _prepare_inputs(self, st, images, B: int, W: int = 1, prefill=None):
         """Everything a step reads besides the ids: the encoder output of the B images, the per-layer cross K/V (B rows), the
         soft-prompt rows' K/V at the head of the cache (copied to the W rows b * W .. b * W + W - 1 of every image) and the packed
-        expert weights."""
+        expert weights.  ``prefill`` = (prompt [B, >= m], m >= 1) under prompt_prefill='pass': the first m prompt columns' K/V go into
+        the cache too, from one pass that also covers the soft-prompt rows (_prefill_pass)."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         # encoder + per-layer cross K/V (once per image)
         # (in slices of ENC_CHUNK images -- 4096: +1.4 % captions/s over 1024 -- every image is independent in the encoder, and its activations -- ~20 MB per
@@ -473,7 +518,9 @@ class GreedyDecoder:
                 p = f'{eng.dp}transformer.h.{l}.cross_attn'
                 ops.gemm(mem, self._w(l, 'xattn_c_attn', f'{p}.in_proj_weight', slice(dc.d, 3 * dc.d)), kv.view(B * S, 2 * dc.d), B * S,
                          2 * dc.d, dc.d, bias=a.P(f'{p}.in_proj_bias')[dc.d:])
-        if st.prefix:       # the prompt rows' keys and values (one causal pass over the encoder outputs) open every caption's cache
+        if prefill is not None:
+            self._prefill_pass(st, enc_out, prefill[0], prefill[1], W)
+        elif st.prefix:     # the prompt rows' keys and values (one causal pass over the encoder outputs) open every caption's cache
                             # (every one of its W rows)
             n_p = st.prefix
             if dc.llama is not None:          # row-major cache [B][slot][Hkv hd]; the saved keys already carry their rotation.  Each layer's
@@ -499,6 +546,46 @@ class GreedyDecoder:
                 for part in ('c_fc', 'c_proj'):
                     mv = eng._moe_views(f'{eng.dp}transformer.h.{l}.mlp.{part}', dc.fam.moe)
                     ops.moe_pack_w2(mv.l2w, mv.l2b, mv.W2aug, mv.out_f, dc.fam.moe.E, dc.fam.moe.P)
+
+    def _prefill_pass(self, st, enc_out, prompt, m: int, W: int):
+        """prompt_prefill='pass' (DESIGN.md 4q): prompt columns 0 .. m - 1 of the B images through the decoder's forward as ONE causal
+        sequence per image -- behind the n_p = st.prefix encoder outputs when the decoder is prefixed, the same sequence
+        decode_prefixed runs -- and every layer's K / V rows into cache slots 0 .. n_p + m - 1 of the W rows of each image, one
+        i2t_kv_prefill launch per layer.  The images go through in slices of PREFILL_ROWS token rows.  A Llama-family layer hands its
+        K / V over as it finishes (eng._layer_sink): its saves never coexist."""
+        eng, dc = self.eng, self.eng.dec
+        B, S, n_p = enc_out.shape[0], enc_out.shape[1], st.prefix
+        T = n_p + m
+        ids = prompt[:, :m].contiguous()
+        if dc.llama is not None:            # row-major cache [R][clen][Hkv hd]; packed q | k | v rows, the keys already rotated
+            ls = dc.llama
+            hd, w = ls.hd, ls.Hkv * ls.hd
+            k_off, v_off = ls.H * ls.hd, (ls.H + ls.Hkv) * ls.hd
+            strides = (st.clen * w, w, hd)
+        else:                               # head-major cache [R][H][clen][64]; packed q | k | v rows of width 3 d
+            hd, w = 64, dc.d
+            k_off, v_off = dc.d, 2 * dc.d
+            strides = (st.clen * dc.d, 64, st.clen * 64)
+        per = max(1, PREFILL_ROWS // T)
+        for i in range(0, B, per):
+            c = min(per, B - i)
+
+            def put(l, sv):
+                ops.kv_prefill(sv.qkv, sv.qkv.stride(0), k_off, v_off, T, 0, T, st.kc[l][i * W:], st.vc[l][i * W:], *strides, hd, w, 0, c, W)
+            part = enc_out[i:i + c]
+            mem = eng._mem_bf16(part) if eng.cross_inputs else None
+            if dc.llama is not None:
+                eng._layer_sink = put
+            try:
+                if n_p:
+                    _, _, pctx = eng.decode_prefixed(c, m, part, mem, True, ids[i:i + c])
+                else:
+                    _, _, pctx = eng.decode_segment(c, m, mem, S, True, ids=ids[i:i + c], pos_offset=st.off)
+            finally:
+                eng._layer_sink = None
+            for l in range(dc.L if dc.llama is None else 0):
+                put(l, pctx.saves[l])
+            del pctx
 
     # ------------------------------------------------------------------------------------------------ public
     @torch.no_grad()
@@ -736,6 +823,7 @@ class CaptionDecoder(GreedyDecoder):
     is below the row's prompt length and counts max_new_tokens per row; those steps have graph keys of their own."""
 
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
+    last_prefill_steps = 0              # prefill replays the last call launched: Pmin - 1, or 0 under prompt_prefill='pass'
 
     def _build_captions(self, B: int, N: int, ids_ld: int):
         R = B * N
@@ -783,10 +871,12 @@ class CaptionDecoder(GreedyDecoder):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
-                          use_graph: bool = True, prompt_lengths=None) -> GeneratedCaptions:
+                          use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps') -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
-        None is the case Pmin = Pmax = P, which needs no forcing table."""
+        None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
+        feeds prompt columns 0 .. Pmin - 2 one prefill replay each; 'pass' takes them through one forward pass per IMAGE
+        (_prefill_pass) and starts the counters behind them -- the full steps, their graphs and everything after are the same."""
         eng = self.eng
         dc = eng.dec
         N = int(num_return_sequences)
@@ -800,6 +890,10 @@ class CaptionDecoder(GreedyDecoder):
             pmin = pmax = P
         if not dc.causal:
             raise ValueError('CaptionDecoder needs a causal decoder')
+        m, start = prefill_plan(prompt_prefill, pmin, min(eng.enc.ncls, dc.block) if dc.prefixed else 0, dc.fam, True)
+        n_prefill = pmin - 1 - m
+        if not max_new_tokens:              # nothing to emit: no step reads the cache, so 'pass' fills nothing -- no pass, no replay
+            m = 0
         a = eng.prepare(False)
         R, total = B * N, pmax + max_new_tokens
         pad = (0 if eos is None else eos) if pad is None else pad
@@ -825,11 +919,13 @@ class CaptionDecoder(GreedyDecoder):
             len_rows = (plen_dev.repeat_interleave(N) if N > 1 else plen_dev) + max_new_tokens
             if max_new_tokens == 0:                           # nothing to emit: the prompts, padded
                 ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
-                self.last_replays = 0
+                self.last_replays = self.last_prefill_steps = 0
                 zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
                 return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev)
             forced = (st.rag_prompt, st.rag_plen, max_new_tokens)
-        self._prepare_inputs(st, images, B, N)
+        self._prepare_inputs(st, images, B, N, prefill=(prompt, m) if m else None)
+        # 'pass': the first step is at slot prefix + m, column 1 + m; st.counters_init stays what 'steps' calls on this state start from
+        start = torch.tensor(start, dtype=torch.int32, device=a.device) if m else st.counters_init
         if sampling is not None:
             _draw_seed(st.seed, sampling.seed)
         top2, head = self._greedy_head(st, sampling, lse=True)
@@ -840,14 +936,16 @@ class CaptionDecoder(GreedyDecoder):
         def reset():
             st.ids.zero_()
             st.ids[:, :pmax] = prompt_rows
-            st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
+            st.counters.copy_(start)                            # device-to-device: no host sync in the loop
             st.ctrl.zero_()
             st.finished.zero_()
             # what a row without an EOS ends with: p_b + max_new_tokens
             st.lengths.copy_(len_rows) if ragged else st.lengths.fill_(total)
             st.tok_lp.zero_()
         # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
-        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced), reset, pmin - 1,
+        # ('pass': those columns' K/V are in the cache already, n_prefill = 0)
+        self.last_prefill_steps = n_prefill
+        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced), reset, n_prefill,
                                          pmax - pmin + max_new_tokens, use_graph, poll_every=poll_every if eos is not None else 0)
         lengths = st.lengths.clone()
         L = int(lengths.max().item()) if max_new_tokens else pmax       # the final host sync

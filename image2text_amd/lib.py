@@ -61,6 +61,7 @@ SIGNATURES = {
     'i2t_add_f32': [P, P, P, L],
     'i2t_decode_attention': [P, P, I, P, P, L, I, L, P, I, P, I, I, I, I],
     'i2t_kv_append': [P, P, I, P, P, L, I, P, I, I],
+    'i2t_kv_prefill': [P, P, I, I, I, I, I, I, P, P, L, I, L, I, I, I, I, I],
     'i2t_ngram_ban_argmax': [P, P, I, I, P, I, P, P, I, I, I, P],
     'i2t_gemm_bf16_top2': [P, P, I, P, I, I, I, I, P, I],
     'i2t_top2_ngram_argmax': [P, P, I, P, I, P, I, I, P, I, P, P, I, I, I],
@@ -141,7 +142,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -234,7 +234,8 @@ class VisionEncoderDecoder(nn.Module):
 
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
-                          temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None):
+                          temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
+                          prompt_prefill='steps'):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -260,10 +261,15 @@ class VisionEncoderDecoder(nn.Module):
         to column Pmin + t and is exactly 0.0 at a row's prompt columns and past its end.  The result carries ``prompt_lengths``
         (int32 [B]; None without the argument).  None (the default) is the path above, unchanged.  For a NON-causal decoder this is
         ``generate_by_recompute`` once per distinct length over the rows of that length, then the host rule and ``score``: it exists
-        for completeness, not for speed."""
+        for completeness, not for speed.
+        ``prompt_prefill`` chooses how the prompt columns every row holds, 0 .. Pmin - 2, reach the cache.  'steps'
+        (the default) is one decode step per column over all B * N rows.  'pass' runs them through the decoder's forward as ONE causal
+        sequence per IMAGE and copies the K/V into the N rows of each image; the steps after it are the same launches, but the two modes
+        are not bit-equal (the prompt's K/V come from the forward's GEMM and attention shapes).  The nano-mini family refuses 'pass'
+        (NotImplementedError); a non-causal decoder has no cache and ignores the argument; any other value is a ValueError."""
         import numpy as np
         from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, check_caption_args,
-                                check_ragged_caption_args, generate_by_recompute)
+                                check_ragged_caption_args, generate_by_recompute, prefill_plan)
         N = int(num_return_sequences)
         sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
         B, P = prompt_ids.shape
@@ -273,6 +279,7 @@ class VisionEncoderDecoder(nn.Module):
         else:
             plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
             pmin, pmax = int(plen.min()), int(plen.max())
+        prefill_plan(prompt_prefill, pmin, 0, self._engine.dec.fam, self._engine.dec.causal)       # its refusals, before anything runs
         blk_size = self.decoder.block_size - self.space_for_prompt
         if pmax + max_new_tokens > blk_size:
             raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({blk_size})')
@@ -282,7 +289,7 @@ class VisionEncoderDecoder(nn.Module):
             if self._captioner is None:
                 object.__setattr__(self, '_captioner', CaptionDecoder(self))
             return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
-                                                     prompt_lengths=plen)
+                                                     prompt_lengths=plen, prompt_prefill=prompt_prefill)
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
         prompt_rep = prompt_ids.repeat_interleave(N, dim=0)

@@ -723,6 +723,14 @@ def kv_append(qkv, qkv_rs, kcache, vcache, cache_bs, cache_rs, pos, B, d):
              'i2t_kv_append')
 
 
+def kv_prefill(src, src_ld, k_off, v_off, src_T, src_t0, m, kcache, vcache, cache_bs, cache_rs, cache_hs, hd, w, slot0, B, N):
+    """The K / V rows a forward pass saved for m tokens of B images into slots slot0 .. slot0 + m - 1 of the N cache rows of every image
+    (include/i2t.h::i2t_kv_prefill); cache_rs / cache_hs as decode_attention (head-major) and gq_decode_attention (row-major: w, hd)."""
+    _need_cuda(src, kcache, vcache)
+    _l.check(_lib().i2t_kv_prefill(_stream(), _p(src), src_ld, k_off, v_off, src_T, src_t0, m, _p(kcache), _p(vcache), cache_bs, cache_rs,
+                                   cache_hs, hd, w, slot0, B, N), 'i2t_kv_prefill')
+
+
 def ngram_ban_argmax(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, margin_out=None):
     _l.check(_lib().i2t_ngram_ban_argmax(_stream(), _p(logits), ld, int(logits.dtype == F32), _p(ids), ids_ld, _p(len_ptr),
                                          _p(ngram_sizes), n_sizes, B, V, _p(margin_out)), 'i2t_ngram_ban_argmax')

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 8
+#define I2T_ABI_VERSION 9
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -381,6 +381,17 @@ int i2t_decode_attention(void* stream, const void* q, int q_rs, void* kcache, vo
                          int append_dm, int B, int H);
 int i2t_kv_append(void* stream, const void* qkv, int qkv_rs, void* kcache, void* vcache, long cache_bs,
                   int cache_rs, const int* pos_ptr, int B, int d);
+/* Prompt prefill of the decode caches (generate_captions(prompt_prefill='pass')): the K and V rows that ONE forward pass over m
+ * prompt tokens of B images left in `src` (bf16 rows src_ld apart, K at column k_off, V at v_off, w = Hkv * hd columns each; token t
+ * of image b is source row b * src_T + src_t0 + t, t < m) are copied to cache slots slot0 .. slot0 + m - 1 of the N cache rows
+ * b * N .. b * N + N - 1 of every image.  Element (row, head, slot, column) of a cache is at row * cache_bs + head * cache_hs +
+ * slot * cache_rs + column, as i2t_decode_attention / i2t_gq_decode_attention address it: head-major [R][H][clen][64] is cache_rs =
+ * 64, cache_hs = clen * 64; row-major [R][clen][w] is cache_rs = w, cache_hs = hd.  Every 16-byte chunk of a source row is loaded
+ * once and stored N times; no other slot and no other cache row is written.  Refused: null pointers, w % 8, hd % 8 (or hd not
+ * dividing w), src_ld % 8, column offsets off a multiple of 8 or outside the row, bases off 16 bytes, strides off 8 elements,
+ * m < 1, src_t0 + m > src_T, slot0 + m beyond what cache_bs (cache_hs) holds. */
+int i2t_kv_prefill(void* stream, const void* src, int src_ld, int k_off, int v_off, int src_T, int src_t0, int m, void* kcache,
+                   void* vcache, long cache_bs, int cache_rs, long cache_hs, int hd, int w, int slot0, int B, int N);
 int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, int logits_is_f32, int64_t* ids, int ids_ld,
                          int* len_ptr, const int* ngram_sizes, int n_sizes, int B, int V, float* margin_out);
 /* The greedy step's lm_head without its logits (vision_encoder_decoder.py:143-180 with top_k = 1): i2t_gemm_bf16_top2 runs
