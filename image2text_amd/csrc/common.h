@@ -210,6 +210,14 @@ __device__ __forceinline__ bool ban_bit(const unsigned* bits, int c) { return (b
 // the kernel's base pointers address -- row b itself, so 0; or (HIST, beam search) row 0, so the row that hs[], the workgroup's
 // LDS copy of row b's history, names for the key.
 constexpr int DECODE_MAX_KEYS = 1024;
+// The split-key form of the grouped-query kernel (family.hip: i2t_gq_decode_attention_long) gives every LONG_CHUNK_KEYS keys of a row
+// a wave of their own, so only a chunk's scores sit in LDS and the bound on a row is the workspace's: DECODE_LONG_MAX_KEYS
+// (decoding.py holds the host's copies of both).  -DLONG_CHUNK_KEYS=... builds an A/B variant (tools/build_variant.sh).
+#ifndef LONG_CHUNK_KEYS
+#define LONG_CHUNK_KEYS 256
+#endif
+static_assert(LONG_CHUNK_KEYS >= 64 && LONG_CHUNK_KEYS <= 1024 && LONG_CHUNK_KEYS % 64 == 0, "LONG_CHUNK_KEYS: a multiple of 64 up to 1024");
+constexpr int DECODE_LONG_MAX_KEYS = 32768;
 template <bool HIST>
 __device__ __forceinline__ int key_row(const int* hs, int key) {
     if constexpr (HIST) return hs[key];

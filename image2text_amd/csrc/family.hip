@@ -380,6 +380,165 @@ __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* _
     }
 }
 
+// ---------------------------------------------------------------------------------------- decode step, split over the keys
+// gq_decode_attention_kernel for caches past DECODE_MAX_KEYS (i2t_gq_decode_attention_long): grid (H, R, NC), one wave per (query head,
+// row, chunk of CH = LONG_CHUNK_KEYS keys).  Chunk ch covers keys [ch CH, min((ch + 1) CH, n)), n = *pos_ptr + 1 read on the device
+// (never past max_keys: the cache and the workspace are sized by it), so the grid depends on max_keys alone and one captured graph
+// serves every position; a chunk at or past n returns before it reads or writes anything.  Inside a chunk: the access pattern of the
+// kernel above, the scores in ps[CH].  The chunk that holds slot n - 1 takes the new token's key / value from LDS and, for the first
+// head of its group, appends them to the cache.  What a chunk leaves in the workspace: its maximum m, sum exp(s - m) and the
+// unnormalised fp32 sum p v -- acc f32 [R][H][NC][HD], then ml f32 [R][H][NC][2].  HIST: key t of row b from cache row hist[b][t],
+// through an LDS copy of the chunk's CH entries; there is no slot_pos and no rows_per_mem here (sparse layers and cross memories never
+// exceed DECODE_MAX_KEYS).
+template <int HD, bool HIST>
+__global__ __launch_bounds__(64) void gq_decode_attention_split_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
+                                                                       const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
+                                                                       bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
+                                                                       float* __restrict__ ws, const int* __restrict__ pos_ptr,
+                                                                       int n_keys_fixed, int max_keys, int G, float scale,
+                                                                       const int* __restrict__ hist, int hist_ld) {
+    constexpr int LPK = HD / 8, KPP = 64 / LPK, CH = LONG_CHUNK_KEYS;
+    __shared__ float qs[HD], kn[HD], vn[HD];
+    __shared__ float ps[CH];
+    __shared__ int hs[HIST ? CH : 1];
+    const int h = blockIdx.x, b = blockIdx.y, ch = blockIdx.z, lane = threadIdx.x, hk = h / G;
+    const int H = gridDim.x, NC = gridDim.z;
+    const int n = min(pos_ptr ? (*pos_ptr + 1) : n_keys_fixed, max_keys);
+    const int k_lo = ch * CH;
+    if (k_lo >= n) return;                                  // wave-uniform: nothing of this chunk is live
+    const int k_hi = min(k_lo + CH, n);
+    const bool append = k_new != nullptr && k_hi == n;      // this chunk holds slot n - 1, the new token's
+    const int nc = (append ? k_hi - 1 : k_hi) - k_lo;       // keys of this chunk read back from the cache: local 0 .. nc - 1
+    const int own = HIST ? b : 0;
+    bf16_t* kb = kc + (size_t)(b - own) * cache_bs + hk * HD;
+    bf16_t* vb = vc + (size_t)(b - own) * cache_bs + hk * HD;
+    if constexpr (HIST)
+        for (int j = lane; j < nc; j += 64) hs[j] = hist[(size_t)b * hist_ld + k_lo + j];
+    for (int i = lane; i < HD; i += 64) {
+        qs[i] = bf16_to_f32(q[(size_t)b * q_rs + h * HD + i]);
+        if (append) {
+            const bf16_t kv = k_new[(size_t)b * kv_rs + hk * HD + i], vv = v_new[(size_t)b * kv_rs + hk * HD + i];
+            kn[i] = bf16_to_f32(kv);
+            vn[i] = bf16_to_f32(vv);
+            if (h % G == 0) {
+                kb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + i] = kv;
+                vb[(size_t)own * cache_bs + (size_t)(n - 1) * cache_rs + i] = vv;
+            }
+        }
+    }
+    __syncthreads();
+    const int kg = lane / LPK, c = lane % LPK;
+    float qv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qv[e] = qs[c * 8 + e];
+    float mx = -INFINITY;
+    if (append && lane == 0) {
+        float s = 0.f;
+        for (int e = 0; e < HD; ++e) s += kn[e] * qs[e];
+        s *= scale;
+        ps[nc] = s;
+        mx = s;
+    }
+    for (int j0 = 0; j0 < nc; j0 += KPP) {
+        const int j = j0 + kg;
+        float s = 0.f;
+        if (j < nc) {
+            const u32x4 kk =
+                *reinterpret_cast<const u32x4*>(kb + (size_t)key_row<HIST>(hs, j) * cache_bs + (size_t)(k_lo + j) * cache_rs + c * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += bf16lo(kk[e]) * qv[2 * e] + bf16hi(kk[e]) * qv[2 * e + 1];
+        }
+#pragma unroll
+        for (int o_ = 1; o_ < LPK; o_ <<= 1) s += __shfl_xor(s, o_, 64);
+        s *= scale;
+        if (j < nc) {
+            if (c == 0) ps[j] = s;
+            mx = fmaxf(mx, s);
+        }
+    }
+    mx = wave_max(mx);
+    __syncthreads();
+    float sum = 0.f;
+    for (int j = lane; j < k_hi - k_lo; j += 64) {
+        const float p = __expf(ps[j] - mx);
+        ps[j] = p;
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    __syncthreads();
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int j0 = 0; j0 < nc; j0 += KPP) {
+        const int j = j0 + kg;
+        if (j < nc) {
+            const u32x4 vv =
+                *reinterpret_cast<const u32x4*>(vb + (size_t)key_row<HIST>(hs, j) * cache_bs + (size_t)(k_lo + j) * cache_rs + c * 8);
+            const float p = ps[j];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                acc[2 * e] += p * bf16lo(vv[e]);
+                acc[2 * e + 1] += p * bf16hi(vv[e]);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int o_ = LPK; o_ < 64; o_ <<= 1) acc[e] += __shfl_xor(acc[e], o_, 64);      // sum the key stripes (lanes with equal c)
+    const size_t part = ((size_t)b * H + h) * NC + ch;
+    if (kg == 0) {
+        if (append) {
+            const float pn = ps[nc];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += pn * vn[c * 8 + e];
+        }
+        float* dst = ws + part * HD + c * 8;
+        *reinterpret_cast<f32x4*>(dst) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<f32x4*>(dst + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    }
+    if (lane == 0) {
+        float* ml = ws + (size_t)gridDim.y * H * NC * HD + part * 2;
+        ml[0] = mx;
+        ml[1] = sum;
+    }
+}
+
+// The combine: one wave per (row, query head) merges the ceil(n / CH) live partials of the kernel above in chunk order -- out =
+// sum_c acc_c exp(m_c - M) / sum_c s_c exp(m_c - M), M the largest m_c -- and writes the bf16 row with the packed 16-byte store of
+// gq_decode_attention_kernel.  Lane c < HD / 8 owns columns 8 c .. 8 c + 7; the order is fixed, so the result is bit-reproducible.
+template <int HD>
+__global__ __launch_bounds__(64) void gq_decode_attention_combine_kernel(const float* __restrict__ ws, int NC, bf16_t* __restrict__ o, int o_rs,
+                                                                         const int* __restrict__ pos_ptr, int n_keys_fixed, int max_keys) {
+    constexpr int LPK = HD / 8, CH = LONG_CHUNK_KEYS;
+    const int h = blockIdx.x, b = blockIdx.y, c = threadIdx.x, H = gridDim.x;
+    const int n = min(pos_ptr ? (*pos_ptr + 1) : n_keys_fixed, max_keys);
+    const int live = (n + CH - 1) / CH;                     // <= NC: n <= max_keys
+    if (live <= 0 || c >= LPK) return;
+    const size_t part0 = ((size_t)b * H + h) * NC;
+    const float* ml = ws + (size_t)gridDim.y * H * NC * HD + part0 * 2;
+    float M = -INFINITY;
+    for (int i = 0; i < live; ++i) M = fmaxf(M, ml[2 * i]);
+    float acc[8], sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int i = 0; i < live; ++i) {
+        const float f = __expf(ml[2 * i] - M);
+        const float* src = ws + (part0 + i) * HD + c * 8;
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
+        sum += ml[2 * i + 1] * f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[e] += a0[e] * f;
+            acc[4 + e] += a1[e] * f;
+        }
+    }
+    const float inv = 1.0f / sum;
+    const u32x4 pk = {pack_bf16x2(acc[0] * inv, acc[1] * inv), pack_bf16x2(acc[2] * inv, acc[3] * inv),
+                      pack_bf16x2(acc[4] * inv, acc[5] * inv), pack_bf16x2(acc[6] * inv, acc[7] * inv)};
+    *reinterpret_cast<u32x4*>(o + (size_t)b * o_rs + h * HD + c * 8) = pk;
+}
+
 // per-layer cache slot and membership of the token at *pos_ptr: lpos[l] = rank[l][pos], lmem[l] = member[l][pos]
 __global__ void sparse_step_setup_kernel(const int* __restrict__ pos_ptr, const int* __restrict__ rank, const int* __restrict__ member,
                                          int* __restrict__ lpos, int* __restrict__ lmem, int L, int tmax) {
@@ -527,6 +686,56 @@ extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_r
                                             const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
     return gq_decode_attention("i2t_beam_gq_decode_attention", true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
                                cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, slot_pos, rows_per_mem, R, H, Hkv, hd);
+}
+
+// i2t_gq_decode_attention_long and i2t_beam_gq_decode_attention_long: one set of checks, the partial launch and the combine behind it
+static int gq_decode_attention_long(const char* fn, bool beam, void* stream, const void* q, int q_rs, const void* k_new, const void* v_new,
+                                    int kv_rs, void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                                    const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, int B, int H, int Hkv,
+                                    int hd, float* ws, long ws_floats) {
+    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0, "%s: bad args", fn);
+    I2T_REQUIRE(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128; heads of 16 and 32 have the classic kernel only, up to %d keys)", fn, hd,
+                DECODE_MAX_KEYS);
+    I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "%s: no key count", fn);
+    I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_LONG_MAX_KEYS, "%s: max_keys %d (1 .. %d)", fn, max_keys, DECODE_LONG_MAX_KEYS);
+    I2T_REQUIRE(n_keys_fixed <= max_keys, "%s: n_keys_fixed %d exceeds max_keys %d", fn, n_keys_fixed, max_keys);
+    I2T_REQUIRE(!beam || hist, "%s: hist is required", fn);
+    I2T_REQUIRE(!beam || hist_ld >= max_keys, "%s: hist_ld %d shorter than max_keys %d", fn, hist_ld, max_keys);
+    const int NC = (max_keys + LONG_CHUNK_KEYS - 1) / LONG_CHUNK_KEYS;
+    const long need = (long)B * H * NC * (hd + 2);
+    I2T_REQUIRE(ws && ALIGNED16(ws) && ws_floats >= need, "%s: ws of %ld floats: %ld needed (rows x heads x %d chunks of %d keys x (hd + 2)), 16-byte aligned",
+                fn, ws ? ws_floats : 0L, need, NC, LONG_CHUNK_KEYS);
+    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
+                "%s: cache / output rows must be 16-byte aligned", fn);
+    const float scale = 1.0f / sqrtf((float)hd);
+    hipStream_t s = (hipStream_t)stream;
+#define GDEC_SPLIT(HD) (beam ? gq_decode_attention_split_kernel<HD, true> : gq_decode_attention_split_kernel<HD, false>)
+    hipLaunchKernelGGL(hd == 64 ? GDEC_SPLIT(64) : GDEC_SPLIT(128), dim3(H, B, NC), dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,
+                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, ws, pos_ptr, n_keys_fixed, max_keys,
+                       H / Hkv, scale, hist, hist_ld);
+#undef GDEC_SPLIT
+    I2T_CHECK_LAUNCH(fn);                                   // no combine over a workspace that was never written
+    hipLaunchKernelGGL(hd == 64 ? gq_decode_attention_combine_kernel<64> : gq_decode_attention_combine_kernel<128>, dim3(H, B), dim3(64), 0, s,
+                       (const float*)ws, NC, (bf16_t*)out, out_rs, pos_ptr, n_keys_fixed, max_keys);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
+}
+
+extern "C" int i2t_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
+                                            void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                                            const int* pos_ptr, int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd, float* ws,
+                                            long ws_floats) {
+    return gq_decode_attention_long("i2t_gq_decode_attention_long", false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                                    cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, B, H, Hkv, hd, ws, ws_floats);
+}
+
+extern "C" int i2t_beam_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
+                                                 void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                                                 const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, int R,
+                                                 int H, int Hkv, int hd, float* ws, long ws_floats) {
+    return gq_decode_attention_long("i2t_beam_gq_decode_attention_long", true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache,
+                                    cache_bs, cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, R, H, Hkv, hd, ws,
+                                    ws_floats);
 }
 
 extern "C" int i2t_sparse_step_setup(void* stream, const int* pos_ptr, const int* rank, const int* member, int* lpos, int* lmem, int L,

@@ -49,7 +49,8 @@ class Sampling(NamedTuple):
 
 
 # i2t_decode_attention and i2t_gq_decode_attention (csrc/common.h::DECODE_MAX_KEYS) keep the scores of at most this many keys per caption
-# in LDS; neither reads a key count from the device against it, so the cache the step attends over is never allocated longer
+# in LDS; neither reads a key count from the device against it, so the cache THEY attend over is never allocated longer (a longer
+# one is the long state's, below, and runs other kernels)
 DECODE_MAX_KEYS = 1024
 
 
@@ -61,6 +62,70 @@ def text_window(block: int, off: int, prefix: int) -> int:
         raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
                          f'no room for text (block {block}, soft-prompt offset {off})')
     return tmax
+
+
+# The Llama-family decoders with heads of 64 or 128 (row-major cache) have a second attention form, i2t_gq_decode_attention_long,
+# which splits a row's keys into chunks of LONG_CHUNK_KEYS across workgroups and bounds a row by its workspace alone
+# (csrc/common.h::LONG_CHUNK_KEYS / DECODE_LONG_MAX_KEYS, both pinned by tests/test_long_decode_host_cpu.py).  A call
+# that fits text_window never sees it.
+LONG_CHUNK_KEYS = ops.LONG_CHUNK_KEYS
+DECODE_LONG_MAX_KEYS = 32768
+LONG_HEAD_DIMS = (64, 128)          # the head widths the split-key kernels are built for
+
+
+def takes_long_cache(llama_spec) -> bool:
+    """Whether a decoder may decode past text_window: ``llama_spec`` is its Llama-family spec (engine.dec.llama; None for the dense and
+    nano-mini decoders).  The plugins also accept heads of 16 and 32, which the split-key kernels are not built for: those decoders
+    keep the classic window and its refusal."""
+    return llama_spec is not None and llama_spec.hd in LONG_HEAD_DIMS
+
+
+def decode_window(block: int, off: int, prefix: int, llama: bool) -> int:
+    """The text positions a KV-cache call may span: text_window, or -- ``llama``: a decoder that takes the long cache -- the model's
+    own block less the soft-prompt offset, with at most DECODE_LONG_MAX_KEYS keys per row, the ``prefix`` prompt rows included."""
+    return min(block - off, DECODE_LONG_MAX_KEYS - prefix) if llama else text_window(block, off, prefix)
+
+
+def cache_plan(block: int, off: int, prefix: int, total: int, llama: bool):
+    """-> (clen, long): the slots per row of the self-attention cache that a call over ``total`` id columns runs on, and whether it is
+    the long cache of the split-key attention.  A call that fits ``text_window(block, off, prefix)`` gets that window's cache -- what
+    every call got before the long form existed -- and long = False.  One that does not, on a decoder that takes the long cache
+    (``llama``: takes_long_cache), gets prefix + total slots rounded up to whole chunks, at most prefix + decode_window, and
+    long = True.  A total past ``decode_window`` is a ValueError naming that window, the same text for every decoder."""
+    try:
+        tmax = text_window(block, off, prefix)
+    except ValueError:
+        if not llama:
+            raise
+        tmax = 0
+    if total <= tmax:
+        return tmax + prefix, False
+    window = decode_window(block, off, prefix, llama)
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    return min(prefix + window, -(-(prefix + total) // LONG_CHUNK_KEYS) * LONG_CHUNK_KEYS), True
+
+
+def split_attention_host(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, chunk: int = LONG_CHUNK_KEYS) -> np.ndarray:
+    """What the split-key decode attention computes, on the host in fp64 (numpy): q [hd] against k / v [n][hd].  Every chunk of
+    ``chunk`` keys yields its maximum m_c, s_c = sum exp(score - m_c) and the unnormalised a_c = sum exp(score - m_c) v
+    (gq_decode_attention_split_kernel); the combine takes M = max m_c and returns sum_c a_c exp(m_c - M) / sum_c s_c exp(m_c - M), the
+    chunks in order."""
+    q, k, v = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    n = k.shape[0]
+    assert n >= 1 and chunk >= 1 and k.shape == v.shape and q.shape == k.shape[1:]
+    parts = []
+    for lo in range(0, n, chunk):
+        s = (k[lo:lo + chunk] @ q) * scale
+        m = s.max()
+        p = np.exp(s - m)
+        parts.append((m, p.sum(), p @ v[lo:lo + chunk]))
+    M = max(m for m, _, _ in parts)
+    num, den = np.zeros_like(q), 0.0
+    for m, s, a in parts:
+        f = np.exp(m - M)
+        num, den = num + a * f, den + s * f
+    return num / den
 
 
 PROMPT_PREFILL_MODES = ('steps', 'pass')
@@ -123,11 +188,36 @@ class GreedyDecoder:
         self.model = model
         self.eng: HotPath = model._engine
         self._state = None
+        self._long_state = None             # the state of calls past text_window (cache_plan): classic calls never run on it
 
     # ------------------------------------------------------------------------------------------------ buffers
-    def _build(self, B: int, ids_ld: int, mem_rows: Optional[int] = None):
+    def _cache_args(self):
+        """(block, off, prefix, llama) of this model, as decode_window and cache_plan take them"""
+        eng, dc = self.eng, self.eng.dec
+        ncls = eng.enc.ncls
+        return (dc.block, ncls if self.model.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
+                takes_long_cache(dc.llama))
+
+    def _state_for(self, rows: int, total: int, build, extra=None):
+        """The cached state that serves a call over ``rows`` rows and ``total`` id columns, (re)built by ``build(clen)`` -- clen None: the
+        classic window's -- when the cached one does not (_reusable).  A call that fits text_window runs on self._state, whatever ran
+        before; one past it (takes_long_cache) on self._long_state, rebuilt when it holds fewer cache slots than the call needs.  A call
+        past decode_window is cache_plan's ValueError."""
+        block, off, prefix, llama = self._cache_args()
+        clen, long = cache_plan(block, off, prefix, total, llama)
+        slot = '_long_state' if long else '_state'
+        st = getattr(self, slot)
+        if not self._reusable(st, rows, total, lambda st: (not long or st.clen >= clen) and (extra is None or extra(st))):
+            setattr(self, slot, None)                           # the old buffers go before the new ones are made
+            st = build(clen if long else None)
+            setattr(self, slot, st)
+        assert total <= st.tmax
+        return st
+
+    def _build(self, B: int, ids_ld: int, mem_rows: Optional[int] = None, clen: Optional[int] = None):
         """Buffers of a step over B rows; the cross-attention memory holds ``mem_rows`` (default B) rows -- the images, when the B
-        rows are beams of them (BeamDecoder)."""
+        rows are beams of them (BeamDecoder).  ``clen``: the cache slots per row of a long state (cache_plan), whose self-attention
+        runs the split-key kernels over st.attn_ws; None: the classic window."""
         eng, a = self.eng, self.eng.arena
         dc = eng.dec
         dev = a.device
@@ -137,7 +227,7 @@ class GreedyDecoder:
         d, ff = dc.d, dc.ff
         # Hugging Face decoder + soft prompt (engine.decode_prefixed): the encoder outputs are the first cache positions of every caption
         prefix = min(ncls, dc.block) if dc.prefixed else 0
-        tmax = text_window(dc.block, off, prefix)
+        tmax = text_window(dc.block, off, prefix) if clen is None else clen - prefix
         st = SimpleNamespace(B=B, ids_ld=ids_ld, off=off, tmax=tmax, arena=a, sparse_epoch=eng.sparse_epoch, prefix=prefix,
                              clen=tmax + prefix)
         e = lambda *s, dtype=BF16: torch.zeros(*s, dtype=dtype, device=dev)
@@ -161,6 +251,8 @@ class GreedyDecoder:
             st.qkv, st.ao, st.gu = e(B, (ls.H + 2 * ls.Hkv) * ls.hd), e(B, ls.H * ls.hd), e(B, 2 * ff)
             st.kc = [e(B, st.clen, ls.Hkv * ls.hd) for _ in range(dc.L)]
             st.vc = [e(B, st.clen, ls.Hkv * ls.hd) for _ in range(dc.L)]
+            if st.clen > DECODE_MAX_KEYS:                       # one layer's chunk partials at a time: every layer overwrites them
+                st.attn_ws = torch.empty(ops.gq_decode_long_workspace_floats(B, ls.H, st.clen, ls.hd), dtype=F32, device=dev)
         elif dc.fam is None:
             st.kc = [e(B, st.clen, d) for _ in range(dc.L)]
             st.vc = [e(B, st.clen, d) for _ in range(dc.L)]
@@ -425,6 +517,10 @@ class GreedyDecoder:
             q, k, v, H, Hkv, hd, slots = gq
             w = Hkv * hd
             args = (q, k, v, st.kc[l], st.vc[l], slots * w, w, st.ao, pos_ptr, 0, slots, B, H, Hkv, hd)
+            if st.clen > DECODE_MAX_KEYS:       # a long state (Llama family: slots = st.clen, no slot_pos): the keys split across workgroups
+                ops.gq_decode_attention_long(*args, st.attn_ws) if st.hist is None else \
+                    ops.beam_gq_decode_attention_long(*args, st.attn_ws, hist=st.hist)
+                return
             ops.gq_decode_attention(*args) if st.hist is None else ops.beam_gq_decode_attention(*args, hist=st.hist, slot_pos=slot_pos)
 
     def _cross_attention(self, st, l: int, gq_hd: Optional[int] = None):
@@ -601,10 +697,9 @@ class GreedyDecoder:
         dc = eng.dec
         B, P = prompt_ids.shape
         total = P + max_new_tokens
-        st = self._state
-        if not self._reusable(st, B, total):
-            st = self._state = self._build(B, max(total, dc.block))
-        assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
+        window = decode_window(*self._cache_args())
+        assert total <= window, f'prompt + new tokens ({total}) exceed the text window ({window})'
+        st = self._state_for(B, total, lambda clen: self._build(B, max(total, dc.block), clen=clen))
         assert not (return_margins and sampling is not None) and not (return_dists and sampling is None)
         self._prepare_inputs(st, images, B)
         if sampling is not None:
@@ -657,10 +752,10 @@ class BeamDecoder(GreedyDecoder):
     (rows_per_mem = W); the prompt is prefilled for all R rows under the identity table.  Once every beam of every caption holds
     EOS the remaining replays do nothing, so the host launches them all and reads the final length once."""
 
-    def _build_beam(self, B: int, spec: BeamSpec, ids_ld: int, record: bool):
+    def _build_beam(self, B: int, spec: BeamSpec, ids_ld: int, record: bool, clen: Optional[int] = None):
         W, E = spec.beam_width, spec.expansion
         R = B * W
-        st = self._build(R, ids_ld, mem_rows=B)
+        st = self._build(R, ids_ld, mem_rows=B, clen=clen)
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         st.W, st.images = W, B
@@ -708,12 +803,10 @@ class BeamDecoder(GreedyDecoder):
         R = B * W
         total = max(P, max_len)
         n_steps = total - P
-        st = self._state
-        if not self._reusable(st, R, total, lambda st: (getattr(st, 'W', None) == W and st.spec.key() == spec.key()
-                                                         and (st.raw_tok is not None) == record)):
-            self._state = None
-            st = self._state = self._build_beam(B, spec, max(total, dc.block), record)
-        assert total <= st.tmax, f'prompt + new tokens ({total}) exceed the text window ({st.tmax})'
+        window = decode_window(*self._cache_args())
+        assert total <= window, f'prompt + new tokens ({total}) exceed the text window ({window})'
+        st = self._state_for(R, total, lambda clen: self._build_beam(B, spec, max(total, dc.block), record, clen),
+                             lambda st: (getattr(st, 'W', None) == W and st.spec.key() == spec.key() and (st.raw_tok is not None) == record))
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
         if spec.eos is not None and bool((prompt_ids == spec.eos).any(dim=-1).all()):
             ids = prompt_rows.view(B, W, P).clone()          # every beam already holds EOS: nothing to do
@@ -825,9 +918,9 @@ class CaptionDecoder(GreedyDecoder):
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
     last_prefill_steps = 0              # prefill replays the last call launched: Pmin - 1, or 0 under prompt_prefill='pass'
 
-    def _build_captions(self, B: int, N: int, ids_ld: int):
+    def _build_captions(self, B: int, N: int, ids_ld: int, clen: Optional[int] = None):
         R = B * N
-        st = self._build(R, ids_ld, mem_rows=B)
+        st = self._build(R, ids_ld, mem_rows=B, clen=clen)
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         st.N, st.images = N, B
@@ -897,12 +990,7 @@ class CaptionDecoder(GreedyDecoder):
         a = eng.prepare(False)
         R, total = B * N, pmax + max_new_tokens
         pad = (0 if eos is None else eos) if pad is None else pad
-        st = self._state
-        if not self._reusable(st, R, total, lambda st: st.N == N):
-            self._state = None
-            st = self._state = self._build_captions(B, N, max(total, dc.block))
-        if total > st.tmax:
-            raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({st.tmax})')
+        st = self._state_for(R, total, lambda clen: self._build_captions(B, N, max(total, dc.block), clen), lambda st: st.N == N)
         prompt = prompt_ids[:, :pmax].to(a.device)
         plen_dev = forced = None
         if ragged:

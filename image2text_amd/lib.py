@@ -88,6 +88,8 @@ SIGNATURES = {
     'i2t_moe_pack_w2': [P, P, P, P, I, I, I, I],
     'i2t_moe_unpack_dw2': [P, P, P, P, I, I, I, I],
     'i2t_gq_decode_attention': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, I, I, I, I],
+    'i2t_gq_decode_attention_long': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, I, I, I, I, P, L],
+    'i2t_beam_gq_decode_attention_long': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, P, I, I, I, I, I, P, L],
     'i2t_beam_candidates': [P, P, I, P, I, P, P, P, I, I, I, I, F, I, I, F, P, P, P, P],
     'i2t_beam_consolidate': [P, P, P, P, P, I, P, I, P, P, P, P, P, I, I, I, F, I, P, P],
     'i2t_beam_advance': [P, P, P],
@@ -142,7 +144,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 

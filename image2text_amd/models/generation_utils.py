@@ -21,7 +21,8 @@ no host sync per token.  Draws without replacement are Gumbel-top-k over a count
 from torch's CPU generator once per call, so ``torch.manual_seed`` reproduces a run) -- the same distribution as the sequential
 draws of ``torch.multinomial``, not the same stream.  Non-causal decoders keep the path above.  Sparse nano-mini decoder blocks
 run on the cache too: a sparse layer caches its kept positions only, and reads slot s through the history entry of the text
-position that slot holds.
+position that slot holds.  The cached search holds at most 1024 keys per beam; on Llama-2 / Qwen2 / Falcon decoders with heads of
+64 or 128 a search past that runs on a long cache up to the model's block (``decoding.cache_plan``).
 """
 import math
 import os

@@ -217,7 +217,11 @@ class VisionEncoderDecoder(nn.Module):
         """Autoregressive generation (reference :136-182) on the static KV cache under hipGraph replay, one replay per token.
         ``top_k=1`` without a nucleus is greedy decoding (argmax after the n-gram ban; the temperature cannot change an argmax);
         every other mode draws each token on the device from the reference's filtered distribution (temperature -> n-gram
-        ban -> top-k -> softmax -> nucleus), see ``decoding.Sampling``.  The draws are reproducible under ``torch.manual_seed``."""
+        ban -> top-k -> softmax -> nucleus), see ``decoding.Sampling``.  The draws are reproducible under ``torch.manual_seed``.
+        The window: prompt + new tokens fit ``block_size`` less the soft prompt, and the cache holds at most 1024 keys per caption
+        (soft-prompt rows of a Hugging Face decoder included) -- except on Llama-2 / Qwen2 / Falcon decoders with heads of 64 or
+        128, where a call past 1024 keys runs on a second, long cache up to the model's block and 32 768 keys
+        (``decoding.cache_plan``)."""
         blk_size = self.decoder.block_size - self.space_for_prompt
         assert max_new_tokens <= blk_size - prompt_ids.size(-1)
         dev = next(self.parameters()).device
@@ -266,7 +270,10 @@ class VisionEncoderDecoder(nn.Module):
         (the default) is one decode step per column over all B * N rows.  'pass' runs them through the decoder's forward as ONE causal
         sequence per IMAGE and copies the K/V into the N rows of each image; the steps after it are the same launches, but the two modes
         are not bit-equal (the prompt's K/V come from the forward's GEMM and attention shapes).  The nano-mini family refuses 'pass'
-        (NotImplementedError); a non-causal decoder has no cache and ignores the argument; any other value is a ValueError."""
+        (NotImplementedError); a non-causal decoder has no cache and ignores the argument; any other value is a ValueError.
+        The text window is ``generate``'s: 1024 cached keys per caption, and on Llama-2 / Qwen2 / Falcon decoders with heads of 64
+        or 128 the model's own block (at most 32 768 keys) -- a call past 1024 keys runs on a long cache of its own, and calls that fit the
+        classic window are bit-identical whatever ran before."""
         import numpy as np
         from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, check_caption_args,
                                 check_ragged_caption_args, generate_by_recompute, prefill_plan)

@@ -402,6 +402,44 @@ def beam_gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs
     return out
 
 
+# the host's copy of csrc/common.h::LONG_CHUNK_KEYS, the keys per wave of the split-key decode attention
+# (tests/test_long_decode_host_cpu.py reads the header against it)
+LONG_CHUNK_KEYS = 256
+
+
+def gq_decode_long_workspace_floats(R: int, H: int, max_keys: int, hd: int) -> int:
+    """fp32 elements of the workspace of gq_decode_attention_long / beam_gq_decode_attention_long over R rows, H query heads of width hd
+    and caches of max_keys slots: R * H * NC * (hd + 2), NC = ceil(max_keys / LONG_CHUNK_KEYS) -- per (row, head, chunk) the
+    unnormalised sum [hd], then the chunk's maximum and sum of exponentials (include/i2t.h::i2t_gq_decode_attention_long)."""
+    return R * H * (-(-max_keys // LONG_CHUNK_KEYS)) * (hd + 2)
+
+
+def gq_decode_attention_long(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, B, H, Hkv, hd, ws):
+    """gq_decode_attention over caches past 1024 keys, the keys split across workgroups (include/i2t.h::i2t_gq_decode_attention_long);
+    ws: fp32, at least gq_decode_long_workspace_floats(B, H, max_keys, hd) elements."""
+    _need_cuda(q, kcache, vcache, out, ws)
+    assert ws.dtype == F32 and ws.is_contiguous()
+    kv_rs = k_new.stride(0) if k_new is not None else 0
+    _l.check(_lib().i2t_gq_decode_attention_long(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
+                                                 cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, B, H, Hkv, hd, _p(ws),
+                                                 ws.numel()), 'i2t_gq_decode_attention_long')
+    return out
+
+
+def beam_gq_decode_attention_long(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, R, H, Hkv, hd,
+                                  ws, hist):
+    """gq_decode_attention_long with key t of row r read from cache row hist[r][t] (int32 [R][>= max_keys];
+    include/i2t.h::i2t_beam_gq_decode_attention_long)"""
+    _need_cuda(q, kcache, vcache, out, ws, hist)
+    assert ws.dtype == F32 and ws.is_contiguous() and hist.dtype == torch.int32 and hist.stride(1) == 1
+    kv_rs = k_new.stride(0) if k_new is not None else 0
+    _l.check(_lib().i2t_beam_gq_decode_attention_long(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache),
+                                                      cache_bs, cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys,
+                                                      _p(hist), hist.stride(0), R, H, Hkv, hd, _p(ws), ws.numel()),
+             'i2t_beam_gq_decode_attention_long')
+    return out
+
+
 def beam_candidates(logits, ids, len_ptr, ctrl, ngram_sizes, R, V, E, temperature, top_k, eos, log_boost, seed, cand_tok, cand_lp,
                     raw_tok=None):
     """E candidates per beam row after ban / crop / EOS rule (include/i2t.h::i2t_beam_candidates); top_k None/0 = no crop, eos None/-1

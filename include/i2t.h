@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 9
+#define I2T_ABI_VERSION 10
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -517,6 +517,32 @@ int i2t_moe_unpack_dw2(void* stream, const float* dW, float* gw, float* gb, int 
 int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
                             void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
                             int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd);
+/* i2t_gq_decode_attention for caches past 1024 keys (hd 64 or 128): the keys of a row are split into chunks of CH = LONG_CHUNK_KEYS
+ * (csrc/common.h, 256), one wave per (query head, row, chunk), and a second launch combines the chunk results in chunk order, so the
+ * output is bit-reproducible.  The grid depends on max_keys only -- the key count *pos_ptr + 1 (or n_keys_fixed) is read on the
+ * device and must not exceed max_keys -- so one captured launch pair serves every position.
+ *   stream                  HIP stream of both launches
+ *   q, q_rs                 bf16 [B][H hd] query rows, row stride q_rs elements
+ *   k_new, v_new, kv_rs     bf16 [B][>= Hkv hd] this token's key / value rows (row stride kv_rs): written to cache slot *pos_ptr and
+ *                           attended to; both null: nothing is appended, all keys come from the cache
+ *   kcache, vcache          bf16 row-major caches, element (row, slot, column) at row * cache_bs + slot * cache_rs + column (16-byte
+ *   cache_bs, cache_rs      aligned, strides multiples of 8); every row holds at least max_keys slots
+ *   out, out_rs             bf16 [B][H hd] result rows (16-byte aligned, out_rs % 8 == 0)
+ *   pos_ptr, n_keys_fixed   device int32: the new token's slot, key count *pos_ptr + 1; null: n_keys_fixed keys (<= max_keys)
+ *   max_keys                1 .. 32768 (DECODE_LONG_MAX_KEYS): sizes the grid, NC = ceil(max_keys / CH) chunks per row and head
+ *   B, H, Hkv, hd           rows, query heads, key/value heads (H % Hkv == 0), head width
+ *   ws, ws_floats           fp32 workspace, 16-byte aligned, at least B * H * NC * (hd + 2) floats: the chunks' unnormalised sums
+ *                           [B][H][NC][hd], then their (maximum, sum of exp) pairs [B][H][NC][2]; overwritten by every call
+ * The beam form reads key t of row r from cache row hist[r][t] (int32 [R][hist_ld], hist_ld >= max_keys, required; the new token goes
+ * to the row's own slot); it has no slot_pos and no rows_per_mem.  With an identity table its output is bit-equal to the plain form's.
+ * Every violated bound above is I2T_EINVAL with a message naming the argument, before anything is launched. */
+int i2t_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
+                                 void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr, int n_keys_fixed,
+                                 int max_keys, int B, int H, int Hkv, int hd, float* ws, long ws_floats);
+int i2t_beam_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
+                                      void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
+                                      int n_keys_fixed, int max_keys, const int* hist, int hist_ld, int R, int H, int Hkv, int hd,
+                                      float* ws, long ws_floats);
 /* Beam-search step over the static KV cache (reference models/generation_utils.py:10-148, BeamSearchTokenGenerator; csrc/beam.hip,
  * the two attention entry points beside their greedy twins in csrc/decode.hip and csrc/family.hip).
  * R = B * W rows, batch-major (row r = b * W + w).  *len_ptr, *pos_ptr and ctrl = [done, unfinished] (int32) live in device memory,
