@@ -649,71 +649,54 @@ extern "C" int i2t_moe_unpack_dw2(void* stream, const float* dW, float* gw, floa
     return I2T_OK;
 }
 
-// i2t_gq_decode_attention and i2t_beam_gq_decode_attention (fn: the entry point the messages name): one set of checks, one launch
-static int gq_decode_attention(const char* fn, bool beam, void* stream, const void* q, int q_rs, const void* k_new, const void* v_new,
-                               int kv_rs, void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+// The four grouped-query decode-attention entry points (fn: the one the messages name): one sequence of checks, in the order and with
+// the texts each entry point has always had, so the checks of one form sit between the shared ones; then the classic launch, or
+// (split) the partial launch and the combine behind it.
+static int gq_decode_attention(const char* fn, bool beam, bool split, void* stream, const void* q, int q_rs, const void* k_new,
+                               const void* v_new, int kv_rs, void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
                                const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, const int* slot_pos,
-                               int rows_per_mem, int B, int H, int Hkv, int hd) {
-    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && H > 0 && Hkv > 0 && H % Hkv == 0 && (!beam || rows_per_mem >= 1), "%s: bad args", fn);
-    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", fn, hd);
+                               int rows_per_mem, int B, int H, int Hkv, int hd, float* ws, long ws_floats) {
+    int NC = 0;                                             // split: the grid's chunks
+    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && (!split || B <= 65535) && H > 0 && Hkv > 0 && H % Hkv == 0 &&
+                (!beam || rows_per_mem >= 1), "%s: bad args", fn);
+    if (split)
+        I2T_REQUIRE(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128; heads of 16 and 32 have the classic kernel only, up to %d keys)", fn, hd,
+                    DECODE_MAX_KEYS);
+    else
+        I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", fn, hd);
     I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "%s: no key count", fn);
-    I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_MAX_KEYS && n_keys_fixed <= max_keys, "%s: at most %d keys", fn, DECODE_MAX_KEYS);
-    I2T_REQUIRE(!beam || !hist || hist_ld >= max_keys, "%s: history rows shorter than max_keys", fn);
-    I2T_REQUIRE(!beam || !slot_pos || hist, "%s: slot_pos needs a history table", fn);
-    I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
-                "%s: cache / output rows must be 16-byte aligned", fn);
-    const float scale = 1.0f / sqrtf((float)hd);
-#define GDEC_KERNEL(HD) (beam ? gq_decode_attention_kernel<HD, true> : gq_decode_attention_kernel<HD, false>)
-    const auto kernel = hd == 16 ? GDEC_KERNEL(16) : hd == 32 ? GDEC_KERNEL(32) : hd == 64 ? GDEC_KERNEL(64) : GDEC_KERNEL(128);
-#undef GDEC_KERNEL
-    hipLaunchKernelGGL(kernel, dim3(H, B), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,
-                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr,
-                       n_keys_fixed, H / Hkv, scale, hist, hist_ld, slot_pos, rows_per_mem);
-    I2T_CHECK_LAUNCH(fn);
-    return I2T_OK;
-}
-
-extern "C" int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
-                                       void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
-                                       int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd) {
-    return gq_decode_attention("i2t_gq_decode_attention", false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs,
-                               out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, nullptr, 1, B, H, Hkv, hd);
-}
-
-extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
-                                            void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
-                                            const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld,
-                                            const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
-    return gq_decode_attention("i2t_beam_gq_decode_attention", true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
-                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, slot_pos, rows_per_mem, R, H, Hkv, hd);
-}
-
-// i2t_gq_decode_attention_long and i2t_beam_gq_decode_attention_long: one set of checks, the partial launch and the combine behind it
-static int gq_decode_attention_long(const char* fn, bool beam, void* stream, const void* q, int q_rs, const void* k_new, const void* v_new,
-                                    int kv_rs, void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
-                                    const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, int B, int H, int Hkv,
-                                    int hd, float* ws, long ws_floats) {
-    I2T_REQUIRE(q && kcache && vcache && out && B > 0 && B <= 65535 && H > 0 && Hkv > 0 && H % Hkv == 0, "%s: bad args", fn);
-    I2T_REQUIRE(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128; heads of 16 and 32 have the classic kernel only, up to %d keys)", fn, hd,
-                DECODE_MAX_KEYS);
-    I2T_REQUIRE((k_new != nullptr) == (v_new != nullptr) && (pos_ptr || n_keys_fixed > 0), "%s: no key count", fn);
-    I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_LONG_MAX_KEYS, "%s: max_keys %d (1 .. %d)", fn, max_keys, DECODE_LONG_MAX_KEYS);
-    I2T_REQUIRE(n_keys_fixed <= max_keys, "%s: n_keys_fixed %d exceeds max_keys %d", fn, n_keys_fixed, max_keys);
-    I2T_REQUIRE(!beam || hist, "%s: hist is required", fn);
-    I2T_REQUIRE(!beam || hist_ld >= max_keys, "%s: hist_ld %d shorter than max_keys %d", fn, hist_ld, max_keys);
-    const int NC = (max_keys + LONG_CHUNK_KEYS - 1) / LONG_CHUNK_KEYS;
-    const long need = (long)B * H * NC * (hd + 2);
-    I2T_REQUIRE(ws && ALIGNED16(ws) && ws_floats >= need, "%s: ws of %ld floats: %ld needed (rows x heads x %d chunks of %d keys x (hd + 2)), 16-byte aligned",
-                fn, ws ? ws_floats : 0L, need, NC, LONG_CHUNK_KEYS);
+    if (split) {
+        I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_LONG_MAX_KEYS, "%s: max_keys %d (1 .. %d)", fn, max_keys, DECODE_LONG_MAX_KEYS);
+        I2T_REQUIRE(n_keys_fixed <= max_keys, "%s: n_keys_fixed %d exceeds max_keys %d", fn, n_keys_fixed, max_keys);
+        I2T_REQUIRE(!beam || hist, "%s: hist is required", fn);
+        I2T_REQUIRE(!beam || hist_ld >= max_keys, "%s: hist_ld %d shorter than max_keys %d", fn, hist_ld, max_keys);
+        NC = (max_keys + LONG_CHUNK_KEYS - 1) / LONG_CHUNK_KEYS;
+        const long need = (long)B * H * NC * (hd + 2);
+        I2T_REQUIRE(ws && ALIGNED16(ws) && ws_floats >= need, "%s: ws of %ld floats: %ld needed (rows x heads x %d chunks of %d keys x (hd + 2)), 16-byte aligned",
+                    fn, ws ? ws_floats : 0L, need, NC, LONG_CHUNK_KEYS);
+    } else {
+        I2T_REQUIRE(max_keys > 0 && max_keys <= DECODE_MAX_KEYS && n_keys_fixed <= max_keys, "%s: at most %d keys", fn, DECODE_MAX_KEYS);
+        I2T_REQUIRE(!beam || !hist || hist_ld >= max_keys, "%s: history rows shorter than max_keys", fn);
+        I2T_REQUIRE(!beam || !slot_pos || hist, "%s: slot_pos needs a history table", fn);
+    }
     I2T_REQUIRE(cache_rs % 8 == 0 && cache_bs % 8 == 0 && out_rs % 8 == 0 && ALIGNED16(kcache) && ALIGNED16(vcache) && ALIGNED16(out),
                 "%s: cache / output rows must be 16-byte aligned", fn);
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t s = (hipStream_t)stream;
-#define GDEC_SPLIT(HD) (beam ? gq_decode_attention_split_kernel<HD, true> : gq_decode_attention_split_kernel<HD, false>)
-    hipLaunchKernelGGL(hd == 64 ? GDEC_SPLIT(64) : GDEC_SPLIT(128), dim3(H, B, NC), dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new,
-                       (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, ws, pos_ptr, n_keys_fixed, max_keys,
-                       H / Hkv, scale, hist, hist_ld);
-#undef GDEC_SPLIT
+#define GQ_KERNEL(K, HD) (beam ? K<HD, true> : K<HD, false>)
+    if (!split) {
+        const auto kernel = hd == 16 ? GQ_KERNEL(gq_decode_attention_kernel, 16) : hd == 32 ? GQ_KERNEL(gq_decode_attention_kernel, 32)
+                          : hd == 64 ? GQ_KERNEL(gq_decode_attention_kernel, 64) : GQ_KERNEL(gq_decode_attention_kernel, 128);
+        hipLaunchKernelGGL(kernel, dim3(H, B), dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new, (const bf16_t*)v_new, kv_rs,
+                           (bf16_t*)kcache, (bf16_t*)vcache, cache_bs, cache_rs, (bf16_t*)out, out_rs, pos_ptr, n_keys_fixed, H / Hkv, scale, hist,
+                           hist_ld, slot_pos, rows_per_mem);
+        I2T_CHECK_LAUNCH(fn);
+        return I2T_OK;
+    }
+    hipLaunchKernelGGL(hd == 64 ? GQ_KERNEL(gq_decode_attention_split_kernel, 64) : GQ_KERNEL(gq_decode_attention_split_kernel, 128),
+                       dim3(H, B, NC), dim3(64), 0, s, (const bf16_t*)q, q_rs, (const bf16_t*)k_new, (const bf16_t*)v_new, kv_rs, (bf16_t*)kcache,
+                       (bf16_t*)vcache, cache_bs, cache_rs, ws, pos_ptr, n_keys_fixed, max_keys, H / Hkv, scale, hist, hist_ld);
+#undef GQ_KERNEL
     I2T_CHECK_LAUNCH(fn);                                   // no combine over a workspace that was never written
     hipLaunchKernelGGL(hd == 64 ? gq_decode_attention_combine_kernel<64> : gq_decode_attention_combine_kernel<128>, dim3(H, B), dim3(64), 0, s,
                        (const float*)ws, NC, (bf16_t*)out, out_rs, pos_ptr, n_keys_fixed, max_keys);
@@ -721,21 +704,36 @@ static int gq_decode_attention_long(const char* fn, bool beam, void* stream, con
     return I2T_OK;
 }
 
+extern "C" int i2t_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs, void* kcache,
+                                       void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr,
+                                       int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd) {
+    return gq_decode_attention("i2t_gq_decode_attention", false, false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, nullptr, 1, B, H, Hkv, hd, nullptr, 0);
+}
+
+extern "C" int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
+                                            void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
+                                            const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld,
+                                            const int* slot_pos, int rows_per_mem, int R, int H, int Hkv, int hd) {
+    return gq_decode_attention("i2t_beam_gq_decode_attention", true, false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, slot_pos, rows_per_mem, R, H, Hkv, hd,
+                               nullptr, 0);
+}
+
 extern "C" int i2t_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
                                             void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
                                             const int* pos_ptr, int n_keys_fixed, int max_keys, int B, int H, int Hkv, int hd, float* ws,
                                             long ws_floats) {
-    return gq_decode_attention_long("i2t_gq_decode_attention_long", false, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
-                                    cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, B, H, Hkv, hd, ws, ws_floats);
+    return gq_decode_attention("i2t_gq_decode_attention_long", false, true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, nullptr, 0, nullptr, 1, B, H, Hkv, hd, ws, ws_floats);
 }
 
 extern "C" int i2t_beam_gq_decode_attention_long(void* stream, const void* q, int q_rs, const void* k_new, const void* v_new, int kv_rs,
                                                  void* kcache, void* vcache, long cache_bs, int cache_rs, void* out, int out_rs,
                                                  const int* pos_ptr, int n_keys_fixed, int max_keys, const int* hist, int hist_ld, int R,
                                                  int H, int Hkv, int hd, float* ws, long ws_floats) {
-    return gq_decode_attention_long("i2t_beam_gq_decode_attention_long", true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache,
-                                    cache_bs, cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, R, H, Hkv, hd, ws,
-                                    ws_floats);
+    return gq_decode_attention("i2t_beam_gq_decode_attention_long", true, true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
+                               cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, nullptr, 1, R, H, Hkv, hd, ws, ws_floats);
 }
 
 extern "C" int i2t_sparse_step_setup(void* stream, const int* pos_ptr, const int* rank, const int* member, int* lpos, int* lmem, int L,
