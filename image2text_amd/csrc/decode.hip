@@ -506,6 +506,98 @@ __global__ __launch_bounds__(FIN_THREADS) void caption_finish_kernel(int64_t* __
     }
 }
 
+// The logits processors of a caption step, a pre-pass over the step's fp32 logits row before the chooser: repetition
+// penalty over ids[r][0 .. len), suppressed ids, EOS below the minimum length -- transformers' RepetitionPenalty -> SuppressTokens ->
+// MinNewTokensLength order.  One workgroup per row.  Pass A: the RAW row's (max, sum exp), a thread's chain, a fixed xor tree, the
+// waves in order (ngram_ban_argmax_kernel's shape: bit-reproducible) -> raw_lse[r].  Pass B: saved[r][j] = z[ids[r][j]], all raw
+// since nothing has been written.  Barrier.  Pass C: z[ids[r][j]] = f(saved[r][j]); every occurrence of a token reads the same raw
+// value and stores the same result, so a token is penalised once however often it occurs, with no first-occurrence search.  Barrier.
+// Pass D: the suppress list and the min-length EOS, plain stores of -inf that read nothing.  An id outside [0, V) takes no part
+// (saved 0).  Nothing is read or written once *done is set.  decoding.process_logits_host is the host's statement of passes C and D.
+constexpr int PROC_THREADS = 256;
+__global__ __launch_bounds__(PROC_THREADS) void caption_logits_process_kernel(float* logits, int ld, const int64_t* __restrict__ ids, int ids_ld,
+                                                                              const int* __restrict__ len_ptr, const int* __restrict__ plen,
+                                                                              int P, int N, const int* __restrict__ suppress, int n_suppress,
+                                                                              int eos, int min_new, float theta, float inv_theta,
+                                                                              const int* __restrict__ done, float* __restrict__ raw_lse,
+                                                                              float* saved, int saved_ld, int V) {
+    __shared__ float rmx[PROC_THREADS / 64], rse[PROC_THREADS / 64];
+    if (*done) return;                                  // block-uniform, before any barrier
+    const int r = blockIdx.x, tid = threadIdx.x;
+    int len = *len_ptr;
+    len = len < 0 ? 0 : (len > ids_ld ? ids_ld : len);
+    float* z = logits + (size_t)r * ld;
+    const int64_t* row = ids + (size_t)r * ids_ld;
+    float* sv = saved + (size_t)r * saved_ld;
+    float mx = -INFINITY, se = 0.f;
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
+    for (int c4 = tid * 4; c4 < vend; c4 += PROC_THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
+    }
+    for (int c = vend + tid; c < V; c += PROC_THREADS) lse_add(mx, se, z[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+    if ((tid & 63) == 0) {
+        rmx[tid >> 6] = mx;
+        rse[tid >> 6] = se;
+    }
+    for (int j = tid; j < len; j += PROC_THREADS) {
+        const int64_t t = row[j];
+        sv[j] = (t >= 0 && t < V) ? z[t] : 0.f;
+    }
+    __syncthreads();                                    // every read of the raw row is done
+    if (tid == 0) {
+        for (int k = 1; k < PROC_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
+        raw_lse[r] = mx + logf(se);
+    }
+    for (int j = tid; j < len; j += PROC_THREADS) {
+        const int64_t t = row[j];
+        if (t >= 0 && t < V) {
+            const float v = sv[j];                      // this thread's own store of pass B
+            z[t] = v > 0.f ? v * inv_theta : v * theta;
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_suppress; i += PROC_THREADS) {
+        const int t = suppress[i];
+        if (t >= 0 && t < V) z[t] = -INFINITY;
+    }
+    if (tid == 0 && eos >= 0) {
+        const int p = plen ? plen[r / N] : P;
+        if (len - p < min_new) z[eos] = -INFINITY;
+    }
+}
+
+// After the chooser of a processed step: tok_lp[r][len] = z_raw[c] - raw_lse[r] for the chosen c = ids[r][len], over the chooser's
+// value (which it took on the processed row).  The raw z[c] is saved[r][j] for any j < len with ids[r][j] == c (they all hold the same
+// value; the largest such j is taken), else logits[r][c], which pass C never wrote; a suppressed or min-length-banned token is not
+// chosen, so pass D needs no restore.  One wave per row, nothing is written once *done is set.
+constexpr int RAWLP_WAVES = 4;
+__global__ __launch_bounds__(64 * RAWLP_WAVES) void caption_raw_logprob_kernel(const int64_t* __restrict__ ids, int ids_ld,
+                                                                               const int* __restrict__ len_ptr, const float* __restrict__ raw_lse,
+                                                                               const float* __restrict__ saved, int saved_ld,
+                                                                               const float* __restrict__ logits, int ld, const int* __restrict__ done,
+                                                                               float* __restrict__ tok_lp, int lp_ld, int R, int V) {
+    if (*done) return;
+    const int lane = threadIdx.x & 63, r = blockIdx.x * RAWLP_WAVES + (threadIdx.x >> 6);
+    const int len = *len_ptr;
+    if (r >= R || len < 0 || len >= ids_ld || len >= lp_ld) return;      // wave-uniform
+    const int64_t* row = ids + (size_t)r * ids_ld;
+    const int64_t c = row[len];
+    if (c < 0 || c >= V) return;                        // (never from a chooser)
+    int at = -1;
+    for (int j = lane; j < len; j += 64)
+        if (row[j] == c) at = j;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) at = max(at, __shfl_xor(at, o, 64));
+    if (lane == 0) {
+        const float zc = at >= 0 ? saved[(size_t)r * saved_ld + at] : logits[(size_t)r * ld + c];
+        tok_lp[(size_t)r * lp_ld + len] = zc - raw_lse[r];
+    }
+}
+
 __global__ void advance_kernel(int* counters, int n, int delta) {
     if ((int)threadIdx.x < n) counters[threadIdx.x] += delta;
 }
@@ -703,6 +795,43 @@ extern "C" int i2t_caption_finish_ragged(void* stream, int64_t* ids, int ids_ld,
     hipLaunchKernelGGL(caption_finish_kernel<true>, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, ids, ids_ld, len_ptr, prompt, prompt_ld,
                        plen, N, max_new, eos, pad, finished, lengths, tok_lp, lp_ld, ctrl, R);
     I2T_CHECK_LAUNCH("i2t_caption_finish_ragged");
+    return I2T_OK;
+}
+
+extern "C" int i2t_caption_logits_process(void* stream, float* logits, int ld, const int64_t* ids, int ids_ld, const int* len_ptr, const int* plen,
+                                          int P, int N, const int* suppress, int n_suppress, int eos, int min_new, float theta, float inv_theta,
+                                          const int* done, float* raw_lse, float* saved, int saved_ld, int R, int V) {
+    I2T_REQUIRE(logits && ids && len_ptr && done && raw_lse && saved, "i2t_caption_logits_process: null pointer");
+    I2T_REQUIRE(n_suppress == 0 || suppress, "i2t_caption_logits_process: n_suppress = %d without a list", n_suppress);
+    I2T_REQUIRE(R > 0 && V > 0 && ids_ld > 0, "i2t_caption_logits_process: R = %d rows, V = %d, ids_ld = %d", R, V, ids_ld);
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_caption_logits_process: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    I2T_REQUIRE(saved_ld >= ids_ld, "i2t_caption_logits_process: saved_ld = %d is shorter than the id rows (ids_ld = %d)", saved_ld, ids_ld);
+    I2T_REQUIRE(n_suppress >= 0 && n_suppress < V, "i2t_caption_logits_process: n_suppress = %d: between 0 and V - 1 = %d ids", n_suppress, V - 1);
+    I2T_REQUIRE(eos < V, "i2t_caption_logits_process: eos = %d outside the vocabulary of %d", eos, V);
+    I2T_REQUIRE(min_new >= 0, "i2t_caption_logits_process: min_new = %d", min_new);
+    I2T_REQUIRE(theta > 0.f && inv_theta > 0.f && theta < INFINITY && inv_theta < INFINITY,
+                "i2t_caption_logits_process: theta = %g, 1 / theta = %g: both positive and finite", (double)theta, (double)inv_theta);
+    I2T_REQUIRE(N >= 1 && R % N == 0 && P >= 0, "i2t_caption_logits_process: %d rows in groups of %d, P = %d", R, N, P);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(saved) && ALIGNED16(raw_lse) && ALIGNED16(ids),
+                "i2t_caption_logits_process: misaligned base pointer (16 bytes)");
+    hipLaunchKernelGGL(caption_logits_process_kernel, dim3(R), dim3(PROC_THREADS), 0, (hipStream_t)stream, logits, ld, ids, ids_ld, len_ptr, plen,
+                       P, N, suppress, n_suppress, eos, min_new, theta, inv_theta, done, raw_lse, saved, saved_ld, V);
+    I2T_CHECK_LAUNCH("i2t_caption_logits_process");
+    return I2T_OK;
+}
+
+extern "C" int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* raw_lse, const float* saved,
+                                       int saved_ld, const float* logits, int ld, const int* done, float* tok_lp, int lp_ld, int R, int V) {
+    I2T_REQUIRE(ids && len_ptr && raw_lse && saved && logits && done && tok_lp, "i2t_caption_raw_logprob: null pointer");
+    I2T_REQUIRE(R > 0 && V > 0 && ids_ld > 0 && lp_ld > 0, "i2t_caption_raw_logprob: R = %d rows, V = %d, ids_ld = %d, lp_ld = %d", R, V, ids_ld,
+                lp_ld);
+    I2T_REQUIRE(ld >= V, "i2t_caption_raw_logprob: ld = %d: logits rows hold V = %d columns", ld, V);
+    I2T_REQUIRE(saved_ld >= ids_ld, "i2t_caption_raw_logprob: saved_ld = %d is shorter than the id rows (ids_ld = %d)", saved_ld, ids_ld);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(saved) && ALIGNED16(raw_lse) && ALIGNED16(ids),
+                "i2t_caption_raw_logprob: misaligned base pointer (16 bytes)");
+    hipLaunchKernelGGL(caption_raw_logprob_kernel, dim3((R + RAWLP_WAVES - 1) / RAWLP_WAVES), dim3(64 * RAWLP_WAVES), 0, (hipStream_t)stream, ids,
+                       ids_ld, len_ptr, raw_lse, saved, saved_ld, logits, ld, done, tok_lp, lp_ld, R, V);
+    I2T_CHECK_LAUNCH("i2t_caption_raw_logprob");
     return I2T_OK;
 }
 

@@ -903,6 +903,85 @@ def _finish_rows(ids: np.ndarray, plen: np.ndarray, pmin: int, max_new: int, eos
     return ids, lengths, lp
 
 
+class Processors(NamedTuple):
+    """The active logits processors of a ``generate_captions`` call, as ``caption_processors`` leaves them."""
+    theta: float                        # repetition penalty; the kernel and the host statement round it to fp32
+    inv_theta: float                    # fp32(1) / fp32(theta), formed once here: the device multiplies
+    min_new: int                        # EOS is banned while a row has emitted fewer tokens (0 without an EOS id: no rule)
+    suppress: tuple                     # distinct ids in [0, V) that are never emitted
+
+    def key(self):
+        """what a captured step bakes of them; the list's contents are copied into st.suppress per call"""
+        return (float(self.theta), int(self.min_new), len(self.suppress))
+
+
+def caption_processors(repetition_penalty: float, min_new_tokens: int, suppress_tokens, max_new_tokens: int, eos, vocab: Optional[int]):
+    """The refusals of ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` (host only) -> Processors, or None when none of
+    them is active: penalty 1, no suppressed id, and min_new_tokens 0 or no EOS id to ban (then the call is the one without them).
+    ``vocab`` None: ids are not checked against a vocabulary.  Duplicates in the list are dropped; an EOS id in the list together with
+    min_new_tokens > 0 is allowed (the same -inf twice)."""
+    theta = float(repetition_penalty)
+    if not np.isfinite(theta) or theta <= 0:
+        raise ValueError(f'repetition_penalty = {repetition_penalty}: a finite value above 0 is needed (1.0: none)')
+    with np.errstate(all='ignore'):
+        inv = np.float32(1.0) / np.float32(theta)
+    if not (np.isfinite(inv) and inv > 0 and np.isfinite(np.float32(theta)) and np.float32(theta) > 0):
+        raise ValueError(f'repetition_penalty = {repetition_penalty}: neither it nor its reciprocal is a positive finite fp32 number')
+    min_new = int(min_new_tokens)
+    if min_new != min_new_tokens or min_new < 0:
+        raise ValueError(f'min_new_tokens = {min_new_tokens}: a whole number of tokens, 0 or more')
+    if min_new > max_new_tokens:
+        raise ValueError(f'min_new_tokens = {min_new} exceeds max_new_tokens = {max_new_tokens}')
+    if isinstance(suppress_tokens, torch.Tensor):
+        suppress_tokens = suppress_tokens.detach().cpu().reshape(-1).tolist()
+    suppress = []
+    for t in (suppress_tokens if suppress_tokens is not None else ()):
+        if int(t) != t:
+            raise ValueError(f'suppress_tokens holds {t!r}: token ids are integers')
+        if int(t) < 0 or (vocab is not None and int(t) >= vocab):
+            raise ValueError(f'suppress_tokens holds {int(t)}: outside the vocabulary [0, {vocab if vocab is not None else "V"})')
+        if int(t) not in suppress:
+            suppress.append(int(t))
+    if vocab is not None and len(suppress) >= vocab:
+        raise ValueError(f'suppress_tokens covers the whole vocabulary of {vocab} tokens: nothing is left to emit')
+    if eos is None:
+        min_new = 0
+    if theta == 1.0 and not suppress and min_new == 0:
+        return None
+    return Processors(theta, float(inv), min_new, tuple(suppress))
+
+
+def process_logits_host(z, ids_row, length: int, emitted: int, theta: float, suppress, eos: Optional[int], min_new: int) -> np.ndarray:
+    """What i2t_caption_logits_process leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): it is to the
+    pre-pass what ``apply_finish_rule`` is to the finish kernel.  In the order of transformers' RepetitionPenaltyLogitsProcessor ->
+    SuppressTokensLogitsProcessor -> MinNewTokensLengthLogitsProcessor: every DISTINCT token t of ``ids_row[:length]`` (the prompt
+    included) gets z[t] * fp32(1 / theta) if z[t] > 0, else z[t] * fp32(theta) -- one fp32 multiply, as on the device; z[t] = -inf
+    for t in ``suppress``; z[eos] = -inf while ``emitted`` < ``min_new`` (``eos`` None: no rule).  Ids outside [0, V) take no part."""
+    z = np.array(z, dtype=np.float32)
+    assert z.ndim == 1
+    V = z.shape[0]
+    th = np.float32(theta)
+    inv = np.float32(1.0) / th
+    seen = np.unique(np.asarray(ids_row).reshape(-1)[:length].astype(np.int64))
+    seen = seen[(seen >= 0) & (seen < V)]
+    v = z[seen]
+    z[seen] = np.where(v > 0, v * inv, v * th).astype(np.float32)
+    sup = [int(t) for t in (suppress if suppress is not None else ()) if 0 <= int(t) < V]
+    z[sup] = -np.inf
+    if eos is not None and 0 <= eos < V and emitted < min_new:
+        z[eos] = -np.inf
+    return z
+
+
+def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0):
+    """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
+    ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
+    ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
+    the count then reads the device's table)."""
+    key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
+    return key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
+
+
 class CaptionDecoder(GreedyDecoder):
     """``generate_captions`` on the static KV cache: R = B * N rows (batch-major, r = b * N + n) through GreedyDecoder's buffers and layer
     sequence, under GreedyDecoder._replay.  The encoder and the cross K/V run once per image (rows_per_mem = N); the
@@ -930,12 +1009,29 @@ class CaptionDecoder(GreedyDecoder):
         st.tok_lp = torch.zeros(R, ids_ld, dtype=F32, device=dev)
         st.top2 = st.seg_se = None
         st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
+        st.raw_lse = st.saved = st.suppress = None              # logits processors: f32 [R] / f32 [R, ids_ld] / int32 list, made at the first active call
         return st
 
-    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None):
+    def _processor_state(self, st, proc: Processors):
+        """The buffers of an active-processor step, persistent because captured steps bake their pointers: st.raw_lse,
+        st.saved (R * ids_ld * 4 bytes) and the suppress list's buffer, which is regrown only together with the graphs that hold it; the
+        list's contents are copied in per call."""
+        dev = st.arena.device
+        if st.raw_lse is None:
+            st.raw_lse = torch.zeros(st.B, dtype=F32, device=dev)
+            st.saved = torch.zeros(st.B, st.ids_ld, dtype=F32, device=dev)
+        n = len(proc.suppress)
+        if st.suppress is None or st.suppress.numel() < n:
+            st.suppress = torch.zeros(max(64, n), dtype=torch.int32, device=dev)
+            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'proc')}
+        if n:
+            st.suppress[:n].copy_(torch.tensor(proc.suppress, dtype=torch.int32))
+
+    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None):
         """The launches of a full step.  ``forced``: None, or (prompt, plen, max_new) of a ``prompt_lengths`` call -- the finish rule is
         then i2t_caption_finish_ragged; the choosers run as they are, on every row, and what they wrote at a forced column is replaced
-        after them."""
+        after them.  ``proc``: None, or (Processors, P) of a call with active logits processors (never with ``top2``):
+        i2t_caption_logits_process between the GEMM and the chooser, i2t_caption_raw_logprob between the chooser and the finish rule."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
@@ -948,11 +1044,18 @@ class CaptionDecoder(GreedyDecoder):
                                      st.tok_lp)
         else:
             ops.gemm(st.hid, a.W(eng.n_head), st.logits, R, dc.V, d, workspace=st.ws)
+            if proc is not None:
+                pr, P = proc
+                ops.caption_logits_process(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, None if forced is None else forced[1], P, st.N,
+                                           st.suppress, len(pr.suppress), eos, pr.min_new, pr.theta, pr.inv_theta, done, st.raw_lse, st.saved,
+                                           R, dc.V)
             if sampling is None:
                 ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
             else:
                 ops.sample_token_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, sampling.temperature,
                                     sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
+            if proc is not None:                                # the chooser's log-prob was taken on the processed row: the raw one over it
+                ops.caption_raw_logprob(st.ids, st.ids_ld, len_ptr, st.raw_lse, st.saved, st.logits, dc.Vp, done, st.tok_lp, R, dc.V)
         if forced is None:
             ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
         else:
@@ -964,23 +1067,30 @@ class CaptionDecoder(GreedyDecoder):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
-                          use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps') -> GeneratedCaptions:
+                          use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps', repetition_penalty: float = 1.0,
+                          min_new_tokens: int = 0, suppress_tokens=None) -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
         None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
         feeds prompt columns 0 .. Pmin - 2 one prefill replay each; 'pass' takes them through one forward pass per IMAGE
-        (_prefill_pass) and starts the counters behind them -- the full steps, their graphs and everything after are the same."""
+        (_prefill_pass) and starts the counters behind them -- the full steps, their graphs and everything after are the same.
+        ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` (``caption_processors``): with any of them active
+        the step takes the fp32-logits head whatever the decoder's width -- the segment-maxima head cannot see a penalised token's
+        neighbours, so a d % 128 == 0 decoder gives up that head's saving -- with i2t_caption_logits_process before the
+        chooser and i2t_caption_raw_logprob after it, under graph keys of their own; inactive, the call is the one without them."""
         eng = self.eng
         dc = eng.dec
         N = int(num_return_sequences)
         B, P = prompt_ids.shape
         ragged = prompt_lengths is not None
+        procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, vocab=dc.V)
         if ragged:
-            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens)
+            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
             pmin, pmax = int(plen.min()), int(plen.max())
         else:
-            check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
+            check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
             pmin = pmax = P
+        proc = caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, dc.V)
         if not dc.causal:
             raise ValueError('CaptionDecoder needs a causal decoder')
         m, start = prefill_plan(prompt_prefill, pmin, min(eng.enc.ncls, dc.block) if dc.prefixed else 0, dc.fam, True)
@@ -1016,9 +1126,12 @@ class CaptionDecoder(GreedyDecoder):
         start = torch.tensor(start, dtype=torch.int32, device=a.device) if m else st.counters_init
         if sampling is not None:
             _draw_seed(st.seed, sampling.seed)
-        top2, head = self._greedy_head(st, sampling, lse=True)
-        # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key)
-        full_key = ('ragged', head, eos, pad, max_new_tokens) if ragged else (head, eos, pad)
+        if proc is not None:
+            self._processor_state(st, proc)
+        top2, head = self._greedy_head(st, sampling, logits=proc is not None, lse=True)
+        # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key), and
+        # so are the processors' scalars ('proc': never an inactive call's key)
+        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax)
         prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
@@ -1033,7 +1146,8 @@ class CaptionDecoder(GreedyDecoder):
         # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
         # ('pass': those columns' K/V are in the cache already, n_prefill = 0)
         self.last_prefill_steps = n_prefill
-        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced), reset, n_prefill,
+        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced, None if proc is None else (proc, pmax)),
+                                         reset, n_prefill,
                                          pmax - pmin + max_new_tokens, use_graph, poll_every=poll_every if eos is not None else 0)
         lengths = st.lengths.clone()
         L = int(lengths.max().item()) if max_new_tokens else pmax       # the final host sync
@@ -1042,8 +1156,9 @@ class CaptionDecoder(GreedyDecoder):
         return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev)
 
 
-def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int):
-    """the refusals of generate_captions that need no device"""
+def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,
+                       min_new_tokens: int = 0, suppress_tokens=None, vocab: Optional[int] = None):
+    """the refusals of generate_captions that need no device; those of the logits processors are ``caption_processors``'"""
     if N < 1:
         raise ValueError(f'num_return_sequences = {N}: at least one caption per image')
     if sampling is None and N > 1:
@@ -1056,13 +1171,14 @@ def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_ever
         raise ValueError(f'pad_token_id = {pad}')
     if poll_every < 0 or max_new_tokens < 0:
         raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+    caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab)
 
 
 def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: Optional[Sampling], eos, pad, poll_every: int,
-                              max_new_tokens: int) -> np.ndarray:
+                              max_new_tokens: int, **processors) -> np.ndarray:
     """check_caption_args, and the refusals of ``prompt_lengths`` (read on the host, before anything moves to the device): one integer
     per image, 1 <= p_b <= P  -> the lengths, int32 [B]"""
-    check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens)
+    check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **processors)
     if isinstance(prompt_lengths, torch.Tensor):
         if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
             raise ValueError(f'prompt_lengths of dtype {prompt_lengths.dtype}: integers are needed')

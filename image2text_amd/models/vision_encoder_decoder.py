@@ -239,7 +239,7 @@ class VisionEncoderDecoder(nn.Module):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
-                          prompt_prefill='steps'):
+                          prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -273,19 +273,38 @@ class VisionEncoderDecoder(nn.Module):
         (NotImplementedError); a non-causal decoder has no cache and ignores the argument; any other value is a ValueError.
         The text window is ``generate``'s: 1024 cached keys per caption, and on Llama-2 / Qwen2 / Falcon decoders with heads of 64
         or 128 the model's own block (at most 32 768 keys) -- a call past 1024 keys runs on a long cache of its own, and calls that fit the
-        classic window are bit-identical whatever ran before."""
+        classic window are bit-identical whatever ran before.
+        ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` are transformers' RepetitionPenalty ->
+        SuppressTokens -> MinNewTokensLength logits processors, applied in that order on the device to the step's raw fp32 logits row
+        before the chooser's own stages (temperature, n-gram ban, top-k, softmax, nucleus): every DISTINCT token of the row so far,
+        the prompt included, has its logit z multiplied by 1 / penalty if z > 0 and by penalty otherwise; an id in ``suppress_tokens``
+        (one list for all rows; duplicates dropped) is never emitted; ``eos_token_id`` is not emitted before a row has emitted
+        ``min_new_tokens`` tokens, counted per row from its own prompt length (a no-op without an EOS id).  ``token_logprobs`` keeps
+        its definition -- log_softmax of the RAW logits, ``score``'s quantity: the processors do not enter it, so ``rerank`` and
+        ``logprob`` stay comparable between calls with different settings.  At the defaults (or ``suppress_tokens=[]``) the call is the
+        one without these arguments, launch for launch.  With any of them active the step takes the fp32-logits head whatever the
+        decoder's width: a d % 128 == 0 decoder gives up the segment-maxima head's saving, and two small launches join
+        the step.  Refusals (ValueError, before anything runs): a penalty that is not finite or <= 0, ``min_new_tokens`` < 0 or >
+        ``max_new_tokens``, a suppressed id outside the vocabulary, a list that covers the whole vocabulary.  A NON-causal decoder
+        refuses an active processor (NotImplementedError): its re-evaluation loop has no processed step."""
         import numpy as np
-        from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, check_caption_args,
+        from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, caption_processors, check_caption_args,
                                 check_ragged_caption_args, generate_by_recompute, prefill_plan)
         N = int(num_return_sequences)
         sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
         B, P = prompt_ids.shape
+        procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
+                     vocab=self._engine.dec.V)
         if prompt_lengths is None:
-            check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+            check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens, **procs)
             plen, pmin, pmax = None, P, P
         else:
-            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens)
+            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens, **procs)
             pmin, pmax = int(plen.min()), int(plen.max())
+        if not self._engine.dec.causal and caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos_token_id,
+                                                              self._engine.dec.V) is not None:
+            raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens run inside the KV-cache caption step; a non-causal '
+                                      'decoder generates by re-evaluation (generate_by_recompute), which has no processed step')
         prefill_plan(prompt_prefill, pmin, 0, self._engine.dec.fam, self._engine.dec.causal)       # its refusals, before anything runs
         blk_size = self.decoder.block_size - self.space_for_prompt
         if pmax + max_new_tokens > blk_size:
@@ -296,7 +315,8 @@ class VisionEncoderDecoder(nn.Module):
             if self._captioner is None:
                 object.__setattr__(self, '_captioner', CaptionDecoder(self))
             return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
-                                                     prompt_lengths=plen, prompt_prefill=prompt_prefill)
+                                                     prompt_lengths=plen, prompt_prefill=prompt_prefill, repetition_penalty=repetition_penalty,
+                                                     min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
         prompt_rep = prompt_ids.repeat_interleave(N, dim=0)

@@ -879,6 +879,34 @@ def caption_finish_ragged(ids, ids_ld, len_ptr, prompt, plen, N, max_new, eos, p
                                               tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish_ragged')
 
 
+def caption_logits_process(logits, ld, ids, ids_ld, len_ptr, plen, P, N, suppress, n_suppress, eos, min_new, theta, inv_theta, done, raw_lse,
+                           saved, R, V):
+    """the logits processors of a caption step on fp32 logits rows, in place, before the chooser: repetition penalty over
+    ids[r][0 .. len), the suppress list (int32, the first n_suppress entries; None: none), EOS below min_new emitted tokens (plen int32
+    [R / N], or None: every prompt P long); raw_lse [R] and saved [R, >= ids_ld] keep what caption_raw_logprob needs; no write once
+    *done (include/i2t.h::i2t_caption_logits_process).  inv_theta: 1 / theta rounded to fp32 by the caller"""
+    _need_cuda(logits, ids, len_ptr, done, raw_lse, saved)
+    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and saved.dtype == F32
+    assert saved.dim() == 2 and saved.stride(-1) == 1 and saved.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    assert plen is None or (plen.is_cuda and plen.dtype == torch.int32 and plen.is_contiguous() and N >= 1 and plen.numel() >= R // N)
+    assert suppress is None or (suppress.is_cuda and suppress.dtype == torch.int32 and suppress.is_contiguous() and suppress.numel() >= n_suppress)
+    assert suppress is not None or n_suppress == 0
+    _l.check(_lib().i2t_caption_logits_process(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(plen), int(P), int(N), _p(suppress),
+                                               int(n_suppress), -1 if eos is None else int(eos), int(min_new), float(theta), float(inv_theta),
+                                               _p(done), _p(raw_lse), _p(saved), saved.stride(0), R, V), 'i2t_caption_logits_process')
+
+
+def caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, logits, ld, done, tok_lp, R, V):
+    """after the chooser of a processed step: tok_lp[r][len] = raw z[ids[r][len]] - raw_lse[r], the raw logit from ``saved`` when the
+    token occurs in ids[r][0 .. len), else from ``logits``; no write once *done (include/i2t.h::i2t_caption_raw_logprob)"""
+    _need_cuda(ids, len_ptr, raw_lse, saved, logits, done, tok_lp)
+    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and saved.dtype == F32
+    assert tok_lp.dtype == F32 and tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
+    assert saved.dim() == 2 and saved.stride(-1) == 1 and saved.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    _l.check(_lib().i2t_caption_raw_logprob(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(raw_lse), _p(saved), saved.stride(0), _p(logits), ld,
+                                            _p(done), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_raw_logprob')
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     _need_cuda(a, b, stats)

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 10
+#define I2T_ABI_VERSION 11
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -458,6 +458,25 @@ int i2t_caption_finish(void* stream, int64_t* ids, int ids_ld, const int* len_pt
 int i2t_caption_finish_ragged(void* stream, int64_t* ids, int ids_ld, const int* len_ptr, const int64_t* prompt, int prompt_ld,
                               const int* plen, int N, int max_new, int eos, int64_t pad, int* finished, int* lengths, float* tok_lp,
                               int lp_ld, int* ctrl, int R);
+/* The logits processors of a caption step (generate_captions' repetition_penalty / suppress_tokens / min_new_tokens; DESIGN.md 4s,
+ * ABI 11): a pre-pass and a post-pass around the fp32-logits choosers above, which run between them as they are.
+ *   i2t_caption_logits_process (after the lm_head GEMM, before the chooser): returns at once if *done.  Per row r of logits f32
+ *     [R][ld] (ld >= V, ld % 4 == 0, base on 16 bytes), one workgroup: raw_lse[r] = log sum_c exp(z[r][c]) over the RAW row, reduced in
+ *     a fixed order (no atomics); saved[r][j] = the raw z[r][ids[r][j]] for j < len = *len_ptr (saved f32 [R][saved_ld], saved_ld >=
+ *     ids_ld); then, in the order of transformers' RepetitionPenalty -> SuppressTokens -> MinNewTokensLength processors, in place:
+ *     every token t of ids[r][0 .. len) gets z[t] = z[t] > 0 ? z[t] * inv_theta : z[t] * theta, ONCE however often it occurs
+ *     (inv_theta = fp32 1 / theta, formed by the caller: one fp32 multiply per token here); z[t] = -inf for the n_suppress ids of
+ *     suppress (int32, device memory; 0 <= n_suppress < V); z[eos] = -inf while len - p < min_new, p = plen[r / N] (int32 [R / N],
+ *     device memory) or P when plen is null (eos < 0: no rule).  An id outside [0, V) takes no part.
+ *   i2t_caption_raw_logprob (after the chooser, before i2t_caption_finish[_ragged]): returns at once if *done.  With c = ids[r][len]
+ *     the chosen token, tok_lp[r][len] = z_raw[c] - raw_lse[r] over what the chooser wrote there, z_raw[c] = saved[r][j] for a j < len
+ *     with ids[r][j] == c, else logits[r][c] (a column the pre-pass left raw: a suppressed or min-length-banned token is never
+ *     chosen).  So tok_lp keeps the definition above -- the processors do not enter it.  One wave per row. */
+int i2t_caption_logits_process(void* stream, float* logits, int ld, const int64_t* ids, int ids_ld, const int* len_ptr, const int* plen,
+                               int P, int N, const int* suppress, int n_suppress, int eos, int min_new, float theta, float inv_theta,
+                               const int* done, float* raw_lse, float* saved, int saved_ld, int R, int V);
+int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* raw_lse, const float* saved,
+                            int saved_ld, const float* logits, int ld, const int* done, float* tok_lp, int lp_ld, int R, int V);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).

@@ -9,7 +9,15 @@ Two comparisons, each alternating its two forms ROUNDS times in one process afte
   N = 4   generate(images repeated 4 times, 64 tokens, sampling)   vs  generate_captions(images, eos, N = 4, sampling)
 The EOS id is taken from a free run: the token whose first emission, over all rows, comes earliest at the latest row -- the rows of
 random weights do end, if late.  Prints wall time per call (median [min .. max] ms, synchronised), the replays launched, the mean
-length, and the rise of the allocator's peak across a call of each form (decoder state included: measured on a fresh model)."""
+length, and the rise of the allocator's peak across a call of each form (decoder state included: measured on a fresh model).
+
+    python tools/bench_generate_captions.py --repetition-penalty 1.3 [--min-new-tokens 8] [--suppress 0,1,2]
+
+With any of the three flags the comparison is instead: generate_captions as it is against generate_captions with the
+logits processors, greedy N = 1 and sampling N = 4, no EOS id unless --min-new-tokens needs one (50256; every call then runs all
+steps that its rows need), alternating in one process -- first with the segment-maxima head in play (nano-224: d % 128 == 0, so the
+processors also cost the switch to the fp32-logits head), then with I2T_DECODE_TOP2's effect switched off in the process (both forms on
+the fp32-logits head: the difference is the two new launches alone)."""
 import argparse
 import os
 import statistics
@@ -75,13 +83,53 @@ def fmt(ts):
     return f'{statistics.median(ts):8.1f} [{min(ts):.1f} .. {max(ts):.1f}] ms'
 
 
+def processors_comparison(a, procs):
+    from image2text_amd import decoding
+    B, T = a.batch, a.new
+    eos = 50256 if procs.get('min_new_tokens') else None
+    print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {T} new tokens, {a.rounds} alternating rounds; '
+          f'processors {procs}, eos id {eos}', flush=True)
+    for top2 in (True, False):
+        decoding.TOP2_HEAD = top2
+        m, images, prompt = fresh(B)
+        print(f'inactive greedy head: {"segment maxima (the processors switch it to fp32 logits)" if top2 else "fp32 logits (both forms)"}', flush=True)
+        for N, mode in ((1, dict(top_k=1)), (4, SAMPLING)):
+            kw = dict(max_new_tokens=T, eos_token_id=eos, num_return_sequences=N, seed=3, **mode)
+            forms = {'as it is': lambda: m.generate_captions(images, prompt, **kw),
+                     'with processors': lambda: m.generate_captions(images, prompt, **kw, **procs)}
+            ts, replays = {k: [] for k in forms}, {}
+            for fn in forms.values():
+                fn()
+            for _ in range(a.rounds):
+                for k, fn in forms.items():
+                    t, _ = wall(fn)
+                    ts[k].append(t)
+                    replays[k] = m._captioner.last_replays
+            for k in forms:
+                print(f'  N = {N} {"greedy  " if N == 1 else "sampling"} {k:16s} {fmt(ts[k])}   replays {replays[k]}', flush=True)
+        del m
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--new', type=int, default=64)
+    ap.add_argument('--repetition-penalty', type=float, default=None)
+    ap.add_argument('--min-new-tokens', type=int, default=None)
+    ap.add_argument('--suppress', type=str, default=None, help='comma-separated token ids')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_generate_captions.py measures on the MI355X; there is nothing to report without one'
+    procs = {}
+    if a.repetition_penalty is not None:
+        procs['repetition_penalty'] = a.repetition_penalty
+    if a.min_new_tokens is not None:
+        procs['min_new_tokens'] = a.min_new_tokens
+    if a.suppress:
+        procs['suppress_tokens'] = [int(t) for t in a.suppress.split(',') if t.strip()]
+    if procs:
+        return processors_comparison(a, procs)
     B, T = a.batch, a.new
     print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {T} new tokens, {a.rounds} alternating rounds',
           flush=True)
