@@ -654,6 +654,7 @@ static int conv_mfma_dispatch(hipStream_t s, const void* src, int src_layout, in
         else if (nt == 1) LAUNCH_CONV(32, 1, SRC_NHWC_BF16, true, false, true);
         else LAUNCH_CONV(32, 2, SRC_NHWC_BF16, true, false, true);
     } else if (dg && !in_gelu && !dst_nchw && (src_layout == SRC_NCHW_BF16 || src_layout == SRC_NHWC_BF16)) {
+        if (nt != 1) { i2t_set_error("conv6 bwd-data: Cin=%d > 16 unsupported", Cout); return I2T_EINVAL; }
         if (src_layout == SRC_NCHW_BF16) {
             if (cp == 8) LAUNCH_CONV(8, 1, SRC_NCHW_BF16, false, true, false);
             else if (cp == 16) LAUNCH_CONV(16, 1, SRC_NCHW_BF16, false, true, false);
@@ -663,7 +664,6 @@ static int conv_mfma_dispatch(hipStream_t s, const void* src, int src_layout, in
             else if (cp == 16) LAUNCH_CONV(16, 1, SRC_NHWC_BF16, false, true, false);
             else LAUNCH_CONV(32, 1, SRC_NHWC_BF16, false, true, false);
         }
-        if (nt != 1) { i2t_set_error("conv6 bwd-data: Cin=%d > 16 unsupported", Cout); return I2T_EINVAL; }
     } else {
         i2t_set_error("conv6 mfma: unsupported layout combination (src=%d gelu=%d dgelu=%d nchw_out=%d)", src_layout, in_gelu, (int)dg, dst_nchw);
         return I2T_EINVAL;
@@ -722,6 +722,7 @@ extern "C" int i2t_conv6_bwd_data(void* stream, const void* dy, int dy_layout, c
 extern "C" int i2t_conv6_bwd_weight(void* stream, const void* dy, int dy_layout, const void* x, int x_layout, int in_gelu,
                                     float* dw, float* db, float* scratch, int B, int Cin, int Cout, int H, int W) {
     I2T_REQUIRE(dy && x && dw && scratch && B > 0 && Cin <= 16 && Cout <= 32, "i2t_conv6_bwd_weight: bad args");
+    I2T_REQUIRE(dy_layout != SRC_NHWC_BF16 || Cout % 8 == 0, "i2t_conv6_bwd_weight: NHWC dy needs Cout %% 8 == 0");
     hipStream_t s = (hipStream_t)stream;
     const int cp = pad8(Cin), cop = Cout <= 16 ? 16 : 32;
     hipError_t e = hipMemsetAsync(scratch, 0, sizeof(float) * (size_t)cop * NTAP * cp, s);
@@ -751,7 +752,6 @@ extern "C" int i2t_conv6_bwd_weight(void* stream, const void* dy, int dy_layout,
         ok = false;
     }
     I2T_REQUIRE(ok, "i2t_conv6_bwd_weight: unsupported layout combination (x_layout=%d gelu=%d Cin=%d)", x_layout, in_gelu, Cin);
-    I2T_REQUIRE(dy_layout != SRC_NHWC_BF16 || Cout % 8 == 0, "i2t_conv6_bwd_weight: NHWC dy needs Cout %% 8 == 0");
     hipLaunchKernelGGL(conv_fold_dw_kernel, dim3(32), dim3(256), 0, s, scratch, dw, Cout, Cin, cp);
     I2T_CHECK_LAUNCH("i2t_conv6_bwd_weight");
     return I2T_OK;
