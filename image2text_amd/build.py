@@ -17,7 +17,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'gemm_route.h'),
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'attention_route.h'), os.path.join(CSRC, 'gemm_route.h'),
                                                       os.path.join(CSRC, '..', '..', 'include', 'i2t.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -38,7 +38,7 @@ def _build(verbose: bool, force_all: bool = False) -> str:
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objs = []
     procs = []
-    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'gemm_route.h'), os.path.join(CSRC, '..', '..', 'include', 'i2t.h'),
+    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'attention_route.h'), os.path.join(CSRC, 'gemm_route.h'), os.path.join(CSRC, '..', '..', 'include', 'i2t.h'),
                os.path.abspath(__file__)]
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -17,6 +17,7 @@
 // (O^T[d][q] = V^T[d][key] . P^T[key][q]) with the key order permuted identically on the V^T side (the transposed
 // LDS read takes any 4-row set) -- cdna_hip_programming.md 3, "An accumulator tile as the next MFMA's operand".
 #include "attention_common.h"
+#include "attention_route.h"
 #include <stdlib.h>
 
 namespace {
@@ -738,8 +739,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
 // walks the resident one in 64-row steps, so an LDS fragment serves 4 MFMAs instead of 1.  The row blocks that do not divide by
 // the 4 waves (T = 260: block 17 holds 4 rows) are shared by all waves ACROSS the resident operand -- every wave takes a quarter
 // of its rows -- and combined through LDS (split softmax: (m, l, O) partials), so no wave carries a fifth block.
-constexpr int V2_MAXROWS = 288, V2_RB = 128, V2_NQB = 4;
-constexpr int V2_MAX_OTHER = 16 * (4 * V2_NQB + 3);                    // 304 rows of the per-wave operand
+using i2t::V2_MAXROWS, i2t::V2_RB, i2t::V2_NQB, i2t::V2_MAX_OTHER;     // attention_route.h: the route reads the same limits
 
 __device__ __forceinline__ void v2_stage2(unsigned char* la, unsigned char* lb, const bf16_t* a, int a_rs, const bf16_t* b, int b_rs,
                                           int nrows, int rows_pad, int tid) {
@@ -1483,23 +1483,13 @@ __global__ __launch_bounds__(64 * NWV, 1) void attn_bwd3_kernel(AttnPtr Q, AttnP
 #undef B3_ARGS
 }
 
-// the resident-operand kernels cover dense, non-causal calls whose operands fit (the encoders); I2T_ATTN_V2=0 keeps the tiled ones
-bool v2_applies(int Tq, int Tk, int causal, const int* cu_q, const int* cu_k, unsigned drop_thr) {
-    const char* e = getenv("I2T_ATTN_V2");                               // read per call: tests switch it inside one process
-    const bool on = !(e && e[0] == '0');
-    // (with dropout the 4 consecutive keys of a lane must be the 4 bytes of one hash: Tk % 4 == 0)
-    return on && !causal && !cu_q && !cu_k && Tk <= V2_MAXROWS && Tq >= 64 && Tq <= V2_MAX_OTHER && (!drop_thr || (Tk & 3) == 0);
+// Every I2T_* variable of the attention host code (attention_route.h says what each one selects), read per call: tests switch them
+// inside one process.
+i2t::AttnKnobs attn_knobs() {
+    const auto zero = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+    const auto number = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    return {!zero("I2T_ATTN_V2"), number("I2T_ATTN_BWD", 3), !zero("I2T_ATTN_BWD2"), !zero("I2T_ATTN_BWD1"), number("I2T_ATTN_BWD3_WAVES", 0)};
 }
-
-// variant of a kernel template <bool DROP, bool EVEN> for this call (EVEN = Tk % 4 == 0; only matters with dropout)
-#define ATTN_DISPATCH(KERNEL, drop_thr, Tk, ...)                                   \
-    do {                                                                           \
-        if (!(drop_thr)) hipLaunchKernelGGL((KERNEL<false, true>), __VA_ARGS__);   \
-        else if (((Tk) & 3) == 0) hipLaunchKernelGGL((KERNEL<true, true>), __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<true, false>), __VA_ARGS__);               \
-    } while (0)
-
-bool strides_ok(const void* p, long bs, int rs) { return p && ALIGNED16(p) && (bs % 8 == 0) && (rs % 8 == 0) && rs >= 64; }
 
 }  // namespace
 
@@ -1507,33 +1497,27 @@ extern "C" int i2t_attention_fwd(void* stream, const void* q, long q_bs, int q_r
                                  const void* v, long v_bs, int v_rs, void* o, long o_bs, int o_rs, float* lse, int B,
                                  int H, int Tq, int Tk, int causal, unsigned drop_key, unsigned drop_thr, float drop_scale,
                                  const int* cu_q, const int* cu_k, int total_q) {
-    I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * Tk < 4294967296.0, "i2t_attention_fwd: dropout index overflows 32 bits");
-    I2T_REQUIRE(!cu_q || total_q > 0, "i2t_attention_fwd: packed queries need total_q");
-    I2T_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0, "i2t_attention_fwd: empty problem");
-    I2T_REQUIRE(strides_ok(q, q_bs, q_rs) && strides_ok(k, k_bs, k_rs) && strides_ok(v, v_bs, v_rs) &&
-                    strides_ok(o, o_bs, o_rs),
-                "i2t_attention_fwd: operands must be 16-byte aligned with strides that are multiples of 8");
-    I2T_REQUIRE(!causal || Tk >= Tq, "i2t_attention_fwd: causal needs Tk >= Tq");
-    I2T_REQUIRE((double)((Tq + 63) / 64) * H * B < 2147483647.0, "i2t_attention_fwd: grid too large");
+    const i2t::AttnCall c{B, H, H, 64, Tq, Tk, causal, cu_q || cu_k, drop_thr != 0, false, 0, 0};
+    if (int rc = attn_check("i2t_attention_fwd", c, false, false, cu_q, total_q, true,
+                            {{q, q_bs, q_rs, 64}, {k, k_bs, k_rs, 64}, {v, v_bs, v_rs, 64}, {o, o_bs, o_rs, 64}}))
+        return rc;
+    const i2t::AttnFwdRoute r = i2t::attn_fwd_route(c, attn_knobs());
+    hipStream_t s = (hipStream_t)stream;
     AttnPtr Q{(const bf16_t*)q, q_bs, q_rs}, K{(const bf16_t*)k, k_bs, k_rs}, V{(const bf16_t*)v, v_bs, v_rs};
-    if (v2_applies(Tq, Tk, causal, cu_q, cu_k, drop_thr)) {
-#define V2_FWD(PER)                                                                                                                  \
-    case PER:                                                                                                                        \
-        if (!drop_thr) hipLaunchKernelGGL((attn_fwd2_kernel<false, PER>), dim3(H * B), dim3(256), 0, (hipStream_t)stream, Q, K, V,   \
-                                          (bf16_t*)o, o_bs, o_rs, lse, H, Tq, Tk, drop_key, drop_thr, drop_scale);                   \
-        else hipLaunchKernelGGL((attn_fwd2_kernel<true, PER>), dim3(H * B), dim3(256), 0, (hipStream_t)stream, Q, K, V,              \
-                                (bf16_t*)o, o_bs, o_rs, lse, H, Tq, Tk, drop_key, drop_thr, drop_scale);                             \
-        break;
-        switch (((Tq + 15) >> 4) >> 2) {
-            V2_FWD(1) V2_FWD(2) V2_FWD(3) V2_FWD(4)
-        }
-#undef V2_FWD
+    if (r.kind == i2t::AttnFwdKind::Fwd2) {
+        with_constant<1, 2, 3, 4>(r.per, [&](auto PER) {
+            with_constant<false, true>(r.drop != i2t::AttnDrop::None, [&](auto DROP) {
+                hipLaunchKernelGGL((attn_fwd2_kernel<decltype(DROP)::value, decltype(PER)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V,
+                                   (bf16_t*)o, o_bs, o_rs, lse, H, Tq, Tk, drop_key, drop_thr, drop_scale);
+            });
+        });
         I2T_CHECK_LAUNCH("i2t_attention_fwd(v2)");
         return I2T_OK;
     }
-    dim3 grid(((Tq + 63) / 64) * H * B);
-    ATTN_DISPATCH(attn_fwd_kernel, drop_thr, Tk, grid, dim3(256), 0, (hipStream_t)stream, Q, K, V, (bf16_t*)o, o_bs, o_rs, lse, H,
-                  Tq, Tk, causal, drop_key, drop_thr, drop_scale, VarLen{cu_q, cu_k, total_q, B});
+    with_drop_variant(r.drop, [&](auto DROP, auto EVEN) {
+        hipLaunchKernelGGL((attn_fwd_kernel<decltype(DROP)::value, decltype(EVEN)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V, (bf16_t*)o,
+                           o_bs, o_rs, lse, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, VarLen{cu_q, cu_k, total_q, B});
+    });
     I2T_CHECK_LAUNCH("i2t_attention_fwd");
     return I2T_OK;
 }
@@ -1557,68 +1541,57 @@ extern "C" int i2t_attention_bwd_ex(void* stream, const void* q, long q_bs, int 
                                     int B, int H, int Tq, int Tk, int causal, unsigned drop_key, unsigned drop_thr, float drop_scale,
                                     const int* cu_q, const int* cu_k, int total_q, unsigned out_drop_key, unsigned out_drop_thr,
                                     float out_drop_scale, int out_drop_q_seq) {
-    if (out_drop_q_seq == Tq || !out_drop_thr) out_drop_q_seq = 0;
-    I2T_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0 && lse && delta_ws, "i2t_attention_bwd: bad args");
-    I2T_REQUIRE(!cu_q || total_q > 0, "i2t_attention_bwd: packed queries need total_q");
-    I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * Tk < 4294967296.0, "i2t_attention_bwd: dropout index overflows 32 bits");
-    I2T_REQUIRE(strides_ok(q, q_bs, q_rs) && strides_ok(k, k_bs, k_rs) && strides_ok(v, v_bs, v_rs) &&
-                    strides_ok(o, o_bs, o_rs) && strides_ok(d_o, do_bs, do_rs) && strides_ok(dq, dq_bs, dq_rs) &&
-                    strides_ok(dk, dk_bs, dk_rs) && strides_ok(dv, dv_bs, dv_rs),
-                "i2t_attention_bwd: operands must be 16-byte aligned with strides that are multiples of 8");
-    I2T_REQUIRE(!causal || Tk >= Tq, "i2t_attention_bwd: causal needs Tk >= Tq");
-    I2T_REQUIRE((double)((Tq + 63) / 64 + (Tk + 63) / 64) * H * B < 2147483647.0, "i2t_attention_bwd: grid too large");
+    const i2t::AttnCall c{B, H, H, 64, Tq, Tk, causal, cu_q || cu_k, drop_thr != 0, out_drop_thr != 0, out_drop_q_seq, 0};
+    if (int rc = attn_check("i2t_attention_bwd", c, false, true, cu_q, total_q, lse && delta_ws,
+                            {{q, q_bs, q_rs, 64}, {k, k_bs, k_rs, 64}, {v, v_bs, v_rs, 64}, {o, o_bs, o_rs, 64}, {d_o, do_bs, do_rs, 64},
+                             {dq, dq_bs, dq_rs, 64}, {dk, dk_bs, dk_rs, 64}, {dv, dv_bs, dv_rs, 64}}))
+        return rc;
+    const i2t::AttnBwdRoute r = i2t::attn_bwd_route(c, attn_knobs());
+    I2T_REQUIRE(r.q_seq_ok, "i2t_attention_bwd_ex: out_drop_q_seq=%d is offered by the one-pass resident kernel only (dense, Tk <= %d)", r.q_seq, V2_MAXROWS);
+    const bool drop = r.drop != i2t::AttnDrop::None;
     hipStream_t s = (hipStream_t)stream;
     AttnPtr Q{(const bf16_t*)q, q_bs, q_rs}, K{(const bf16_t*)k, k_bs, k_rs}, V{(const bf16_t*)v, v_bs, v_rs};
     AttnPtr DO{(const bf16_t*)d_o, do_bs, do_rs};
     const VarLen vl{cu_q, cu_k, total_q, B};
     const AttnPtr Ow{(const bf16_t*)o, o_bs, o_rs};
-    // I2T_ATTN_BWD = 3 (default): the one-pass kernel | 2: the two-phase one (attn_bwd2) | 0: the tiled pair; I2T_ATTN_BWD2=0: as 0
-    const char* be = getenv("I2T_ATTN_BWD");
-    const int bmode = (getenv("I2T_ATTN_BWD2") && getenv("I2T_ATTN_BWD2")[0] == '0') ? 0 : (be ? atoi(be) : 3);
-    I2T_REQUIRE(!out_drop_q_seq || (bmode == 3 && v2_applies(Tq, Tk, causal, cu_q, cu_k, drop_thr) && Tq <= V2_MAXROWS),
-                "i2t_attention_bwd_ex: out_drop_q_seq=%d is offered by the one-pass resident kernel only (dense, Tk <= %d)", out_drop_q_seq, V2_MAXROWS);
-    if (bmode == 3 && v2_applies(Tq, Tk, causal, cu_q, cu_k, drop_thr) && Tq <= V2_MAXROWS) {
-        // 9 waves whenever 8 would leave a wave with a third key block (I2T_ATTN_BWD3_WAVES = 8 | 9 forces one: A/B runs)
-        const char* we = getenv("I2T_ATTN_BWD3_WAVES");
-        const int nkb = (Tk + 15) >> 4;
-        const bool nine = we && atoi(we) == 9;      // measured (B = 1024, T = 260, dropout): 1295 us against 1228 for 8 waves -- the third register-limited
-        // wave of a SIMD and its spills cost more than wave 0's third block: off unless asked for
-        (void)nkb;
-#define B3_LAUNCH(D_, W_) hipLaunchKernelGGL((attn_bwd3_kernel<D_, W_>), dim3(H * B), dim3(64 * W_), 0, s, Q, K, V, DO, Ow, lse, (bf16_t*)dq, dq_bs, dq_rs, \
-                                             (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, drop_key, drop_thr, drop_scale,          \
-                                             out_drop_key, out_drop_thr, out_drop_scale, out_drop_q_seq)
-        if (!drop_thr) { if (nine) B3_LAUNCH(false, 9); else B3_LAUNCH(false, 8); }
-        else { if (nine) B3_LAUNCH(true, 9); else B3_LAUNCH(true, 8); }
-#undef B3_LAUNCH
+    switch (r.kind) {
+    case i2t::AttnBwdKind::Bwd3:
+        with_constant<false, true>(drop, [&](auto DROP) {
+            with_constant<9, 8>(r.nwv, [&](auto NWV) {
+                hipLaunchKernelGGL((attn_bwd3_kernel<decltype(DROP)::value, decltype(NWV)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V, DO, Ow, lse,
+                                   (bf16_t*)dq, dq_bs, dq_rs, (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, drop_key, drop_thr, drop_scale,
+                                   out_drop_key, out_drop_thr, out_drop_scale, r.q_seq);
+            });
+        });
         I2T_CHECK_LAUNCH("i2t_attention_bwd(v3)");
         return I2T_OK;
-    }
-    if (bmode != 0 && v2_applies(Tq, Tk, causal, cu_q, cu_k, drop_thr) && Tq <= V2_MAXROWS) {
-        if (!drop_thr) hipLaunchKernelGGL((attn_bwd2_kernel<false>), dim3(H * B), dim3(512), 0, s, Q, K, V, DO, Ow, lse, (bf16_t*)dq, dq_bs, dq_rs,
-                                          (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, drop_key, drop_thr, drop_scale,
-                                          out_drop_key, out_drop_thr, out_drop_scale);
-        else hipLaunchKernelGGL((attn_bwd2_kernel<true>), dim3(H * B), dim3(512), 0, s, Q, K, V, DO, Ow, lse, (bf16_t*)dq, dq_bs, dq_rs,
-                                (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, drop_key, drop_thr, drop_scale,
-                                out_drop_key, out_drop_thr, out_drop_scale);
+    case i2t::AttnBwdKind::Bwd2:
+        with_constant<false, true>(drop, [&](auto DROP) {
+            hipLaunchKernelGGL((attn_bwd2_kernel<decltype(DROP)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V, DO, Ow, lse, (bf16_t*)dq, dq_bs, dq_rs,
+                               (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, drop_key, drop_thr, drop_scale, out_drop_key, out_drop_thr,
+                               out_drop_scale);
+        });
         I2T_CHECK_LAUNCH("i2t_attention_bwd(v2)");
         return I2T_OK;
+    case i2t::AttnBwdKind::Bwd1:
+        with_drop_variant(r.drop, [&](auto DROP, auto EVEN) {
+            hipLaunchKernelGGL((attn_bwd1_kernel<decltype(DROP)::value, decltype(EVEN)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V, DO, Ow, lse,
+                               (bf16_t*)dq, dq_bs, dq_rs, (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, causal, drop_key, drop_thr,
+                               drop_scale, vl, out_drop_key, out_drop_thr, out_drop_scale);
+        });
+        I2T_CHECK_LAUNCH("i2t_attention_bwd(1)");
+        return I2T_OK;
+    case i2t::AttnBwdKind::Pair:
+        break;
     }
-    {   // one tile of queries and keys (the decoder's attentions): the fused single-pass kernel (I2T_ATTN_BWD1=0: the tiled pair, for A/B runs)
-        const char* e1 = getenv("I2T_ATTN_BWD1");
-        if (Tq <= 64 && Tk <= 64 && !(e1 && e1[0] == '0')) {
-            ATTN_DISPATCH(attn_bwd1_kernel, drop_thr, Tk, dim3(H * B), dim3(256), 0, s, Q, K, V, DO, Ow, lse, (bf16_t*)dq, dq_bs, dq_rs,
-                          (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, vl,
-                          out_drop_key, out_drop_thr, out_drop_scale);
-            I2T_CHECK_LAUNCH("i2t_attention_bwd(1)");
-            return I2T_OK;
-        }
-    }
-    ATTN_DISPATCH(attn_bwd_dq_kernel, drop_thr, Tk, dim3(((Tq + 63) / 64) * H * B), dim3(256), 0, s, Q, K, V, DO, Ow, lse, delta_ws,
-                  (bf16_t*)dq, dq_bs, dq_rs, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, vl, out_drop_key, out_drop_thr,
-                  out_drop_scale);
-    ATTN_DISPATCH(attn_bwd_dkv_kernel, drop_thr, Tk, dim3(((Tk + 63) / 64) * H * B), dim3(256), 0, s, Q, K, V, DO, lse, delta_ws,
-                  (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, vl,
-                  out_drop_key, out_drop_thr, out_drop_scale);
+    with_drop_variant(r.drop, [&](auto DROP, auto EVEN) {
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<decltype(DROP)::value, decltype(EVEN)::value>), dim3(r.grid), dim3(r.block), 0, s, Q, K, V, DO, Ow, lse,
+                           delta_ws, (bf16_t*)dq, dq_bs, dq_rs, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, vl, out_drop_key, out_drop_thr,
+                           out_drop_scale);
+        hipLaunchKernelGGL((attn_bwd_dkv_kernel<decltype(DROP)::value, decltype(EVEN)::value>), dim3(r.grid_dkv), dim3(r.block), 0, s, Q, K, V, DO, lse,
+                           delta_ws, (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, H, Tq, Tk, causal, drop_key, drop_thr, drop_scale, vl,
+                           out_drop_key, out_drop_thr, out_drop_scale);
+    });
     I2T_CHECK_LAUNCH("i2t_attention_bwd");
     return I2T_OK;
 }

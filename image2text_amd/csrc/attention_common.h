@@ -1,6 +1,9 @@
 // Pieces shared by the head_dim-64 attention kernels (attention.hip) and the grouped-query / any-head-dim ones (attention_g.hip).
 #pragma once
 #include "common.h"
+#include "attention_route.h"
+#include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -59,6 +62,56 @@ __device__ __forceinline__ void attn_block_coords(int ntile, int H, int B, int& 
     }
     h = pair % H;
     b = pair / H;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host side
+// Each entry point validates (attn_check), describes the call (i2t::AttnCall), asks attention_route.h and launches what it says.
+
+struct AttnOperand {
+    const void* p;
+    long bs;
+    int rs, min_rs;           // min_rs: the columns a row must cover (64-wide path: 64; grouped path: heads x head width)
+};
+
+// The argument checks of the four entry points, stated once.  grouped: the any-head-width path (it also checks the head counts and
+// the head width, and its rows must cover every head); backward: lse and the delta workspace (`stats`) are required.  The forward
+// of the 64-wide path launches query tiles only, every other call also key tiles: hence the two grid sizes.
+inline int attn_check(const char* who, const i2t::AttnCall& c, bool grouped, bool backward, const int* cu_q, int total_q, bool stats,
+                      std::initializer_list<AttnOperand> operands) {
+    I2T_REQUIRE(c.split == 0 || (!c.causal && !c.packed && c.Tq == c.Tk && c.split < c.Tq), "%s: split needs dense non-causal self-attention", who);
+    const bool some = c.B > 0 && c.H > 0 && c.Hkv > 0 && c.Tq > 0 && c.Tk > 0;
+    if (backward && !grouped) I2T_REQUIRE(some && stats, "%s: bad args", who);
+    else I2T_REQUIRE(some, "%s: empty problem", who);
+    if (grouped) {
+        I2T_REQUIRE(c.H % c.Hkv == 0, "%s: H = %d is not a multiple of H_kv = %d", who, c.H, c.Hkv);
+        I2T_REQUIRE(c.hd == 16 || c.hd == 32 || c.hd == 64 || c.hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", who, c.hd);
+    }
+    I2T_REQUIRE(!cu_q || total_q > 0, "%s: packed queries need total_q", who);
+    I2T_REQUIRE(!c.drop || (double)c.B * c.H * c.Tq * c.Tk < 4294967296.0, "%s: dropout index overflows 32 bits", who);
+    I2T_REQUIRE(!c.causal || c.Tk >= c.Tq, "%s: causal needs Tk >= Tq", who);
+    const int tiles = (c.Tq + 63) / 64 + (grouped || backward ? (c.Tk + 63) / 64 : 0);
+    I2T_REQUIRE((double)tiles * c.H * c.B < 2147483647.0, "%s: grid too large", who);
+    if (grouped && backward) I2T_REQUIRE(stats, "%s: lse and the delta workspace are required", who);
+    bool ok = true;
+    for (const AttnOperand& o : operands) ok = ok && o.p && ALIGNED16(o.p) && (o.bs % 8 == 0) && (o.rs % 8 == 0) && o.rs >= o.min_rs;
+    I2T_REQUIRE(ok, grouped ? "%s: operands must be 16-byte aligned with strides that are multiples of 8 and cover every head"
+                            : "%s: operands must be 16-byte aligned with strides that are multiples of 8", who);
+    return I2T_OK;
+}
+
+// A runtime value as a template argument: calls f(std::integral_constant<T, V>{}) for the V of the list that equals v (none: no call).
+// A kernel template is launched inside a generic lambda, with decltype(arg)::value as its template arguments.
+template <auto... Vs, class T, class F>
+inline void with_constant(T v, F&& f) {
+    (void)((v == Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+}
+
+// f(DROP, EVEN) for the <bool DROP, bool EVEN> variant of a tiled 64-wide kernel (EVEN = Tk % 4 == 0; only matters with dropout)
+template <class F>
+inline void with_drop_variant(i2t::AttnDrop d, F&& f) {
+    with_constant<i2t::AttnDrop::None, i2t::AttnDrop::Even, i2t::AttnDrop::Odd>(d, [&](auto V) {
+        f(std::bool_constant<decltype(V)::value != i2t::AttnDrop::None>{}, std::bool_constant<decltype(V)::value != i2t::AttnDrop::Odd>{});
+    });
 }
 
 }  // namespace

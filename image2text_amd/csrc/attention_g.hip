@@ -11,6 +11,7 @@
 // (key tile, kv head) walks the query tiles of all G heads back to back and accumulates in registers -- no atomics, no second
 // pass, and K / V are loaded once per workgroup.
 #include "attention_common.h"
+#include "attention_route.h"
 
 namespace {
 
@@ -495,31 +496,10 @@ __global__ __launch_bounds__(256) void gattn_bwd_dkv_kernel(AttnPtr Q, AttnPtr K
     }
 }
 
-#define GATTN_DISPATCH(KERNEL, hd, drop_thr, ...)                                                    \
-    do {                                                                                             \
-        if ((hd) <= 32) {                                                                            \
-            if (drop_thr) hipLaunchKernelGGL((KERNEL<32, true>), __VA_ARGS__);                       \
-            else hipLaunchKernelGGL((KERNEL<32, false>), __VA_ARGS__);                               \
-        } else if ((hd) == 64) {                                                                     \
-            if (drop_thr) hipLaunchKernelGGL((KERNEL<64, true>), __VA_ARGS__);                       \
-            else hipLaunchKernelGGL((KERNEL<64, false>), __VA_ARGS__);                               \
-        } else {                                                                                     \
-            if (drop_thr) hipLaunchKernelGGL((KERNEL<128, true>), __VA_ARGS__);                      \
-            else hipLaunchKernelGGL((KERNEL<128, false>), __VA_ARGS__);                              \
-        }                                                                                            \
-    } while (0)
-
-bool g_strides_ok(const void* p, long bs, int rs, int width) { return p && ALIGNED16(p) && (bs % 8 == 0) && (rs % 8 == 0) && rs >= width; }
-
-int g_check(const char* who, int B, int H, int Hkv, int hd, int Tq, int Tk, int causal, unsigned drop_thr, const int* cu_q, int total_q) {
-    I2T_REQUIRE(B > 0 && H > 0 && Hkv > 0 && Tq > 0 && Tk > 0, "%s: empty problem", who);
-    I2T_REQUIRE(H % Hkv == 0, "%s: H = %d is not a multiple of H_kv = %d", who, H, Hkv);
-    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", who, hd);
-    I2T_REQUIRE(!cu_q || total_q > 0, "%s: packed queries need total_q", who);
-    I2T_REQUIRE(drop_thr == 0 || (double)B * H * Tq * Tk < 4294967296.0, "%s: dropout index overflows 32 bits", who);
-    I2T_REQUIRE(!causal || Tk >= Tq, "%s: causal needs Tk >= Tq", who);
-    I2T_REQUIRE((double)((Tq + 63) / 64 + (Tk + 63) / 64) * H * B < 2147483647.0, "%s: grid too large", who);
-    return I2T_OK;
+// f(D, DROP) for the <int D, bool DROP> instantiation the route names
+template <class F>
+void with_gq_variant(const i2t::GqRoute& r, F&& f) {
+    with_constant<32, 64, 128>(r.d, [&](auto D) { with_constant<true, false>(r.drop, [&](auto DROP) { f(D, DROP); }); });
 }
 
 }  // namespace
@@ -528,15 +508,18 @@ extern "C" int i2t_gq_attention_fwd(void* stream, const void* q, long q_bs, int 
                                     long v_bs, int v_rs, void* o, long o_bs, int o_rs, float* lse, int B, int H, int Hkv, int hd, int Tq,
                                     int Tk, int causal, unsigned drop_key, unsigned drop_thr, float drop_scale, const int* cu_q,
                                     const int* cu_k, int total_q, int split) {
-    I2T_REQUIRE(split == 0 || (!causal && !cu_q && !cu_k && Tq == Tk && split < Tq), "i2t_gq_attention_fwd: split needs dense non-causal self-attention");
-    if (int rc = g_check("i2t_gq_attention_fwd", B, H, Hkv, hd, Tq, Tk, causal, drop_thr, cu_q, total_q)) return rc;
-    I2T_REQUIRE(g_strides_ok(q, q_bs, q_rs, H * hd) && g_strides_ok(k, k_bs, k_rs, Hkv * hd) && g_strides_ok(v, v_bs, v_rs, Hkv * hd) &&
-                    g_strides_ok(o, o_bs, o_rs, H * hd),
-                "i2t_gq_attention_fwd: operands must be 16-byte aligned with strides that are multiples of 8 and cover every head");
+    const i2t::AttnCall c{B, H, Hkv, hd, Tq, Tk, causal, cu_q || cu_k, drop_thr != 0, false, 0, split};
+    const int wq = H * hd, wkv = Hkv * hd;
+    if (int rc = attn_check("i2t_gq_attention_fwd", c, true, false, cu_q, total_q, true,
+                            {{q, q_bs, q_rs, wq}, {k, k_bs, k_rs, wkv}, {v, v_bs, v_rs, wkv}, {o, o_bs, o_rs, wq}}))
+        return rc;
+    const i2t::GqRoute r = i2t::gq_route(c);
     AttnPtr Q{(const bf16_t*)q, q_bs, q_rs}, K{(const bf16_t*)k, k_bs, k_rs}, V{(const bf16_t*)v, v_bs, v_rs};
     const GShape sh{H, H / Hkv, hd, Tq, Tk, causal, split, 1.0f / sqrtf((float)hd), drop_key, drop_thr, drop_scale};
-    GATTN_DISPATCH(gattn_fwd_kernel, hd, drop_thr, dim3(((Tq + 63) / 64) * H * B), dim3(256), 0, (hipStream_t)stream, Q, K, V, (bf16_t*)o,
-                   o_bs, o_rs, lse, sh, VarLen{cu_q, cu_k, total_q, B});
+    with_gq_variant(r, [&](auto D, auto DROP) {
+        hipLaunchKernelGGL((gattn_fwd_kernel<decltype(D)::value, decltype(DROP)::value>), dim3(r.grid_q), dim3(r.block), 0, (hipStream_t)stream, Q, K, V,
+                           (bf16_t*)o, o_bs, o_rs, lse, sh, VarLen{cu_q, cu_k, total_q, B});
+    });
     I2T_CHECK_LAUNCH("i2t_gq_attention_fwd");
     return I2T_OK;
 }
@@ -547,22 +530,25 @@ extern "C" int i2t_gq_attention_bwd(void* stream, const void* q, long q_bs, int 
                                     void* dv, long dv_bs, int dv_rs, int B, int H, int Hkv, int hd, int Tq, int Tk, int causal,
                                     unsigned drop_key, unsigned drop_thr, float drop_scale, const int* cu_q, const int* cu_k, int total_q,
                                     unsigned out_drop_key, unsigned out_drop_thr, float out_drop_scale) {
-    if (int rc = g_check("i2t_gq_attention_bwd", B, H, Hkv, hd, Tq, Tk, causal, drop_thr, cu_q, total_q)) return rc;
-    I2T_REQUIRE(lse && delta_ws, "i2t_gq_attention_bwd: lse and the delta workspace are required");
-    I2T_REQUIRE(g_strides_ok(q, q_bs, q_rs, H * hd) && g_strides_ok(k, k_bs, k_rs, Hkv * hd) && g_strides_ok(v, v_bs, v_rs, Hkv * hd) &&
-                    g_strides_ok(o, o_bs, o_rs, H * hd) && g_strides_ok(d_o, do_bs, do_rs, H * hd) && g_strides_ok(dq, dq_bs, dq_rs, H * hd) &&
-                    g_strides_ok(dk, dk_bs, dk_rs, Hkv * hd) && g_strides_ok(dv, dv_bs, dv_rs, Hkv * hd),
-                "i2t_gq_attention_bwd: operands must be 16-byte aligned with strides that are multiples of 8 and cover every head");
+    const i2t::AttnCall c{B, H, Hkv, hd, Tq, Tk, causal, cu_q || cu_k, drop_thr != 0, out_drop_thr != 0, 0, 0};
+    const int wq = H * hd, wkv = Hkv * hd;
+    if (int rc = attn_check("i2t_gq_attention_bwd", c, true, true, cu_q, total_q, lse && delta_ws,
+                            {{q, q_bs, q_rs, wq}, {k, k_bs, k_rs, wkv}, {v, v_bs, v_rs, wkv}, {o, o_bs, o_rs, wq}, {d_o, do_bs, do_rs, wq},
+                             {dq, dq_bs, dq_rs, wq}, {dk, dk_bs, dk_rs, wkv}, {dv, dv_bs, dv_rs, wkv}}))
+        return rc;
+    const i2t::GqRoute r = i2t::gq_route(c);
     hipStream_t s = (hipStream_t)stream;
     AttnPtr Q{(const bf16_t*)q, q_bs, q_rs}, K{(const bf16_t*)k, k_bs, k_rs}, V{(const bf16_t*)v, v_bs, v_rs};
     AttnPtr DO{(const bf16_t*)d_o, do_bs, do_rs}, Ow{(const bf16_t*)o, o_bs, o_rs};
     const VarLen vl{cu_q, cu_k, total_q, B};
     const GShape sh{H, H / Hkv, hd, Tq, Tk, causal, 0, 1.0f / sqrtf((float)hd), drop_key, drop_thr, drop_scale};
     const GOutDrop od{out_drop_key, out_drop_thr, out_drop_scale};
-    GATTN_DISPATCH(gattn_bwd_dq_kernel, hd, drop_thr, dim3(((Tq + 63) / 64) * H * B), dim3(256), 0, s, Q, K, V, DO, Ow, lse, delta_ws,
-                   (bf16_t*)dq, dq_bs, dq_rs, sh, vl, od);
-    GATTN_DISPATCH(gattn_bwd_dkv_kernel, hd, drop_thr, dim3(((Tk + 63) / 64) * Hkv * B), dim3(256), 0, s, Q, K, V, DO, lse, delta_ws,
-                   (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, sh, vl, od);
+    with_gq_variant(r, [&](auto D, auto DROP) {
+        hipLaunchKernelGGL((gattn_bwd_dq_kernel<decltype(D)::value, decltype(DROP)::value>), dim3(r.grid_q), dim3(r.block), 0, s, Q, K, V, DO, Ow, lse,
+                           delta_ws, (bf16_t*)dq, dq_bs, dq_rs, sh, vl, od);
+        hipLaunchKernelGGL((gattn_bwd_dkv_kernel<decltype(D)::value, decltype(DROP)::value>), dim3(r.grid_dkv), dim3(r.block), 0, s, Q, K, V, DO, lse,
+                           delta_ws, (bf16_t*)dk, dk_bs, dk_rs, (bf16_t*)dv, dv_bs, dv_rs, sh, vl, od);
+    });
     I2T_CHECK_LAUNCH("i2t_gq_attention_bwd");
     return I2T_OK;
 }

@@ -286,7 +286,8 @@ def attention_bwd(q, k, v, o, do, lse, delta_ws, dq, dk, dv, B, H, Tq, Tk, causa
 
 def attention_bwd_takes_q_seq(Tq: int, Tk: int, drop) -> bool:
     """whether a dense, non-causal attention_bwd of these sizes runs on the one-pass resident-operand kernel, the only one that takes
-    out_drop_q_seq (the rule of csrc/attention.hip::v2_applies + the default I2T_ATTN_BWD mode; the C side refuses loudly otherwise)"""
+    out_drop_q_seq: csrc/attention_route.h::attn_bwd_route says attn_bwd3_kernel (tests/test_attention_route_cpu.py holds the two
+    together over every size up to 320 and every switch; the C side refuses loudly otherwise)"""
     if os.environ.get('I2T_ATTN_V2', '1')[:1] == '0' or os.environ.get('I2T_ATTN_BWD2', '1')[:1] == '0' or os.environ.get('I2T_ATTN_BWD', '3') != '3':
         return False
     return 64 <= Tq <= 288 and Tk <= 288 and (drop is None or Tk % 4 == 0)

@@ -168,3 +168,109 @@ def make_sequence(gen, H, Hkv, hd, Tq, Tk, causal, regime, plant):
         k[:, :, OFF_DIM] = 16.0
         q[:, :, OFF_DIM] = (sign * (60.0 / (16.0 * scale)))[:, None]
     return q, k, v, do
+
+
+# ------------------------------------------------------------------------------------------------------------------ cases
+# The cases of tests/test_attention_kernels_gpu.py and the kernel each one is meant for.  They live here, in a module that imports
+# without a device, so that tests/test_attention_route_cpu.py can hold ``route`` against csrc/attention_route.h for every one of them.
+ENVS = ('I2T_ATTN_V2', 'I2T_ATTN_BWD', 'I2T_ATTN_BWD2', 'I2T_ATTN_BWD1', 'I2T_ATTN_BWD3_WAVES')
+
+
+def C(api='mha', B=1, H=2, Hkv=None, hd=64, Tq=64, Tk=None, causal=False, drop=False, lens=None, cross=False, split=0, od=False,
+      q_seq=0, regime='n01', plant='first', bwd=True):
+    """one case.  lens: packed queries (cu_q; with cross=False the keys are packed the same way, cu_k = cu_q); q_seq: the queries are
+    the first Tq rows of sequences of q_seq rows (out_drop_q_seq); od: out_drop on."""
+    Tk = Tq if Tk is None else Tk
+    Hkv = H if Hkv is None else Hkv
+    if lens is not None:
+        B = len(lens)
+    c = SimpleNamespace(api=api, B=B, H=H, Hkv=Hkv, hd=hd, Tq=Tq, Tk=Tk, causal=causal, drop=drop, lens=lens, cross=cross or Tq != Tk,
+                        split=split, od=od, q_seq=q_seq, regime=regime, plant=plant if regime == 'peak' else '-', bwd=bwd)
+    c.id = (f'{api}-B{B}H{H}' + (f'kv{Hkv}d{hd}' if api == 'gq' else '') + f'-{Tq}x{Tk}' + ('-causal' if causal else '') +
+            ('-drop' if drop else '') + (f'-lens{"_".join(map(str, lens))}' + ('x' if c.cross else 's') if lens is not None else '') +
+            (f'-split{split}' if split else '') + ('-od' if od else '') + (f'-qseq{q_seq}' if q_seq else '') +
+            f'-{regime}' + (f'_{plant}' if regime == 'peak' else ''))
+    return c
+
+
+def regimes(bases):
+    """every base case in the three input regimes; the planted key's place rotates over the cases"""
+    out, n = [], 0
+    for kw in bases:
+        for regime in ('n01', 'peak', 'offset'):
+            plants = ('first', 'diag', 'rising') if kw.get('causal') else ('first', 'last', 'tail', 'rising')
+            out.append(C(regime=regime, plant=plants[n % len(plants)], **kw))
+            n += regime == 'peak'
+    return out
+
+
+def v2_applies(c, env):
+    """csrc/attention_route.h::attn_resident"""
+    return (env.get('I2T_ATTN_V2', '1')[:1] != '0' and not c.causal and c.lens is None and c.Tk <= 288 and 64 <= c.Tq <= 304 and
+            (not c.drop or c.Tk % 4 == 0))
+
+
+def drop_variant(c):
+    return 'nodrop' if not c.drop else ('even' if c.Tk % 4 == 0 else 'odd')
+
+
+def route(c, env):
+    """(forward kernel, backward kernel) of a head_dim-64 call: csrc/attention_route.h::attn_fwd_route / attn_bwd_route restated
+    (tests/test_attention_route_cpu.py holds the two together).  CNT, the key blocks per wave, is chosen inside attn_bwd3_kernel."""
+    v2 = v2_applies(c, env)
+    fwd = f'fwd2<PER={((c.Tq + 15) >> 4) >> 2}>' if v2 else f'fwd<{drop_variant(c)}>'
+    mode = 0 if env.get('I2T_ATTN_BWD2', '1')[:1] == '0' else int(env.get('I2T_ATTN_BWD', '3'))
+    nkb = (c.Tk + 15) >> 4
+    if mode == 3 and v2 and c.Tq <= 288:
+        nwv = 9 if env.get('I2T_ATTN_BWD3_WAVES') == '9' else 8
+        bwd = f'bwd3<{nwv},CNT={min(-(-nkb // nwv), 2 if nwv == 9 else 3)}>'
+    elif mode != 0 and v2 and c.Tq <= 288:
+        bwd = 'bwd2'
+    elif c.Tq <= 64 and c.Tk <= 64 and env.get('I2T_ATTN_BWD1', '1')[:1] != '0':
+        bwd = f'bwd1<{drop_variant(c)}>'
+    else:
+        bwd = f'pair<{drop_variant(c)}>'
+    return fwd, bwd
+
+
+# head_dim 64 (the smallest sizes that reach each branch; B, H > 1 in at least one case per kernel)
+FWD_TILED = regimes(
+    [dict(Tq=1, causal=True, bwd=False), dict(B=2, H=3, Tq=16, causal=True), dict(Tq=37, causal=True), dict(B=2, Tq=64, causal=True),
+     dict(Tq=65, causal=True), dict(B=2, H=2, Tq=130, causal=True), dict(B=2, H=1, Tq=33, Tk=131, causal=True), dict(B=2, Tq=1, Tk=50, causal=True),
+     dict(B=2, H=1, Tq=5, Tk=9), dict(B=2, H=1, Tq=24), dict(Tq=70, Tk=320), dict(B=2, H=3, Tq=320, Tk=40),
+     dict(Tq=70, Tk=37, drop=True), dict(B=2, H=3, Tq=100, Tk=131, drop=True), dict(B=2, Tq=130, causal=True, drop=True),
+     dict(H=2, Tq=65, lens=(0, 1, 64, 65, 5), causal=True), dict(H=2, Tq=65, lens=(0, 1, 64, 65, 5), causal=True, drop=True),
+     dict(H=2, Tq=65, Tk=130, lens=(5, 64, 0, 65, 1), cross=True), dict(H=3, Tq=65, Tk=197, lens=(5, 64, 0, 65, 1), cross=True),
+     dict(H=2, Tq=65, Tk=197, lens=(5, 64, 0, 65, 1), cross=True, drop=True, od=True)])
+FWD_V2 = regimes(
+    [dict(B=2, H=3, Tq=64, Tk=9), dict(Tq=112, Tk=64), dict(Tq=113, Tk=197), dict(Tq=176, Tk=288), dict(Tq=177, Tk=64, drop=True),
+     dict(B=2, Tq=240, Tk=197), dict(Tq=241, Tk=9), dict(Tq=241, Tk=288, drop=True), dict(B=2, H=2, Tq=304, Tk=288), dict(Tq=304, Tk=64, drop=True)])
+BWD3 = regimes(
+    [dict(B=2, H=3, Tq=64, Tk=16), dict(Tq=197, Tk=17), dict(Tq=288, Tk=128), dict(Tq=64, Tk=129), dict(B=2, Tq=197, Tk=197),
+     dict(Tq=288, Tk=256), dict(Tq=64, Tk=257), dict(Tq=197, Tk=272), dict(Tq=288, Tk=288),
+     dict(Tq=64, Tk=16, drop=True), dict(B=2, Tq=288, Tk=128, drop=True), dict(Tq=197, Tk=272, drop=True), dict(Tq=288, Tk=288, drop=True, od=True),
+     dict(B=2, Tq=197, Tk=197, od=True)])
+BWD3_QSEQ = regimes([dict(B=2, H=2, Tq=64, Tk=197, od=True, q_seq=197), dict(B=2, H=2, Tq=64, Tk=196, od=True, q_seq=196, drop=True)])
+BWD1 = regimes(
+    [dict(B=2, H=3, Tq=64, causal=True), dict(Tq=37, causal=True), dict(Tq=16, causal=True), dict(Tq=33, Tk=50, causal=True), dict(B=2, H=1, Tq=5, Tk=9),
+     dict(Tq=24), dict(Tq=40, Tk=64), dict(B=2, Tq=64, causal=True, drop=True), dict(Tq=24, drop=True), dict(Tq=37, causal=True, drop=True),
+     dict(B=2, Tq=5, Tk=9, drop=True), dict(B=2, Tq=40, causal=True, od=True),
+     dict(H=2, Tq=64, lens=(0, 1, 64, 37), causal=True), dict(H=2, Tq=64, lens=(0, 1, 64, 37), causal=True, drop=True, od=True),
+     dict(H=2, Tq=64, Tk=24, lens=(5, 0, 64, 16), cross=True), dict(H=2, Tq=64, Tk=37, lens=(5, 0, 64, 16), cross=True, drop=True)])
+PAIR = [c for c in FWD_TILED if c.bwd and route(c, {})[1].startswith('pair')] + regimes([dict(B=2, H=2, Tq=304, Tk=288), dict(Tq=304, Tk=64, drop=True)])
+
+# the A/B switches of the encoder backward: name -> (environment, the kernel the BWD3 shapes then run on)
+SWITCHES = {'waves9': ({'I2T_ATTN_BWD3_WAVES': '9'}, 'bwd3<9'), 'bwd2': ({'I2T_ATTN_BWD': '2'}, 'bwd2'), 'bwd0': ({'I2T_ATTN_BWD': '0'}, 'pair<'),
+            'bwd2off': ({'I2T_ATTN_BWD2': '0'}, 'pair<')}
+
+# grouped heads
+GQ = regimes(
+    [dict(api='gq', B=2, H=8, Hkv=1, hd=16, Tq=70, causal=True), dict(api='gq', H=8, Hkv=1, hd=16, Tq=33, Tk=131),
+     dict(api='gq', B=2, H=4, Hkv=2, hd=32, Tq=130, causal=True), dict(api='gq', H=4, Hkv=2, hd=32, Tq=257), dict(api='gq', H=2, Hkv=2, hd=32, Tq=1, Tk=50, causal=True),
+     dict(api='gq', B=2, H=2, Hkv=2, hd=64, Tq=65, causal=True), dict(api='gq', H=8, Hkv=1, hd=64, Tq=70, Tk=37, drop=True),
+     dict(api='gq', H=2, Hkv=1, hd=128, Tq=257, causal=True), dict(api='gq', B=2, H=2, Hkv=2, hd=128, Tq=64, Tk=130),
+     dict(api='gq', H=2, Hkv=1, hd=128, Tq=100, Tk=131, drop=True, od=True), dict(api='gq', B=2, H=4, Hkv=2, hd=16, Tq=40, Tk=37, drop=True),
+     dict(api='gq', H=4, Hkv=2, hd=32, Tq=65, lens=(0, 1, 64, 65, 5), causal=True), dict(api='gq', H=4, Hkv=2, hd=64, Tq=65, lens=(0, 1, 64, 65, 5), causal=True, drop=True, od=True),
+     dict(api='gq', H=8, Hkv=1, hd=64, Tq=65, Tk=130, lens=(5, 64, 0, 65), cross=True), dict(api='gq', B=2, H=4, Hkv=2, hd=64, Tq=96, od=True)])
+GQ_SPLIT = regimes([dict(api='gq', B=B, H=H, Hkv=Hkv, hd=hd, Tq=T, split=s, bwd=False)
+                    for T, (B, H, Hkv, hd) in ((96, (2, 4, 2, 32)), (130, (1, 2, 1, 64))) for s in (1, 63, 64, 65, T - 1)])
