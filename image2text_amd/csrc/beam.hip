@@ -261,6 +261,182 @@ __global__ __launch_bounds__(CS_THREADS) void beam_consolidate_kernel(const int*
     }
 }
 
+constexpr int PS_THREADS = 256, PS_MAX_W = 8, PS_MAX_WE = 2 * PS_MAX_W * PS_MAX_W;
+
+// The selection step of generate_captions(num_beams = W) (decoding.beam_pool_select_host is the host replica): one
+// workgroup per image, E = 2 W candidates per row.  The top 2 W of the image's W x E totals are ranked (descending, lower flat index
+// w * E + e first); a candidate HITS when its token is eos or it is the max_new-th emitted token.  Hits ranked below W are offered to
+// the image's pool of finished captions at total / powf(emitted, length_penalty); the pool keeps its W best, sorted, an entry it
+// already holds before a new one of the same score.  The first W candidates that do not hit become the running beams.  Pool rows and
+// running rows are moved a column at a time through registers -- the pool first, it reads the parents' rows --, so no column is
+// read after it was overwritten.  An image closes at the bound, with early_stopping once its pool is full, and without it once the
+// best running total / powf(emitted, length_penalty) no longer exceeds the full pool's worst score; a closed image's block returns at
+// once, and every open image stores the same 1 into ctrl[1], so the word needs no atomic.
+__global__ __launch_bounds__(PS_THREADS) void beam_pool_select_kernel(const int* __restrict__ cand_tok, const float* __restrict__ cand_lp,
+                                                                      float* __restrict__ scores, int64_t* __restrict__ ids, int ids_ld,
+                                                                      int* __restrict__ hist, int hist_ld, float* __restrict__ tok_lp, int lp_ld,
+                                                                      int64_t* __restrict__ pool_ids, float* __restrict__ pool_lp,
+                                                                      float* __restrict__ pool_score, float* __restrict__ pool_sum,
+                                                                      int* __restrict__ pool_len, int* __restrict__ pool_n, int* __restrict__ closed,
+                                                                      const int* __restrict__ pos_ptr, const int* __restrict__ len_ptr,
+                                                                      int* __restrict__ ctrl, int W, int P, int max_new, int eos, int pad,
+                                                                      float length_penalty, int early_stopping) {
+    __shared__ float tot[PS_MAX_WE];
+    __shared__ int taken[PS_MAX_WE];
+    __shared__ int pick[2 * PS_MAX_W];
+    __shared__ int c_par[PS_MAX_W], c_tok[PS_MAX_W];                         // the running children
+    __shared__ float c_score[PS_MAX_W], c_lp[PS_MAX_W];
+    __shared__ int e_src[PS_MAX_W + 1], e_par[PS_MAX_W + 1], e_tok[PS_MAX_W + 1], e_len[PS_MAX_W + 1];      // the pool after the merge; src >= 0:
+    __shared__ float e_score[PS_MAX_W + 1], e_sum[PS_MAX_W + 1], e_lp[PS_MAX_W + 1];                         // the row it held, -1: a new one
+    __shared__ int flags[2];                                                  // [the pool changed, the image closes]
+    if (ctrl[0]) return;
+    const int b = blockIdx.x, tid = threadIdx.x, E = 2 * W, WE = W * E;
+    if (closed[b]) return;
+    const int pos = *pos_ptr, len = *len_ptr;
+    if (len < P || len >= P + max_new || pos < 0 || pos >= hist_ld) return;   // counters outside the call's columns: nothing is written
+    const int r0 = b * W, total_cols = P + max_new;
+    for (int j = tid; j < WE; j += PS_THREADS) {
+        const int w = j / E;
+        tot[j] = scores[r0 + w] + cand_lp[(size_t)(r0 + w) * E + (j - w * E)];
+        taken[j] = 0;
+    }
+    __syncthreads();
+    if (tid < 64) {                                          // 2 W rounds of a wave arg-max (total descending, flat index ascending)
+        for (int k = 0; k < E; ++k) {
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int j = tid; j < WE; j += 64)
+                if (!taken[j] && better(tot[j], j, bv, bi)) { bv = tot[j]; bi = j; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (tid == 0) pick[k] = bi;
+            if (bi != 0x7fffffff && (bi & 63) == tid) taken[bi] = 1;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int emitted = len + 1 - P;
+        const bool bound = emitted >= max_new;
+        const float denom = powf((float)emitted, length_penalty);
+        int m = pool_n[b], nchild = 0, changed = 0;
+        for (int i = 0; i < W; ++i) {
+            e_src[i] = i;
+            e_score[i] = pool_score[r0 + i];
+            e_sum[i] = pool_sum[r0 + i];
+            e_len[i] = pool_len[r0 + i];
+        }
+        for (int k = 0; k < E; ++k) {
+            const int j = pick[k];
+            if (j == 0x7fffffff) continue;                   // NaN totals only: nothing ranks
+            const int w = j / E;
+            const int tk = cand_tok[(size_t)(r0 + w) * E + (j - w * E)];
+            const float lpv = cand_lp[(size_t)(r0 + w) * E + (j - w * E)];
+            if (bound || (eos >= 0 && tk == eos)) {
+                if (k >= W) continue;
+                const float s = tot[j] / denom;
+                int at = 0;
+                while (at < m && e_score[at] >= s) ++at;     // behind everything at least as good
+                if (at >= W) continue;
+                for (int i = (m < W ? m : W - 1); i > at; --i) {
+                    e_src[i] = e_src[i - 1]; e_par[i] = e_par[i - 1]; e_tok[i] = e_tok[i - 1]; e_len[i] = e_len[i - 1];
+                    e_score[i] = e_score[i - 1]; e_sum[i] = e_sum[i - 1]; e_lp[i] = e_lp[i - 1];
+                }
+                e_src[at] = -1; e_par[at] = r0 + w; e_tok[at] = tk; e_len[at] = len + 1;
+                e_score[at] = s; e_sum[at] = tot[j]; e_lp[at] = lpv;
+                if (m < W) ++m;
+                changed = 1;
+            } else if (nchild < W) {
+                c_par[nchild] = r0 + w; c_tok[nchild] = tk; c_score[nchild] = tot[j]; c_lp[nchild] = lpv;
+                ++nchild;
+            }
+        }
+        for (int w = nchild; w < W; ++w) {                   // fewer than W live candidates (NaN or repeated-EOS inputs only): the row stays, dead
+            c_par[w] = r0 + w; c_tok[w] = pad; c_score[w] = -INFINITY; c_lp[w] = 0.f;
+        }
+        for (int i = m; i < W; ++i) e_src[i] = i;            // slots past the pool's count keep what they hold
+        int cl = bound ? 1 : 0;
+        if (!cl && m == W) cl = early_stopping ? 1 : (c_score[0] / denom > e_score[W - 1] ? 0 : 1);
+        for (int i = 0; i < m; ++i) {
+            pool_score[r0 + i] = e_score[i];
+            pool_sum[r0 + i] = e_sum[i];
+            pool_len[r0 + i] = e_len[i];
+        }
+        pool_n[b] = m;
+        closed[b] = cl;
+        if (!cl) ctrl[1] = 1;
+        flags[0] = changed;
+        flags[1] = cl;
+    }
+    __syncthreads();
+    if (flags[0]) {                                          // the pool's rows: a kept row from the slot it held, a new one from its parent
+        int64_t vi[PS_MAX_W];
+        float vf[PS_MAX_W];
+        for (int t = tid; t < total_cols; t += PS_THREADS) {
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) {
+                    const int s = e_src[w];
+                    if (s >= 0) {
+                        vi[w] = pool_ids[(size_t)(r0 + s) * ids_ld + t];
+                        vf[w] = pool_lp[(size_t)(r0 + s) * lp_ld + t];
+                    } else if (t < len) {
+                        vi[w] = ids[(size_t)e_par[w] * ids_ld + t];
+                        vf[w] = tok_lp[(size_t)e_par[w] * lp_ld + t];
+                    } else {
+                        vi[w] = t == len ? (int64_t)e_tok[w] : (int64_t)pad;
+                        vf[w] = t == len ? e_lp[w] : 0.f;
+                    }
+                }
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) {
+                    pool_ids[(size_t)(r0 + w) * ids_ld + t] = vi[w];
+                    pool_lp[(size_t)(r0 + w) * lp_ld + t] = vf[w];
+                }
+        }
+    }
+    __syncthreads();
+    if (flags[1] && len + 1 >= total_cols) return;           // at the bound nothing runs on: the rows stay
+    {
+        int64_t vi[PS_MAX_W];
+        float vf[PS_MAX_W];
+        for (int t = tid; t < len; t += PS_THREADS) {
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) {
+                    vi[w] = ids[(size_t)c_par[w] * ids_ld + t];
+                    vf[w] = tok_lp[(size_t)c_par[w] * lp_ld + t];
+                }
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) {
+                    ids[(size_t)(r0 + w) * ids_ld + t] = vi[w];
+                    tok_lp[(size_t)(r0 + w) * lp_ld + t] = vf[w];
+                }
+        }
+        int vh[PS_MAX_W];
+        for (int t = tid; t < pos; t += PS_THREADS) {
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) vh[w] = hist[(size_t)c_par[w] * hist_ld + t];
+#pragma unroll
+            for (int w = 0; w < PS_MAX_W; ++w)
+                if (w < W) hist[(size_t)(r0 + w) * hist_ld + t] = vh[w];
+        }
+    }
+    if (tid < W) {
+        const int c = r0 + tid;
+        ids[(size_t)c * ids_ld + len] = c_tok[tid];
+        tok_lp[(size_t)c * lp_ld + len] = c_lp[tid];
+        hist[(size_t)c * hist_ld + pos] = c_par[tid];
+        scores[c] = c_score[tid];
+    }
+}
+
 // pos / len advance while work remains; the flag is set once no caption is left unfinished, and the counter is cleared for the
 // next step
 __global__ void beam_advance_kernel(int* counters, int* ctrl) {
@@ -300,6 +476,30 @@ extern "C" int i2t_beam_consolidate(void* stream, const int* cand_tok, const flo
     hipLaunchKernelGGL(beam_consolidate_kernel, dim3(B), dim3(CS_THREADS), 0, (hipStream_t)stream, cand_tok, cand_lp, scores, ids, ids_ld,
                        hist, hist_ld, has_eos, parent, pos_ptr, len_ptr, ctrl, W, E, temperature, eos, seed, raw_pick);
     I2T_CHECK_LAUNCH("i2t_beam_consolidate");
+    return I2T_OK;
+}
+
+extern "C" int i2t_beam_pool_select(void* stream, const int* cand_tok, const float* cand_lp, float* scores, int64_t* ids, int ids_ld, int* hist,
+                                    int hist_ld, float* tok_lp, int lp_ld, int64_t* pool_ids, float* pool_lp, float* pool_score,
+                                    float* pool_sum, int* pool_len, int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr,
+                                    int* ctrl, int B, int W, int P, int max_new, int eos, int pad, float length_penalty,
+                                    int early_stopping) {
+    I2T_REQUIRE(cand_tok && cand_lp && scores && ids && hist && tok_lp && pool_ids && pool_lp && pool_score && pool_sum && pool_len &&
+                    pool_n && closed && pos_ptr && len_ptr && ctrl && B > 0,
+                "i2t_beam_pool_select: bad args");
+    I2T_REQUIRE(W >= 1 && W <= PS_MAX_W, "i2t_beam_pool_select: beam width %d (1 .. %d)", W, PS_MAX_W);
+    I2T_REQUIRE(P >= 1 && max_new >= 1 && pad >= 0, "i2t_beam_pool_select: P = %d, max_new = %d (each at least 1), pad = %d (at least 0)", P,
+                max_new, pad);
+    I2T_REQUIRE((long)P + max_new <= ids_ld && (long)P + max_new <= lp_ld && hist_ld >= 1,
+                "i2t_beam_pool_select: P + max_new = %ld columns exceed ids_ld = %d or lp_ld = %d (hist_ld = %d)", (long)P + max_new, ids_ld,
+                lp_ld, hist_ld);
+    // the exponent bits, not a comparison: no fast-math folding of a NaN test
+    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u && (early_stopping == 0 || early_stopping == 1),
+                "i2t_beam_pool_select: length_penalty must be finite and early_stopping 0 or 1 (%d)", early_stopping);
+    hipLaunchKernelGGL(beam_pool_select_kernel, dim3(B), dim3(PS_THREADS), 0, (hipStream_t)stream, cand_tok, cand_lp, scores, ids, ids_ld, hist,
+                       hist_ld, tok_lp, lp_ld, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P,
+                       max_new, eos, pad, length_penalty, early_stopping);
+    I2T_CHECK_LAUNCH("i2t_beam_pool_select");
     return I2T_OK;
 }
 

@@ -848,10 +848,13 @@ class GeneratedCaptions(_CaptionFields):
     from p_b and ``token_logprobs`` is [B, N, L - Pmin], entry t belonging to column Pmin + t.  ``_replace`` and
     ``_make`` build the four fields only."""
     prompt_lengths: Optional[torch.Tensor] = None
+    beam_scores: Optional[torch.Tensor] = None      # fp32 [B, N] under num_beams > 1 (DESIGN.md 4t): the length-penalised score the N
+                                                    # captions of an image are sorted by, best first; None in every other mode
 
-    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None):
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None):
         self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
         self.prompt_lengths = prompt_lengths
+        self.beam_scores = beam_scores
         return self
 
 
@@ -1194,6 +1197,356 @@ def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: 
     if B and int(plen.max()) > P:
         raise ValueError(f'prompt_lengths[{int(plen.argmax())}] = {int(plen.max())} exceeds the {P} columns of prompt_ids')
     return plen.astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ caption beams
+MAX_CAPTION_BEAMS = 8               # i2t_beam_candidates takes E = 2 W <= 16
+BEAM_DEAD = -1.0e9                  # the running score of beams 1 .. W - 1 before the first step (transformers' constant)
+
+
+def check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature=1.0, top_k=None, nucleus_p=None,
+                            seed=None, prompt_lengths=None, prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0,
+                            suppress_tokens=None, max_new_tokens=1, eos=None, pad=None, poll_every=8, causal=True, vocab=None) -> int:
+    """The refusals of ``generate_captions(num_beams=W, ...)`` that need no device, all before anything runs -> W.  W = 1 is the call
+    without the beam arguments: only W itself, ``length_penalty`` and ``early_stopping`` are looked at.  ValueError: W outside
+    1 .. MAX_CAPTION_BEAMS (the candidates kernel takes E = 2 W <= 16), N outside 1 .. W, a non-finite ``length_penalty``,
+    ``early_stopping`` not False / True ("never" is out of scope), any sampling argument (beam sampling is out of scope), a negative
+    id or count.  NotImplementedError, naming the reason: ``prompt_lengths``, ``prompt_prefill='pass'``, an active
+    ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens``, a non-causal decoder."""
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
+        raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the candidates kernel takes 2 * num_beams '
+                         f'<= 16 candidates per row)')
+    W = int(num_beams)
+    try:
+        finite = bool(np.isfinite(float(length_penalty)))
+    except (TypeError, ValueError):
+        finite = False
+    if not finite:
+        raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
+    if not isinstance(early_stopping, (bool, np.bool_)):
+        raise ValueError(f'early_stopping = {early_stopping!r}: False or True ("never" is not supported)')
+    if W == 1:
+        return W
+    N = int(num_return_sequences)
+    if not 1 <= N <= W:
+        raise ValueError(f'num_return_sequences = {N} with num_beams = {W}: from 1 to num_beams captions per image')
+    if temperature != 1 or top_k is not None or nucleus_p is not None or seed is not None:
+        raise ValueError('num_beams > 1 is deterministic beam search: temperature, top_k, nucleus_p and seed must stay at their defaults '
+                         '(beam sampling is not supported)')
+    if (eos is not None and eos < 0) or (pad is not None and pad < 0):
+        raise ValueError(f'eos_token_id = {eos}, pad_token_id = {pad}: neither may be negative')
+    if poll_every < 0 or max_new_tokens < 0:
+        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+    if caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab) is not None:
+        raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens under num_beams > 1: the beam step has no '
+                                  'logits-processor pass')
+    if prompt_lengths is not None:
+        raise NotImplementedError('prompt_lengths under num_beams > 1: the beam step has no forcing table for ragged prompts')
+    if prompt_prefill not in PROMPT_PREFILL_MODES:
+        raise ValueError(f'prompt_prefill = {prompt_prefill!r}: one of {PROMPT_PREFILL_MODES}')
+    if prompt_prefill != 'steps':
+        raise NotImplementedError("prompt_prefill='pass' under num_beams > 1: the beam rows are prefilled step by step under the identity "
+                                  "history table")
+    if not causal:
+        raise NotImplementedError('num_beams > 1 needs a causal decoder: a non-causal one has no KV cache to run the beams on')
+    return W
+
+
+def beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
+                          counters, ctrl, W: int, P: int, max_new: int, eos, pad: int, length_penalty: float, early_stopping: bool,
+                          gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
+    """One i2t_beam_pool_select call on the host (numpy, in place on the arrays given; fp32 arithmetic in the kernel's order): the
+    normative statement of the selection step of ``generate_captions(num_beams=W)``, pinned to transformers 5.x
+    ``GenerationMixin._beam_search`` (do_sample=False, one EOS id).  ``cand_tok`` / ``cand_lp`` [R, 2 W]: every row's 2 W best tokens and
+    their log-probs; ``scores`` f32 [R]; ``ids`` int64 [R, ids_ld]; ``hist`` int32 [R, hist_ld]; ``tok_lp`` f32 [R, lp_ld]; the pool
+    ``pool_ids`` [B, W, ids_ld], ``pool_lp`` [B, W, lp_ld], ``pool_score`` / ``pool_sum`` f32 [B, W], ``pool_len`` int32 [B, W], ``pool_n``
+    / ``closed`` int32 [B]; ``counters`` = [pos, len], ``ctrl`` = [done, open] (``i2t_beam_advance`` moves both; ``beam_advance_host``).
+    Per image that is not closed (nothing happens once ctrl[0] is set):
+      * totals = scores[row] + cand_lp (fp32); the top 2 W of the W * 2 W, descending, the lower flat index w * 2 W + e first on ties;
+      * emitted = len + 1 - P counts the token being added; a candidate HITS if its token is ``eos`` or emitted == max_new;
+      * hits ranked below W are offered at total / fp32(emitted) ** fp32(length_penalty) (one fp32 power, one fp32 division); the pool
+        keeps the W best of (pool, offers), sorted descending, an entry it holds before a new one of equal score, an earlier offer
+        before a later one; a pool row is the parent's ids and log-probs, the token and its log-prob, then ``pad`` and 0.0;
+      * the first W candidates that do not hit, in rank order, become the image's rows: ids, history and log-prob rows move from
+        parent to child;
+      * the image closes at the bound (its rows then stay as they are); with ``early_stopping`` once the pool holds W; without it
+        once the pool holds W and not (best running total / fp32(emitted) ** fp32(length_penalty) > the pool's worst score) --
+        ``_check_early_stop_heuristic`` with early_stopping=False: the length is cur_len - prompt length AFTER the step's increment;
+      * an image left open sets ctrl[1] = 1.
+    ``gaps`` (a list, optional) receives the differences between neighbours among the top 2 W totals; ``pool_gaps`` those between an
+    offer and the pool entries beside it and between the close test's two sides."""
+    if ctrl[0]:
+        return
+    pos, ln = int(counters[0]), int(counters[1])
+    R = scores.shape[0]
+    B, E = R // W, 2 * W
+    if ln < P or ln >= P + max_new or pos < 0 or pos >= hist.shape[1]:
+        return
+    f32 = np.float32
+    emitted = ln + 1 - P
+    bound = emitted >= max_new
+    with np.errstate(all='ignore'):
+        denom = np.power(f32(emitted), f32(length_penalty)).astype(f32)
+    for b in range(B):
+        if closed[b]:
+            continue
+        r0 = b * W
+        tot = (scores[r0:r0 + W].astype(f32)[:, None] + cand_lp[r0:r0 + W].astype(f32)).astype(f32).reshape(-1)
+        order = sorted(range(W * E), key=lambda j: (-tot[j], j))[:E]
+        if gaps is not None:
+            gaps.extend(float(tot[order[k]]) - float(tot[order[k + 1]]) for k in range(E - 1) if np.isfinite(tot[order[k + 1]]))
+        m = int(pool_n[b])
+        entries = [(f32(pool_score[b, i]), i, None) for i in range(m)]          # (score, the slot it held or -1, the candidate)
+        children = []
+        for k, j in enumerate(order):
+            w, e = divmod(j, E)
+            tk, lpv = int(cand_tok[r0 + w, e]), f32(cand_lp[r0 + w, e])
+            if bound or (eos is not None and eos >= 0 and tk == eos):
+                if k >= W:
+                    continue
+                s = f32(tot[j] / denom)
+                at = 0
+                while at < len(entries) and entries[at][0] >= s:
+                    at += 1
+                if pool_gaps is not None:
+                    pool_gaps.extend(abs(float(entries[i][0]) - float(s)) for i in (at - 1, at) if 0 <= i < len(entries))
+                if at >= W:
+                    continue
+                entries.insert(at, (s, -1, (r0 + w, tk, f32(tot[j]), lpv)))
+                del entries[W:]
+            elif len(children) < W:
+                children.append((r0 + w, tk, f32(tot[j]), lpv))
+        while len(children) < W:
+            children.append((r0 + len(children), int(pad), f32(-np.inf), f32(0.0)))
+        if any(src < 0 for _, src, _ in entries):
+            old_ids, old_lp = pool_ids[b].copy(), pool_lp[b].copy()
+            old_sum, old_len = pool_sum[b].copy(), pool_len[b].copy()
+            total = P + max_new
+            for d, (s, src, c) in enumerate(entries):
+                pool_score[b, d] = s
+                if src >= 0:
+                    pool_ids[b, d, :total], pool_lp[b, d, :total] = old_ids[src, :total], old_lp[src, :total]
+                    pool_sum[b, d], pool_len[b, d] = old_sum[src], old_len[src]
+                else:
+                    par, tk, t, lpv = c
+                    pool_ids[b, d, :ln], pool_lp[b, d, :ln] = ids[par, :ln], tok_lp[par, :ln]
+                    pool_ids[b, d, ln], pool_lp[b, d, ln] = tk, lpv
+                    pool_ids[b, d, ln + 1:total], pool_lp[b, d, ln + 1:total] = pad, 0.0
+                    pool_sum[b, d], pool_len[b, d] = t, ln + 1
+        m = len(entries)
+        pool_n[b] = m
+        cl = bool(bound)
+        if not cl and m == W:
+            if early_stopping:
+                cl = True
+            else:
+                with np.errstate(all='ignore'):
+                    best = f32(children[0][2] / denom)
+                cl = not (best > entries[W - 1][0])
+                if pool_gaps is not None and np.isfinite(best):
+                    pool_gaps.append(abs(float(best) - float(entries[W - 1][0])))
+        closed[b] = 1 if cl else 0
+        if not cl:
+            ctrl[1] = 1
+        if bound:
+            continue
+        pars = [c[0] for c in children]
+        ids[r0:r0 + W, :ln] = ids[pars, :ln]
+        tok_lp[r0:r0 + W, :ln] = tok_lp[pars, :ln]
+        hist[r0:r0 + W, :pos] = hist[pars, :pos]
+        for w, (par, tk, t, lpv) in enumerate(children):
+            ids[r0 + w, ln], tok_lp[r0 + w, ln], hist[r0 + w, pos], scores[r0 + w] = tk, lpv, par, t
+
+
+def beam_advance_host(counters, ctrl):
+    """i2t_beam_advance on the host: while ctrl[0] is clear pos and len advance and ctrl[0] = (ctrl[1] == 0); then ctrl[1] = 0"""
+    if not ctrl[0]:
+        counters[0] += 1
+        counters[1] += 1
+        if ctrl[1] == 0:
+            ctrl[0] = 1
+    ctrl[1] = 0
+
+
+def banned_log_softmax_host(z, ids_row, ngram_sizes) -> np.ndarray:
+    """fp32 log_softmax of one logits row after the no-repeat-n-gram ban over ``ids_row`` (-inf at a token that would complete an
+    n-gram the row already holds): the quantity ``i2t_beam_candidates`` returns at temperature <= 0"""
+    z = np.array(z, dtype=np.float32).reshape(-1)
+    row = [int(t) for t in ids_row]
+    for n in ngram_sizes:
+        if n < 1 or len(row) < n:
+            continue
+        tail = tuple(row[len(row) - n + 1:]) if n > 1 else ()
+        for i in range(len(row) - n + 1):
+            if tuple(row[i:i + n - 1]) == tail and 0 <= row[i + n - 1] < z.shape[0]:
+                z[row[i + n - 1]] = -np.inf
+    m = z.max()
+    return (z - (m + np.log(np.exp(z - m, dtype=np.float32).sum(dtype=np.float32), dtype=np.float32))).astype(np.float32)
+
+
+def beam_search_host(step_logits, prompt, W: int, N: int, max_new: int, eos, pad, length_penalty: float, early_stopping: bool,
+                     ngram_sizes=()):
+    """The whole search of ``generate_captions(num_beams=W)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32 logits
+    row [V] that follows a token sequence (a list of ints, the prompt included); ``prompt`` is the image's prompt (P >= 1 ids).  Every
+    step takes each running row's ``banned_log_softmax_host``, its 2 W best tokens (descending, the lower id first on ties), one
+    ``beam_pool_select_host`` call and ``beam_advance_host``; running scores start at [0, BEAM_DEAD, ...].  -> SimpleNamespace(ids
+    int64 [N, L], lengths int32 [N], token_logprobs f32 [N, L - P], logprob f32 [N], beam_scores f32 [N], steps, gaps, pool_gaps): the
+    first N pool entries, L = lengths.max(), the pad id and 0.0 past each length; ``gaps``: per step the differences between
+    neighbours among the top 2 W totals and between the 2 W-th and the next one; ``pool_gaps``: those the pool merges and the close
+    tests hung on (``beam_pool_select_host``); ``decision_gaps``: per step the gap between the last total that runs on and the next one
+    that does not, and -- when a hit ranks among the top 2 W -- between ranks W - 1 and W.  A search whose ``decision_gaps`` and
+    ``pool_gaps`` all exceed a perturbation of the totals keeps its result under it."""
+    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    P, E = len(prompt), 2 * W
+    assert P >= 1 and 1 <= N <= W and max_new >= 1
+    pad = int((0 if eos is None else eos) if pad is None else pad)
+    total = P + max_new
+    f32, i32 = np.float32, np.int32
+    ids = np.zeros((W, total), dtype=np.int64)
+    ids[:, :P] = prompt
+    hist = np.repeat(np.arange(W, dtype=i32)[:, None], total, axis=1)
+    tok_lp = np.zeros((W, total), dtype=f32)
+    scores = np.full(W, BEAM_DEAD, dtype=f32)
+    scores[0] = 0.0
+    pool_ids, pool_lp = np.full((1, W, total), pad, dtype=np.int64), np.zeros((1, W, total), dtype=f32)
+    pool_score, pool_sum = np.full((1, W), BEAM_DEAD, dtype=f32), np.zeros((1, W), dtype=f32)
+    pool_len, pool_n, closed = np.zeros((1, W), dtype=i32), np.zeros(1, dtype=i32), np.zeros(1, dtype=i32)
+    counters, ctrl = np.array([P - 1, P], dtype=i32), np.zeros(2, dtype=i32)
+    gaps, pool_gaps, decision_gaps, steps = [], [], [], 0
+    while steps < max_new and not ctrl[0]:
+        ln = int(counters[1])
+        cand_tok, cand_lp = np.zeros((W, E), dtype=i32), np.zeros((W, E), dtype=f32)
+        spare, seen, tops, lps = [], {}, [], []
+        for w in range(W):
+            key = tuple(int(t) for t in ids[w, :ln])
+            if key not in seen:
+                seen[key] = banned_log_softmax_host(step_logits(list(key)), key, ngram_sizes)
+            lp = seen[key]
+            order = sorted(range(lp.shape[0]), key=lambda t: (-lp[t], t))[:E + 1]
+            assert len(order) >= E, 'the vocabulary holds fewer than 2 W tokens'
+            cand_tok[w], cand_lp[w] = order[:E], lp[order[:E]]
+            tops.append(order)
+            lps.append(lp)
+            spare.extend(f32(scores[w] + lp[t]) for t in order[E:])
+        if not closed[0]:
+            # what the step's outcome hangs on: the last candidate that runs on against the next one that does not, and -- with a hit
+            # in sight, or at the bound -- rank W - 1 against rank W, the line below which a hit is dropped
+            every = sorted(((float(f32(scores[w] + lps[w][t])), w * (E + 1) + e, t) for w in range(W) for e, t in enumerate(tops[w])),
+                           key=lambda c: (-c[0], c[1]))
+            at_bound = ln + 1 - P >= max_new
+            hit = [at_bound or (eos is not None and c[2] == eos) for c in every]
+            live = [c[0] for c, h in zip(every, hit) if not h]
+            if len(live) > W and np.isfinite(live[W]):
+                decision_gaps.append(live[W - 1] - live[W])
+            if any(hit[:E]) and len(every) > W and np.isfinite(every[W][0]):
+                decision_gaps.append(every[W - 1][0] - every[W][0])
+            tot = np.sort((scores[:, None] + cand_lp).astype(f32).reshape(-1))[::-1]
+            nxt = max([float(tot[E])] + [float(v) for v in spare]) if W > 1 else max([float(v) for v in spare], default=-np.inf)
+            if np.isfinite(nxt):
+                gaps.append(float(tot[E - 1]) - nxt)
+        beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
+                              counters, ctrl, W, P, max_new, eos, pad, length_penalty, early_stopping, gaps, pool_gaps)
+        beam_advance_host(counters, ctrl)
+        steps += 1
+    assert int(pool_n[0]) >= N
+    lengths = pool_len[0, :N].copy()
+    L = int(lengths.max())
+    lp = pool_lp[0, :N, P:L].copy()
+    return SimpleNamespace(ids=pool_ids[0, :N, :L].copy(), lengths=lengths, token_logprobs=lp, logprob=lp.sum(axis=-1, dtype=f32),
+                           beam_scores=pool_score[0, :N].copy(), steps=steps, gaps=gaps, pool_gaps=pool_gaps, decision_gaps=decision_gaps)
+
+
+class CaptionBeamDecoder(BeamDecoder):
+    """``generate_captions(num_beams=W)`` on the static KV cache: BeamDecoder's R = B * W rows, history table and
+    attention kernels, under GreedyDecoder._replay with ``poll_every``.  A step is _body -> _final_norm -> fp32 lm_head ->
+    i2t_beam_candidates (temperature 0, E = 2 W, no EOS rule, no crop) -> i2t_beam_pool_select -> i2t_beam_advance; the finished pool and
+    the per-image closed flags live in device memory, and the result is the first N pool rows of every image.  The decoder keeps its own
+    state; its graph key is ('caption_beam', ...), never 'beam'."""
+
+    last_replays = 0                    # full-step replays the last call launched (tests, tools)
+
+    def _build_caption_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None):
+        spec = BeamSpec(W, 2 * W, 0.0, None, 0.0, None, 0.0, tuple(int(n) for n in self.model.config.no_repeat_n_grams))
+        st = self._build_beam(B, spec, ids_ld, False, clen)
+        dev = st.arena.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        st.tok_lp = torch.zeros(B * W, ids_ld, dtype=F32, device=dev)
+        st.pool_ids = torch.zeros(B, W, ids_ld, dtype=torch.long, device=dev)
+        st.pool_lp = torch.zeros(B, W, ids_ld, dtype=F32, device=dev)
+        st.pool_score, st.pool_sum = torch.zeros(B, W, dtype=F32, device=dev), torch.zeros(B, W, dtype=F32, device=dev)
+        st.pool_len, st.pool_n, st.closed = torch.zeros(B, W, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        st.scores_init = torch.full((B, W), BEAM_DEAD, dtype=F32, device=dev)
+        st.scores_init[:, 0] = 0.0
+        st.caption_beam = True
+        return st
+
+    def _caption_beam_step(self, st, P: int, max_new: int, eos, pad: int, length_penalty: float, early_stopping: bool):
+        eng, a, dc, sp = self.eng, self.eng.arena, self.eng.dec, st.spec
+        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
+        self._body(st)
+        self._final_norm(st)
+        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        ops.beam_candidates(st.logits, st.ids, len_ptr, st.ctrl, st.beam_ngrams, st.B, dc.V, sp.expansion, 0.0, None, None, 0.0, st.seed,
+                            st.cand_tok, st.cand_lp, None)
+        ops.beam_pool_select(st.cand_tok, st.cand_lp, st.scores, st.ids, st.hist, st.tok_lp, st.pool_ids, st.pool_lp, st.pool_score,
+                             st.pool_sum, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl, st.images, st.W, P, max_new, eos, pad,
+                             length_penalty, early_stopping)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    @torch.no_grad()
+    def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, num_beams: int, eos: Optional[int] = None,
+                          pad: Optional[int] = None, num_return_sequences: int = 1, length_penalty: float = 1.0,
+                          early_stopping: bool = False, poll_every: int = 8, use_graph: bool = True, each=None) -> GeneratedCaptions:
+        """``beam_search_host`` for every image of the batch, on the device -> GeneratedCaptions with ``beam_scores``.  ``each(i)`` runs
+        after full step i (tests read the step's buffers there)."""
+        eng = self.eng
+        dc = eng.dec
+        N = int(num_return_sequences)
+        W = check_beam_caption_args(num_beams, N, length_penalty, early_stopping, max_new_tokens=max_new_tokens, eos=eos, pad=pad,
+                                    poll_every=poll_every, causal=dc.causal)
+        if W * 2 > dc.V:
+            raise ValueError(f'num_beams = {W} needs 2 * num_beams candidates per row: the vocabulary holds {dc.V} tokens')
+        a = eng.prepare(False)
+        prompt_ids = prompt_ids.to(a.device)
+        B, P = prompt_ids.shape
+        R, total = B * W, P + max_new_tokens
+        pad = int((0 if eos is None else eos) if pad is None else pad)
+        if max_new_tokens == 0:             # nothing to emit: the prompts, N times, at score 0
+            self.last_replays = 0
+            zero = torch.zeros(B, N, 0, dtype=F32, device=a.device)
+            return GeneratedCaptions(prompt_ids[:, None].expand(B, N, P).clone(), torch.full((B, N), P, dtype=torch.int32, device=a.device),
+                                     zero, zero.sum(dim=-1), None, torch.zeros(B, N, dtype=F32, device=a.device))
+        st = self._state_for(R, total, lambda clen: self._build_caption_beam(B, W, max(total, dc.block), clen),
+                             lambda st: getattr(st, 'caption_beam', False) and st.W == W)
+        self._prepare_inputs(st, images, B, W)
+        prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
+        length_penalty, early_stopping = float(length_penalty), bool(early_stopping)
+
+        def reset():
+            st.ids.zero_()
+            st.ids[:, :P] = prompt_rows
+            st.counters.copy_(st.counters_init)
+            st.hist.copy_(st.hist_init)
+            st.scores.copy_(st.scores_init.view(-1))
+            st.ctrl.zero_()
+            st.tok_lp.zero_()
+            st.pool_ids.fill_(pad)
+            st.pool_lp.zero_()
+            st.pool_score.fill_(BEAM_DEAD)
+            st.pool_sum.zero_()
+            st.pool_len.zero_()
+            st.pool_n.zero_()
+            st.closed.zero_()
+        # P, max_new_tokens, eos, pad and the two beam arguments are kernel arguments: a captured step holds them
+        key = ('caption_beam', P, max_new_tokens, -1 if eos is None else int(eos), pad, length_penalty, early_stopping)
+        self.last_replays = self._replay(st, key, lambda: self._caption_beam_step(st, P, max_new_tokens, eos, pad, length_penalty,
+                                                                                  early_stopping),
+                                         reset, P - 1, max_new_tokens, use_graph, each=each, poll_every=poll_every, prefill_first=True)
+        lengths = st.pool_len[:, :N].contiguous()
+        L = int(lengths.max().item())                           # the final host sync
+        tok_lp = st.pool_lp[:, :N, P:L].contiguous()
+        return GeneratedCaptions(st.pool_ids[:, :N, :L].contiguous(), lengths, tok_lp, tok_lp.sum(dim=-1), None,
+                                 st.pool_score[:, :N].contiguous())
 
 
 def _draw_seed(buf: torch.Tensor, seed: Optional[int]):

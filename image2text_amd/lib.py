@@ -94,6 +94,7 @@ SIGNATURES = {
     'i2t_beam_gq_decode_attention_long': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, P, I, I, I, I, I, P, L],
     'i2t_beam_candidates': [P, P, I, P, I, P, P, P, I, I, I, I, F, I, I, F, P, P, P, P],
     'i2t_beam_consolidate': [P, P, P, P, P, I, P, I, P, P, P, P, P, I, I, I, F, I, P, P],
+    'i2t_beam_pool_select': [P, P, P, P, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I],
     'i2t_beam_advance': [P, P, P],
     'i2t_beam_decode_attention': [P, P, I, P, P, L, I, L, P, I, P, I, I, P, I, I, I, I],
     'i2t_beam_gq_decode_attention': [P, P, I, P, P, I, P, P, L, I, P, I, P, I, I, P, I, P, I, I, I, I, I],
@@ -146,7 +147,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _lib = None
 
 

@@ -151,6 +151,7 @@ class VisionEncoderDecoder(nn.Module):
         object.__setattr__(self, '_hook', None)
         object.__setattr__(self, '_greedy', None)
         object.__setattr__(self, '_captioner', None)
+        object.__setattr__(self, '_beam_captioner', None)
         if config.chkpt_path is not None:
             update_state_dict_from_partial_checkpoint(self, config.chkpt_path, map_location=None)
 
@@ -239,7 +240,8 @@ class VisionEncoderDecoder(nn.Module):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
-                          prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None):
+                          prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1,
+                          length_penalty=1.0, early_stopping=False):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -286,8 +288,38 @@ class VisionEncoderDecoder(nn.Module):
         decoder's width: a d % 128 == 0 decoder gives up the segment-maxima head's saving, and two small launches join
         the step.  Refusals (ValueError, before anything runs): a penalty that is not finite or <= 0, ``min_new_tokens`` < 0 or >
         ``max_new_tokens``, a suppressed id outside the vocabulary, a list that covers the whole vocabulary.  A NON-causal decoder
-        refuses an active processor (NotImplementedError): its re-evaluation loop has no processed step."""
+        refuses an active processor (NotImplementedError): its re-evaluation loop has no processed step.
+        ``num_beams`` = W > 1 is deterministic beam search with a finished pool, transformers' ``num_beams`` /
+        ``length_penalty`` / ``early_stopping`` with ``do_sample=False`` as transformers 5.x runs it (``decoding.beam_search_host`` is the
+        normative statement): running scores start at [0, -1e9, ...]; a step takes the top 2 W of an image's W * V totals; a
+        continuation that emits ``eos_token_id`` or is the ``max_new_tokens``-th token and ranks below W enters the image's pool at
+        total / emitted ** length_penalty (fp32; ``emitted`` counts the token just added), the pool keeping its W best; the W best
+        other continuations run on.  An image closes at the bound, with ``early_stopping=True`` once its pool holds W, and with False
+        once the pool holds W and the best running total / emitted ** length_penalty no longer exceeds the pool's worst score
+        (``emitted`` again counting the step just taken, as ``_check_early_stop_heuristic`` does).  The result holds the first
+        ``num_return_sequences`` = N <= W pool entries per image, best first, and ``beam_scores`` [B, N] (fp32), the penalised score
+        they are sorted by (None in every other mode).  ``lengths`` counts the prompt and the emitted tokens up to and including an
+        EOS (P + max_new_tokens for a hypothesis that ran to the bound); later columns hold the pad id and log-prob exactly 0.0.
+        ``token_logprobs[b, n, t]`` is the quantity the search summed at that step: log_softmax of the row's logits AFTER the model's
+        no-repeat-n-gram ban, at the chosen token; ``logprob`` is its row sum, the unpenalised beam score.  With an empty
+        ``no_repeat_n_grams`` this is ``score``'s quantity; with a ban it is larger by the banned tokens' mass.  Refusals, all before
+        anything runs (``decoding.check_beam_caption_args``): ValueError for W < 1 or W > 8, N > W, a non-finite ``length_penalty``,
+        ``early_stopping`` not False / True, any sampling argument (``temperature`` != 1, ``top_k``, ``nucleus_p``, ``seed``) with W > 1;
+        NotImplementedError for ``prompt_lengths``, ``prompt_prefill='pass'``, an active logits processor or a non-causal decoder with
+        W > 1.  At ``num_beams=1`` the call is the one without these arguments, launch for launch."""
         import numpy as np
+        from ..decoding import CaptionBeamDecoder, check_beam_caption_args
+        if check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature, top_k, nucleus_p, seed,
+                                   prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens,
+                                   eos_token_id, pad_token_id, poll_every, self._engine.dec.causal, self._engine.dec.V) > 1:
+            blk_size = self.decoder.block_size - self.space_for_prompt
+            if prompt_ids.shape[1] + max_new_tokens > blk_size:
+                raise ValueError(f'prompt + new tokens ({prompt_ids.shape[1] + max_new_tokens}) exceed the text window ({blk_size})')
+            if self._beam_captioner is None:
+                object.__setattr__(self, '_beam_captioner', CaptionBeamDecoder(self))
+            return self._beam_captioner.generate_captions(images, prompt_ids.to(next(self.parameters()).device), max_new_tokens, int(num_beams),
+                                                          eos_token_id, pad_token_id, int(num_return_sequences), length_penalty,
+                                                          early_stopping, poll_every)
         from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, caption_processors, check_caption_args,
                                 check_ragged_caption_args, generate_by_recompute, prefill_plan)
         N = int(num_return_sequences)

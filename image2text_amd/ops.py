@@ -463,6 +463,22 @@ def beam_consolidate(cand_tok, cand_lp, scores, ids, hist, has_eos, parent, pos_
                                          -1 if eos is None else int(eos), _p(seed), _p(raw_pick)), 'i2t_beam_consolidate')
 
 
+def beam_pool_select(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed, pos_ptr,
+                     len_ptr, ctrl, B, W, P, max_new, eos, pad, length_penalty, early_stopping):
+    """the selection step of generate_captions(num_beams = W): finished pool, running children, close test
+    (include/i2t.h::i2t_beam_pool_select); pool_ids [B, W, ids_ld] and pool_lp [B, W, lp_ld] share the row strides of ids and tok_lp"""
+    assert ids.dtype == torch.long and pool_ids.dtype == torch.long and hist.dtype == torch.int32 and cand_tok.dtype == torch.int32
+    assert cand_tok.shape == (B * W, 2 * W) and cand_lp.shape == (B * W, 2 * W) and cand_tok.is_contiguous() and cand_lp.is_contiguous()
+    assert pool_ids.is_contiguous() and pool_lp.is_contiguous() and pool_ids.shape == (B, W, ids.stride(0)) and pool_lp.shape == (B, W, tok_lp.stride(0))
+    assert ids.shape[0] == B * W and hist.shape[0] == B * W and tok_lp.shape[0] == B * W and scores.numel() == B * W
+    assert pool_score.numel() == B * W and pool_sum.numel() == B * W and pool_len.numel() == B * W and pool_n.numel() == B and closed.numel() == B
+    _l.check(_lib().i2t_beam_pool_select(_stream(), _p(cand_tok), _p(cand_lp), _p(scores), _p(ids), ids.stride(0), _p(hist), hist.stride(0),
+                                         _p(tok_lp), tok_lp.stride(0), _p(pool_ids), _p(pool_lp), _p(pool_score), _p(pool_sum), _p(pool_len),
+                                         _p(pool_n), _p(closed), _p(pos_ptr), _p(len_ptr), _p(ctrl), B, W, P, max_new,
+                                         -1 if eos is None else int(eos), int(pad), float(length_penalty), int(bool(early_stopping))),
+             'i2t_beam_pool_select')
+
+
 def beam_advance(counters, ctrl):
     _l.check(_lib().i2t_beam_advance(_stream(), _p(counters), _p(ctrl)), 'i2t_beam_advance')
 

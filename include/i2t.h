@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 11
+#define I2T_ABI_VERSION 12
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -579,6 +579,20 @@ int i2t_beam_gq_decode_attention_long(void* stream, const void* q, int q_rs, con
  *     parent, the new score, parent[child] and has_eos[child] (int [R]: the row holds eos anywhere); ctrl[1] counts the captions
  *     with a beam that has no eos (every caption when eos < 0).  raw_pick (optional, int [R]): the flat index each child was made
  *     from.  W <= 16, W * E <= 1024.
+ *   beam_pool_select (generate_captions(num_beams = W); in beam_consolidate's place, after beam_candidates with
+ *     temperature <= 0, E = 2 W, eos = -1): one workgroup per image, no atomics; returns at once if ctrl[0], and for an image whose
+ *     closed[b] is set.  Ranks the top 2 W of the image's W * 2 W totals scores[r] + cand_lp (descending, lower flat index first).  A
+ *     candidate HITS if its token is eos (eos < 0: never) or it is the max_new-th emitted token (emitted = *len_ptr + 1 - P).  Hits
+ *     ranked below W are offered to the pool at total / powf((float)emitted, length_penalty), fp32; the pool (pool_ids int64
+ *     [B][W][ids_ld], pool_lp f32 [B][W][lp_ld], pool_score / pool_sum f32 [B][W], pool_len int [B][W], pool_n int [B]) keeps the W
+ *     best, sorted descending, an entry it holds before a new one on ties; a new row is the parent's ids / tok_lp columns [0, len),
+ *     the token and its log-prob at column len, then pad / 0.0 up to column P + max_new; pool_sum is the total, pool_len = len + 1.
+ *     The first W candidates that do not hit become rows b * W + k: the parent's ids, tok_lp [0, len) and history [0, pos) move to
+ *     the child, ids[child][len] = token, tok_lp[child][len] = its log-prob, hist[child][pos] = parent, scores[child] = total.
+ *     closed[b] is set at the bound (the rows then stay as they are), with early_stopping once pool_n[b] = W, and without it once
+ *     pool_n[b] = W and not (scores[b * W] / powf((float)emitted, length_penalty) > pool_score[b][W - 1]).  Every image left open
+ *     stores 1 into ctrl[1] (a flag, not a count: no atomic).  W <= 8; P + max_new <= ids_ld, lp_ld; counters outside
+ *     P <= len < P + max_new, 0 <= pos < hist_ld write nothing.
  *   beam_advance: while ctrl[0] is clear: pos += 1, len += 1, and ctrl[0] = (ctrl[1] == 0); then ctrl[1] = 0.
  *   beam_decode_attention / beam_gq_decode_attention: i2t_decode_attention / i2t_gq_decode_attention with key t of row r read from
  *     cache row hist[r][t] (int32 [R][hist_ld]; the new token's key / value are written to the row's own slot *pos); hist NULL: row
@@ -592,6 +606,10 @@ int i2t_beam_candidates(void* stream, const float* logits, int ld, const int64_t
 int i2t_beam_consolidate(void* stream, const int* cand_tok, const float* cand_lp, float* scores, int64_t* ids, int ids_ld, int* hist,
                          int hist_ld, int* has_eos, int* parent, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int E,
                          float temperature, int eos, const unsigned* seed, int* raw_pick);
+int i2t_beam_pool_select(void* stream, const int* cand_tok, const float* cand_lp, float* scores, int64_t* ids, int ids_ld, int* hist,
+                         int hist_ld, float* tok_lp, int lp_ld, int64_t* pool_ids, float* pool_lp, float* pool_score, float* pool_sum,
+                         int* pool_len, int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P,
+                         int max_new, int eos, int pad, float length_penalty, int early_stopping);
 int i2t_beam_advance(void* stream, int* counters, int* ctrl);
 int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, void* kcache, void* vcache, long cache_bs, int cache_rs,
                               long cache_hs, void* o, int o_rs, const int* pos_ptr, int n_keys_fixed, int append_dm, const int* hist,
