@@ -68,6 +68,15 @@ __device__ __forceinline__ void lse_merge(float& mx, float& se, float omx, float
     se = se * fa + ose * fb;
     mx = m;
 }
+// one more value for a thread's running (max, sum exp): the online-softmax update
+__device__ __forceinline__ void lse_add(float& mx, float& se, float v) {
+    if (v > mx) {
+        se = se * __expf(mx - v) + 1.f;                 // (mx = -inf: se is 0 and stays 0 through the product)
+        mx = v;
+    } else if (v > -INFINITY) {
+        se += __expf(v - mx);
+    }
+}
 
 // ---- GELU(tanh): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3), evaluated as x * sigmoid(2u): one v_exp_f32 and
 // one v_rcp_f32 (1 ulp each) instead of an IEEE division -- the epilogue VALU work of a K = 512 GEMM rivals its MFMA work,

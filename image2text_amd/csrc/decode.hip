@@ -177,15 +177,6 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
 // HF NoRepeatNGramLogitsProcessor + argmax for one caption per workgroup.  A row with no finite allowed column (all banned)
 // gets token 0, torch.argmax's answer for a row of -inf, and margin 0.
 constexpr int BAN_THREADS = 1024;
-// one more column for a thread's running (max, sum exp): the online-softmax update
-__device__ __forceinline__ void lse_add(float& mx, float& se, float v) {
-    if (v > mx) {
-        se = se * __expf(mx - v) + 1.f;                 // (mx = -inf: se is 0 and stays 0 through the product)
-        mx = v;
-    } else if (v > -INFINITY) {
-        se += __expf(v - mx);
-    }
-}
 // LP (i2t_ngram_ban_argmax_lp, a caption step): the same choice, and tok_lp[b][len] = z[chosen] - logsumexp(z[b][:V]) over the RAW
 // row -- the ban does not enter -- from an online (max, sum exp) pass folded into the scan: per thread in its scan order, the
 // lanes by a fixed xor tree, the waves in order.  Nothing is written once *done is set.

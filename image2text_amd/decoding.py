@@ -850,11 +850,14 @@ class GeneratedCaptions(_CaptionFields):
     prompt_lengths: Optional[torch.Tensor] = None
     beam_scores: Optional[torch.Tensor] = None      # fp32 [B, N] under num_beams > 1: the length-penalised score the N
                                                     # captions of an image are sorted by, best first; None in every other mode
+    phrase_index: Optional[torch.Tensor] = None     # int32 [B, N] under ``phrases``: the index into ``phrases`` of the
+                                                    # phrase the row emitted; None in every other mode
 
-    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None):
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None):
         self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
         self.prompt_lengths = prompt_lengths
         self.beam_scores = beam_scores
+        self.phrase_index = phrase_index
         return self
 
 
@@ -976,13 +979,181 @@ def process_logits_host(z, ids_row, length: int, emitted: int, theta: float, sup
     return z
 
 
-def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0):
+def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False):
     """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
     ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
     ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
-    the count then reads the device's table)."""
+    the count then reads the device's table).  ``trie`` (a ``phrases`` call): ('trie', eos, ...that key) -- the trie's
+    contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key."""
     key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
-    return key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
+    key = key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
+    return ('trie', eos) + key if trie else key
+
+
+# ------------------------------------------------------------------------------------------------ phrase sets (DESIGN.md 4u)
+class PhraseTrie(NamedTuple):
+    """A phrase set as a flat CSR trie (``phrase_trie``); node 0 is the root.  All arrays numpy int32."""
+    child_off: np.ndarray               # [nodes + 1]: the children of node n are edges child_off[n] .. child_off[n + 1)
+    child_tok: np.ndarray               # [edges]: an edge's token, ascending within a node
+    child_next: np.ndarray              # [edges]: the node the edge leads to
+    term: np.ndarray                    # [nodes]: the index of the phrase that ends at the node (the lowest among duplicates), or -1
+    max_fanout: int                     # the largest number of children of a node
+    longest: int                        # the tokens of the longest phrase
+
+    @property
+    def nodes(self) -> int:
+        return int(self.term.shape[0])
+
+    @property
+    def edges(self) -> int:
+        return int(self.child_tok.shape[0])
+
+    def children(self, node: int):
+        """-> (tokens, next nodes) of ``node``"""
+        lo, hi = int(self.child_off[node]), int(self.child_off[node + 1])
+        return self.child_tok[lo:hi], self.child_next[lo:hi]
+
+
+def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
+    """The refusals of ``generate_captions(phrases=...)`` that concern the set itself (host only, ValueError) and the set as a
+    ``PhraseTrie``.  ``phrases``: K >= 1 sequences (or 1-D tensors) of token ids in [0, ``vocab``), none empty, none holding ``eos``;
+    ``eos`` is needed (a row ends its phrase by emitting it) and ``max_new_tokens`` must reach the longest phrase + 1, so that every
+    row can end with EOS and the finish rule never cuts a phrase.  Duplicate phrases keep the lowest index."""
+    if eos is None:
+        raise ValueError('phrases need eos_token_id: a row ends its phrase by emitting it')
+    eos = int(eos)
+    if not 0 <= eos < vocab:
+        raise ValueError(f'eos_token_id = {eos} outside the vocabulary [0, {vocab})')
+    if isinstance(phrases, torch.Tensor):
+        phrases = phrases.detach().cpu().tolist()
+    rows = []
+    for k, ph in enumerate(phrases):
+        if isinstance(ph, torch.Tensor):
+            ph = ph.detach().cpu().reshape(-1).tolist()
+        row = []
+        for t in ph:
+            if int(t) != t:
+                raise ValueError(f'phrases[{k}] holds {t!r}: token ids are integers')
+            t = int(t)
+            if not 0 <= t < vocab:
+                raise ValueError(f'phrases[{k}] holds {t}: outside the vocabulary [0, {vocab})')
+            if t == eos:
+                raise ValueError(f'phrases[{k}] holds eos_token_id = {eos}: the EOS ends a phrase, it cannot be inside one')
+            row.append(t)
+        if not row:
+            raise ValueError(f'phrases[{k}] is empty: a phrase holds at least one token')
+        rows.append(row)
+    if not rows:
+        raise ValueError('phrases is empty: at least one phrase is needed')
+    longest = max(len(r) for r in rows)
+    if max_new_tokens < longest + 1:
+        raise ValueError(f'max_new_tokens = {max_new_tokens} is below the longest phrase + 1 = {longest + 1}: every row ends with EOS')
+    kids, term = [{}], [-1]                                     # insertion: node -> {token: next node}
+    for k, row in enumerate(rows):
+        n = 0
+        for t in row:
+            if t not in kids[n]:
+                kids[n][t] = len(kids)
+                kids.append({})
+                term.append(-1)
+            n = kids[n][t]
+        if term[n] < 0:
+            term[n] = k
+    off, tok, nxt = [0], [], []
+    for d in kids:
+        for t in sorted(d):
+            tok.append(t)
+            nxt.append(d[t])
+        off.append(len(tok))
+    i32 = np.int32
+    return PhraseTrie(np.array(off, dtype=i32), np.array(tok, dtype=i32), np.array(nxt, dtype=i32), np.array(term, dtype=i32),
+                      max(len(d) for d in kids), longest)
+
+
+def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
+                              num_beams=1, causal: bool = True) -> PhraseTrie:
+    """``phrase_trie`` and then what ``phrases`` does not combine with, all before anything runs -> the trie.  NotImplementedError,
+    naming the reason: ``prompt_lengths``, an active logits processor, ``num_beams`` > 1, a non-causal decoder.  ``phrases`` may be a
+    ``PhraseTrie`` that an earlier call of this function built (the model hands its own to the decoder): it is not built again, only
+    held against this call's ``eos``, ``vocab`` and ``max_new_tokens``."""
+    if isinstance(phrases, PhraseTrie):
+        trie = phrases
+        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+                or bool((trie.child_tok == int(eos)).any()) or max_new_tokens < trie.longest + 1:
+            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}, max_new_tokens = '
+                             f'{max_new_tokens} against a longest phrase of {trie.longest} tokens')
+    else:
+        trie = phrase_trie(phrases, eos, vocab, max_new_tokens)
+    if prompt_lengths is not None:
+        raise NotImplementedError('phrases with prompt_lengths: a forced prompt column would have to hold the trie still, and the ragged '
+                                  'finish rule has no such case')
+    if processors_active:
+        raise NotImplementedError('phrases with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
+                                  'emitted, and a processor could leave a node without an allowed token')
+    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
+        raise NotImplementedError('phrases under num_beams > 1: the beam step has no trie state per hypothesis')
+    if not causal:
+        raise NotImplementedError('phrases run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
+                                  '(generate_by_recompute), which has no constrained step')
+    return trie
+
+
+def trie_mask_host(z, node: int, trie: PhraseTrie, eos: int) -> np.ndarray:
+    """What i2t_caption_trie_mask leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): -inf everywhere except
+    the columns of ``node``'s children and, when a phrase ends at ``node``, the EOS column; those keep their raw values."""
+    z = np.array(z, dtype=np.float32)
+    assert z.ndim == 1
+    out = np.full_like(z, -np.inf)
+    toks, _ = trie.children(node)
+    out[toks] = z[toks]
+    if trie.term[node] >= 0:
+        out[eos] = z[eos]
+    return out
+
+
+def trie_advance_host(node: int, token: int, trie: PhraseTrie, eos: int):
+    """What i2t_caption_trie_advance does with a row at ``node`` whose chooser wrote ``token`` -> (node, phrase index or -1, whether
+    the token was one the node allows).  EOS at a node that ends a phrase names that phrase and the node stays; a child moves the row;
+    anything else (never from a chooser) changes nothing, and the kernel then leaves the step's log-prob as it was."""
+    token = int(token)
+    if token == eos:
+        p = int(trie.term[node])
+        return node, p, p >= 0
+    toks, nxt = trie.children(node)
+    at = int(np.searchsorted(toks, token))
+    if at < toks.shape[0] and int(toks[at]) == token:
+        return int(nxt[at]), -1, True
+    return node, -1, False
+
+
+def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad, max_new: int):
+    """The whole greedy search of ``generate_captions(phrases=...)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32
+    logits row [V] that follows a token sequence (a list of ints, the prompt included).  Every step takes ``trie_mask_host`` of the
+    row, its argmax (the lower id on ties), the fp32 log_softmax of the RAW row there, and ``trie_advance_host``; the search ends with
+    the EOS.  -> SimpleNamespace(ids int64 [L], length, token_logprobs f32 [L - P], logprob f32, phrase_index, steps, gaps): ``gaps``
+    holds per step the best allowed logit minus the second-best allowed one (inf where a node allows one token).  A search whose gaps
+    all exceed a perturbation of the logits keeps its result under it.  (``pad`` takes no part for one image -- nothing follows the EOS;
+    the signature is ``beam_search_host``'s.)"""
+    seq = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    P = len(seq)
+    assert P >= 1 and max_new >= 1
+    f32 = np.float32
+    node, phrase, lps, gaps = 0, -1, [], []
+    while phrase < 0 and len(seq) - P < max_new:
+        z = np.asarray(step_logits(list(seq)), dtype=f32).reshape(-1)
+        masked = trie_mask_host(z, node, trie, eos)
+        order = sorted(np.flatnonzero(masked > -np.inf).tolist(), key=lambda t: (-masked[t], t))
+        assert order, 'no allowed token has a finite logit'
+        c = order[0]
+        gaps.append(float(masked[c]) - float(masked[order[1]]) if len(order) > 1 else float('inf'))
+        m = z.max()
+        lps.append(f32(z[c] - (m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))))
+        node, phrase, ok = trie_advance_host(node, c, trie, eos)
+        assert ok
+        seq.append(c)
+    lp = np.array(lps, dtype=f32)
+    return SimpleNamespace(ids=np.array(seq, dtype=np.int64), length=len(seq), token_logprobs=lp, logprob=lp.sum(dtype=f32),
+                           phrase_index=phrase, steps=len(lps), gaps=gaps)
 
 
 class CaptionDecoder(GreedyDecoder):
@@ -1013,6 +1184,7 @@ class CaptionDecoder(GreedyDecoder):
         st.top2 = st.seg_se = None
         st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
         st.raw_lse = st.saved = st.suppress = None              # logits processors: f32 [R] / f32 [R, ids_ld] / int32 list, made at the first active call
+        st.node = st.phrase_index = st.kept = st.trie = None    # phrases: int32 [R] / int32 [R] / f32 [R, fan-out + 1] / the four trie arrays (and raw_lse)
         return st
 
     def _processor_state(self, st, proc: Processors):
@@ -1020,8 +1192,9 @@ class CaptionDecoder(GreedyDecoder):
         st.saved (R * ids_ld * 4 bytes) and the suppress list's buffer, which is regrown only together with the graphs that hold it; the
         list's contents are copied in per call."""
         dev = st.arena.device
-        if st.raw_lse is None:
+        if st.raw_lse is None:                                  # (a phrases call may have made it: _trie_state)
             st.raw_lse = torch.zeros(st.B, dtype=F32, device=dev)
+        if st.saved is None:
             st.saved = torch.zeros(st.B, st.ids_ld, dtype=F32, device=dev)
         n = len(proc.suppress)
         if st.suppress is None or st.suppress.numel() < n:
@@ -1030,15 +1203,42 @@ class CaptionDecoder(GreedyDecoder):
         if n:
             st.suppress[:n].copy_(torch.tensor(proc.suppress, dtype=torch.int32))
 
-    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None):
+    def _trie_state(self, st, trie: PhraseTrie):
+        """The buffers of a phrase-constrained step, persistent because captured steps bake their pointers: st.node,
+        st.phrase_index, st.raw_lse, and -- regrown only together with the graphs that hold them -- st.kept and the four trie arrays
+        st.trie = (child_off, child_tok, child_next, term).  The kernels take the arrays' CAPACITIES as nodes / edges, so a captured step
+        serves any trie that fits; the trie's contents are copied in per call, the spare nodes childless and ending no phrase."""
+        dev = st.arena.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        if st.node is None:
+            st.node, st.phrase_index = torch.zeros(st.B, **i32), torch.full((st.B,), -1, **i32)
+        if st.raw_lse is None:                                  # (shared with the logits processors: _processor_state)
+            st.raw_lse = torch.zeros(st.B, dtype=F32, device=dev)
+        if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges or st.kept.shape[1] < trie.max_fanout + 1:
+            nodes, edges = max(64, trie.nodes), max(64, trie.edges)
+            st.trie = (torch.zeros(nodes + 1, **i32), torch.zeros(edges, **i32), torch.zeros(edges, **i32), torch.full((nodes,), -1, **i32))
+            st.kept = torch.zeros(st.B, (max(64, trie.max_fanout + 1) + 3) // 4 * 4, dtype=F32, device=dev)
+            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'trie')}
+        nodes, edges = st.trie[3].numel(), st.trie[1].numel()
+        off = np.full(nodes + 1, trie.edges, dtype=np.int32)
+        off[:trie.nodes + 1] = trie.child_off
+        tok, nxt, term = np.zeros(edges, dtype=np.int32), np.zeros(edges, dtype=np.int32), np.full(nodes, -1, dtype=np.int32)
+        tok[:trie.edges], nxt[:trie.edges], term[:trie.nodes] = trie.child_tok, trie.child_next, trie.term
+        for buf, host in zip(st.trie, (off, tok, nxt, term)):
+            buf.copy_(torch.from_numpy(host))
+
+    def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None,
+                      trie: bool = False):
         """The launches of a full step.  ``forced``: None, or (prompt, plen, max_new) of a ``prompt_lengths`` call -- the finish rule is
         then i2t_caption_finish_ragged; the choosers run as they are, on every row, and what they wrote at a forced column is replaced
         after them.  ``proc``: None, or (Processors, P) of a call with active logits processors (never with ``top2``):
-        i2t_caption_logits_process between the GEMM and the chooser, i2t_caption_raw_logprob between the chooser and the finish rule."""
+        i2t_caption_logits_process between the GEMM and the chooser, i2t_caption_raw_logprob between the chooser and the finish rule.
+        ``trie`` (a ``phrases`` call; never with ``top2``, ``forced`` or ``proc``): i2t_caption_trie_mask before the
+        chooser, which then runs without n-gram sizes -- the phrase set says what may be emitted --, i2t_caption_trie_advance after it."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
-        nn = st.ngrams.numel()
+        nn = 0 if trie else st.ngrams.numel()
         self._body(st)
         self._final_norm(st)
         if top2:
@@ -1052,6 +1252,9 @@ class CaptionDecoder(GreedyDecoder):
                 ops.caption_logits_process(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, None if forced is None else forced[1], P, st.N,
                                            st.suppress, len(pr.suppress), eos, pr.min_new, pr.theta, pr.inv_theta, done, st.raw_lse, st.saved,
                                            R, dc.V)
+            if trie:
+                off, tok, nxt, term = st.trie
+                ops.caption_trie_mask(st.logits, dc.Vp, st.node, off, tok, term, eos, done, st.raw_lse, st.kept, R, dc.V)
             if sampling is None:
                 ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
             else:
@@ -1059,6 +1262,9 @@ class CaptionDecoder(GreedyDecoder):
                                     sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
             if proc is not None:                                # the chooser's log-prob was taken on the processed row: the raw one over it
                 ops.caption_raw_logprob(st.ids, st.ids_ld, len_ptr, st.raw_lse, st.saved, st.logits, dc.Vp, done, st.tok_lp, R, dc.V)
+            if trie:                                            # the row moves along the chosen edge; the raw log-prob over the chooser's
+                ops.caption_trie_advance(st.ids, st.ids_ld, len_ptr, st.finished, st.logits, dc.Vp, st.raw_lse, off, tok, nxt, term, eos, done,
+                                         st.node, st.phrase_index, st.tok_lp, R, dc.V)
         if forced is None:
             ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
         else:
@@ -1071,7 +1277,7 @@ class CaptionDecoder(GreedyDecoder):
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
                           use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps', repetition_penalty: float = 1.0,
-                          min_new_tokens: int = 0, suppress_tokens=None) -> GeneratedCaptions:
+                          min_new_tokens: int = 0, suppress_tokens=None, phrases=None, each=None) -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
         None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
@@ -1080,7 +1286,13 @@ class CaptionDecoder(GreedyDecoder):
         ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` (``caption_processors``): with any of them active
         the step takes the fp32-logits head whatever the decoder's width -- the segment-maxima head cannot see a penalised token's
         neighbours, so a d % 128 == 0 decoder gives up that head's saving -- with i2t_caption_logits_process before the
-        chooser and i2t_caption_raw_logprob after it, under graph keys of their own; inactive, the call is the one without them."""
+        chooser and i2t_caption_raw_logprob after it, under graph keys of their own; inactive, the call is the one without them.
+        ``phrases`` (a sequence of token-id sequences, or the ``PhraseTrie`` the model built of one; ``check_phrase_caption_args``,
+        DESIGN.md 4u): every row emits
+        one of the phrases, then EOS.  The step takes the fp32-logits head with i2t_caption_trie_mask before the chooser -- which runs
+        over the allowed tokens only, without the n-gram ban -- and i2t_caption_trie_advance after it, under graph keys of their own;
+        the result carries ``phrase_index``.  None: the call is the one without the argument.  ``each(i)`` runs after full step i (tests
+        read the step's buffers there)."""
         eng = self.eng
         dc = eng.dec
         N = int(num_return_sequences)
@@ -1094,6 +1306,9 @@ class CaptionDecoder(GreedyDecoder):
             check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
             pmin = pmax = P
         proc = caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, dc.V)
+        trie = None
+        if phrases is not None:
+            trie = check_phrase_caption_args(phrases, eos, dc.V, max_new_tokens, prompt_lengths, proc is not None, 1, dc.causal)
         if not dc.causal:
             raise ValueError('CaptionDecoder needs a causal decoder')
         m, start = prefill_plan(prompt_prefill, pmin, min(eng.enc.ncls, dc.block) if dc.prefixed else 0, dc.fam, True)
@@ -1131,10 +1346,12 @@ class CaptionDecoder(GreedyDecoder):
             _draw_seed(st.seed, sampling.seed)
         if proc is not None:
             self._processor_state(st, proc)
-        top2, head = self._greedy_head(st, sampling, logits=proc is not None, lse=True)
+        if trie is not None:
+            self._trie_state(st, trie)
+        top2, head = self._greedy_head(st, sampling, logits=proc is not None or trie is not None, lse=True)
         # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key), and
-        # so are the processors' scalars ('proc': never an inactive call's key)
-        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax)
+        # so are the processors' scalars ('proc': never an inactive call's key); 'trie': never a key of a call without phrases
+        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax, trie is not None)
         prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
@@ -1146,17 +1363,22 @@ class CaptionDecoder(GreedyDecoder):
             # what a row without an EOS ends with: p_b + max_new_tokens
             st.lengths.copy_(len_rows) if ragged else st.lengths.fill_(total)
             st.tok_lp.zero_()
+            if trie is not None:                                # every row at the root, no phrase named yet
+                st.node.zero_()
+                st.phrase_index.fill_(-1)
         # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
         # ('pass': those columns' K/V are in the cache already, n_prefill = 0)
         self.last_prefill_steps = n_prefill
-        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced, None if proc is None else (proc, pmax)),
+        self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced, None if proc is None else (proc, pmax),
+                                                                                  trie is not None),
                                          reset, n_prefill,
-                                         pmax - pmin + max_new_tokens, use_graph, poll_every=poll_every if eos is not None else 0)
+                                         pmax - pmin + max_new_tokens, use_graph, each=each, poll_every=poll_every if eos is not None else 0)
         lengths = st.lengths.clone()
         L = int(lengths.max().item()) if max_new_tokens else pmax       # the final host sync
         ids = st.ids[:, :L].reshape(B, N, L).clone()
         tok_lp = st.tok_lp[:, pmin:L].reshape(B, N, L - pmin).clone()
-        return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev)
+        return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev,
+                                 phrase_index=None if trie is None else st.phrase_index.view(B, N).clone())
 
 
 def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,

@@ -241,7 +241,7 @@ class VisionEncoderDecoder(nn.Module):
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
                           prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1,
-                          length_penalty=1.0, early_stopping=False):
+                          length_penalty=1.0, early_stopping=False, phrases=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -306,9 +306,28 @@ class VisionEncoderDecoder(nn.Module):
         anything runs (``decoding.check_beam_caption_args``): ValueError for W < 1 or W > 8, N > W, a non-finite ``length_penalty``,
         ``early_stopping`` not False / True, any sampling argument (``temperature`` != 1, ``top_k``, ``nucleus_p``, ``seed``) with W > 1;
         NotImplementedError for ``prompt_lengths``, ``prompt_prefill='pass'``, an active logits processor or a non-causal decoder with
-        W > 1.  At ``num_beams=1`` the call is the one without these arguments, launch for launch."""
+        W > 1.  At ``num_beams=1`` the call is the one without these arguments, launch for launch.
+        ``phrases`` is closed-set decoding: a sequence of K >= 1 token-id sequences, one set per call shared by all
+        images, and every row emits exactly one of them followed by ``eos_token_id``, then the pad id -- "answer with one of these K
+        phrases" in as many steps as the phrase has tokens plus one, where ``rerank`` costs a decoder forward per (image, candidate).
+        At each step the allowed tokens are the children of the row's node in the set's token trie, and the EOS when a phrase ends
+        there (a phrase that is a prefix of another allows both); the chooser -- greedy, or sampling with temperature / ``top_k`` /
+        ``nucleus_p`` and ``num_return_sequences`` rows per image -- runs over the allowed tokens only, and the model's
+        ``no_repeat_n_grams`` ban is off: the set says what may be emitted.  The result carries ``phrase_index`` (int32 [B, N], the index
+        into ``phrases`` of the row's phrase, the lowest among duplicates; None in every other mode).  ``token_logprobs`` keeps its
+        definition -- log_softmax of the RAW logits -- so ``logprob`` is the model's log-likelihood of phrase + EOS, comparable with
+        ``score`` and ``rerank``.  The step takes the fp32-logits head whatever the decoder's width, as with the logits processors.
+        Refusals, before anything runs (``decoding.check_phrase_caption_args``): ValueError for an empty set or phrase, an id outside
+        the vocabulary, the EOS inside a phrase, no ``eos_token_id``, ``max_new_tokens`` below the longest phrase + 1;
+        NotImplementedError with ``prompt_lengths``, an active logits processor, ``num_beams`` > 1 or a non-causal decoder.
+        ``prompt_prefill='pass'`` works as without phrases.  None (the default) is the call without the argument, launch for launch."""
         import numpy as np
-        from ..decoding import CaptionBeamDecoder, check_beam_caption_args
+        from ..decoding import CaptionBeamDecoder, caption_processors, check_beam_caption_args, check_phrase_caption_args
+        if phrases is not None:     # before the beam checks: those keep their own texts.  The decoder below takes the trie built here
+            active = caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos_token_id,
+                                        self._engine.dec.V) is not None
+            phrases = check_phrase_caption_args(phrases, eos_token_id, self._engine.dec.V, max_new_tokens, prompt_lengths, active, num_beams,
+                                                self._engine.dec.causal)
         if check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature, top_k, nucleus_p, seed,
                                    prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens,
                                    eos_token_id, pad_token_id, poll_every, self._engine.dec.causal, self._engine.dec.V) > 1:
@@ -348,7 +367,7 @@ class VisionEncoderDecoder(nn.Module):
                 object.__setattr__(self, '_captioner', CaptionDecoder(self))
             return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
                                                      prompt_lengths=plen, prompt_prefill=prompt_prefill, repetition_penalty=repetition_penalty,
-                                                     min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens)
+                                                     min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, phrases=phrases)
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
         prompt_rep = prompt_ids.repeat_interleave(N, dim=0)

@@ -924,6 +924,44 @@ def caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, logits, ld, done, 
                                             _p(done), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_raw_logprob')
 
 
+def _trie_args(child_off, child_tok, term, child_next=None):
+    """the shared checks of the trie kernels: int32 CSR arrays on the device -> (nodes, edges) the arrays hold"""
+    arrays = (child_off, child_tok, term) + (() if child_next is None else (child_next,))
+    _need_cuda(*arrays)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in arrays)
+    assert child_off.numel() == term.numel() + 1 and (child_next is None or child_next.numel() == child_tok.numel())
+    return term.numel(), child_tok.numel()
+
+
+def caption_trie_mask(logits, ld, node, child_off, child_tok, term, eos, done, raw_lse, kept, R, V):
+    """the pre-pass of a phrase-constrained caption step on fp32 logits rows, in place, before the chooser: -inf everywhere in [0, V)
+    except the children of node[r] and, at a node that ends a phrase, EOS; raw_lse [R] and kept [R, >= max fan-out + 1] take the raw
+    row's log-sum-exp and the raw allowed logits; no write once *done (include/i2t.h::i2t_caption_trie_mask)"""
+    nodes, edges = _trie_args(child_off, child_tok, term)
+    _need_cuda(logits, node, done, raw_lse, kept)
+    assert logits.dtype == F32 and node.dtype == torch.int32 and done.dtype == torch.int32 and raw_lse.dtype == F32 and kept.dtype == F32
+    assert kept.dim() == 2 and kept.stride(-1) == 1 and kept.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    assert node.is_contiguous() and node.numel() >= R
+    _l.check(_lib().i2t_caption_trie_mask(_stream(), _p(logits), ld, _p(node), _p(child_off), _p(child_tok), _p(term), nodes, edges, int(eos),
+                                          _p(done), _p(raw_lse), _p(kept), kept.stride(0), R, V), 'i2t_caption_trie_mask')
+
+
+def caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, eos, done, node,
+                         phrase_index, tok_lp, R, V):
+    """the post-pass of a phrase-constrained caption step, after the chooser: a row that is not finished moves to the chosen child or,
+    on EOS at a node that ends a phrase, takes that phrase's index; tok_lp[r][len] = logits[r][chosen] - raw_lse[r]; no write once
+    *done (include/i2t.h::i2t_caption_trie_advance)"""
+    nodes, edges = _trie_args(child_off, child_tok, term, child_next)
+    _need_cuda(ids, len_ptr, finished, logits, raw_lse, done, node, phrase_index, tok_lp)
+    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and finished.dtype == torch.int32
+    assert node.dtype == torch.int32 and phrase_index.dtype == torch.int32 and node.is_contiguous() and phrase_index.is_contiguous()
+    assert node.numel() >= R and phrase_index.numel() >= R and finished.numel() >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    assert tok_lp.dtype == F32 and tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
+    _l.check(_lib().i2t_caption_trie_advance(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(finished), _p(logits), ld, _p(raw_lse), _p(child_off),
+                                             _p(child_tok), _p(child_next), _p(term), nodes, edges, int(eos), _p(done), _p(node),
+                                             _p(phrase_index), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_trie_advance')
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     _need_cuda(a, b, stats)

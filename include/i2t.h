@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 12
+#define I2T_ABI_VERSION 13
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -477,6 +477,28 @@ int i2t_caption_logits_process(void* stream, float* logits, int ld, const int64_
                                const int* done, float* raw_lse, float* saved, int saved_ld, int R, int V);
 int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* raw_lse, const float* saved,
                             int saved_ld, const float* logits, int ld, const int* done, float* tok_lp, int lp_ld, int R, int V);
+/* Closed-set decoding (generate_captions' phrases; DESIGN.md 4u, ABI 13): every row emits one phrase of a set and then EOS.  The set is
+ * a flat CSR trie in device memory, all int32: the children of node n are edges child_off[n] .. child_off[n + 1) (child_off [nodes + 1]),
+ * child_tok [edges] ascending within a node, child_next [edges] the node an edge leads to, term [nodes] the index of the phrase that
+ * ends at the node or -1; node 0 is the root; node [R] holds every row's node.  `nodes` and `edges` are what the arrays hold: the
+ * kernels clip every index to them.  A pre-pass and a post-pass around the fp32-logits choosers above, which run between them as they
+ * are (with no n-gram sizes).  Bases on 16 bytes; ld >= V, ld % 4 == 0; 0 <= eos < V.
+ *   i2t_caption_trie_mask (after the lm_head GEMM, before the chooser): returns at once if *done.  Per row r of logits f32 [R][ld], one
+ *     workgroup: raw_lse[r] = log sum_c exp(z[r][c]) over the RAW row, reduced in a fixed order (no atomics); kept[r][i] = the raw
+ *     z[r][child_tok[off + i]] for the fan children of node[r] and kept[r][fan] = z[r][eos] when term[node[r]] >= 0 (kept f32
+ *     [R][kept_ld], kept_ld >= the largest fan-out + 1); then columns [0, V) of the row hold -inf except the children's and, at such a
+ *     node, the EOS column, which hold their raw values.  Columns V .. ld are not touched.  Any fan-out from 1 to V - 1.
+ *   i2t_caption_trie_advance (after the chooser, before i2t_caption_finish): returns at once if *done; a row with finished[r] is
+ *     skipped.  With c = ids[r][len]: c == eos at a node with term >= 0 sets phrase_index[r] = term[node[r]]; a child of the node sets
+ *     node[r] = its child_next; in both cases tok_lp[r][len] = logits[r][c] - raw_lse[r], the raw row's log_softmax at c, over what the
+ *     chooser wrote there.  Any other token leaves node, phrase_index and tok_lp as they were.  One wave per row. */
+int i2t_caption_trie_mask(void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
+                          const int* term, int nodes, int edges, int eos, const int* done, float* raw_lse, float* kept, int kept_ld,
+                          int R, int V);
+int i2t_caption_trie_advance(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const int* finished,
+                             const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok,
+                             const int* child_next, const int* term, int nodes, int edges, int eos, const int* done, int* node,
+                             int* phrase_index, float* tok_lp, int lp_ld, int R, int V);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).

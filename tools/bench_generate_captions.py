@@ -17,7 +17,13 @@ With any of the three flags the comparison is instead: generate_c
 logits processors, greedy N = 1 and sampling N = 4, no EOS id unless --min-new-tokens needs one (50256; every call then runs all
 steps that its rows need), alternating in one process -- first with the segment-maxima head in play (nano-224: d % 128 == 0, so the
 processors also cost the switch to the fp32-logits head), then with I2T_DECODE_TOP2's effect switched off in the process (both forms on
-the fp32-logits head: the difference is the two new launches alone)."""
+the fp32-logits head: the difference is the two new launches alone).
+
+    python tools/bench_generate_captions.py --phrases 3000 [--phrase-len 3]
+
+The comparison is instead: generate_captions without phrases for phrase-len + 1 new tokens against
+generate_captions(phrases=K random phrases of phrase-len tokens), greedy N = 1 and sampling N = 4, alternating in one process; the
+constrained call includes building the trie on the host and copying it to the device."""
 import argparse
 import os
 import statistics
@@ -111,8 +117,36 @@ def processors_comparison(a, procs):
         torch.cuda.empty_cache()
 
 
+def phrases_comparison(a):
+    """generate_captions without phrases (--phrase-len + 1 new tokens, no EOS id: as many steps as the constrained call needs at the
+    most) against generate_captions(phrases=K random phrases of --phrase-len tokens), greedy N = 1 and sampling N = 4"""
+    B, K, T = a.batch, a.phrases, a.phrase_len
+    eos = 50256
+    g = torch.Generator().manual_seed(1)
+    phrases = torch.randint(0, eos, (K, T), generator=g).tolist()
+    print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {K} phrases of {T} tokens, {a.rounds} '
+          f'alternating rounds', flush=True)
+    m, images, prompt = fresh(B)
+    for N, mode in ((1, dict(top_k=1)), (4, SAMPLING)):
+        kw = dict(max_new_tokens=T + 1, num_return_sequences=N, seed=3, **mode)
+        forms = {'as it is': lambda: m.generate_captions(images, prompt, **kw),
+                 'with phrases': lambda: m.generate_captions(images, prompt, eos_token_id=eos, phrases=phrases, **kw)}
+        ts, replays = {k: [] for k in forms}, {}
+        for fn in forms.values():
+            fn()
+        for _ in range(a.rounds):
+            for k, fn in forms.items():
+                t, _ = wall(fn)
+                ts[k].append(t)
+                replays[k] = m._captioner.last_replays
+        for k in forms:
+            print(f'  N = {N} {"greedy  " if N == 1 else "sampling"} {k:13s} {fmt(ts[k])}   replays {replays[k]}', flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--phrases', type=int, default=None, help='K: compare against generate_captions(phrases=K random phrases) (DESIGN.md 4u)')
+    ap.add_argument('--phrase-len', type=int, default=3)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--new', type=int, default=64)
@@ -121,6 +155,8 @@ def main():
     ap.add_argument('--suppress', type=str, default=None, help='comma-separated token ids')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_generate_captions.py measures on the MI355X; there is nothing to report without one'
+    if a.phrases:
+        return phrases_comparison(a)
     procs = {}
     if a.repetition_penalty is not None:
         procs['repetition_penalty'] = a.repetition_penalty
