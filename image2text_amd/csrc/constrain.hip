@@ -123,6 +123,107 @@ __global__ __launch_bounds__(64 * TRIE_ADV_WAVES) void caption_trie_advance_kern
     }
 }
 
+// ---- Exact closed-set scoring (score_phrases): the trie is walked level by level, every node of a level a row, nothing
+// pruned.  The level tables are host-built (decoding.trie_levels) and static.
+
+// The RAW row's log-sum-exp alone, for the fp32-logits head: caption_trie_mask_kernel's pass A -- a thread's chain over its 16-byte
+// groups, a fixed xor tree, the waves in order -- and nothing else: one workgroup per row, bit-reproducible, the row is only read.
+__global__ __launch_bounds__(TRIE_THREADS) void rows_lse_kernel(const float* __restrict__ logits, int ld, float* __restrict__ lse, int V) {
+    __shared__ float rmx[TRIE_THREADS / 64], rse[TRIE_THREADS / 64];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (size_t)r * ld;
+    float mx = -INFINITY, se = 0.f;
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
+    for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
+    }
+    for (int c = vend + tid; c < V; c += TRIE_THREADS) lse_add(mx, se, z[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+    if ((tid & 63) == 0) {
+        rmx[tid >> 6] = mx;
+        rse[tid >> 6] = se;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < TRIE_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
+        lse[r] = mx + logf(se);
+    }
+}
+
+// One level of the walk, after the level's step and its rows' LSE: one wave per (image b, entry j).  The first B * n_child waves are
+// the CHILD part: row b * W + j of the next level takes the node whose parent sits in row p = child_parent[j] and whose token is
+// k = child_tok[j]: path_out[b W + j] = path_in[b W + p] + (z - lse[b W + p]) in exactly this order, ids[b W + j][len] = k.  The other
+// B * n_term waves are the TERMINAL part: row p = term_row[j] of THIS level holds a node that ends a phrase, and every phrase index i
+// of term_phrase[term_off[j] .. term_off[j + 1]) (the node's duplicates) gets logprob[b][i] = path_in[b W + p] + (z_eos - lse[b W + p]).
+// z is logits[row][k] when a logits pointer is given, else scale . hidden[row] . w_head[k] re-evaluated in fp32 from the bf16 operands
+// as lse_token_logprob_kernel does (lane l the 8-element groups l, l + 64, ..., a fixed xor tree; the scale one rounded multiply, kept
+// out of the subtraction).  path_in and path_out are two buffers: no cell is read and written in one launch.  An entry whose parent row
+// or token lies outside its range (never from decoding.trie_levels) writes nothing, and so does a column outside the id rows.
+constexpr int EXPAND_WAVES = 4;
+__global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
+    const bf16_t* __restrict__ hid, int ld_h, const bf16_t* __restrict__ Wh, int ldw, int d, float scale, const float* __restrict__ logits, int ld,
+    const float* __restrict__ lse, const float* __restrict__ path_in, float* __restrict__ path_out, const int* __restrict__ child_parent,
+    const int* __restrict__ child_tok, int n_child, const int* __restrict__ term_row, const int* __restrict__ term_off,
+    const int* __restrict__ term_phrase, int n_term, int n_term_phrases, int64_t* __restrict__ ids, int ids_ld, const int* __restrict__ len_ptr,
+    float* __restrict__ logprob, int lp_ld, int eos, int B, int W, int V) {
+    const int lane = threadIdx.x & 63;
+    const long wv = (long)blockIdx.x * EXPAND_WAVES + (threadIdx.x >> 6);
+    const long n_exp = (long)B * n_child, total = n_exp + (long)B * n_term;
+    if (wv >= total) return;                                 // wave-uniform, as every return below
+    const bool child = wv < n_exp;
+    int b, j, p, tok;
+    if (child) {
+        b = (int)(wv / n_child);
+        j = (int)(wv % n_child);
+        p = child_parent[j];
+        tok = child_tok[j];
+    } else {
+        b = (int)((wv - n_exp) / n_term);
+        j = (int)((wv - n_exp) % n_term);
+        p = term_row[j];
+        tok = eos;
+    }
+    if (p < 0 || p >= W || tok < 0 || tok >= V) return;
+    const size_t pr = (size_t)b * W + p;
+    float z;
+    if (logits != nullptr) {
+        z = logits[pr * ld + tok];
+    } else {
+        const bf16_t* wr = Wh + (size_t)tok * ldw;
+        const bf16_t* hr = hid + pr * ld_h;
+        float acc = 0.f;
+        for (int k = 8 * lane; k < d; k += 8 * 64) {
+            const u32x4 wq = *reinterpret_cast<const u32x4*>(wr + k), hq = *reinterpret_cast<const u32x4*>(hr + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc += bf16lo(wq[e]) * bf16lo(hq[e]) + bf16hi(wq[e]) * bf16hi(hq[e]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        z = __fmul_rn(scale, acc);                           // its own rounding: never fused into the subtraction below
+    }
+    const float v = path_in[pr] + (z - lse[pr]);
+    if (child) {
+        const int len = *len_ptr;
+        if (len < 0 || len >= ids_ld) return;
+        if (lane == 0) {
+            const size_t c = (size_t)b * W + j;
+            path_out[c] = v;
+            ids[c * ids_ld + len] = tok;
+        }
+        return;
+    }
+    int lo = term_off[j], hi = term_off[j + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n_term_phrases ? n_term_phrases : hi;
+    for (int i = lo + lane; i < hi; i += 64) {
+        const int ph = term_phrase[i];
+        if (ph >= 0 && ph < lp_ld) logprob[(size_t)b * lp_ld + ph] = v;
+    }
+}
+
 }  // namespace
 
 extern "C" int i2t_caption_trie_mask(void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
@@ -162,5 +263,52 @@ extern "C" int i2t_caption_trie_advance(void* stream, const int64_t* ids, int id
                        (hipStream_t)stream, ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, nodes,
                        edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V);
     I2T_CHECK_LAUNCH("i2t_caption_trie_advance");
+    return I2T_OK;
+}
+
+extern "C" int i2t_rows_lse(void* stream, const float* logits, int ld, float* lse, int R, int V) {
+    I2T_REQUIRE(logits && lse, "i2t_rows_lse: null pointer");
+    I2T_REQUIRE(R > 0 && V > 0, "i2t_rows_lse: R = %d rows, V = %d", R, V);
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_rows_lse: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(lse), "i2t_rows_lse: misaligned base pointer (16 bytes)");
+    hipLaunchKernelGGL(rows_lse_kernel, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, lse, V);
+    I2T_CHECK_LAUNCH("i2t_rows_lse");
+    return I2T_OK;
+}
+
+extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
+                                     const float* logits, int ld, const float* lse, const float* path_in, float* path_out,
+                                     const int* child_parent, const int* child_tok, int n_child, const int* term_row, const int* term_off,
+                                     const int* term_phrase, int n_term, int n_term_phrases, int64_t* ids, int ids_ld, const int* len_ptr,
+                                     float* logprob, int lp_ld, int eos, int B, int W, int V) {
+    I2T_REQUIRE(lse && path_in && path_out && ids && len_ptr && logprob && (logits || (hidden && w_head)), "i2t_trie_level_expand: null pointer");
+    I2T_REQUIRE(n_child >= 0 && n_term >= 0 && n_term_phrases >= 0, "i2t_trie_level_expand: n_child = %d, n_term = %d, n_term_phrases = %d: none may be negative",
+                n_child, n_term, n_term_phrases);
+    I2T_REQUIRE((n_child == 0 || (child_parent && child_tok)) && (n_term == 0 || (term_row && term_off && term_phrase)),
+                "i2t_trie_level_expand: null pointer (a level table)");
+    I2T_REQUIRE(B > 0 && W > 0 && V > 0 && ids_ld > 0 && lp_ld > 0 && (long)B * W < (1l << 31),
+                "i2t_trie_level_expand: B = %d images, W = %d rows each, V = %d, ids_ld = %d, lp_ld = %d", B, W, V, ids_ld, lp_ld);
+    I2T_REQUIRE(n_child <= W && n_term <= W, "i2t_trie_level_expand: n_child = %d, n_term = %d exceed the W = %d rows of an image", n_child, n_term, W);
+    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_trie_level_expand: eos = %d outside the vocabulary of %d", eos, V);
+    I2T_REQUIRE(path_in != path_out, "i2t_trie_level_expand: path_in and path_out are one buffer: they swap each level");
+    if (logits) {
+        I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_trie_level_expand: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    } else {
+        I2T_REQUIRE(d > 0 && d % 8 == 0 && ld_hidden >= d && ld_w >= d && ld_hidden % 8 == 0 && ld_w % 8 == 0,
+                    "i2t_trie_level_expand: d = %d must be a multiple of 8, hidden / head rows (ld %d / %d) 16-byte aligned", d, ld_hidden, ld_w);
+        I2T_REQUIRE(scale == scale && scale - scale == 0.f, "i2t_trie_level_expand: scale must be finite");
+    }
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(hidden) && ALIGNED16(w_head) && ALIGNED16(lse) && ALIGNED16(path_in) && ALIGNED16(path_out) &&
+                    ALIGNED16(child_parent) && ALIGNED16(child_tok) && ALIGNED16(term_row) && ALIGNED16(term_off) && ALIGNED16(term_phrase) &&
+                    ALIGNED16(ids) && ALIGNED16(logprob),
+                "i2t_trie_level_expand: misaligned base pointer (16 bytes)");
+    const long waves = (long)B * n_child + (long)B * n_term;
+    if (waves == 0) return I2T_OK;
+    I2T_REQUIRE((waves + EXPAND_WAVES - 1) / EXPAND_WAVES < (1l << 31), "i2t_trie_level_expand: %ld waves exceed a grid", waves);
+    hipLaunchKernelGGL(trie_level_expand_kernel, dim3((unsigned)((waves + EXPAND_WAVES - 1) / EXPAND_WAVES)), dim3(64 * EXPAND_WAVES), 0,
+                       (hipStream_t)stream, (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, scale, logits, ld, lse, path_in,
+                       path_out, child_parent, child_tok, n_child, term_row, term_off, term_phrase, n_term, n_term_phrases, ids, ids_ld, len_ptr,
+                       logprob, lp_ld, eos, B, W, V);
+    I2T_CHECK_LAUNCH("i2t_trie_level_expand");
     return I2T_OK;
 }

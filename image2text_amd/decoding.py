@@ -999,6 +999,8 @@ class PhraseTrie(NamedTuple):
     term: np.ndarray                    # [nodes]: the index of the phrase that ends at the node (the lowest among duplicates), or -1
     max_fanout: int                     # the largest number of children of a node
     longest: int                        # the tokens of the longest phrase
+    phrase_node: Optional[np.ndarray] = None    # [K]: the node at which phrase k ends, duplicates included (``phrase_trie`` fills it;
+                                                # ``score_phrases`` needs it: ``term`` keeps the lowest index of a node only)
 
     @property
     def nodes(self) -> int:
@@ -1048,7 +1050,7 @@ def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
     longest = max(len(r) for r in rows)
     if max_new_tokens < longest + 1:
         raise ValueError(f'max_new_tokens = {max_new_tokens} is below the longest phrase + 1 = {longest + 1}: every row ends with EOS')
-    kids, term = [{}], [-1]                                     # insertion: node -> {token: next node}
+    kids, term, ends = [{}], [-1], []                           # insertion: node -> {token: next node}
     for k, row in enumerate(rows):
         n = 0
         for t in row:
@@ -1059,6 +1061,7 @@ def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
             n = kids[n][t]
         if term[n] < 0:
             term[n] = k
+        ends.append(n)
     off, tok, nxt = [0], [], []
     for d in kids:
         for t in sorted(d):
@@ -1067,7 +1070,7 @@ def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
         off.append(len(tok))
     i32 = np.int32
     return PhraseTrie(np.array(off, dtype=i32), np.array(tok, dtype=i32), np.array(nxt, dtype=i32), np.array(term, dtype=i32),
-                      max(len(d) for d in kids), longest)
+                      max(len(d) for d in kids), longest, np.array(ends, dtype=i32))
 
 
 def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
@@ -1154,6 +1157,160 @@ def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad
     lp = np.array(lps, dtype=f32)
     return SimpleNamespace(ids=np.array(seq, dtype=np.int64), length=len(seq), token_logprobs=lp, logprob=lp.sum(dtype=f32),
                            phrase_index=phrase, steps=len(lps), gaps=gaps)
+
+
+# ------------------------------------------------------------------------------------------------ exact phrase scores
+class PhraseScores(NamedTuple):
+    """What ``score_phrases`` returns."""
+    logprob: torch.Tensor               # fp32 [B, K]: the raw log-likelihood of phrase k + EOS after image b's prompt (``score``'s quantity)
+    best: torch.Tensor                  # int64 [B]: the argmax over k, the lowest index on ties (duplicate phrases tie exactly)
+    lengths: torch.Tensor               # int32 [K]: the tokens of each phrase + 1 (the EOS)
+
+
+class TrieLevel(NamedTuple):
+    """The nodes of one depth of a phrase trie (``trie_levels``); all arrays numpy int32."""
+    nodes: np.ndarray                   # [n_t]: the nodes at depth t, ascending (node order)
+    rows: np.ndarray                    # [n_t]: the row w each of them holds during the level's step -- its rank in ``nodes``
+    parent_rows: np.ndarray             # [n_t]: the row its parent held at depth t - 1 (-1 at the root)
+    tokens: np.ndarray                  # [n_t]: the token of the edge that leads to it (-1 at the root)
+    term: np.ndarray                    # [n_t]: trie.term of the node
+    anc: np.ndarray                     # [wmax, t + 1]: anc[w][j] = the row the depth-j ancestor of row w's node held (j = t: w itself);
+                                        # rows w >= n_t hold no node: w in every column
+
+
+class TrieLevels(NamedTuple):
+    levels: tuple                       # TrieLevel for t = 0 (the root alone) .. longest
+    wmax: int                           # the widest level: the rows per image of the walk
+
+    def history(self, t: int, first: int, clen: int) -> np.ndarray:
+        """int32 [wmax, clen]: the static history table of level t's step.  ``first`` is the cache slot the level-0 step writes (the
+        last prompt token's: soft-prompt rows + P - 1), so the level-j step writes slot first + j, in the row the depth-j node holds.
+        Key slot s of row w is read from cache row history[w][s]: slots up to ``first`` -- soft prompt and prompt, which every row ran
+        itself -- and slot first + t, which the row writes in this very step, from row w; slot first + j, 0 < j < t, from anc[w][j];
+        later slots are not read (w)."""
+        lv = self.levels[t]
+        assert first >= 0 and first + t < clen
+        h = np.repeat(np.arange(self.wmax, dtype=np.int32)[:, None], clen, axis=1)
+        h[:, first + 1:first + t] = lv.anc[:, 1:t]
+        return h
+
+
+def trie_levels(trie: PhraseTrie) -> TrieLevels:
+    """The CSR trie as per-depth tables, t = 0 .. trie.longest, built once on the host: ``score_phrases`` walks them level by level, a
+    "beam search" that prunes nothing and whose parents come from the trie instead of a top-k, so every table is static."""
+    n = trie.nodes
+    depth, parent, token = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    depth[0] = 0
+    order = [0]
+    for nd in order:                                            # breadth first from the root: a parent is placed before its children
+        toks, nxt = trie.children(nd)
+        for tk, c in zip(toks.tolist(), nxt.tolist()):
+            assert depth[c] < 0, 'not a tree'
+            depth[c], parent[c], token[c] = depth[nd] + 1, nd, tk
+            order.append(c)
+    assert len(order) == n and int(depth.max()) == trie.longest, 'the trie holds nodes its root does not reach, or a wrong longest'
+    per = [np.flatnonzero(depth == t).astype(np.int32) for t in range(trie.longest + 1)]
+    wmax = max(p.shape[0] for p in per)
+    row_of = np.zeros(n, dtype=np.int32)
+    for p in per:
+        row_of[p] = np.arange(p.shape[0], dtype=np.int32)
+    levels = []
+    for t, nodes in enumerate(per):
+        anc = np.repeat(np.arange(wmax, dtype=np.int32)[:, None], t + 1, axis=1)
+        at = nodes.copy()
+        for j in range(t, -1, -1):                              # up the tree: the depth-j ancestor of every node of the level
+            anc[:nodes.shape[0], j] = row_of[at]
+            at = parent[at] if j else at
+        levels.append(TrieLevel(nodes, np.arange(nodes.shape[0], dtype=np.int32),
+                                row_of[parent[nodes]] if t else np.full(1, -1, dtype=np.int32), token[nodes], trie.term[nodes], anc))
+    return TrieLevels(tuple(levels), int(wmax))
+
+
+def phrase_node_csr(trie: PhraseTrie):
+    """-> (off int32 [nodes + 1], idx int32 [K]): the phrases that end at node n are idx[off[n] .. off[n + 1]), ascending -- the
+    duplicates of a phrase share its node, which ``trie.term`` names by the lowest index only"""
+    if trie.phrase_node is None:
+        raise ValueError('a PhraseTrie without phrase_node (not built by phrase_trie): the phrases that share a node are unknown')
+    ends = np.asarray(trie.phrase_node, dtype=np.int64)
+    idx = np.argsort(ends, kind='stable').astype(np.int32)
+    off = np.zeros(trie.nodes + 1, dtype=np.int32)
+    np.cumsum(np.bincount(ends, minlength=trie.nodes), out=off[1:])
+    return off, idx
+
+
+def level_expand_tables(trie: PhraseTrie, levels: TrieLevels, t: int):
+    """The five tables i2t_trie_level_expand takes at level t (numpy int32) -> (child_parent, child_tok, term_row, term_off,
+    term_phrase): the nodes of level t + 1 in row order with their parents' rows at level t (empty at the last level), and the rows of
+    level t whose node ends a phrase with the CSR of the phrase indices that end there."""
+    i32 = np.int32
+    lv = levels.levels[t]
+    nxt = levels.levels[t + 1] if t + 1 < len(levels.levels) else None
+    child_parent = nxt.parent_rows if nxt is not None else np.zeros(0, dtype=i32)
+    child_tok = nxt.tokens if nxt is not None else np.zeros(0, dtype=i32)
+    off, idx = phrase_node_csr(trie)
+    rows = [w for w, nd in enumerate(lv.nodes.tolist()) if off[nd + 1] > off[nd]]
+    term_off, term_phrase = [0], []
+    for w in rows:
+        nd = int(lv.nodes[w])
+        term_phrase += idx[off[nd]:off[nd + 1]].tolist()
+        term_off.append(len(term_phrase))
+    return child_parent.astype(i32), child_tok.astype(i32), np.array(rows, dtype=i32), np.array(term_off, dtype=i32), np.array(term_phrase, dtype=i32)
+
+
+def phrase_scores_host(step_logits_fn, trie: PhraseTrie, eos: int, prompt=()):
+    """The normative replica of ``score_phrases`` for ONE image on the host: ``step_logits_fn(sequence)`` gives the raw fp32 logits row
+    [V] that follows a token sequence (a list of ints: ``prompt``, then the path from the root).  The levels are walked in order; every
+    node's row gives lse = m + log(sum exp(z - m)) in fp32, a child's path sum is path[parent] + (z[token] - lse) and a phrase that ends
+    at the node gets path[node] + (z[eos] - lse), in exactly this order in fp32 -- the device's (i2t_trie_level_expand).
+    -> SimpleNamespace(logprob f32 [K], best: the argmax, the lowest index on ties, lengths int32 [K])."""
+    f32 = np.float32
+    levels = trie_levels(trie)
+    off, idx = phrase_node_csr(trie)
+    K = idx.shape[0]
+    logprob = np.zeros(K, dtype=f32)
+    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    path, seq = {0: f32(0.0)}, {0: []}
+    for lv in levels.levels:
+        for nd in lv.nodes.tolist():
+            z = np.asarray(step_logits_fn(prompt + seq[nd]), dtype=f32).reshape(-1)
+            m = z.max()
+            lse = f32(m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))
+            toks, kids = trie.children(nd)
+            for tk, c in zip(toks.tolist(), kids.tolist()):
+                path[c], seq[c] = f32(path[nd] + f32(z[tk] - lse)), seq[nd] + [tk]
+            for k in idx[off[nd]:off[nd + 1]].tolist():
+                logprob[k] = f32(path[nd] + f32(z[eos] - lse))
+    depth_of = {int(nd): t for t, lv in enumerate(levels.levels) for nd in lv.nodes.tolist()}
+    lengths = np.array([depth_of[int(nd)] + 1 for nd in trie.phrase_node], dtype=np.int32)
+    return SimpleNamespace(logprob=logprob, best=int(np.flatnonzero(logprob == logprob.max())[0]), lengths=lengths)
+
+
+def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
+                            images_per_pass=None) -> PhraseTrie:
+    """The refusals of ``score_phrases``, all before anything runs -> the trie.  ValueError: everything ``phrase_trie`` refuses about the
+    set (or a ``PhraseTrie`` built for another EOS / vocabulary, or one without ``phrase_node``), prompt + longest phrase + 1 past
+    the decode ``window`` (the text of every other call), ``images_per_pass`` < 1.  NotImplementedError, naming the reason: a
+    non-causal decoder, sparse nano-mini blocks."""
+    if isinstance(phrases, PhraseTrie):
+        trie = phrases
+        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+                or bool((trie.child_tok == int(eos)).any()):
+            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
+        phrase_node_csr(trie)
+    else:
+        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
+    if not causal:
+        raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
+                                  'state of the earlier ones --, so use rerank')
+    if sparse:
+        raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
+                                  'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
+    total = int(P) + trie.longest + 1
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
+        raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
+    return trie
 
 
 class CaptionDecoder(GreedyDecoder):
@@ -1769,6 +1926,159 @@ class CaptionBeamDecoder(BeamDecoder):
         tok_lp = st.pool_lp[:, :N, P:L].contiguous()
         return GeneratedCaptions(st.pool_ids[:, :N, :L].contiguous(), lengths, tok_lp, tok_lp.sum(dim=-1), None,
                                  st.pool_score[:, :N].contiguous())
+
+
+TRIE_SCORE_BYTES = int(os.environ.get('I2T_TRIE_SCORE_BYTES', str(8 << 30)))      # the per-pass state budget images_per_pass is derived from
+
+
+class TrieScoreDecoder(BeamDecoder):
+    """``score_phrases`` on the static KV cache: the phrase trie walked level by level, every node of a level a row,
+    nothing pruned -- BeamDecoder's R = images * W rows (W = the widest level), history table, shared cross K/V (rows_per_mem = W) and
+    attention kernels, but none of its candidates / consolidate / pool kernels, so their W <= 8 does not apply: the state is
+    GreedyDecoder._build's plus the few buffers below.  The prompt goes through P - 1 ordinary prefill steps on all rows under the
+    identity table.  Level t = 0 .. longest is then: the level's history columns into st.hist -> _body -> _final_norm -> the rows' LSE
+    (d % 128 == 0: i2t_gemm_bf16_lse + i2t_lse_token_logprob with every label ignored, no logits; else the fp32 lm_head + i2t_rows_lse)
+    -> i2t_trie_level_expand -> i2t_advance.  Rows beyond a level's width keep token 0 and the identity history; they run and their
+    results are never read.  Eager launches: a level is one step and its tables differ from the last one's."""
+
+    last_passes = 0                     # the image groups the last call ran (tests, tools)
+    _score_state = None                 # this decoder's own state: neither GreedyDecoder._state nor ._long_state
+
+    def row_bytes(self, clen: int, ids_ld: int) -> int:
+        """what one row of the state costs, for the images_per_pass default: its K/V cache over every layer, its fp32 logits row (the
+        shared allocation makes it whatever the head), the two history tables, ids, segment statistics and the step's activations"""
+        dc = self.eng.dec
+        if dc.llama is not None:
+            kvw = dc.llama.Hkv * dc.llama.hd
+        elif dc.fam is not None:
+            kvw = (1 if dc.fam.mqa else dc.H) * dc.fam.hd
+        else:
+            kvw = dc.d
+        return 2 * dc.L * clen * kvw * 2 + dc.Vp * 4 + 2 * clen * 4 + ids_ld * 8 + (dc.V + 63) // 64 * 8 + (16 * dc.d + 3 * dc.ff) * 4
+
+    def _build_trie_score(self, B: int, W: int, ids_ld: int, clen: int):
+        R = B * W
+        st = self._build(R, ids_ld, mem_rows=B, clen=clen)
+        dev, dc = st.arena.device, self.eng.dec
+        st.W, st.images, st.mem_div = W, B, W
+        st.hist_init = torch.arange(R, dtype=torch.int32, device=dev).unsqueeze(1).expand(R, st.clen).contiguous()
+        st.hist = st.hist_init.clone()
+        st.row_base = (torch.arange(B, dtype=torch.int32, device=dev) * W).view(B, 1, 1)
+        st.path = (torch.zeros(R, dtype=F32, device=dev), torch.zeros(R, dtype=F32, device=dev))      # swapped every level
+        st.lse = torch.zeros(R, dtype=F32, device=dev)
+        st.lse_route = dc.d % 128 == 0                           # the persistent GEMM kernel's K rule, as HotPath.token_logprobs
+        if st.lse_route:
+            st.stats = torch.zeros(R, (dc.V + 63) // 64, 2, dtype=F32, device=dev)
+            st.no_label = torch.full((R,), -100, dtype=torch.long, device=dev)
+            st.no_lp = torch.zeros(R, dtype=F32, device=dev)
+        st.trie_score = True
+        return st
+
+    def _encode_all(self, st, images, B: int):
+        """The encoder, the cross K/V and the soft-prompt rows' K/V of ALL B images, once, through _prepare_inputs on a one-row-per-image
+        stand-in for the state: what a group of images starts from does not depend on how the images are grouped (the forward's GEMMs
+        choose their kernels by the number of rows)."""
+        dev = st.arena.device
+        e = lambda *s: torch.zeros(*s, dtype=BF16, device=dev)
+        pre = SimpleNamespace(prefix=st.prefix, clen=max(st.prefix, 1), cross_kv={l: (e(B, *kv.shape[1:]), S) for l, (kv, S) in st.cross_kv.items()})
+        if st.prefix:
+            pre.kc = [e(B, st.prefix, k.shape[-1]) for k in st.kc]
+            pre.vc = [e(B, st.prefix, v.shape[-1]) for v in st.vc]
+        self._prepare_inputs(pre, images, B, 1)
+        return pre
+
+    def _load_group(self, st, pre, take):
+        """the cross K/V of images ``take`` [st.images] and their soft-prompt K/V into the head of every row's cache"""
+        dc = self.eng.dec
+        Bp, W, n_p = st.images, st.W, st.prefix
+        for l, (kv, _) in st.cross_kv.items():
+            kv.copy_(pre.cross_kv[l][0][take])
+        for l in range(dc.L if n_p else 0):
+            for dst, src in ((st.kc[l], pre.kc[l]), (st.vc[l], pre.vc[l])):
+                if dc.llama is not None:                        # row-major [R][slot][Hkv hd]
+                    dst.view(Bp, W, st.clen, -1)[:, :, :n_p].copy_(src[take].unsqueeze(1))
+                else:                                           # head-major [R][H][slot][64]
+                    dst.view(Bp, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(src.view(-1, dc.H, n_p, 64)[take].unsqueeze(1))
+
+    def _level_step(self, st, tables, t: int, eos: int, logprob):
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        R, V, d = st.B, dc.V, dc.d
+        self._body(st)
+        self._final_norm(st)
+        head = a.W(eng.n_head)
+        if st.lse_route:
+            ops.gemm_lse(st.hid, head, st.stats, R, V, d)
+            ops.lse_token_logprob(st.stats, st.hid, head, st.no_label, st.lse, st.no_lp, R, V, d, ignore_index=-100)
+            z = dict(hidden=st.hid, w_head=head, d=d)
+        else:
+            ops.gemm(st.hid, head, st.logits, R, V, d, workspace=st.ws)
+            ops.rows_lse(st.logits, dc.Vp, st.lse, R, V)
+            z = dict(logits=st.logits, ld=dc.Vp)
+        ops.trie_level_expand(tables, st.lse, st.path[t & 1], st.path[(t + 1) & 1], st.ids, st.ids_ld, st.counters[1:2], logprob, eos,
+                              st.images, st.W, V, **z)
+        ops.advance(st.counters, 1)
+
+    @torch.no_grad()
+    def score(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, images_per_pass: Optional[int] = None) -> PhraseScores:
+        """``phrase_scores_host`` for every image of the batch, on the device.  ``trie``: what ``check_phrase_score_args`` returned."""
+        eng = self.eng
+        dc = eng.dec
+        a = eng.prepare(False)
+        dev = a.device
+        prompt_ids = prompt_ids.to(dev)
+        B, P = prompt_ids.shape
+        K = int(trie.phrase_node.shape[0])
+        levels = trie_levels(trie)
+        W = levels.wmax
+        total = P + trie.longest + 1
+        block, off, prefix, llama = self._cache_args()
+        # The walk reads prompt + longest phrase + 1 cache slots however long the text window is, and W rows per image multiply every
+        # slot: the state is this decoder's own, with a cache of that many slots (in whole 16s) -- or, past text_window on a decoder that
+        # takes the long cache, cache_plan's whole chunks
+        clen, long = cache_plan(block, off, prefix, total, llama)
+        clen = clen if long else min(clen, prefix + -(-total // 16) * 16)
+        ids_ld = -(-total // 8) * 8
+        if images_per_pass is None:
+            images_per_pass = max(1, TRIE_SCORE_BYTES // (W * self.row_bytes(clen, ids_ld)))
+        Bp = min(int(images_per_pass), B)
+        st = self._score_state
+        if not self._reusable(st, Bp * W, total, lambda st: st.W == W and st.images == Bp and st.clen >= clen):
+            self._score_state = st = None                       # the old buffers go before the new ones are made
+            self._score_state = st = self._build_trie_score(Bp, W, ids_ld, clen)
+        assert total <= st.tmax
+        # every level's tables, checked on the host and uploaded once per call
+        tables = [ops.trie_level_tables(*level_expand_tables(trie, levels, t), W, dc.V, K, dev) for t in range(trie.longest + 1)]
+        anc = [torch.from_numpy(lv.anc).to(dev) for lv in levels.levels]
+        first = st.prefix + P - 1                               # the cache slot of the level-0 step (TrieLevels.history)
+        out = torch.zeros(B, K, dtype=F32, device=dev)
+        part = torch.zeros(Bp, (K + 3) // 4 * 4, dtype=F32, device=dev)
+        self.last_passes = 0
+        pre = self._encode_all(st, images, B)
+        for i in range(0, B, Bp):
+            n = min(Bp, B - i)
+            take = torch.arange(i, i + Bp, device=dev).clamp(max=B - 1)         # a short last group is filled with its last image
+            self._load_group(st, pre, take)
+            st.ids.zero_()
+            st.ids[:, :P] = prompt_ids[take].repeat_interleave(W, dim=0)
+            st.counters.copy_(st.counters_init)
+            st.hist.copy_(st.hist_init)
+            st.path[0].zero_()
+            part.zero_()
+            for _ in range(P - 1):                              # prompt tokens before the last: fill the cache only
+                self._step(st, False)
+            for t in range(trie.longest + 1):
+                if t >= 2:                                      # the columns in which level t's table is not the identity
+                    st.hist.view(Bp, W, st.clen)[:, :, first + 1:first + t] = st.row_base + anc[t][None, :, 1:t]
+                self._level_step(st, tables[t], t, eos, part)
+            out[i:i + n] = part[:n, :K]
+            self.last_passes += 1
+        top = out.max(dim=1, keepdim=True).values
+        best = torch.where(out == top, torch.arange(K, device=dev)[None, :], torch.full((), K, device=dev)).min(dim=1).values
+        depth = np.zeros(trie.nodes, dtype=np.int32)
+        for t, lv in enumerate(levels.levels):
+            depth[lv.nodes] = t
+        lengths = torch.from_numpy((depth[trie.phrase_node] + 1).astype(np.int32)).to(dev)
+        return PhraseScores(out, best, lengths)
 
 
 def _draw_seed(buf: torch.Tensor, seed: Optional[int]):

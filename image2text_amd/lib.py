@@ -80,6 +80,8 @@ SIGNATURES = {
     'i2t_caption_raw_logprob': [P, P, I, P, P, P, I, P, I, P, P, I, I, I],
     'i2t_caption_trie_mask': [P, P, I, P, P, P, P, I, I, I, P, P, P, I, I, I],
     'i2t_caption_trie_advance': [P, P, I, P, P, P, I, P, P, P, P, P, I, I, I, P, P, P, P, I, I, I],
+    'i2t_rows_lse': [P, P, I, P, I, I],
+    'i2t_trie_level_expand': [P, P, I, P, I, I, F, P, I, P, P, P, P, P, I, P, P, P, I, I, P, I, P, P, I, I, I, I, I],
     'i2t_gq_attention_fwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, I, U, U, F, P, P, I, I],
     'i2t_gq_attention_bwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, L, I, P, P, P, L, I, P, L, I, P, L, I, I, I, I, I, I, I, I, U, U, F, P, P, I,
                              U, U, F],
@@ -149,7 +151,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _lib = None
 
 

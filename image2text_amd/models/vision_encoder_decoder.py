@@ -152,6 +152,7 @@ class VisionEncoderDecoder(nn.Module):
         object.__setattr__(self, '_greedy', None)
         object.__setattr__(self, '_captioner', None)
         object.__setattr__(self, '_beam_captioner', None)
+        object.__setattr__(self, '_trie_scorer', None)
         if config.chkpt_path is not None:
             update_state_dict_from_partial_checkpoint(self, config.chkpt_path, map_location=None)
 
@@ -387,6 +388,37 @@ class VisionEncoderDecoder(nn.Module):
         lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, pmin - 1:L - 1] if L > pmin else torch.zeros(B * N, 0, device=dev)
         lp = lp.reshape(B, N, L - pmin).contiguous()
         return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), None if plen is None else torch.from_numpy(plen).to(dev))
+
+    @torch.no_grad()
+    def score_phrases(self, images, prompt_ids, phrases, eos_token_id, images_per_pass=None):
+        """Exact closed-set scoring (no counterpart in the reference) -> ``decoding.PhraseScores(logprob [B, K], best [B],
+        lengths [K])``: ``logprob[b, k]`` (fp32) is the raw log-likelihood of ``phrases[k]`` followed by ``eos_token_id`` after
+        ``prompt_ids[b]`` for image b -- the sum of the raw log_softmax over the phrase's tokens and the EOS, the quantity ``score`` /
+        ``rerank`` and ``generate_captions(phrases=...).logprob`` report, so the three are comparable; ``best[b]`` (int64) its argmax over
+        k, the lowest index on ties; ``lengths[k]`` (int32) the tokens of phrase k + 1.  Duplicate phrases get equal values.
+        ``phrases`` is what ``generate_captions`` takes: K >= 1 token-id sequences (or the ``PhraseTrie`` ``decoding.phrase_trie`` built
+        of them), one set for all images.  Where ``generate_captions(phrases=...)`` walks the set's trie greedily -- one phrase and one
+        number per row, and a first token picked by its marginal is never taken back -- this call visits EVERY node once: the trie is
+        walked level by level on the KV cache, every node of a level a row, in prompt + longest phrase + 1 decode steps over
+        (widest level) rows per image, where ``rerank`` costs a decoder forward per (image, phrase).  Images go through in groups of
+        ``images_per_pass`` (default: what fits ``decoding.TRIE_SCORE_BYTES`` of per-pass state); the grouping does not change a bit of
+        the result.  Refusals, before anything runs (``decoding.check_phrase_score_args``): ValueError for everything
+        ``generate_captions`` refuses about the set itself, prompt + longest phrase + 1 past the text window, ``images_per_pass`` < 1;
+        NotImplementedError for a non-causal decoder and for sparse nano-mini blocks.  ``generate_captions``, ``score`` and ``rerank``
+        are untouched by this call: it keeps a decoder state of its own."""
+        from ..decoding import TrieScoreDecoder, check_phrase_score_args, decode_window, takes_long_cache
+        eng = self._engine
+        dc = eng.dec
+        ncls = eng.enc.ncls
+        window = self.decoder.block_size - self.space_for_prompt
+        if dc.causal:
+            window = min(window, decode_window(dc.block, ncls if self.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
+                                               takes_long_cache(dc.llama)))
+        trie = check_phrase_score_args(phrases, eos_token_id, dc.V, prompt_ids.shape[1], window, dc.causal,
+                                       dc.fam is not None and bool(dc.fam.sparse), images_per_pass)
+        if self._trie_scorer is None:
+            object.__setattr__(self, '_trie_scorer', TrieScoreDecoder(self))
+        return self._trie_scorer.score(images, prompt_ids.to(next(self.parameters()).device), trie, int(eos_token_id), images_per_pass)
 
     @torch.no_grad()
     def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:

@@ -962,6 +962,73 @@ def caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, ch
                                              _p(phrase_index), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_trie_advance')
 
 
+def rows_lse(logits, ld, lse, R, V):
+    """lse[r] = the log-sum-exp of columns [0, V) of fp32 logits row r, in caption_trie_mask's reduction order; the rows are only read
+    (include/i2t.h::i2t_rows_lse)"""
+    _need_cuda(logits, lse)
+    assert logits.dtype == F32 and lse.dtype == F32 and lse.is_contiguous() and lse.numel() >= R
+    _l.check(_lib().i2t_rows_lse(_stream(), _p(logits), ld, _p(lse), R, V), 'i2t_rows_lse')
+    return lse
+
+
+class TrieLevelTables:
+    """One level's tables of trie_level_expand on the device (int32, one allocation each): child_parent / child_tok [n_child] -- the next
+    level's row j takes token child_tok[j] behind the parent in row child_parent[j] of this level --, term_row [n_term], term_off
+    [n_term + 1], term_phrase [n_term_phrases]: row term_row[j] ends the phrases term_phrase[term_off[j] .. term_off[j + 1])."""
+
+    def __init__(self, child_parent, child_tok, term_row, term_off, term_phrase, n_child, n_term, n_term_phrases):
+        self.child_parent, self.child_tok, self.term_row, self.term_off, self.term_phrase = child_parent, child_tok, term_row, term_off, term_phrase
+        self.n_child, self.n_term, self.n_term_phrases = n_child, n_term, n_term_phrases
+
+
+def trie_level_tables(child_parent, child_tok, term_row, term_off, term_phrase, W: int, V: int, K: int, device) -> TrieLevelTables:
+    """The host-built tables of one level (integer sequences or numpy arrays), checked BEFORE upload -- the kernel cannot refuse what it
+    reads from device memory -- and uploaded: I2TError for a parent or terminal row outside [0, W), more children or terminal rows than
+    W, a token outside [0, V), offsets that do not ascend from 0 to len(term_phrase), a phrase index outside [0, K)."""
+    import numpy as np
+    arr = lambda a: np.asarray(a, dtype=np.int64).reshape(-1)
+    child_parent, child_tok, term_row, term_off, term_phrase = (arr(a) for a in (child_parent, child_tok, term_row, term_off, term_phrase))
+    bad = lambda a, hi: bool(a.size) and (int(a.min()) < 0 or int(a.max()) >= hi)
+    if child_parent.shape != child_tok.shape or term_off.shape != (term_row.shape[0] + 1,):
+        raise _l.I2TError(f'trie_level_tables: {child_parent.shape[0]} parent rows for {child_tok.shape[0]} tokens, {term_off.shape[0]} offsets for '
+                          f'{term_row.shape[0]} terminal rows')
+    if child_parent.shape[0] > W or term_row.shape[0] > W:
+        raise _l.I2TError(f'trie_level_tables: {child_parent.shape[0]} child rows, {term_row.shape[0]} terminal rows exceed the W = {W} rows of an image')
+    if bad(child_parent, W):
+        raise _l.I2TError(f'trie_level_tables: a parent row outside [0, {W})')
+    if bad(term_row, W):
+        raise _l.I2TError(f'trie_level_tables: a terminal row outside [0, {W})')
+    if bad(child_tok, V):
+        raise _l.I2TError(f'trie_level_tables: a token outside the vocabulary [0, {V})')
+    if int(term_off[0]) != 0 or int(term_off[-1]) != term_phrase.shape[0] or bool((np.diff(term_off) < 0).any()):
+        raise _l.I2TError(f'trie_level_tables: term_off does not ascend from 0 to the {term_phrase.shape[0]} phrase indices')
+    if bad(term_phrase, K):
+        raise _l.I2TError(f'trie_level_tables: a phrase index outside [0, {K})')
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(np.concatenate((a, np.zeros(1, np.int64))).astype(np.int32))).to(device)
+    return TrieLevelTables(up(child_parent), up(child_tok), up(term_row), up(term_off), up(term_phrase), int(child_tok.shape[0]),
+                           int(term_row.shape[0]), int(term_phrase.shape[0]))
+
+
+def trie_level_expand(tables: TrieLevelTables, lse, path_in, path_out, ids, ids_ld, len_ptr, logprob, eos, B, W, V, *, hidden=None,
+                      w_head=None, d=0, scale=1.0, logits=None, ld=0):
+    """one level of score_phrases' walk over ``tables`` (trie_level_tables): the next level's path sums and tokens, and the log-probs of
+    the phrases that end at this level; z from ``logits`` [B W, ld] when given, else re-evaluated from ``hidden`` [B W, d] and ``w_head``
+    [V, d] (include/i2t.h::i2t_trie_level_expand)"""
+    _need_cuda(lse, path_in, path_out, ids, len_ptr, logprob, hidden, w_head, logits)
+    assert lse.dtype == F32 and path_in.dtype == F32 and path_out.dtype == F32 and logprob.dtype == F32 and ids.dtype == torch.long
+    assert all(t.is_contiguous() and t.numel() >= B * W for t in (lse, path_in, path_out)) and ids.shape[0] >= B * W
+    assert logprob.dim() == 2 and logprob.stride(-1) == 1 and logprob.shape[0] >= B and len_ptr.dtype == torch.int32
+    assert logits is None or (logits.dtype == F32 and logits.shape[0] >= B * W)
+    assert logits is not None or (hidden.dtype == BF16 and w_head.dtype == BF16 and hidden.stride(-1) == 1 and w_head.stride(-1) == 1
+                                  and hidden.shape[0] >= B * W and w_head.shape[0] >= V)
+    t = tables
+    _l.check(_lib().i2t_trie_level_expand(_stream(), _p(hidden), 0 if hidden is None else hidden.stride(0), _p(w_head),
+                                          0 if w_head is None else w_head.stride(0), int(d), float(scale), _p(logits), int(ld), _p(lse),
+                                          _p(path_in), _p(path_out), _p(t.child_parent), _p(t.child_tok), t.n_child, _p(t.term_row),
+                                          _p(t.term_off), _p(t.term_phrase), t.n_term, t.n_term_phrases, _p(ids), ids_ld, _p(len_ptr),
+                                          _p(logprob), logprob.stride(0), int(eos), B, W, V), 'i2t_trie_level_expand')
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     _need_cuda(a, b, stats)

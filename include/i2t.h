@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 13
+#define I2T_ABI_VERSION 14
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -499,6 +499,26 @@ int i2t_caption_trie_advance(void* stream, const int64_t* ids, int ids_ld, const
                              const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok,
                              const int* child_next, const int* term, int nodes, int edges, int eos, const int* done, int* node,
                              int* phrase_index, float* tok_lp, int lp_ld, int R, int V);
+/* Exact closed-set scoring (score_phrases; DESIGN.md 4v, ABI 14): the log-likelihood of EVERY phrase of a set, the trie walked level by
+ * level with every node of a level a row (W rows per image, row b * W + w) and nothing pruned.  The level tables are host-built, static
+ * and int32; bases on 16 bytes.
+ *   i2t_rows_lse: lse[r] = log sum_c exp(logits[r][c]) over columns [0, V) of logits f32 [R][ld] (ld >= V, ld % 4 == 0), one workgroup
+ *     per row in i2t_caption_trie_mask's reduction order (no atomics, bit-reproducible); the rows are only read.
+ *   i2t_trie_level_expand, one wave per (image, entry), after the level's step and its rows' lse.  Child part, entry j < n_child: the
+ *     next level's row b W + j takes token k = child_tok[j] behind the parent in row p = child_parent[j] (0 <= p < W) of this level:
+ *     path_out[b W + j] = path_in[b W + p] + (z - lse[b W + p]) in this order in fp32, ids[b W + j][*len_ptr] = k.  Terminal part,
+ *     entry j < n_term: row p = term_row[j] holds a node that ends a phrase; every phrase index i of term_phrase[term_off[j] ..
+ *     term_off[j + 1]) (term_off [n_term + 1], term_phrase [n_term_phrases]) gets logprob[b][i] = path_in[b W + p] + (z_eos - lse[b W + p])
+ *     (logprob f32 [B][lp_ld]).  z = logits[b W + p][k] when `logits` is given (f32 [B W][ld]); else scale . hidden[b W + p] .
+ *     w_head[k], re-evaluated in fp32 from the bf16 operands as i2t_lse_token_logprob does (d % 8 == 0, rows on 16 bytes).  path_in and
+ *     path_out are two buffers.  Nothing else is written; an entry whose parent row or token is outside its range writes nothing (the
+ *     host checks the tables before upload).  n_child = n_term = 0 launches nothing. */
+int i2t_rows_lse(void* stream, const float* logits, int ld, float* lse, int R, int V);
+int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
+                          const float* logits, int ld, const float* lse, const float* path_in, float* path_out,
+                          const int* child_parent, const int* child_tok, int n_child, const int* term_row, const int* term_off,
+                          const int* term_phrase, int n_term, int n_term_phrases, int64_t* ids, int ids_ld, const int* len_ptr,
+                          float* logprob, int lp_ld, int eos, int B, int W, int V);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).
