@@ -1,0 +1,448 @@
+"""What a decoding call means, decided on the host before anything runs: the argument tuples (``Sampling``, ``Processors``, ``BeamSpec``),
+the window and cache planners, the refusals of ``generate_captions`` / ``score_phrases`` and -- composing them -- ``plan_captions``, the
+one function that resolves a ``generate_captions`` call into a ``CaptionPlan``; the result tuples and the graph key beside them.  numpy,
+and torch only to accept tensors; no device, engine or library.  ``decoding`` re-exports every name."""
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from .phrase_trie import PhraseTrie, phrase_node_csr, phrase_trie
+
+
+class Sampling(NamedTuple):
+    """How the next token is chosen when it is not the argmax (arguments of the reference's generate, :136-137)."""
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    nucleus_p: Optional[float] = None
+    seed: Optional[int] = None          # 64-bit; None: drawn from torch's CPU generator at the start of the call
+
+    def key(self):
+        return (float(self.temperature), int(self.top_k or 0), None if self.nucleus_p is None else float(self.nucleus_p))
+
+
+# i2t_decode_attention and i2t_gq_decode_attention (csrc/common.h::DECODE_MAX_KEYS) keep the scores of at most this many keys per caption
+# in LDS; neither reads a key count from the device against it, so the cache THEY attend over is never allocated longer (a longer
+# one is the long state's, below, and runs other kernels)
+DECODE_MAX_KEYS = 1024
+
+
+def text_window(block: int, off: int, prefix: int) -> int:
+    """Text positions of the decode step's self-attention cache: the decoder's block less the soft-prompt offset ``off``, capped so
+    that ``prefix`` cached prompt rows + the text fit in DECODE_MAX_KEYS keys."""
+    tmax = min(block - off, DECODE_MAX_KEYS - prefix)
+    if tmax < 1:
+        raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
+                         f'no room for text (block {block}, soft-prompt offset {off})')
+    return tmax
+
+
+# The Llama-family decoders with heads of 64 or 128 (row-major cache) have a second attention form, i2t_gq_decode_attention_long,
+# which splits a row's keys into chunks of LONG_CHUNK_KEYS across workgroups and bounds a row by its workspace alone
+# (csrc/common.h::LONG_CHUNK_KEYS / DECODE_LONG_MAX_KEYS, both pinned by tests/test_long_decode_host_cpu.py).  A call
+# that fits text_window never sees it.
+LONG_CHUNK_KEYS = 256               # = ops.LONG_CHUNK_KEYS, which this module does not import (decoding.py holds the two equal)
+DECODE_LONG_MAX_KEYS = 32768
+LONG_HEAD_DIMS = (64, 128)          # the head widths the split-key kernels are built for
+
+
+def takes_long_cache(llama_spec) -> bool:
+    """Whether a decoder may decode past text_window: ``llama_spec`` is its Llama-family spec (engine.dec.llama; None for the dense and
+    nano-mini decoders).  The plugins also accept heads of 16 and 32, which the split-key kernels are not built for: those decoders
+    keep the classic window and its refusal."""
+    return llama_spec is not None and llama_spec.hd in LONG_HEAD_DIMS
+
+
+def decode_window(block: int, off: int, prefix: int, llama: bool) -> int:
+    """The text positions a KV-cache call may span: text_window, or -- ``llama``: a decoder that takes the long cache -- the model's
+    own block less the soft-prompt offset, with at most DECODE_LONG_MAX_KEYS keys per row, the ``prefix`` prompt rows included."""
+    return min(block - off, DECODE_LONG_MAX_KEYS - prefix) if llama else text_window(block, off, prefix)
+
+
+def cache_plan(block: int, off: int, prefix: int, total: int, llama: bool):
+    """-> (clen, long): the slots per row of the self-attention cache that a call over ``total`` id columns runs on, and whether it is
+    the long cache of the split-key attention.  A call that fits ``text_window(block, off, prefix)`` gets that window's cache -- what
+    every call got before the long form existed -- and long = False.  One that does not, on a decoder that takes the long cache
+    (``llama``: takes_long_cache), gets prefix + total slots rounded up to whole chunks, at most prefix + decode_window, and
+    long = True.  A total past ``decode_window`` is a ValueError naming that window, the same text for every decoder."""
+    try:
+        tmax = text_window(block, off, prefix)
+    except ValueError:
+        if not llama:
+            raise
+        tmax = 0
+    if total <= tmax:
+        return tmax + prefix, False
+    window = decode_window(block, off, prefix, llama)
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    return min(prefix + window, -(-(prefix + total) // LONG_CHUNK_KEYS) * LONG_CHUNK_KEYS), True
+
+
+PROMPT_PREFILL_MODES = ('steps', 'pass')
+
+
+def prefill_plan(mode: str, pmin: int, prefix: int, fam, causal: bool):
+    """How ``generate_captions`` fills the cache with the prompt columns every row shares -> (m, (pos, len)): the first m
+    prompt columns go through ONE forward pass, the counters start at (pos, len) -- the cache slot and the id column of the first
+    step -- and pmin - 1 - m prefill replays follow.  'steps': m = 0, the counters (prefix, 1), pmin - 1 replays: every prompt token a
+    decode step.  'pass': m = pmin - 1 and the counters (prefix + m, 1 + m): no prefill replay; pmin = 1 leaves m = 0, which IS
+    'steps'.  ``prefix``: the soft-prompt rows at the head of the cache; ``fam``: the nano-mini family's spec (None: a dense or
+    Llama-family decoder), refused under 'pass'; a non-causal decoder has no cache and nothing to plan: the mode is checked and ignored."""
+    if mode not in PROMPT_PREFILL_MODES:
+        raise ValueError(f'prompt_prefill = {mode!r}: one of {PROMPT_PREFILL_MODES}')
+    if pmin < 1 or prefix < 0:
+        raise ValueError(f'pmin = {pmin}, prefix = {prefix}: every row needs a prompt token, and a prefix cannot be negative')
+    if mode == 'steps' or not causal:
+        return 0, (prefix, 1)
+    if fam is not None:
+        raise NotImplementedError("prompt_prefill='pass' is not available for the nano-mini decoder family: a sparse layer caches the "
+                                  "positions it keeps by slot, not by position, which the one-pass scatter does not map; use 'steps'")
+    m = pmin - 1
+    return m, (prefix + m, 1 + m)
+
+
+class BeamSpec(NamedTuple):
+    """Arguments of a beam search (BeamSearchTokenGenerator's, models/generation_utils.py); eos None: no EOS rule."""
+    beam_width: int = 3
+    expansion: int = 4
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    consolidation_temperature: float = 1.0
+    eos: Optional[int] = None
+    log_boost: float = 0.0
+    ngram_sizes: tuple = (2, 3, 4)
+
+    def key(self):
+        return (int(self.beam_width), int(self.expansion), float(self.temperature), int(self.top_k or 0),
+                float(self.consolidation_temperature), -1 if self.eos is None else int(self.eos), float(self.log_boost),
+                tuple(int(n) for n in self.ngram_sizes))
+
+
+class _CaptionFields(NamedTuple):
+    ids: torch.Tensor                   # int64 [B, N, L]: prompt, new tokens up to and including the first emitted EOS, then the pad id
+    lengths: torch.Tensor               # int32 [B, N]: prompt + new tokens up to and including that EOS (P + max_new_tokens without one)
+    token_logprobs: torch.Tensor        # fp32 [B, N, L - P]: log_softmax of the step's raw logits at the chosen token; 0.0 past the EOS
+    logprob: torch.Tensor               # fp32 [B, N]: the row sums
+
+
+class GeneratedCaptions(_CaptionFields):
+    """What ``generate_captions`` returns; rows are batch-major (caption n of image b).  The four fields above are the tuple: it
+    unpacks into four and ``_fields`` names four, as before ``prompt_lengths`` existed.  ``prompt_lengths`` (int32 [B], or None when
+    every row's prompt fills all P columns) is the optional fifth argument and an attribute beside them; with it ``lengths`` counts
+    from p_b and ``token_logprobs`` is [B, N, L - Pmin], entry t belonging to column Pmin + t.  ``_replace`` and
+    ``_make`` build the four fields only."""
+    prompt_lengths: Optional[torch.Tensor] = None
+    beam_scores: Optional[torch.Tensor] = None      # fp32 [B, N] under num_beams > 1: the length-penalised score the N
+                                                    # captions of an image are sorted by, best first; None in every other mode
+    phrase_index: Optional[torch.Tensor] = None     # int32 [B, N] under ``phrases``: the index into ``phrases`` of the
+                                                    # phrase the row emitted; None in every other mode
+
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None):
+        self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
+        self.prompt_lengths = prompt_lengths
+        self.beam_scores = beam_scores
+        self.phrase_index = phrase_index
+        return self
+
+
+class Processors(NamedTuple):
+    """The active logits processors of a ``generate_captions`` call, as ``caption_processors`` leaves them."""
+    theta: float                        # repetition penalty; the kernel and the host statement round it to fp32
+    inv_theta: float                    # fp32(1) / fp32(theta), formed once here: the device multiplies
+    min_new: int                        # EOS is banned while a row has emitted fewer tokens (0 without an EOS id: no rule)
+    suppress: tuple                     # distinct ids in [0, V) that are never emitted
+
+    def key(self):
+        """what a captured step bakes of them; the list's contents are copied into st.suppress per call"""
+        return (float(self.theta), int(self.min_new), len(self.suppress))
+
+
+def caption_processors(repetition_penalty: float, min_new_tokens: int, suppress_tokens, max_new_tokens: int, eos, vocab: Optional[int]):
+    """The refusals of ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` (host only) -> Processors, or None when none of
+    them is active: penalty 1, no suppressed id, and min_new_tokens 0 or no EOS id to ban (then the call is the one without them).
+    ``vocab`` None: ids are not checked against a vocabulary.  Duplicates in the list are dropped; an EOS id in the list together with
+    min_new_tokens > 0 is allowed (the same -inf twice)."""
+    theta = float(repetition_penalty)
+    if not np.isfinite(theta) or theta <= 0:
+        raise ValueError(f'repetition_penalty = {repetition_penalty}: a finite value above 0 is needed (1.0: none)')
+    with np.errstate(all='ignore'):
+        inv = np.float32(1.0) / np.float32(theta)
+    if not (np.isfinite(inv) and inv > 0 and np.isfinite(np.float32(theta)) and np.float32(theta) > 0):
+        raise ValueError(f'repetition_penalty = {repetition_penalty}: neither it nor its reciprocal is a positive finite fp32 number')
+    min_new = int(min_new_tokens)
+    if min_new != min_new_tokens or min_new < 0:
+        raise ValueError(f'min_new_tokens = {min_new_tokens}: a whole number of tokens, 0 or more')
+    if min_new > max_new_tokens:
+        raise ValueError(f'min_new_tokens = {min_new} exceeds max_new_tokens = {max_new_tokens}')
+    if isinstance(suppress_tokens, torch.Tensor):
+        suppress_tokens = suppress_tokens.detach().cpu().reshape(-1).tolist()
+    suppress = []
+    for t in (suppress_tokens if suppress_tokens is not None else ()):
+        if int(t) != t:
+            raise ValueError(f'suppress_tokens holds {t!r}: token ids are integers')
+        if int(t) < 0 or (vocab is not None and int(t) >= vocab):
+            raise ValueError(f'suppress_tokens holds {int(t)}: outside the vocabulary [0, {vocab if vocab is not None else "V"})')
+        if int(t) not in suppress:
+            suppress.append(int(t))
+    if vocab is not None and len(suppress) >= vocab:
+        raise ValueError(f'suppress_tokens covers the whole vocabulary of {vocab} tokens: nothing is left to emit')
+    if eos is None:
+        min_new = 0
+    if theta == 1.0 and not suppress and min_new == 0:
+        return None
+    return Processors(theta, float(inv), min_new, tuple(suppress))
+
+
+def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False):
+    """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
+    ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
+    ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
+    the count then reads the device's table).  ``trie`` (a ``phrases`` call): ('trie', eos, ...that key) -- the trie's
+    contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key."""
+    key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
+    key = key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
+    return ('trie', eos) + key if trie else key
+
+
+def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
+                              num_beams=1, causal: bool = True) -> PhraseTrie:
+    """``phrase_trie`` and then what ``phrases`` does not combine with, all before anything runs -> the trie.  NotImplementedError,
+    naming the reason: ``prompt_lengths``, an active logits processor, ``num_beams`` > 1, a non-causal decoder.  ``phrases`` may be a
+    ``PhraseTrie`` that an earlier call of this function built (the model hands its own to the decoder): it is not built again, only
+    held against this call's ``eos``, ``vocab`` and ``max_new_tokens``."""
+    if isinstance(phrases, PhraseTrie):
+        trie = phrases
+        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+                or bool((trie.child_tok == int(eos)).any()) or max_new_tokens < trie.longest + 1:
+            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}, max_new_tokens = '
+                             f'{max_new_tokens} against a longest phrase of {trie.longest} tokens')
+    else:
+        trie = phrase_trie(phrases, eos, vocab, max_new_tokens)
+    if prompt_lengths is not None:
+        raise NotImplementedError('phrases with prompt_lengths: a forced prompt column would have to hold the trie still, and the ragged '
+                                  'finish rule has no such case')
+    if processors_active:
+        raise NotImplementedError('phrases with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
+                                  'emitted, and a processor could leave a node without an allowed token')
+    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
+        raise NotImplementedError('phrases under num_beams > 1: the beam step has no trie state per hypothesis')
+    if not causal:
+        raise NotImplementedError('phrases run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
+                                  '(generate_by_recompute), which has no constrained step')
+    return trie
+
+
+class PhraseScores(NamedTuple):
+    """What ``score_phrases`` returns."""
+    logprob: torch.Tensor               # fp32 [B, K]: the raw log-likelihood of phrase k + EOS after image b's prompt (``score``'s quantity)
+    best: torch.Tensor                  # int64 [B]: the argmax over k, the lowest index on ties (duplicate phrases tie exactly)
+    lengths: torch.Tensor               # int32 [K]: the tokens of each phrase + 1 (the EOS)
+
+
+def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
+                            images_per_pass=None) -> PhraseTrie:
+    """The refusals of ``score_phrases``, all before anything runs -> the trie.  ValueError: everything ``phrase_trie`` refuses about the
+    set (or a ``PhraseTrie`` built for another EOS / vocabulary, or one without ``phrase_node``), prompt + longest phrase + 1 past
+    the decode ``window`` (the text of every other call), ``images_per_pass`` < 1.  NotImplementedError, naming the reason: a
+    non-causal decoder, sparse nano-mini blocks."""
+    if isinstance(phrases, PhraseTrie):
+        trie = phrases
+        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+                or bool((trie.child_tok == int(eos)).any()):
+            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
+        phrase_node_csr(trie)
+    else:
+        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
+    if not causal:
+        raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
+                                  'state of the earlier ones --, so use rerank')
+    if sparse:
+        raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
+                                  'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
+    total = int(P) + trie.longest + 1
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
+        raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
+    return trie
+
+
+def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,
+                       min_new_tokens: int = 0, suppress_tokens=None, vocab: Optional[int] = None, formed=None):
+    """the refusals of generate_captions that need no device; those of the logits processors are ``caption_processors``' (``formed``:
+    what ``plan_captions`` hands every check in its place -- it enters ``caption_processors`` once per call and yields the result)"""
+    if N < 1:
+        raise ValueError(f'num_return_sequences = {N}: at least one caption per image')
+    if sampling is None and N > 1:
+        raise ValueError(f'greedy decoding with num_return_sequences = {N}: the {N} rows of an image would be identical; sample instead')
+    if sampling is not None and not sampling.temperature > 0:
+        raise ValueError('sampling needs a positive temperature')
+    if eos is not None and eos < 0:
+        raise ValueError(f'eos_token_id = {eos}')
+    if pad is not None and pad < 0:
+        raise ValueError(f'pad_token_id = {pad}')
+    if poll_every < 0 or max_new_tokens < 0:
+        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+    formed() if formed is not None else caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab)
+
+
+def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: Optional[Sampling], eos, pad, poll_every: int,
+                              max_new_tokens: int, **processors) -> np.ndarray:
+    """check_caption_args, and the refusals of ``prompt_lengths`` (read on the host, before anything moves to the device): one integer
+    per image, 1 <= p_b <= P  -> the lengths, int32 [B]"""
+    check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **processors)
+    if isinstance(prompt_lengths, torch.Tensor):
+        if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
+            raise ValueError(f'prompt_lengths of dtype {prompt_lengths.dtype}: integers are needed')
+        plen = prompt_lengths.detach().cpu().numpy()
+    else:
+        plen = np.asarray(prompt_lengths)
+        if plen.size and not np.issubdtype(plen.dtype, np.integer):
+            raise ValueError(f'prompt_lengths of type {plen.dtype}: integers are needed')
+    if plen.shape != (B,):
+        raise ValueError(f'prompt_lengths of shape {tuple(plen.shape)} for prompt_ids of {B} rows: one length per image, shape ({B},)')
+    if B and int(plen.min()) < 1:
+        raise ValueError(f'prompt_lengths[{int(plen.argmin())}] = {int(plen.min())}: every row needs at least one prompt token')
+    if B and int(plen.max()) > P:
+        raise ValueError(f'prompt_lengths[{int(plen.argmax())}] = {int(plen.max())} exceeds the {P} columns of prompt_ids')
+    return plen.astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------ caption beams
+MAX_CAPTION_BEAMS = 8               # i2t_beam_candidates takes E = 2 W <= 16
+BEAM_DEAD = -1.0e9                  # the running score of beams 1 .. W - 1 before the first step (transformers' constant)
+
+
+def check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature=1.0, top_k=None, nucleus_p=None,
+                            seed=None, prompt_lengths=None, prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0,
+                            suppress_tokens=None, max_new_tokens=1, eos=None, pad=None, poll_every=8, causal=True, vocab=None, formed=None) -> int:
+    """The refusals of ``generate_captions(num_beams=W, ...)`` that need no device, all before anything runs -> W.  W = 1 is the call
+    without the beam arguments: only W itself, ``length_penalty`` and ``early_stopping`` are looked at.  ValueError: W outside
+    1 .. MAX_CAPTION_BEAMS (the candidates kernel takes E = 2 W <= 16), N outside 1 .. W, a non-finite ``length_penalty``,
+    ``early_stopping`` not False / True ("never" is out of scope), any sampling argument (beam sampling is out of scope), a negative
+    id or count.  NotImplementedError, naming the reason: ``prompt_lengths``, ``prompt_prefill='pass'``, an active
+    ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens``, a non-causal decoder.  ``formed``: as in ``check_caption_args``."""
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
+        raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the candidates kernel takes 2 * num_beams '
+                         f'<= 16 candidates per row)')
+    W = int(num_beams)
+    try:
+        finite = bool(np.isfinite(float(length_penalty)))
+    except (TypeError, ValueError):
+        finite = False
+    if not finite:
+        raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
+    if not isinstance(early_stopping, (bool, np.bool_)):
+        raise ValueError(f'early_stopping = {early_stopping!r}: False or True ("never" is not supported)')
+    if W == 1:
+        return W
+    N = int(num_return_sequences)
+    if not 1 <= N <= W:
+        raise ValueError(f'num_return_sequences = {N} with num_beams = {W}: from 1 to num_beams captions per image')
+    if temperature != 1 or top_k is not None or nucleus_p is not None or seed is not None:
+        raise ValueError('num_beams > 1 is deterministic beam search: temperature, top_k, nucleus_p and seed must stay at their defaults '
+                         '(beam sampling is not supported)')
+    if (eos is not None and eos < 0) or (pad is not None and pad < 0):
+        raise ValueError(f'eos_token_id = {eos}, pad_token_id = {pad}: neither may be negative')
+    if poll_every < 0 or max_new_tokens < 0:
+        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
+    if (formed() if formed is not None else caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab)) is not None:
+        raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens under num_beams > 1: the beam step has no '
+                                  'logits-processor pass')
+    if prompt_lengths is not None:
+        raise NotImplementedError('prompt_lengths under num_beams > 1: the beam step has no forcing table for ragged prompts')
+    if prompt_prefill not in PROMPT_PREFILL_MODES:
+        raise ValueError(f'prompt_prefill = {prompt_prefill!r}: one of {PROMPT_PREFILL_MODES}')
+    if prompt_prefill != 'steps':
+        raise NotImplementedError("prompt_prefill='pass' under num_beams > 1: the beam rows are prefilled step by step under the identity "
+                                  "history table")
+    if not causal:
+        raise NotImplementedError('num_beams > 1 needs a causal decoder: a non-causal one has no KV cache to run the beams on')
+    return W
+
+
+# ------------------------------------------------------------------------------------------------ one plan per call
+class CaptionFacts(NamedTuple):
+    """What ``plan_captions`` needs to know of the model."""
+    V: int                              # the vocabulary
+    causal: bool                        # False: no cache, the call runs by re-evaluation
+    fam: object                         # the nano-mini family's spec, as ``prefill_plan`` takes it (None: a dense or Llama-family decoder)
+    window: int                         # the text window: decoder.block_size - space_for_prompt
+    prefix: int                         # the soft-prompt rows at the head of the cache: min(ncls, block) when the decoder is prefixed, else 0
+
+
+class CaptionPlan(NamedTuple):
+    """What a ``generate_captions`` call is, every argument checked and resolved (``plan_captions``): the drivers run it as it stands."""
+    mode: str                           # 'cache' (CaptionDecoder), 'beam' (CaptionBeamDecoder), 'recompute' (a non-causal decoder)
+    N: int                              # captions per image
+    W: int                              # beams per image (1: no beam search)
+    sampling: Optional[Sampling]        # None: greedy
+    eos: Optional[int]
+    pad: int                            # resolved: the EOS id by default, 0 without one
+    poll_every: int
+    max_new: int
+    plen: Optional[np.ndarray]          # int32 [B] under ``prompt_lengths``, else None
+    pmin: int                           # the shortest and the longest prompt (both P without ``prompt_lengths``)
+    pmax: int
+    prompt_prefill: str
+    m: int                              # ``prefill_plan``'s: the prompt columns one forward pass takes ...
+    start: tuple                        # ... and the (pos, len) the counters start at
+    proc: Optional[Processors]          # None: no logits processor is active
+    trie: Optional[PhraseTrie]          # None: no ``phrases``
+    length_penalty: float
+    early_stopping: bool
+
+
+def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
+                  temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None, prompt_prefill='steps',
+                  repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1, length_penalty=1.0, early_stopping=False,
+                  phrases=None, *, sampling=...) -> CaptionPlan:
+    """The one place that says what ``generate_captions(...)`` on ``prompt_ids`` [B, P] means, or refuses it: the arguments are the model
+    method's (``sampling``: the decoders' keyword methods hand their ``Sampling`` or None in place of the four sampling arguments).
+    Refusals come in this order, the first that applies wins: ``phrases`` (``check_phrase_caption_args``, behind the logits processors'
+    own ValueErrors); the beam arguments (``check_beam_caption_args``); under num_beams = W > 1 the text window, then 2 W > V; else
+    ``check_caption_args`` / ``check_ragged_caption_args``; an active processor on a non-causal decoder; ``prefill_plan``'s; the text
+    window.  At W = 1 only ``num_beams``, ``length_penalty`` and ``early_stopping`` are looked at among the beam arguments."""
+    eos, pad, formed = eos_token_id, pad_token_id, []
+
+    def processors():                   # caption_processors, entered once, by the first check that reaches it: its refusals keep their place
+        if not formed:
+            formed.append(caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, facts.V))
+        return formed[0]
+    procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, vocab=facts.V,
+                 formed=processors)
+    trie = None
+    if phrases is not None:             # before the beam checks: those keep their own texts
+        trie = check_phrase_caption_args(phrases, eos, facts.V, max_new_tokens, prompt_lengths, processors() is not None, num_beams,
+                                         facts.causal)
+    W = check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature=temperature, top_k=top_k,
+                                nucleus_p=nucleus_p, seed=seed, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
+                                max_new_tokens=max_new_tokens, eos=eos, pad=pad, poll_every=poll_every, causal=facts.causal, **procs)
+    N = int(num_return_sequences)
+    if W > 1:
+        if P + max_new_tokens > facts.window:
+            raise ValueError(f'prompt + new tokens ({P + max_new_tokens}) exceed the text window ({facts.window})')
+        if W * 2 > facts.V:
+            raise ValueError(f'num_beams = {W} needs 2 * num_beams candidates per row: the vocabulary holds {facts.V} tokens')
+        return CaptionPlan('beam', N, W, None, eos, int((0 if eos is None else eos) if pad is None else pad), poll_every, max_new_tokens, None,
+                           P, P, prompt_prefill, 0, (facts.prefix, 1), None, None, float(length_penalty), bool(early_stopping))
+    if sampling is ...:
+        sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
+    if prompt_lengths is None:
+        check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
+        plen, pmin, pmax = None, P, P
+    else:
+        plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
+        pmin, pmax = int(plen.min()), int(plen.max())
+    proc = processors()
+    if not facts.causal and proc is not None:
+        raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens run inside the KV-cache caption step; a non-causal '
+                                  'decoder generates by re-evaluation (generate_by_recompute), which has no processed step')
+    m, start = prefill_plan(prompt_prefill, pmin, facts.prefix, facts.fam, facts.causal)
+    if pmax + max_new_tokens > facts.window:
+        raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({facts.window})')
+    return CaptionPlan('cache' if facts.causal else 'recompute', N, 1, sampling, eos, (0 if eos is None else eos) if pad is None else pad,
+                       poll_every, max_new_tokens, plen, pmin, pmax, prompt_prefill, m, start, proc, trie, float(length_penalty),
+                       bool(early_stopping))
+

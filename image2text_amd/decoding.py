@@ -18,16 +18,31 @@ trainer.py:41-56) run on the same cached step: only its last kernel differs -- `
 instead of the ban + argmax -- so a sampled token also costs one hipGraph replay and no host sync.  The draw is a
 counter-based function of (seed, step, row): ``Sampling.seed`` comes from torch's CPU generator once per call, so
 ``torch.manual_seed`` reproduces a run.
+
+This module holds the device drivers and re-exports its device-free siblings: caption_plan.py says what a call means (argument
+tuples, window and cache planners, every refusal, ``plan_captions``), phrase_trie.py builds the phrase tries and their level tables,
+decoding_host.py holds the numpy statements the kernels are tested against.
 """
 import os
 from types import SimpleNamespace
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import ops
+from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
+                           PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseScores, Processors, Sampling,
+                           cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
+                           check_phrase_caption_args, check_phrase_score_args, check_ragged_caption_args, decode_window, plan_captions,
+                           prefill_plan, takes_long_cache, text_window)
+from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
+                            beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_scores_host,
+                            process_logits_host, slot_positions, split_attention_host, trie_advance_host, trie_mask_host)
 from .engine import BF16, F32, HotPath
+from .phrase_trie import PhraseTrie, TrieLevel, TrieLevels, level_expand_tables, phrase_node_csr, phrase_trie, trie_levels
+
+assert LONG_CHUNK_KEYS == ops.LONG_CHUNK_KEYS       # caption_plan.py loads no library: it keeps the figure, ops.py the kernels' copy
 
 
 ENC_CHUNK = int(os.environ.get('I2T_DECODE_ENC_CHUNK', '4096'))      # images per encoder pass inside generate()
@@ -35,150 +50,6 @@ TOP2_HEAD = os.environ.get('I2T_DECODE_TOP2', '1') not in ('', '0')    # greedy 
 
 
 PREFILL_ROWS = int(os.environ.get('I2T_PREFILL_ROWS', '8192'))       # token rows per forward pass of prompt_prefill='pass' 
-
-
-class Sampling(NamedTuple):
-    """How the next token is chosen when it is not the argmax (arguments of the reference's generate, :136-137)."""
-    temperature: float = 1.0
-    top_k: Optional[int] = None
-    nucleus_p: Optional[float] = None
-    seed: Optional[int] = None          # 64-bit; None: drawn from torch's CPU generator at the start of the call
-
-    def key(self):
-        return (float(self.temperature), int(self.top_k or 0), None if self.nucleus_p is None else float(self.nucleus_p))
-
-
-# i2t_decode_attention and i2t_gq_decode_attention (csrc/common.h::DECODE_MAX_KEYS) keep the scores of at most this many keys per caption
-# in LDS; neither reads a key count from the device against it, so the cache THEY attend over is never allocated longer (a longer
-# one is the long state's, below, and runs other kernels)
-DECODE_MAX_KEYS = 1024
-
-
-def text_window(block: int, off: int, prefix: int) -> int:
-    """Text positions of the decode step's self-attention cache: the decoder's block less the soft-prompt offset ``off``, capped so
-    that ``prefix`` cached prompt rows + the text fit in DECODE_MAX_KEYS keys."""
-    tmax = min(block - off, DECODE_MAX_KEYS - prefix)
-    if tmax < 1:
-        raise ValueError(f'the KV-cache decode step attends over at most {DECODE_MAX_KEYS} keys per caption: {prefix} prompt rows leave '
-                         f'no room for text (block {block}, soft-prompt offset {off})')
-    return tmax
-
-
-# The Llama-family decoders with heads of 64 or 128 (row-major cache) have a second attention form, i2t_gq_decode_attention_long,
-# which splits a row's keys into chunks of LONG_CHUNK_KEYS across workgroups and bounds a row by its workspace alone
-# (csrc/common.h::LONG_CHUNK_KEYS / DECODE_LONG_MAX_KEYS, both pinned by tests/test_long_decode_host_cpu.py; DESIGN.md 4r).  A call
-# that fits text_window never sees it.
-LONG_CHUNK_KEYS = ops.LONG_CHUNK_KEYS
-DECODE_LONG_MAX_KEYS = 32768
-LONG_HEAD_DIMS = (64, 128)          # the head widths the split-key kernels are built for
-
-
-def takes_long_cache(llama_spec) -> bool:
-    """Whether a decoder may decode past text_window: ``llama_spec`` is its Llama-family spec (engine.dec.llama; None for the dense and
-    nano-mini decoders).  The plugins also accept heads of 16 and 32, which the split-key kernels are not built for: those decoders
-    keep the classic window and its refusal."""
-    return llama_spec is not None and llama_spec.hd in LONG_HEAD_DIMS
-
-
-def decode_window(block: int, off: int, prefix: int, llama: bool) -> int:
-    """The text positions a KV-cache call may span: text_window, or -- ``llama``: a decoder that takes the long cache -- the model's
-    own block less the soft-prompt offset, with at most DECODE_LONG_MAX_KEYS keys per row, the ``prefix`` prompt rows included."""
-    return min(block - off, DECODE_LONG_MAX_KEYS - prefix) if llama else text_window(block, off, prefix)
-
-
-def cache_plan(block: int, off: int, prefix: int, total: int, llama: bool):
-    """-> (clen, long): the slots per row of the self-attention cache that a call over ``total`` id columns runs on, and whether it is
-    the long cache of the split-key attention.  A call that fits ``text_window(block, off, prefix)`` gets that window's cache -- what
-    every call got before the long form existed -- and long = False.  One that does not, on a decoder that takes the long cache
-    (``llama``: takes_long_cache), gets prefix + total slots rounded up to whole chunks, at most prefix + decode_window, and
-    long = True.  A total past ``decode_window`` is a ValueError naming that window, the same text for every decoder."""
-    try:
-        tmax = text_window(block, off, prefix)
-    except ValueError:
-        if not llama:
-            raise
-        tmax = 0
-    if total <= tmax:
-        return tmax + prefix, False
-    window = decode_window(block, off, prefix, llama)
-    if total > window:
-        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
-    return min(prefix + window, -(-(prefix + total) // LONG_CHUNK_KEYS) * LONG_CHUNK_KEYS), True
-
-
-def split_attention_host(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, chunk: int = LONG_CHUNK_KEYS) -> np.ndarray:
-    """What the split-key decode attention computes, on the host in fp64 (numpy): q [hd] against k / v [n][hd].  Every chunk of
-    ``chunk`` keys yields its maximum m_c, s_c = sum exp(score - m_c) and the unnormalised a_c = sum exp(score - m_c) v
-    (gq_decode_attention_split_kernel); the combine takes M = max m_c and returns sum_c a_c exp(m_c - M) / sum_c s_c exp(m_c - M), the
-    chunks in order."""
-    q, k, v = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64), np.asarray(v, dtype=np.float64)
-    n = k.shape[0]
-    assert n >= 1 and chunk >= 1 and k.shape == v.shape and q.shape == k.shape[1:]
-    parts = []
-    for lo in range(0, n, chunk):
-        s = (k[lo:lo + chunk] @ q) * scale
-        m = s.max()
-        p = np.exp(s - m)
-        parts.append((m, p.sum(), p @ v[lo:lo + chunk]))
-    M = max(m for m, _, _ in parts)
-    num, den = np.zeros_like(q), 0.0
-    for m, s, a in parts:
-        f = np.exp(m - M)
-        num, den = num + a * f, den + s * f
-    return num / den
-
-
-PROMPT_PREFILL_MODES = ('steps', 'pass')
-
-
-def prefill_plan(mode: str, pmin: int, prefix: int, fam, causal: bool):
-    """How ``generate_captions`` fills the cache with the prompt columns every row shares -> (m, (pos, len)): the first m
-    prompt columns go through ONE forward pass, the counters start at (pos, len) -- the cache slot and the id column of the first
-    step -- and pmin - 1 - m prefill replays follow.  'steps': m = 0, the counters (prefix, 1), pmin - 1 replays: every prompt token a
-    decode step.  'pass': m = pmin - 1 and the counters (prefix + m, 1 + m): no prefill replay; pmin = 1 leaves m = 0, which IS
-    'steps'.  ``prefix``: the soft-prompt rows at the head of the cache; ``fam``: the nano-mini family's spec (None: a dense or
-    Llama-family decoder), refused under 'pass'; a non-causal decoder has no cache and nothing to plan: the mode is checked and ignored."""
-    if mode not in PROMPT_PREFILL_MODES:
-        raise ValueError(f'prompt_prefill = {mode!r}: one of {PROMPT_PREFILL_MODES}')
-    if pmin < 1 or prefix < 0:
-        raise ValueError(f'pmin = {pmin}, prefix = {prefix}: every row needs a prompt token, and a prefix cannot be negative')
-    if mode == 'steps' or not causal:
-        return 0, (prefix, 1)
-    if fam is not None:
-        raise NotImplementedError("prompt_prefill='pass' is not available for the nano-mini decoder family: a sparse layer caches the "
-                                  "positions it keeps by slot, not by position, which the one-pass scatter does not map; use 'steps'")
-    m = pmin - 1
-    return m, (prefix + m, 1 + m)
-
-
-def kv_prefill_host(src: np.ndarray, k_off: int, v_off: int, src_T: int, src_t0: int, m: int, kcache: np.ndarray, vcache: np.ndarray,
-                    cache_bs: int, cache_rs: int, cache_hs: int, hd: int, w: int, slot0: int, B: int, N: int):
-    """What i2t_kv_prefill does, on the host (numpy): ``src`` [rows, src_ld] holds K at columns k_off .. k_off + w - 1 and V at v_off ..;
-    token t < m of image b is source row b * src_T + src_t0 + t and goes to slot slot0 + t of cache rows b * N .. b * N + N - 1.
-    ``kcache`` / ``vcache`` are FLAT arrays, element (row, head, slot, column) at row * cache_bs + head * cache_hs + slot * cache_rs +
-    column (head-major [R][H][clen][64]: cache_rs = 64, cache_hs = clen * 64; row-major [R][clen][w]: cache_rs = w, cache_hs = hd).
-    Written in place; nothing else is touched."""
-    assert kcache.ndim == 1 and vcache.ndim == 1 and w % hd == 0 and src_t0 + m <= src_T
-    for b in range(B):
-        for t in range(m):
-            row = src[b * src_T + src_t0 + t]
-            for n in range(N):
-                for h in range(w // hd):
-                    at = (b * N + n) * cache_bs + h * cache_hs + (slot0 + t) * cache_rs
-                    kcache[at:at + hd] = row[k_off + h * hd:k_off + (h + 1) * hd]
-                    vcache[at:at + hd] = row[v_off + h * hd:v_off + (h + 1) * hd]
-
-
-def slot_positions(member: np.ndarray) -> np.ndarray:
-    """int32 [L][slots] from a sparse decoder's membership table (int [L][tmax], 1 where layer l keeps text position p): row l lists
-    the text positions layer l keeps, in order, zero-padded -- the position whose K/V sit at each cache slot (slot = rank of the
-    position among the kept ones); slots = the largest count, at least 1."""
-    member = np.asarray(member) != 0
-    kpos = np.zeros((member.shape[0], max(int(member.sum(axis=1).max(initial=0)), 1)), dtype=np.int32)
-    for l, row in enumerate(member):
-        kept = np.flatnonzero(row)
-        kpos[l, :kept.size] = kept
-    return kpos
 
 
 class GreedyDecoder:
@@ -725,23 +596,6 @@ class GreedyDecoder:
         return out
 
 
-class BeamSpec(NamedTuple):
-    """Arguments of a beam search (BeamSearchTokenGenerator's, models/generation_utils.py); eos None: no EOS rule."""
-    beam_width: int = 3
-    expansion: int = 4
-    temperature: float = 1.0
-    top_k: Optional[int] = None
-    consolidation_temperature: float = 1.0
-    eos: Optional[int] = None
-    log_boost: float = 0.0
-    ngram_sizes: tuple = (2, 3, 4)
-
-    def key(self):
-        return (int(self.beam_width), int(self.expansion), float(self.temperature), int(self.top_k or 0),
-                float(self.consolidation_temperature), -1 if self.eos is None else int(self.eos), float(self.log_boost),
-                tuple(int(n) for n in self.ngram_sizes))
-
-
 class BeamDecoder(GreedyDecoder):
     """Beam search on the static KV cache: R = B * W rows (batch-major, r = b * W + w) through GreedyDecoder's buffers and layer
     sequence, under GreedyDecoder._replay (no poll).  The step's head is the fp32 lm_head, then on the device (csrc/beam.hip):
@@ -832,485 +686,6 @@ class BeamDecoder(GreedyDecoder):
         ids = st.ids[:, :L].reshape(B, W, L).clone()
         scores = st.scores.view(B, W).clone()
         return (ids, scores, draws[:L - P]) if record else (ids, scores)
-
-
-class _CaptionFields(NamedTuple):
-    ids: torch.Tensor                   # int64 [B, N, L]: prompt, new tokens up to and including the first emitted EOS, then the pad id
-    lengths: torch.Tensor               # int32 [B, N]: prompt + new tokens up to and including that EOS (P + max_new_tokens without one)
-    token_logprobs: torch.Tensor        # fp32 [B, N, L - P]: log_softmax of the step's raw logits at the chosen token; 0.0 past the EOS
-    logprob: torch.Tensor               # fp32 [B, N]: the row sums
-
-
-class GeneratedCaptions(_CaptionFields):
-    """What ``generate_captions`` returns; rows are batch-major (caption n of image b).  The four fields above are the tuple: it
-    unpacks into four and ``_fields`` names four, as before ``prompt_lengths`` existed.  ``prompt_lengths`` (int32 [B], or None when
-    every row's prompt fills all P columns) is the optional fifth argument and an attribute beside them; with it ``lengths`` counts
-    from p_b and ``token_logprobs`` is [B, N, L - Pmin], entry t belonging to column Pmin + t.  ``_replace`` and
-    ``_make`` build the four fields only."""
-    prompt_lengths: Optional[torch.Tensor] = None
-    beam_scores: Optional[torch.Tensor] = None      # fp32 [B, N] under num_beams > 1 (DESIGN.md 4t): the length-penalised score the N
-                                                    # captions of an image are sorted by, best first; None in every other mode
-    phrase_index: Optional[torch.Tensor] = None     # int32 [B, N] under ``phrases`` (DESIGN.md 4u): the index into ``phrases`` of the
-                                                    # phrase the row emitted; None in every other mode
-
-    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None):
-        self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
-        self.prompt_lengths = prompt_lengths
-        self.beam_scores = beam_scores
-        self.phrase_index = phrase_index
-        return self
-
-
-def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional[int] = None, token_logprobs: Optional[np.ndarray] = None):
-    """The finish rule of ``generate_captions`` on the host (numpy): what i2t_caption_finish does step by step on the device, applied to
-    whole rows.  ``ids`` [R, P + T]: the prompt and the T tokens a chooser emitted for every row (it goes on emitting after an EOS).  A row
-    is finished once it has EMITTED ``eos`` -- an EOS inside the prompt does not count --, that EOS is kept, later columns hold ``pad``
-    (default: the EOS id) and log-prob 0.0, a row without one has length P + T; ``eos`` None: no rule.  The steps end once every row has
-    finished, so L = lengths.max().  This is ``apply_finish_rule_ragged`` with every prompt P long, less its refusals (no rows, or an
-    empty prompt, pass).  -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - P] or None)"""
-    ids = np.array(ids)
-    return _finish_rows(ids, np.full(ids.shape[0], P, dtype=np.int64), P, ids.shape[1] - P, eos, pad, token_logprobs)
-
-
-def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[int], pad: Optional[int] = None,
-                             token_logprobs: Optional[np.ndarray] = None):
-    """``apply_finish_rule`` for rows whose prompts differ in length: what i2t_caption_finish_ragged does step by step on the device.
-    ``ids`` [R, Pmax + max_new]: row r holds its prompt in columns < plen[r] and the tokens a chooser emitted from column plen[r] on
-    (columns at or past plen[r] + max_new are not read); ``token_logprobs`` [R, Pmax + max_new - Pmin] is aligned by COLUMN, entry t
-    belonging to column Pmin + t.  A row is finished once it has EMITTED ``eos`` (an EOS inside its prompt does not count; ``eos``
-    None: never) or ``max_new`` tokens; ``lengths[r]`` = plen[r] + the emitted tokens up to and including that EOS; later columns hold
-    ``pad`` (default: the EOS id, 0 without one) and log-prob 0.0, and so do a row's prompt columns (nothing was chosen there).
-    L = lengths.max().  With every plen[r] = P this is ``apply_finish_rule(ids, P, eos, pad, token_logprobs)``.
-    -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - Pmin] or None)"""
-    ids = np.array(ids)
-    plen = np.asarray(plen, dtype=np.int64).reshape(-1)
-    R, total = ids.shape
-    assert plen.shape == (R,) and R >= 1 and max_new >= 0 and int(plen.min()) >= 1 and int(plen.max()) + max_new == total
-    return _finish_rows(ids, plen, int(plen.min()), max_new, eos, pad, token_logprobs)
-
-
-def _finish_rows(ids: np.ndarray, plen: np.ndarray, pmin: int, max_new: int, eos, pad, token_logprobs):
-    """the rule both ``apply_finish_rule`` forms state; ``ids`` is the caller's copy and is written"""
-    R, total = ids.shape
-    pad = (0 if eos is None else eos) if pad is None else pad
-    lengths = (plen + max_new).astype(np.int32)
-    for r in range(R if eos is not None else 0):
-        hit = np.flatnonzero(ids[r, plen[r]:plen[r] + max_new] == eos)
-        if hit.size:
-            lengths[r] = plen[r] + int(hit[0]) + 1
-    L = int(lengths.max()) if R else total
-    ids = ids[:, :L]
-    lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - pmin]
-    for r in range(R):
-        ids[r, lengths[r]:] = pad
-        if lp is not None:
-            lp[r, :plen[r] - pmin] = 0.0
-            lp[r, lengths[r] - pmin:] = 0.0
-    return ids, lengths, lp
-
-
-class Processors(NamedTuple):
-    """The active logits processors of a ``generate_captions`` call, as ``caption_processors`` leaves them."""
-    theta: float                        # repetition penalty; the kernel and the host statement round it to fp32
-    inv_theta: float                    # fp32(1) / fp32(theta), formed once here: the device multiplies
-    min_new: int                        # EOS is banned while a row has emitted fewer tokens (0 without an EOS id: no rule)
-    suppress: tuple                     # distinct ids in [0, V) that are never emitted
-
-    def key(self):
-        """what a captured step bakes of them; the list's contents are copied into st.suppress per call"""
-        return (float(self.theta), int(self.min_new), len(self.suppress))
-
-
-def caption_processors(repetition_penalty: float, min_new_tokens: int, suppress_tokens, max_new_tokens: int, eos, vocab: Optional[int]):
-    """The refusals of ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens`` (host only) -> Processors, or None when none of
-    them is active: penalty 1, no suppressed id, and min_new_tokens 0 or no EOS id to ban (then the call is the one without them).
-    ``vocab`` None: ids are not checked against a vocabulary.  Duplicates in the list are dropped; an EOS id in the list together with
-    min_new_tokens > 0 is allowed (the same -inf twice)."""
-    theta = float(repetition_penalty)
-    if not np.isfinite(theta) or theta <= 0:
-        raise ValueError(f'repetition_penalty = {repetition_penalty}: a finite value above 0 is needed (1.0: none)')
-    with np.errstate(all='ignore'):
-        inv = np.float32(1.0) / np.float32(theta)
-    if not (np.isfinite(inv) and inv > 0 and np.isfinite(np.float32(theta)) and np.float32(theta) > 0):
-        raise ValueError(f'repetition_penalty = {repetition_penalty}: neither it nor its reciprocal is a positive finite fp32 number')
-    min_new = int(min_new_tokens)
-    if min_new != min_new_tokens or min_new < 0:
-        raise ValueError(f'min_new_tokens = {min_new_tokens}: a whole number of tokens, 0 or more')
-    if min_new > max_new_tokens:
-        raise ValueError(f'min_new_tokens = {min_new} exceeds max_new_tokens = {max_new_tokens}')
-    if isinstance(suppress_tokens, torch.Tensor):
-        suppress_tokens = suppress_tokens.detach().cpu().reshape(-1).tolist()
-    suppress = []
-    for t in (suppress_tokens if suppress_tokens is not None else ()):
-        if int(t) != t:
-            raise ValueError(f'suppress_tokens holds {t!r}: token ids are integers')
-        if int(t) < 0 or (vocab is not None and int(t) >= vocab):
-            raise ValueError(f'suppress_tokens holds {int(t)}: outside the vocabulary [0, {vocab if vocab is not None else "V"})')
-        if int(t) not in suppress:
-            suppress.append(int(t))
-    if vocab is not None and len(suppress) >= vocab:
-        raise ValueError(f'suppress_tokens covers the whole vocabulary of {vocab} tokens: nothing is left to emit')
-    if eos is None:
-        min_new = 0
-    if theta == 1.0 and not suppress and min_new == 0:
-        return None
-    return Processors(theta, float(inv), min_new, tuple(suppress))
-
-
-def process_logits_host(z, ids_row, length: int, emitted: int, theta: float, suppress, eos: Optional[int], min_new: int) -> np.ndarray:
-    """What i2t_caption_logits_process leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): it is to the
-    pre-pass what ``apply_finish_rule`` is to the finish kernel.  In the order of transformers' RepetitionPenaltyLogitsProcessor ->
-    SuppressTokensLogitsProcessor -> MinNewTokensLengthLogitsProcessor: every DISTINCT token t of ``ids_row[:length]`` (the prompt
-    included) gets z[t] * fp32(1 / theta) if z[t] > 0, else z[t] * fp32(theta) -- one fp32 multiply, as on the device; z[t] = -inf
-    for t in ``suppress``; z[eos] = -inf while ``emitted`` < ``min_new`` (``eos`` None: no rule).  Ids outside [0, V) take no part."""
-    z = np.array(z, dtype=np.float32)
-    assert z.ndim == 1
-    V = z.shape[0]
-    th = np.float32(theta)
-    inv = np.float32(1.0) / th
-    seen = np.unique(np.asarray(ids_row).reshape(-1)[:length].astype(np.int64))
-    seen = seen[(seen >= 0) & (seen < V)]
-    v = z[seen]
-    z[seen] = np.where(v > 0, v * inv, v * th).astype(np.float32)
-    sup = [int(t) for t in (suppress if suppress is not None else ()) if 0 <= int(t) < V]
-    z[sup] = -np.inf
-    if eos is not None and 0 <= eos < V and emitted < min_new:
-        z[eos] = -np.inf
-    return z
-
-
-def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False):
-    """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
-    ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
-    ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
-    the count then reads the device's table).  ``trie`` (a ``phrases`` call): ('trie', eos, ...that key) -- the trie's
-    contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key."""
-    key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
-    key = key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
-    return ('trie', eos) + key if trie else key
-
-
-# ------------------------------------------------------------------------------------------------ phrase sets (DESIGN.md 4u)
-class PhraseTrie(NamedTuple):
-    """A phrase set as a flat CSR trie (``phrase_trie``); node 0 is the root.  All arrays numpy int32."""
-    child_off: np.ndarray               # [nodes + 1]: the children of node n are edges child_off[n] .. child_off[n + 1)
-    child_tok: np.ndarray               # [edges]: an edge's token, ascending within a node
-    child_next: np.ndarray              # [edges]: the node the edge leads to
-    term: np.ndarray                    # [nodes]: the index of the phrase that ends at the node (the lowest among duplicates), or -1
-    max_fanout: int                     # the largest number of children of a node
-    longest: int                        # the tokens of the longest phrase
-    phrase_node: Optional[np.ndarray] = None    # [K]: the node at which phrase k ends, duplicates included (``phrase_trie`` fills it;
-                                                # ``score_phrases`` needs it: ``term`` keeps the lowest index of a node only)
-
-    @property
-    def nodes(self) -> int:
-        return int(self.term.shape[0])
-
-    @property
-    def edges(self) -> int:
-        return int(self.child_tok.shape[0])
-
-    def children(self, node: int):
-        """-> (tokens, next nodes) of ``node``"""
-        lo, hi = int(self.child_off[node]), int(self.child_off[node + 1])
-        return self.child_tok[lo:hi], self.child_next[lo:hi]
-
-
-def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
-    """The refusals of ``generate_captions(phrases=...)`` that concern the set itself (host only, ValueError) and the set as a
-    ``PhraseTrie``.  ``phrases``: K >= 1 sequences (or 1-D tensors) of token ids in [0, ``vocab``), none empty, none holding ``eos``;
-    ``eos`` is needed (a row ends its phrase by emitting it) and ``max_new_tokens`` must reach the longest phrase + 1, so that every
-    row can end with EOS and the finish rule never cuts a phrase.  Duplicate phrases keep the lowest index."""
-    if eos is None:
-        raise ValueError('phrases need eos_token_id: a row ends its phrase by emitting it')
-    eos = int(eos)
-    if not 0 <= eos < vocab:
-        raise ValueError(f'eos_token_id = {eos} outside the vocabulary [0, {vocab})')
-    if isinstance(phrases, torch.Tensor):
-        phrases = phrases.detach().cpu().tolist()
-    rows = []
-    for k, ph in enumerate(phrases):
-        if isinstance(ph, torch.Tensor):
-            ph = ph.detach().cpu().reshape(-1).tolist()
-        row = []
-        for t in ph:
-            if int(t) != t:
-                raise ValueError(f'phrases[{k}] holds {t!r}: token ids are integers')
-            t = int(t)
-            if not 0 <= t < vocab:
-                raise ValueError(f'phrases[{k}] holds {t}: outside the vocabulary [0, {vocab})')
-            if t == eos:
-                raise ValueError(f'phrases[{k}] holds eos_token_id = {eos}: the EOS ends a phrase, it cannot be inside one')
-            row.append(t)
-        if not row:
-            raise ValueError(f'phrases[{k}] is empty: a phrase holds at least one token')
-        rows.append(row)
-    if not rows:
-        raise ValueError('phrases is empty: at least one phrase is needed')
-    longest = max(len(r) for r in rows)
-    if max_new_tokens < longest + 1:
-        raise ValueError(f'max_new_tokens = {max_new_tokens} is below the longest phrase + 1 = {longest + 1}: every row ends with EOS')
-    kids, term, ends = [{}], [-1], []                           # insertion: node -> {token: next node}
-    for k, row in enumerate(rows):
-        n = 0
-        for t in row:
-            if t not in kids[n]:
-                kids[n][t] = len(kids)
-                kids.append({})
-                term.append(-1)
-            n = kids[n][t]
-        if term[n] < 0:
-            term[n] = k
-        ends.append(n)
-    off, tok, nxt = [0], [], []
-    for d in kids:
-        for t in sorted(d):
-            tok.append(t)
-            nxt.append(d[t])
-        off.append(len(tok))
-    i32 = np.int32
-    return PhraseTrie(np.array(off, dtype=i32), np.array(tok, dtype=i32), np.array(nxt, dtype=i32), np.array(term, dtype=i32),
-                      max(len(d) for d in kids), longest, np.array(ends, dtype=i32))
-
-
-def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
-                              num_beams=1, causal: bool = True) -> PhraseTrie:
-    """``phrase_trie`` and then what ``phrases`` does not combine with, all before anything runs -> the trie.  NotImplementedError,
-    naming the reason: ``prompt_lengths``, an active logits processor, ``num_beams`` > 1, a non-causal decoder.  ``phrases`` may be a
-    ``PhraseTrie`` that an earlier call of this function built (the model hands its own to the decoder): it is not built again, only
-    held against this call's ``eos``, ``vocab`` and ``max_new_tokens``."""
-    if isinstance(phrases, PhraseTrie):
-        trie = phrases
-        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
-                or bool((trie.child_tok == int(eos)).any()) or max_new_tokens < trie.longest + 1:
-            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}, max_new_tokens = '
-                             f'{max_new_tokens} against a longest phrase of {trie.longest} tokens')
-    else:
-        trie = phrase_trie(phrases, eos, vocab, max_new_tokens)
-    if prompt_lengths is not None:
-        raise NotImplementedError('phrases with prompt_lengths: a forced prompt column would have to hold the trie still, and the ragged '
-                                  'finish rule has no such case')
-    if processors_active:
-        raise NotImplementedError('phrases with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
-                                  'emitted, and a processor could leave a node without an allowed token')
-    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
-        raise NotImplementedError('phrases under num_beams > 1: the beam step has no trie state per hypothesis')
-    if not causal:
-        raise NotImplementedError('phrases run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
-                                  '(generate_by_recompute), which has no constrained step')
-    return trie
-
-
-def trie_mask_host(z, node: int, trie: PhraseTrie, eos: int) -> np.ndarray:
-    """What i2t_caption_trie_mask leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): -inf everywhere except
-    the columns of ``node``'s children and, when a phrase ends at ``node``, the EOS column; those keep their raw values."""
-    z = np.array(z, dtype=np.float32)
-    assert z.ndim == 1
-    out = np.full_like(z, -np.inf)
-    toks, _ = trie.children(node)
-    out[toks] = z[toks]
-    if trie.term[node] >= 0:
-        out[eos] = z[eos]
-    return out
-
-
-def trie_advance_host(node: int, token: int, trie: PhraseTrie, eos: int):
-    """What i2t_caption_trie_advance does with a row at ``node`` whose chooser wrote ``token`` -> (node, phrase index or -1, whether
-    the token was one the node allows).  EOS at a node that ends a phrase names that phrase and the node stays; a child moves the row;
-    anything else (never from a chooser) changes nothing, and the kernel then leaves the step's log-prob as it was."""
-    token = int(token)
-    if token == eos:
-        p = int(trie.term[node])
-        return node, p, p >= 0
-    toks, nxt = trie.children(node)
-    at = int(np.searchsorted(toks, token))
-    if at < toks.shape[0] and int(toks[at]) == token:
-        return int(nxt[at]), -1, True
-    return node, -1, False
-
-
-def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad, max_new: int):
-    """The whole greedy search of ``generate_captions(phrases=...)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32
-    logits row [V] that follows a token sequence (a list of ints, the prompt included).  Every step takes ``trie_mask_host`` of the
-    row, its argmax (the lower id on ties), the fp32 log_softmax of the RAW row there, and ``trie_advance_host``; the search ends with
-    the EOS.  -> SimpleNamespace(ids int64 [L], length, token_logprobs f32 [L - P], logprob f32, phrase_index, steps, gaps): ``gaps``
-    holds per step the best allowed logit minus the second-best allowed one (inf where a node allows one token).  A search whose gaps
-    all exceed a perturbation of the logits keeps its result under it.  (``pad`` takes no part for one image -- nothing follows the EOS;
-    the signature is ``beam_search_host``'s.)"""
-    seq = [int(t) for t in np.asarray(prompt).reshape(-1)]
-    P = len(seq)
-    assert P >= 1 and max_new >= 1
-    f32 = np.float32
-    node, phrase, lps, gaps = 0, -1, [], []
-    while phrase < 0 and len(seq) - P < max_new:
-        z = np.asarray(step_logits(list(seq)), dtype=f32).reshape(-1)
-        masked = trie_mask_host(z, node, trie, eos)
-        order = sorted(np.flatnonzero(masked > -np.inf).tolist(), key=lambda t: (-masked[t], t))
-        assert order, 'no allowed token has a finite logit'
-        c = order[0]
-        gaps.append(float(masked[c]) - float(masked[order[1]]) if len(order) > 1 else float('inf'))
-        m = z.max()
-        lps.append(f32(z[c] - (m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))))
-        node, phrase, ok = trie_advance_host(node, c, trie, eos)
-        assert ok
-        seq.append(c)
-    lp = np.array(lps, dtype=f32)
-    return SimpleNamespace(ids=np.array(seq, dtype=np.int64), length=len(seq), token_logprobs=lp, logprob=lp.sum(dtype=f32),
-                           phrase_index=phrase, steps=len(lps), gaps=gaps)
-
-
-# ------------------------------------------------------------------------------------------------ exact phrase scores (DESIGN.md 4v)
-class PhraseScores(NamedTuple):
-    """What ``score_phrases`` returns."""
-    logprob: torch.Tensor               # fp32 [B, K]: the raw log-likelihood of phrase k + EOS after image b's prompt (``score``'s quantity)
-    best: torch.Tensor                  # int64 [B]: the argmax over k, the lowest index on ties (duplicate phrases tie exactly)
-    lengths: torch.Tensor               # int32 [K]: the tokens of each phrase + 1 (the EOS)
-
-
-class TrieLevel(NamedTuple):
-    """The nodes of one depth of a phrase trie (``trie_levels``); all arrays numpy int32."""
-    nodes: np.ndarray                   # [n_t]: the nodes at depth t, ascending (node order)
-    rows: np.ndarray                    # [n_t]: the row w each of them holds during the level's step -- its rank in ``nodes``
-    parent_rows: np.ndarray             # [n_t]: the row its parent held at depth t - 1 (-1 at the root)
-    tokens: np.ndarray                  # [n_t]: the token of the edge that leads to it (-1 at the root)
-    term: np.ndarray                    # [n_t]: trie.term of the node
-    anc: np.ndarray                     # [wmax, t + 1]: anc[w][j] = the row the depth-j ancestor of row w's node held (j = t: w itself);
-                                        # rows w >= n_t hold no node: w in every column
-
-
-class TrieLevels(NamedTuple):
-    levels: tuple                       # TrieLevel for t = 0 (the root alone) .. longest
-    wmax: int                           # the widest level: the rows per image of the walk
-
-    def history(self, t: int, first: int, clen: int) -> np.ndarray:
-        """int32 [wmax, clen]: the static history table of level t's step.  ``first`` is the cache slot the level-0 step writes (the
-        last prompt token's: soft-prompt rows + P - 1), so the level-j step writes slot first + j, in the row the depth-j node holds.
-        Key slot s of row w is read from cache row history[w][s]: slots up to ``first`` -- soft prompt and prompt, which every row ran
-        itself -- and slot first + t, which the row writes in this very step, from row w; slot first + j, 0 < j < t, from anc[w][j];
-        later slots are not read (w)."""
-        lv = self.levels[t]
-        assert first >= 0 and first + t < clen
-        h = np.repeat(np.arange(self.wmax, dtype=np.int32)[:, None], clen, axis=1)
-        h[:, first + 1:first + t] = lv.anc[:, 1:t]
-        return h
-
-
-def trie_levels(trie: PhraseTrie) -> TrieLevels:
-    """The CSR trie as per-depth tables, t = 0 .. trie.longest, built once on the host: ``score_phrases`` walks them level by level, a
-    "beam search" that prunes nothing and whose parents come from the trie instead of a top-k, so every table is static."""
-    n = trie.nodes
-    depth, parent, token = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
-    depth[0] = 0
-    order = [0]
-    for nd in order:                                            # breadth first from the root: a parent is placed before its children
-        toks, nxt = trie.children(nd)
-        for tk, c in zip(toks.tolist(), nxt.tolist()):
-            assert depth[c] < 0, 'not a tree'
-            depth[c], parent[c], token[c] = depth[nd] + 1, nd, tk
-            order.append(c)
-    assert len(order) == n and int(depth.max()) == trie.longest, 'the trie holds nodes its root does not reach, or a wrong longest'
-    per = [np.flatnonzero(depth == t).astype(np.int32) for t in range(trie.longest + 1)]
-    wmax = max(p.shape[0] for p in per)
-    row_of = np.zeros(n, dtype=np.int32)
-    for p in per:
-        row_of[p] = np.arange(p.shape[0], dtype=np.int32)
-    levels = []
-    for t, nodes in enumerate(per):
-        anc = np.repeat(np.arange(wmax, dtype=np.int32)[:, None], t + 1, axis=1)
-        at = nodes.copy()
-        for j in range(t, -1, -1):                              # up the tree: the depth-j ancestor of every node of the level
-            anc[:nodes.shape[0], j] = row_of[at]
-            at = parent[at] if j else at
-        levels.append(TrieLevel(nodes, np.arange(nodes.shape[0], dtype=np.int32),
-                                row_of[parent[nodes]] if t else np.full(1, -1, dtype=np.int32), token[nodes], trie.term[nodes], anc))
-    return TrieLevels(tuple(levels), int(wmax))
-
-
-def phrase_node_csr(trie: PhraseTrie):
-    """-> (off int32 [nodes + 1], idx int32 [K]): the phrases that end at node n are idx[off[n] .. off[n + 1]), ascending -- the
-    duplicates of a phrase share its node, which ``trie.term`` names by the lowest index only"""
-    if trie.phrase_node is None:
-        raise ValueError('a PhraseTrie without phrase_node (not built by phrase_trie): the phrases that share a node are unknown')
-    ends = np.asarray(trie.phrase_node, dtype=np.int64)
-    idx = np.argsort(ends, kind='stable').astype(np.int32)
-    off = np.zeros(trie.nodes + 1, dtype=np.int32)
-    np.cumsum(np.bincount(ends, minlength=trie.nodes), out=off[1:])
-    return off, idx
-
-
-def level_expand_tables(trie: PhraseTrie, levels: TrieLevels, t: int):
-    """The five tables i2t_trie_level_expand takes at level t (numpy int32) -> (child_parent, child_tok, term_row, term_off,
-    term_phrase): the nodes of level t + 1 in row order with their parents' rows at level t (empty at the last level), and the rows of
-    level t whose node ends a phrase with the CSR of the phrase indices that end there."""
-    i32 = np.int32
-    lv = levels.levels[t]
-    nxt = levels.levels[t + 1] if t + 1 < len(levels.levels) else None
-    child_parent = nxt.parent_rows if nxt is not None else np.zeros(0, dtype=i32)
-    child_tok = nxt.tokens if nxt is not None else np.zeros(0, dtype=i32)
-    off, idx = phrase_node_csr(trie)
-    rows = [w for w, nd in enumerate(lv.nodes.tolist()) if off[nd + 1] > off[nd]]
-    term_off, term_phrase = [0], []
-    for w in rows:
-        nd = int(lv.nodes[w])
-        term_phrase += idx[off[nd]:off[nd + 1]].tolist()
-        term_off.append(len(term_phrase))
-    return child_parent.astype(i32), child_tok.astype(i32), np.array(rows, dtype=i32), np.array(term_off, dtype=i32), np.array(term_phrase, dtype=i32)
-
-
-def phrase_scores_host(step_logits_fn, trie: PhraseTrie, eos: int, prompt=()):
-    """The normative replica of ``score_phrases`` for ONE image on the host: ``step_logits_fn(sequence)`` gives the raw fp32 logits row
-    [V] that follows a token sequence (a list of ints: ``prompt``, then the path from the root).  The levels are walked in order; every
-    node's row gives lse = m + log(sum exp(z - m)) in fp32, a child's path sum is path[parent] + (z[token] - lse) and a phrase that ends
-    at the node gets path[node] + (z[eos] - lse), in exactly this order in fp32 -- the device's (i2t_trie_level_expand).
-    -> SimpleNamespace(logprob f32 [K], best: the argmax, the lowest index on ties, lengths int32 [K])."""
-    f32 = np.float32
-    levels = trie_levels(trie)
-    off, idx = phrase_node_csr(trie)
-    K = idx.shape[0]
-    logprob = np.zeros(K, dtype=f32)
-    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
-    path, seq = {0: f32(0.0)}, {0: []}
-    for lv in levels.levels:
-        for nd in lv.nodes.tolist():
-            z = np.asarray(step_logits_fn(prompt + seq[nd]), dtype=f32).reshape(-1)
-            m = z.max()
-            lse = f32(m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))
-            toks, kids = trie.children(nd)
-            for tk, c in zip(toks.tolist(), kids.tolist()):
-                path[c], seq[c] = f32(path[nd] + f32(z[tk] - lse)), seq[nd] + [tk]
-            for k in idx[off[nd]:off[nd + 1]].tolist():
-                logprob[k] = f32(path[nd] + f32(z[eos] - lse))
-    depth_of = {int(nd): t for t, lv in enumerate(levels.levels) for nd in lv.nodes.tolist()}
-    lengths = np.array([depth_of[int(nd)] + 1 for nd in trie.phrase_node], dtype=np.int32)
-    return SimpleNamespace(logprob=logprob, best=int(np.flatnonzero(logprob == logprob.max())[0]), lengths=lengths)
-
-
-def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
-                            images_per_pass=None) -> PhraseTrie:
-    """The refusals of ``score_phrases``, all before anything runs -> the trie.  ValueError: everything ``phrase_trie`` refuses about the
-    set (or a ``PhraseTrie`` built for another EOS / vocabulary, or one without ``phrase_node``), prompt + longest phrase + 1 past
-    the decode ``window`` (the text of every other call), ``images_per_pass`` < 1.  NotImplementedError, naming the reason: a
-    non-causal decoder, sparse nano-mini blocks."""
-    if isinstance(phrases, PhraseTrie):
-        trie = phrases
-        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
-                or bool((trie.child_tok == int(eos)).any()):
-            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
-        phrase_node_csr(trie)
-    else:
-        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
-    if not causal:
-        raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
-                                  'state of the earlier ones --, so use rerank')
-    if sparse:
-        raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
-                                  'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
-    total = int(P) + trie.longest + 1
-    if total > window:
-        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
-    if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
-        raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
-    return trie
 
 
 class CaptionDecoder(GreedyDecoder):
@@ -1450,31 +825,28 @@ class CaptionDecoder(GreedyDecoder):
         over the allowed tokens only, without the n-gram ban -- and i2t_caption_trie_advance after it, under graph keys of their own;
         the result carries ``phrase_index``.  None: the call is the one without the argument.  ``each(i)`` runs after full step i (tests
         read the step's buffers there)."""
+        plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
+                             poll_every=poll_every, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
+                             repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
+                             phrases=phrases, sampling=sampling)
+        return self.run(images, prompt_ids, plan, use_graph, each)
+
+    @torch.no_grad()
+    def run(self, images, prompt_ids: torch.Tensor, plan: CaptionPlan, use_graph: bool = True, each=None) -> GeneratedCaptions:
+        """A 'cache' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here."""
+        if plan.mode != 'cache':
+            raise ValueError('CaptionDecoder needs a causal decoder')
         eng = self.eng
         dc = eng.dec
-        N = int(num_return_sequences)
-        B, P = prompt_ids.shape
-        ragged = prompt_lengths is not None
-        procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, vocab=dc.V)
-        if ragged:
-            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
-            pmin, pmax = int(plen.min()), int(plen.max())
-        else:
-            check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **procs)
-            pmin = pmax = P
-        proc = caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, dc.V)
-        trie = None
-        if phrases is not None:
-            trie = check_phrase_caption_args(phrases, eos, dc.V, max_new_tokens, prompt_lengths, proc is not None, 1, dc.causal)
-        if not dc.causal:
-            raise ValueError('CaptionDecoder needs a causal decoder')
-        m, start = prefill_plan(prompt_prefill, pmin, min(eng.enc.ncls, dc.block) if dc.prefixed else 0, dc.fam, True)
+        B = prompt_ids.shape[0]
+        N, sampling, eos, pad, poll_every, max_new_tokens = plan.N, plan.sampling, plan.eos, plan.pad, plan.poll_every, plan.max_new
+        plen, pmin, pmax, proc, trie, m, start = plan.plen, plan.pmin, plan.pmax, plan.proc, plan.trie, plan.m, plan.start
+        ragged = plen is not None
         n_prefill = pmin - 1 - m
         if not max_new_tokens:              # nothing to emit: no step reads the cache, so 'pass' fills nothing -- no pass, no replay
             m = 0
         a = eng.prepare(False)
         R, total = B * N, pmax + max_new_tokens
-        pad = (0 if eos is None else eos) if pad is None else pad
         st = self._state_for(R, total, lambda clen: self._build_captions(B, N, max(total, dc.block), clen), lambda st: st.N == N)
         prompt = prompt_ids[:, :pmax].to(a.device)
         plen_dev = forced = None
@@ -1538,303 +910,6 @@ class CaptionDecoder(GreedyDecoder):
                                  phrase_index=None if trie is None else st.phrase_index.view(B, N).clone())
 
 
-def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,
-                       min_new_tokens: int = 0, suppress_tokens=None, vocab: Optional[int] = None):
-    """the refusals of generate_captions that need no device; those of the logits processors are ``caption_processors``'"""
-    if N < 1:
-        raise ValueError(f'num_return_sequences = {N}: at least one caption per image')
-    if sampling is None and N > 1:
-        raise ValueError(f'greedy decoding with num_return_sequences = {N}: the {N} rows of an image would be identical; sample instead')
-    if sampling is not None and not sampling.temperature > 0:
-        raise ValueError('sampling needs a positive temperature')
-    if eos is not None and eos < 0:
-        raise ValueError(f'eos_token_id = {eos}')
-    if pad is not None and pad < 0:
-        raise ValueError(f'pad_token_id = {pad}')
-    if poll_every < 0 or max_new_tokens < 0:
-        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
-    caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab)
-
-
-def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: Optional[Sampling], eos, pad, poll_every: int,
-                              max_new_tokens: int, **processors) -> np.ndarray:
-    """check_caption_args, and the refusals of ``prompt_lengths`` (read on the host, before anything moves to the device): one integer
-    per image, 1 <= p_b <= P  -> the lengths, int32 [B]"""
-    check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **processors)
-    if isinstance(prompt_lengths, torch.Tensor):
-        if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
-            raise ValueError(f'prompt_lengths of dtype {prompt_lengths.dtype}: integers are needed')
-        plen = prompt_lengths.detach().cpu().numpy()
-    else:
-        plen = np.asarray(prompt_lengths)
-        if plen.size and not np.issubdtype(plen.dtype, np.integer):
-            raise ValueError(f'prompt_lengths of type {plen.dtype}: integers are needed')
-    if plen.shape != (B,):
-        raise ValueError(f'prompt_lengths of shape {tuple(plen.shape)} for prompt_ids of {B} rows: one length per image, shape ({B},)')
-    if B and int(plen.min()) < 1:
-        raise ValueError(f'prompt_lengths[{int(plen.argmin())}] = {int(plen.min())}: every row needs at least one prompt token')
-    if B and int(plen.max()) > P:
-        raise ValueError(f'prompt_lengths[{int(plen.argmax())}] = {int(plen.max())} exceeds the {P} columns of prompt_ids')
-    return plen.astype(np.int32)
-
-
-# ------------------------------------------------------------------------------------------------ caption beams (DESIGN.md 4t)
-MAX_CAPTION_BEAMS = 8               # i2t_beam_candidates takes E = 2 W <= 16
-BEAM_DEAD = -1.0e9                  # the running score of beams 1 .. W - 1 before the first step (transformers' constant)
-
-
-def check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature=1.0, top_k=None, nucleus_p=None,
-                            seed=None, prompt_lengths=None, prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0,
-                            suppress_tokens=None, max_new_tokens=1, eos=None, pad=None, poll_every=8, causal=True, vocab=None) -> int:
-    """The refusals of ``generate_captions(num_beams=W, ...)`` that need no device, all before anything runs -> W.  W = 1 is the call
-    without the beam arguments: only W itself, ``length_penalty`` and ``early_stopping`` are looked at.  ValueError: W outside
-    1 .. MAX_CAPTION_BEAMS (the candidates kernel takes E = 2 W <= 16), N outside 1 .. W, a non-finite ``length_penalty``,
-    ``early_stopping`` not False / True ("never" is out of scope), any sampling argument (beam sampling is out of scope), a negative
-    id or count.  NotImplementedError, naming the reason: ``prompt_lengths``, ``prompt_prefill='pass'``, an active
-    ``repetition_penalty`` / ``min_new_tokens`` / ``suppress_tokens``, a non-causal decoder."""
-    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
-        raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the candidates kernel takes 2 * num_beams '
-                         f'<= 16 candidates per row)')
-    W = int(num_beams)
-    try:
-        finite = bool(np.isfinite(float(length_penalty)))
-    except (TypeError, ValueError):
-        finite = False
-    if not finite:
-        raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
-    if not isinstance(early_stopping, (bool, np.bool_)):
-        raise ValueError(f'early_stopping = {early_stopping!r}: False or True ("never" is not supported)')
-    if W == 1:
-        return W
-    N = int(num_return_sequences)
-    if not 1 <= N <= W:
-        raise ValueError(f'num_return_sequences = {N} with num_beams = {W}: from 1 to num_beams captions per image')
-    if temperature != 1 or top_k is not None or nucleus_p is not None or seed is not None:
-        raise ValueError('num_beams > 1 is deterministic beam search: temperature, top_k, nucleus_p and seed must stay at their defaults '
-                         '(beam sampling is not supported)')
-    if (eos is not None and eos < 0) or (pad is not None and pad < 0):
-        raise ValueError(f'eos_token_id = {eos}, pad_token_id = {pad}: neither may be negative')
-    if poll_every < 0 or max_new_tokens < 0:
-        raise ValueError(f'poll_every = {poll_every}, max_new_tokens = {max_new_tokens}: neither may be negative')
-    if caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos, vocab) is not None:
-        raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens under num_beams > 1: the beam step has no '
-                                  'logits-processor pass')
-    if prompt_lengths is not None:
-        raise NotImplementedError('prompt_lengths under num_beams > 1: the beam step has no forcing table for ragged prompts')
-    if prompt_prefill not in PROMPT_PREFILL_MODES:
-        raise ValueError(f'prompt_prefill = {prompt_prefill!r}: one of {PROMPT_PREFILL_MODES}')
-    if prompt_prefill != 'steps':
-        raise NotImplementedError("prompt_prefill='pass' under num_beams > 1: the beam rows are prefilled step by step under the identity "
-                                  "history table")
-    if not causal:
-        raise NotImplementedError('num_beams > 1 needs a causal decoder: a non-causal one has no KV cache to run the beams on')
-    return W
-
-
-def beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
-                          counters, ctrl, W: int, P: int, max_new: int, eos, pad: int, length_penalty: float, early_stopping: bool,
-                          gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
-    """One i2t_beam_pool_select call on the host (numpy, in place on the arrays given; fp32 arithmetic in the kernel's order): the
-    normative statement of the selection step of ``generate_captions(num_beams=W)``, pinned to transformers 5.x
-    ``GenerationMixin._beam_search`` (do_sample=False, one EOS id).  ``cand_tok`` / ``cand_lp`` [R, 2 W]: every row's 2 W best tokens and
-    their log-probs; ``scores`` f32 [R]; ``ids`` int64 [R, ids_ld]; ``hist`` int32 [R, hist_ld]; ``tok_lp`` f32 [R, lp_ld]; the pool
-    ``pool_ids`` [B, W, ids_ld], ``pool_lp`` [B, W, lp_ld], ``pool_score`` / ``pool_sum`` f32 [B, W], ``pool_len`` int32 [B, W], ``pool_n``
-    / ``closed`` int32 [B]; ``counters`` = [pos, len], ``ctrl`` = [done, open] (``i2t_beam_advance`` moves both; ``beam_advance_host``).
-    Per image that is not closed (nothing happens once ctrl[0] is set):
-      * totals = scores[row] + cand_lp (fp32); the top 2 W of the W * 2 W, descending, the lower flat index w * 2 W + e first on ties;
-      * emitted = len + 1 - P counts the token being added; a candidate HITS if its token is ``eos`` or emitted == max_new;
-      * hits ranked below W are offered at total / fp32(emitted) ** fp32(length_penalty) (one fp32 power, one fp32 division); the pool
-        keeps the W best of (pool, offers), sorted descending, an entry it holds before a new one of equal score, an earlier offer
-        before a later one; a pool row is the parent's ids and log-probs, the token and its log-prob, then ``pad`` and 0.0;
-      * the first W candidates that do not hit, in rank order, become the image's rows: ids, history and log-prob rows move from
-        parent to child;
-      * the image closes at the bound (its rows then stay as they are); with ``early_stopping`` once the pool holds W; without it
-        once the pool holds W and not (best running total / fp32(emitted) ** fp32(length_penalty) > the pool's worst score) --
-        ``_check_early_stop_heuristic`` with early_stopping=False: the length is cur_len - prompt length AFTER the step's increment;
-      * an image left open sets ctrl[1] = 1.
-    ``gaps`` (a list, optional) receives the differences between neighbours among the top 2 W totals; ``pool_gaps`` those between an
-    offer and the pool entries beside it and between the close test's two sides."""
-    if ctrl[0]:
-        return
-    pos, ln = int(counters[0]), int(counters[1])
-    R = scores.shape[0]
-    B, E = R // W, 2 * W
-    if ln < P or ln >= P + max_new or pos < 0 or pos >= hist.shape[1]:
-        return
-    f32 = np.float32
-    emitted = ln + 1 - P
-    bound = emitted >= max_new
-    with np.errstate(all='ignore'):
-        denom = np.power(f32(emitted), f32(length_penalty)).astype(f32)
-    for b in range(B):
-        if closed[b]:
-            continue
-        r0 = b * W
-        tot = (scores[r0:r0 + W].astype(f32)[:, None] + cand_lp[r0:r0 + W].astype(f32)).astype(f32).reshape(-1)
-        order = sorted(range(W * E), key=lambda j: (-tot[j], j))[:E]
-        if gaps is not None:
-            gaps.extend(float(tot[order[k]]) - float(tot[order[k + 1]]) for k in range(E - 1) if np.isfinite(tot[order[k + 1]]))
-        m = int(pool_n[b])
-        entries = [(f32(pool_score[b, i]), i, None) for i in range(m)]          # (score, the slot it held or -1, the candidate)
-        children = []
-        for k, j in enumerate(order):
-            w, e = divmod(j, E)
-            tk, lpv = int(cand_tok[r0 + w, e]), f32(cand_lp[r0 + w, e])
-            if bound or (eos is not None and eos >= 0 and tk == eos):
-                if k >= W:
-                    continue
-                s = f32(tot[j] / denom)
-                at = 0
-                while at < len(entries) and entries[at][0] >= s:
-                    at += 1
-                if pool_gaps is not None:
-                    pool_gaps.extend(abs(float(entries[i][0]) - float(s)) for i in (at - 1, at) if 0 <= i < len(entries))
-                if at >= W:
-                    continue
-                entries.insert(at, (s, -1, (r0 + w, tk, f32(tot[j]), lpv)))
-                del entries[W:]
-            elif len(children) < W:
-                children.append((r0 + w, tk, f32(tot[j]), lpv))
-        while len(children) < W:
-            children.append((r0 + len(children), int(pad), f32(-np.inf), f32(0.0)))
-        if any(src < 0 for _, src, _ in entries):
-            old_ids, old_lp = pool_ids[b].copy(), pool_lp[b].copy()
-            old_sum, old_len = pool_sum[b].copy(), pool_len[b].copy()
-            total = P + max_new
-            for d, (s, src, c) in enumerate(entries):
-                pool_score[b, d] = s
-                if src >= 0:
-                    pool_ids[b, d, :total], pool_lp[b, d, :total] = old_ids[src, :total], old_lp[src, :total]
-                    pool_sum[b, d], pool_len[b, d] = old_sum[src], old_len[src]
-                else:
-                    par, tk, t, lpv = c
-                    pool_ids[b, d, :ln], pool_lp[b, d, :ln] = ids[par, :ln], tok_lp[par, :ln]
-                    pool_ids[b, d, ln], pool_lp[b, d, ln] = tk, lpv
-                    pool_ids[b, d, ln + 1:total], pool_lp[b, d, ln + 1:total] = pad, 0.0
-                    pool_sum[b, d], pool_len[b, d] = t, ln + 1
-        m = len(entries)
-        pool_n[b] = m
-        cl = bool(bound)
-        if not cl and m == W:
-            if early_stopping:
-                cl = True
-            else:
-                with np.errstate(all='ignore'):
-                    best = f32(children[0][2] / denom)
-                cl = not (best > entries[W - 1][0])
-                if pool_gaps is not None and np.isfinite(best):
-                    pool_gaps.append(abs(float(best) - float(entries[W - 1][0])))
-        closed[b] = 1 if cl else 0
-        if not cl:
-            ctrl[1] = 1
-        if bound:
-            continue
-        pars = [c[0] for c in children]
-        ids[r0:r0 + W, :ln] = ids[pars, :ln]
-        tok_lp[r0:r0 + W, :ln] = tok_lp[pars, :ln]
-        hist[r0:r0 + W, :pos] = hist[pars, :pos]
-        for w, (par, tk, t, lpv) in enumerate(children):
-            ids[r0 + w, ln], tok_lp[r0 + w, ln], hist[r0 + w, pos], scores[r0 + w] = tk, lpv, par, t
-
-
-def beam_advance_host(counters, ctrl):
-    """i2t_beam_advance on the host: while ctrl[0] is clear pos and len advance and ctrl[0] = (ctrl[1] == 0); then ctrl[1] = 0"""
-    if not ctrl[0]:
-        counters[0] += 1
-        counters[1] += 1
-        if ctrl[1] == 0:
-            ctrl[0] = 1
-    ctrl[1] = 0
-
-
-def banned_log_softmax_host(z, ids_row, ngram_sizes) -> np.ndarray:
-    """fp32 log_softmax of one logits row after the no-repeat-n-gram ban over ``ids_row`` (-inf at a token that would complete an
-    n-gram the row already holds): the quantity ``i2t_beam_candidates`` returns at temperature <= 0"""
-    z = np.array(z, dtype=np.float32).reshape(-1)
-    row = [int(t) for t in ids_row]
-    for n in ngram_sizes:
-        if n < 1 or len(row) < n:
-            continue
-        tail = tuple(row[len(row) - n + 1:]) if n > 1 else ()
-        for i in range(len(row) - n + 1):
-            if tuple(row[i:i + n - 1]) == tail and 0 <= row[i + n - 1] < z.shape[0]:
-                z[row[i + n - 1]] = -np.inf
-    m = z.max()
-    return (z - (m + np.log(np.exp(z - m, dtype=np.float32).sum(dtype=np.float32), dtype=np.float32))).astype(np.float32)
-
-
-def beam_search_host(step_logits, prompt, W: int, N: int, max_new: int, eos, pad, length_penalty: float, early_stopping: bool,
-                     ngram_sizes=()):
-    """The whole search of ``generate_captions(num_beams=W)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32 logits
-    row [V] that follows a token sequence (a list of ints, the prompt included); ``prompt`` is the image's prompt (P >= 1 ids).  Every
-    step takes each running row's ``banned_log_softmax_host``, its 2 W best tokens (descending, the lower id first on ties), one
-    ``beam_pool_select_host`` call and ``beam_advance_host``; running scores start at [0, BEAM_DEAD, ...].  -> SimpleNamespace(ids
-    int64 [N, L], lengths int32 [N], token_logprobs f32 [N, L - P], logprob f32 [N], beam_scores f32 [N], steps, gaps, pool_gaps): the
-    first N pool entries, L = lengths.max(), the pad id and 0.0 past each length; ``gaps``: per step the differences between
-    neighbours among the top 2 W totals and between the 2 W-th and the next one; ``pool_gaps``: those the pool merges and the close
-    tests hung on (``beam_pool_select_host``); ``decision_gaps``: per step the gap between the last total that runs on and the next one
-    that does not, and -- when a hit ranks among the top 2 W -- between ranks W - 1 and W.  A search whose ``decision_gaps`` and
-    ``pool_gaps`` all exceed a perturbation of the totals keeps its result under it."""
-    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
-    P, E = len(prompt), 2 * W
-    assert P >= 1 and 1 <= N <= W and max_new >= 1
-    pad = int((0 if eos is None else eos) if pad is None else pad)
-    total = P + max_new
-    f32, i32 = np.float32, np.int32
-    ids = np.zeros((W, total), dtype=np.int64)
-    ids[:, :P] = prompt
-    hist = np.repeat(np.arange(W, dtype=i32)[:, None], total, axis=1)
-    tok_lp = np.zeros((W, total), dtype=f32)
-    scores = np.full(W, BEAM_DEAD, dtype=f32)
-    scores[0] = 0.0
-    pool_ids, pool_lp = np.full((1, W, total), pad, dtype=np.int64), np.zeros((1, W, total), dtype=f32)
-    pool_score, pool_sum = np.full((1, W), BEAM_DEAD, dtype=f32), np.zeros((1, W), dtype=f32)
-    pool_len, pool_n, closed = np.zeros((1, W), dtype=i32), np.zeros(1, dtype=i32), np.zeros(1, dtype=i32)
-    counters, ctrl = np.array([P - 1, P], dtype=i32), np.zeros(2, dtype=i32)
-    gaps, pool_gaps, decision_gaps, steps = [], [], [], 0
-    while steps < max_new and not ctrl[0]:
-        ln = int(counters[1])
-        cand_tok, cand_lp = np.zeros((W, E), dtype=i32), np.zeros((W, E), dtype=f32)
-        spare, seen, tops, lps = [], {}, [], []
-        for w in range(W):
-            key = tuple(int(t) for t in ids[w, :ln])
-            if key not in seen:
-                seen[key] = banned_log_softmax_host(step_logits(list(key)), key, ngram_sizes)
-            lp = seen[key]
-            order = sorted(range(lp.shape[0]), key=lambda t: (-lp[t], t))[:E + 1]
-            assert len(order) >= E, 'the vocabulary holds fewer than 2 W tokens'
-            cand_tok[w], cand_lp[w] = order[:E], lp[order[:E]]
-            tops.append(order)
-            lps.append(lp)
-            spare.extend(f32(scores[w] + lp[t]) for t in order[E:])
-        if not closed[0]:
-            # what the step's outcome hangs on: the last candidate that runs on against the next one that does not, and -- with a hit
-            # in sight, or at the bound -- rank W - 1 against rank W, the line below which a hit is dropped
-            every = sorted(((float(f32(scores[w] + lps[w][t])), w * (E + 1) + e, t) for w in range(W) for e, t in enumerate(tops[w])),
-                           key=lambda c: (-c[0], c[1]))
-            at_bound = ln + 1 - P >= max_new
-            hit = [at_bound or (eos is not None and c[2] == eos) for c in every]
-            live = [c[0] for c, h in zip(every, hit) if not h]
-            if len(live) > W and np.isfinite(live[W]):
-                decision_gaps.append(live[W - 1] - live[W])
-            if any(hit[:E]) and len(every) > W and np.isfinite(every[W][0]):
-                decision_gaps.append(every[W - 1][0] - every[W][0])
-            tot = np.sort((scores[:, None] + cand_lp).astype(f32).reshape(-1))[::-1]
-            nxt = max([float(tot[E])] + [float(v) for v in spare]) if W > 1 else max([float(v) for v in spare], default=-np.inf)
-            if np.isfinite(nxt):
-                gaps.append(float(tot[E - 1]) - nxt)
-        beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
-                              counters, ctrl, W, P, max_new, eos, pad, length_penalty, early_stopping, gaps, pool_gaps)
-        beam_advance_host(counters, ctrl)
-        steps += 1
-    assert int(pool_n[0]) >= N
-    lengths = pool_len[0, :N].copy()
-    L = int(lengths.max())
-    lp = pool_lp[0, :N, P:L].copy()
-    return SimpleNamespace(ids=pool_ids[0, :N, :L].copy(), lengths=lengths, token_logprobs=lp, logprob=lp.sum(axis=-1, dtype=f32),
-                           beam_scores=pool_score[0, :N].copy(), steps=steps, gaps=gaps, pool_gaps=pool_gaps, decision_gaps=decision_gaps)
-
-
 class CaptionBeamDecoder(BeamDecoder):
     """``generate_captions(num_beams=W)`` on the static KV cache: BeamDecoder's R = B * W rows, history table and
     attention kernels, under GreedyDecoder._replay with ``poll_every``.  A step is _body -> _final_norm -> fp32 lm_head ->
@@ -1878,18 +953,22 @@ class CaptionBeamDecoder(BeamDecoder):
                           early_stopping: bool = False, poll_every: int = 8, use_graph: bool = True, each=None) -> GeneratedCaptions:
         """``beam_search_host`` for every image of the batch, on the device -> GeneratedCaptions with ``beam_scores``.  ``each(i)`` runs
         after full step i (tests read the step's buffers there)."""
+        plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
+                             poll_every=poll_every, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+        return self.run(images, prompt_ids, plan, use_graph, each)
+
+    @torch.no_grad()
+    def run(self, images, prompt_ids: torch.Tensor, plan: CaptionPlan, use_graph: bool = True, each=None) -> GeneratedCaptions:
+        """A 'beam' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here."""
+        assert plan.mode == 'beam', plan.mode
         eng = self.eng
         dc = eng.dec
-        N = int(num_return_sequences)
-        W = check_beam_caption_args(num_beams, N, length_penalty, early_stopping, max_new_tokens=max_new_tokens, eos=eos, pad=pad,
-                                    poll_every=poll_every, causal=dc.causal)
-        if W * 2 > dc.V:
-            raise ValueError(f'num_beams = {W} needs 2 * num_beams candidates per row: the vocabulary holds {dc.V} tokens')
+        N, W, eos, pad, poll_every, max_new_tokens = plan.N, plan.W, plan.eos, plan.pad, plan.poll_every, plan.max_new
+        length_penalty, early_stopping = plan.length_penalty, plan.early_stopping
         a = eng.prepare(False)
         prompt_ids = prompt_ids.to(a.device)
         B, P = prompt_ids.shape
         R, total = B * W, P + max_new_tokens
-        pad = int((0 if eos is None else eos) if pad is None else pad)
         if max_new_tokens == 0:             # nothing to emit: the prompts, N times, at score 0
             self.last_replays = 0
             zero = torch.zeros(B, N, 0, dtype=F32, device=a.device)
@@ -1899,7 +978,6 @@ class CaptionBeamDecoder(BeamDecoder):
                              lambda st: getattr(st, 'caption_beam', False) and st.W == W)
         self._prepare_inputs(st, images, B, W)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
-        length_penalty, early_stopping = float(length_penalty), bool(early_stopping)
 
         def reset():
             st.ids.zero_()
@@ -2079,6 +1157,14 @@ class TrieScoreDecoder(BeamDecoder):
             depth[lv.nodes] = t
         lengths = torch.from_numpy((depth[trie.phrase_node] + 1).astype(np.int32)).to(dev)
         return PhraseScores(out, best, lengths)
+
+
+def caption_facts(model) -> CaptionFacts:
+    """what ``plan_captions`` needs to know of ``model``"""
+    eng = model._engine
+    dc = eng.dec
+    return CaptionFacts(dc.V, dc.causal, dc.fam, model.decoder.block_size - model.space_for_prompt,
+                        min(eng.enc.ncls, dc.block) if dc.prefixed else 0)
 
 
 def _draw_seed(buf: torch.Tensor, seed: Optional[int]):

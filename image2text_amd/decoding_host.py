@@ -1,0 +1,423 @@
+"""The numpy statements the decode kernels and drivers are held to: what a kernel, or a whole search, computes, written out on the host
+(``*_host``, the finish rules).  Two serve production code as well: ``slot_positions`` (GreedyDecoder._build_family) and
+``apply_finish_rule_ragged`` (the non-causal path of ``generate_captions``).  No device, engine or library; ``decoding`` re-exports
+every name."""
+from types import SimpleNamespace
+from typing import Optional
+
+import numpy as np
+
+from .caption_plan import BEAM_DEAD, LONG_CHUNK_KEYS
+from .phrase_trie import PhraseTrie, phrase_node_csr, trie_levels
+
+
+def split_attention_host(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, chunk: int = LONG_CHUNK_KEYS) -> np.ndarray:
+    """What the split-key decode attention computes, on the host in fp64 (numpy): q [hd] against k / v [n][hd].  Every chunk of
+    ``chunk`` keys yields its maximum m_c, s_c = sum exp(score - m_c) and the unnormalised a_c = sum exp(score - m_c) v
+    (gq_decode_attention_split_kernel); the combine takes M = max m_c and returns sum_c a_c exp(m_c - M) / sum_c s_c exp(m_c - M), the
+    chunks in order."""
+    q, k, v = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    n = k.shape[0]
+    assert n >= 1 and chunk >= 1 and k.shape == v.shape and q.shape == k.shape[1:]
+    parts = []
+    for lo in range(0, n, chunk):
+        s = (k[lo:lo + chunk] @ q) * scale
+        m = s.max()
+        p = np.exp(s - m)
+        parts.append((m, p.sum(), p @ v[lo:lo + chunk]))
+    M = max(m for m, _, _ in parts)
+    num, den = np.zeros_like(q), 0.0
+    for m, s, a in parts:
+        f = np.exp(m - M)
+        num, den = num + a * f, den + s * f
+    return num / den
+
+
+def kv_prefill_host(src: np.ndarray, k_off: int, v_off: int, src_T: int, src_t0: int, m: int, kcache: np.ndarray, vcache: np.ndarray,
+                    cache_bs: int, cache_rs: int, cache_hs: int, hd: int, w: int, slot0: int, B: int, N: int):
+    """What i2t_kv_prefill does, on the host (numpy): ``src`` [rows, src_ld] holds K at columns k_off .. k_off + w - 1 and V at v_off ..;
+    token t < m of image b is source row b * src_T + src_t0 + t and goes to slot slot0 + t of cache rows b * N .. b * N + N - 1.
+    ``kcache`` / ``vcache`` are FLAT arrays, element (row, head, slot, column) at row * cache_bs + head * cache_hs + slot * cache_rs +
+    column (head-major [R][H][clen][64]: cache_rs = 64, cache_hs = clen * 64; row-major [R][clen][w]: cache_rs = w, cache_hs = hd).
+    Written in place; nothing else is touched."""
+    assert kcache.ndim == 1 and vcache.ndim == 1 and w % hd == 0 and src_t0 + m <= src_T
+    for b in range(B):
+        for t in range(m):
+            row = src[b * src_T + src_t0 + t]
+            for n in range(N):
+                for h in range(w // hd):
+                    at = (b * N + n) * cache_bs + h * cache_hs + (slot0 + t) * cache_rs
+                    kcache[at:at + hd] = row[k_off + h * hd:k_off + (h + 1) * hd]
+                    vcache[at:at + hd] = row[v_off + h * hd:v_off + (h + 1) * hd]
+
+
+def slot_positions(member: np.ndarray) -> np.ndarray:
+    """int32 [L][slots] from a sparse decoder's membership table (int [L][tmax], 1 where layer l keeps text position p): row l lists
+    the text positions layer l keeps, in order, zero-padded -- the position whose K/V sit at each cache slot (slot = rank of the
+    position among the kept ones); slots = the largest count, at least 1."""
+    member = np.asarray(member) != 0
+    kpos = np.zeros((member.shape[0], max(int(member.sum(axis=1).max(initial=0)), 1)), dtype=np.int32)
+    for l, row in enumerate(member):
+        kept = np.flatnonzero(row)
+        kpos[l, :kept.size] = kept
+    return kpos
+
+
+def apply_finish_rule(ids: np.ndarray, P: int, eos: Optional[int], pad: Optional[int] = None, token_logprobs: Optional[np.ndarray] = None):
+    """The finish rule of ``generate_captions`` on the host (numpy): what i2t_caption_finish does step by step on the device, applied to
+    whole rows.  ``ids`` [R, P + T]: the prompt and the T tokens a chooser emitted for every row (it goes on emitting after an EOS).  A row
+    is finished once it has EMITTED ``eos`` -- an EOS inside the prompt does not count --, that EOS is kept, later columns hold ``pad``
+    (default: the EOS id) and log-prob 0.0, a row without one has length P + T; ``eos`` None: no rule.  The steps end once every row has
+    finished, so L = lengths.max().  This is ``apply_finish_rule_ragged`` with every prompt P long, less its refusals (no rows, or an
+    empty prompt, pass).  -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - P] or None)"""
+    ids = np.array(ids)
+    return _finish_rows(ids, np.full(ids.shape[0], P, dtype=np.int64), P, ids.shape[1] - P, eos, pad, token_logprobs)
+
+
+def apply_finish_rule_ragged(ids: np.ndarray, plen, max_new: int, eos: Optional[int], pad: Optional[int] = None,
+                             token_logprobs: Optional[np.ndarray] = None):
+    """``apply_finish_rule`` for rows whose prompts differ in length: what i2t_caption_finish_ragged does step by step on the device.
+    ``ids`` [R, Pmax + max_new]: row r holds its prompt in columns < plen[r] and the tokens a chooser emitted from column plen[r] on
+    (columns at or past plen[r] + max_new are not read); ``token_logprobs`` [R, Pmax + max_new - Pmin] is aligned by COLUMN, entry t
+    belonging to column Pmin + t.  A row is finished once it has EMITTED ``eos`` (an EOS inside its prompt does not count; ``eos``
+    None: never) or ``max_new`` tokens; ``lengths[r]`` = plen[r] + the emitted tokens up to and including that EOS; later columns hold
+    ``pad`` (default: the EOS id, 0 without one) and log-prob 0.0, and so do a row's prompt columns (nothing was chosen there).
+    L = lengths.max().  With every plen[r] = P this is ``apply_finish_rule(ids, P, eos, pad, token_logprobs)``.
+    -> (ids [R, L], lengths int32 [R], token_logprobs [R, L - Pmin] or None)"""
+    ids = np.array(ids)
+    plen = np.asarray(plen, dtype=np.int64).reshape(-1)
+    R, total = ids.shape
+    assert plen.shape == (R,) and R >= 1 and max_new >= 0 and int(plen.min()) >= 1 and int(plen.max()) + max_new == total
+    return _finish_rows(ids, plen, int(plen.min()), max_new, eos, pad, token_logprobs)
+
+
+def _finish_rows(ids: np.ndarray, plen: np.ndarray, pmin: int, max_new: int, eos, pad, token_logprobs):
+    """the rule both ``apply_finish_rule`` forms state; ``ids`` is the caller's copy and is written"""
+    R, total = ids.shape
+    pad = (0 if eos is None else eos) if pad is None else pad
+    lengths = (plen + max_new).astype(np.int32)
+    for r in range(R if eos is not None else 0):
+        hit = np.flatnonzero(ids[r, plen[r]:plen[r] + max_new] == eos)
+        if hit.size:
+            lengths[r] = plen[r] + int(hit[0]) + 1
+    L = int(lengths.max()) if R else total
+    ids = ids[:, :L]
+    lp = None if token_logprobs is None else np.array(token_logprobs)[:, :L - pmin]
+    for r in range(R):
+        ids[r, lengths[r]:] = pad
+        if lp is not None:
+            lp[r, :plen[r] - pmin] = 0.0
+            lp[r, lengths[r] - pmin:] = 0.0
+    return ids, lengths, lp
+
+
+def process_logits_host(z, ids_row, length: int, emitted: int, theta: float, suppress, eos: Optional[int], min_new: int) -> np.ndarray:
+    """What i2t_caption_logits_process leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): it is to the
+    pre-pass what ``apply_finish_rule`` is to the finish kernel.  In the order of transformers' RepetitionPenaltyLogitsProcessor ->
+    SuppressTokensLogitsProcessor -> MinNewTokensLengthLogitsProcessor: every DISTINCT token t of ``ids_row[:length]`` (the prompt
+    included) gets z[t] * fp32(1 / theta) if z[t] > 0, else z[t] * fp32(theta) -- one fp32 multiply, as on the device; z[t] = -inf
+    for t in ``suppress``; z[eos] = -inf while ``emitted`` < ``min_new`` (``eos`` None: no rule).  Ids outside [0, V) take no part."""
+    z = np.array(z, dtype=np.float32)
+    assert z.ndim == 1
+    V = z.shape[0]
+    th = np.float32(theta)
+    inv = np.float32(1.0) / th
+    seen = np.unique(np.asarray(ids_row).reshape(-1)[:length].astype(np.int64))
+    seen = seen[(seen >= 0) & (seen < V)]
+    v = z[seen]
+    z[seen] = np.where(v > 0, v * inv, v * th).astype(np.float32)
+    sup = [int(t) for t in (suppress if suppress is not None else ()) if 0 <= int(t) < V]
+    z[sup] = -np.inf
+    if eos is not None and 0 <= eos < V and emitted < min_new:
+        z[eos] = -np.inf
+    return z
+
+
+def trie_mask_host(z, node: int, trie: PhraseTrie, eos: int) -> np.ndarray:
+    """What i2t_caption_trie_mask leaves of one raw fp32 logits row ``z`` [V], on the host (numpy fp32, a copy): -inf everywhere except
+    the columns of ``node``'s children and, when a phrase ends at ``node``, the EOS column; those keep their raw values."""
+    z = np.array(z, dtype=np.float32)
+    assert z.ndim == 1
+    out = np.full_like(z, -np.inf)
+    toks, _ = trie.children(node)
+    out[toks] = z[toks]
+    if trie.term[node] >= 0:
+        out[eos] = z[eos]
+    return out
+
+
+def trie_advance_host(node: int, token: int, trie: PhraseTrie, eos: int):
+    """What i2t_caption_trie_advance does with a row at ``node`` whose chooser wrote ``token`` -> (node, phrase index or -1, whether
+    the token was one the node allows).  EOS at a node that ends a phrase names that phrase and the node stays; a child moves the row;
+    anything else (never from a chooser) changes nothing, and the kernel then leaves the step's log-prob as it was."""
+    token = int(token)
+    if token == eos:
+        p = int(trie.term[node])
+        return node, p, p >= 0
+    toks, nxt = trie.children(node)
+    at = int(np.searchsorted(toks, token))
+    if at < toks.shape[0] and int(toks[at]) == token:
+        return int(nxt[at]), -1, True
+    return node, -1, False
+
+
+def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad, max_new: int):
+    """The whole greedy search of ``generate_captions(phrases=...)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32
+    logits row [V] that follows a token sequence (a list of ints, the prompt included).  Every step takes ``trie_mask_host`` of the
+    row, its argmax (the lower id on ties), the fp32 log_softmax of the RAW row there, and ``trie_advance_host``; the search ends with
+    the EOS.  -> SimpleNamespace(ids int64 [L], length, token_logprobs f32 [L - P], logprob f32, phrase_index, steps, gaps): ``gaps``
+    holds per step the best allowed logit minus the second-best allowed one (inf where a node allows one token).  A search whose gaps
+    all exceed a perturbation of the logits keeps its result under it.  (``pad`` takes no part for one image -- nothing follows the EOS;
+    the signature is ``beam_search_host``'s.)"""
+    seq = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    P = len(seq)
+    assert P >= 1 and max_new >= 1
+    f32 = np.float32
+    node, phrase, lps, gaps = 0, -1, [], []
+    while phrase < 0 and len(seq) - P < max_new:
+        z = np.asarray(step_logits(list(seq)), dtype=f32).reshape(-1)
+        masked = trie_mask_host(z, node, trie, eos)
+        order = sorted(np.flatnonzero(masked > -np.inf).tolist(), key=lambda t: (-masked[t], t))
+        assert order, 'no allowed token has a finite logit'
+        c = order[0]
+        gaps.append(float(masked[c]) - float(masked[order[1]]) if len(order) > 1 else float('inf'))
+        m = z.max()
+        lps.append(f32(z[c] - (m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))))
+        node, phrase, ok = trie_advance_host(node, c, trie, eos)
+        assert ok
+        seq.append(c)
+    lp = np.array(lps, dtype=f32)
+    return SimpleNamespace(ids=np.array(seq, dtype=np.int64), length=len(seq), token_logprobs=lp, logprob=lp.sum(dtype=f32),
+                           phrase_index=phrase, steps=len(lps), gaps=gaps)
+
+
+def phrase_scores_host(step_logits_fn, trie: PhraseTrie, eos: int, prompt=()):
+    """The normative replica of ``score_phrases`` for ONE image on the host: ``step_logits_fn(sequence)`` gives the raw fp32 logits row
+    [V] that follows a token sequence (a list of ints: ``prompt``, then the path from the root).  The levels are walked in order; every
+    node's row gives lse = m + log(sum exp(z - m)) in fp32, a child's path sum is path[parent] + (z[token] - lse) and a phrase that ends
+    at the node gets path[node] + (z[eos] - lse), in exactly this order in fp32 -- the device's (i2t_trie_level_expand).
+    -> SimpleNamespace(logprob f32 [K], best: the argmax, the lowest index on ties, lengths int32 [K])."""
+    f32 = np.float32
+    levels = trie_levels(trie)
+    off, idx = phrase_node_csr(trie)
+    K = idx.shape[0]
+    logprob = np.zeros(K, dtype=f32)
+    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    path, seq = {0: f32(0.0)}, {0: []}
+    for lv in levels.levels:
+        for nd in lv.nodes.tolist():
+            z = np.asarray(step_logits_fn(prompt + seq[nd]), dtype=f32).reshape(-1)
+            m = z.max()
+            lse = f32(m + np.log(np.exp(z - m, dtype=f32).sum(dtype=f32), dtype=f32))
+            toks, kids = trie.children(nd)
+            for tk, c in zip(toks.tolist(), kids.tolist()):
+                path[c], seq[c] = f32(path[nd] + f32(z[tk] - lse)), seq[nd] + [tk]
+            for k in idx[off[nd]:off[nd + 1]].tolist():
+                logprob[k] = f32(path[nd] + f32(z[eos] - lse))
+    depth_of = {int(nd): t for t, lv in enumerate(levels.levels) for nd in lv.nodes.tolist()}
+    lengths = np.array([depth_of[int(nd)] + 1 for nd in trie.phrase_node], dtype=np.int32)
+    return SimpleNamespace(logprob=logprob, best=int(np.flatnonzero(logprob == logprob.max())[0]), lengths=lengths)
+
+
+def beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
+                          counters, ctrl, W: int, P: int, max_new: int, eos, pad: int, length_penalty: float, early_stopping: bool,
+                          gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
+    """One i2t_beam_pool_select call on the host (numpy, in place on the arrays given; fp32 arithmetic in the kernel's order): the
+    normative statement of the selection step of ``generate_captions(num_beams=W)``, pinned to transformers 5.x
+    ``GenerationMixin._beam_search`` (do_sample=False, one EOS id).  ``cand_tok`` / ``cand_lp`` [R, 2 W]: every row's 2 W best tokens and
+    their log-probs; ``scores`` f32 [R]; ``ids`` int64 [R, ids_ld]; ``hist`` int32 [R, hist_ld]; ``tok_lp`` f32 [R, lp_ld]; the pool
+    ``pool_ids`` [B, W, ids_ld], ``pool_lp`` [B, W, lp_ld], ``pool_score`` / ``pool_sum`` f32 [B, W], ``pool_len`` int32 [B, W], ``pool_n``
+    / ``closed`` int32 [B]; ``counters`` = [pos, len], ``ctrl`` = [done, open] (``i2t_beam_advance`` moves both; ``beam_advance_host``).
+    Per image that is not closed (nothing happens once ctrl[0] is set):
+      * totals = scores[row] + cand_lp (fp32); the top 2 W of the W * 2 W, descending, the lower flat index w * 2 W + e first on ties;
+      * emitted = len + 1 - P counts the token being added; a candidate HITS if its token is ``eos`` or emitted == max_new;
+      * hits ranked below W are offered at total / fp32(emitted) ** fp32(length_penalty) (one fp32 power, one fp32 division); the pool
+        keeps the W best of (pool, offers), sorted descending, an entry it holds before a new one of equal score, an earlier offer
+        before a later one; a pool row is the parent's ids and log-probs, the token and its log-prob, then ``pad`` and 0.0;
+      * the first W candidates that do not hit, in rank order, become the image's rows: ids, history and log-prob rows move from
+        parent to child;
+      * the image closes at the bound (its rows then stay as they are); with ``early_stopping`` once the pool holds W; without it
+        once the pool holds W and not (best running total / fp32(emitted) ** fp32(length_penalty) > the pool's worst score) --
+        ``_check_early_stop_heuristic`` with early_stopping=False: the length is cur_len - prompt length AFTER the step's increment;
+      * an image left open sets ctrl[1] = 1.
+    ``gaps`` (a list, optional) receives the differences between neighbours among the top 2 W totals; ``pool_gaps`` those between an
+    offer and the pool entries beside it and between the close test's two sides."""
+    if ctrl[0]:
+        return
+    pos, ln = int(counters[0]), int(counters[1])
+    R = scores.shape[0]
+    B, E = R // W, 2 * W
+    if ln < P or ln >= P + max_new or pos < 0 or pos >= hist.shape[1]:
+        return
+    f32 = np.float32
+    emitted = ln + 1 - P
+    bound = emitted >= max_new
+    with np.errstate(all='ignore'):
+        denom = np.power(f32(emitted), f32(length_penalty)).astype(f32)
+    for b in range(B):
+        if closed[b]:
+            continue
+        r0 = b * W
+        tot = (scores[r0:r0 + W].astype(f32)[:, None] + cand_lp[r0:r0 + W].astype(f32)).astype(f32).reshape(-1)
+        order = sorted(range(W * E), key=lambda j: (-tot[j], j))[:E]
+        if gaps is not None:
+            gaps.extend(float(tot[order[k]]) - float(tot[order[k + 1]]) for k in range(E - 1) if np.isfinite(tot[order[k + 1]]))
+        m = int(pool_n[b])
+        entries = [(f32(pool_score[b, i]), i, None) for i in range(m)]          # (score, the slot it held or -1, the candidate)
+        children = []
+        for k, j in enumerate(order):
+            w, e = divmod(j, E)
+            tk, lpv = int(cand_tok[r0 + w, e]), f32(cand_lp[r0 + w, e])
+            if bound or (eos is not None and eos >= 0 and tk == eos):
+                if k >= W:
+                    continue
+                s = f32(tot[j] / denom)
+                at = 0
+                while at < len(entries) and entries[at][0] >= s:
+                    at += 1
+                if pool_gaps is not None:
+                    pool_gaps.extend(abs(float(entries[i][0]) - float(s)) for i in (at - 1, at) if 0 <= i < len(entries))
+                if at >= W:
+                    continue
+                entries.insert(at, (s, -1, (r0 + w, tk, f32(tot[j]), lpv)))
+                del entries[W:]
+            elif len(children) < W:
+                children.append((r0 + w, tk, f32(tot[j]), lpv))
+        while len(children) < W:
+            children.append((r0 + len(children), int(pad), f32(-np.inf), f32(0.0)))
+        if any(src < 0 for _, src, _ in entries):
+            old_ids, old_lp = pool_ids[b].copy(), pool_lp[b].copy()
+            old_sum, old_len = pool_sum[b].copy(), pool_len[b].copy()
+            total = P + max_new
+            for d, (s, src, c) in enumerate(entries):
+                pool_score[b, d] = s
+                if src >= 0:
+                    pool_ids[b, d, :total], pool_lp[b, d, :total] = old_ids[src, :total], old_lp[src, :total]
+                    pool_sum[b, d], pool_len[b, d] = old_sum[src], old_len[src]
+                else:
+                    par, tk, t, lpv = c
+                    pool_ids[b, d, :ln], pool_lp[b, d, :ln] = ids[par, :ln], tok_lp[par, :ln]
+                    pool_ids[b, d, ln], pool_lp[b, d, ln] = tk, lpv
+                    pool_ids[b, d, ln + 1:total], pool_lp[b, d, ln + 1:total] = pad, 0.0
+                    pool_sum[b, d], pool_len[b, d] = t, ln + 1
+        m = len(entries)
+        pool_n[b] = m
+        cl = bool(bound)
+        if not cl and m == W:
+            if early_stopping:
+                cl = True
+            else:
+                with np.errstate(all='ignore'):
+                    best = f32(children[0][2] / denom)
+                cl = not (best > entries[W - 1][0])
+                if pool_gaps is not None and np.isfinite(best):
+                    pool_gaps.append(abs(float(best) - float(entries[W - 1][0])))
+        closed[b] = 1 if cl else 0
+        if not cl:
+            ctrl[1] = 1
+        if bound:
+            continue
+        pars = [c[0] for c in children]
+        ids[r0:r0 + W, :ln] = ids[pars, :ln]
+        tok_lp[r0:r0 + W, :ln] = tok_lp[pars, :ln]
+        hist[r0:r0 + W, :pos] = hist[pars, :pos]
+        for w, (par, tk, t, lpv) in enumerate(children):
+            ids[r0 + w, ln], tok_lp[r0 + w, ln], hist[r0 + w, pos], scores[r0 + w] = tk, lpv, par, t
+
+
+def beam_advance_host(counters, ctrl):
+    """i2t_beam_advance on the host: while ctrl[0] is clear pos and len advance and ctrl[0] = (ctrl[1] == 0); then ctrl[1] = 0"""
+    if not ctrl[0]:
+        counters[0] += 1
+        counters[1] += 1
+        if ctrl[1] == 0:
+            ctrl[0] = 1
+    ctrl[1] = 0
+
+
+def banned_log_softmax_host(z, ids_row, ngram_sizes) -> np.ndarray:
+    """fp32 log_softmax of one logits row after the no-repeat-n-gram ban over ``ids_row`` (-inf at a token that would complete an
+    n-gram the row already holds): the quantity ``i2t_beam_candidates`` returns at temperature <= 0"""
+    z = np.array(z, dtype=np.float32).reshape(-1)
+    row = [int(t) for t in ids_row]
+    for n in ngram_sizes:
+        if n < 1 or len(row) < n:
+            continue
+        tail = tuple(row[len(row) - n + 1:]) if n > 1 else ()
+        for i in range(len(row) - n + 1):
+            if tuple(row[i:i + n - 1]) == tail and 0 <= row[i + n - 1] < z.shape[0]:
+                z[row[i + n - 1]] = -np.inf
+    m = z.max()
+    return (z - (m + np.log(np.exp(z - m, dtype=np.float32).sum(dtype=np.float32), dtype=np.float32))).astype(np.float32)
+
+
+def beam_search_host(step_logits, prompt, W: int, N: int, max_new: int, eos, pad, length_penalty: float, early_stopping: bool,
+                     ngram_sizes=()):
+    """The whole search of ``generate_captions(num_beams=W)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32 logits
+    row [V] that follows a token sequence (a list of ints, the prompt included); ``prompt`` is the image's prompt (P >= 1 ids).  Every
+    step takes each running row's ``banned_log_softmax_host``, its 2 W best tokens (descending, the lower id first on ties), one
+    ``beam_pool_select_host`` call and ``beam_advance_host``; running scores start at [0, BEAM_DEAD, ...].  -> SimpleNamespace(ids
+    int64 [N, L], lengths int32 [N], token_logprobs f32 [N, L - P], logprob f32 [N], beam_scores f32 [N], steps, gaps, pool_gaps): the
+    first N pool entries, L = lengths.max(), the pad id and 0.0 past each length; ``gaps``: per step the differences between
+    neighbours among the top 2 W totals and between the 2 W-th and the next one; ``pool_gaps``: those the pool merges and the close
+    tests hung on (``beam_pool_select_host``); ``decision_gaps``: per step the gap between the last total that runs on and the next one
+    that does not, and -- when a hit ranks among the top 2 W -- between ranks W - 1 and W.  A search whose ``decision_gaps`` and
+    ``pool_gaps`` all exceed a perturbation of the totals keeps its result under it."""
+    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    P, E = len(prompt), 2 * W
+    assert P >= 1 and 1 <= N <= W and max_new >= 1
+    pad = int((0 if eos is None else eos) if pad is None else pad)
+    total = P + max_new
+    f32, i32 = np.float32, np.int32
+    ids = np.zeros((W, total), dtype=np.int64)
+    ids[:, :P] = prompt
+    hist = np.repeat(np.arange(W, dtype=i32)[:, None], total, axis=1)
+    tok_lp = np.zeros((W, total), dtype=f32)
+    scores = np.full(W, BEAM_DEAD, dtype=f32)
+    scores[0] = 0.0
+    pool_ids, pool_lp = np.full((1, W, total), pad, dtype=np.int64), np.zeros((1, W, total), dtype=f32)
+    pool_score, pool_sum = np.full((1, W), BEAM_DEAD, dtype=f32), np.zeros((1, W), dtype=f32)
+    pool_len, pool_n, closed = np.zeros((1, W), dtype=i32), np.zeros(1, dtype=i32), np.zeros(1, dtype=i32)
+    counters, ctrl = np.array([P - 1, P], dtype=i32), np.zeros(2, dtype=i32)
+    gaps, pool_gaps, decision_gaps, steps = [], [], [], 0
+    while steps < max_new and not ctrl[0]:
+        ln = int(counters[1])
+        cand_tok, cand_lp = np.zeros((W, E), dtype=i32), np.zeros((W, E), dtype=f32)
+        spare, seen, tops, lps = [], {}, [], []
+        for w in range(W):
+            key = tuple(int(t) for t in ids[w, :ln])
+            if key not in seen:
+                seen[key] = banned_log_softmax_host(step_logits(list(key)), key, ngram_sizes)
+            lp = seen[key]
+            order = sorted(range(lp.shape[0]), key=lambda t: (-lp[t], t))[:E + 1]
+            assert len(order) >= E, 'the vocabulary holds fewer than 2 W tokens'
+            cand_tok[w], cand_lp[w] = order[:E], lp[order[:E]]
+            tops.append(order)
+            lps.append(lp)
+            spare.extend(f32(scores[w] + lp[t]) for t in order[E:])
+        if not closed[0]:
+            # what the step's outcome hangs on: the last candidate that runs on against the next one that does not, and -- with a hit
+            # in sight, or at the bound -- rank W - 1 against rank W, the line below which a hit is dropped
+            every = sorted(((float(f32(scores[w] + lps[w][t])), w * (E + 1) + e, t) for w in range(W) for e, t in enumerate(tops[w])),
+                           key=lambda c: (-c[0], c[1]))
+            at_bound = ln + 1 - P >= max_new
+            hit = [at_bound or (eos is not None and c[2] == eos) for c in every]
+            live = [c[0] for c, h in zip(every, hit) if not h]
+            if len(live) > W and np.isfinite(live[W]):
+                decision_gaps.append(live[W - 1] - live[W])
+            if any(hit[:E]) and len(every) > W and np.isfinite(every[W][0]):
+                decision_gaps.append(every[W - 1][0] - every[W][0])
+            tot = np.sort((scores[:, None] + cand_lp).astype(f32).reshape(-1))[::-1]
+            nxt = max([float(tot[E])] + [float(v) for v in spare]) if W > 1 else max([float(v) for v in spare], default=-np.inf)
+            if np.isfinite(nxt):
+                gaps.append(float(tot[E - 1]) - nxt)
+        beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,
+                              counters, ctrl, W, P, max_new, eos, pad, length_penalty, early_stopping, gaps, pool_gaps)
+        beam_advance_host(counters, ctrl)
+        steps += 1
+    assert int(pool_n[0]) >= N
+    lengths = pool_len[0, :N].copy()
+    L = int(lengths.max())
+    lp = pool_lp[0, :N, P:L].copy()
+    return SimpleNamespace(ids=pool_ids[0, :N, :L].copy(), lengths=lengths, token_logprobs=lp, logprob=lp.sum(axis=-1, dtype=f32),
+                           beam_scores=pool_score[0, :N].copy(), steps=steps, gaps=gaps, pool_gaps=pool_gaps, decision_gaps=decision_gaps)

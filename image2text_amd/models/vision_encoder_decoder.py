@@ -304,7 +304,7 @@ class VisionEncoderDecoder(nn.Module):
         ``token_logprobs[b, n, t]`` is the quantity the search summed at that step: log_softmax of the row's logits AFTER the model's
         no-repeat-n-gram ban, at the chosen token; ``logprob`` is its row sum, the unpenalised beam score.  With an empty
         ``no_repeat_n_grams`` this is ``score``'s quantity; with a ban it is larger by the banned tokens' mass.  Refusals, all before
-        anything runs (``decoding.check_beam_caption_args``): ValueError for W < 1 or W > 8, N > W, a non-finite ``length_penalty``,
+        anything runs (``caption_plan.check_beam_caption_args``): ValueError for W < 1 or W > 8, N > W, a non-finite ``length_penalty``,
         ``early_stopping`` not False / True, any sampling argument (``temperature`` != 1, ``top_k``, ``nucleus_p``, ``seed``) with W > 1;
         NotImplementedError for ``prompt_lengths``, ``prompt_prefill='pass'``, an active logits processor or a non-causal decoder with
         W > 1.  At ``num_beams=1`` the call is the one without these arguments, launch for launch.
@@ -318,57 +318,28 @@ class VisionEncoderDecoder(nn.Module):
         into ``phrases`` of the row's phrase, the lowest among duplicates; None in every other mode).  ``token_logprobs`` keeps its
         definition -- log_softmax of the RAW logits -- so ``logprob`` is the model's log-likelihood of phrase + EOS, comparable with
         ``score`` and ``rerank``.  The step takes the fp32-logits head whatever the decoder's width, as with the logits processors.
-        Refusals, before anything runs (``decoding.check_phrase_caption_args``): ValueError for an empty set or phrase, an id outside
+        Refusals, before anything runs (``caption_plan.check_phrase_caption_args``): ValueError for an empty set or phrase, an id outside
         the vocabulary, the EOS inside a phrase, no ``eos_token_id``, ``max_new_tokens`` below the longest phrase + 1;
         NotImplementedError with ``prompt_lengths``, an active logits processor, ``num_beams`` > 1 or a non-causal decoder.
         ``prompt_prefill='pass'`` works as without phrases.  None (the default) is the call without the argument, launch for launch."""
         import numpy as np
-        from ..decoding import CaptionBeamDecoder, caption_processors, check_beam_caption_args, check_phrase_caption_args
-        if phrases is not None:     # before the beam checks: those keep their own texts.  The decoder below takes the trie built here
-            active = caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos_token_id,
-                                        self._engine.dec.V) is not None
-            phrases = check_phrase_caption_args(phrases, eos_token_id, self._engine.dec.V, max_new_tokens, prompt_lengths, active, num_beams,
-                                                self._engine.dec.causal)
-        if check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature, top_k, nucleus_p, seed,
-                                   prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens,
-                                   eos_token_id, pad_token_id, poll_every, self._engine.dec.causal, self._engine.dec.V) > 1:
-            blk_size = self.decoder.block_size - self.space_for_prompt
-            if prompt_ids.shape[1] + max_new_tokens > blk_size:
-                raise ValueError(f'prompt + new tokens ({prompt_ids.shape[1] + max_new_tokens}) exceed the text window ({blk_size})')
-            if self._beam_captioner is None:
-                object.__setattr__(self, '_beam_captioner', CaptionBeamDecoder(self))
-            return self._beam_captioner.generate_captions(images, prompt_ids.to(next(self.parameters()).device), max_new_tokens, int(num_beams),
-                                                          eos_token_id, pad_token_id, int(num_return_sequences), length_penalty,
-                                                          early_stopping, poll_every)
-        from ..decoding import (CaptionDecoder, GeneratedCaptions, Sampling, apply_finish_rule_ragged, caption_processors, check_caption_args,
-                                check_ragged_caption_args, generate_by_recompute, prefill_plan)
-        N = int(num_return_sequences)
-        sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
+        from ..decoding import CaptionBeamDecoder, CaptionDecoder, GeneratedCaptions, caption_facts, generate_by_recompute, plan_captions
+        from ..decoding_host import apply_finish_rule_ragged
         B, P = prompt_ids.shape
-        procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                     vocab=self._engine.dec.V)
-        if prompt_lengths is None:
-            check_caption_args(N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens, **procs)
-            plen, pmin, pmax = None, P, P
-        else:
-            plen = check_ragged_caption_args(prompt_lengths, B, P, N, sampling, eos_token_id, pad_token_id, poll_every, max_new_tokens, **procs)
-            pmin, pmax = int(plen.min()), int(plen.max())
-        if not self._engine.dec.causal and caption_processors(repetition_penalty, min_new_tokens, suppress_tokens, max_new_tokens, eos_token_id,
-                                                              self._engine.dec.V) is not None:
-            raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens run inside the KV-cache caption step; a non-causal '
-                                      'decoder generates by re-evaluation (generate_by_recompute), which has no processed step')
-        prefill_plan(prompt_prefill, pmin, 0, self._engine.dec.fam, self._engine.dec.causal)       # its refusals, before anything runs
-        blk_size = self.decoder.block_size - self.space_for_prompt
-        if pmax + max_new_tokens > blk_size:
-            raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({blk_size})')
+        plan = plan_captions(caption_facts(self), B, P, max_new_tokens, eos_token_id, pad_token_id, num_return_sequences, temperature, top_k,
+                             nucleus_p, seed, poll_every, prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens,
+                             num_beams, length_penalty, early_stopping, phrases)
         dev = next(self.parameters()).device
         prompt_ids = prompt_ids.to(dev)
-        if self._engine.dec.causal:
+        if plan.mode == 'beam':
+            if self._beam_captioner is None:
+                object.__setattr__(self, '_beam_captioner', CaptionBeamDecoder(self))
+            return self._beam_captioner.run(images, prompt_ids, plan)
+        if plan.mode == 'cache':
             if self._captioner is None:
                 object.__setattr__(self, '_captioner', CaptionDecoder(self))
-            return self._captioner.generate_captions(images, prompt_ids, max_new_tokens, eos_token_id, pad_token_id, N, sampling, poll_every,
-                                                     prompt_lengths=plen, prompt_prefill=prompt_prefill, repetition_penalty=repetition_penalty,
-                                                     min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, phrases=phrases)
+            return self._captioner.run(images, prompt_ids, plan)
+        N, sampling, plen, pmin, pmax = plan.N, plan.sampling, plan.plen, plan.pmin, plan.pmax
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
         prompt_rep = prompt_ids.repeat_interleave(N, dim=0)
@@ -378,7 +349,7 @@ class VisionEncoderDecoder(nn.Module):
             of_p = torch.from_numpy(np.flatnonzero(rows == p)).to(dev)
             raw = generate_by_recompute(self, images_rep[of_p], prompt_rep[of_p, :p], max_new_tokens, sampling)
             table[rows == p, :p + max_new_tokens] = raw.cpu().numpy()
-        ids, lengths, _ = apply_finish_rule_ragged(table, rows, max_new_tokens, eos_token_id, pad_token_id)
+        ids, lengths, _ = apply_finish_rule_ragged(table, rows, max_new_tokens, plan.eos, plan.pad)
         ids, lengths = torch.from_numpy(ids).to(dev), torch.from_numpy(lengths).to(dev)
         L = ids.shape[1]
         col = torch.arange(L, device=dev)[None, :]
@@ -402,7 +373,7 @@ class VisionEncoderDecoder(nn.Module):
         walked level by level on the KV cache, every node of a level a row, in prompt + longest phrase + 1 decode steps over
         (widest level) rows per image, where ``rerank`` costs a decoder forward per (image, phrase).  Images go through in groups of
         ``images_per_pass`` (default: what fits ``decoding.TRIE_SCORE_BYTES`` of per-pass state); the grouping does not change a bit of
-        the result.  Refusals, before anything runs (``decoding.check_phrase_score_args``): ValueError for everything
+        the result.  Refusals, before anything runs (``caption_plan.check_phrase_score_args``): ValueError for everything
         ``generate_captions`` refuses about the set itself, prompt + longest phrase + 1 past the text window, ``images_per_pass`` < 1;
         NotImplementedError for a non-causal decoder and for sparse nano-mini blocks.  ``generate_captions``, ``score`` and ``rerank``
         are untouched by this call: it keeps a decoder state of its own."""

@@ -226,3 +226,31 @@ def test_refusals(tiny_weights):
     ms = _ved(mini_config(use_soft_prompting=False), sharpen=True)                          # sparse blocks without >= 2 kept prompt positions
     with pytest.raises(NotImplementedError, match='kept positions'):
         ms.generate_captions(images, prompt, max_new_tokens=4, **GREEDY)
+
+
+@pytest.mark.parametrize('mode', ['plain', 'ragged', 'beams'])
+def test_model_call_and_decoder_shim_run_one_plan(tiny_weights, mode):
+    """``m.generate_captions`` and the decoder's keyword ``generate_captions`` resolve equal arguments into equal plans: the second call
+    returns the first one's result bit for bit, on the same state, and captures nothing"""
+    m = _ved(tiny_config(), tiny_weights)
+    images, labels = synthetic_batch(2, 32, 12, 384, seed=11)
+    images, prompt = images.to(dev()), labels[:, :3].clamp(min=0).to(dev())
+    T, eos = 4, 5
+    if mode == 'beams':
+        out = m.generate_captions(images, prompt, max_new_tokens=T, eos_token_id=eos, num_beams=2)
+        dec = m._beam_captioner
+        call = lambda: dec.generate_captions(images, prompt, T, 2, eos)
+    else:
+        plen = [2, 3] if mode == 'ragged' else None
+        out = m.generate_captions(images, prompt, max_new_tokens=T, eos_token_id=eos, prompt_lengths=plen, **GREEDY)
+        dec = m._captioner
+        call = lambda: dec.generate_captions(images, prompt, T, eos, None, 1, None, prompt_lengths=plen)
+    st, keys = dec._state, set(dec._state.graphs)
+    again = call()
+    assert dec._state is st and set(st.graphs) == keys
+    for name in ('ids', 'lengths', 'token_logprobs'):
+        assert torch.equal(getattr(again, name), getattr(out, name)), name
+    if mode == 'beams':
+        assert torch.equal(again.beam_scores, out.beam_scores)
+    else:
+        assert again.beam_scores is None and out.beam_scores is None
