@@ -1,7 +1,10 @@
-"""Tensor-level wrappers over the C ABI: pointer/stride marshalling only, one function per entry point.
+"""Tensor-level wrappers over the C ABI: stride marshalling and shape checks only, one function per entry point.
 
 PyTorch supplies device memory and the current HIP stream; every op below launches hand-written gfx950 kernels
-through ``libi2t_hip.so`` and raises ``I2TError`` on any failure (no fallback).
+through ``libi2t_hip.so`` and raises ``I2TError`` on any failure (no fallback).  A kernel entry point is reached through ``_k`` alone:
+``_k.i2t_x(...)`` adds the stream, refuses a pointer operand that is not a device tensor of the dtype ``lib.SIGNATURES`` gives that
+position, passes its address, and checks the return code.  A wrapper keeps what the table cannot know: shapes, strides, contiguity,
+and the dtype of a ``void*`` operand.
 """
 import os
 import weakref
@@ -13,24 +16,57 @@ from . import lib as _l
 
 BF16 = torch.bfloat16
 F32 = torch.float32
+NO_CPU_PATH = 'image2text_amd ops need tensors on the MI355X (cuda) device; there is no CPU path'
 
 
 def _lib():
     return _l.load()
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+def operand_error(kind, is_cuda, dtype):
+    """Why a tensor on that device, of that dtype, may not stand behind a pointer of this kind (lib.POINTER_DTYPE); None: it may."""
+    if not is_cuda:
+        return NO_CPU_PATH
+    want = _l.POINTER_DTYPE[kind]
+    if want is not None and dtype != want:
+        return f'wants {want}, got {dtype}'
+    return None
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+class _Kernels:
+    """The checked callers of the entry points whose first argument is the stream, one per entry point, built from its row of
+    lib.SIGNATURES on first use (``load`` gives the library then)."""
+
+    def __init__(self, load):
+        self._load = load
+
+    def __getattr__(self, name):            # the first use only: the caller then stands in the instance's __dict__
+        if name not in _l.SIGNATURES:
+            raise AttributeError(name)
+        fn, check, current_stream = getattr(self._load(), name), _l.check, torch.cuda.current_stream
+        ptrs = tuple((i, kind, _l.POINTER_DTYPE[kind]) for i, kind in enumerate(_l.SIGNATURES[name][1:]) if issubclass(kind, _l.P))
+
+        def call(*args):
+            args = list(args)
+            try:
+                for i, kind, want in ptrs:
+                    t = args[i]
+                    if t is not None:
+                        if not t.is_cuda or (want is not None and t.dtype is not want):          # operand_error(...) is not None, inlined
+                            why = operand_error(kind, t.is_cuda, t.dtype)
+                            raise _l.I2TError(why if why is NO_CPU_PATH else f'{name}: argument {i} ({kind.__doc__}) {why}')
+                        args[i] = t.data_ptr()
+            except AttributeError:
+                raise _l.I2TError(f'{name}: argument {i} wants a tensor or None, got {type(t).__name__}') from None
+            rc = fn(current_stream().cuda_stream, *args)
+            if rc:
+                check(rc, name)
+
+        setattr(self, name, call)
+        return call
 
 
-def _need_cuda(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise _l.I2TError('image2text_amd ops need tensors on the MI355X (cuda) device; there is no CPU path')
+_k = _Kernels(_l.load)
 
 
 def _drop(drop):
@@ -58,9 +94,8 @@ def precise() -> bool:
 
 def split_f32(src: torch.Tensor, hi: torch.Tensor, lo: Optional[torch.Tensor], n: Optional[int] = None, act: int = 0):
     """hi = bf16(f(src)), lo = bf16(f(src) - hi) over the first n elements (include/i2t.h::i2t_split_f32_bf16)"""
-    _need_cuda(src, hi, lo)
-    assert src.dtype == F32 and hi.dtype == BF16 and (lo is None or lo.dtype == BF16)
-    _l.check(_lib().i2t_split_f32_bf16(_stream(), _p(src), _p(hi), _p(lo), src.numel() if n is None else n, int(act)), 'i2t_split_f32_bf16')
+    assert hi.dtype == BF16 and (lo is None or lo.dtype == BF16)
+    _k.i2t_split_f32_bf16(src, hi, lo, src.numel() if n is None else n, int(act))
     PRECISE_CALLS['splits'] += 1
     return hi
 
@@ -137,7 +172,6 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: int, K:
 
 def _gemm(a, b, out, M, N, K, *, a_kmajor=False, b_kmajor=False, lda=None, ldb=None, ldc=None, alpha=1.0, bias=None, act=0, aux_in=None,
           aux_out=None, residual=None, ldr=None, accumulate=False, drop=None, workspace=None, alpha_sumsq=None):
-    _need_cuda(a, b, out)
     assert a.dtype == BF16 and b.dtype == BF16 and out.dtype in (BF16, F32)
     lda = a.stride(0) if lda is None else lda
     ldb = b.stride(0) if ldb is None else ldb
@@ -145,20 +179,17 @@ def _gemm(a, b, out, M, N, K, *, a_kmajor=False, b_kmajor=False, lda=None, ldb=N
     if workspace is not None and not (a_kmajor or b_kmajor or accumulate or drop is not None or aux_in is not None
                                       or aux_out is not None or alpha != 1.0 or act not in (0, 1)):
         ldr_ = (residual.stride(0) if residual is not None else 0) if ldr is None else ldr
-        _l.check(_lib().i2t_gemm_bf16_ws(_stream(), _p(a), lda, _p(b), ldb, _p(out), ldc, int(out.dtype == F32), M, N, K, _p(bias), int(act),
-                                         _p(residual), ldr_, _p(workspace), workspace.numel()), 'i2t_gemm_bf16_ws')
+        _k.i2t_gemm_bf16_ws(a, lda, b, ldb, out, ldc, int(out.dtype == F32), M, N, K, bias, int(act), residual, ldr_, workspace, workspace.numel())
         return out
     ld_ai = aux_in.stride(0) if aux_in is not None else 0
     ld_ao = aux_out.stride(0) if aux_out is not None else 0
     ldr = (residual.stride(0) if residual is not None else 0) if ldr is None else ldr
     if alpha_sumsq is not None:
-        _l.check(_lib().i2t_gemm_bf16_ex(_stream(), _p(a), lda, int(a_kmajor), _p(b), ldb, int(b_kmajor), _p(out), ldc,
-                                         int(out.dtype == F32), M, N, K, float(alpha), _p(bias), int(act), _p(aux_in), ld_ai,
-                                         _p(aux_out), ld_ao, _p(residual), ldr, int(accumulate), *_drop(drop), _p(alpha_sumsq)), 'i2t_gemm_bf16_ex')
+        _k.i2t_gemm_bf16_ex(a, lda, int(a_kmajor), b, ldb, int(b_kmajor), out, ldc, int(out.dtype == F32), M, N, K, float(alpha), bias, int(act),
+                            aux_in, ld_ai, aux_out, ld_ao, residual, ldr, int(accumulate), *_drop(drop), alpha_sumsq)
         return out
-    _l.check(_lib().i2t_gemm_bf16(_stream(), _p(a), lda, int(a_kmajor), _p(b), ldb, int(b_kmajor), _p(out), ldc,
-                                  int(out.dtype == F32), M, N, K, float(alpha), _p(bias), int(act), _p(aux_in), ld_ai,
-                                  _p(aux_out), ld_ao, _p(residual), ldr, int(accumulate), *_drop(drop)), 'i2t_gemm_bf16')
+    _k.i2t_gemm_bf16(a, lda, int(a_kmajor), b, ldb, int(b_kmajor), out, ldc, int(out.dtype == F32), M, N, K, float(alpha), bias, int(act), aux_in,
+                     ld_ai, aux_out, ld_ao, residual, ldr, int(accumulate), *_drop(drop))
     return out
 
 
@@ -181,9 +212,7 @@ def gemm_reserved_cus() -> int:
 
 
 def colsum(x: torch.Tensor, out: torch.Tensor, M: int, N: int, ld=None, accumulate=False, alpha_sumsq=None):
-    _need_cuda(x, out)
-    _l.check(_lib().i2t_colsum_bf16_ex(_stream(), _p(x), x.stride(0) if ld is None else ld, M, N, _p(out), int(accumulate), _p(alpha_sumsq)),
-             'i2t_colsum_bf16_ex')
+    _k.i2t_colsum_bf16_ex(x, x.stride(0) if ld is None else ld, M, N, out, int(accumulate), alpha_sumsq)
     return out
 
 
@@ -196,28 +225,23 @@ def gemm_dw_colsum(dy: torch.Tensor, x: torch.Tensor, gw: torch.Tensor, gb, N: i
         if gb is not None:
             colsum(dy, gb, M, N, ld=lda, accumulate=True, alpha_sumsq=alpha_sumsq)
         return gemm(dy, x, gw, N, K, M, a_kmajor=True, b_kmajor=True, lda=lda, ldb=ldb, ldc=ldc, alpha=alpha, accumulate=True, alpha_sumsq=alpha_sumsq)
-    _need_cuda(dy, x, gw)
-    assert dy.dtype == BF16 and x.dtype == BF16 and gw.dtype == F32 and (gb is None or gb.dtype == F32)
-    _l.check(_lib().i2t_gemm_dw_colsum_bf16(_stream(), _p(dy), dy.stride(0) if lda is None else lda, _p(x), x.stride(0) if ldb is None else ldb,
-                                            _p(gw), gw.stride(0) if ldc is None else ldc, N, K, M, float(alpha), _p(alpha_sumsq), _p(gb)),
-             'i2t_gemm_dw_colsum_bf16')
+    assert dy.dtype == BF16 and x.dtype == BF16
+    _k.i2t_gemm_dw_colsum_bf16(dy, dy.stride(0) if lda is None else lda, x, x.stride(0) if ldb is None else ldb, gw,
+                               gw.stride(0) if ldc is None else ldc, N, K, M, float(alpha), alpha_sumsq, gb)
     return gw
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, M, d, eps=None):
     """eps None: the reference's LayerNorm (1e-5); torchvision's ViT blocks pass 1e-6."""
-    _need_cuda(x, y)
     if y.dtype == BF16 and precise():          # parity mode: the row in fp32, then its two bf16 terms
         y32 = torch.empty(y.shape, dtype=F32, device=y.device)
         layernorm_fwd(x, gamma, beta, y32, mean, rstd, M, d, eps)
         y._i2t_lo = torch.empty_like(y)
         return split_f32(y32, y, y._i2t_lo)
     if eps is not None:
-        _l.check(_lib().i2t_layernorm_fwd_eps(_stream(), _p(x), _p(gamma), _p(beta), _p(y), int(y.dtype == F32), _p(mean), _p(rstd),
-                                              M, d, float(eps)), 'i2t_layernorm_fwd_eps')
+        _k.i2t_layernorm_fwd_eps(x, gamma, beta, y, int(y.dtype == F32), mean, rstd, M, d, float(eps))
         return y
-    _l.check(_lib().i2t_layernorm_fwd(_stream(), _p(x), _p(gamma), _p(beta), _p(y), int(y.dtype == F32), _p(mean), _p(rstd),
-                                      M, d), 'i2t_layernorm_fwd')
+    _k.i2t_layernorm_fwd(x, gamma, beta, y, int(y.dtype == F32), mean, rstd, M, d)
     return y
 
 
@@ -226,11 +250,9 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, M, d, dx_accumula
     """bf16_drop = (1, key, thr, scale): elementwise dropout mask applied to the bf16 copy only; dx_mask = (1, key, thr, scale): the
     same kind of mask on the f32 dx this call stores; acc_period / acc_rows: accumulate onto the first acc_rows rows of every period only
     (see include/i2t.h::i2t_layernorm_bwd_ex)."""
-    _need_cuda(dy, x, dx)
     assert (bf16_drop is None or int(bf16_drop[0]) == 1) and (dx_mask is None or int(dx_mask[0]) == 1)
-    _l.check(_lib().i2t_layernorm_bwd_ex(_stream(), _p(dy), int(dy.dtype == F32), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx),
-                                         int(dx_accumulate), _p(dx_bf16), _p(dgamma), _p(dbeta), M, d, *_drop(bf16_drop)[1:],
-                                         _p(sumsq_out), _p(dx_pre_sumsq), *_drop(dx_mask)[1:], int(acc_period), int(acc_rows)), 'i2t_layernorm_bwd_ex')
+    _k.i2t_layernorm_bwd_ex(dy, int(dy.dtype == F32), x, gamma, mean, rstd, dx, int(dx_accumulate), dx_bf16, dgamma, dbeta, M, d,
+                            *_drop(bf16_drop)[1:], sumsq_out, dx_pre_sumsq, *_drop(dx_mask)[1:], int(acc_period), int(acc_rows))
     return dx
 
 
@@ -240,17 +262,13 @@ LNND_STATS_STRIDE = 34
 def layernorm_nd_fwd(x, add, gamma, beta, y, y_batch_stride, stats, B, rows, d, drop=None, drop_base=0):
     """drop = (1, key, thr, scale) + drop_base: the elementwise dropout of the tensor y is a slab of, applied while writing
     (include/i2t.h::i2t_layernorm_nd_fwd_drop)"""
-    _need_cuda(x, y, stats)
     assert drop is None or int(drop[0]) == 1
-    _l.check(_lib().i2t_layernorm_nd_fwd_drop(_stream(), _p(x), _p(add), _p(gamma), _p(beta), _p(y), y_batch_stride, _p(stats), B,
-                                              rows, d, *_drop(drop)[1:], int(drop_base)), 'i2t_layernorm_nd_fwd_drop')
+    _k.i2t_layernorm_nd_fwd_drop(x, add, gamma, beta, y, y_batch_stride, stats, B, rows, d, *_drop(drop)[1:], int(drop_base))
     return y
 
 
 def layernorm_nd_bwd(dy, dy_batch_stride, x, add, gamma, stats, dx, dgamma, dbeta, dadd, B, rows, d):
-    _need_cuda(dy, x, dx)
-    _l.check(_lib().i2t_layernorm_nd_bwd(_stream(), _p(dy), dy_batch_stride, _p(x), _p(add), _p(gamma), _p(stats), _p(dx),
-                                         _p(dgamma), _p(dbeta), _p(dadd), B, rows, d), 'i2t_layernorm_nd_bwd')
+    _k.i2t_layernorm_nd_bwd(dy, dy_batch_stride, x, add, gamma, stats, dx, dgamma, dbeta, dadd, B, rows, d)
     return dx
 
 
@@ -264,10 +282,8 @@ def _bs_rs(t: torch.Tensor):
 def attention_fwd(q, k, v, o, lse, B, H, Tq, Tk, causal, drop=None, cu_q=None, cu_k=None, total_q=0):
     """q,k,v,o: bf16 [B, T, >=64H] views (last dim contiguous; heads at 64-column steps), or packed [rows, >=64H] views
     together with cu_q / cu_k (device int32 [B+1])."""
-    _need_cuda(q, k, v, o)
     qb, qr = _bs_rs(q); kb, kr = _bs_rs(k); vb, vr = _bs_rs(v); ob, orr = _bs_rs(o)
-    _l.check(_lib().i2t_attention_fwd(_stream(), _p(q), qb, qr, _p(k), kb, kr, _p(v), vb, vr, _p(o), ob, orr, _p(lse), B, H, Tq,
-                                      Tk, int(causal), *_drop(drop)[1:], _p(cu_q), _p(cu_k), int(total_q)), 'i2t_attention_fwd')
+    _k.i2t_attention_fwd(q, qb, qr, k, kb, kr, v, vb, vr, o, ob, orr, lse, B, H, Tq, Tk, int(causal), *_drop(drop)[1:], cu_q, cu_k, int(total_q))
     return o
 
 
@@ -275,13 +291,10 @@ def attention_bwd(q, k, v, o, do, lse, delta_ws, dq, dk, dv, B, H, Tq, Tk, causa
                   out_drop=None, out_drop_q_seq=0):
     """out_drop = (2, key, thr, scale): the forward's per-token q/k/v multipliers applied to dq/dk/dv on the way out;
     out_drop_q_seq: the queries are the first Tq rows of sequences of that many rows (i2t_attention_bwd_ex)."""
-    _need_cuda(q, k, v, o, do, dq, dk, dv)
     qb, qr = _bs_rs(q); kb, kr = _bs_rs(k); vb, vr = _bs_rs(v); ob, orr = _bs_rs(o); gb, gr = _bs_rs(do)
     dqb, dqr = _bs_rs(dq); dkb, dkr = _bs_rs(dk); dvb, dvr = _bs_rs(dv)
-    _l.check(_lib().i2t_attention_bwd_ex(_stream(), _p(q), qb, qr, _p(k), kb, kr, _p(v), vb, vr, _p(o), ob, orr, _p(do), gb, gr,
-                                         _p(lse), _p(delta_ws), _p(dq), dqb, dqr, _p(dk), dkb, dkr, _p(dv), dvb, dvr, B, H, Tq, Tk,
-                                         int(causal), *_drop(drop)[1:], _p(cu_q), _p(cu_k), int(total_q), *_drop(out_drop)[1:],
-                                         int(out_drop_q_seq)), 'i2t_attention_bwd_ex')
+    _k.i2t_attention_bwd_ex(q, qb, qr, k, kb, kr, v, vb, vr, o, ob, orr, do, gb, gr, lse, delta_ws, dq, dqb, dqr, dk, dkb, dkr, dv, dvb, dvr, B, H,
+                            Tq, Tk, int(causal), *_drop(drop)[1:], cu_q, cu_k, int(total_q), *_drop(out_drop)[1:], int(out_drop_q_seq))
 
 
 def attention_bwd_takes_q_seq(Tq: int, Tk: int, drop) -> bool:
@@ -295,52 +308,40 @@ def attention_bwd_takes_q_seq(Tq: int, Tk: int, drop) -> bool:
 
 def gq_attention_fwd(q, k, v, o, lse, B, H, Hkv, hd, Tq, Tk, causal, drop=None, cu_q=None, cu_k=None, total_q=0, split=0):
     """Grouped-query attention (include/i2t.h::i2t_gq_attention_fwd): H query heads of width hd on Hkv shared key/value heads."""
-    _need_cuda(q, k, v, o, lse)
     qb, qr = _bs_rs(q); kb, kr = _bs_rs(k); vb, vr = _bs_rs(v); ob, orr = _bs_rs(o)
-    _l.check(_lib().i2t_gq_attention_fwd(_stream(), _p(q), qb, qr, _p(k), kb, kr, _p(v), vb, vr, _p(o), ob, orr, _p(lse), B, H, Hkv, hd,
-                                         Tq, Tk, int(causal), *_drop(drop)[1:], _p(cu_q), _p(cu_k), int(total_q), int(split)), 'i2t_gq_attention_fwd')
+    _k.i2t_gq_attention_fwd(q, qb, qr, k, kb, kr, v, vb, vr, o, ob, orr, lse, B, H, Hkv, hd, Tq, Tk, int(causal), *_drop(drop)[1:], cu_q, cu_k,
+                            int(total_q), int(split))
     return o
 
 
 def gq_attention_bwd(q, k, v, o, do, lse, delta_ws, dq, dk, dv, B, H, Hkv, hd, Tq, Tk, causal, drop=None, cu_q=None, cu_k=None,
                      total_q=0, out_drop=None):
-    _need_cuda(q, k, v, o, do, dq, dk, dv)
     qb, qr = _bs_rs(q); kb, kr = _bs_rs(k); vb, vr = _bs_rs(v); ob, orr = _bs_rs(o); gb, gr = _bs_rs(do)
     dqb, dqr = _bs_rs(dq); dkb, dkr = _bs_rs(dk); dvb, dvr = _bs_rs(dv)
-    _l.check(_lib().i2t_gq_attention_bwd(_stream(), _p(q), qb, qr, _p(k), kb, kr, _p(v), vb, vr, _p(o), ob, orr, _p(do), gb, gr,
-                                         _p(lse), _p(delta_ws), _p(dq), dqb, dqr, _p(dk), dkb, dkr, _p(dv), dvb, dvr, B, H, Hkv, hd, Tq,
-                                         Tk, int(causal), *_drop(drop)[1:], _p(cu_q), _p(cu_k), int(total_q), *_drop(out_drop)[1:]),
-             'i2t_gq_attention_bwd')
+    _k.i2t_gq_attention_bwd(q, qb, qr, k, kb, kr, v, vb, vr, o, ob, orr, do, gb, gr, lse, delta_ws, dq, dqb, dqr, dk, dkb, dkr, dv, dvb, dvr, B, H,
+                            Hkv, hd, Tq, Tk, int(causal), *_drop(drop)[1:], cu_q, cu_k, int(total_q), *_drop(out_drop)[1:])
 
 
 def row_sections_dropout(x, rows, cols, section, drop, key_offset=0):
     """drop = (2, key, thr, scale): x[m, n] *= multiplier(key + key_offset + n // section, m)  (bf16 [rows, ld], in place)."""
     if drop is None:
         return x
-    _need_cuda(x)
     assert x.dtype == BF16 and x.stride(-1) == 1
-    _l.check(_lib().i2t_row_sections_dropout(_stream(), _p(x), x.stride(-2), rows, cols, section, (int(drop[1]) + key_offset) & 0xFFFFFFFF,
-                                             int(drop[2]), float(drop[3])), 'i2t_row_sections_dropout')
+    _k.i2t_row_sections_dropout(x, x.stride(-2), rows, cols, section, (int(drop[1]) + key_offset) & 0xFFFFFFFF, int(drop[2]), float(drop[3]))
     return x
 
 
 def gather_rows(src, idx, n, d, out_f32=None, out_bf16=None):
-    _need_cuda(src, idx, out_f32, out_bf16)
-    assert src.dtype == F32 and idx.dtype == torch.int32
-    _l.check(_lib().i2t_gather_rows(_stream(), _p(src), _p(idx), _p(out_f32), _p(out_bf16), n, d), 'i2t_gather_rows')
+    _k.i2t_gather_rows(src, idx, out_f32, out_bf16, n, d)
 
 
 def scatter_rows(src, idx, dst, n, d):
-    _need_cuda(src, idx, dst)
-    assert src.dtype == F32 and dst.dtype == F32 and idx.dtype == torch.int32
-    _l.check(_lib().i2t_scatter_rows(_stream(), _p(src), _p(idx), _p(dst), n, d), 'i2t_scatter_rows')
+    _k.i2t_scatter_rows(src, idx, dst, n, d)
 
 
 def moe_gate_fwd(U, wg2, bg2, A, gates, wsel, M, E, P, G, top_k, inv_sqrt_in):
-    _need_cuda(U, A, gates, wsel)
-    assert U.dtype == F32 and A.dtype == BF16
-    _l.check(_lib().i2t_moe_gate_fwd(_stream(), _p(U), U.stride(0), _p(wg2), _p(bg2), _p(A), A.stride(0), _p(gates), _p(wsel), M, E, P, G,
-                                     top_k, float(inv_sqrt_in)), 'i2t_moe_gate_fwd')
+    assert A.dtype == BF16
+    _k.i2t_moe_gate_fwd(U, U.stride(0), wg2, bg2, A, A.stride(0), gates, wsel, M, E, P, G, top_k, float(inv_sqrt_in))
 
 
 def moe_gate_bwd_blocks(M: int) -> int:
@@ -348,31 +349,25 @@ def moe_gate_bwd_blocks(M: int) -> int:
 
 
 def moe_gate_bwd(dA, U, gates, wsel, wg2, D1, dwg2, dbg2, part_ws, M, E, P, G, top_k, inv_sqrt_in):
-    _need_cuda(dA, U, D1)
-    assert dA.dtype == BF16 and D1.dtype == BF16 and U.dtype == F32
-    _l.check(_lib().i2t_moe_gate_bwd(_stream(), _p(dA), dA.stride(0), _p(U), U.stride(0), _p(gates), _p(wsel), _p(wg2), _p(D1), D1.stride(0),
-                                     _p(dwg2), _p(dbg2), _p(part_ws), M, E, P, G, top_k, float(inv_sqrt_in)), 'i2t_moe_gate_bwd')
+    assert dA.dtype == BF16 and D1.dtype == BF16
+    _k.i2t_moe_gate_bwd(dA, dA.stride(0), U, U.stride(0), gates, wsel, wg2, D1, D1.stride(0), dwg2, dbg2, part_ws, M, E, P, G, top_k,
+                        float(inv_sqrt_in))
 
 
 def moe_pack_w2(l2w, l2b, W, out, E, P):
-    _need_cuda(l2w, l2b, W)
-    assert l2w.dtype == BF16 and l2b.dtype == F32 and W.dtype == BF16
-    _l.check(_lib().i2t_moe_pack_w2(_stream(), _p(l2w), _p(l2b), _p(W), out, E, P, W.stride(0)), 'i2t_moe_pack_w2')
+    assert l2w.dtype == BF16 and W.dtype == BF16
+    _k.i2t_moe_pack_w2(l2w, l2b, W, out, E, P, W.stride(0))
 
 
 def moe_unpack_dw2(dW, gw, gb, out, E, P):
-    _need_cuda(dW, gw, gb)
-    assert dW.dtype == F32 and gw.dtype == F32
-    _l.check(_lib().i2t_moe_unpack_dw2(_stream(), _p(dW), _p(gw), _p(gb), out, E, P, dW.stride(0)), 'i2t_moe_unpack_dw2')
+    _k.i2t_moe_unpack_dw2(dW, gw, gb, out, E, P, dW.stride(0))
 
 
 def gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, B, H, Hkv, hd):
     """Decode-step attention of the family (include/i2t.h::i2t_gq_decode_attention); q / k_new / v_new / out are row-major 2-D views."""
-    _need_cuda(q, kcache, vcache, out)
     kv_rs = k_new.stride(0) if k_new is not None else 0
-    _l.check(_lib().i2t_gq_decode_attention(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
-                                            cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, B, H, Hkv, hd),
-             'i2t_gq_decode_attention')
+    _k.i2t_gq_decode_attention(q, q.stride(0), k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs, out, out.stride(0), pos_ptr, n_keys_fixed,
+                               max_keys, B, H, Hkv, hd)
     return out
 
 
@@ -380,26 +375,20 @@ def beam_decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, o, o_rs, 
                           append_dm=0, cache_hs=64):
     """decode_attention with key t of row r read from cache row hist[r][t] (hist None: row r // rows_per_mem) -- include/i2t.h::
     i2t_beam_decode_attention"""
-    _need_cuda(q, kcache, vcache, o, hist)
-    assert hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1)
-    _l.check(_lib().i2t_beam_decode_attention(_stream(), _p(q), q_rs, _p(kcache), _p(vcache), cache_bs, cache_rs, cache_hs, _p(o), o_rs,
-                                              _p(pos), n_keys_fixed, append_dm, _p(hist), 0 if hist is None else hist.stride(0),
-                                              rows_per_mem, R, H), 'i2t_beam_decode_attention')
+    assert hist is None or hist.stride(1) == 1
+    _k.i2t_beam_decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, cache_hs, o, o_rs, pos, n_keys_fixed, append_dm, hist,
+                                 0 if hist is None else hist.stride(0), rows_per_mem, R, H)
 
 
 def beam_gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, R, H, Hkv, hd,
                              hist=None, rows_per_mem=1, slot_pos=None):
     """gq_decode_attention with the same history indirection (include/i2t.h::i2t_beam_gq_decode_attention); slot_pos (int32
     [max_keys], sparse layers): key s of row r is read from cache row hist[r][slot_pos[s]]"""
-    _need_cuda(q, kcache, vcache, out, hist, slot_pos)
-    assert hist is None or (hist.dtype == torch.int32 and hist.stride(1) == 1)
-    assert slot_pos is None or (hist is not None and slot_pos.dtype == torch.int32 and slot_pos.is_contiguous()
-                                and slot_pos.numel() >= max_keys)
+    assert hist is None or hist.stride(1) == 1
+    assert slot_pos is None or (hist is not None and slot_pos.is_contiguous() and slot_pos.numel() >= max_keys)
     kv_rs = k_new.stride(0) if k_new is not None else 0
-    _l.check(_lib().i2t_beam_gq_decode_attention(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
-                                                 cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, _p(hist),
-                                                 0 if hist is None else hist.stride(0), _p(slot_pos), rows_per_mem, R, H, Hkv, hd),
-             'i2t_beam_gq_decode_attention')
+    _k.i2t_beam_gq_decode_attention(q, q.stride(0), k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs, out, out.stride(0), pos_ptr,
+                                    n_keys_fixed, max_keys, hist, 0 if hist is None else hist.stride(0), slot_pos, rows_per_mem, R, H, Hkv, hd)
     return out
 
 
@@ -418,12 +407,10 @@ def gq_decode_long_workspace_floats(R: int, H: int, max_keys: int, hd: int) -> i
 def gq_decode_attention_long(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs, out, pos_ptr, n_keys_fixed, max_keys, B, H, Hkv, hd, ws):
     """gq_decode_attention over caches past 1024 keys, the keys split across workgroups (include/i2t.h::i2t_gq_decode_attention_long);
     ws: fp32, at least gq_decode_long_workspace_floats(B, H, max_keys, hd) elements."""
-    _need_cuda(q, kcache, vcache, out, ws)
-    assert ws.dtype == F32 and ws.is_contiguous()
+    assert ws.is_contiguous()
     kv_rs = k_new.stride(0) if k_new is not None else 0
-    _l.check(_lib().i2t_gq_decode_attention_long(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache), cache_bs,
-                                                 cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys, B, H, Hkv, hd, _p(ws),
-                                                 ws.numel()), 'i2t_gq_decode_attention_long')
+    _k.i2t_gq_decode_attention_long(q, q.stride(0), k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs, out, out.stride(0), pos_ptr,
+                                    n_keys_fixed, max_keys, B, H, Hkv, hd, ws, ws.numel())
     return out
 
 
@@ -431,13 +418,10 @@ def beam_gq_decode_attention_long(q, k_new, v_new, kcache, vcache, cache_bs, cac
                                   ws, hist):
     """gq_decode_attention_long with key t of row r read from cache row hist[r][t] (int32 [R][>= max_keys];
     include/i2t.h::i2t_beam_gq_decode_attention_long)"""
-    _need_cuda(q, kcache, vcache, out, ws, hist)
-    assert ws.dtype == F32 and ws.is_contiguous() and hist.dtype == torch.int32 and hist.stride(1) == 1
+    assert ws.is_contiguous() and hist.stride(1) == 1
     kv_rs = k_new.stride(0) if k_new is not None else 0
-    _l.check(_lib().i2t_beam_gq_decode_attention_long(_stream(), _p(q), q.stride(0), _p(k_new), _p(v_new), kv_rs, _p(kcache), _p(vcache),
-                                                      cache_bs, cache_rs, _p(out), out.stride(0), _p(pos_ptr), n_keys_fixed, max_keys,
-                                                      _p(hist), hist.stride(0), R, H, Hkv, hd, _p(ws), ws.numel()),
-             'i2t_beam_gq_decode_attention_long')
+    _k.i2t_beam_gq_decode_attention_long(q, q.stride(0), k_new, v_new, kv_rs, kcache, vcache, cache_bs, cache_rs, out, out.stride(0), pos_ptr,
+                                         n_keys_fixed, max_keys, hist, hist.stride(0), R, H, Hkv, hd, ws, ws.numel())
     return out
 
 
@@ -445,114 +429,89 @@ def beam_candidates(logits, ids, len_ptr, ctrl, ngram_sizes, R, V, E, temperatur
                     raw_tok=None):
     """E candidates per beam row after ban / crop / EOS rule (include/i2t.h::i2t_beam_candidates); top_k None/0 = no crop, eos None/-1
     = no EOS rule"""
-    _need_cuda(logits, ids, len_ptr, ctrl, seed, cand_tok, cand_lp)
-    assert logits.dtype == F32 and cand_tok.dtype == torch.int32 and cand_lp.dtype == F32 and seed.dtype == torch.int32
-    _l.check(_lib().i2t_beam_candidates(_stream(), _p(logits), logits.stride(0), _p(ids), ids.stride(0), _p(len_ptr), _p(ctrl),
-                                        _p(ngram_sizes), 0 if ngram_sizes is None else ngram_sizes.numel(), R, V, E, float(temperature),
-                                        int(top_k or 0), -1 if eos is None else int(eos), float(log_boost), _p(seed), _p(cand_tok),
-                                        _p(cand_lp), _p(raw_tok)), 'i2t_beam_candidates')
+    _k.i2t_beam_candidates(logits, logits.stride(0), ids, ids.stride(0), len_ptr, ctrl, ngram_sizes,
+                           0 if ngram_sizes is None else ngram_sizes.numel(), R, V, E, float(temperature), int(top_k or 0),
+                           -1 if eos is None else int(eos), float(log_boost), seed, cand_tok, cand_lp, raw_tok)
 
 
 def beam_consolidate(cand_tok, cand_lp, scores, ids, hist, has_eos, parent, pos_ptr, len_ptr, ctrl, B, W, E, temperature, eos, seed,
                      raw_pick=None):
     """W survivors per caption, ids / history rows moved to the children (include/i2t.h::i2t_beam_consolidate)"""
-    _need_cuda(cand_tok, cand_lp, scores, ids, hist, has_eos, parent, ctrl, seed)
-    assert hist.dtype == torch.int32 and scores.dtype == F32 and ids.dtype == torch.long
-    _l.check(_lib().i2t_beam_consolidate(_stream(), _p(cand_tok), _p(cand_lp), _p(scores), _p(ids), ids.stride(0), _p(hist), hist.stride(0),
-                                         _p(has_eos), _p(parent), _p(pos_ptr), _p(len_ptr), _p(ctrl), B, W, E, float(temperature),
-                                         -1 if eos is None else int(eos), _p(seed), _p(raw_pick)), 'i2t_beam_consolidate')
+    _k.i2t_beam_consolidate(cand_tok, cand_lp, scores, ids, ids.stride(0), hist, hist.stride(0), has_eos, parent, pos_ptr, len_ptr, ctrl, B, W, E,
+                            float(temperature), -1 if eos is None else int(eos), seed, raw_pick)
 
 
 def beam_pool_select(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed, pos_ptr,
                      len_ptr, ctrl, B, W, P, max_new, eos, pad, length_penalty, early_stopping):
     """the selection step of generate_captions(num_beams = W): finished pool, running children, close test
     (include/i2t.h::i2t_beam_pool_select); pool_ids [B, W, ids_ld] and pool_lp [B, W, lp_ld] share the row strides of ids and tok_lp"""
-    assert ids.dtype == torch.long and pool_ids.dtype == torch.long and hist.dtype == torch.int32 and cand_tok.dtype == torch.int32
     assert cand_tok.shape == (B * W, 2 * W) and cand_lp.shape == (B * W, 2 * W) and cand_tok.is_contiguous() and cand_lp.is_contiguous()
     assert pool_ids.is_contiguous() and pool_lp.is_contiguous() and pool_ids.shape == (B, W, ids.stride(0)) and pool_lp.shape == (B, W, tok_lp.stride(0))
     assert ids.shape[0] == B * W and hist.shape[0] == B * W and tok_lp.shape[0] == B * W and scores.numel() == B * W
     assert pool_score.numel() == B * W and pool_sum.numel() == B * W and pool_len.numel() == B * W and pool_n.numel() == B and closed.numel() == B
-    _l.check(_lib().i2t_beam_pool_select(_stream(), _p(cand_tok), _p(cand_lp), _p(scores), _p(ids), ids.stride(0), _p(hist), hist.stride(0),
-                                         _p(tok_lp), tok_lp.stride(0), _p(pool_ids), _p(pool_lp), _p(pool_score), _p(pool_sum), _p(pool_len),
-                                         _p(pool_n), _p(closed), _p(pos_ptr), _p(len_ptr), _p(ctrl), B, W, P, max_new,
-                                         -1 if eos is None else int(eos), int(pad), float(length_penalty), int(bool(early_stopping))),
-             'i2t_beam_pool_select')
+    _k.i2t_beam_pool_select(cand_tok, cand_lp, scores, ids, ids.stride(0), hist, hist.stride(0), tok_lp, tok_lp.stride(0), pool_ids, pool_lp,
+                            pool_score, pool_sum, pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, B, W, P, max_new, -1 if eos is None else int(eos),
+                            int(pad), float(length_penalty), int(bool(early_stopping)))
 
 
 def beam_advance(counters, ctrl):
-    _l.check(_lib().i2t_beam_advance(_stream(), _p(counters), _p(ctrl)), 'i2t_beam_advance')
+    _k.i2t_beam_advance(counters, ctrl)
 
 
 def sparse_step_setup(pos_ptr, rank, member, lpos, lmem, L, tmax):
-    _need_cuda(pos_ptr, rank, member, lpos, lmem)
-    _l.check(_lib().i2t_sparse_step_setup(_stream(), _p(pos_ptr), _p(rank), _p(member), _p(lpos), _p(lmem), L, tmax), 'i2t_sparse_step_setup')
+    _k.i2t_sparse_step_setup(pos_ptr, rank, member, lpos, lmem, L, tmax)
 
 
 def select_rows(flag, a, b, out, n):
-    _need_cuda(flag, a, b, out)
-    _l.check(_lib().i2t_select_rows(_stream(), _p(flag), _p(a), _p(b), _p(out), n), 'i2t_select_rows')
+    _k.i2t_select_rows(flag, a, b, out, n)
 
 
 def grouped_gemm(mode, a, b, c, N, K, *, b_group_stride=0, c_group_stride=0, bias=None, bias_group_stride=0, act=0, aux_in=None,
                  aux_out=None, residual=None, accumulate=False, seg=None, n_groups=1, max_rows=0, group_ptr=None, group0=0):
     """One GEMM per group (position) in one launch; see include/i2t.h::i2t_grouped_gemm for the three modes."""
-    _need_cuda(a, b, c)
     assert a.dtype == BF16 and b.dtype == BF16 and c.dtype in (BF16, F32)
     aux = aux_in if aux_in is not None else aux_out
-    _l.check(_lib().i2t_grouped_gemm(_stream(), mode, _p(a), a.stride(0), _p(b), b.stride(0), b_group_stride, _p(c), c.stride(0),
-                                     c_group_stride, int(c.dtype == F32), _p(bias), bias_group_stride, int(act), _p(aux_in), _p(aux_out),
-                                     aux.stride(0) if aux is not None else 0, _p(residual), residual.stride(0) if residual is not None else 0,
-                                     int(accumulate), _p(seg), n_groups, max_rows, _p(group_ptr), group0, N, K), 'i2t_grouped_gemm')
+    _k.i2t_grouped_gemm(mode, a, a.stride(0), b, b.stride(0), b_group_stride, c, c.stride(0), c_group_stride, int(c.dtype == F32), bias,
+                        bias_group_stride, int(act), aux_in, aux_out, aux.stride(0) if aux is not None else 0, residual,
+                        residual.stride(0) if residual is not None else 0, int(accumulate), seg, n_groups, max_rows, group_ptr, group0, N, K)
     return c
 
 
 def grouped_colsum(x, seg, n_groups, out, out_group_stride, group0, N):
-    _need_cuda(x, seg, out)
-    _l.check(_lib().i2t_grouped_colsum(_stream(), _p(x), x.stride(0), _p(seg), n_groups, _p(out), out_group_stride, group0, N),
-             'i2t_grouped_colsum')
+    _k.i2t_grouped_colsum(x, x.stride(0), seg, n_groups, out, out_group_stride, group0, N)
 
 
 def xattn_kv_fused(mem, w_kv, bias_kv, q, kv, o, lse, B, S, H, Tq, drop=None, cu_q=None, total_q=0):
     """Fused cross-attention forward (include/i2t.h::i2t_xattn_kv_fused): kv = mem . w_kv^T + bias written once, attention of every
     (image, head) out of the projection's accumulators.  q / o: [B, Tq, >= 64 H] views or packed [rows, >= 64 H] with cu_q.
     S (memory tokens per image) is 64, or 8 / 16 / 32 (64 / S whole images per wave); H even; any other S raises I2TError."""
-    _need_cuda(mem, w_kv, q, kv, o)
     qb, qr = _bs_rs(q); ob, orr = _bs_rs(o)
     assert mem.dtype == BF16 and w_kv.dtype == BF16 and q.dtype == BF16 and kv.dtype == BF16 and o.dtype == BF16
-    _l.check(_lib().i2t_xattn_kv_fused(_stream(), _p(mem), mem.stride(0), _p(w_kv), w_kv.stride(0), _p(bias_kv), _p(q), qb, qr,
-                                       _p(cu_q), int(total_q), _p(kv), kv.stride(-2), _p(o), ob, orr, _p(lse), B, S, H, Tq,
-                                       *_drop(drop)[1:]), 'i2t_xattn_kv_fused')
+    _k.i2t_xattn_kv_fused(mem, mem.stride(0), w_kv, w_kv.stride(0), bias_kv, q, qb, qr, cu_q, int(total_q), kv, kv.stride(-2), o, ob, orr, lse, B, S,
+                          H, Tq, *_drop(drop)[1:])
     return o
 
 
 def embed_fwd(ids, wte, wpe, x, B, T, d, pos_offset, vocab, pos=None):
-    _need_cuda(ids, wte, x)
-    _l.check(_lib().i2t_embed_fwd(_stream(), _p(ids), _p(wte), _p(wpe), _p(x), B, T, d, pos_offset, vocab, _p(pos)), 'i2t_embed_fwd')
+    _k.i2t_embed_fwd(ids, wte, wpe, x, B, T, d, pos_offset, vocab, pos)
     return x
 
 
 def embed_bwd(ids, dx, dwte, dwpe, B, T, d, pos_offset, vocab, pos=None):
-    _need_cuda(ids, dx)
-    _l.check(_lib().i2t_embed_bwd(_stream(), _p(ids), _p(dx), _p(dwte), _p(dwpe), B, T, d, pos_offset, vocab, _p(pos)), 'i2t_embed_bwd')
+    _k.i2t_embed_bwd(ids, dx, dwte, dwpe, B, T, d, pos_offset, vocab, pos)
 
 
 def ce_fwd(logits, ld, labels, w, inv_temp, ignore_index, lse, loss, M, V):
-    _need_cuda(logits, labels, w, lse, loss)
-    _l.check(_lib().i2t_ce_fwd(_stream(), _p(logits), ld, _p(labels), _p(w), float(inv_temp), int(ignore_index), _p(lse),
-                               _p(loss), M, V), 'i2t_ce_fwd')
+    _k.i2t_ce_fwd(logits, ld, labels, w, float(inv_temp), int(ignore_index), lse, loss, M, V)
 
 
 def ce_bwd(logits, ld, labels, w, inv_temp, ignore_index, lse, gscale, M, V):
-    _need_cuda(logits, labels, w, lse, gscale)
-    _l.check(_lib().i2t_ce_bwd(_stream(), _p(logits), ld, _p(labels), _p(w), float(inv_temp), int(ignore_index), _p(lse),
-                               _p(gscale), M, V), 'i2t_ce_bwd')
+    _k.i2t_ce_bwd(logits, ld, labels, w, float(inv_temp), int(ignore_index), lse, gscale, M, V)
 
 
 def ce_fwd_bwd(logits, ld, labels, w, inv_temp, ignore_index, lse, loss, M, V):
     """One pass: lse / loss as ce_fwd, and the rows overwritten with the un-scaled gradient (include/i2t.h::i2t_ce_fwd_bwd)."""
-    _need_cuda(logits, labels, w, lse, loss)
-    _l.check(_lib().i2t_ce_fwd_bwd(_stream(), _p(logits), ld, _p(labels), _p(w), float(inv_temp), int(ignore_index), _p(lse),
-                                   _p(loss), M, V), 'i2t_ce_fwd_bwd')
+    _k.i2t_ce_fwd_bwd(logits, ld, labels, w, float(inv_temp), int(ignore_index), lse, loss, M, V)
 
 
 CE_ONE_PASS_MAX_V = 8 * 16 * 512
@@ -560,35 +519,27 @@ CE_ONE_PASS_MAX_V = 8 * 16 * 512
 
 def scale_bf16(x, n, scale):
     """x[0 .. n) *= scale[0] in place (bf16 x, device scalar); a no-op launch when the scale is exactly 1."""
-    _need_cuda(x, scale)
-    assert x.dtype == BF16 and scale.dtype == F32
-    _l.check(_lib().i2t_scale_bf16(_stream(), _p(x), int(n), _p(scale)), 'i2t_scale_bf16')
+    assert x.dtype == BF16
+    _k.i2t_scale_bf16(x, int(n), scale)
 
 
 def ce_distill_fwd(logits, ld, teacher, ld_t, alpha, labels, w, inv_temp, ignore_index, lse, lse_t, loss, M, V):
-    _need_cuda(logits, teacher, labels, w, lse, lse_t, loss)
-    _l.check(_lib().i2t_ce_distill_fwd(_stream(), _p(logits), ld, _p(teacher), ld_t, float(alpha), _p(labels), _p(w), float(inv_temp),
-                                       int(ignore_index), _p(lse), _p(lse_t), _p(loss), M, V), 'i2t_ce_distill_fwd')
+    _k.i2t_ce_distill_fwd(logits, ld, teacher, ld_t, float(alpha), labels, w, float(inv_temp), int(ignore_index), lse, lse_t, loss, M, V)
 
 
 def ce_distill_bwd(logits, ld, teacher, ld_t, alpha, labels, w, inv_temp, ignore_index, lse, lse_t, gscale, M, V):
-    _need_cuda(logits, teacher, labels, w, lse, lse_t, gscale)
-    _l.check(_lib().i2t_ce_distill_bwd(_stream(), _p(logits), ld, _p(teacher), ld_t, float(alpha), _p(labels), _p(w), float(inv_temp),
-                                       int(ignore_index), _p(lse), _p(lse_t), _p(gscale), M, V), 'i2t_ce_distill_bwd')
+    _k.i2t_ce_distill_bwd(logits, ld, teacher, ld_t, float(alpha), labels, w, float(inv_temp), int(ignore_index), lse, lse_t, gscale, M, V)
 
 
 def ema_update(pm, p, pm_bf16, n, momentum):
-    _need_cuda(pm, p)
-    _l.check(_lib().i2t_ema_update(_stream(), _p(pm), _p(p), _p(pm_bf16), int(n), float(momentum)), 'i2t_ema_update')
+    _k.i2t_ema_update(pm, p, pm_bf16, int(n), float(momentum))
 
 
 def lm_inputs(labels, ids, B, L, bos, eos, mask_id, vocab, ignore_index, mask_fraction=0.0, random_fraction=0.0, seed=0):
     """ids = [BOS, labels[:-1]] with ignored labels -> EOS and the optional MLM corruption (include/i2t.h::i2t_lm_inputs)."""
-    _need_cuda(labels, ids)
-    assert labels.dtype == torch.long and ids.dtype == torch.long and labels.is_contiguous() and ids.is_contiguous()
-    _l.check(_lib().i2t_lm_inputs(_stream(), _p(labels), _p(ids), B, L, int(bos), int(eos), int(-1 if mask_id is None else mask_id), int(vocab),
-                                  int(ignore_index), float(mask_fraction), float(random_fraction), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF),
-             'i2t_lm_inputs')
+    assert labels.is_contiguous() and ids.is_contiguous()
+    _k.i2t_lm_inputs(labels, ids, B, L, int(bos), int(eos), int(-1 if mask_id is None else mask_id), int(vocab), int(ignore_index),
+                     float(mask_fraction), float(random_fraction), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
     return ids
 
 
@@ -596,304 +547,242 @@ def grad_normalize(g: torch.Tensor, ws: torch.Tensor, g_bf16=None, bf16_drop=Non
                    keep_f32=False):
     """presummed: ws already holds sum(g^2) (layernorm_bwd's sumsq_out); clear_after: 1-float tensor zeroed afterwards;
     keep_f32: g stays un-normalised, only the bf16 copy is written (the first layernorm_bwd onto g passes dx_pre_sumsq=ws)."""
-    _need_cuda(g, ws)
     assert bf16_drop is None or int(bf16_drop[0]) == 1
-    _l.check(_lib().i2t_grad_normalize(_stream(), _p(g), g.numel(), _p(ws), _p(g_bf16), *_drop(bf16_drop)[1:],
-                                       int(bool(presummed)) | (2 if keep_f32 else 0), _p(clear_after)), 'i2t_grad_normalize')
+    _k.i2t_grad_normalize(g, g.numel(), ws, g_bf16, *_drop(bf16_drop)[1:], int(bool(presummed)) | (2 if keep_f32 else 0), clear_after)
     return g
 
 
 def rmsnorm_fwd(x, w, y, rstd, M, d, eps, y_f32=None):
-    _need_cuda(x, w)
-    _l.check(_lib().i2t_rmsnorm_fwd(_stream(), _p(x), _p(w), _p(y), _p(y_f32), _p(rstd), M, d, float(eps)), 'i2t_rmsnorm_fwd')
+    _k.i2t_rmsnorm_fwd(x, w, y, y_f32, rstd, M, d, float(eps))
     return y
 
 
 def rmsnorm_bwd(dy, x, w, rstd, dx, dw, M, d, dx_accumulate=False, dx_bf16=None):
-    _need_cuda(dy, x, w, rstd, dx)
-    _l.check(_lib().i2t_rmsnorm_bwd(_stream(), _p(dy), int(dy.dtype == F32), _p(x), _p(w), _p(rstd), _p(dx), int(dx_accumulate),
-                                    _p(dx_bf16), _p(dw), M, d), 'i2t_rmsnorm_bwd')
+    _k.i2t_rmsnorm_bwd(dy, int(dy.dtype == F32), x, w, rstd, dx, int(dx_accumulate), dx_bf16, dw, M, d)
     return dx
 
 
 def rope(x, rs, col0, n_heads, hd, cos_sin, M, pos=None, pos_ptr=None, pos_offset=0, T=0, inverse=False):
     """in place on bf16 rows (include/i2t.h::i2t_rope)"""
-    _need_cuda(x, cos_sin)
-    _l.check(_lib().i2t_rope(_stream(), _p(x), rs, col0, n_heads, hd, _p(cos_sin), cos_sin.shape[0], _p(pos), _p(pos_ptr), pos_offset,
-                             T, M, int(inverse)), 'i2t_rope')
+    _k.i2t_rope(x, rs, col0, n_heads, hd, cos_sin, cos_sin.shape[0], pos, pos_ptr, pos_offset, T, M, int(inverse))
     return x
 
 
 def swiglu_fwd(gate_up, h, M, ff):
-    _need_cuda(gate_up, h)
-    _l.check(_lib().i2t_swiglu_fwd(_stream(), _p(gate_up), gate_up.stride(0), _p(h), M, ff), 'i2t_swiglu_fwd')
+    _k.i2t_swiglu_fwd(gate_up, gate_up.stride(0), h, M, ff)
     return h
 
 
 def swiglu_bwd(dh, gate_up, d_gate_up, M, ff):
-    _need_cuda(dh, gate_up, d_gate_up)
-    _l.check(_lib().i2t_swiglu_bwd(_stream(), _p(dh), _p(gate_up), gate_up.stride(0), _p(d_gate_up), M, ff), 'i2t_swiglu_bwd')
+    _k.i2t_swiglu_bwd(dh, gate_up, gate_up.stride(0), d_gate_up, M, ff)
     return d_gate_up
 
 
 def dgelu_mul(dh, pre, out, erf=False):
     """out (bf16) = dh (fp32) * gelu'(pre (bf16)), contiguous; tanh form (include/i2t.h::i2t_dgelu_mul) or exact (i2t_dgelu_erf_mul)"""
-    _need_cuda(dh, pre, out)
-    assert dh.dtype == F32 and pre.dtype == BF16 and out.dtype == BF16 and dh.is_contiguous() and pre.is_contiguous() and out.is_contiguous()
+    assert pre.dtype == BF16 and out.dtype == BF16 and dh.is_contiguous() and pre.is_contiguous() and out.is_contiguous()
     if erf:
-        _l.check(_lib().i2t_dgelu_erf_mul(_stream(), _p(dh), _p(pre), _p(out), dh.numel()), 'i2t_dgelu_erf_mul')
+        _k.i2t_dgelu_erf_mul(dh, pre, out, dh.numel())
     else:
-        _l.check(_lib().i2t_dgelu_mul(_stream(), _p(dh), _p(pre), _p(out), dh.numel()), 'i2t_dgelu_mul')
+        _k.i2t_dgelu_mul(dh, pre, out, dh.numel())
     return out
 
 
 def gelu_fwd(pre, out, erf=False):
     """out (bf16) = gelu(pre (bf16)), contiguous (include/i2t.h::i2t_gelu_fwd)"""
-    _need_cuda(pre, out)
     assert pre.dtype == BF16 and out.dtype == BF16 and pre.is_contiguous() and out.is_contiguous()
-    _l.check(_lib().i2t_gelu_fwd(_stream(), _p(pre), _p(out), pre.numel(), int(bool(erf))), 'i2t_gelu_fwd')
+    _k.i2t_gelu_fwd(pre, out, pre.numel(), int(bool(erf)))
     return out
 
 
 def lora_stage(x, xcat, xd, M, K, drop):
     """xcat[:, :K] = x and (xd not None) xd = dropout(x): include/i2t.h::i2t_lora_stage; drop = (1, key, thr, scale) | None"""
-    _need_cuda(x, xcat)
     assert x.is_contiguous() and (drop is None) == (xd is None) and (drop is None or int(drop[0]) == 1)
-    _l.check(_lib().i2t_lora_stage(_stream(), _p(x), _p(xcat), xcat.stride(0), _p(xd), M, K, *_drop(drop)[1:]), 'i2t_lora_stage')
+    _k.i2t_lora_stage(x, xcat, xcat.stride(0), xd, M, K, *_drop(drop)[1:])
 
 
 def sumsq(g: torch.Tensor, ws: torch.Tensor, accumulate=False):
     """ws[0] (+)= sum(g^2)  (include/i2t.h::i2t_sumsq)"""
-    _need_cuda(g, ws)
-    _l.check(_lib().i2t_sumsq(_stream(), _p(g), g.numel(), _p(ws), int(accumulate)), 'i2t_sumsq')
+    _k.i2t_sumsq(g, g.numel(), ws, int(accumulate))
     return ws
 
 
 def conv_fwd(x, in_gelu, w, bias, y, w_ws, B, Cin, Cout, H, W, k):
-    _need_cuda(x, w, y, w_ws)
-    _l.check(_lib().i2t_conv_fwd(_stream(), _p(x), int(x.dtype == F32), int(in_gelu), _p(w), _p(bias), _p(y), _p(w_ws), B, Cin,
-                                 Cout, H, W, k), 'i2t_conv_fwd')
+    _k.i2t_conv_fwd(x, int(x.dtype == F32), int(in_gelu), w, bias, y, w_ws, B, Cin, Cout, H, W, k)
     return y
 
 
 def conv_bwd_data(dy, w, x_pre, in_gelu, dx, w_ws, B, Cin, Cout, H, W, k):
-    _need_cuda(dy, w, dx, w_ws)
-    _l.check(_lib().i2t_conv_bwd_data(_stream(), _p(dy), _p(w), _p(x_pre), int(in_gelu), _p(dx), _p(w_ws), B, Cin, Cout, H, W,
-                                      k), 'i2t_conv_bwd_data')
+    _k.i2t_conv_bwd_data(dy, w, x_pre, int(in_gelu), dx, w_ws, B, Cin, Cout, H, W, k)
     return dx
 
 
 def conv_bwd_weight(dy, x, in_gelu, dw, db, B, Cin, Cout, H, W, k):
-    _need_cuda(dy, x, dw)
-    _l.check(_lib().i2t_conv_bwd_weight(_stream(), _p(dy), _p(x), int(x.dtype == F32), int(in_gelu), _p(dw), _p(db), B, Cin,
-                                        Cout, H, W, k), 'i2t_conv_bwd_weight')
+    _k.i2t_conv_bwd_weight(dy, x, int(x.dtype == F32), int(in_gelu), dw, db, B, Cin, Cout, H, W, k)
 
 
 LAYOUT_NCHW_F32, LAYOUT_NCHW_BF16, LAYOUT_NHWC_BF16 = 0, 1, 2
 
 
 def conv6_fwd(x, x_layout, in_gelu, w, bias, y, y_nchw, w_ws, B, Cin, Cout, H, W):
-    _need_cuda(x, w, y, w_ws)
-    _l.check(_lib().i2t_conv6_fwd(_stream(), _p(x), x_layout, int(in_gelu), _p(w), _p(bias), _p(y), int(y_nchw), _p(w_ws), B, Cin,
-                                  Cout, H, W), 'i2t_conv6_fwd')
+    _k.i2t_conv6_fwd(x, x_layout, int(in_gelu), w, bias, y, int(y_nchw), w_ws, B, Cin, Cout, H, W)
     return y
 
 
 def conv6_bwd_data(dy, dy_layout, w, x_pre, dx, w_ws, B, Cin, Cout, H, W):
-    _need_cuda(dy, w, x_pre, dx, w_ws)
-    _l.check(_lib().i2t_conv6_bwd_data(_stream(), _p(dy), dy_layout, _p(w), _p(x_pre), _p(dx), _p(w_ws), B, Cin, Cout, H, W),
-             'i2t_conv6_bwd_data')
+    _k.i2t_conv6_bwd_data(dy, dy_layout, w, x_pre, dx, w_ws, B, Cin, Cout, H, W)
     return dx
 
 
 def conv6_bwd_weight(dy, dy_layout, x, x_layout, in_gelu, dw, db, scratch, B, Cin, Cout, H, W):
-    _need_cuda(dy, x, dw, scratch)
-    _l.check(_lib().i2t_conv6_bwd_weight(_stream(), _p(dy), dy_layout, _p(x), x_layout, int(in_gelu), _p(dw), _p(db), _p(scratch),
-                                         B, Cin, Cout, H, W), 'i2t_conv6_bwd_weight')
+    _k.i2t_conv6_bwd_weight(dy, dy_layout, x, x_layout, int(in_gelu), dw, db, scratch, B, Cin, Cout, H, W)
 
 
 def dropout_apply(x, rows, cols, drop):
     """in place; drop = (mode, key, thr, scale)"""
-    _need_cuda(x)
-    _l.check(_lib().i2t_dropout_apply(_stream(), _p(x), int(x.dtype == F32), rows, cols, *_drop(drop)), 'i2t_dropout_apply')
+    _k.i2t_dropout_apply(x, int(x.dtype == F32), rows, cols, *_drop(drop))
     return x
 
 
 def nchw_to_nhwc(src, dst, B, C, H, W):
-    _need_cuda(src, dst)
-    _l.check(_lib().i2t_nchw_to_nhwc_bf16(_stream(), _p(src), _p(dst), B, C, H, W), 'i2t_nchw_to_nhwc_bf16')
+    _k.i2t_nchw_to_nhwc_bf16(src, dst, B, C, H, W)
     return dst
 
 
 def cast_f32_bf16(src, dst, n=None):
-    _need_cuda(src, dst)
     if precise():
         dst._i2t_lo = torch.zeros_like(dst)
         return split_f32(src, dst, dst._i2t_lo, n)
-    _l.check(_lib().i2t_cast_f32_bf16(_stream(), _p(src), _p(dst), src.numel() if n is None else n), 'i2t_cast_f32_bf16')
+    _k.i2t_cast_f32_bf16(src, dst, src.numel() if n is None else n)
     return dst
 
 
 def adamw_step(p, g, m, v, p_bf16, n, seg_end, seg_lr, seg_wd, nseg, beta1, beta2, eps, step, grad_scale=1.0):
-    _need_cuda(p, g, m, v)
-    _l.check(_lib().i2t_adamw_step(_stream(), _p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(seg_end), _p(seg_lr), _p(seg_wd),
-                                   nseg, float(beta1), float(beta2), float(eps), int(step), float(grad_scale)),
-             'i2t_adamw_step')
+    _k.i2t_adamw_step(p, g, m, v, p_bf16, n, seg_end, seg_lr, seg_wd, nseg, float(beta1), float(beta2), float(eps), int(step), float(grad_scale))
 
 
 def snradam_step(p, g, m, v, p_bf16, n, seg_end, seg_lr, seg_wd, nseg, beta1, beta2, eps, step, grad_scale=1.0):
-    _need_cuda(p, g, m, v)
-    _l.check(_lib().i2t_snradam_step(_stream(), _p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(seg_end), _p(seg_lr), _p(seg_wd),
-                                     nseg, float(beta1), float(beta2), float(eps), int(step), float(grad_scale)),
-             'i2t_snradam_step')
+    _k.i2t_snradam_step(p, g, m, v, p_bf16, n, seg_end, seg_lr, seg_wd, nseg, float(beta1), float(beta2), float(eps), int(step), float(grad_scale))
 
 
 def bcast_rows(src, y, y_batch_stride, B, rows, d, drop=None):
     assert drop is None or int(drop[0]) == 1
-    _l.check(_lib().i2t_bcast_rows_drop(_stream(), _p(src), _p(y), y_batch_stride, B, rows, d, *_drop(drop)[1:]), 'i2t_bcast_rows_drop')
+    _k.i2t_bcast_rows_drop(src, y, y_batch_stride, B, rows, d, *_drop(drop)[1:])
 
 
 def sum_over_batch(x, x_batch_stride, dst, B, rows, d, accumulate=False):
-    _l.check(_lib().i2t_sum_over_batch(_stream(), _p(x), x_batch_stride, _p(dst), B, rows, d, int(accumulate)),
-             'i2t_sum_over_batch')
+    _k.i2t_sum_over_batch(x, x_batch_stride, dst, B, rows, d, int(accumulate))
 
 
 def copy_rows(x, x_bs, y, y_bs, B, rows, d):
-    _l.check(_lib().i2t_copy_rows(_stream(), _p(x), x_bs, _p(y), y_bs, int(y.dtype == BF16), B, rows, d), 'i2t_copy_rows')
+    _k.i2t_copy_rows(x, x_bs, y, y_bs, int(y.dtype == BF16), B, rows, d)
 
 
 def add_(dst, src):
-    _l.check(_lib().i2t_add_f32(_stream(), _p(dst), _p(src), dst.numel()), 'i2t_add_f32')
+    _k.i2t_add_f32(dst, src, dst.numel())
     return dst
 
 
 def decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, o, o_rs, pos, n_keys_fixed, B, H, append_dm=0, cache_hs=64):
     """cache_hs = 64: token-major cache rows [t][H][64]; cache_hs = tmax * 64 with cache_rs = 64: head-major [H][t][64]"""
-    _l.check(_lib().i2t_decode_attention(_stream(), _p(q), q_rs, _p(kcache), _p(vcache), cache_bs, cache_rs, cache_hs, _p(o), o_rs,
-                                         _p(pos), n_keys_fixed, append_dm, B, H), 'i2t_decode_attention')
+    _k.i2t_decode_attention(q, q_rs, kcache, vcache, cache_bs, cache_rs, cache_hs, o, o_rs, pos, n_keys_fixed, append_dm, B, H)
 
 
 def kv_append(qkv, qkv_rs, kcache, vcache, cache_bs, cache_rs, pos, B, d):
-    _l.check(_lib().i2t_kv_append(_stream(), _p(qkv), qkv_rs, _p(kcache), _p(vcache), cache_bs, cache_rs, _p(pos), B, d),
-             'i2t_kv_append')
+    _k.i2t_kv_append(qkv, qkv_rs, kcache, vcache, cache_bs, cache_rs, pos, B, d)
 
 
 def kv_prefill(src, src_ld, k_off, v_off, src_T, src_t0, m, kcache, vcache, cache_bs, cache_rs, cache_hs, hd, w, slot0, B, N):
     """The K / V rows a forward pass saved for m tokens of B images into slots slot0 .. slot0 + m - 1 of the N cache rows of every image
     (include/i2t.h::i2t_kv_prefill); cache_rs / cache_hs as decode_attention (head-major) and gq_decode_attention (row-major: w, hd)."""
-    _need_cuda(src, kcache, vcache)
-    _l.check(_lib().i2t_kv_prefill(_stream(), _p(src), src_ld, k_off, v_off, src_T, src_t0, m, _p(kcache), _p(vcache), cache_bs, cache_rs,
-                                   cache_hs, hd, w, slot0, B, N), 'i2t_kv_prefill')
+    _k.i2t_kv_prefill(src, src_ld, k_off, v_off, src_T, src_t0, m, kcache, vcache, cache_bs, cache_rs, cache_hs, hd, w, slot0, B, N)
 
 
 def ngram_ban_argmax(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, margin_out=None):
-    _l.check(_lib().i2t_ngram_ban_argmax(_stream(), _p(logits), ld, int(logits.dtype == F32), _p(ids), ids_ld, _p(len_ptr),
-                                         _p(ngram_sizes), n_sizes, B, V, _p(margin_out)), 'i2t_ngram_ban_argmax')
+    _k.i2t_ngram_ban_argmax(logits, ld, int(logits.dtype == F32), ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, margin_out)
 
 
 def gemm_top2(a, b, top2, M, N, K):
     """the two largest of every 64-column segment of a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_top2); top2 f32 [M, ceil(N/64), 4]"""
-    _need_cuda(a, b, top2)
-    assert a.dtype == BF16 and b.dtype == BF16 and top2.dtype == F32 and top2.is_contiguous() and top2.shape[-2] == (N + 63) // 64
-    _l.check(_lib().i2t_gemm_bf16_top2(_stream(), _p(a), a.stride(0), _p(b), b.stride(0), M, N, K, _p(top2), (N + 63) // 64), 'i2t_gemm_bf16_top2')
+    assert a.dtype == BF16 and b.dtype == BF16 and top2.is_contiguous() and top2.shape[-2] == (N + 63) // 64
+    _k.i2t_gemm_bf16_top2(a, a.stride(0), b, b.stride(0), M, N, K, top2, (N + 63) // 64)
     return top2
 
 
 def top2_ngram_argmax(top2, hidden, w_head, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, d):
     """n-gram ban + argmax over gemm_top2's segments (include/i2t.h::i2t_top2_ngram_argmax)"""
-    _need_cuda(top2, hidden, w_head, ids)
-    _l.check(_lib().i2t_top2_ngram_argmax(_stream(), _p(top2), (V + 63) // 64, _p(hidden), hidden.stride(0), _p(w_head), w_head.stride(0), d,
-                                          _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V), 'i2t_top2_ngram_argmax')
+    _k.i2t_top2_ngram_argmax(top2, (V + 63) // 64, hidden, hidden.stride(0), w_head, w_head.stride(0), d, ids, ids_ld, len_ptr, ngram_sizes, n_sizes,
+                             B, V)
 
 
 def sample_token(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, temperature, top_k, nucleus_p, seed, dist_out=None):
     """One sampling step (include/i2t.h::i2t_sample_token); top_k None/0 = no crop, nucleus_p None = no cut."""
-    _need_cuda(logits, ids, seed)
-    assert logits.dtype == F32 and seed.dtype == torch.int32 and seed.numel() >= 2
-    _l.check(_lib().i2t_sample_token(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V,
-                                     float(temperature), int(top_k or 0), float(-1.0 if nucleus_p is None else nucleus_p),
-                                     _p(seed), _p(dist_out), 0 if dist_out is None else dist_out.stride(0)), 'i2t_sample_token')
+    assert seed.numel() >= 2
+    _k.i2t_sample_token(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, float(temperature), int(top_k or 0),
+                        float(-1.0 if nucleus_p is None else nucleus_p), seed, dist_out, 0 if dist_out is None else dist_out.stride(0))
 
 
 def embed_step(ids, ids_ld, len_ptr, wte, wpe, x, B, d, pos_offset, vocab):
-    _l.check(_lib().i2t_embed_step(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(wte), _p(wpe), _p(x), B, d, pos_offset, vocab),
-             'i2t_embed_step')
+    _k.i2t_embed_step(ids, ids_ld, len_ptr, wte, wpe, x, B, d, pos_offset, vocab)
 
 
 def advance(counters, delta=1):
-    _l.check(_lib().i2t_advance(_stream(), _p(counters), counters.numel(), delta), 'i2t_advance')
+    _k.i2t_advance(counters, counters.numel(), delta)
 
 
 def gemm_top2_lse(a, b, top2, se, M, N, K):
     """gemm_top2 that also leaves se f32 [M, ceil(N/64)]: the segment's sum of exp(z - v1) (include/i2t.h::i2t_gemm_bf16_top2_lse)"""
-    _need_cuda(a, b, top2, se)
     nseg = (N + 63) // 64
-    assert a.dtype == BF16 and b.dtype == BF16 and top2.dtype == F32 and se.dtype == F32 and top2.is_contiguous() and se.is_contiguous()
+    assert a.dtype == BF16 and b.dtype == BF16 and top2.is_contiguous() and se.is_contiguous()
     assert top2.shape[-1] == 4 and top2.shape[-2] == nseg and top2.numel() >= M * nseg * 4 and se.shape[-1] == nseg and se.numel() >= M * nseg
     assert a.stride(-1) == 1 and b.stride(-1) == 1 and a.shape[0] >= M and b.shape[0] >= N
-    _l.check(_lib().i2t_gemm_bf16_top2_lse(_stream(), _p(a), a.stride(0), _p(b), b.stride(0), M, N, K, _p(top2), _p(se), nseg),
-             'i2t_gemm_bf16_top2_lse')
+    _k.i2t_gemm_bf16_top2_lse(a, a.stride(0), b, b.stride(0), M, N, K, top2, se, nseg)
     return top2, se
 
 
 def _lp_args(ids, ids_ld, done, tok_lp, B):
     """the shared checks of the caption-step choosers: tok_lp f32 rows addressed like the id rows, done an int32 device word"""
-    _need_cuda(ids, done, tok_lp)
-    assert ids.dtype == torch.long and tok_lp.dtype == F32 and done.dtype == torch.int32 and done.numel() >= 1
-    assert tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= B and tok_lp.shape[1] >= ids_ld
+    assert done.numel() >= 1 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= B and tok_lp.shape[1] >= ids_ld
 
 
 def top2_ngram_argmax_lp(top2, se, hidden, w_head, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, d, done, tok_lp):
     """top2_ngram_argmax + tok_lp[b][len] = log-prob of the chosen token; no write once *done (include/i2t.h::i2t_top2_ngram_argmax_lp)"""
-    _need_cuda(top2, se, hidden, w_head)
     _lp_args(ids, ids_ld, done, tok_lp, B)
-    assert top2.dtype == F32 and se.dtype == F32 and hidden.dtype == BF16 and w_head.dtype == BF16
-    _l.check(_lib().i2t_top2_ngram_argmax_lp(_stream(), _p(top2), _p(se), (V + 63) // 64, _p(hidden), hidden.stride(0), _p(w_head),
-                                             w_head.stride(0), d, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V, _p(done),
-                                             _p(tok_lp), tok_lp.stride(0)), 'i2t_top2_ngram_argmax_lp')
+    assert hidden.dtype == BF16 and w_head.dtype == BF16
+    _k.i2t_top2_ngram_argmax_lp(top2, se, (V + 63) // 64, hidden, hidden.stride(0), w_head, w_head.stride(0), d, ids, ids_ld, len_ptr, ngram_sizes,
+                                n_sizes, B, V, done, tok_lp, tok_lp.stride(0))
 
 
 def ngram_ban_argmax_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, done, tok_lp):
     """ngram_ban_argmax over fp32 logits + tok_lp[b][len]; no write once *done (include/i2t.h::i2t_ngram_ban_argmax_lp)"""
-    _need_cuda(logits)
     _lp_args(ids, ids_ld, done, tok_lp, B)
-    assert logits.dtype == F32
-    _l.check(_lib().i2t_ngram_ban_argmax_lp(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V, _p(done),
-                                            _p(tok_lp), tok_lp.stride(0)), 'i2t_ngram_ban_argmax_lp')
+    _k.i2t_ngram_ban_argmax_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, done, tok_lp, tok_lp.stride(0))
 
 
 def sample_token_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, temperature, top_k, nucleus_p, seed, done, tok_lp,
                     dist_out=None):
     """sample_token + tok_lp[b][len] = log-prob of the drawn token under the RAW row; no write once *done (i2t_sample_token_lp)"""
-    _need_cuda(logits, seed)
     _lp_args(ids, ids_ld, done, tok_lp, B)
-    assert logits.dtype == F32 and seed.dtype == torch.int32 and seed.numel() >= 2
-    _l.check(_lib().i2t_sample_token_lp(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(ngram_sizes), n_sizes, B, V,
-                                        float(temperature), int(top_k or 0), float(-1.0 if nucleus_p is None else nucleus_p), _p(seed),
-                                        _p(dist_out), 0 if dist_out is None else dist_out.stride(0), _p(done), _p(tok_lp), tok_lp.stride(0)),
-             'i2t_sample_token_lp')
+    assert seed.numel() >= 2
+    _k.i2t_sample_token_lp(logits, ld, ids, ids_ld, len_ptr, ngram_sizes, n_sizes, B, V, float(temperature), int(top_k or 0),
+                           float(-1.0 if nucleus_p is None else nucleus_p), seed, dist_out, 0 if dist_out is None else dist_out.stride(0), done,
+                           tok_lp, tok_lp.stride(0))
 
 
 def caption_finish(ids, ids_ld, len_ptr, eos, pad, finished, lengths, tok_lp, ctrl, R):
     """the finish rule of a caption step (include/i2t.h::i2t_caption_finish); eos None/-1 = no rule"""
-    _need_cuda(ids, len_ptr, finished, lengths, tok_lp, ctrl)
-    assert ids.dtype == torch.long and finished.dtype == torch.int32 and lengths.dtype == torch.int32 and ctrl.dtype == torch.int32
-    assert tok_lp.dtype == F32 and tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
-    _l.check(_lib().i2t_caption_finish(_stream(), _p(ids), ids_ld, _p(len_ptr), -1 if eos is None else int(eos), int(pad), _p(finished),
-                                       _p(lengths), _p(tok_lp), tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish')
+    assert tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
+    _k.i2t_caption_finish(ids, ids_ld, len_ptr, -1 if eos is None else int(eos), int(pad), finished, lengths, tok_lp, tok_lp.stride(0), ctrl, R)
 
 
 def caption_finish_ragged(ids, ids_ld, len_ptr, prompt, plen, N, max_new, eos, pad, finished, lengths, tok_lp, ctrl, R):
     """the finish rule of a caption step whose rows have prompts of different lengths: forced while len < plen[r // N], the budget
     of max_new emitted tokens counted per row (include/i2t.h::i2t_caption_finish_ragged); prompt int64 [B, ld], plen int32 [B]"""
-    _need_cuda(ids, len_ptr, prompt, plen, finished, lengths, tok_lp, ctrl)
-    assert ids.dtype == torch.long and finished.dtype == torch.int32 and lengths.dtype == torch.int32 and ctrl.dtype == torch.int32
-    assert tok_lp.dtype == F32 and tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
-    assert prompt.dtype == torch.long and prompt.dim() == 2 and prompt.stride(-1) == 1 and plen.dtype == torch.int32 and plen.is_contiguous()
+    assert tok_lp.stride(-1) == 1 and finished.numel() >= R and lengths.numel() >= R and ctrl.numel() >= 2
+    assert prompt.dim() == 2 and prompt.stride(-1) == 1 and plen.is_contiguous()
     assert N >= 1 and R % N == 0 and prompt.shape[0] >= R // N and plen.numel() >= R // N
-    _l.check(_lib().i2t_caption_finish_ragged(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(prompt), prompt.stride(0), _p(plen), N, int(max_new),
-                                              -1 if eos is None else int(eos), int(pad), _p(finished), _p(lengths), _p(tok_lp),
-                                              tok_lp.stride(0), _p(ctrl), R), 'i2t_caption_finish_ragged')
+    _k.i2t_caption_finish_ragged(ids, ids_ld, len_ptr, prompt, prompt.stride(0), plen, N, int(max_new), -1 if eos is None else int(eos), int(pad),
+                                 finished, lengths, tok_lp, tok_lp.stride(0), ctrl, R)
 
 
 def caption_logits_process(logits, ld, ids, ids_ld, len_ptr, plen, P, N, suppress, n_suppress, eos, min_new, theta, inv_theta, done, raw_lse,
@@ -902,33 +791,26 @@ def caption_logits_process(logits, ld, ids, ids_ld, len_ptr, plen, P, N, suppres
     ids[r][0 .. len), the suppress list (int32, the first n_suppress entries; None: none), EOS below min_new emitted tokens (plen int32
     [R / N], or None: every prompt P long); raw_lse [R] and saved [R, >= ids_ld] keep what caption_raw_logprob needs; no write once
     *done (include/i2t.h::i2t_caption_logits_process).  inv_theta: 1 / theta rounded to fp32 by the caller"""
-    _need_cuda(logits, ids, len_ptr, done, raw_lse, saved)
-    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and saved.dtype == F32
     assert saved.dim() == 2 and saved.stride(-1) == 1 and saved.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
-    assert plen is None or (plen.is_cuda and plen.dtype == torch.int32 and plen.is_contiguous() and N >= 1 and plen.numel() >= R // N)
-    assert suppress is None or (suppress.is_cuda and suppress.dtype == torch.int32 and suppress.is_contiguous() and suppress.numel() >= n_suppress)
+    assert plen is None or (plen.is_contiguous() and N >= 1 and plen.numel() >= R // N)
+    assert suppress is None or (suppress.is_contiguous() and suppress.numel() >= n_suppress)
     assert suppress is not None or n_suppress == 0
-    _l.check(_lib().i2t_caption_logits_process(_stream(), _p(logits), ld, _p(ids), ids_ld, _p(len_ptr), _p(plen), int(P), int(N), _p(suppress),
-                                               int(n_suppress), -1 if eos is None else int(eos), int(min_new), float(theta), float(inv_theta),
-                                               _p(done), _p(raw_lse), _p(saved), saved.stride(0), R, V), 'i2t_caption_logits_process')
+    _k.i2t_caption_logits_process(logits, ld, ids, ids_ld, len_ptr, plen, int(P), int(N), suppress, int(n_suppress), -1 if eos is None else int(eos),
+                                  int(min_new), float(theta), float(inv_theta), done, raw_lse, saved, saved.stride(0), R, V)
 
 
 def caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, logits, ld, done, tok_lp, R, V):
     """after the chooser of a processed step: tok_lp[r][len] = raw z[ids[r][len]] - raw_lse[r], the raw logit from ``saved`` when the
     token occurs in ids[r][0 .. len), else from ``logits``; no write once *done (include/i2t.h::i2t_caption_raw_logprob)"""
-    _need_cuda(ids, len_ptr, raw_lse, saved, logits, done, tok_lp)
-    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and saved.dtype == F32
-    assert tok_lp.dtype == F32 and tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
+    assert tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
     assert saved.dim() == 2 and saved.stride(-1) == 1 and saved.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
-    _l.check(_lib().i2t_caption_raw_logprob(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(raw_lse), _p(saved), saved.stride(0), _p(logits), ld,
-                                            _p(done), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_raw_logprob')
+    _k.i2t_caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, saved.stride(0), logits, ld, done, tok_lp, tok_lp.stride(0), R, V)
 
 
 def _trie_args(child_off, child_tok, term, child_next=None):
     """the shared checks of the trie kernels: int32 CSR arrays on the device -> (nodes, edges) the arrays hold"""
     arrays = (child_off, child_tok, term) + (() if child_next is None else (child_next,))
-    _need_cuda(*arrays)
-    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in arrays)
+    assert all(t.is_contiguous() for t in arrays)
     assert child_off.numel() == term.numel() + 1 and (child_next is None or child_next.numel() == child_tok.numel())
     return term.numel(), child_tok.numel()
 
@@ -938,12 +820,9 @@ def caption_trie_mask(logits, ld, node, child_off, child_tok, term, eos, done, r
     except the children of node[r] and, at a node that ends a phrase, EOS; raw_lse [R] and kept [R, >= max fan-out + 1] take the raw
     row's log-sum-exp and the raw allowed logits; no write once *done (include/i2t.h::i2t_caption_trie_mask)"""
     nodes, edges = _trie_args(child_off, child_tok, term)
-    _need_cuda(logits, node, done, raw_lse, kept)
-    assert logits.dtype == F32 and node.dtype == torch.int32 and done.dtype == torch.int32 and raw_lse.dtype == F32 and kept.dtype == F32
     assert kept.dim() == 2 and kept.stride(-1) == 1 and kept.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
     assert node.is_contiguous() and node.numel() >= R
-    _l.check(_lib().i2t_caption_trie_mask(_stream(), _p(logits), ld, _p(node), _p(child_off), _p(child_tok), _p(term), nodes, edges, int(eos),
-                                          _p(done), _p(raw_lse), _p(kept), kept.stride(0), R, V), 'i2t_caption_trie_mask')
+    _k.i2t_caption_trie_mask(logits, ld, node, child_off, child_tok, term, nodes, edges, int(eos), done, raw_lse, kept, kept.stride(0), R, V)
 
 
 def caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, eos, done, node,
@@ -952,22 +831,18 @@ def caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, ch
     on EOS at a node that ends a phrase, takes that phrase's index; tok_lp[r][len] = logits[r][chosen] - raw_lse[r]; no write once
     *done (include/i2t.h::i2t_caption_trie_advance)"""
     nodes, edges = _trie_args(child_off, child_tok, term, child_next)
-    _need_cuda(ids, len_ptr, finished, logits, raw_lse, done, node, phrase_index, tok_lp)
-    assert logits.dtype == F32 and ids.dtype == torch.long and done.dtype == torch.int32 and raw_lse.dtype == F32 and finished.dtype == torch.int32
-    assert node.dtype == torch.int32 and phrase_index.dtype == torch.int32 and node.is_contiguous() and phrase_index.is_contiguous()
+    assert node.is_contiguous() and phrase_index.is_contiguous()
     assert node.numel() >= R and phrase_index.numel() >= R and finished.numel() >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
-    assert tok_lp.dtype == F32 and tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
-    _l.check(_lib().i2t_caption_trie_advance(_stream(), _p(ids), ids_ld, _p(len_ptr), _p(finished), _p(logits), ld, _p(raw_lse), _p(child_off),
-                                             _p(child_tok), _p(child_next), _p(term), nodes, edges, int(eos), _p(done), _p(node),
-                                             _p(phrase_index), _p(tok_lp), tok_lp.stride(0), R, V), 'i2t_caption_trie_advance')
+    assert tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
+    _k.i2t_caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, nodes, edges, int(eos),
+                                done, node, phrase_index, tok_lp, tok_lp.stride(0), R, V)
 
 
 def rows_lse(logits, ld, lse, R, V):
     """lse[r] = the log-sum-exp of columns [0, V) of fp32 logits row r, in caption_trie_mask's reduction order; the rows are only read
     (include/i2t.h::i2t_rows_lse)"""
-    _need_cuda(logits, lse)
-    assert logits.dtype == F32 and lse.dtype == F32 and lse.is_contiguous() and lse.numel() >= R
-    _l.check(_lib().i2t_rows_lse(_stream(), _p(logits), ld, _p(lse), R, V), 'i2t_rows_lse')
+    assert lse.is_contiguous() and lse.numel() >= R
+    _k.i2t_rows_lse(logits, ld, lse, R, V)
     return lse
 
 
@@ -1014,42 +889,35 @@ def trie_level_expand(tables: TrieLevelTables, lse, path_in, path_out, ids, ids_
     """one level of score_phrases' walk over ``tables`` (trie_level_tables): the next level's path sums and tokens, and the log-probs of
     the phrases that end at this level; z from ``logits`` [B W, ld] when given, else re-evaluated from ``hidden`` [B W, d] and ``w_head``
     [V, d] (include/i2t.h::i2t_trie_level_expand)"""
-    _need_cuda(lse, path_in, path_out, ids, len_ptr, logprob, hidden, w_head, logits)
-    assert lse.dtype == F32 and path_in.dtype == F32 and path_out.dtype == F32 and logprob.dtype == F32 and ids.dtype == torch.long
     assert all(t.is_contiguous() and t.numel() >= B * W for t in (lse, path_in, path_out)) and ids.shape[0] >= B * W
-    assert logprob.dim() == 2 and logprob.stride(-1) == 1 and logprob.shape[0] >= B and len_ptr.dtype == torch.int32
-    assert logits is None or (logits.dtype == F32 and logits.shape[0] >= B * W)
+    assert logprob.dim() == 2 and logprob.stride(-1) == 1 and logprob.shape[0] >= B
+    assert logits is None or logits.shape[0] >= B * W
     assert logits is not None or (hidden.dtype == BF16 and w_head.dtype == BF16 and hidden.stride(-1) == 1 and w_head.stride(-1) == 1
                                   and hidden.shape[0] >= B * W and w_head.shape[0] >= V)
     t = tables
-    _l.check(_lib().i2t_trie_level_expand(_stream(), _p(hidden), 0 if hidden is None else hidden.stride(0), _p(w_head),
-                                          0 if w_head is None else w_head.stride(0), int(d), float(scale), _p(logits), int(ld), _p(lse),
-                                          _p(path_in), _p(path_out), _p(t.child_parent), _p(t.child_tok), t.n_child, _p(t.term_row),
-                                          _p(t.term_off), _p(t.term_phrase), t.n_term, t.n_term_phrases, _p(ids), ids_ld, _p(len_ptr),
-                                          _p(logprob), logprob.stride(0), int(eos), B, W, V), 'i2t_trie_level_expand')
+    _k.i2t_trie_level_expand(hidden, 0 if hidden is None else hidden.stride(0), w_head, 0 if w_head is None else w_head.stride(0), int(d),
+                             float(scale), logits, int(ld), lse, path_in, path_out, t.child_parent, t.child_tok, t.n_child, t.term_row, t.term_off,
+                             t.term_phrase, t.n_term, t.n_term_phrases, ids, ids_ld, len_ptr, logprob, logprob.stride(0), int(eos), B, W, V)
 
 
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
-    _need_cuda(a, b, stats)
-    assert a.dtype == BF16 and b.dtype == BF16 and stats.dtype == F32 and stats.is_contiguous()
+    assert a.dtype == BF16 and b.dtype == BF16 and stats.is_contiguous()
     assert stats.shape[-1] == 2 and stats.shape[-2] == (N + 63) // 64 and stats.numel() >= M * stats.shape[-2] * 2
     assert a.stride(-1) == 1 and b.stride(-1) == 1 and a.shape[0] >= M and b.shape[0] >= N
-    _l.check(_lib().i2t_gemm_bf16_lse(_stream(), _p(a), a.stride(0), _p(b), b.stride(0), M, N, K, float(scale), _p(stats), (N + 63) // 64),
-             'i2t_gemm_bf16_lse')
+    _k.i2t_gemm_bf16_lse(a, a.stride(0), b, b.stride(0), M, N, K, float(scale), stats, (N + 63) // 64)
     return stats
 
 
 def lse_token_logprob(stats, hidden, w_head, labels, lse, logprob, M, V, d, scale=1.0, ignore_index=-100):
     """lse[m] and logprob[m] = scale . hidden[m] . w_head[labels[m]] - lse[m] from gemm_lse's segments (include/i2t.h::i2t_lse_token_logprob)"""
-    _need_cuda(stats, hidden, w_head, labels, lse, logprob)
-    assert hidden.dtype == BF16 and w_head.dtype == BF16 and stats.dtype == F32 and lse.dtype == F32 and logprob.dtype == F32
-    assert labels.dtype == torch.long and labels.is_contiguous() and lse.is_contiguous() and logprob.is_contiguous() and stats.is_contiguous()
+    assert hidden.dtype == BF16 and w_head.dtype == BF16
+    assert labels.is_contiguous() and lse.is_contiguous() and logprob.is_contiguous() and stats.is_contiguous()
     assert stats.shape[-1] == 2 and stats.shape[-2] == (V + 63) // 64 and stats.numel() >= M * stats.shape[-2] * 2
     assert hidden.stride(-1) == 1 and w_head.stride(-1) == 1 and hidden.shape[0] >= M and w_head.shape[0] >= V
     assert labels.numel() >= M and lse.numel() >= M and logprob.numel() >= M
-    _l.check(_lib().i2t_lse_token_logprob(_stream(), _p(stats), (V + 63) // 64, _p(hidden), hidden.stride(0), _p(w_head), w_head.stride(0), d,
-                                          float(scale), _p(labels), int(ignore_index), _p(lse), _p(logprob), M, V), 'i2t_lse_token_logprob')
+    _k.i2t_lse_token_logprob(stats, (V + 63) // 64, hidden, hidden.stride(0), w_head, w_head.stride(0), d, float(scale), labels, int(ignore_index),
+                             lse, logprob, M, V)
     return logprob, lse
 
 
@@ -1086,155 +954,123 @@ ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_ERF, ACT_DGELU_ERF, ACT_GELU_DOUT, ACT_M
 
 
 def patchify(images, out, B, C, H, W, p):
-    _need_cuda(images, out)
-    assert images.dtype == F32 and out.dtype == BF16 and images.is_contiguous()
-    _l.check(_lib().i2t_patchify(_stream(), _p(images), _p(out), B, C, H, W, p), 'i2t_patchify')
+    assert out.dtype == BF16 and images.is_contiguous()
+    _k.i2t_patchify(images, out, B, C, H, W, p)
     return out
 
 
 def vit_tokens(proj, cls, pos, x, B, T, d):
-    _need_cuda(proj, cls, pos, x)
-    _l.check(_lib().i2t_vit_tokens(_stream(), _p(proj), _p(cls), _p(pos), _p(x), B, T, d), 'i2t_vit_tokens')
+    _k.i2t_vit_tokens(proj, cls, pos, x, B, T, d)
     return x
 
 
 def l2norm_fwd(x, y, y_bf16, inv_norm, M, d):
-    _need_cuda(x, y, y_bf16, inv_norm)
-    _l.check(_lib().i2t_l2norm_fwd(_stream(), _p(x), _p(y), _p(y_bf16), _p(inv_norm), M, d), 'i2t_l2norm_fwd')
+    _k.i2t_l2norm_fwd(x, y, y_bf16, inv_norm, M, d)
 
 
 def l2norm_bwd(dy, x, inv_norm, dx, M, d, accumulate=False):
-    _need_cuda(dy, x, inv_norm, dx)
-    _l.check(_lib().i2t_l2norm_bwd(_stream(), _p(dy), _p(x), _p(inv_norm), _p(dx), int(accumulate), M, d), 'i2t_l2norm_bwd')
+    _k.i2t_l2norm_bwd(dy, x, inv_norm, dx, int(accumulate), M, d)
     return dx
 
 
 def transpose_last2(src, dst, dst_bf16, B, R, C):
-    _need_cuda(src, dst, dst_bf16)
-    assert src.dtype == F32 and src.is_contiguous()
-    _l.check(_lib().i2t_transpose_last2(_stream(), _p(src), _p(dst), _p(dst_bf16), B, R, C), 'i2t_transpose_last2')
+    assert src.is_contiguous()
+    _k.i2t_transpose_last2(src, dst, dst_bf16, B, R, C)
 
 
 def peer_lookup_fwd(scores, inp_proj, residual, emb_in, emb_out, out, sv, M, nhead, nq, topk, din, dout):
     """sv: namespace(unit int32 [M, nhead, topk], lr int32 [M, nhead, topk, 2], score f32, dot f32)."""
-    _need_cuda(scores, inp_proj, residual, emb_in, emb_out, out)
-    assert scores.dtype == F32 and inp_proj.dtype == BF16 and emb_in.dtype == BF16 and emb_out.dtype == BF16 and residual.dtype == F32
-    _l.check(_lib().i2t_peer_lookup_fwd(_stream(), _p(scores), _p(inp_proj), _p(residual), _p(emb_in), _p(emb_out), _p(out), _p(sv.unit),
-                                        _p(sv.lr), _p(sv.score), _p(sv.dot), M, nhead, nq, topk, din, dout), 'i2t_peer_lookup_fwd')
+    assert inp_proj.dtype == BF16 and emb_in.dtype == BF16 and emb_out.dtype == BF16
+    _k.i2t_peer_lookup_fwd(scores, inp_proj, residual, emb_in, emb_out, out, sv.unit, sv.lr, sv.score, sv.dot, M, nhead, nq, topk, din, dout)
     return out
 
 
 def peer_lookup_bwd(dout, inp_proj, emb_in, emb_out, sv, dscores, dinp_proj, g_emb_in, g_emb_out, M, nhead, nq, topk, din, dout_w):
-    _need_cuda(dout, inp_proj, emb_in, emb_out, dscores, dinp_proj)
-    _l.check(_lib().i2t_peer_lookup_bwd(_stream(), _p(dout), _p(inp_proj), _p(emb_in), _p(emb_out), _p(sv.unit), _p(sv.lr), _p(sv.score),
-                                        _p(sv.dot), _p(dscores), _p(dinp_proj), _p(g_emb_in), _p(g_emb_out), M, nhead, nq, topk, din, dout_w),
-             'i2t_peer_lookup_bwd')
+    _k.i2t_peer_lookup_bwd(dout, inp_proj, emb_in, emb_out, sv.unit, sv.lr, sv.score, sv.dot, dscores, dinp_proj, g_emb_in, g_emb_out, M, nhead, nq,
+                           topk, din, dout_w)
 
 
 def gemm_f32(x, P, z, M, N, K):
-    _need_cuda(x, P, z)
-    assert x.dtype == F32 and P.dtype == F32 and z.dtype == F32 and x.is_contiguous() and P.is_contiguous() and z.is_contiguous()
-    _l.check(_lib().i2t_gemm_f32(_stream(), _p(x), _p(P), _p(z), M, N, K), 'i2t_gemm_f32')
+    assert x.is_contiguous() and P.is_contiguous() and z.is_contiguous()
+    _k.i2t_gemm_f32(x, P, z, M, N, K)
     return z
 
 
 def lsh_embed_fwd(z, tables, slot_stride, tab_off, nbins, grids, grid_off, out, rows, B, n_cls, nK, n_proj, dout):
-    _need_cuda(z, tables, tab_off, nbins, grids, grid_off, out, rows)
-    assert tab_off.dtype == torch.int64 and nbins.dtype == torch.int32 and grid_off.dtype == torch.int32 and rows.dtype == torch.int32
-    _l.check(_lib().i2t_lsh_embed_fwd(_stream(), _p(z), _p(tables), int(slot_stride), _p(tab_off), _p(nbins), _p(grids), _p(grid_off), _p(out),
-                                      _p(rows), B, n_cls, nK, n_proj, dout), 'i2t_lsh_embed_fwd')
+    _k.i2t_lsh_embed_fwd(z, tables, int(slot_stride), tab_off, nbins, grids, grid_off, out, rows, B, n_cls, nK, n_proj, dout)
     return out
 
 
 def lsh_embed_bwd(dy, rows, g_tables, slot_stride, tab_off, B, n_cls, nK, n_proj, dout):
-    _need_cuda(dy, rows, g_tables, tab_off)
-    _l.check(_lib().i2t_lsh_embed_bwd(_stream(), _p(dy), _p(rows), _p(g_tables), int(slot_stride), _p(tab_off), B, n_cls, nK, n_proj, dout),
-             'i2t_lsh_embed_bwd')
+    _k.i2t_lsh_embed_bwd(dy, rows, g_tables, int(slot_stride), tab_off, B, n_cls, nK, n_proj, dout)
 
 
 def l2norm_groups_fwd(x, group_off, y, inv_norm, G, rows, d):
     """l2norm_fwd over G matrices of ``rows`` rows at x + group_off[g] (int64 element offsets); y / inv_norm contiguous"""
-    _need_cuda(x, group_off, y, inv_norm)
-    assert x.dtype == F32 and y.dtype == F32 and group_off.dtype == torch.int64 and group_off.numel() >= G and y.is_contiguous()
-    _l.check(_lib().i2t_l2norm_groups_fwd(_stream(), _p(x), _p(group_off), _p(y), _p(inv_norm), G, rows, d), 'i2t_l2norm_groups_fwd')
+    assert group_off.numel() >= G and y.is_contiguous()
+    _k.i2t_l2norm_groups_fwd(x, group_off, y, inv_norm, G, rows, d)
     return y
 
 
 def l2norm_groups_bwd(dy, x, group_off, inv_norm, dx, G, rows, d, accumulate=False):
-    _need_cuda(dy, x, group_off, inv_norm, dx)
-    assert dy.dtype == F32 and x.dtype == F32 and dx.dtype == F32 and group_off.dtype == torch.int64 and group_off.numel() >= G and dy.is_contiguous()
-    _l.check(_lib().i2t_l2norm_groups_bwd(_stream(), _p(dy), _p(x), _p(group_off), _p(inv_norm), _p(dx), int(accumulate), G, rows, d),
-             'i2t_l2norm_groups_bwd')
+    assert group_off.numel() >= G and dy.is_contiguous()
+    _k.i2t_l2norm_groups_bwd(dy, x, group_off, inv_norm, dx, int(accumulate), G, rows, d)
     return dx
 
 
 def lsh_soft_fwd(c, params, slot_stride, mean_off, nbins, col_off, z, inv_norm, B, n_cls, nK, n_proj, Ktot):
     """Gaussian-kernel activations of the learnable LSH head, normalised, bf16, slot-major (include/i2t.h::i2t_lsh_soft_fwd)"""
-    _need_cuda(c, params, mean_off, nbins, col_off, z, inv_norm)
-    assert c.dtype == F32 and params.dtype == F32 and z.dtype == BF16 and inv_norm.dtype == F32 and c.is_contiguous() and z.is_contiguous()
-    assert mean_off.dtype == torch.int64 and nbins.dtype == torch.int32 and col_off.dtype == torch.int32 and col_off.numel() == nK + 1
+    assert z.dtype == BF16 and c.is_contiguous() and z.is_contiguous() and col_off.numel() == nK + 1
     assert c.numel() == B * n_cls * nK * n_proj == inv_norm.numel() and z.numel() == B * n_cls * Ktot
-    _l.check(_lib().i2t_lsh_soft_fwd(_stream(), _p(c), _p(params), int(slot_stride), _p(mean_off), _p(nbins), _p(col_off), _p(z), _p(inv_norm),
-                                     B, n_cls, nK, n_proj, Ktot), 'i2t_lsh_soft_fwd')
+    _k.i2t_lsh_soft_fwd(c, params, int(slot_stride), mean_off, nbins, col_off, z, inv_norm, B, n_cls, nK, n_proj, Ktot)
     return z
 
 
 def lsh_soft_bwd(dz, c, inv_norm, params, g_params, slot_stride, mean_off, nbins, col_off, dc, t_ws, B, n_cls, nK, n_proj, Ktot):
     """dz f32 [n_cls B, Ktot] -> dc (c's layout) and g_params (+)= d/d(mean) (None: frozen); include/i2t.h::i2t_lsh_soft_bwd"""
-    _need_cuda(dz, c, inv_norm, params, g_params, mean_off, nbins, col_off, dc, t_ws)
-    assert dz.dtype == F32 and dz.is_contiguous() and dz.numel() == B * n_cls * Ktot and dc.dtype == F32 and t_ws.dtype == F32
+    assert dz.is_contiguous() and dz.numel() == B * n_cls * Ktot and col_off.numel() == nK + 1
     assert c.numel() == B * n_cls * nK * n_proj == inv_norm.numel() == dc.numel() == t_ws.numel()
-    assert mean_off.dtype == torch.int64 and nbins.dtype == torch.int32 and col_off.dtype == torch.int32 and col_off.numel() == nK + 1
-    _l.check(_lib().i2t_lsh_soft_bwd(_stream(), _p(dz), _p(c), _p(inv_norm), _p(params), _p(g_params), int(slot_stride), _p(mean_off), _p(nbins),
-                                     _p(col_off), _p(dc), _p(t_ws), B, n_cls, nK, n_proj, Ktot), 'i2t_lsh_soft_bwd')
+    _k.i2t_lsh_soft_bwd(dz, c, inv_norm, params, g_params, int(slot_stride), mean_off, nbins, col_off, dc, t_ws, B, n_cls, nK, n_proj, Ktot)
     return dc
 
 
 # ---- fp8 (e4m3) operand path for frozen weights (csrc/fp8.hip)
 def quant_rows_fp8(x, out, scale, M, K):
     """x bf16 / f32 [M, >= K] -> out uint8 [M, ld_out] (e4m3 bytes, zero pad), scale f32 [M] (amax / 448)."""
-    _need_cuda(x, out, scale)
-    assert out.dtype == torch.uint8 and scale.dtype == F32 and x.dtype in (BF16, F32) and x.stride(-1) == 1
-    _l.check(_lib().i2t_quant_rows_fp8(_stream(), _p(x), int(x.dtype == F32), x.stride(0), _p(out), out.stride(0), _p(scale), M, K), 'i2t_quant_rows_fp8')
+    assert out.dtype == torch.uint8 and x.dtype in (BF16, F32) and x.stride(-1) == 1
+    _k.i2t_quant_rows_fp8(x, int(x.dtype == F32), x.stride(0), out, out.stride(0), scale, M, K)
     return out
 
 
 def quant_cols_fp8(w, out, scale, N, K):
     """W bf16 [N, K] -> out uint8 [K, ld_out] = W^T quantised per k, scale f32 [K]."""
-    _need_cuda(w, out, scale)
     assert w.dtype == BF16 and out.dtype == torch.uint8
-    _l.check(_lib().i2t_quant_cols_fp8(_stream(), _p(w), w.stride(0), _p(out), out.stride(0), _p(scale), N, K), 'i2t_quant_cols_fp8')
+    _k.i2t_quant_cols_fp8(w, w.stride(0), out, out.stride(0), scale, N, K)
     return out
 
 
 def rmsnorm_fwd_fp8(x, w, y8, scale, rstd, M, d, eps, y_bf16=None):
     """y8 (e4m3 [M, ld8]) , scale [M] = quantised RMSNorm(x); rstd [M] or None; y_bf16: optional contiguous bf16 copy  (include/i2t.h)"""
-    _need_cuda(x, w, y8, scale)
     assert y_bf16 is None or (y_bf16.dtype == BF16 and y_bf16.is_contiguous())
-    _l.check(_lib().i2t_rmsnorm_fwd_fp8(_stream(), _p(x), _p(w), _p(y8), y8.stride(0), _p(scale), _p(rstd), M, d, float(eps), _p(y_bf16)),
-             'i2t_rmsnorm_fwd_fp8')
+    _k.i2t_rmsnorm_fwd_fp8(x, w, y8, y8.stride(0), scale, rstd, M, d, float(eps), y_bf16)
     return y8
 
 
 def swiglu_fwd_fp8(gate_up, h8, scale, M, ff, h_bf16=None):
-    _need_cuda(gate_up, h8, scale)
     assert h_bf16 is None or (h_bf16.dtype == BF16 and h_bf16.is_contiguous())
-    _l.check(_lib().i2t_swiglu_fwd_fp8(_stream(), _p(gate_up), gate_up.stride(0), _p(h8), h8.stride(0), _p(scale), M, ff, _p(h_bf16)), 'i2t_swiglu_fwd_fp8')
+    _k.i2t_swiglu_fwd_fp8(gate_up, gate_up.stride(0), h8, h8.stride(0), scale, M, ff, h_bf16)
     return h8
 
 
 def swiglu_bwd_fp8(dh, gate_up, dgu8, scale, M, ff, dgu_bf16=None):
-    _need_cuda(dh, gate_up, dgu8, scale)
     assert dh.is_contiguous() and (dgu_bf16 is None or (dgu_bf16.dtype == BF16 and dgu_bf16.is_contiguous()))
-    _l.check(_lib().i2t_swiglu_bwd_fp8(_stream(), _p(dh), _p(gate_up), gate_up.stride(0), _p(dgu8), dgu8.stride(0), _p(scale), M, ff, _p(dgu_bf16)),
-             'i2t_swiglu_bwd_fp8')
+    _k.i2t_swiglu_bwd_fp8(dh, gate_up, gate_up.stride(0), dgu8, dgu8.stride(0), scale, M, ff, dgu_bf16)
     return dgu8
 
 
 def gemm_fp8(a8, sa, b8, sb, out, M, N, K, bias=None, residual=None, act=0):
     """out[M, N] = act((a8[M, K] . b8[N, K]^T) * sa[m] * sb[n] (+ bias)) (+ residual f32); include/i2t.h::i2t_gemm_fp8."""
-    _need_cuda(a8, b8, sa, sb, out)
     assert a8.dtype == torch.uint8 and b8.dtype == torch.uint8 and out.dtype in (BF16, F32)
-    _l.check(_lib().i2t_gemm_fp8(_stream(), _p(a8), a8.stride(0), _p(sa), _p(b8), b8.stride(0), _p(sb), _p(out), out.stride(0), int(out.dtype == F32),
-                                 M, N, K, _p(bias), int(act), _p(residual), residual.stride(0) if residual is not None else 0), 'i2t_gemm_fp8')
+    _k.i2t_gemm_fp8(a8, a8.stride(0), sa, b8, b8.stride(0), sb, out, out.stride(0), int(out.dtype == F32), M, N, K, bias, int(act), residual,
+                    residual.stride(0) if residual is not None else 0)
     return out

@@ -22,14 +22,15 @@ def header_functions():
     return out
 
 
+# the pointee a declaration names (const ignored) -> the binding's kind for it
+POINTER_KINDS = {'void*': i2tlib.P, 'float*': i2tlib.PF, 'int*': i2tlib.PI, 'int64_t*': i2tlib.PL, 'long*': i2tlib.PN, 'unsigned*': i2tlib.PU,
+                 'char*': C.c_char_p, 'void**': C.POINTER(C.c_void_p)}
+
+
 def ctype_of(decl: str):
-    decl = decl.strip()
-    if decl.endswith('*') or '*' in decl:
-        if decl.startswith('char*') or decl.startswith('char *'):
-            return C.c_char_p
-        if 'void**' in decl.replace(' ', ''):
-            return C.POINTER(C.c_void_p)
-        return C.c_void_p
+    decl = re.sub(r'\bconst\b', '', decl).strip()
+    if '*' in decl:
+        return POINTER_KINDS[decl[:decl.rindex('*') + 1].replace(' ', '')]
     base = decl.rsplit(' ', 1)[0].strip()
     return {'int': C.c_int, 'long': C.c_long, 'float': C.c_float, 'int64_t': C.c_int64, 'size_t': C.c_size_t,
             'unsigned': C.c_uint}[base]
@@ -62,7 +63,7 @@ def test_binding_matches_header_argument_types(built):
         got = i2tlib.SIGNATURES[name]
         assert len(want) == len(got), f'{name}: header has {len(want)} args, binding {len(got)}'
         for i, (w, g) in enumerate(zip(want, got)):
-            assert w is g or (w is C.c_void_p and g is C.c_void_p), f'{name} arg {i} ({args[i]}): {w} vs {g}'
+            assert w is g, f'{name} arg {i} ({args[i]}): {w} vs {g}'
 
 
 def test_error_channel(built):

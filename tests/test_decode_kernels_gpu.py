@@ -513,3 +513,16 @@ def test_embed_step(ops):
         ops.embed_step(ids, 16, i32([ln]), wte, pe, x, B, d, off, V)
         want = wte[want_id] + pe[ln - 1 + off] if pe is not None else wte[want_id]
         assert torch.equal(x, want), (off, pe is None)
+
+
+# ------------------------------------------------------------------------------------------------------ g. operand refusal
+def test_select_rows_refuses_an_int64_flag(ops):
+    """flag is an int* of i2t_select_rows: an int64 device tensor is refused on the host, by dtype, and nothing is launched"""
+    from image2text_amd.lib import I2TError
+    a, b = torch.arange(4., device=dev()), -torch.arange(4., device=dev())
+    out = torch.tensor([float('nan'), -0.0, 3e38, 1e-45], device=dev())
+    before = out.clone().view(torch.int32)
+    with pytest.raises(I2TError, match=r'i2t_select_rows.*torch\.int32.*torch\.int64'):
+        ops.select_rows(torch.ones(1, dtype=torch.int64, device=dev()), a, b, out, 4)
+    torch.cuda.synchronize()
+    assert torch.equal(out.view(torch.int32), before)
