@@ -1,5 +1,5 @@
 """What a decoding call means, decided on the host before anything runs: the argument tuples (``Sampling``, ``Processors``, ``BeamSpec``),
-the window and cache planners, the refusals of ``generate_captions`` / ``score_phrases`` and -- composing them -- ``plan_captions``, the
+the window and cache planners, the refusals of ``generate_captions`` / ``score_phrases`` / ``search_phrases`` and -- composing them -- ``plan_captions``, the
 one function that resolves a ``generate_captions`` call into a ``CaptionPlan``; the result tuples and the graph key beside them.  numpy,
 and torch only to accept tensors; no device, engine or library.  ``decoding`` re-exports every name."""
 from typing import NamedTuple, Optional
@@ -266,6 +266,67 @@ def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causa
     if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
         raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
     return trie
+
+
+class PhraseBeams(NamedTuple):
+    """What ``search_phrases`` returns: the N best phrases of the set per image, best first."""
+    phrase_index: torch.Tensor          # int64 [B, N]: the index into ``phrases``; among duplicates the one the trie's ``term`` holds (the lowest)
+    logprob: torch.Tensor               # fp32 [B, N]: the raw log-likelihood of phrase + EOS after image b's prompt (``score``'s quantity)
+    scores: torch.Tensor                # fp32 [B, N]: logprob / (tokens + 1) ** length_penalty, the sort key; at penalty 0.0 it equals logprob
+    lengths: torch.Tensor               # int32 [B, N]: the tokens of the phrase + 1 (the EOS)
+    exhaustive: bool                    # num_beams >= the widest trie level: nothing was pruned, the result is the exact top N of the set
+
+
+def trie_widest_level(trie: PhraseTrie) -> int:
+    """the largest number of nodes at one depth of the trie (the root's level counts: at least 1)"""
+    widest, level = 1, [0]
+    while level:
+        widest = max(widest, len(level))
+        level = [int(c) for nd in level for c in trie.children(nd)[1]]
+    return widest
+
+
+def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_beams=4, num_return_sequences=1, length_penalty=0.0,
+                             poll_every=8, causal: bool = True, sparse: bool = False):
+    """The refusals of ``search_phrases``, all before anything runs (host only) -> (trie, W, N).  ValueError, in this order: everything
+    ``phrase_trie`` refuses about the set (or a ``PhraseTrie`` built for another EOS / vocabulary); ``num_beams`` outside
+    1 .. MAX_CAPTION_BEAMS; ``num_return_sequences`` outside 1 .. min(num_beams, distinct phrases); a non-finite ``length_penalty``;
+    prompt + longest phrase + 1 past the decode ``window`` (the text of every other call); a negative ``poll_every``.
+    NotImplementedError, naming the reason: a non-causal decoder, sparse nano-mini blocks."""
+    if isinstance(phrases, PhraseTrie):
+        trie = phrases
+        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+                or bool((trie.child_tok == int(eos)).any()):
+            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
+    else:
+        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
+    if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
+        raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the trie beam kernels keep at most '
+                         f'{MAX_CAPTION_BEAMS} rows per image)')
+    W = int(num_beams)
+    distinct = int((trie.term >= 0).sum())
+    N = num_return_sequences
+    if isinstance(N, bool) or int(N) != N or not 1 <= int(N) <= min(W, distinct):
+        raise ValueError(f'num_return_sequences = {N!r} with num_beams = {W} and {distinct} distinct phrases: from 1 to '
+                         f'{min(W, distinct)} phrases per image')
+    try:
+        finite = bool(np.isfinite(float(length_penalty)))
+    except (TypeError, ValueError):
+        finite = False
+    if not finite:
+        raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
+    total = int(P) + trie.longest + 1
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    if isinstance(poll_every, bool) or int(poll_every) != poll_every or int(poll_every) < 0:
+        raise ValueError(f'poll_every = {poll_every!r}: it may not be negative')
+    if not causal:
+        raise NotImplementedError('search_phrases runs its beam over the trie on the KV cache; a non-causal decoder has none -- every new '
+                                  'token changes the state of the earlier ones --, so use rerank')
+    if sparse:
+        raise NotImplementedError('search_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, '
+                                  'and the trie beam step has not been run through its slot table (slot_pos); use rerank')
+    return trie, W, int(N)
 
 
 def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,

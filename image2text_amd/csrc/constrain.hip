@@ -312,3 +312,297 @@ extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hi
     I2T_CHECK_LAUNCH("i2t_trie_level_expand");
     return I2T_OK;
 }
+
+// ---- Beam search over the trie (search_phrases): W rows per image, each a trie node and an fp32 path sum; the N best
+// phrases of the set come out of a pool of finished ones.  decoding_host.trie_beam_candidates_host / trie_beam_select_host are the
+// host's statements of the two kernels.  Plain loads and vector stores, no atomics.
+namespace {
+
+constexpr int TB_MAX_W = 8, TB_NONE = 0x7fffffff;
+// (total descending, edge ascending)
+__device__ __forceinline__ bool tb_better(float v, int e, float bv, int be) { return v > bv || (v == bv && e < be); }
+
+// One workgroup per row, between the fp32 lm_head and the select kernel.  Pass A is rows_lse_kernel's, operation for operation, so
+// lse is that entry point's value on the same row.  Pass B gathers the node's children: thread i takes edges off + i, off + i + 256,
+// ..., total = path + (z[child_tok] - lse), and keeps its W best in registers; W rounds of a block arg-max over the threads' list
+// heads (the waves in order) give the row's W best, descending, the lower edge first on ties.  One pass over V plus a gather over the
+// fan-out -- no top-k over the vocabulary.  A dead row (node outside [0, nodes)) writes -1 / -inf and reads no logits.
+__global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ node,
+                                                                            const float* __restrict__ path, const int* __restrict__ child_off,
+                                                                            const int* __restrict__ child_tok, const int* __restrict__ term,
+                                                                            int nodes, int edges, int eos, const int* __restrict__ ctrl,
+                                                                            int* __restrict__ cand_edge, float* __restrict__ cand_total,
+                                                                            float* __restrict__ fin_total, float* __restrict__ lse_out, int W, int V) {
+    __shared__ float rmx[TRIE_THREADS / 64], rse[TRIE_THREADS / 64], sh_v[TRIE_THREADS / 64], sh_lse;
+    __shared__ int sh_e[TRIE_THREADS / 64], sh_win;
+    if (ctrl[0]) return;                                // block-uniform, before any barrier
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nd = node[r];
+    if (nd < 0 || nd >= nodes) {                        // block-uniform
+        if (tid < W) {
+            cand_edge[(size_t)r * W + tid] = -1;
+            cand_total[(size_t)r * W + tid] = -INFINITY;
+        }
+        if (tid == 0) fin_total[r] = -INFINITY;
+        return;
+    }
+    const float* z = logits + (size_t)r * ld;
+    float mx = -INFINITY, se = 0.f;
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
+    for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
+    }
+    for (int c = vend + tid; c < V; c += TRIE_THREADS) lse_add(mx, se, z[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
+    if ((tid & 63) == 0) {
+        rmx[tid >> 6] = mx;
+        rse[tid >> 6] = se;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < TRIE_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
+        sh_lse = mx + logf(se);
+    }
+    __syncthreads();
+    const float lse = sh_lse, p = path[r];
+    if (tid == 0) {
+        if (lse_out) lse_out[r] = lse;
+        fin_total[r] = term[nd] >= 0 ? p + (z[eos] - lse) : -INFINITY;
+    }
+    int off, fan;
+    node_edges(child_off, nd, edges, edges, off, fan);
+    float kv[TB_MAX_W];
+    int ke[TB_MAX_W];
+#pragma unroll
+    for (int j = 0; j < TB_MAX_W; ++j) {
+        kv[j] = -INFINITY;
+        ke[j] = TB_NONE;
+    }
+    for (int i = tid; i < fan; i += TRIE_THREADS) {
+        const int t = child_tok[off + i];
+        float cv = p + (((t >= 0 && t < V) ? z[t] : -INFINITY) - lse);
+        int ce = off + i;
+#pragma unroll
+        for (int j = 0; j < TB_MAX_W; ++j) {
+            if (j < W && tb_better(cv, ce, kv[j], ke[j])) {
+                const float tv = kv[j];
+                const int te = ke[j];
+                kv[j] = cv;
+                ke[j] = ce;
+                cv = tv;
+                ce = te;
+            }
+        }
+    }
+    for (int j = 0; j < W; ++j) {                       // W rounds of a block arg-max over the threads' list heads
+        float bv = kv[0];
+        int be = ke[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oe = __shfl_xor(be, o, 64);
+            if (tb_better(ov, oe, bv, be)) {
+                bv = ov;
+                be = oe;
+            }
+        }
+        if (lane == 0) {
+            sh_v[wave] = bv;
+            sh_e[wave] = be;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < TRIE_THREADS / 64; ++w)
+                if (tb_better(sh_v[w], sh_e[w], bv, be)) {
+                    bv = sh_v[w];
+                    be = sh_e[w];
+                }
+            cand_edge[(size_t)r * W + j] = be == TB_NONE ? -1 : be;
+            cand_total[(size_t)r * W + j] = be == TB_NONE ? -INFINITY : bv;
+            sh_win = be;
+        }
+        __syncthreads();
+        const int win = sh_win;
+        if (win != TB_NONE && ke[0] == win) {           // the owner of the winning edge pops its head
+#pragma unroll
+            for (int t = 0; t < TB_MAX_W - 1; ++t) {
+                kv[t] = kv[t + 1];
+                ke[t] = ke[t + 1];
+            }
+            kv[TB_MAX_W - 1] = -INFINITY;
+            ke[TB_MAX_W - 1] = TB_NONE;
+        }
+        __syncthreads();
+    }
+}
+
+// One workgroup per image, after the candidates kernel.  Thread 0 does the bookkeeping in the replica's order: the rows' offers into
+// the pool (an entry held before a new one of equal score), the W best of the rows' sorted candidate lists by a W-way merge (the lower
+// row first on ties; within a row the list's order), the close test.  Then every thread moves history columns [0, pos) from the W
+// parents to the W children a column at a time through registers -- every parent column is read before a child row is written --,
+// and threads 0 .. W - 1 write the children's node, path, token and hist[child][pos] = parent.  A row without a child is dead: node
+// -1, path -inf, token eos, its own history row.  Every open image stores the same 1 into ctrl[1]: no atomic.
+constexpr int TS_THREADS = 256;
+__global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int* __restrict__ cand_edge, const float* __restrict__ cand_total,
+                                                                      const float* __restrict__ fin_total, int* __restrict__ node,
+                                                                      float* __restrict__ path, const int* __restrict__ child_tok,
+                                                                      const int* __restrict__ child_next, const int* __restrict__ term, int nodes,
+                                                                      int edges, int eos, int64_t* __restrict__ ids, int ids_ld, int* hist,
+                                                                      int hist_ld, int* __restrict__ pool_phrase, float* __restrict__ pool_sum,
+                                                                      float* __restrict__ pool_score, int* __restrict__ pool_len,
+                                                                      int* __restrict__ pool_n, int* __restrict__ closed,
+                                                                      const int* __restrict__ pos_ptr, const int* __restrict__ len_ptr,
+                                                                      int* __restrict__ ctrl, int W, int P, int longest, float length_penalty) {
+    __shared__ int c_par[TB_MAX_W], c_node[TB_MAX_W], c_tok[TB_MAX_W], head[TB_MAX_W];
+    __shared__ float c_path[TB_MAX_W];
+    __shared__ int e_ph[TB_MAX_W + 1], e_len[TB_MAX_W + 1];
+    __shared__ float e_score[TB_MAX_W + 1], e_sum[TB_MAX_W + 1];
+    if (ctrl[0]) return;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (closed[b]) return;
+    const int pos = *pos_ptr, len = *len_ptr, t = len - P;
+    if (t < 0 || t > longest || len >= ids_ld || pos < 0 || pos >= hist_ld) return;      // counters outside the call's columns: nothing is written
+    const int r0 = b * W;
+    if (tid == 0) {
+        int m = pool_n[b];
+        m = m < 0 ? 0 : (m > W ? W : m);
+        for (int i = 0; i < m; ++i) {
+            e_score[i] = pool_score[r0 + i];
+            e_sum[i] = pool_sum[r0 + i];
+            e_ph[i] = pool_phrase[r0 + i];
+            e_len[i] = pool_len[r0 + i];
+        }
+        const float denom = powf((float)(t + 1), length_penalty);
+        for (int w = 0; w < W; ++w) {
+            const int nd = node[r0 + w];
+            head[w] = (nd >= 0 && nd < nodes) ? 0 : W;       // a dead row has no list
+            if (nd < 0 || nd >= nodes || term[nd] < 0) continue;
+            const float f = fin_total[r0 + w], s = f / denom;
+            int at = 0;
+            while (at < m && e_score[at] >= s) ++at;         // behind everything at least as good
+            if (at >= W) continue;
+            for (int i = (m < W ? m : W - 1); i > at; --i) {
+                e_score[i] = e_score[i - 1];
+                e_sum[i] = e_sum[i - 1];
+                e_ph[i] = e_ph[i - 1];
+                e_len[i] = e_len[i - 1];
+            }
+            e_score[at] = s;
+            e_sum[at] = f;
+            e_ph[at] = term[nd];
+            e_len[at] = t + 1;
+            if (m < W) ++m;
+        }
+        int nchild = 0;
+        for (int k = 0; k < W; ++k) {
+            int bw = -1, be = -1;
+            float bv = 0.f;
+            for (int w = 0; w < W; ++w) {
+                if (head[w] >= W) continue;
+                const int e = cand_edge[(size_t)(r0 + w) * W + head[w]];
+                if (e < 0 || e >= edges) {                   // the row's list ends here
+                    head[w] = W;
+                    continue;
+                }
+                const float v = cand_total[(size_t)(r0 + w) * W + head[w]];
+                if (bw < 0 || v > bv) {
+                    bw = w;
+                    be = e;
+                    bv = v;
+                }
+            }
+            if (bw < 0) break;
+            c_par[k] = r0 + bw;
+            c_node[k] = child_next[be];
+            c_tok[k] = child_tok[be];
+            c_path[k] = bv;
+            ++head[bw];
+            ++nchild;
+        }
+        for (int k = nchild; k < W; ++k) {
+            c_par[k] = r0 + k;
+            c_node[k] = -1;
+            c_tok[k] = eos;
+            c_path[k] = -INFINITY;
+        }
+        int cl = nchild == 0 ? 1 : 0;
+        if (!cl && m == W) {
+            const float lopt = powf((float)(length_penalty >= 0.f ? longest + 1 : t + 2), length_penalty);
+            cl = c_path[0] / lopt > e_score[W - 1] ? 0 : 1;
+        }
+        for (int i = 0; i < m; ++i) {
+            pool_score[r0 + i] = e_score[i];
+            pool_sum[r0 + i] = e_sum[i];
+            pool_phrase[r0 + i] = e_ph[i];
+            pool_len[r0 + i] = e_len[i];
+        }
+        pool_n[b] = m;
+        closed[b] = cl;
+        if (!cl) ctrl[1] = 1;
+    }
+    __syncthreads();
+    int vh[TB_MAX_W];
+    for (int c = tid; c < pos; c += TS_THREADS) {
+#pragma unroll
+        for (int w = 0; w < TB_MAX_W; ++w)
+            if (w < W) vh[w] = hist[(size_t)c_par[w] * hist_ld + c];
+#pragma unroll
+        for (int w = 0; w < TB_MAX_W; ++w)
+            if (w < W) hist[(size_t)(r0 + w) * hist_ld + c] = vh[w];
+    }
+    if (tid < W) {
+        const int c = r0 + tid;
+        node[c] = c_node[tid];
+        path[c] = c_path[tid];
+        ids[(size_t)c * ids_ld + len] = c_tok[tid];
+        hist[(size_t)c * hist_ld + pos] = c_par[tid];
+    }
+}
+
+}  // namespace
+
+extern "C" int i2t_trie_beam_candidates(void* stream, const float* logits, int ld, const int* node, const float* path, const int* child_off,
+                                        const int* child_tok, const int* term, int nodes, int edges, int eos, const int* ctrl, int* cand_edge,
+                                        float* cand_total, float* fin_total, float* lse, int R, int W, int V) {
+    I2T_REQUIRE(logits && node && path && child_off && child_tok && term && ctrl && cand_edge && cand_total && fin_total,
+                "i2t_trie_beam_candidates: null pointer");
+    I2T_REQUIRE(R > 0 && V > 0, "i2t_trie_beam_candidates: R = %d rows, V = %d", R, V);
+    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_candidates: W = %d candidates per row (1 .. %d)", W, TB_MAX_W);
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_trie_beam_candidates: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_trie_beam_candidates: eos = %d outside the vocabulary of %d", eos, V);
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_candidates: nodes = %d, edges = %d: a trie has a root", nodes, edges);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(node) && ALIGNED16(path) && ALIGNED16(child_off) && ALIGNED16(child_tok) && ALIGNED16(term) &&
+                    ALIGNED16(cand_edge) && ALIGNED16(cand_total) && ALIGNED16(fin_total) && ALIGNED16(lse),
+                "i2t_trie_beam_candidates: misaligned base pointer (16 bytes)");
+    hipLaunchKernelGGL(trie_beam_candidates_kernel, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, node, path, child_off,
+                       child_tok, term, nodes, edges, eos, ctrl, cand_edge, cand_total, fin_total, lse, W, V);
+    I2T_CHECK_LAUNCH("i2t_trie_beam_candidates");
+    return I2T_OK;
+}
+
+extern "C" int i2t_trie_beam_select(void* stream, const int* cand_edge, const float* cand_total, const float* fin_total, int* node, float* path,
+                                    const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos, int64_t* ids,
+                                    int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len,
+                                    int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P,
+                                    int longest, float length_penalty) {
+    I2T_REQUIRE(cand_edge && cand_total && fin_total && node && path && child_tok && child_next && term && ids && hist && pool_phrase &&
+                    pool_sum && pool_score && pool_len && pool_n && closed && pos_ptr && len_ptr && ctrl,
+                "i2t_trie_beam_select: null pointer");
+    I2T_REQUIRE(B > 0 && (long)B * TB_MAX_W < (1l << 31), "i2t_trie_beam_select: B = %d images", B);
+    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_select: W = %d rows per image (1 .. %d)", W, TB_MAX_W);
+    I2T_REQUIRE(P >= 1 && longest >= 1, "i2t_trie_beam_select: P = %d, longest = %d (each at least 1)", P, longest);
+    I2T_REQUIRE((long)P + longest + 1 <= ids_ld && hist_ld >= 1,
+                "i2t_trie_beam_select: P + longest + 1 = %ld columns exceed ids_ld = %d (hist_ld = %d)", (long)P + longest + 1, ids_ld, hist_ld);
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_select: nodes = %d, edges = %d: a trie has a root", nodes, edges);
+    I2T_REQUIRE(eos >= 0, "i2t_trie_beam_select: eos = %d: a dead row takes it as its token", eos);
+    // the exponent bits, not a comparison: no fast-math folding of a NaN test
+    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u, "i2t_trie_beam_select: length_penalty must be finite");
+    hipLaunchKernelGGL(trie_beam_select_kernel, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node, path,
+                       child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score, pool_len,
+                       pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, longest, length_penalty);
+    I2T_CHECK_LAUNCH("i2t_trie_beam_select");
+    return I2T_OK;
+}

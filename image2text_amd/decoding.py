@@ -32,13 +32,14 @@ import torch
 
 from . import ops
 from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
-                           PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseScores, Processors, Sampling,
+                           PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseBeams, PhraseScores, Processors, Sampling,
                            cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
-                           check_phrase_caption_args, check_phrase_score_args, check_ragged_caption_args, decode_window, plan_captions,
-                           prefill_plan, takes_long_cache, text_window)
+                           check_phrase_caption_args, check_phrase_score_args, check_phrase_search_args, check_ragged_caption_args, decode_window,
+                           plan_captions, prefill_plan, takes_long_cache, text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
-                            beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_scores_host,
-                            process_logits_host, slot_positions, split_attention_host, trie_advance_host, trie_mask_host)
+                            beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
+                            phrase_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
+                            trie_beam_candidates_host, trie_beam_select_host, trie_mask_host)
 from .engine import BF16, F32, HotPath
 from .phrase_trie import PhraseTrie, TrieLevel, TrieLevels, level_expand_tables, phrase_node_csr, phrase_trie, trie_levels
 
@@ -1157,6 +1158,102 @@ class TrieScoreDecoder(BeamDecoder):
             depth[lv.nodes] = t
         lengths = torch.from_numpy((depth[trie.phrase_node] + 1).astype(np.int32)).to(dev)
         return PhraseScores(out, best, lengths)
+
+
+class PhraseBeamDecoder(BeamDecoder):
+    """``search_phrases`` on the static KV cache: a beam over the phrase trie -- BeamDecoder's R = B * W rows, history
+    table, shared cross K/V and attention kernels, under GreedyDecoder._replay with ``poll_every``; W rows per image however large the
+    set.  A step is _body -> _final_norm -> fp32 lm_head -> i2t_trie_beam_candidates (every live row's W best children and the total of
+    ending at its node) -> i2t_trie_beam_select (the pool of finished phrases, the image's next rows, the close test) ->
+    i2t_beam_advance.  Every row carries its trie node and path sum in device memory; the trie lives in device buffers the step only
+    points at, sized by capacity as in CaptionDecoder._trie_state, so a captured step serves any set that fits.  The decoder keeps its
+    own state; its graph key is ('phrase_beam', ...)."""
+
+    last_replays = 0                    # full-step replays the last call launched (tests, tools)
+
+    def _build_phrase_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None):
+        st = self._build_beam(B, BeamSpec(W, W, 0.0, None, 0.0, None, 0.0, ()), ids_ld, False, clen)       # cand_tok / cand_lp: [R, W]
+        dev = st.arena.device
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=F32, device=dev)
+        R = B * W
+        st.node, st.path, st.fin_total = torch.zeros(R, **i32), torch.zeros(R, **f32), torch.zeros(R, **f32)
+        st.node_init = torch.full((B, W), -1, **i32)
+        st.node_init[:, 0] = 0
+        st.pool_phrase, st.pool_len = torch.zeros(B, W, **i32), torch.zeros(B, W, **i32)
+        st.pool_sum, st.pool_score = torch.zeros(B, W, **f32), torch.zeros(B, W, **f32)
+        st.pool_n, st.closed = torch.zeros(B, **i32), torch.zeros(B, **i32)
+        st.trie = None
+        st.phrase_beam = True
+        return st
+
+    def _load_trie(self, st, trie: PhraseTrie):
+        """the trie into st.trie = (child_off, child_tok, child_next, term), regrown -- with the graphs that hold their pointers -- when
+        it does not fit; spare nodes are childless and end no phrase"""
+        i32 = dict(dtype=torch.int32, device=st.arena.device)
+        if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges:
+            nodes, edges = max(64, trie.nodes), max(64, trie.edges)
+            st.trie = (torch.zeros(nodes + 1, **i32), torch.zeros(edges, **i32), torch.zeros(edges, **i32), torch.full((nodes,), -1, **i32))
+            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'phrase_beam')}
+        nodes, edges = st.trie[3].numel(), st.trie[1].numel()
+        off = np.full(nodes + 1, trie.edges, dtype=np.int32)
+        off[:trie.nodes + 1] = trie.child_off
+        tok, nxt, term = np.zeros(edges, dtype=np.int32), np.zeros(edges, dtype=np.int32), np.full(nodes, -1, dtype=np.int32)
+        tok[:trie.edges], nxt[:trie.edges], term[:trie.nodes] = trie.child_tok, trie.child_next, trie.term
+        for buf, host in zip(st.trie, (off, tok, nxt, term)):
+            buf.copy_(torch.from_numpy(host))
+
+    def _phrase_beam_step(self, st, P: int, eos: int, longest: int, length_penalty: float):
+        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
+        off, tok, nxt, term = st.trie
+        self._body(st)
+        self._final_norm(st)
+        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        ops.trie_beam_candidates(st.logits, dc.Vp, st.node, st.path, off, tok, term, eos, st.ctrl, st.cand_tok, st.cand_lp, st.fin_total,
+                                 st.B, st.W, dc.V)
+        ops.trie_beam_select(st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist, st.pool_phrase,
+                             st.pool_sum, st.pool_score, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl, st.images, st.W, P,
+                             longest, length_penalty)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    @torch.no_grad()
+    def search(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float = 0.0,
+               poll_every: int = 8, use_graph: bool = True, each=None) -> PhraseBeams:
+        """``phrase_beam_search_host`` for every image of the batch, on the device.  ``trie``, ``W``, ``N``: what
+        ``check_phrase_search_args`` returned -- nothing is checked again here.  ``each(i)`` runs after full step i."""
+        eng = self.eng
+        dc = eng.dec
+        a = eng.prepare(False)
+        prompt_ids = prompt_ids.to(a.device)
+        B, P = prompt_ids.shape
+        longest, length_penalty = int(trie.longest), float(length_penalty)
+        R, total = B * W, P + longest + 1
+        st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
+                             lambda st: getattr(st, 'phrase_beam', False) and st.W == W)
+        self._load_trie(st, trie)
+        self._prepare_inputs(st, images, B, W)
+        prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
+
+        def reset():
+            st.ids.zero_()
+            st.ids[:, :P] = prompt_rows
+            st.counters.copy_(st.counters_init)
+            st.hist.copy_(st.hist_init)
+            st.ctrl.zero_()
+            st.node.copy_(st.node_init.view(-1))
+            st.path.zero_()
+            st.pool_phrase.fill_(-1)
+            st.pool_score.fill_(BEAM_DEAD)
+            st.pool_sum.zero_()
+            st.pool_len.zero_()
+            st.pool_n.zero_()
+            st.closed.zero_()
+        # P, eos, longest and the penalty are kernel arguments: a captured step holds them (W is the state's)
+        key = ('phrase_beam', P, W, int(eos), longest, length_penalty)
+        self.last_replays = self._replay(st, key, lambda: self._phrase_beam_step(st, P, int(eos), longest, length_penalty), reset, P - 1,
+                                         longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
+        return PhraseBeams(st.pool_phrase[:, :N].long(), st.pool_sum[:, :N].clone(), st.pool_score[:, :N].clone(), st.pool_len[:, :N].clone(),
+                           W >= trie_widest_level(trie))
 
 
 def caption_facts(model) -> CaptionFacts:

@@ -421,3 +421,179 @@ def beam_search_host(step_logits, prompt, W: int, N: int, max_new: int, eos, pad
     lp = pool_lp[0, :N, P:L].copy()
     return SimpleNamespace(ids=pool_ids[0, :N, :L].copy(), lengths=lengths, token_logprobs=lp, logprob=lp.sum(axis=-1, dtype=f32),
                            beam_scores=pool_score[0, :N].copy(), steps=steps, gaps=gaps, pool_gaps=pool_gaps, decision_gaps=decision_gaps)
+
+
+# ------------------------------------------------------------------------------------------------ search_phrases
+def _row_lse_host(z) -> np.float32:
+    """m + log(sum exp(z - m)) of one fp32 row in fp32, as ``phrase_scores_host`` forms it"""
+    z = np.asarray(z, dtype=np.float32).reshape(-1)
+    m = z.max()
+    return np.float32(m + np.log(np.exp(z - m, dtype=np.float32).sum(dtype=np.float32), dtype=np.float32))
+
+
+def trie_beam_candidates_host(logits, node, path, trie: PhraseTrie, eos: int, W: int, V: Optional[int] = None, lse=None):
+    """One i2t_trie_beam_candidates call on the host (numpy, fp32 arithmetic in the kernel's order).  ``logits`` [R, >= V]: the raw rows;
+    ``node`` int [R]: every row's trie node, -1 a dead row; ``path`` f32 [R]: the row's path sum.  Per live row, with z its raw row and
+    lse its log-sum-exp over [0, V) -- the mask does not enter the normaliser --: fin_total = path + (z[eos] - lse) when a phrase ends
+    at the node, else -inf; every edge e of the node (a global index into child_tok / child_next) has total = path + (z[child_tok[e]] -
+    lse), in exactly this order in fp32, and the row keeps its W largest, descending, the lower edge first on ties: cand_edge (-1 where
+    the node has fewer than W children) and cand_total (-inf there).  A dead row gives -1 / -inf and reads no logits.  ``lse`` f32 [R]
+    (optional): the rows' log-sum-exp as given -- on the device it is i2t_rows_lse's value on the same row, bit for bit, which a test
+    hands in here; None: ``_row_lse_host``, the form ``phrase_scores_host`` takes.
+    -> (cand_edge int32 [R, W], cand_total f32 [R, W], fin_total f32 [R], lse f32 [R], 0 at a dead row)"""
+    f32 = np.float32
+    logits = np.asarray(logits, dtype=f32)
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    cand_edge, cand_total = np.full((R, W), -1, dtype=np.int32), np.full((R, W), -np.inf, dtype=f32)
+    fin_total, out_lse = np.full(R, -np.inf, dtype=f32), np.zeros(R, dtype=f32)
+    for r in range(R):
+        nd = int(node[r])
+        if nd < 0 or nd >= trie.nodes:
+            continue
+        z = logits[r, :V]
+        ls = _row_lse_host(z) if lse is None else f32(lse[r])
+        out_lse[r] = ls
+        p = f32(path[r])
+        if trie.term[nd] >= 0:
+            fin_total[r] = f32(p + f32(z[eos] - ls))
+        lo, hi = int(trie.child_off[nd]), int(trie.child_off[nd + 1])
+        tot = {e: f32(p + f32(z[int(trie.child_tok[e])] - ls)) for e in range(lo, hi)}
+        for i, e in enumerate(sorted(tot, key=lambda e: (-tot[e], e))[:W]):
+            cand_edge[r, i], cand_total[r, i] = e, tot[e]
+    return cand_edge, cand_total, fin_total, out_lse
+
+
+def trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie: PhraseTrie, eos: int, ids, hist, pool_phrase, pool_sum,
+                          pool_score, pool_len, pool_n, closed, counters, ctrl, W: int, P: int, longest: int, length_penalty: float,
+                          close_rule: bool = True, gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
+    """One i2t_trie_beam_select call on the host (numpy, in place on the arrays given; fp32 arithmetic in the kernel's order): the
+    normative statement of the selection step of ``search_phrases``.  ``cand_edge`` / ``cand_total`` [R, W] and ``fin_total`` [R]:
+    ``trie_beam_candidates_host``'s; ``node`` int32 [R], ``path`` f32 [R]; ``ids`` int64 [R, ids_ld]; ``hist`` int32 [R, hist_ld]; the
+    pool ``pool_phrase`` int32 / ``pool_sum`` f32 / ``pool_score`` f32 / ``pool_len`` int32 [B, W], ``pool_n`` / ``closed`` int32 [B];
+    ``counters`` = [pos, len], ``ctrl`` = [done, open] (``beam_advance_host`` moves both).  The depth is t = len - P; nothing happens
+    once ctrl[0] is set, for a closed image, or with t outside 0 .. longest or pos outside the history rows.  Per open image:
+      * FINISH: the rows in order; a live row at a node where a phrase ends (term >= 0) offers (term, f = fin_total, s = f /
+        fp32(t + 1) ** fp32(length_penalty), t + 1) -- one fp32 power, one fp32 division; the pool keeps the W best of (pool, offers),
+        descending by s, an entry it holds before a new one of equal score, an earlier offer before a later one;
+      * NEXT ROWS: the W largest child totals of the image's rows, descending, the lower row first and then the lower edge on ties
+        (an absent candidate, edge -1, never ranks); child k takes node child_next[e], path = its total, the token child_tok[e] at
+        ids[row k][len] and hist[row k][pos] = the parent's row behind the parent's history columns [0, pos); rows without a child
+        are dead: node -1, path -inf, the token ``eos`` (a valid id for the next embedding lookup), their own history row;
+      * CLOSE: when no row is live; or (``close_rule``) when the pool holds W and not (best / fp32(Lopt) ** fp32(length_penalty) >
+        pool_score[W - 1]) with best the largest next total and Lopt = longest + 1 for a penalty >= 0, else t + 2.  Log-probs are
+        <= 0 (lse >= max z in fp32 as well, and fp32 addition is monotone), so no continuation of a running row -- its sum at most
+        best, its length between t + 2 and longest + 1 -- can score above that bound: every later offer would be refused by the
+        full pool.  Closing there never changes the pool; it only saves steps (``close_rule`` False shows it);
+      * an image left open sets ctrl[1] = 1.
+    ``gaps`` (a list, optional) receives, per image and step, the W-th next total minus the best child total that was left out by
+    this merge; ``pool_gaps`` the differences between an offer's score and the pool entries beside it."""
+    if ctrl[0]:
+        return
+    pos, ln = int(counters[0]), int(counters[1])
+    t = ln - P
+    R = node.shape[0]
+    B = R // W
+    if t < 0 or t > longest or ln >= ids.shape[1] or pos < 0 or pos >= hist.shape[1]:
+        return
+    f32 = np.float32
+    with np.errstate(all='ignore'):
+        denom = np.power(f32(t + 1), f32(length_penalty)).astype(f32)
+        lopt = np.power(f32(longest + 1 if length_penalty >= 0 else t + 2), f32(length_penalty)).astype(f32)
+    for b in range(B):
+        if closed[b]:
+            continue
+        r0 = b * W
+        m = int(pool_n[b])
+        entries = [(f32(pool_score[b, i]), int(pool_phrase[b, i]), f32(pool_sum[b, i]), int(pool_len[b, i])) for i in range(m)]
+        for w in range(W):
+            nd = int(node[r0 + w])
+            if nd < 0 or nd >= trie.nodes or trie.term[nd] < 0:
+                continue
+            f = f32(fin_total[r0 + w])
+            s = f32(f / denom)
+            at = 0
+            while at < len(entries) and entries[at][0] >= s:
+                at += 1
+            if pool_gaps is not None:
+                pool_gaps.extend(abs(float(entries[i][0]) - float(s)) for i in (at - 1, at) if 0 <= i < len(entries))
+            if at >= W:
+                continue
+            entries.insert(at, (s, int(trie.term[nd]), f, t + 1))
+            del entries[W:]
+        m = len(entries)
+        for i, (s, ph, f, length) in enumerate(entries):
+            pool_score[b, i], pool_phrase[b, i], pool_sum[b, i], pool_len[b, i] = s, ph, f, length
+        pool_n[b] = m
+        flat = [(f32(cand_total[r0 + w, i]), w * W + i, int(cand_edge[r0 + w, i])) for w in range(W) for i in range(W)
+                if int(node[r0 + w]) >= 0 and cand_edge[r0 + w, i] >= 0]
+        flat.sort(key=lambda c: (-c[0], c[1]))
+        children = flat[:W]
+        if gaps is not None and len(flat) > W and np.isfinite(flat[W][0]):
+            gaps.append(float(children[W - 1][0]) - float(flat[W][0]))
+        cl = not children
+        if not cl and close_rule and m == W:
+            with np.errstate(all='ignore'):
+                cl = not (f32(children[0][0] / lopt) > entries[W - 1][0])
+        closed[b] = 1 if cl else 0
+        if not cl:
+            ctrl[1] = 1
+        pars = [r0 + c[1] // W for c in children] + [r0 + k for k in range(len(children), W)]
+        hist[r0:r0 + W, :pos] = hist[pars, :pos]
+        for k in range(W):
+            if k < len(children):
+                tot, _, e = children[k]
+                node[r0 + k], path[r0 + k], ids[r0 + k, ln] = int(trie.child_next[e]), tot, int(trie.child_tok[e])
+            else:
+                node[r0 + k], path[r0 + k], ids[r0 + k, ln] = -1, -np.inf, eos
+            hist[r0 + k, pos] = pars[k]
+
+
+def phrase_beam_search_host(step_logits, prompt, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float,
+                            close_rule: bool = True):
+    """The whole search of ``search_phrases`` for ONE image on the host: ``step_logits(sequence)`` gives the raw fp32 logits row [V] that
+    follows a token sequence (a list of ints, the prompt included).  W rows, each a trie node and an fp32 path sum: row 0 starts at the
+    root with path 0, the others dead.  Depth t = 0, 1, ...: ``trie_beam_candidates_host`` over the live rows, one
+    ``trie_beam_select_host`` call and ``beam_advance_host``; at most longest + 1 steps.  -> SimpleNamespace(phrase_index int64 [N],
+    logprob f32 [N], scores f32 [N], lengths int32 [N]: the first N pool entries; steps; pool_n; gaps, pool_gaps:
+    ``trie_beam_select_host``'s, and in ``gaps`` also, per row, the W-th kept child total minus the best one the row dropped).  A
+    search whose gaps all exceed a perturbation of the totals keeps its phrases and their order under it."""
+    prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
+    P, longest = len(prompt), int(trie.longest)
+    assert P >= 1 and 1 <= N <= W
+    total = P + longest + 1
+    f32, i32 = np.float32, np.int32
+    ids = np.zeros((W, total), dtype=np.int64)
+    ids[:, :P] = prompt
+    hist = np.repeat(np.arange(W, dtype=i32)[:, None], total, axis=1)
+    node, path = np.full(W, -1, dtype=i32), np.zeros(W, dtype=f32)
+    node[0] = 0
+    seqs = [list(prompt)] + [None] * (W - 1)
+    pool_phrase, pool_sum = np.full((1, W), -1, dtype=i32), np.zeros((1, W), dtype=f32)
+    pool_score, pool_len = np.full((1, W), BEAM_DEAD, dtype=f32), np.zeros((1, W), dtype=i32)
+    pool_n, closed = np.zeros(1, dtype=i32), np.zeros(1, dtype=i32)
+    counters, ctrl = np.array([P - 1, P], dtype=i32), np.zeros(2, dtype=i32)
+    gaps, pool_gaps, steps = [], [], 0
+    V = None
+    while steps < longest + 1 and not ctrl[0]:
+        rows = [np.asarray(step_logits(list(seqs[w])), dtype=f32).reshape(-1) if node[w] >= 0 else None for w in range(W)]
+        V = next(z.shape[0] for z in rows if z is not None)
+        logits = np.stack([z if z is not None else np.zeros(V, dtype=f32) for z in rows])
+        cand_edge, cand_total, fin_total, lse = trie_beam_candidates_host(logits, node, path, trie, eos, W)
+        for w in range(W):                                      # what a row's own top W hung on
+            nd = int(node[w])
+            if nd >= 0 and trie.child_off[nd + 1] - trie.child_off[nd] > W:
+                rest = [f32(path[w] + f32(logits[w, int(trie.child_tok[e])] - lse[w])) for e in range(int(trie.child_off[nd]), int(trie.child_off[nd + 1]))
+                        if e not in cand_edge[w].tolist()]
+                gaps.append(float(cand_total[w, W - 1]) - float(max(rest)))
+        before = [(int(node[w]), seqs[w]) for w in range(W)]
+        ln = int(counters[1])
+        trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie, eos, ids, hist, pool_phrase, pool_sum, pool_score,
+                              pool_len, pool_n, closed, counters, ctrl, W, P, longest, length_penalty, close_rule, gaps, pool_gaps)
+        for w in range(W):                                      # the sequence a child row continues: its parent's and its token
+            seqs[w] = before[int(hist[w, counters[0]])][1] + [int(ids[w, ln])] if node[w] >= 0 else None
+        beam_advance_host(counters, ctrl)
+        steps += 1
+    assert int(pool_n[0]) >= N
+    return SimpleNamespace(phrase_index=pool_phrase[0, :N].astype(np.int64), logprob=pool_sum[0, :N].copy(), scores=pool_score[0, :N].copy(),
+                           lengths=pool_len[0, :N].copy(), steps=steps, pool_n=int(pool_n[0]), gaps=gaps, pool_gaps=pool_gaps)

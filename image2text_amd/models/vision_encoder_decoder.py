@@ -153,6 +153,7 @@ class VisionEncoderDecoder(nn.Module):
         object.__setattr__(self, '_captioner', None)
         object.__setattr__(self, '_beam_captioner', None)
         object.__setattr__(self, '_trie_scorer', None)
+        object.__setattr__(self, '_phrase_searcher', None)
         if config.chkpt_path is not None:
             update_state_dict_from_partial_checkpoint(self, config.chkpt_path, map_location=None)
 
@@ -390,6 +391,39 @@ class VisionEncoderDecoder(nn.Module):
         if self._trie_scorer is None:
             object.__setattr__(self, '_trie_scorer', TrieScoreDecoder(self))
         return self._trie_scorer.score(images, prompt_ids.to(next(self.parameters()).device), trie, int(eos_token_id), images_per_pass)
+
+    @torch.no_grad()
+    def search_phrases(self, images, prompt_ids, phrases, eos_token_id, num_beams=4, num_return_sequences=1, length_penalty=0.0, poll_every=8):
+        """The N best phrases of a closed set by beam search on the set's token trie (no counterpart in the reference) ->
+        ``decoding.PhraseBeams(phrase_index [B, N], logprob [B, N], scores [B, N], lengths [B, N], exhaustive)``, best first.
+        ``phrases`` is what ``generate_captions`` and ``score_phrases`` take: K >= 1 token-id sequences (or the ``PhraseTrie`` built of
+        them), one set for all images.  ``num_beams`` = W rows per image walk the trie whatever K is: every step each live row offers
+        its W best children and, at a node that ends a phrase, the phrase itself -- ``logprob`` is the raw log-likelihood of phrase +
+        ``eos_token_id`` after the image's prompt, the quantity ``score`` / ``rerank`` / ``score_phrases`` report --; the W best children
+        of an image run on, the finished phrases collect in a pool of W sorted by ``scores`` = logprob / (tokens + 1) **
+        ``length_penalty`` (0.0, the default: ``score_phrases``' order), and the first ``num_return_sequences`` = N <= W are returned;
+        ``phrase_index`` names a duplicate phrase by its lowest index.  An image stops as soon as no running row can still enter its
+        full pool.  With W at least the widest level of the trie nothing is pruned: ``exhaustive`` is True and the result is the exact
+        top N of the set; below that it is a beam search's approximation at W / (widest level) of ``score_phrases``' rows.  Where the
+        greedy walk of ``generate_captions(phrases=...)`` commits to the first token's argmax and returns one phrase, this call ranks;
+        at W = 1 it is that walk.  Refusals, before anything runs (``caption_plan.check_phrase_search_args``): ValueError for
+        everything ``generate_captions`` refuses about the set itself, W outside 1 .. 8, N outside 1 .. min(W, distinct phrases), a
+        non-finite ``length_penalty``, prompt + longest phrase + 1 past the text window, a negative ``poll_every``; NotImplementedError
+        for a non-causal decoder and for sparse nano-mini blocks.  The call keeps a decoder state of its own."""
+        from ..decoding import PhraseBeamDecoder, check_phrase_search_args, decode_window, takes_long_cache
+        eng = self._engine
+        dc = eng.dec
+        ncls = eng.enc.ncls
+        window = self.decoder.block_size - self.space_for_prompt
+        if dc.causal:
+            window = min(window, decode_window(dc.block, ncls if self.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
+                                               takes_long_cache(dc.llama)))
+        trie, W, N = check_phrase_search_args(phrases, eos_token_id, dc.V, prompt_ids.shape[1], window, num_beams, num_return_sequences,
+                                              length_penalty, poll_every, dc.causal, dc.fam is not None and bool(dc.fam.sparse))
+        if self._phrase_searcher is None:
+            object.__setattr__(self, '_phrase_searcher', PhraseBeamDecoder(self))
+        return self._phrase_searcher.search(images, prompt_ids.to(next(self.parameters()).device), trie, int(eos_token_id), W, N,
+                                            float(length_penalty), int(poll_every))
 
     @torch.no_grad()
     def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:

@@ -900,6 +900,33 @@ def trie_level_expand(tables: TrieLevelTables, lse, path_in, path_out, ids, ids_
                              t.term_phrase, t.n_term, t.n_term_phrases, ids, ids_ld, len_ptr, logprob, logprob.stride(0), int(eos), B, W, V)
 
 
+def trie_beam_candidates(logits, ld, node, path, child_off, child_tok, term, eos, ctrl, cand_edge, cand_total, fin_total, R, W, V, lse=None):
+    """the candidates of search_phrases' step on fp32 logits rows: per live row (node[r] a trie node) the W best children by
+    path + (z[token] - lse) as edge indices and totals, and the total of ending here at a node that ends a phrase; lse (optional, f32
+    [R]) takes the rows' log-sum-exp, rows_lse's value; no write once ctrl[0] (include/i2t.h::i2t_trie_beam_candidates)"""
+    nodes, edges = _trie_args(child_off, child_tok, term)
+    assert node.is_contiguous() and path.is_contiguous() and node.numel() >= R and path.numel() >= R and ctrl.numel() >= 2
+    assert cand_edge.is_contiguous() and cand_total.is_contiguous() and cand_edge.shape == (R, W) and cand_total.shape == (R, W)
+    assert fin_total.is_contiguous() and fin_total.numel() >= R and (lse is None or (lse.is_contiguous() and lse.numel() >= R))
+    assert logits.shape[0] >= R and logits.stride(-1) == 1
+    _k.i2t_trie_beam_candidates(logits, int(ld), node, path, child_off, child_tok, term, nodes, edges, int(eos), ctrl, cand_edge, cand_total,
+                                fin_total, lse, R, W, V)
+
+
+def trie_beam_select(cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, eos, ids, hist, pool_phrase, pool_sum,
+                     pool_score, pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, B, W, P, longest, length_penalty):
+    """the selection step of search_phrases: the rows' offers into the pool of finished phrases, the W best children as the image's next
+    rows (node, path, token, history), the close test (include/i2t.h::i2t_trie_beam_select)"""
+    assert child_tok.is_contiguous() and child_next.is_contiguous() and term.is_contiguous() and child_next.numel() == child_tok.numel()
+    assert cand_edge.is_contiguous() and cand_total.is_contiguous() and cand_edge.shape == (B * W, W) and cand_total.shape == (B * W, W)
+    assert all(t.is_contiguous() and t.numel() == B * W for t in (fin_total, node, path, pool_phrase, pool_sum, pool_score, pool_len))
+    assert pool_n.numel() == B and closed.numel() == B and ctrl.numel() >= 2
+    assert ids.shape[0] == B * W and hist.shape[0] == B * W and ids.stride(-1) == 1 and hist.stride(-1) == 1
+    _k.i2t_trie_beam_select(cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, term.numel(), child_tok.numel(), int(eos),
+                            ids, ids.stride(0), hist, hist.stride(0), pool_phrase, pool_sum, pool_score, pool_len, pool_n, closed, pos_ptr,
+                            len_ptr, ctrl, B, W, int(P), int(longest), float(length_penalty))
+
+
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):
     """(max, sum exp) of every 64-column segment of scale . a . b^T, not the product (include/i2t.h::i2t_gemm_bf16_lse); stats f32 [M, ceil(N/64), 2]"""
     assert a.dtype == BF16 and b.dtype == BF16 and stats.is_contiguous()

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 14
+#define I2T_ABI_VERSION 15
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -519,6 +519,33 @@ int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hidden, const
                           const int* child_parent, const int* child_tok, int n_child, const int* term_row, const int* term_off,
                           const int* term_phrase, int n_term, int n_term_phrases, int64_t* ids, int ids_ld, const int* len_ptr,
                           float* logprob, int lp_ld, int eos, int B, int W, int V);
+/* Beam search over the phrase trie (search_phrases; DESIGN.md 4w, ABI 15): the N best phrases of a set, W <= 8 rows per image (row
+ * b * W + w) whatever the size of the set; every row holds a trie node (node int32 [R], -1 or anything outside [0, nodes): a dead row) and
+ * an fp32 path sum (path [R]).  The trie is the CSR trie above, `nodes` and `edges` what its arrays hold.  No atomics, fixed reduction
+ * orders: both kernels are bit-reproducible.  decoding_host.trie_beam_candidates_host / trie_beam_select_host state them on the host.
+ *   i2t_trie_beam_candidates (after the fp32 lm_head), one workgroup per row: returns at once if ctrl[0].  Per live row of logits f32
+ *     [R][ld] (ld >= V, ld % 4 == 0, bases on 16 bytes): lse = log sum_c exp(z[c]) over the RAW row in i2t_rows_lse's order, bit-equal to
+ *     that entry point (written to lse[r] when `lse` is given); fin_total[r] = path[r] + (z[eos] - lse) when term[node[r]] >= 0, else
+ *     -inf; every edge e of the node has total = path[r] + (z[child_tok[e]] - lse), in this order in fp32, and cand_edge [R][W] /
+ *     cand_total [R][W] take the W largest, descending, the lower edge first on ties (-1 / -inf where the node has fewer than W
+ *     children).  A dead row writes -1 / -inf / -inf and reads no logits.  Any fan-out from 0 to V - 1.  1 <= W <= 8, 0 <= eos < V.
+ *   i2t_trie_beam_select, one workgroup per image: returns at once if ctrl[0] or closed[b]; with t = *len_ptr - P outside 0 .. longest,
+ *     *len_ptr >= ids_ld or *pos_ptr outside [0, hist_ld) nothing is written.  In row order, a live row whose node ends a phrase offers
+ *     (term[node], f = fin_total, s = f / powf(t + 1, length_penalty), t + 1) to the image's pool pool_phrase / pool_sum / pool_score /
+ *     pool_len [B][W] (pool_n [B] entries, descending by score): the pool keeps the W best, an entry it holds before a new one of equal
+ *     score.  The W largest candidates of the image's rows (descending, the lower row first, then the lower edge on ties) become rows
+ *     0 .. of the image: node = child_next[e], path = the total, ids[row][*len_ptr] = child_tok[e], hist[row][*pos_ptr] = the parent's
+ *     row behind the parent's history columns [0, *pos_ptr); a row without a candidate is dead: node -1, path -inf, token eos, its own
+ *     history row.  closed[b] = 1 when no row is live, or when the pool holds W and not (best next total / powf(Lopt, length_penalty) >
+ *     pool_score[b][W - 1]), Lopt = longest + 1 for a penalty >= 0, else t + 2; an image left open stores 1 into ctrl[1].
+ *     i2t_beam_advance moves the counters.  1 <= W <= 8, P >= 1, longest >= 1, P + longest + 1 <= ids_ld, a finite length_penalty. */
+int i2t_trie_beam_candidates(void* stream, const float* logits, int ld, const int* node, const float* path, const int* child_off,
+                             const int* child_tok, const int* term, int nodes, int edges, int eos, const int* ctrl, int* cand_edge,
+                             float* cand_total, float* fin_total, float* lse, int R, int W, int V);
+int i2t_trie_beam_select(void* stream, const int* cand_edge, const float* cand_total, const float* fin_total, int* node, float* path,
+                         const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos, int64_t* ids, int ids_ld,
+                         int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len, int* pool_n, int* closed,
+                         const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P, int longest, float length_penalty);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).
