@@ -425,12 +425,15 @@ def check_beam_caption_args(num_beams, num_return_sequences, length_penalty, ear
 
 # ------------------------------------------------------------------------------------------------ one plan per call
 class CaptionFacts(NamedTuple):
-    """What ``plan_captions`` needs to know of the model."""
+    """What ``plan_captions`` and the checks of the phrase calls need to know of the model."""
     V: int                              # the vocabulary
     causal: bool                        # False: no cache, the call runs by re-evaluation
     fam: object                         # the nano-mini family's spec, as ``prefill_plan`` takes it (None: a dense or Llama-family decoder)
     window: int                         # the text window: decoder.block_size - space_for_prompt
     prefix: int                         # the soft-prompt rows at the head of the cache: min(ncls, block) when the decoder is prefixed, else 0
+    # what ``check_phrase_score_args`` / ``check_phrase_search_args`` take (``plan_captions`` reads neither; the defaults are a hand-made record's)
+    cache_window: Optional[int] = None  # min(window, decode_window) on a causal decoder, else window
+    sparse: bool = False                # sparse nano-mini decoder blocks
 
 
 class CaptionPlan(NamedTuple):

@@ -115,9 +115,11 @@ class GreedyDecoder:
         st.hid = e(B, d)
         st.logits = e(B, dc.Vp, dtype=F32)                      # rows padded to 8 columns: 16-byte aligned rows for the GEMM epilogue
         st.margin = e(B, dtype=F32)
+        st.top2 = st.seg_se = None          # the segment-maxima head's buffers, made at the first step that takes it (_greedy_head)
         # fp32 planes of the deterministic split-K GEMM form (ops.gemm(workspace=...)): the step's GEMMs with few output tiles and a
         # long K (attention / MLP output projections at anything but the largest caption batches) spread over K slices
         st.ws = torch.empty(16 << 20, dtype=F32, device=dev)
+        st.attn_ws = None                   # a long state's chunk partials (below)
         if dc.llama is not None:
             ls = dc.llama
             st.qkv, st.ao, st.gu = e(B, (ls.H + 2 * ls.Hkv) * ls.hd), e(B, ls.H * ls.hd), e(B, 2 * ff)
@@ -130,7 +132,8 @@ class GreedyDecoder:
             st.vc = [e(B, st.clen, d) for _ in range(dc.L)]
         S = ncls
         st.cross_kv = {l: (e(mem_rows or B, S, 2 * d), S) for l in self._cross_layers()}
-        st.hist = None                      # beam search: int32 [B][clen] history table (BeamDecoder), None: row b's keys are row b's
+        st.hist = st.hist_init = None       # beam search: int32 [B][clen] history table (BeamDecoder), None: row b's keys are row b's
+        st.ctrl = None                      # int32 [done, unfinished]: the modes that stop early (_reset clears it, _replay polls it)
         st.mem_div = 1                      # rows per cross-attention memory row
         if dc.fam is not None:
             self._build_family(st, e)
@@ -248,23 +251,30 @@ class GreedyDecoder:
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         B, d = st.B, dc.d
         len_ptr = st.counters[1:2]
-        self._body(st)
-        if with_head:
+        if not with_head:
+            self._body(st)
+        elif top2 and sampling is None:
+            # greedy, nobody asked for margins: the lm_head leaves the two largest logits of every 64-column segment of a row
+            # instead of the row (51 MB instead of 823 MB written and read back at 4096 captions), the ban + argmax merges them
+            self._body(st)
             self._final_norm(st)
-            if top2 and sampling is None:
-                # greedy, nobody asked for margins: the lm_head leaves the two largest logits of every 64-column segment of a row
-                # instead of the row (51 MB instead of 823 MB written and read back at 4096 captions), the ban + argmax merges them
-                ops.gemm_top2(st.hid, a.W(eng.n_head), st.top2, B, dc.V, d)
-                ops.top2_ngram_argmax(st.top2, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, d)
-                ops.advance(st.counters, 1)
-                return
-            ops.gemm(st.hid, a.W(eng.n_head), st.logits, B, dc.V, d, workspace=st.ws)
+            ops.gemm_top2(st.hid, a.W(eng.n_head), st.top2, B, dc.V, d)
+            ops.top2_ngram_argmax(st.top2, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, d)
+        else:
+            self._logits_head(st)
             if sampling is None:
                 ops.ngram_ban_argmax(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V, st.margin)
             else:
                 ops.sample_token(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, st.ngrams.numel(), B, dc.V,
                                  sampling.temperature, sampling.top_k, sampling.nucleus_p, st.seed, dist_out=st.dist)
         ops.advance(st.counters, 1)                            # pos and len together
+
+    def _logits_head(self, st):
+        """The step up to its raw logits, for every mode that reads the whole row: _body, _final_norm, the fp32 lm_head into st.logits."""
+        self._body(st)
+        self._final_norm(st)
+        dc = self.eng.dec
+        ops.gemm(st.hid, self.eng.arena.W(self.eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
 
     def _body(self, st):
         """Embedding of the token at ids[:, len - 1] and the decoder blocks at position pos: st.x holds the new hidden rows."""
@@ -421,12 +431,53 @@ class GreedyDecoder:
         buffers are made at the first such call, with the segment sums beside them when the step takes the token's log-prob (``lse``)."""
         dc = self.eng.dec
         top2 = sampling is None and not logits and TOP2_HEAD and dc.d % 128 == 0
-        if top2 and getattr(st, 'top2', None) is None:
+        if top2 and st.top2 is None:
             nseg = (dc.V + 63) // 64
             st.top2 = torch.zeros(st.B, nseg, 4, dtype=F32, device=st.arena.device)
             if lse:
                 st.seg_se = torch.zeros(st.B, nseg, dtype=F32, device=st.arena.device)
         return top2, ('greedy_top2' if top2 else 'greedy') if sampling is None else sampling.key()
+
+    @staticmethod
+    def _drop_graphs(st, tag):
+        """Forget the captured steps that hold a buffer about to be replaced: those whose key is a tuple that starts with ``tag``, or --
+        tag None -- ``generate``'s sampling steps, every key but None / 'greedy' / 'greedy_top2'."""
+        stale = (lambda k: k not in (None, 'greedy', 'greedy_top2')) if tag is None else (lambda k: isinstance(k, tuple) and k[:1] == (tag,))
+        st.graphs = {k: g for k, g in st.graphs.items() if not stale(k)}
+
+    def _upload_trie(self, st, trie: PhraseTrie, tag: str, fanout: bool = False):
+        """The trie into st.trie = (child_off, child_tok, child_next, term): persistent because captured steps bake their pointers, and
+        regrown -- together with the graphs tagged ``tag`` -- only when the trie does not fit.  The kernels take the arrays' CAPACITIES as
+        nodes / edges, so a captured step serves any trie that fits; the trie's contents are copied in per call, the spare nodes
+        childless and ending no phrase.  ``fanout``: st.kept, f32 [B, widest fan-out + 1 in whole 4s], is kept and regrown with them."""
+        dev = st.arena.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges \
+                or (fanout and st.kept.shape[1] < trie.max_fanout + 1):
+            nodes, edges = max(64, trie.nodes), max(64, trie.edges)
+            st.trie = (torch.zeros(nodes + 1, **i32), torch.zeros(edges, **i32), torch.zeros(edges, **i32), torch.full((nodes,), -1, **i32))
+            if fanout:
+                st.kept = torch.zeros(st.B, (max(64, trie.max_fanout + 1) + 3) // 4 * 4, dtype=F32, device=dev)
+            self._drop_graphs(st, tag)
+        nodes, edges = st.trie[3].numel(), st.trie[1].numel()
+        off = np.full(nodes + 1, trie.edges, dtype=np.int32)
+        off[:trie.nodes + 1] = trie.child_off
+        tok, nxt, term = np.zeros(edges, dtype=np.int32), np.zeros(edges, dtype=np.int32), np.full(nodes, -1, dtype=np.int32)
+        tok[:trie.edges], nxt[:trie.edges], term[:trie.nodes] = trie.child_tok, trie.child_next, trie.term
+        for buf, host in zip(st.trie, (off, tok, nxt, term)):
+            buf.copy_(torch.from_numpy(host))
+
+    @staticmethod
+    def _reset(st, prompt_rows, P: int, start=None):
+        """What every mode's loop starts from: the prompt in the id buffer, the counters at ``start`` (default st.counters_init) and, in
+        the states that have them, the identity history table and a cleared control word."""
+        st.ids.zero_()
+        st.ids[:, :P] = prompt_rows
+        st.counters.copy_(st.counters_init if start is None else start)      # device-to-device: no host sync in the loop
+        if st.hist is not None:
+            st.hist.copy_(st.hist_init)
+        if st.ctrl is not None:
+            st.ctrl.zero_()
 
     def _replay(self, st, full_key, full_step, reset, n_prefill: int, n_full: int, use_graph: bool, each=None, poll_every: int = 0,
                 prefill_first: bool = False) -> int:
@@ -578,13 +629,9 @@ class GreedyDecoder:
             _draw_seed(st.seed, sampling.seed)
             if return_dists != (st.dist is not None):         # captured sampling steps bake the dist pointer (or its absence)
                 st.dist = torch.zeros(B, dc.V, dtype=F32, device=a.device) if return_dists else None
-                st.graphs = {k: g for k, g in st.graphs.items() if k in (None, 'greedy', 'greedy_top2')}
+                self._drop_graphs(st, None)
         top2, full_key = self._greedy_head(st, sampling, logits=return_margins)
-
-        def reset():
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_ids
-            st.counters.copy_(st.counters_init)                 # device-to-device: no host sync in the loop
+        reset = lambda: self._reset(st, prompt_ids, P)
         margins = torch.zeros(max_new_tokens, B, dtype=F32, device=a.device) if return_margins else None
         dists = torch.zeros(max_new_tokens, B, dc.V, dtype=F32, device=a.device) if return_dists else None
         keep = (lambda i: margins[i].copy_(st.margin)) if return_margins else (lambda i: dists[i].copy_(st.dist)) if return_dists else None
@@ -627,12 +674,29 @@ class BeamDecoder(GreedyDecoder):
         st.beam_ngrams = torch.tensor(list(spec.ngram_sizes), **i32)
         return st
 
+    @staticmethod
+    def _build_pool(st, B: int, W: int, ids_ld: Optional[int] = None):
+        """The finished pool of a mode that keeps one (CaptionBeamDecoder, PhraseBeamDecoder), W entries per image: the score they are
+        sorted by, the raw sum, the length, the count, and the image's closed flag.  ``ids_ld``: also the entries' id and token
+        log-prob rows (captions)."""
+        dev = st.arena.device
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=F32, device=dev)
+        st.pool_score, st.pool_sum = torch.zeros(B, W, **f32), torch.zeros(B, W, **f32)
+        st.pool_len, st.pool_n, st.closed = torch.zeros(B, W, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        if ids_ld is not None:
+            st.pool_ids, st.pool_lp = torch.zeros(B, W, ids_ld, dtype=torch.long, device=dev), torch.zeros(B, W, ids_ld, **f32)
+
+    @staticmethod
+    def _reset_pool(st):
+        """an empty pool and every image open (the mode's own pool rows -- ids, phrases -- are its reset's)"""
+        st.pool_score.fill_(BEAM_DEAD)
+        for buf in (st.pool_sum, st.pool_len, st.pool_n, st.closed):
+            buf.zero_()
+
     def _beam_step(self, st):
-        eng, a, dc, sp = self.eng, self.eng.arena, self.eng.dec, st.spec
+        dc, sp = self.eng.dec, st.spec
         pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
-        self._body(st)
-        self._final_norm(st)
-        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        self._logits_head(st)
         ops.beam_candidates(st.logits, st.ids, len_ptr, st.ctrl, st.beam_ngrams, st.B, dc.V, sp.expansion, sp.temperature, sp.top_k,
                             sp.eos, sp.log_boost, st.seed, st.cand_tok, st.cand_lp, st.raw_tok)
         ops.beam_consolidate(st.cand_tok, st.cand_lp, st.scores, st.ids, st.hist, st.has_eos, st.parent, pos_ptr, len_ptr, st.ctrl,
@@ -661,7 +725,7 @@ class BeamDecoder(GreedyDecoder):
         window = decode_window(*self._cache_args())
         assert total <= window, f'prompt + new tokens ({total}) exceed the text window ({window})'
         st = self._state_for(R, total, lambda clen: self._build_beam(B, spec, max(total, dc.block), record, clen),
-                             lambda st: (getattr(st, 'W', None) == W and st.spec.key() == spec.key() and (st.raw_tok is not None) == record))
+                             lambda st: st.W == W and st.spec.key() == spec.key() and (st.raw_tok is not None) == record)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
         if spec.eos is not None and bool((prompt_ids == spec.eos).any(dim=-1).all()):
             ids = prompt_rows.view(B, W, P).clone()          # every beam already holds EOS: nothing to do
@@ -670,12 +734,8 @@ class BeamDecoder(GreedyDecoder):
         _draw_seed(st.seed, seed)
 
         def reset():
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_rows
-            st.counters.copy_(st.counters_init)
-            st.hist.copy_(st.hist_init)
+            self._reset(st, prompt_rows, P)
             st.scores.zero_()
-            st.ctrl.zero_()
             if spec.eos is None:
                 st.has_eos.zero_()
             else:
@@ -714,7 +774,6 @@ class CaptionDecoder(GreedyDecoder):
         st.ctrl = torch.zeros(2, **i32)                         # [done, unfinished rows]
         st.finished, st.lengths = torch.zeros(R, **i32), torch.zeros(R, **i32)
         st.tok_lp = torch.zeros(R, ids_ld, dtype=F32, device=dev)
-        st.top2 = st.seg_se = None
         st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
         st.raw_lse = st.saved = st.suppress = None              # logits processors: f32 [R] / f32 [R, ids_ld] / int32 list, made at the first active call
         st.node = st.phrase_index = st.kept = st.trie = None    # phrases: int32 [R] / int32 [R] / f32 [R, fan-out + 1] / the four trie arrays (and raw_lse)
@@ -732,33 +791,20 @@ class CaptionDecoder(GreedyDecoder):
         n = len(proc.suppress)
         if st.suppress is None or st.suppress.numel() < n:
             st.suppress = torch.zeros(max(64, n), dtype=torch.int32, device=dev)
-            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'proc')}
+            self._drop_graphs(st, 'proc')
         if n:
             st.suppress[:n].copy_(torch.tensor(proc.suppress, dtype=torch.int32))
 
     def _trie_state(self, st, trie: PhraseTrie):
         """The buffers of a phrase-constrained step, persistent because captured steps bake their pointers: st.node,
-        st.phrase_index, st.raw_lse, and -- regrown only together with the graphs that hold them -- st.kept and the four trie arrays
-        st.trie = (child_off, child_tok, child_next, term).  The kernels take the arrays' CAPACITIES as nodes / edges, so a captured step
-        serves any trie that fits; the trie's contents are copied in per call, the spare nodes childless and ending no phrase."""
+        st.phrase_index, st.raw_lse, and the trie with st.kept beside it (_upload_trie), under the graph tag 'trie'."""
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         if st.node is None:
             st.node, st.phrase_index = torch.zeros(st.B, **i32), torch.full((st.B,), -1, **i32)
         if st.raw_lse is None:                                  # (shared with the logits processors: _processor_state)
             st.raw_lse = torch.zeros(st.B, dtype=F32, device=dev)
-        if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges or st.kept.shape[1] < trie.max_fanout + 1:
-            nodes, edges = max(64, trie.nodes), max(64, trie.edges)
-            st.trie = (torch.zeros(nodes + 1, **i32), torch.zeros(edges, **i32), torch.zeros(edges, **i32), torch.full((nodes,), -1, **i32))
-            st.kept = torch.zeros(st.B, (max(64, trie.max_fanout + 1) + 3) // 4 * 4, dtype=F32, device=dev)
-            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'trie')}
-        nodes, edges = st.trie[3].numel(), st.trie[1].numel()
-        off = np.full(nodes + 1, trie.edges, dtype=np.int32)
-        off[:trie.nodes + 1] = trie.child_off
-        tok, nxt, term = np.zeros(edges, dtype=np.int32), np.zeros(edges, dtype=np.int32), np.full(nodes, -1, dtype=np.int32)
-        tok[:trie.edges], nxt[:trie.edges], term[:trie.nodes] = trie.child_tok, trie.child_next, trie.term
-        for buf, host in zip(st.trie, (off, tok, nxt, term)):
-            buf.copy_(torch.from_numpy(host))
+        self._upload_trie(st, trie, 'trie', fanout=True)
 
     def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None,
                       trie: bool = False):
@@ -772,14 +818,14 @@ class CaptionDecoder(GreedyDecoder):
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
         nn = 0 if trie else st.ngrams.numel()
-        self._body(st)
-        self._final_norm(st)
         if top2:
+            self._body(st)
+            self._final_norm(st)
             ops.gemm_top2_lse(st.hid, a.W(eng.n_head), st.top2, st.seg_se, R, dc.V, d)
             ops.top2_ngram_argmax_lp(st.top2, st.seg_se, st.hid, a.W(eng.n_head), st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, d, done,
                                      st.tok_lp)
         else:
-            ops.gemm(st.hid, a.W(eng.n_head), st.logits, R, dc.V, d, workspace=st.ws)
+            self._logits_head(st)
             if proc is not None:
                 pr, P = proc
                 ops.caption_logits_process(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, None if forced is None else forced[1], P, st.N,
@@ -885,10 +931,7 @@ class CaptionDecoder(GreedyDecoder):
         prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
-            st.ids.zero_()
-            st.ids[:, :pmax] = prompt_rows
-            st.counters.copy_(start)                            # device-to-device: no host sync in the loop
-            st.ctrl.zero_()
+            self._reset(st, prompt_rows, pmax, start)
             st.finished.zero_()
             # what a row without an EOS ends with: p_b + max_new_tokens
             st.lengths.copy_(len_rows) if ragged else st.lengths.fill_(total)
@@ -924,23 +967,16 @@ class CaptionBeamDecoder(BeamDecoder):
         spec = BeamSpec(W, 2 * W, 0.0, None, 0.0, None, 0.0, tuple(int(n) for n in self.model.config.no_repeat_n_grams))
         st = self._build_beam(B, spec, ids_ld, False, clen)
         dev = st.arena.device
-        i32 = dict(dtype=torch.int32, device=dev)
         st.tok_lp = torch.zeros(B * W, ids_ld, dtype=F32, device=dev)
-        st.pool_ids = torch.zeros(B, W, ids_ld, dtype=torch.long, device=dev)
-        st.pool_lp = torch.zeros(B, W, ids_ld, dtype=F32, device=dev)
-        st.pool_score, st.pool_sum = torch.zeros(B, W, dtype=F32, device=dev), torch.zeros(B, W, dtype=F32, device=dev)
-        st.pool_len, st.pool_n, st.closed = torch.zeros(B, W, **i32), torch.zeros(B, **i32), torch.zeros(B, **i32)
+        self._build_pool(st, B, W, ids_ld)
         st.scores_init = torch.full((B, W), BEAM_DEAD, dtype=F32, device=dev)
         st.scores_init[:, 0] = 0.0
-        st.caption_beam = True
         return st
 
     def _caption_beam_step(self, st, P: int, max_new: int, eos, pad: int, length_penalty: float, early_stopping: bool):
-        eng, a, dc, sp = self.eng, self.eng.arena, self.eng.dec, st.spec
+        dc, sp = self.eng.dec, st.spec
         pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
-        self._body(st)
-        self._final_norm(st)
-        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        self._logits_head(st)
         ops.beam_candidates(st.logits, st.ids, len_ptr, st.ctrl, st.beam_ngrams, st.B, dc.V, sp.expansion, 0.0, None, None, 0.0, st.seed,
                             st.cand_tok, st.cand_lp, None)
         ops.beam_pool_select(st.cand_tok, st.cand_lp, st.scores, st.ids, st.hist, st.tok_lp, st.pool_ids, st.pool_lp, st.pool_score,
@@ -976,25 +1012,17 @@ class CaptionBeamDecoder(BeamDecoder):
             return GeneratedCaptions(prompt_ids[:, None].expand(B, N, P).clone(), torch.full((B, N), P, dtype=torch.int32, device=a.device),
                                      zero, zero.sum(dim=-1), None, torch.zeros(B, N, dtype=F32, device=a.device))
         st = self._state_for(R, total, lambda clen: self._build_caption_beam(B, W, max(total, dc.block), clen),
-                             lambda st: getattr(st, 'caption_beam', False) and st.W == W)
+                             lambda st: st.W == W)
         self._prepare_inputs(st, images, B, W)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
 
         def reset():
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_rows
-            st.counters.copy_(st.counters_init)
-            st.hist.copy_(st.hist_init)
+            self._reset(st, prompt_rows, P)
             st.scores.copy_(st.scores_init.view(-1))
-            st.ctrl.zero_()
             st.tok_lp.zero_()
             st.pool_ids.fill_(pad)
             st.pool_lp.zero_()
-            st.pool_score.fill_(BEAM_DEAD)
-            st.pool_sum.zero_()
-            st.pool_len.zero_()
-            st.pool_n.zero_()
-            st.closed.zero_()
+            self._reset_pool(st)
         # P, max_new_tokens, eos, pad and the two beam arguments are kernel arguments: a captured step holds them
         key = ('caption_beam', P, max_new_tokens, -1 if eos is None else int(eos), pad, length_penalty, early_stopping)
         self.last_replays = self._replay(st, key, lambda: self._caption_beam_step(st, P, max_new_tokens, eos, pad, length_penalty,
@@ -1035,7 +1063,7 @@ class TrieScoreDecoder(BeamDecoder):
             kvw = dc.d
         return 2 * dc.L * clen * kvw * 2 + dc.Vp * 4 + 2 * clen * 4 + ids_ld * 8 + (dc.V + 63) // 64 * 8 + (16 * dc.d + 3 * dc.ff) * 4
 
-    def _build_trie_score(self, B: int, W: int, ids_ld: int, clen: int):
+    def _build_score(self, B: int, W: int, ids_ld: int, clen: int):
         R = B * W
         st = self._build(R, ids_ld, mem_rows=B, clen=clen)
         dev, dc = st.arena.device, self.eng.dec
@@ -1050,7 +1078,6 @@ class TrieScoreDecoder(BeamDecoder):
             st.stats = torch.zeros(R, (dc.V + 63) // 64, 2, dtype=F32, device=dev)
             st.no_label = torch.full((R,), -100, dtype=torch.long, device=dev)
             st.no_lp = torch.zeros(R, dtype=F32, device=dev)
-        st.trie_score = True
         return st
 
     def _encode_all(self, st, images, B: int):
@@ -1082,15 +1109,15 @@ class TrieScoreDecoder(BeamDecoder):
     def _level_step(self, st, tables, t: int, eos: int, logprob):
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, V, d = st.B, dc.V, dc.d
-        self._body(st)
-        self._final_norm(st)
         head = a.W(eng.n_head)
         if st.lse_route:
+            self._body(st)
+            self._final_norm(st)
             ops.gemm_lse(st.hid, head, st.stats, R, V, d)
             ops.lse_token_logprob(st.stats, st.hid, head, st.no_label, st.lse, st.no_lp, R, V, d, ignore_index=-100)
             z = dict(hidden=st.hid, w_head=head, d=d)
         else:
-            ops.gemm(st.hid, head, st.logits, R, V, d, workspace=st.ws)
+            self._logits_head(st)
             ops.rows_lse(st.logits, dc.Vp, st.lse, R, V)
             z = dict(logits=st.logits, ld=dc.Vp)
         ops.trie_level_expand(tables, st.lse, st.path[t & 1], st.path[(t + 1) & 1], st.ids, st.ids_ld, st.counters[1:2], logprob, eos,
@@ -1123,7 +1150,7 @@ class TrieScoreDecoder(BeamDecoder):
         st = self._score_state
         if not self._reusable(st, Bp * W, total, lambda st: st.W == W and st.images == Bp and st.clen >= clen):
             self._score_state = st = None                       # the old buffers go before the new ones are made
-            self._score_state = st = self._build_trie_score(Bp, W, ids_ld, clen)
+            self._score_state = st = self._build_score(Bp, W, ids_ld, clen)
         assert total <= st.tmax
         # every level's tables, checked on the host and uploaded once per call
         tables = [ops.trie_level_tables(*level_expand_tables(trie, levels, t), W, dc.V, K, dev) for t in range(trie.longest + 1)]
@@ -1137,10 +1164,7 @@ class TrieScoreDecoder(BeamDecoder):
             n = min(Bp, B - i)
             take = torch.arange(i, i + Bp, device=dev).clamp(max=B - 1)         # a short last group is filled with its last image
             self._load_group(st, pre, take)
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_ids[take].repeat_interleave(W, dim=0)
-            st.counters.copy_(st.counters_init)
-            st.hist.copy_(st.hist_init)
+            self._reset(st, prompt_ids[take].repeat_interleave(W, dim=0), P)
             st.path[0].zero_()
             part.zero_()
             for _ in range(P - 1):                              # prompt tokens before the last: fill the cache only
@@ -1166,7 +1190,7 @@ class PhraseBeamDecoder(BeamDecoder):
     set.  A step is _body -> _final_norm -> fp32 lm_head -> i2t_trie_beam_candidates (every live row's W best children and the total of
     ending at its node) -> i2t_trie_beam_select (the pool of finished phrases, the image's next rows, the close test) ->
     i2t_beam_advance.  Every row carries its trie node and path sum in device memory; the trie lives in device buffers the step only
-    points at, sized by capacity as in CaptionDecoder._trie_state, so a captured step serves any set that fits.  The decoder keeps its
+    points at, sized by capacity (_upload_trie), so a captured step serves any set that fits.  The decoder keeps its
     own state; its graph key is ('phrase_beam', ...)."""
 
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
@@ -1179,36 +1203,16 @@ class PhraseBeamDecoder(BeamDecoder):
         st.node, st.path, st.fin_total = torch.zeros(R, **i32), torch.zeros(R, **f32), torch.zeros(R, **f32)
         st.node_init = torch.full((B, W), -1, **i32)
         st.node_init[:, 0] = 0
-        st.pool_phrase, st.pool_len = torch.zeros(B, W, **i32), torch.zeros(B, W, **i32)
-        st.pool_sum, st.pool_score = torch.zeros(B, W, **f32), torch.zeros(B, W, **f32)
-        st.pool_n, st.closed = torch.zeros(B, **i32), torch.zeros(B, **i32)
-        st.trie = None
-        st.phrase_beam = True
+        self._build_pool(st, B, W)
+        st.pool_phrase = torch.zeros(B, W, **i32)
+        st.trie = None                      # (child_off, child_tok, child_next, term), made at the first call (_upload_trie)
         return st
 
-    def _load_trie(self, st, trie: PhraseTrie):
-        """the trie into st.trie = (child_off, child_tok, child_next, term), regrown -- with the graphs that hold their pointers -- when
-        it does not fit; spare nodes are childless and end no phrase"""
-        i32 = dict(dtype=torch.int32, device=st.arena.device)
-        if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges:
-            nodes, edges = max(64, trie.nodes), max(64, trie.edges)
-            st.trie = (torch.zeros(nodes + 1, **i32), torch.zeros(edges, **i32), torch.zeros(edges, **i32), torch.full((nodes,), -1, **i32))
-            st.graphs = {k: g for k, g in st.graphs.items() if not (isinstance(k, tuple) and k and k[0] == 'phrase_beam')}
-        nodes, edges = st.trie[3].numel(), st.trie[1].numel()
-        off = np.full(nodes + 1, trie.edges, dtype=np.int32)
-        off[:trie.nodes + 1] = trie.child_off
-        tok, nxt, term = np.zeros(edges, dtype=np.int32), np.zeros(edges, dtype=np.int32), np.full(nodes, -1, dtype=np.int32)
-        tok[:trie.edges], nxt[:trie.edges], term[:trie.nodes] = trie.child_tok, trie.child_next, trie.term
-        for buf, host in zip(st.trie, (off, tok, nxt, term)):
-            buf.copy_(torch.from_numpy(host))
-
     def _phrase_beam_step(self, st, P: int, eos: int, longest: int, length_penalty: float):
-        eng, a, dc = self.eng, self.eng.arena, self.eng.dec
+        dc = self.eng.dec
         pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
         off, tok, nxt, term = st.trie
-        self._body(st)
-        self._final_norm(st)
-        ops.gemm(st.hid, a.W(eng.n_head), st.logits, st.B, dc.V, dc.d, workspace=st.ws)
+        self._logits_head(st)
         ops.trie_beam_candidates(st.logits, dc.Vp, st.node, st.path, off, tok, term, eos, st.ctrl, st.cand_tok, st.cand_lp, st.fin_total,
                                  st.B, st.W, dc.V)
         ops.trie_beam_select(st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist, st.pool_phrase,
@@ -1229,25 +1233,17 @@ class PhraseBeamDecoder(BeamDecoder):
         longest, length_penalty = int(trie.longest), float(length_penalty)
         R, total = B * W, P + longest + 1
         st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
-                             lambda st: getattr(st, 'phrase_beam', False) and st.W == W)
-        self._load_trie(st, trie)
+                             lambda st: st.W == W)
+        self._upload_trie(st, trie, 'phrase_beam')
         self._prepare_inputs(st, images, B, W)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
 
         def reset():
-            st.ids.zero_()
-            st.ids[:, :P] = prompt_rows
-            st.counters.copy_(st.counters_init)
-            st.hist.copy_(st.hist_init)
-            st.ctrl.zero_()
+            self._reset(st, prompt_rows, P)
             st.node.copy_(st.node_init.view(-1))
             st.path.zero_()
             st.pool_phrase.fill_(-1)
-            st.pool_score.fill_(BEAM_DEAD)
-            st.pool_sum.zero_()
-            st.pool_len.zero_()
-            st.pool_n.zero_()
-            st.closed.zero_()
+            self._reset_pool(st)
         # P, eos, longest and the penalty are kernel arguments: a captured step holds them (W is the state's)
         key = ('phrase_beam', P, W, int(eos), longest, length_penalty)
         self.last_replays = self._replay(st, key, lambda: self._phrase_beam_step(st, P, int(eos), longest, length_penalty), reset, P - 1,
@@ -1257,11 +1253,12 @@ class PhraseBeamDecoder(BeamDecoder):
 
 
 def caption_facts(model) -> CaptionFacts:
-    """what ``plan_captions`` needs to know of ``model``"""
-    eng = model._engine
-    dc = eng.dec
-    return CaptionFacts(dc.V, dc.causal, dc.fam, model.decoder.block_size - model.space_for_prompt,
-                        min(eng.enc.ncls, dc.block) if dc.prefixed else 0)
+    """what ``plan_captions`` and the phrase calls' checks need to know of ``model``"""
+    dc = model._engine.dec
+    block, off, prefix, llama = GreedyDecoder(model)._cache_args()
+    window = model.decoder.block_size - model.space_for_prompt
+    return CaptionFacts(dc.V, dc.causal, dc.fam, window, prefix, min(window, decode_window(block, off, prefix, llama)) if dc.causal else window,
+                        dc.fam is not None and bool(dc.fam.sparse))
 
 
 def _draw_seed(buf: torch.Tensor, seed: Optional[int]):

@@ -149,11 +149,8 @@ class VisionEncoderDecoder(nn.Module):
             raise ValueError('Misconfigured!!! Need to either use cross attn or soft prompting or both')
         object.__setattr__(self, '_engine', HotPath(self))
         object.__setattr__(self, '_hook', None)
-        object.__setattr__(self, '_greedy', None)
-        object.__setattr__(self, '_captioner', None)
-        object.__setattr__(self, '_beam_captioner', None)
-        object.__setattr__(self, '_trie_scorer', None)
-        object.__setattr__(self, '_phrase_searcher', None)
+        for slot in ('_greedy', '_captioner', '_beam_captioner', '_trie_scorer', '_phrase_searcher'):      # the decoding drivers (_decoder)
+            object.__setattr__(self, slot, None)
         if config.chkpt_path is not None:
             update_state_dict_from_partial_checkpoint(self, config.chkpt_path, map_location=None)
 
@@ -169,6 +166,12 @@ class VisionEncoderDecoder(nn.Module):
         if self._hook is None or self._hook.device != device:
             object.__setattr__(self, '_hook', torch.zeros(1, device=device, requires_grad=True))
         return self._hook
+
+    def _decoder(self, slot: str, cls):
+        """the decoding driver kept in ``slot``, made at the first call that has passed its refusals"""
+        if getattr(self, slot) is None:
+            object.__setattr__(self, slot, cls(self))
+        return getattr(self, slot)
 
     def _check_mask(self, attn_msk, bs: int, L: int):
         """The reference expands the mask (einops ``repeat``, :61-72) and then loses it (bool masked_fill, :97-98):
@@ -233,11 +236,10 @@ class VisionEncoderDecoder(nn.Module):
         if not self._engine.dec.causal:      # bidirectional attention: every new token changes the state of the earlier ones
             return generate_by_recompute(self, images, prompt_ids, max_new_tokens,
                                          None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p))
-        if self._greedy is None:
-            object.__setattr__(self, '_greedy', GreedyDecoder(self))
+        greedy = self._decoder('_greedy', GreedyDecoder)
         if top_k == 1 and nucleus_p is None:
-            return self._greedy.generate(images, prompt_ids, max_new_tokens)
-        return self._greedy.generate(images, prompt_ids, max_new_tokens, sampling=Sampling(temperature, top_k, nucleus_p))
+            return greedy.generate(images, prompt_ids, max_new_tokens)
+        return greedy.generate(images, prompt_ids, max_new_tokens, sampling=Sampling(temperature, top_k, nucleus_p))
 
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
@@ -333,13 +335,9 @@ class VisionEncoderDecoder(nn.Module):
         dev = next(self.parameters()).device
         prompt_ids = prompt_ids.to(dev)
         if plan.mode == 'beam':
-            if self._beam_captioner is None:
-                object.__setattr__(self, '_beam_captioner', CaptionBeamDecoder(self))
-            return self._beam_captioner.run(images, prompt_ids, plan)
+            return self._decoder('_beam_captioner', CaptionBeamDecoder).run(images, prompt_ids, plan)
         if plan.mode == 'cache':
-            if self._captioner is None:
-                object.__setattr__(self, '_captioner', CaptionDecoder(self))
-            return self._captioner.run(images, prompt_ids, plan)
+            return self._decoder('_captioner', CaptionDecoder).run(images, prompt_ids, plan)
         N, sampling, plen, pmin, pmax = plan.N, plan.sampling, plan.plen, plan.pmin, plan.pmax
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
@@ -378,19 +376,12 @@ class VisionEncoderDecoder(nn.Module):
         ``generate_captions`` refuses about the set itself, prompt + longest phrase + 1 past the text window, ``images_per_pass`` < 1;
         NotImplementedError for a non-causal decoder and for sparse nano-mini blocks.  ``generate_captions``, ``score`` and ``rerank``
         are untouched by this call: it keeps a decoder state of its own."""
-        from ..decoding import TrieScoreDecoder, check_phrase_score_args, decode_window, takes_long_cache
-        eng = self._engine
-        dc = eng.dec
-        ncls = eng.enc.ncls
-        window = self.decoder.block_size - self.space_for_prompt
-        if dc.causal:
-            window = min(window, decode_window(dc.block, ncls if self.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
-                                               takes_long_cache(dc.llama)))
-        trie = check_phrase_score_args(phrases, eos_token_id, dc.V, prompt_ids.shape[1], window, dc.causal,
-                                       dc.fam is not None and bool(dc.fam.sparse), images_per_pass)
-        if self._trie_scorer is None:
-            object.__setattr__(self, '_trie_scorer', TrieScoreDecoder(self))
-        return self._trie_scorer.score(images, prompt_ids.to(next(self.parameters()).device), trie, int(eos_token_id), images_per_pass)
+        from ..decoding import TrieScoreDecoder, caption_facts, check_phrase_score_args
+        facts = caption_facts(self)
+        trie = check_phrase_score_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, facts.causal, facts.sparse,
+                                       images_per_pass)
+        return self._decoder('_trie_scorer', TrieScoreDecoder).score(images, prompt_ids.to(next(self.parameters()).device), trie,
+                                                                     int(eos_token_id), images_per_pass)
 
     @torch.no_grad()
     def search_phrases(self, images, prompt_ids, phrases, eos_token_id, num_beams=4, num_return_sequences=1, length_penalty=0.0, poll_every=8):
@@ -410,20 +401,12 @@ class VisionEncoderDecoder(nn.Module):
         everything ``generate_captions`` refuses about the set itself, W outside 1 .. 8, N outside 1 .. min(W, distinct phrases), a
         non-finite ``length_penalty``, prompt + longest phrase + 1 past the text window, a negative ``poll_every``; NotImplementedError
         for a non-causal decoder and for sparse nano-mini blocks.  The call keeps a decoder state of its own."""
-        from ..decoding import PhraseBeamDecoder, check_phrase_search_args, decode_window, takes_long_cache
-        eng = self._engine
-        dc = eng.dec
-        ncls = eng.enc.ncls
-        window = self.decoder.block_size - self.space_for_prompt
-        if dc.causal:
-            window = min(window, decode_window(dc.block, ncls if self.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
-                                               takes_long_cache(dc.llama)))
-        trie, W, N = check_phrase_search_args(phrases, eos_token_id, dc.V, prompt_ids.shape[1], window, num_beams, num_return_sequences,
-                                              length_penalty, poll_every, dc.causal, dc.fam is not None and bool(dc.fam.sparse))
-        if self._phrase_searcher is None:
-            object.__setattr__(self, '_phrase_searcher', PhraseBeamDecoder(self))
-        return self._phrase_searcher.search(images, prompt_ids.to(next(self.parameters()).device), trie, int(eos_token_id), W, N,
-                                            float(length_penalty), int(poll_every))
+        from ..decoding import PhraseBeamDecoder, caption_facts, check_phrase_search_args
+        facts = caption_facts(self)
+        trie, W, N = check_phrase_search_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, num_beams,
+                                              num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse)
+        return self._decoder('_phrase_searcher', PhraseBeamDecoder).search(images, prompt_ids.to(next(self.parameters()).device), trie,
+                                                                           int(eos_token_id), W, N, float(length_penalty), int(poll_every))
 
     @torch.no_grad()
     def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:
