@@ -7,7 +7,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from .phrase_trie import PhraseTrie, phrase_node_csr, phrase_trie
+from .phrase_trie import PhraseForest, PhraseTrie, phrase_forest, phrase_node_csr, phrase_trie
 
 
 class Sampling(NamedTuple):
@@ -194,15 +194,93 @@ def caption_processors(repetition_penalty: float, min_new_tokens: int, suppress_
     return Processors(theta, float(inv), min_new, tuple(suppress))
 
 
-def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False):
+def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False,
+                      sets: bool = False):
     """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
     ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
     ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
     the count then reads the device's table).  ``trie`` (a ``phrases`` call): ('trie', eos, ...that key) -- the trie's
-    contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key."""
+    contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key.
+    ``sets`` (a ``phrase_sets`` call): ('trie_sets', eos, ...the ragged or plain key) -- the forest, the start nodes and the
+    prompt lengths are device tables; a call without ``phrase_sets`` never sees a 'trie_sets' key."""
     key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
     key = key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
+    if sets:
+        return ('trie_sets', eos) + key
     return ('trie', eos) + key if trie else key
+
+
+def phrase_beam_sets_graph_key(pmax: int, W: int, eos: int, length_penalty: float):
+    """The graph key of a ``search_phrases(phrase_sets=...)`` full step: the longest prompt, W, eos and the penalty are
+    kernel arguments; every image's prompt length and longest phrase are device tables, so they are no part of it."""
+    return ('phrase_beam_sets', int(pmax), int(W), int(eos), float(length_penalty))
+
+
+class PhraseSets(NamedTuple):
+    """``phrase_sets`` / ``phrase_set_index`` of a call, checked (``check_phrase_sets``)."""
+    forest: PhraseForest
+    index: np.ndarray                   # int32 [B]: image b answers from set index[b]
+    roots: np.ndarray                   # int32 [B]: forest.roots[index]
+    longest: np.ndarray                 # int32 [B]: forest.longest[index]
+    widest: int                         # the widest level over the sets in use
+    smallest: int                       # the fewest distinct phrases of a set in use
+
+
+def check_phrase_sets(phrases, phrase_sets, phrase_set_index, B: int, eos, vocab: int) -> PhraseSets:
+    """What ``phrase_sets`` / ``phrase_set_index`` refuse about themselves (host only, ValueError), in this order: ``phrase_set_index``
+    without ``phrase_sets``; ``phrases`` given too; no set, or what ``phrase_trie`` refuses about set s in its own words behind
+    'phrase_sets[s]: ' (``phrase_forest``); an index that is not one whole number per image; ``phrase_set_index`` None with S != B; an
+    index outside [0, S)."""
+    if phrase_sets is None:
+        raise ValueError('phrase_set_index without phrase_sets: it names a set of phrase_sets per image')
+    if phrases is not None:
+        raise ValueError('phrases and phrase_sets are both given: one set for all images, or phrase_sets with a set per image')
+    forest = phrase_forest(phrase_sets, eos, vocab)
+    S = forest.sets
+    if phrase_set_index is None:
+        if S != B:
+            raise ValueError(f'phrase_set_index = None needs one set per image: {S} sets for {B} images')
+        index = np.arange(B, dtype=np.int64)
+    else:
+        if isinstance(phrase_set_index, torch.Tensor):
+            if phrase_set_index.is_floating_point() or phrase_set_index.is_complex() or phrase_set_index.dtype == torch.bool:
+                raise ValueError(f'phrase_set_index of dtype {phrase_set_index.dtype}: integers are needed')
+            index = phrase_set_index.detach().cpu().numpy()
+        else:
+            index = np.asarray(phrase_set_index)
+            if index.size and not np.issubdtype(index.dtype, np.integer):
+                raise ValueError(f'phrase_set_index of type {index.dtype}: integers are needed')
+        if index.shape != (B,):
+            raise ValueError(f'phrase_set_index of shape {tuple(index.shape)} for {B} images: one set index per image, shape ({B},)')
+        if B and (int(index.min()) < 0 or int(index.max()) >= S):
+            bad = int(np.flatnonzero((index < 0) | (index >= S))[0])
+            raise ValueError(f'phrase_set_index[{bad}] = {int(index[bad])} is outside the {S} sets of phrase_sets: [0, {S})')
+    index = index.astype(np.int32)
+    used = np.unique(index)
+    return PhraseSets(forest, index, forest.roots[index].astype(np.int32), forest.longest[index].astype(np.int32),
+                      int(forest.widest[used].max()) if used.size else 1, int(forest.distinct[used].min()) if used.size else 0)
+
+
+def check_phrase_set_caption_args(phrases, phrase_sets, phrase_set_index, B: int, eos, vocab: int, max_new_tokens: int,
+                                  processors_active=False, num_beams=1, causal: bool = True) -> PhraseSets:
+    """``check_phrase_sets``, then ``max_new_tokens`` below the longest phrase of a set in use + 1 (ValueError), then what
+    ``phrase_sets`` does not combine with in ``generate_captions`` (NotImplementedError, naming the reason): an active logits
+    processor, ``num_beams`` > 1, a non-causal decoder.  ``prompt_lengths`` is NOT among them.  ``processors_active``
+    may be a callable: it is asked only once the ValueErrors above have passed."""
+    sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
+    longest = int(sets.longest.max()) if B else 1
+    if max_new_tokens < longest + 1:
+        raise ValueError(f'max_new_tokens = {max_new_tokens} is below the longest phrase + 1 = {longest + 1} of the sets in use: every row '
+                         f'ends with EOS')
+    if processors_active() if callable(processors_active) else processors_active:
+        raise NotImplementedError('phrase_sets with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
+                                  'emitted, and a processor could leave a node without an allowed token')
+    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
+        raise NotImplementedError('phrase_sets under num_beams > 1: the beam step has no trie state per hypothesis')
+    if not causal:
+        raise NotImplementedError('phrase_sets run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
+                                  '(generate_by_recompute), which has no constrained step')
+    return sets
 
 
 def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
@@ -287,12 +365,30 @@ def trie_widest_level(trie: PhraseTrie) -> int:
 
 
 def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_beams=4, num_return_sequences=1, length_penalty=0.0,
-                             poll_every=8, causal: bool = True, sparse: bool = False):
+                             poll_every=8, causal: bool = True, sparse: bool = False, phrase_sets=None, phrase_set_index=None,
+                             prompt_lengths=None, B: Optional[int] = None):
     """The refusals of ``search_phrases``, all before anything runs (host only) -> (trie, W, N).  ValueError, in this order: everything
     ``phrase_trie`` refuses about the set (or a ``PhraseTrie`` built for another EOS / vocabulary); ``num_beams`` outside
     1 .. MAX_CAPTION_BEAMS; ``num_return_sequences`` outside 1 .. min(num_beams, distinct phrases); a non-finite ``length_penalty``;
     prompt + longest phrase + 1 past the decode ``window`` (the text of every other call); a negative ``poll_every``.
-    NotImplementedError, naming the reason: a non-causal decoder, sparse nano-mini blocks."""
+    NotImplementedError, naming the reason: a non-causal decoder, sparse nano-mini blocks.
+    With ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths`` (``B``: the images) -> (``PhraseSets``, W, N, plen int32
+    [B] or None): ``check_phrase_sets`` first, the same checks with N held against the smallest set in use and the window against the
+    longest prompt + the longest phrase in use + 1, and ``prompt_lengths``' own refusals (``check_ragged_caption_args``' texts) behind
+    ``num_return_sequences``'.  ``prompt_lengths`` with ``phrases=`` is refused (ValueError): the forced column is ``phrase_sets``' rule."""
+    if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
+        if phrase_sets is None and phrase_set_index is None:
+            raise ValueError('search_phrases(prompt_lengths=...) needs phrase_sets: one answer list for all images is '
+                             'phrase_sets=[answers], phrase_set_index=[0] * B')
+        assert B is not None
+        sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
+        W, N = _check_search_beams(num_beams, num_return_sequences, sets.smallest, length_penalty)
+        plen = None if prompt_lengths is None else _prompt_lengths(prompt_lengths, B, P)
+        total = (int(P) if plen is None else int(plen.max())) + int(sets.longest.max()) + 1
+        _check_search_rest(total, window, poll_every, causal, sparse)
+        return sets, W, N, plen
+    if phrases is None:
+        raise ValueError('search_phrases needs phrases or phrase_sets')
     if isinstance(phrases, PhraseTrie):
         trie = phrases
         if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
@@ -300,11 +396,17 @@ def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_
             raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
     else:
         trie = phrase_trie(phrases, eos, vocab, 1 << 30)
+    W, N = _check_search_beams(num_beams, num_return_sequences, int((trie.term >= 0).sum()), length_penalty)
+    _check_search_rest(int(P) + trie.longest + 1, window, poll_every, causal, sparse)
+    return trie, W, N
+
+
+def _check_search_beams(num_beams, num_return_sequences, distinct: int, length_penalty):
+    """``check_phrase_search_args``' refusals of W, N and the penalty -> (W, N); ``distinct``: the distinct phrases (of the smallest set)"""
     if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
         raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the trie beam kernels keep at most '
                          f'{MAX_CAPTION_BEAMS} rows per image)')
     W = int(num_beams)
-    distinct = int((trie.term >= 0).sum())
     N = num_return_sequences
     if isinstance(N, bool) or int(N) != N or not 1 <= int(N) <= min(W, distinct):
         raise ValueError(f'num_return_sequences = {N!r} with num_beams = {W} and {distinct} distinct phrases: from 1 to '
@@ -315,7 +417,11 @@ def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_
         finite = False
     if not finite:
         raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
-    total = int(P) + trie.longest + 1
+    return W, int(N)
+
+
+def _check_search_rest(total: int, window: int, poll_every, causal: bool, sparse: bool):
+    """``check_phrase_search_args``' refusals behind the penalty: the window, ``poll_every``, the decoder"""
     if total > window:
         raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
     if isinstance(poll_every, bool) or int(poll_every) != poll_every or int(poll_every) < 0:
@@ -326,7 +432,6 @@ def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_
     if sparse:
         raise NotImplementedError('search_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, '
                                   'and the trie beam step has not been run through its slot table (slot_pos); use rerank')
-    return trie, W, int(N)
 
 
 def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,
@@ -353,6 +458,11 @@ def check_ragged_caption_args(prompt_lengths, B: int, P: int, N: int, sampling: 
     """check_caption_args, and the refusals of ``prompt_lengths`` (read on the host, before anything moves to the device): one integer
     per image, 1 <= p_b <= P  -> the lengths, int32 [B]"""
     check_caption_args(N, sampling, eos, pad, poll_every, max_new_tokens, **processors)
+    return _prompt_lengths(prompt_lengths, B, P)
+
+
+def _prompt_lengths(prompt_lengths, B: int, P: int) -> np.ndarray:
+    """the refusals of ``prompt_lengths`` itself -> int32 [B]"""
     if isinstance(prompt_lengths, torch.Tensor):
         if prompt_lengths.is_floating_point() or prompt_lengths.is_complex() or prompt_lengths.dtype == torch.bool:
             raise ValueError(f'prompt_lengths of dtype {prompt_lengths.dtype}: integers are needed')
@@ -456,16 +566,18 @@ class CaptionPlan(NamedTuple):
     trie: Optional[PhraseTrie]          # None: no ``phrases``
     length_penalty: float
     early_stopping: bool
+    sets: Optional[PhraseSets] = None   # ``phrase_sets``: the forest, every image's set, root and longest phrase; None: no sets
 
 
 def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                   temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None, prompt_prefill='steps',
                   repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1, length_penalty=1.0, early_stopping=False,
-                  phrases=None, *, sampling=...) -> CaptionPlan:
+                  phrases=None, phrase_sets=None, phrase_set_index=None, *, sampling=...) -> CaptionPlan:
     """The one place that says what ``generate_captions(...)`` on ``prompt_ids`` [B, P] means, or refuses it: the arguments are the model
     method's (``sampling``: the decoders' keyword methods hand their ``Sampling`` or None in place of the four sampling arguments).
-    Refusals come in this order, the first that applies wins: ``phrases`` (``check_phrase_caption_args``, behind the logits processors'
-    own ValueErrors); the beam arguments (``check_beam_caption_args``); under num_beams = W > 1 the text window, then 2 W > V; else
+    Refusals come in this order, the first that applies wins: ``phrase_sets`` / ``phrase_set_index``
+    (``check_phrase_set_caption_args``: its ValueErrors, then the logits processors' own, then its NotImplementedErrors); ``phrases``
+    (``check_phrase_caption_args``, behind the logits processors' own ValueErrors); the beam arguments (``check_beam_caption_args``); under num_beams = W > 1 the text window, then 2 W > V; else
     ``check_caption_args`` / ``check_ragged_caption_args``; an active processor on a non-causal decoder; ``prefill_plan``'s; the text
     window.  At W = 1 only ``num_beams``, ``length_penalty`` and ``early_stopping`` are looked at among the beam arguments."""
     eos, pad, formed = eos_token_id, pad_token_id, []
@@ -476,8 +588,11 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
         return formed[0]
     procs = dict(repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens, vocab=facts.V,
                  formed=processors)
-    trie = None
-    if phrases is not None:             # before the beam checks: those keep their own texts
+    trie = sets = None
+    if phrase_sets is not None or phrase_set_index is not None:
+        sets = check_phrase_set_caption_args(phrases, phrase_sets, phrase_set_index, B, eos, facts.V, max_new_tokens,
+                                             lambda: processors() is not None, num_beams, facts.causal)
+    elif phrases is not None:           # before the beam checks: those keep their own texts
         trie = check_phrase_caption_args(phrases, eos, facts.V, max_new_tokens, prompt_lengths, processors() is not None, num_beams,
                                          facts.causal)
     W = check_beam_caption_args(num_beams, num_return_sequences, length_penalty, early_stopping, temperature=temperature, top_k=top_k,
@@ -508,5 +623,5 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
         raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({facts.window})')
     return CaptionPlan('cache' if facts.causal else 'recompute', N, 1, sampling, eos, (0 if eos is None else eos) if pad is None else pad,
                        poll_every, max_new_tokens, plen, pmin, pmax, prompt_prefill, m, start, proc, trie, float(length_penalty),
-                       bool(early_stopping))
+                       bool(early_stopping), sets)
 

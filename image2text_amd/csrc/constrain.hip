@@ -26,15 +26,21 @@ __device__ __forceinline__ void node_edges(const int* __restrict__ child_off, in
 // been written.  Barrier.  Pass B: -inf over columns [0, V), 16-byte stores; columns V .. ld are not touched.  Barrier.  Pass C: the
 // kept values back into their columns (thread i of pass A wrote kept[r][i] and reads it here itself).  Any fan-out works: no LDS bitmap,
 // no limit on V.  decoding.trie_mask_host is the host's statement of what the row holds afterwards.
+// RAGGED (i2t_caption_trie_mask_ragged): row r belongs to image r / N, and while *len_ptr < plen[r / N] the row sits in
+// a forced prompt column: its workgroup returns before it reads or writes anything of the row -- the logits stay raw, raw_lse[r] and
+// kept[r] keep what they held.  Every other row runs the body below unchanged.
 constexpr int TRIE_THREADS = 256;
+template <bool RAGGED>
 __global__ __launch_bounds__(TRIE_THREADS) void caption_trie_mask_kernel(float* logits, int ld, const int* __restrict__ node,
                                                                          const int* __restrict__ child_off, const int* __restrict__ child_tok,
                                                                          const int* __restrict__ term, int nodes, int edges, int eos,
                                                                          const int* __restrict__ done, float* __restrict__ raw_lse, float* kept,
-                                                                         int kept_ld, int V) {
+                                                                         int kept_ld, int V, const int* __restrict__ len_ptr,
+                                                                         const int* __restrict__ plen, int N) {
     __shared__ float rmx[TRIE_THREADS / 64], rse[TRIE_THREADS / 64];
     if (*done) return;                                  // block-uniform, before any barrier
     const int r = blockIdx.x, tid = threadIdx.x;
+    if (RAGGED && *len_ptr < plen[r / N]) return;       // block-uniform: a forced column
     const int nd = node[r];
     if (nd < 0 || nd >= nodes) return;                  // block-uniform (never from the advance kernel)
     int off, fan;
@@ -82,7 +88,10 @@ __global__ __launch_bounds__(TRIE_THREADS) void caption_trie_mask_kernel(float* 
 // child_next (the lanes stride over the node's sorted children; at most one matches); either way tok_lp[r][len] = logits[r][c] -
 // raw_lse[r] over what the chooser wrote there -- the allowed columns hold their raw values after the pre-pass, so this is the raw
 // row's log_softmax at c.  Any other token (never from a chooser) leaves node and log-prob as they were.
+// RAGGED (i2t_caption_trie_advance_ragged): a row in a forced column (len < plen[r / N]) is skipped like a finished one -- node,
+// phrase_index and tok_lp[r][len] stay; i2t_caption_finish_ragged replaces the chooser's token and log-prob after this kernel.
 constexpr int TRIE_ADV_WAVES = 4;
+template <bool RAGGED>
 __global__ __launch_bounds__(64 * TRIE_ADV_WAVES) void caption_trie_advance_kernel(const int64_t* __restrict__ ids, int ids_ld,
                                                                                    const int* __restrict__ len_ptr, const int* __restrict__ finished,
                                                                                    const float* __restrict__ logits, int ld,
@@ -91,12 +100,13 @@ __global__ __launch_bounds__(64 * TRIE_ADV_WAVES) void caption_trie_advance_kern
                                                                                    const int* __restrict__ term, int nodes, int edges, int eos,
                                                                                    const int* __restrict__ done, int* __restrict__ node,
                                                                                    int* __restrict__ phrase_index, float* __restrict__ tok_lp, int lp_ld,
-                                                                                   int R, int V) {
+                                                                                   int R, int V, const int* __restrict__ plen, int N) {
     if (*done) return;
     const int lane = threadIdx.x & 63, r = blockIdx.x * TRIE_ADV_WAVES + (threadIdx.x >> 6);
     const int len = *len_ptr;
     if (r >= R || len < 0 || len >= ids_ld || len >= lp_ld) return;      // wave-uniform, as every return below
     if (finished[r]) return;
+    if (RAGGED && len < plen[r / N]) return;                             // a forced column
     const int64_t c = ids[(size_t)r * ids_ld + len];
     const int nd = node[r];
     if (c < 0 || c >= V || nd < 0 || nd >= nodes) return;
@@ -226,44 +236,97 @@ __global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
 
 }  // namespace
 
+namespace {
+
+// The checks and the launch the plain and the ragged entry point share; `fn` names the caller in every message.  plen null: the plain
+// kernel, which reads neither len_ptr nor N.
+int trie_mask_launch(const char* fn, void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
+                     const int* term, int nodes, int edges, int eos, const int* done, float* raw_lse, float* kept, int kept_ld, int R, int V,
+                     const int* len_ptr, const int* plen, int N) {
+    I2T_REQUIRE(logits && node && child_off && child_tok && term && done && raw_lse && kept, "%s: null pointer", fn);
+    I2T_REQUIRE(R > 0 && V > 0, "%s: R = %d rows, V = %d", fn, R, V);
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "%s: ld = %d: logits rows hold V = %d columns and start on 16 bytes", fn, ld, V);
+    I2T_REQUIRE(eos >= 0 && eos < V, "%s: eos = %d outside the vocabulary of %d", fn, eos, V);
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "%s: nodes = %d, edges = %d: a trie has a root", fn, nodes, edges);
+    I2T_REQUIRE(kept_ld >= 1, "%s: kept_ld = %d: a row keeps at least the EOS logit", fn, kept_ld);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(kept) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(child_off) && ALIGNED16(child_tok) &&
+                    ALIGNED16(term),
+                "%s: misaligned base pointer (16 bytes)", fn);
+    if (plen)
+        hipLaunchKernelGGL(caption_trie_mask_kernel<true>, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, node, child_off,
+                           child_tok, term, nodes, edges, eos, done, raw_lse, kept, kept_ld, V, len_ptr, plen, N);
+    else
+        hipLaunchKernelGGL(caption_trie_mask_kernel<false>, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, node, child_off,
+                           child_tok, term, nodes, edges, eos, done, raw_lse, kept, kept_ld, V, nullptr, nullptr, 1);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
+}
+
+int trie_advance_launch(const char* fn, void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const int* finished,
+                        const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok, const int* child_next,
+                        const int* term, int nodes, int edges, int eos, const int* done, int* node, int* phrase_index, float* tok_lp, int lp_ld,
+                        int R, int V, const int* plen, int N) {
+    I2T_REQUIRE(ids && len_ptr && finished && logits && raw_lse && child_off && child_tok && child_next && term && done && node && phrase_index &&
+                    tok_lp,
+                "%s: null pointer", fn);
+    I2T_REQUIRE(R > 0 && V > 0 && ids_ld > 0 && lp_ld > 0, "%s: R = %d rows, V = %d, ids_ld = %d, lp_ld = %d", fn, R, V, ids_ld, lp_ld);
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "%s: ld = %d: logits rows hold V = %d columns and start on 16 bytes", fn, ld, V);
+    I2T_REQUIRE(eos >= 0 && eos < V, "%s: eos = %d outside the vocabulary of %d", fn, eos, V);
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "%s: nodes = %d, edges = %d: a trie has a root", fn, nodes, edges);
+    I2T_REQUIRE(ALIGNED16(ids) && ALIGNED16(logits) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(phrase_index) && ALIGNED16(child_off) &&
+                    ALIGNED16(child_tok) && ALIGNED16(child_next) && ALIGNED16(term),
+                "%s: misaligned base pointer (16 bytes)", fn);
+    const dim3 grid((R + TRIE_ADV_WAVES - 1) / TRIE_ADV_WAVES), block(64 * TRIE_ADV_WAVES);
+    if (plen)
+        hipLaunchKernelGGL(caption_trie_advance_kernel<true>, grid, block, 0, (hipStream_t)stream, ids, ids_ld, len_ptr, finished, logits, ld,
+                           raw_lse, child_off, child_tok, child_next, term, nodes, edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V, plen,
+                           N);
+    else
+        hipLaunchKernelGGL(caption_trie_advance_kernel<false>, grid, block, 0, (hipStream_t)stream, ids, ids_ld, len_ptr, finished, logits, ld,
+                           raw_lse, child_off, child_tok, child_next, term, nodes, edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V,
+                           nullptr, 1);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
+}
+
+}  // namespace
+
 extern "C" int i2t_caption_trie_mask(void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
                                      const int* term, int nodes, int edges, int eos, const int* done, float* raw_lse, float* kept, int kept_ld,
                                      int R, int V) {
-    I2T_REQUIRE(logits && node && child_off && child_tok && term && done && raw_lse && kept, "i2t_caption_trie_mask: null pointer");
-    I2T_REQUIRE(R > 0 && V > 0, "i2t_caption_trie_mask: R = %d rows, V = %d", R, V);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_caption_trie_mask: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
-    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_caption_trie_mask: eos = %d outside the vocabulary of %d", eos, V);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_caption_trie_mask: nodes = %d, edges = %d: a trie has a root", nodes, edges);
-    I2T_REQUIRE(kept_ld >= 1, "i2t_caption_trie_mask: kept_ld = %d: a row keeps at least the EOS logit", kept_ld);
-    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(kept) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(child_off) && ALIGNED16(child_tok) &&
-                    ALIGNED16(term),
-                "i2t_caption_trie_mask: misaligned base pointer (16 bytes)");
-    hipLaunchKernelGGL(caption_trie_mask_kernel, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, node, child_off, child_tok, term,
-                       nodes, edges, eos, done, raw_lse, kept, kept_ld, V);
-    I2T_CHECK_LAUNCH("i2t_caption_trie_mask");
-    return I2T_OK;
+    return trie_mask_launch("i2t_caption_trie_mask", stream, logits, ld, node, child_off, child_tok, term, nodes, edges, eos, done, raw_lse, kept,
+                            kept_ld, R, V, nullptr, nullptr, 1);
+}
+
+extern "C" int i2t_caption_trie_mask_ragged(void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
+                                            const int* term, int nodes, int edges, int eos, const int* done, float* raw_lse, float* kept,
+                                            int kept_ld, const int* len_ptr, const int* plen, int N, int R, int V) {
+    I2T_REQUIRE(N >= 1, "i2t_caption_trie_mask_ragged: N = %d rows per image (at least 1)", N);
+    I2T_REQUIRE(R % N == 0, "i2t_caption_trie_mask_ragged: R = %d rows are not whole groups of N = %d", R, N);
+    I2T_REQUIRE(plen && len_ptr, "i2t_caption_trie_mask_ragged: null plen or len_ptr: the prompt lengths are device memory");
+    I2T_REQUIRE(ALIGNED16(plen), "i2t_caption_trie_mask_ragged: misaligned plen (16 bytes)");
+    return trie_mask_launch("i2t_caption_trie_mask_ragged", stream, logits, ld, node, child_off, child_tok, term, nodes, edges, eos, done, raw_lse,
+                            kept, kept_ld, R, V, len_ptr, plen, N);
 }
 
 extern "C" int i2t_caption_trie_advance(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const int* finished,
                                         const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok,
                                         const int* child_next, const int* term, int nodes, int edges, int eos, const int* done, int* node,
                                         int* phrase_index, float* tok_lp, int lp_ld, int R, int V) {
-    I2T_REQUIRE(ids && len_ptr && finished && logits && raw_lse && child_off && child_tok && child_next && term && done && node && phrase_index &&
-                    tok_lp,
-                "i2t_caption_trie_advance: null pointer");
-    I2T_REQUIRE(R > 0 && V > 0 && ids_ld > 0 && lp_ld > 0, "i2t_caption_trie_advance: R = %d rows, V = %d, ids_ld = %d, lp_ld = %d", R, V, ids_ld,
-                lp_ld);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_caption_trie_advance: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
-    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_caption_trie_advance: eos = %d outside the vocabulary of %d", eos, V);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_caption_trie_advance: nodes = %d, edges = %d: a trie has a root", nodes, edges);
-    I2T_REQUIRE(ALIGNED16(ids) && ALIGNED16(logits) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(phrase_index) && ALIGNED16(child_off) &&
-                    ALIGNED16(child_tok) && ALIGNED16(child_next) && ALIGNED16(term),
-                "i2t_caption_trie_advance: misaligned base pointer (16 bytes)");
-    hipLaunchKernelGGL(caption_trie_advance_kernel, dim3((R + TRIE_ADV_WAVES - 1) / TRIE_ADV_WAVES), dim3(64 * TRIE_ADV_WAVES), 0,
-                       (hipStream_t)stream, ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, nodes,
-                       edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V);
-    I2T_CHECK_LAUNCH("i2t_caption_trie_advance");
-    return I2T_OK;
+    return trie_advance_launch("i2t_caption_trie_advance", stream, ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok,
+                               child_next, term, nodes, edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V, nullptr, 1);
+}
+
+extern "C" int i2t_caption_trie_advance_ragged(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const int* finished,
+                                               const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok,
+                                               const int* child_next, const int* term, int nodes, int edges, int eos, const int* done,
+                                               int* node, int* phrase_index, float* tok_lp, int lp_ld, const int* plen, int N, int R, int V) {
+    I2T_REQUIRE(N >= 1, "i2t_caption_trie_advance_ragged: N = %d rows per image (at least 1)", N);
+    I2T_REQUIRE(R % N == 0, "i2t_caption_trie_advance_ragged: R = %d rows are not whole groups of N = %d", R, N);
+    I2T_REQUIRE(plen, "i2t_caption_trie_advance_ragged: null plen: the prompt lengths are device memory");
+    I2T_REQUIRE(ALIGNED16(plen), "i2t_caption_trie_advance_ragged: misaligned plen (16 bytes)");
+    return trie_advance_launch("i2t_caption_trie_advance_ragged", stream, ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off,
+                               child_tok, child_next, term, nodes, edges, eos, done, node, phrase_index, tok_lp, lp_ld, R, V, plen, N);
 }
 
 extern "C" int i2t_rows_lse(void* stream, const float* logits, int ld, float* lse, int R, int V) {
@@ -445,7 +508,11 @@ __global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(cons
 // parents to the W children a column at a time through registers -- every parent column is read before a child row is written --,
 // and threads 0 .. W - 1 write the children's node, path, token and hist[child][pos] = parent.  A row without a child is dead: node
 // -1, path -inf, token eos, its own history row.  Every open image stores the same 1 into ctrl[1]: no atomic.
+// SETS (i2t_trie_beam_select_sets): image b has its own prompt length plen[b] (plen null: P) and its own longest phrase
+// longest_of[b].  With t = len - plen[b] < 0 the image sits in a forced prompt column: pool, node, path, closed and ids stay, every row
+// records itself as its parent at hist[row][pos], and the image stores the 1 into ctrl[1] that keeps the search open.
 constexpr int TS_THREADS = 256;
+template <bool SETS>
 __global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int* __restrict__ cand_edge, const float* __restrict__ cand_total,
                                                                       const float* __restrict__ fin_total, int* __restrict__ node,
                                                                       float* __restrict__ path, const int* __restrict__ child_tok,
@@ -455,7 +522,8 @@ __global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int*
                                                                       float* __restrict__ pool_score, int* __restrict__ pool_len,
                                                                       int* __restrict__ pool_n, int* __restrict__ closed,
                                                                       const int* __restrict__ pos_ptr, const int* __restrict__ len_ptr,
-                                                                      int* __restrict__ ctrl, int W, int P, int longest, float length_penalty) {
+                                                                      int* __restrict__ ctrl, int W, int P, int longest_all, float length_penalty,
+                                                                      const int* __restrict__ plen, const int* __restrict__ longest_of) {
     __shared__ int c_par[TB_MAX_W], c_node[TB_MAX_W], c_tok[TB_MAX_W], head[TB_MAX_W];
     __shared__ float c_path[TB_MAX_W];
     __shared__ int e_ph[TB_MAX_W + 1], e_len[TB_MAX_W + 1];
@@ -463,9 +531,16 @@ __global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int*
     if (ctrl[0]) return;
     const int b = blockIdx.x, tid = threadIdx.x;
     if (closed[b]) return;
-    const int pos = *pos_ptr, len = *len_ptr, t = len - P;
-    if (t < 0 || t > longest || len >= ids_ld || pos < 0 || pos >= hist_ld) return;      // counters outside the call's columns: nothing is written
+    const int longest = SETS ? longest_of[b] : longest_all;
+    const int pos = *pos_ptr, len = *len_ptr, t = len - ((SETS && plen) ? plen[b] : P);
     const int r0 = b * W;
+    if (SETS && t < 0) {                                // block-uniform: a forced column
+        if (len < 0 || pos < 0 || pos >= hist_ld) return;
+        if (tid < W) hist[(size_t)(r0 + tid) * hist_ld + pos] = r0 + tid;
+        if (tid == 0) ctrl[1] = 1;
+        return;
+    }
+    if (t < 0 || t > longest || len >= ids_ld || pos < 0 || pos >= hist_ld) return;      // counters outside the call's columns: nothing is written
     if (tid == 0) {
         int m = pool_n[b];
         m = m < 0 ? 0 : (m > W ? W : m);
@@ -600,9 +675,37 @@ extern "C" int i2t_trie_beam_select(void* stream, const int* cand_edge, const fl
     I2T_REQUIRE(eos >= 0, "i2t_trie_beam_select: eos = %d: a dead row takes it as its token", eos);
     // the exponent bits, not a comparison: no fast-math folding of a NaN test
     I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u, "i2t_trie_beam_select: length_penalty must be finite");
-    hipLaunchKernelGGL(trie_beam_select_kernel, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node, path,
-                       child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score, pool_len,
-                       pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, longest, length_penalty);
+    hipLaunchKernelGGL(trie_beam_select_kernel<false>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
+                       path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
+                       pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, longest, length_penalty, nullptr, nullptr);
     I2T_CHECK_LAUNCH("i2t_trie_beam_select");
+    return I2T_OK;
+}
+
+// i2t_trie_beam_select with a prompt length and a longest phrase per image, both device tables.  The host cannot hold
+// the tables against ids_ld; the kernel writes no id column at or past ids_ld and no history column outside [0, hist_ld).
+extern "C" int i2t_trie_beam_select_sets(void* stream, const int* cand_edge, const float* cand_total, const float* fin_total, int* node,
+                                         float* path, const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos,
+                                         int64_t* ids, int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score,
+                                         int* pool_len, int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W,
+                                         int P, const int* plen, const int* longest_of, float length_penalty) {
+    I2T_REQUIRE(cand_edge && cand_total && fin_total && node && path && child_tok && child_next && term && ids && hist && pool_phrase &&
+                    pool_sum && pool_score && pool_len && pool_n && closed && pos_ptr && len_ptr && ctrl,
+                "i2t_trie_beam_select_sets: null pointer");
+    I2T_REQUIRE(longest_of, "i2t_trie_beam_select_sets: null longest_of: every image names its set's longest phrase");
+    I2T_REQUIRE(ALIGNED16(plen) && ALIGNED16(longest_of), "i2t_trie_beam_select_sets: misaligned plen or longest_of (16 bytes)");
+    I2T_REQUIRE(B > 0 && (long)B * TB_MAX_W < (1l << 31), "i2t_trie_beam_select_sets: B = %d images", B);
+    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_select_sets: W = %d rows per image (1 .. %d)", W, TB_MAX_W);
+    I2T_REQUIRE(P >= 1, "i2t_trie_beam_select_sets: P = %d (at least 1)", P);
+    I2T_REQUIRE((long)P + 2 <= ids_ld && hist_ld >= 1, "i2t_trie_beam_select_sets: P + 2 = %ld columns exceed ids_ld = %d (hist_ld = %d)",
+                (long)P + 2, ids_ld, hist_ld);
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_select_sets: nodes = %d, edges = %d: a trie has a root", nodes, edges);
+    I2T_REQUIRE(eos >= 0, "i2t_trie_beam_select_sets: eos = %d: a dead row takes it as its token", eos);
+    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u,
+                "i2t_trie_beam_select_sets: length_penalty must be finite");
+    hipLaunchKernelGGL(trie_beam_select_kernel<true>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
+                       path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
+                       pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, 0, length_penalty, plen, longest_of);
+    I2T_CHECK_LAUNCH("i2t_trie_beam_select_sets");
     return I2T_OK;
 }

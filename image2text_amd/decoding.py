@@ -33,15 +33,18 @@ import torch
 from . import ops
 from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
                            PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseBeams, PhraseScores, Processors, Sampling,
-                           cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
-                           check_phrase_caption_args, check_phrase_score_args, check_phrase_search_args, check_ragged_caption_args, decode_window,
-                           plan_captions, prefill_plan, takes_long_cache, text_window, trie_widest_level)
+                           PhraseSets, cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
+                           check_phrase_caption_args, check_phrase_score_args, check_phrase_search_args, check_phrase_set_caption_args,
+                           check_phrase_sets, check_ragged_caption_args, decode_window, phrase_beam_sets_graph_key, plan_captions, prefill_plan,
+                           takes_long_cache, text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
                             beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
                             phrase_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
-                            trie_beam_candidates_host, trie_beam_select_host, trie_mask_host)
+                            trie_advance_ragged_host, trie_beam_candidates_host, trie_beam_select_host, trie_beam_select_sets_host,
+                            trie_mask_host, trie_mask_ragged_host)
 from .engine import BF16, F32, HotPath
-from .phrase_trie import PhraseTrie, TrieLevel, TrieLevels, level_expand_tables, phrase_node_csr, phrase_trie, trie_levels
+from .phrase_trie import (PhraseForest, PhraseTrie, TrieLevel, TrieLevels, level_expand_tables, phrase_forest, phrase_node_csr, phrase_trie,
+                          trie_levels)
 
 assert LONG_CHUNK_KEYS == ops.LONG_CHUNK_KEYS       # caption_plan.py loads no library: it keeps the figure, ops.py the kernels' copy
 
@@ -440,16 +443,19 @@ class GreedyDecoder:
 
     @staticmethod
     def _drop_graphs(st, tag):
-        """Forget the captured steps that hold a buffer about to be replaced: those whose key is a tuple that starts with ``tag``, or --
-        tag None -- ``generate``'s sampling steps, every key but None / 'greedy' / 'greedy_top2'."""
-        stale = (lambda k: k not in (None, 'greedy', 'greedy_top2')) if tag is None else (lambda k: isinstance(k, tuple) and k[:1] == (tag,))
+        """Forget the captured steps that hold a buffer about to be replaced: those whose key is a tuple that starts with ``tag`` (or with
+        one of a tuple of tags), or -- tag None -- ``generate``'s sampling steps, every key but None / 'greedy' / 'greedy_top2'."""
+        tags = tag if isinstance(tag, tuple) else (tag,)
+        stale = (lambda k: k not in (None, 'greedy', 'greedy_top2')) if tag is None else (lambda k: isinstance(k, tuple) and k[:1] and k[0] in tags)
         st.graphs = {k: g for k, g in st.graphs.items() if not stale(k)}
 
-    def _upload_trie(self, st, trie: PhraseTrie, tag: str, fanout: bool = False):
-        """The trie into st.trie = (child_off, child_tok, child_next, term): persistent because captured steps bake their pointers, and
-        regrown -- together with the graphs tagged ``tag`` -- only when the trie does not fit.  The kernels take the arrays' CAPACITIES as
-        nodes / edges, so a captured step serves any trie that fits; the trie's contents are copied in per call, the spare nodes
-        childless and ending no phrase.  ``fanout``: st.kept, f32 [B, widest fan-out + 1 in whole 4s], is kept and regrown with them."""
+    def _upload_trie(self, st, trie, tag, fanout: bool = False):
+        """The trie -- a ``PhraseTrie``, or a ``PhraseForest``, which the kernels walk as they walk a trie -- into st.trie =
+        (child_off, child_tok, child_next, term): persistent because captured steps bake their pointers, and regrown -- together with
+        the graphs tagged ``tag`` (a tag or a tuple of them: every kind of step that points at it) -- only when the trie does not fit.
+        The kernels take the arrays' CAPACITIES as nodes / edges, so a captured step serves any trie that fits; the trie's contents
+        are copied in per call, the spare nodes childless and ending no phrase.  ``fanout``: st.kept, f32 [B, widest fan-out + 1 in
+        whole 4s], is kept and regrown with them."""
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         if st.trie is None or st.trie[3].numel() < trie.nodes or st.trie[1].numel() < trie.edges \
@@ -777,6 +783,7 @@ class CaptionDecoder(GreedyDecoder):
         st.rag_prompt = st.rag_plen = None                      # prompt_lengths: int64 [B, ids_ld] / int32 [B], made at the first such call
         st.raw_lse = st.saved = st.suppress = None              # logits processors: f32 [R] / f32 [R, ids_ld] / int32 list, made at the first active call
         st.node = st.phrase_index = st.kept = st.trie = None    # phrases: int32 [R] / int32 [R] / f32 [R, fan-out + 1] / the four trie arrays (and raw_lse)
+        st.node_init = None                                     # phrase_sets: int32 [R], every row's start node, made at the first such call
         return st
 
     def _processor_state(self, st, proc: Processors):
@@ -795,16 +802,22 @@ class CaptionDecoder(GreedyDecoder):
         if n:
             st.suppress[:n].copy_(torch.tensor(proc.suppress, dtype=torch.int32))
 
-    def _trie_state(self, st, trie: PhraseTrie):
+    def _trie_state(self, st, trie, roots=None):
         """The buffers of a phrase-constrained step, persistent because captured steps bake their pointers: st.node,
-        st.phrase_index, st.raw_lse, and the trie with st.kept beside it (_upload_trie), under the graph tag 'trie'."""
+        st.phrase_index, st.raw_lse, and the trie with st.kept beside it (_upload_trie), under the graph tags 'trie' and 'trie_sets' --
+        both kinds of step point at the same buffers.  ``roots`` (a ``phrase_sets`` call, DESIGN.md 4x: int32 [B], the root of every
+        image's set in the forest ``trie``): st.node_init, which reset() copies into st.node; no step reads it."""
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         if st.node is None:
             st.node, st.phrase_index = torch.zeros(st.B, **i32), torch.full((st.B,), -1, **i32)
         if st.raw_lse is None:                                  # (shared with the logits processors: _processor_state)
             st.raw_lse = torch.zeros(st.B, dtype=F32, device=dev)
-        self._upload_trie(st, trie, 'trie', fanout=True)
+        self._upload_trie(st, trie, ('trie', 'trie_sets'), fanout=True)
+        if roots is not None:
+            if st.node_init is None:
+                st.node_init = torch.zeros(st.B, **i32)
+            st.node_init.copy_(torch.from_numpy(np.repeat(np.asarray(roots, dtype=np.int32), st.N)))
 
     def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None,
                       trie: bool = False):
@@ -812,8 +825,10 @@ class CaptionDecoder(GreedyDecoder):
         then i2t_caption_finish_ragged; the choosers run as they are, on every row, and what they wrote at a forced column is replaced
         after them.  ``proc``: None, or (Processors, P) of a call with active logits processors (never with ``top2``):
         i2t_caption_logits_process between the GEMM and the chooser, i2t_caption_raw_logprob between the chooser and the finish rule.
-        ``trie`` (a ``phrases`` call; never with ``top2``, ``forced`` or ``proc``): i2t_caption_trie_mask before the
-        chooser, which then runs without n-gram sizes -- the phrase set says what may be emitted --, i2t_caption_trie_advance after it."""
+        ``trie`` (a ``phrases`` or ``phrase_sets`` call; never with ``top2`` or ``proc``): i2t_caption_trie_mask before
+        the chooser, which then runs without n-gram sizes -- the phrase set says what may be emitted --, i2t_caption_trie_advance after it.
+        Together with ``forced`` (``phrase_sets`` under ``prompt_lengths``) the pair is i2t_caption_trie_mask_ragged /
+        i2t_caption_trie_advance_ragged, which hold a row's trie state still while its column is forced."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
@@ -833,7 +848,11 @@ class CaptionDecoder(GreedyDecoder):
                                            R, dc.V)
             if trie:
                 off, tok, nxt, term = st.trie
-                ops.caption_trie_mask(st.logits, dc.Vp, st.node, off, tok, term, eos, done, st.raw_lse, st.kept, R, dc.V)
+                if forced is None:
+                    ops.caption_trie_mask(st.logits, dc.Vp, st.node, off, tok, term, eos, done, st.raw_lse, st.kept, R, dc.V)
+                else:
+                    ops.caption_trie_mask_ragged(st.logits, dc.Vp, st.node, off, tok, term, eos, done, st.raw_lse, st.kept, len_ptr, forced[1],
+                                                 st.N, R, dc.V)
             if sampling is None:
                 ops.ngram_ban_argmax_lp(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, st.ngrams, nn, R, dc.V, done, st.tok_lp)
             else:
@@ -841,9 +860,12 @@ class CaptionDecoder(GreedyDecoder):
                                     sampling.top_k, sampling.nucleus_p, st.seed, done, st.tok_lp)
             if proc is not None:                                # the chooser's log-prob was taken on the processed row: the raw one over it
                 ops.caption_raw_logprob(st.ids, st.ids_ld, len_ptr, st.raw_lse, st.saved, st.logits, dc.Vp, done, st.tok_lp, R, dc.V)
-            if trie:                                            # the row moves along the chosen edge; the raw log-prob over the chooser's
+            if trie and forced is None:                         # the row moves along the chosen edge; the raw log-prob over the chooser's
                 ops.caption_trie_advance(st.ids, st.ids_ld, len_ptr, st.finished, st.logits, dc.Vp, st.raw_lse, off, tok, nxt, term, eos, done,
                                          st.node, st.phrase_index, st.tok_lp, R, dc.V)
+            elif trie:
+                ops.caption_trie_advance_ragged(st.ids, st.ids_ld, len_ptr, st.finished, st.logits, dc.Vp, st.raw_lse, off, tok, nxt, term, eos,
+                                                done, st.node, st.phrase_index, st.tok_lp, forced[1], st.N, R, dc.V)
         if forced is None:
             ops.caption_finish(st.ids, st.ids_ld, len_ptr, eos, pad, st.finished, st.lengths, st.tok_lp, st.ctrl, R)
         else:
@@ -856,7 +878,8 @@ class CaptionDecoder(GreedyDecoder):
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, eos: Optional[int] = None, pad: Optional[int] = None,
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
                           use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps', repetition_penalty: float = 1.0,
-                          min_new_tokens: int = 0, suppress_tokens=None, phrases=None, each=None) -> GeneratedCaptions:
+                          min_new_tokens: int = 0, suppress_tokens=None, phrases=None, each=None, phrase_sets=None,
+                          phrase_set_index=None) -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
         None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
@@ -870,12 +893,14 @@ class CaptionDecoder(GreedyDecoder):
         DESIGN.md 4u): every row emits
         one of the phrases, then EOS.  The step takes the fp32-logits head with i2t_caption_trie_mask before the chooser -- which runs
         over the allowed tokens only, without the n-gram ban -- and i2t_caption_trie_advance after it, under graph keys of their own;
-        the result carries ``phrase_index``.  None: the call is the one without the argument.  ``each(i)`` runs after full step i (tests
-        read the step's buffers there)."""
+        the result carries ``phrase_index``.  None: the call is the one without the argument.  ``phrase_sets`` / ``phrase_set_index``
+        (``check_phrase_set_caption_args``): a phrase set per image -- the sets as one forest in the trie's buffers, every
+        row starting at its set's root --, with or without ``prompt_lengths``; graph keys ('trie_sets', ...).  ``each(i)`` runs after full
+        step i (tests read the step's buffers there)."""
         plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
                              poll_every=poll_every, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
                              repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                             phrases=phrases, sampling=sampling)
+                             phrases=phrases, phrase_sets=phrase_sets, phrase_set_index=phrase_set_index, sampling=sampling)
         return self.run(images, prompt_ids, plan, use_graph, each)
 
     @torch.no_grad()
@@ -888,6 +913,9 @@ class CaptionDecoder(GreedyDecoder):
         B = prompt_ids.shape[0]
         N, sampling, eos, pad, poll_every, max_new_tokens = plan.N, plan.sampling, plan.eos, plan.pad, plan.poll_every, plan.max_new
         plen, pmin, pmax, proc, trie, m, start = plan.plen, plan.pmin, plan.pmax, plan.proc, plan.trie, plan.m, plan.start
+        sets = plan.sets
+        if sets is not None:                # the forest stands where the trie stands: the step's launches differ only under prompt_lengths
+            trie = sets.forest
         ragged = plen is not None
         n_prefill = pmin - 1 - m
         if not max_new_tokens:              # nothing to emit: no step reads the cache, so 'pass' fills nothing -- no pass, no replay
@@ -923,11 +951,12 @@ class CaptionDecoder(GreedyDecoder):
         if proc is not None:
             self._processor_state(st, proc)
         if trie is not None:
-            self._trie_state(st, trie)
+            self._trie_state(st, trie, None if sets is None else sets.roots)
         top2, head = self._greedy_head(st, sampling, logits=proc is not None or trie is not None, lse=True)
         # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key), and
         # so are the processors' scalars ('proc': never an inactive call's key); 'trie': never a key of a call without phrases
-        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax, trie is not None)
+        # 'trie_sets': never a key of a call without phrase_sets
+        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax, trie is not None, sets is not None)
         prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
@@ -936,8 +965,8 @@ class CaptionDecoder(GreedyDecoder):
             # what a row without an EOS ends with: p_b + max_new_tokens
             st.lengths.copy_(len_rows) if ragged else st.lengths.fill_(total)
             st.tok_lp.zero_()
-            if trie is not None:                                # every row at the root, no phrase named yet
-                st.node.zero_()
+            if trie is not None:                                # every row at the root (of its set), no phrase named yet
+                st.node.zero_() if sets is None else st.node.copy_(st.node_init)
                 st.phrase_index.fill_(-1)
         # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
         # ('pass': those columns' K/V are in the cache already, n_prefill = 0)
@@ -1206,6 +1235,7 @@ class PhraseBeamDecoder(BeamDecoder):
         self._build_pool(st, B, W)
         st.pool_phrase = torch.zeros(B, W, **i32)
         st.trie = None                      # (child_off, child_tok, child_next, term), made at the first call (_upload_trie)
+        st.set_node_init = st.set_plen = st.set_longest = None      # phrase_sets: int32 [B, W] / [B] / [B], made at the first such call
         return st
 
     def _phrase_beam_step(self, st, P: int, eos: int, longest: int, length_penalty: float):
@@ -1219,6 +1249,64 @@ class PhraseBeamDecoder(BeamDecoder):
                              st.pool_sum, st.pool_score, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl, st.images, st.W, P,
                              longest, length_penalty)
         ops.beam_advance(st.counters, st.ctrl)
+
+    def _phrase_beam_sets_step(self, st, pmax: int, eos: int, length_penalty: float):
+        """_phrase_beam_step with every image's prompt length and longest phrase read from st.set_plen / st.set_longest"""
+        dc = self.eng.dec
+        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
+        off, tok, nxt, term = st.trie
+        self._logits_head(st)
+        ops.trie_beam_candidates(st.logits, dc.Vp, st.node, st.path, off, tok, term, eos, st.ctrl, st.cand_tok, st.cand_lp, st.fin_total,
+                                 st.B, st.W, dc.V)
+        ops.trie_beam_select_sets(st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist,
+                                  st.pool_phrase, st.pool_sum, st.pool_score, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl,
+                                  st.images, st.W, pmax, st.set_plen, st.set_longest, length_penalty)
+        ops.beam_advance(st.counters, st.ctrl)
+
+    @torch.no_grad()
+    def search_sets(self, images, prompt_ids: torch.Tensor, sets: PhraseSets, eos: int, W: int, N: int, length_penalty: float = 0.0,
+                    poll_every: int = 8, use_graph: bool = True, each=None, plen=None) -> PhraseBeams:
+        """``search`` with a phrase set and (``plen`` int32 [B], or None) a prompt length per image: ``sets``, ``W``, ``N``,
+        ``plen``: what ``check_phrase_search_args`` returned.  Row 0 of image b starts at its set's root; Pmin - 1 prefill steps, then
+        Pmax - Pmin + max(longest) + 1 full steps in which an image whose prompt reaches past the column is held still by
+        i2t_trie_beam_select_sets.  The start nodes, prompt lengths and longest phrases are device tables filled per call: the graph
+        key is ('phrase_beam_sets', Pmax, W, eos, penalty)."""
+        eng = self.eng
+        dc = eng.dec
+        a = eng.prepare(False)
+        dev = a.device
+        prompt_ids = prompt_ids.to(dev)
+        B, P = prompt_ids.shape
+        plen = np.full(B, P, dtype=np.int32) if plen is None else np.asarray(plen, dtype=np.int32)
+        pmin, pmax = int(plen.min()), int(plen.max())
+        longest, length_penalty = int(sets.longest.max()), float(length_penalty)
+        R, total = B * W, pmax + longest + 1
+        st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
+                             lambda st: st.W == W)
+        self._upload_trie(st, sets.forest, ('phrase_beam', 'phrase_beam_sets'))
+        if st.set_node_init is None:        # persistent: the captured steps bake the two tables' pointers
+            i32 = dict(dtype=torch.int32, device=dev)
+            st.set_node_init, st.set_plen, st.set_longest = torch.full((B, W), -1, **i32), torch.ones(B, **i32), torch.ones(B, **i32)
+        st.set_node_init[:, 0] = torch.from_numpy(sets.roots).to(dev)
+        st.set_plen.copy_(torch.from_numpy(plen))
+        st.set_longest.copy_(torch.from_numpy(sets.longest))
+        self._prepare_inputs(st, images, B, W)
+        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
+        keep = torch.arange(pmax, device=dev)[None, :] < st.set_plen[:, None]
+        prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
+        prompt_rows = prompt.repeat_interleave(W, dim=0)
+
+        def reset():
+            self._reset(st, prompt_rows, pmax)
+            st.node.copy_(st.set_node_init.view(-1))
+            st.path.zero_()
+            st.pool_phrase.fill_(-1)
+            self._reset_pool(st)
+        key = phrase_beam_sets_graph_key(pmax, W, eos, length_penalty)
+        self.last_replays = self._replay(st, key, lambda: self._phrase_beam_sets_step(st, pmax, int(eos), length_penalty), reset, pmin - 1,
+                                         pmax - pmin + longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
+        return PhraseBeams(st.pool_phrase[:, :N].long(), st.pool_sum[:, :N].clone(), st.pool_score[:, :N].clone(), st.pool_len[:, :N].clone(),
+                           W >= sets.widest)
 
     @torch.no_grad()
     def search(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float = 0.0,
@@ -1234,7 +1322,7 @@ class PhraseBeamDecoder(BeamDecoder):
         R, total = B * W, P + longest + 1
         st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
                              lambda st: st.W == W)
-        self._upload_trie(st, trie, 'phrase_beam')
+        self._upload_trie(st, trie, ('phrase_beam', 'phrase_beam_sets'))
         self._prepare_inputs(st, images, B, W)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
 

@@ -161,19 +161,37 @@ def trie_advance_host(node: int, token: int, trie: PhraseTrie, eos: int):
     return node, -1, False
 
 
-def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad, max_new: int):
+def trie_mask_ragged_host(z, node: int, trie, eos: int, length: int, plen: int) -> np.ndarray:
+    """What i2t_caption_trie_mask_ragged leaves of one raw fp32 logits row at column ``length`` of a row whose prompt is ``plen`` long
+    (DESIGN.md 4x): the raw row while length < plen -- a forced column, where the kernel also leaves raw_lse and kept alone --, else
+    ``trie_mask_host``'s.  ``trie``: a ``PhraseTrie`` or a ``PhraseForest``."""
+    if int(length) < int(plen):
+        return np.array(z, dtype=np.float32)
+    return trie_mask_host(z, node, trie, eos)
+
+
+def trie_advance_ragged_host(node: int, token: int, trie, eos: int, length: int, plen: int):
+    """What i2t_caption_trie_advance_ragged does with a row at column ``length`` whose prompt is ``plen`` long -> ``trie_advance_host``'s
+    triple; in a forced column (length < plen) the row keeps its node, names no phrase and its log-prob is not written (False)."""
+    if int(length) < int(plen):
+        return int(node), -1, False
+    return trie_advance_host(node, token, trie, eos)
+
+
+def constrained_decode_host(step_logits, prompt, trie: PhraseTrie, eos: int, pad, max_new: int, start: int = 0):
     """The whole greedy search of ``generate_captions(phrases=...)`` for ONE image on the host: ``step_logits(sequence)`` gives the fp32
     logits row [V] that follows a token sequence (a list of ints, the prompt included).  Every step takes ``trie_mask_host`` of the
     row, its argmax (the lower id on ties), the fp32 log_softmax of the RAW row there, and ``trie_advance_host``; the search ends with
     the EOS.  -> SimpleNamespace(ids int64 [L], length, token_logprobs f32 [L - P], logprob f32, phrase_index, steps, gaps): ``gaps``
     holds per step the best allowed logit minus the second-best allowed one (inf where a node allows one token).  A search whose gaps
     all exceed a perturbation of the logits keeps its result under it.  (``pad`` takes no part for one image -- nothing follows the EOS;
-    the signature is ``beam_search_host``'s.)"""
+    the signature is ``beam_search_host``'s.)  ``start``: the node the walk begins at -- the root of the image's set in a
+    ``PhraseForest``, whose ``term`` then names the phrase within that set; 0: a trie's root."""
     seq = [int(t) for t in np.asarray(prompt).reshape(-1)]
     P = len(seq)
     assert P >= 1 and max_new >= 1
     f32 = np.float32
-    node, phrase, lps, gaps = 0, -1, [], []
+    node, phrase, lps, gaps = int(start), -1, [], []
     while phrase < 0 and len(seq) - P < max_new:
         z = np.asarray(step_logits(list(seq)), dtype=f32).reshape(-1)
         masked = trie_mask_host(z, node, trie, eos)
@@ -466,7 +484,7 @@ def trie_beam_candidates_host(logits, node, path, trie: PhraseTrie, eos: int, W:
 
 def trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie: PhraseTrie, eos: int, ids, hist, pool_phrase, pool_sum,
                           pool_score, pool_len, pool_n, closed, counters, ctrl, W: int, P: int, longest: int, length_penalty: float,
-                          close_rule: bool = True, gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
+                          close_rule: bool = True, gaps: Optional[list] = None, pool_gaps: Optional[list] = None, plen=None, longest_of=None):
     """One i2t_trie_beam_select call on the host (numpy, in place on the arrays given; fp32 arithmetic in the kernel's order): the
     normative statement of the selection step of ``search_phrases``.  ``cand_edge`` / ``cand_total`` [R, W] and ``fin_total`` [R]:
     ``trie_beam_candidates_host``'s; ``node`` int32 [R], ``path`` f32 [R]; ``ids`` int64 [R, ids_ld]; ``hist`` int32 [R, hist_ld]; the
@@ -487,23 +505,34 @@ def trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie: Ph
         full pool.  Closing there never changes the pool; it only saves steps (``close_rule`` False shows it);
       * an image left open sets ctrl[1] = 1.
     ``gaps`` (a list, optional) receives, per image and step, the W-th next total minus the best child total that was left out by
-    this merge; ``pool_gaps`` the differences between an offer's score and the pool entries beside it."""
+    this merge; ``pool_gaps`` the differences between an offer's score and the pool entries beside it.
+    ``plen`` / ``longest_of`` (int [B], optional: ``trie_beam_select_sets_host`` hands them in) replace ``P`` / ``longest`` per image."""
     if ctrl[0]:
         return
     pos, ln = int(counters[0]), int(counters[1])
-    t = ln - P
     R = node.shape[0]
     B = R // W
-    if t < 0 or t > longest or ln >= ids.shape[1] or pos < 0 or pos >= hist.shape[1]:
-        return
+    sets = plen is not None or longest_of is not None
     f32 = np.float32
-    with np.errstate(all='ignore'):
-        denom = np.power(f32(t + 1), f32(length_penalty)).astype(f32)
-        lopt = np.power(f32(longest + 1 if length_penalty >= 0 else t + 2), f32(length_penalty)).astype(f32)
+    P_all, longest_all = P, longest
     for b in range(B):
         if closed[b]:
             continue
         r0 = b * W
+        P = P_all if plen is None else int(plen[b])
+        longest = longest_all if longest_of is None else int(longest_of[b])
+        t = ln - P
+        if sets and t < 0:                                      # a forced column (DESIGN.md 4x): the identity history column, the search stays open
+            if ln < 0 or pos < 0 or pos >= hist.shape[1]:
+                continue
+            hist[r0:r0 + W, pos] = np.arange(r0, r0 + W)
+            ctrl[1] = 1
+            continue
+        if t < 0 or t > longest or ln >= ids.shape[1] or pos < 0 or pos >= hist.shape[1]:
+            continue
+        with np.errstate(all='ignore'):
+            denom = np.power(f32(t + 1), f32(length_penalty)).astype(f32)
+            lopt = np.power(f32(longest + 1 if length_penalty >= 0 else t + 2), f32(length_penalty)).astype(f32)
         m = int(pool_n[b])
         entries = [(f32(pool_score[b, i]), int(pool_phrase[b, i]), f32(pool_sum[b, i]), int(pool_len[b, i])) for i in range(m)]
         for w in range(W):
@@ -549,17 +578,33 @@ def trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie: Ph
             hist[r0 + k, pos] = pars[k]
 
 
+def trie_beam_select_sets_host(cand_edge, cand_total, fin_total, node, path, trie, eos: int, ids, hist, pool_phrase, pool_sum, pool_score,
+                               pool_len, pool_n, closed, counters, ctrl, W: int, P: int, plen, longest_of, length_penalty: float,
+                               close_rule: bool = True, gaps: Optional[list] = None, pool_gaps: Optional[list] = None):
+    """One i2t_trie_beam_select_sets call on the host: ``trie_beam_select_host`` with image b's depth t = len -
+    ``plen[b]`` (``plen`` None: ``P`` for every image) and its own ``longest_of[b]`` in the guard, the close test's optimistic length
+    and the column bound.  An image with t < 0 sits in a forced prompt column: nothing of its pool, node, path, closed or ids is
+    touched, every row records itself as its parent, hist[r][pos] = r, and ctrl[1] = 1.  ``trie``: a ``PhraseTrie`` or a
+    ``PhraseForest`` -- ``term`` then names a phrase within its set."""
+    assert longest_of is not None
+    trie_beam_select_host(cand_edge, cand_total, fin_total, node, path, trie, eos, ids, hist, pool_phrase, pool_sum, pool_score, pool_len,
+                          pool_n, closed, counters, ctrl, W, P, 0, length_penalty, close_rule, gaps, pool_gaps, plen=plen,
+                          longest_of=np.asarray(longest_of))
+
+
 def phrase_beam_search_host(step_logits, prompt, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float,
-                            close_rule: bool = True):
+                            close_rule: bool = True, start: int = 0, longest: Optional[int] = None):
     """The whole search of ``search_phrases`` for ONE image on the host: ``step_logits(sequence)`` gives the raw fp32 logits row [V] that
     follows a token sequence (a list of ints, the prompt included).  W rows, each a trie node and an fp32 path sum: row 0 starts at the
     root with path 0, the others dead.  Depth t = 0, 1, ...: ``trie_beam_candidates_host`` over the live rows, one
     ``trie_beam_select_host`` call and ``beam_advance_host``; at most longest + 1 steps.  -> SimpleNamespace(phrase_index int64 [N],
     logprob f32 [N], scores f32 [N], lengths int32 [N]: the first N pool entries; steps; pool_n; gaps, pool_gaps:
     ``trie_beam_select_host``'s, and in ``gaps`` also, per row, the W-th kept child total minus the best one the row dropped).  A
-    search whose gaps all exceed a perturbation of the totals keeps its phrases and their order under it."""
+    search whose gaps all exceed a perturbation of the totals keeps its phrases and their order under it.  ``start`` / ``longest``: the
+    node row 0 starts at and the longest phrase below it -- the root and the longest phrase of the image's set in a ``PhraseForest``
+    (DESIGN.md 4x); 0 / None: a trie's root and its own ``longest``."""
     prompt = [int(t) for t in np.asarray(prompt).reshape(-1)]
-    P, longest = len(prompt), int(trie.longest)
+    P, longest = len(prompt), int(trie.longest if longest is None else longest)
     assert P >= 1 and 1 <= N <= W
     total = P + longest + 1
     f32, i32 = np.float32, np.int32
@@ -567,7 +612,7 @@ def phrase_beam_search_host(step_logits, prompt, trie: PhraseTrie, eos: int, W: 
     ids[:, :P] = prompt
     hist = np.repeat(np.arange(W, dtype=i32)[:, None], total, axis=1)
     node, path = np.full(W, -1, dtype=i32), np.zeros(W, dtype=f32)
-    node[0] = 0
+    node[0] = int(start)
     seqs = [list(prompt)] + [None] * (W - 1)
     pool_phrase, pool_sum = np.full((1, W), -1, dtype=i32), np.zeros((1, W), dtype=f32)
     pool_score, pool_len = np.full((1, W), BEAM_DEAD, dtype=f32), np.zeros((1, W), dtype=i32)

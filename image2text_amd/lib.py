@@ -114,6 +114,10 @@ SIGNATURES = {
     'i2t_trie_level_expand': [P, P, I, P, I, I, F, PF, I, PF, PF, PF, PI, PI, I, PI, PI, PI, I, I, PL, I, PI, PF, I, I, I, I, I],
     'i2t_trie_beam_candidates': [P, PF, I, PI, PF, PI, PI, PI, I, I, I, PI, PI, PF, PF, PF, I, I, I],
     'i2t_trie_beam_select': [P, PI, PF, PF, PI, PF, PI, PI, PI, I, I, I, PL, I, PI, I, PI, PF, PF, PI, PI, PI, PI, PI, PI, I, I, I, I, F],
+    'i2t_caption_trie_mask_ragged': [P, PF, I, PI, PI, PI, PI, I, I, I, PI, PF, PF, I, PI, PI, I, I, I],
+    'i2t_caption_trie_advance_ragged': [P, PL, I, PI, PI, PF, I, PF, PI, PI, PI, PI, I, I, I, PI, PI, PI, PF, I, PI, I, I, I],
+    'i2t_trie_beam_select_sets': [P, PI, PF, PF, PI, PF, PI, PI, PI, I, I, I, PL, I, PI, I, PI, PF, PF, PI, PI, PI, PI, PI, PI, I, I, I, PI, PI,
+                                  F],
     'i2t_gq_attention_fwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, PF, I, I, I, I, I, I, I, U, U, F, PI, PI, I, I],
     'i2t_gq_attention_bwd': [P, P, L, I, P, L, I, P, L, I, P, L, I, P, L, I, PF, PF, P, L, I, P, L, I, P, L, I, I, I, I, I, I, I, I, U, U, F, PI, PI,
                              I, U, U, F],
@@ -183,7 +187,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 _lib = None
 
 

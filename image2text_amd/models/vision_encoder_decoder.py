@@ -245,7 +245,7 @@ class VisionEncoderDecoder(nn.Module):
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
                           prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1,
-                          length_penalty=1.0, early_stopping=False, phrases=None):
+                          length_penalty=1.0, early_stopping=False, phrases=None, phrase_sets=None, phrase_set_index=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -324,14 +324,25 @@ class VisionEncoderDecoder(nn.Module):
         Refusals, before anything runs (``caption_plan.check_phrase_caption_args``): ValueError for an empty set or phrase, an id outside
         the vocabulary, the EOS inside a phrase, no ``eos_token_id``, ``max_new_tokens`` below the longest phrase + 1;
         NotImplementedError with ``prompt_lengths``, an active logits processor, ``num_beams`` > 1 or a non-causal decoder.
-        ``prompt_prefill='pass'`` works as without phrases.  None (the default) is the call without the argument, launch for launch."""
+        ``prompt_prefill='pass'`` works as without phrases.  None (the default) is the call without the argument, launch for launch.
+        ``phrase_sets`` / ``phrase_set_index`` give every image a phrase set of its own -- a VQA batch with a question and
+        an answer list per image: ``phrase_sets`` is a sequence of S >= 1 sets, each what ``phrases`` takes, and image b answers from set
+        ``phrase_set_index[b]`` (ints [B] in [0, S); None: S == B and image b uses set b; one answer list for all images is
+        ``phrase_sets=[answers], phrase_set_index=[0] * B``).  Unlike ``phrases`` it combines with ``prompt_lengths``: a row whose
+        column is still inside its prompt keeps its trie state.  Greedy or sampled, any ``num_return_sequences``, either
+        ``prompt_prefill``.  ``phrase_index`` indexes into the IMAGE'S OWN set (the lowest among duplicates); ``logprob`` stays the raw
+        log-likelihood of phrase + EOS.  Refusals, before anything runs (``caption_plan.check_phrase_set_caption_args``): ValueError for
+        ``phrases`` given too, ``phrase_set_index`` without ``phrase_sets``, what ``phrases`` refuses about a set (behind
+        'phrase_sets[s]: '), an index of the wrong length or outside [0, S), None with S != B, ``max_new_tokens`` below the longest
+        phrase of a set in use + 1; NotImplementedError with an active logits processor, ``num_beams`` > 1 or a non-causal decoder.
+        Without the two arguments the call is the one before they existed, launch for launch."""
         import numpy as np
         from ..decoding import CaptionBeamDecoder, CaptionDecoder, GeneratedCaptions, caption_facts, generate_by_recompute, plan_captions
         from ..decoding_host import apply_finish_rule_ragged
         B, P = prompt_ids.shape
         plan = plan_captions(caption_facts(self), B, P, max_new_tokens, eos_token_id, pad_token_id, num_return_sequences, temperature, top_k,
                              nucleus_p, seed, poll_every, prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens,
-                             num_beams, length_penalty, early_stopping, phrases)
+                             num_beams, length_penalty, early_stopping, phrases, phrase_sets, phrase_set_index)
         dev = next(self.parameters()).device
         prompt_ids = prompt_ids.to(dev)
         if plan.mode == 'beam':
@@ -384,7 +395,8 @@ class VisionEncoderDecoder(nn.Module):
                                                                      int(eos_token_id), images_per_pass)
 
     @torch.no_grad()
-    def search_phrases(self, images, prompt_ids, phrases, eos_token_id, num_beams=4, num_return_sequences=1, length_penalty=0.0, poll_every=8):
+    def search_phrases(self, images, prompt_ids, phrases=None, eos_token_id=None, num_beams=4, num_return_sequences=1, length_penalty=0.0,
+                       poll_every=8, phrase_sets=None, phrase_set_index=None, prompt_lengths=None):
         """The N best phrases of a closed set by beam search on the set's token trie (no counterpart in the reference) ->
         ``decoding.PhraseBeams(phrase_index [B, N], logprob [B, N], scores [B, N], lengths [B, N], exhaustive)``, best first.
         ``phrases`` is what ``generate_captions`` and ``score_phrases`` take: K >= 1 token-id sequences (or the ``PhraseTrie`` built of
@@ -400,9 +412,21 @@ class VisionEncoderDecoder(nn.Module):
         at W = 1 it is that walk.  Refusals, before anything runs (``caption_plan.check_phrase_search_args``): ValueError for
         everything ``generate_captions`` refuses about the set itself, W outside 1 .. 8, N outside 1 .. min(W, distinct phrases), a
         non-finite ``length_penalty``, prompt + longest phrase + 1 past the text window, a negative ``poll_every``; NotImplementedError
-        for a non-causal decoder and for sparse nano-mini blocks.  The call keeps a decoder state of its own."""
+        for a non-causal decoder and for sparse nano-mini blocks.  The call keeps a decoder state of its own.
+        ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths`` are ``generate_captions``' arguments of those names: a
+        phrase set and a prompt of its own length per image (``prompt_ids[b, :p_b]``; later columns are ignored).  ``phrase_index``
+        then indexes into the image's own set; N is at most W and at most the distinct phrases of the smallest set in use;
+        ``exhaustive`` says W >= the widest level of every set in use.  ``prompt_lengths`` needs ``phrase_sets`` (one list for all
+        images: ``phrase_sets=[answers], phrase_set_index=[0] * B``); ``phrases`` together with ``phrase_sets`` is a ValueError."""
         from ..decoding import PhraseBeamDecoder, caption_facts, check_phrase_search_args
         facts = caption_facts(self)
+        if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
+            sets, W, N, plen = check_phrase_search_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, num_beams,
+                                                        num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse,
+                                                        phrase_sets, phrase_set_index, prompt_lengths, prompt_ids.shape[0])
+            return self._decoder('_phrase_searcher', PhraseBeamDecoder).search_sets(
+                images, prompt_ids.to(next(self.parameters()).device), sets, int(eos_token_id), W, N, float(length_penalty), int(poll_every),
+                plen=plen)
         trie, W, N = check_phrase_search_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, num_beams,
                                               num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse)
         return self._decoder('_phrase_searcher', PhraseBeamDecoder).search(images, prompt_ids.to(next(self.parameters()).device), trie,

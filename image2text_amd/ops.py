@@ -838,6 +838,30 @@ def caption_trie_advance(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, ch
                                 done, node, phrase_index, tok_lp, tok_lp.stride(0), R, V)
 
 
+def caption_trie_mask_ragged(logits, ld, node, child_off, child_tok, term, eos, done, raw_lse, kept, len_ptr, plen, N, R, V):
+    """caption_trie_mask under ``prompt_lengths``: row r belongs to image r // N, and while *len_ptr < plen[r // N] (plen int32 [R / N])
+    its logits row stays raw and raw_lse[r] / kept[r] are not written (include/i2t.h::i2t_caption_trie_mask_ragged)"""
+    nodes, edges = _trie_args(child_off, child_tok, term)
+    assert kept.dim() == 2 and kept.stride(-1) == 1 and kept.shape[0] >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    assert node.is_contiguous() and node.numel() >= R
+    assert plen is None or (plen.is_contiguous() and (N < 1 or plen.numel() >= R // N))
+    _k.i2t_caption_trie_mask_ragged(logits, ld, node, child_off, child_tok, term, nodes, edges, int(eos), done, raw_lse, kept, kept.stride(0),
+                                    len_ptr, plen, int(N), R, V)
+
+
+def caption_trie_advance_ragged(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, eos, done, node,
+                                phrase_index, tok_lp, plen, N, R, V):
+    """caption_trie_advance under ``prompt_lengths``: a row in a forced column (*len_ptr < plen[r // N]) keeps node, phrase_index and
+    tok_lp[r][len] (include/i2t.h::i2t_caption_trie_advance_ragged)"""
+    nodes, edges = _trie_args(child_off, child_tok, term, child_next)
+    assert node.is_contiguous() and phrase_index.is_contiguous()
+    assert node.numel() >= R and phrase_index.numel() >= R and finished.numel() >= R and raw_lse.is_contiguous() and raw_lse.numel() >= R
+    assert tok_lp.dim() == 2 and tok_lp.stride(-1) == 1 and tok_lp.shape[0] >= R
+    assert plen is None or (plen.is_contiguous() and (N < 1 or plen.numel() >= R // N))
+    _k.i2t_caption_trie_advance_ragged(ids, ids_ld, len_ptr, finished, logits, ld, raw_lse, child_off, child_tok, child_next, term, nodes, edges,
+                                       int(eos), done, node, phrase_index, tok_lp, tok_lp.stride(0), plen, int(N), R, V)
+
+
 def rows_lse(logits, ld, lse, R, V):
     """lse[r] = the log-sum-exp of columns [0, V) of fp32 logits row r, in caption_trie_mask's reduction order; the rows are only read
     (include/i2t.h::i2t_rows_lse)"""
@@ -925,6 +949,23 @@ def trie_beam_select(cand_edge, cand_total, fin_total, node, path, child_tok, ch
     _k.i2t_trie_beam_select(cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, term.numel(), child_tok.numel(), int(eos),
                             ids, ids.stride(0), hist, hist.stride(0), pool_phrase, pool_sum, pool_score, pool_len, pool_n, closed, pos_ptr,
                             len_ptr, ctrl, B, W, int(P), int(longest), float(length_penalty))
+
+
+def trie_beam_select_sets(cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, eos, ids, hist, pool_phrase, pool_sum,
+                          pool_score, pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, B, W, P, plen, longest_of, length_penalty):
+    """trie_beam_select with a prompt length and a longest phrase per image: plen int32 [B] (None: every prompt P long), longest_of
+    int32 [B]; an image whose prompt reaches past the column only records the identity history column
+    (include/i2t.h::i2t_trie_beam_select_sets)"""
+    assert child_tok.is_contiguous() and child_next.is_contiguous() and term.is_contiguous() and child_next.numel() == child_tok.numel()
+    assert cand_edge.is_contiguous() and cand_total.is_contiguous() and cand_edge.shape == (B * W, W) and cand_total.shape == (B * W, W)
+    assert all(t.is_contiguous() and t.numel() == B * W for t in (fin_total, node, path, pool_phrase, pool_sum, pool_score, pool_len))
+    assert pool_n.numel() == B and closed.numel() == B and ctrl.numel() >= 2
+    assert ids.shape[0] == B * W and hist.shape[0] == B * W and ids.stride(-1) == 1 and hist.stride(-1) == 1
+    assert plen is None or (plen.is_contiguous() and plen.numel() >= B)
+    assert longest_of is None or (longest_of.is_contiguous() and longest_of.numel() >= B)
+    _k.i2t_trie_beam_select_sets(cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, term.numel(), child_tok.numel(),
+                                 int(eos), ids, ids.stride(0), hist, hist.stride(0), pool_phrase, pool_sum, pool_score, pool_len, pool_n, closed,
+                                 pos_ptr, len_ptr, ctrl, B, W, int(P), plen, longest_of, float(length_penalty))
 
 
 def gemm_lse(a, b, stats, M, N, K, scale=1.0):

@@ -88,6 +88,75 @@ def phrase_trie(phrases, eos, vocab: int, max_new_tokens: int) -> PhraseTrie:
                       max(len(d) for d in kids), longest, np.array(ends, dtype=i32))
 
 
+class PhraseForest(NamedTuple):
+    """S phrase sets as ONE flat CSR (``phrase_forest``): the sets' tries laid end to end, so the device kernels -- which
+    index nodes blindly -- walk it as they walk a trie; a row that starts at ``roots[s]`` never leaves set s.  All arrays numpy int32.
+    It has what the drivers and the host statements read of a ``PhraseTrie``: ``nodes``, ``edges``, ``children``, ``max_fanout``."""
+    child_off: np.ndarray               # [nodes + 1]
+    child_tok: np.ndarray               # [edges]: ascending within a node
+    child_next: np.ndarray              # [edges]: a node of the same set
+    term: np.ndarray                    # [nodes]: the index WITHIN ITS SET of the phrase that ends at the node (the lowest among duplicates), or -1
+    roots: np.ndarray                   # [S]: the root of set s; roots[0] == 0
+    longest: np.ndarray                 # [S]: the tokens of set s's longest phrase
+    widest: np.ndarray                  # [S]: the nodes of set s's widest level (the root's level counts)
+    max_fanout: int                     # the largest number of children of a node, over all sets
+    distinct: np.ndarray                # [S]: the distinct phrases of set s
+
+    @property
+    def nodes(self) -> int:
+        return int(self.term.shape[0])
+
+    @property
+    def edges(self) -> int:
+        return int(self.child_tok.shape[0])
+
+    @property
+    def sets(self) -> int:
+        return int(self.roots.shape[0])
+
+    def children(self, node: int):
+        """-> (tokens, next nodes) of ``node``"""
+        lo, hi = int(self.child_off[node]), int(self.child_off[node + 1])
+        return self.child_tok[lo:hi], self.child_next[lo:hi]
+
+
+def widest_level(trie, root: int = 0) -> int:
+    """the largest number of nodes at one depth below ``root`` (the root's level counts: at least 1)"""
+    widest, level = 1, [int(root)]
+    while level:
+        widest = max(widest, len(level))
+        level = [int(c) for nd in level for c in trie.children(nd)[1]]
+    return widest
+
+
+def phrase_forest(sets, eos, vocab: int, max_new_tokens: int = 1 << 30) -> PhraseForest:
+    """``sets``: S >= 1 phrase sets, each what ``phrase_trie`` takes -> their tries laid end to end (set 0 first, so its root is node 0
+    and a one-set forest has ``phrase_trie``'s arrays element for element).  ValueError: no set; whatever ``phrase_trie`` refuses about
+    set s, in its words behind 'phrase_sets[s]: '.  ``max_new_tokens`` is held against EVERY set here; a caller that knows which sets
+    are in use (``caption_plan``) leaves the default and checks those alone."""
+    if isinstance(sets, torch.Tensor):
+        sets = sets.detach().cpu().tolist()
+    sets = list(sets)
+    if not sets:
+        raise ValueError('phrase_sets is empty: at least one set is needed')
+    tries = []
+    for s, one in enumerate(sets):
+        try:
+            tries.append(phrase_trie(one, eos, vocab, max_new_tokens))
+        except ValueError as e:
+            raise ValueError(f'phrase_sets[{s}]: {e}') from None
+    i32 = np.int32
+    node0 = np.cumsum([0] + [t.nodes for t in tries])
+    edge0 = np.cumsum([0] + [t.edges for t in tries])
+    off = np.concatenate([t.child_off[:-1].astype(np.int64) + edge0[s] for s, t in enumerate(tries)] + [edge0[-1:]]).astype(i32)
+    tok = np.concatenate([t.child_tok for t in tries]).astype(i32)
+    nxt = np.concatenate([t.child_next.astype(np.int64) + node0[s] for s, t in enumerate(tries)]).astype(i32)
+    term = np.concatenate([t.term for t in tries]).astype(i32)
+    return PhraseForest(off, tok, nxt, term, node0[:-1].astype(i32), np.array([t.longest for t in tries], dtype=i32),
+                        np.array([widest_level(t) for t in tries], dtype=i32), max(t.max_fanout for t in tries),
+                        np.array([int((t.term >= 0).sum()) for t in tries], dtype=i32))
+
+
 class TrieLevel(NamedTuple):
     """The nodes of one depth of a phrase trie (``trie_levels``); all arrays numpy int32."""
     nodes: np.ndarray                   # [n_t]: the nodes at depth t, ascending (node order)

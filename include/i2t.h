@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 15
+#define I2T_ABI_VERSION 16
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -546,6 +546,34 @@ int i2t_trie_beam_select(void* stream, const int* cand_edge, const float* cand_t
                          const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos, int64_t* ids, int ids_ld,
                          int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len, int* pool_n, int* closed,
                          const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P, int longest, float length_penalty);
+
+/* A prompt length and a phrase set per image (generate_captions' / search_phrases' phrase_sets; DESIGN.md 4x, ABI 16).  The sets' tries
+ * lie end to end in the CSR arrays above (phrase_trie.phrase_forest): the kernels index nodes blindly, so a row that starts at its
+ * set's root never leaves that set, and term holds the phrase index WITHIN the set.  The start nodes are the caller's (no kernel).
+ *   i2t_caption_trie_mask_ragged / i2t_caption_trie_advance_ragged: the two kernels above with row r belonging to image r / N (R % N
+ *     == 0, N >= 1) whose prompt is plen[r / N] long (int32 [R / N], device memory, base on 16 bytes).  While *len_ptr < plen[r / N]
+ *     the row sits in a forced column: the mask leaves its logits row raw and writes neither raw_lse[r] nor kept[r]; the advance
+ *     leaves node[r], phrase_index[r] and tok_lp[r][len].  The chooser still runs on the row; i2t_caption_finish_ragged replaces its
+ *     token and log-prob afterwards.  Every other row: exactly the kernels above.
+ *   i2t_trie_beam_select_sets: i2t_trie_beam_select with plen int32 [B] and longest_of int32 [B] (device memory, bases on 16 bytes) in
+ *     place of the scalars; plen null: every image's prompt is P long (with plen given the kernel does not read P; the entry point
+ *     still holds it to 1 <= P and P + 2 <= ids_ld, so pass the longest prompt).  For image b, t = *len_ptr - plen[b].  t < 0 is a forced
+ *     column: pool, node, path, closed and ids are not touched (the caller put the prompt into ids), hist[b W + w][*pos_ptr] = b W + w
+ *     for every row and the image stores 1 into ctrl[1].  t >= 0: the rule above with longest_of[b] in the guard, the close test and
+ *     the column bound.  No id column at or past ids_ld and no history column outside [0, hist_ld) is written whatever the tables
+ *     hold.  i2t_trie_beam_candidates runs unchanged on all rows; a forced image's candidates are ignored.  P >= 1, P + 2 <= ids_ld. */
+int i2t_caption_trie_mask_ragged(void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
+                                 const int* term, int nodes, int edges, int eos, const int* done, float* raw_lse, float* kept, int kept_ld,
+                                 const int* len_ptr, const int* plen, int N, int R, int V);
+int i2t_caption_trie_advance_ragged(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const int* finished,
+                                    const float* logits, int ld, const float* raw_lse, const int* child_off, const int* child_tok,
+                                    const int* child_next, const int* term, int nodes, int edges, int eos, const int* done, int* node,
+                                    int* phrase_index, float* tok_lp, int lp_ld, const int* plen, int N, int R, int V);
+int i2t_trie_beam_select_sets(void* stream, const int* cand_edge, const float* cand_total, const float* fin_total, int* node, float* path,
+                              const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos, int64_t* ids,
+                              int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len,
+                              int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P,
+                              const int* plen, const int* longest_of, float length_penalty);
 
 /* -----------------------------------------------------------------------------------------------------------
  * The nano-mini block family (reference training_configs/gpu/nano-mini.yaml).

@@ -23,7 +23,13 @@ the fp32-logits head: the difference is the two new launches alone).
 
 The comparison is instead: generate_captions without phrases for phrase-len + 1 new tokens against
 generate_captions(phrases=K random phrases of phrase-len tokens), greedy N = 1 and sampling N = 4, alternating in one process; the
-constrained call includes building the trie on the host and copying it to the device."""
+constrained call includes building the trie on the host and copying it to the device.
+
+    python tools/bench_generate_captions.py --phrase-sets 8 [--phrases 3000] [--phrase-len 3]
+
+The comparison is instead: generate_captions(phrases=set 0), one set for all images, against
+generate_captions(phrase_sets=S sets of K random phrases each, image b answering from set b mod S), greedy N = 1 and sampling N = 4,
+alternating in one process; both calls include building their tries on the host and copying them to the device."""
 import argparse
 import os
 import statistics
@@ -143,8 +149,36 @@ def phrases_comparison(a):
             print(f'  N = {N} {"greedy  " if N == 1 else "sampling"} {k:13s} {fmt(ts[k])}   replays {replays[k]}', flush=True)
 
 
+def phrase_sets_comparison(a):
+    """generate_captions(phrases=set 0) against generate_captions(phrase_sets=S sets, image b from set b mod S), greedy N = 1 and
+    sampling N = 4"""
+    B, K, T, S = a.batch, a.phrases or 3000, a.phrase_len, a.phrase_sets
+    eos = 50256
+    g = torch.Generator().manual_seed(1)
+    sets = [torch.randint(0, eos, (K, T), generator=g).tolist() for _ in range(S)]
+    index = [b % S for b in range(B)]
+    print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {S} sets of {K} phrases of {T} tokens, '
+          f'{a.rounds} alternating rounds', flush=True)
+    m, images, prompt = fresh(B)
+    for N, mode in ((1, dict(top_k=1)), (4, SAMPLING)):
+        kw = dict(max_new_tokens=T + 1, eos_token_id=eos, num_return_sequences=N, seed=3, **mode)
+        forms = {'one set': lambda: m.generate_captions(images, prompt, phrases=sets[0], **kw),
+                 f'{S} sets, per image': lambda: m.generate_captions(images, prompt, phrase_sets=sets, phrase_set_index=index, **kw)}
+        ts, replays = {k: [] for k in forms}, {}
+        for fn in forms.values():
+            fn()
+        for _ in range(a.rounds):
+            for k, fn in forms.items():
+                t, _ = wall(fn)
+                ts[k].append(t)
+                replays[k] = m._captioner.last_replays
+        for k in forms:
+            print(f'  N = {N} {"greedy  " if N == 1 else "sampling"} {k:20s} {fmt(ts[k])}   replays {replays[k]}', flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--phrase-sets', type=int, default=None, help='S: compare phrases=one set against phrase_sets=S sets (DESIGN.md 4x)')
     ap.add_argument('--phrases', type=int, default=None, help='K: compare against generate_captions(phrases=K random phrases) (DESIGN.md 4u)')
     ap.add_argument('--phrase-len', type=int, default=3)
     ap.add_argument('--batch', type=int, default=256)
@@ -155,6 +189,8 @@ def main():
     ap.add_argument('--suppress', type=str, default=None, help='comma-separated token ids')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_generate_captions.py measures on the MI355X; there is nothing to report without one'
+    if a.phrase_sets:
+        return phrase_sets_comparison(a)
     if a.phrases:
         return phrases_comparison(a)
     procs = {}

@@ -7,7 +7,13 @@ K synthetic phrases of one to three tokens whose first tokens come from a pool o
 hundreds of nodes (printed).  score_phrases and search_phrases (W = 4 and W = 8, N = W, penalty 0) alternate ROUNDS times in one process
 on the same model and images after a warm-up of each; every call includes building its trie on the host and copying it to the device.
 Prints wall time per call (median [min .. max] ms, synchronised), each search's time over score_phrases', the full steps it replayed,
-and how many of score_phrases' first choices lead the search's result.  Nothing is asserted about a time."""
+and how many of score_phrases' first choices lead the search's result.  Nothing is asserted about a time.
+
+    python tools/bench_phrase_search.py --phrase-sets 8 [--batch 16] [--phrases 1000] [--first 300] [--rounds 3]
+
+The comparison is instead: search_phrases(phrases=set 0), one set for all images, against
+search_phrases(phrase_sets=S synthetic sets of K phrases each, image b answering from set b mod S), W = 4 and W = 8, alternating in one
+process after a warm-up of each; both calls include building their tries on the host and copying them to the device."""
 import argparse
 import os
 import statistics
@@ -41,8 +47,32 @@ def synthetic_phrases(K, first, eos, g):
     return [list(p) for p in sorted(seen)]
 
 
+def phrase_sets_comparison(a, m, images, prompt, eos, g):
+    B, K, S = a.batch, a.phrases, a.phrase_sets
+    sets = [synthetic_phrases(K, a.first, eos, g) for _ in range(S)]
+    index = [b % S for b in range(B)]
+    print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {S} sets of {K} phrases of 1 .. 3 tokens, '
+          f'{a.rounds} alternating rounds', flush=True)
+    forms = {}
+    for W in (4, 8):
+        forms[f'W={W} one set'] = lambda W=W: m.search_phrases(images, prompt, sets[0], eos, num_beams=W, num_return_sequences=W)
+        forms[f'W={W} {S} sets, per image'] = lambda W=W: m.search_phrases(images, prompt, eos_token_id=eos, num_beams=W, num_return_sequences=W,
+                                                                           phrase_sets=sets, phrase_set_index=index)
+    ts, replays = {k: [] for k in forms}, {}
+    for fn in forms.values():
+        fn()
+    for _ in range(a.rounds):
+        for k, fn in forms.items():
+            t, _ = wall(fn)
+            ts[k].append(t)
+            replays[k] = m._phrase_searcher.last_replays
+    for k in forms:
+        print(f'  {k:26s} {statistics.median(ts[k]):9.1f} [{min(ts[k]):.1f} .. {max(ts[k]):.1f}] ms   {replays[k]} full steps', flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--phrase-sets', type=int, default=None, help='S: compare phrases=one set against phrase_sets=S sets (DESIGN.md 4x)')
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--phrases', type=int, default=1000)
     ap.add_argument('--first', type=int, default=300)
@@ -58,6 +88,8 @@ def main():
     phrases = synthetic_phrases(K, a.first, eos, g)
     images = torch.randn(B, 3, 224, 224, generator=g).to('cuda')
     prompt = torch.full((B, 1), eos, dtype=torch.long, device='cuda')
+    if a.phrase_sets:
+        return phrase_sets_comparison(a, m, images, prompt, eos, g)
     wmax = trie_levels(phrase_trie(phrases, eos, m._engine.dec.V, 4)).wmax
     print(f'device: {torch.cuda.get_device_name(0)}; nano-224 shape, random weights, {B} images, {K} phrases of 1 .. 3 tokens (widest trie '
           f'level {wmax} rows per image), {a.rounds} alternating rounds', flush=True)
