@@ -7,6 +7,9 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libi2t_hip.so')
 SOURCES = ['abi.cpp', 'comm.cpp', 'gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'conv.hip', 'conv_mfma.hip', 'decode.hip', 'constrain.hip', 'sample.hip', 'beam.hip',
            'attention_g.hip', 'family.hip', 'grouped.hip', 'llama.hip', 'lora.hip', 'vit.hip', 'fp8.hip']
+# every header a source may include: _stale and _build both read this list, so a library is rebuilt whenever one of them changes
+HEADERS = [os.path.join(CSRC, h) for h in ('common.h', 'select_common.h', 'attention_common.h', 'attention_route.h', 'gemm_route.h')] + [
+    os.path.join(CSRC, '..', '..', 'include', 'i2t.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast']
 # per-file additions.  attention: keep MFMA accumulators in VGPRs -- the softmax rescales them every key tile, and the
 # AGPR form cost ~110 v_accvgpr_read/write per tile in kernels that are VALU-bound
@@ -17,9 +20,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'attention_route.h'), os.path.join(CSRC, 'gemm_route.h'),
-                                                      os.path.join(CSRC, '..', '..', 'include', 'i2t.h')]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -38,8 +39,7 @@ def _build(verbose: bool, force_all: bool = False) -> str:
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     objs = []
     procs = []
-    headers = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'attention_route.h'), os.path.join(CSRC, 'gemm_route.h'), os.path.join(CSRC, '..', '..', 'include', 'i2t.h'),
-               os.path.abspath(__file__)]
+    headers = HEADERS + [os.path.abspath(__file__)]
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(CSRC, os.path.splitext(s)[0] + '.o')

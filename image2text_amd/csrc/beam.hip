@@ -7,21 +7,17 @@
 // parent.  Each position of each physical row is written once, so no entry a live beam points at is ever overwritten.  A sparse
 // layer caches its kept positions only (slot = rank among them): key s of beam r is at (hist[r][slot_pos[s]], s), and a slot
 // written again before a kept token lands there is named by no history.
-#include "common.h"
+#include "select_common.h"
 
 namespace {
 
-__device__ __forceinline__ unsigned bmix32(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
 // counter-based uniform in (0, 1) on a grid of 2^-23, a pure function of (seed, step, row, index, salt); image2text_amd/rng.py::beam_uniform
 // is the host replica.  salt 0: candidate draws (row = beam row, index = token id); salt 1: consolidation (row = caption, index =
 // flat candidate w * E + e).
 __device__ __forceinline__ float beam_uniform(const unsigned* seed, unsigned step, unsigned row, unsigned index, unsigned salt) {
-    const unsigned h1 = bmix32(seed[0] ^ (row * 0x9E3779B9u));
-    const unsigned h2 = bmix32(h1 + seed[1] + step * 0x85EBCA6Bu + salt * 0x27D4EB2Fu);
-    const unsigned h = bmix32(h2 + index * 0x165667B1u);
+    const unsigned h1 = mix32(seed[0] ^ (row * 0x9E3779B9u));
+    const unsigned h2 = mix32(h1 + seed[1] + step * 0x85EBCA6Bu + salt * 0x27D4EB2Fu);
+    const unsigned h = mix32(h2 + index * 0x165667B1u);
     return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);     // exact in fp32: 23 bits + 1/2
 }
 // Gumbel noise: key = logit + gumbel; the top-k keys are k draws without replacement, in draw order, from softmax(logits)
@@ -31,15 +27,13 @@ __device__ __forceinline__ unsigned okey(float f) {            // monotone float
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-// (value descending, index ascending)
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 constexpr int BC_THREADS = 1024, BC_MAX_E = 16;
 
 // One workgroup per beam row.  The row is streamed from the logits (fp32, 16-byte loads, every lane visits its columns in
 // ascending order): the top-k threshold by bisection on the order-preserving integer image of the scores (only with a crop, 32
 // block-wide counts), then ONE pass that keeps the online max / sum of exp of the scores and a per-lane list of the E best keys
-// (raw score or score / T + Gumbel noise), merged across the block in E rounds.
+// (raw score or score / T + Gumbel noise; select_common.h's sorted list), merged across the block in E rounds.
 __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float* __restrict__ logits, int ld, const int64_t* __restrict__ ids,
                                                                      int ids_ld, const int* __restrict__ len_ptr, const int* __restrict__ done,
                                                                      const int* __restrict__ ngram_sizes, int n_sizes, int V, int E,
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float
     __shared__ int sh_i[BC_THREADS / 64];
     __shared__ int sel[BC_MAX_E];
     if (*done) return;                                     // every beam has ended: the replays that are left do nothing
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.x, tid = threadIdx.x;
     const int len = *len_ptr;
     const int64_t* row = ids + (size_t)r * ids_ld;
     const float* src = logits + (size_t)r * ld;
@@ -84,8 +78,7 @@ __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float
     float m = -INFINITY, z = 0.f;
     float kv[BC_MAX_E];
     int ki[BC_MAX_E];
-#pragma unroll
-    for (int j = 0; j < BC_MAX_E; ++j) { kv[j] = -INFINITY; ki[j] = 0x7fffffff; }
+    topk_clear(kv, ki);
     float last = -INFINITY;                                 // the list's E-th key
     for (int c4 = tid * 4; c4 < V; c4 += BC_THREADS * 4) {
         const f32x4 q = *reinterpret_cast<const f32x4*>(src + c4);
@@ -105,17 +98,7 @@ __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float
             }
             const float key = sampled ? y + gumbel(beam_uniform(seed, (unsigned)len, (unsigned)r, (unsigned)c, 0u)) : y;
             if (key > last) {                               // strictly: an earlier (lower) column keeps a tie
-                float cv = key;
-                int ci = c;
-#pragma unroll
-                for (int j = 0; j < BC_MAX_E; ++j) {
-                    if (j < E && better(cv, ci, kv[j], ki[j])) {
-                        const float tv = kv[j];
-                        const int ti = ki[j];
-                        kv[j] = cv; ki[j] = ci;
-                        cv = tv; ci = ti;
-                    }
-                }
+                topk_insert(kv, ki, E, key, c);
 #pragma unroll
                 for (int j = 0; j < BC_MAX_E; ++j) last = j < E ? kv[j] : last;      // kv[E - 1] without a dynamic register index
             }
@@ -126,37 +109,11 @@ __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float
     const float logz = logf(zs);
 
     // ---- E rounds of a block arg-max over the lanes' list heads (key descending, column ascending)
-    for (int j = 0; j < E; ++j) {
-        float bv = kv[0];
-        int bi = ki[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { sh_v[wave] = bv; sh_i[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < BC_THREADS / 64; ++w)
-                if (better(sh_v[w], sh_i[w], bv, bi)) { bv = sh_v[w]; bi = sh_i[w]; }
-            sel[j] = bi;
-            redi[0] = bi;
-        }
-        __syncthreads();
-        const int win = redi[0];
-        if (win != 0x7fffffff && ki[0] == win) {            // the owner of the winning column pops its head
-#pragma unroll
-            for (int t = 0; t < BC_MAX_E - 1; ++t) { kv[t] = kv[t + 1]; ki[t] = ki[t + 1]; }
-            kv[BC_MAX_E - 1] = -INFINITY;
-            ki[BC_MAX_E - 1] = 0x7fffffff;
-        }
-        __syncthreads();
-    }
+    for (int j = 0; j < E; ++j) topk_round<BC_THREADS>(kv, ki, sh_v, sh_i, &redi[0], [&](float, int bi) { sel[j] = bi; });
     if (tid < E) {
         int tok = sel[tid];
         float lp = -INFINITY;                               // fewer than E allowed columns: token 0 at log-probability -inf
-        if (tok == 0x7fffffff) tok = 0;
+        if (tok == TOPK_NONE) tok = 0;
         else lp = (sampled ? src[tok] / temperature : src[tok]) - gm - logz;
         if (raw_tok) raw_tok[(size_t)r * E + tid] = tok;
         if (eos >= 0) {                                     // the EOS rule: an ended beam pads with EOS for free
@@ -175,9 +132,8 @@ __global__ __launch_bounds__(BC_THREADS) void beam_candidates_kernel(const float
 
 constexpr int CS_THREADS = 256, CS_MAX_W = 16, CS_MAX_WE = 1024;
 
-// One workgroup per caption: the W survivors of its W x E candidates, then the survivors' id rows and history rows.  Every
-// thread owns a set of columns and moves column t of the W parents into column t of the W children through registers, so no
-// column is read after it was overwritten.
+// One workgroup per caption: the W survivors of its W x E candidates (wave_rank_rounds), then the survivors' id rows and history
+// rows (move_rows: no column is read after it was overwritten).
 __global__ __launch_bounds__(CS_THREADS) void beam_consolidate_kernel(const int* __restrict__ cand_tok, const float* __restrict__ cand_lp,
                                                                       float* __restrict__ scores, int64_t* __restrict__ ids, int ids_ld,
                                                                       int* __restrict__ hist, int hist_ld, int* __restrict__ has_eos,
@@ -202,22 +158,7 @@ __global__ __launch_bounds__(CS_THREADS) void beam_consolidate_kernel(const int*
         taken[j] = 0;
     }
     __syncthreads();
-    if (tid < 64) {                                          // W rounds of a wave arg-max (key descending, flat index ascending)
-        for (int k = 0; k < W; ++k) {
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            for (int j = tid; j < WE; j += 64)
-                if (!taken[j] && better(key[j], j, bv, bi)) { bv = key[j]; bi = j; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (tid == 0) pick[k] = bi;
-            if (bi != 0x7fffffff && (bi & 63) == tid) taken[bi] = 1;    // the lane that scans column bi marks it itself
-        }
-    }
+    wave_rank_rounds(key, taken, pick, WE, W);               // (key descending, flat index ascending)
     __syncthreads();
     if (tid < W) {
         const int j = pick[tid], w = j / E;
@@ -228,24 +169,8 @@ __global__ __launch_bounds__(CS_THREADS) void beam_consolidate_kernel(const int*
         if (raw_pick) raw_pick[r0 + tid] = j;
     }
     __syncthreads();
-    int64_t vi[CS_MAX_W];
-    for (int t = tid; t < len; t += CS_THREADS) {
-#pragma unroll
-        for (int w = 0; w < CS_MAX_W; ++w)
-            if (w < W) vi[w] = ids[(size_t)par[w] * ids_ld + t];
-#pragma unroll
-        for (int w = 0; w < CS_MAX_W; ++w)
-            if (w < W) ids[(size_t)(r0 + w) * ids_ld + t] = vi[w];
-    }
-    int vh[CS_MAX_W];
-    for (int t = tid; t < pos; t += CS_THREADS) {
-#pragma unroll
-        for (int w = 0; w < CS_MAX_W; ++w)
-            if (w < W) vh[w] = hist[(size_t)par[w] * hist_ld + t];
-#pragma unroll
-        for (int w = 0; w < CS_MAX_W; ++w)
-            if (w < W) hist[(size_t)(r0 + w) * hist_ld + t] = vh[w];
-    }
+    move_rows<CS_MAX_W>(ids, ids_ld, par, r0, W, len, CS_THREADS);
+    move_rows<CS_MAX_W>(hist, hist_ld, par, r0, W, pos, CS_THREADS);
     if (tid < W) {
         const int c = r0 + tid;
         ids[(size_t)c * ids_ld + len] = tok[tid];
@@ -268,8 +193,8 @@ constexpr int PS_THREADS = 256, PS_MAX_W = 8, PS_MAX_WE = 2 * PS_MAX_W * PS_MAX_
 // w * E + e first); a candidate HITS when its token is eos or it is the max_new-th emitted token.  Hits ranked below W are offered to
 // the image's pool of finished captions at total / powf(emitted, length_penalty); the pool keeps its W best, sorted, an entry it
 // already holds before a new one of the same score.  The first W candidates that do not hit become the running beams.  Pool rows and
-// running rows are moved a column at a time through registers -- the pool first, it reads the parents' rows --, so no column is
-// read after it was overwritten.  An image closes at the bound, with early_stopping once its pool is full, and without it once the
+// running rows (move_rows) are moved a column at a time through registers -- the pool first, it reads the parents' rows --, so no
+// column is read after it was overwritten.  An image closes at the bound, with early_stopping once its pool is full, and without it once the
 // best running total / powf(emitted, length_penalty) no longer exceeds the full pool's worst score; a closed image's block returns at
 // once, and every open image stores the same 1 into ctrl[1], so the word needs no atomic.
 __global__ __launch_bounds__(PS_THREADS) void beam_pool_select_kernel(const int* __restrict__ cand_tok, const float* __restrict__ cand_lp,
@@ -301,22 +226,7 @@ __global__ __launch_bounds__(PS_THREADS) void beam_pool_select_kernel(const int*
         taken[j] = 0;
     }
     __syncthreads();
-    if (tid < 64) {                                          // 2 W rounds of a wave arg-max (total descending, flat index ascending)
-        for (int k = 0; k < E; ++k) {
-            float bv = -INFINITY;
-            int bi = 0x7fffffff;
-            for (int j = tid; j < WE; j += 64)
-                if (!taken[j] && better(tot[j], j, bv, bi)) { bv = tot[j]; bi = j; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-            }
-            if (tid == 0) pick[k] = bi;
-            if (bi != 0x7fffffff && (bi & 63) == tid) taken[bi] = 1;
-        }
-    }
+    wave_rank_rounds(tot, taken, pick, WE, E);               // (total descending, flat index ascending)
     __syncthreads();
     if (tid == 0) {
         const int emitted = len + 1 - P;
@@ -331,7 +241,7 @@ __global__ __launch_bounds__(PS_THREADS) void beam_pool_select_kernel(const int*
         }
         for (int k = 0; k < E; ++k) {
             const int j = pick[k];
-            if (j == 0x7fffffff) continue;                   // NaN totals only: nothing ranks
+            if (j == TOPK_NONE) continue;                   // NaN totals only: nothing ranks
             const int w = j / E;
             const int tk = cand_tok[(size_t)(r0 + w) * E + (j - w * E)];
             const float lpv = cand_lp[(size_t)(r0 + w) * E + (j - w * E)];
@@ -401,33 +311,9 @@ __global__ __launch_bounds__(PS_THREADS) void beam_pool_select_kernel(const int*
     }
     __syncthreads();
     if (flags[1] && len + 1 >= total_cols) return;           // at the bound nothing runs on: the rows stay
-    {
-        int64_t vi[PS_MAX_W];
-        float vf[PS_MAX_W];
-        for (int t = tid; t < len; t += PS_THREADS) {
-#pragma unroll
-            for (int w = 0; w < PS_MAX_W; ++w)
-                if (w < W) {
-                    vi[w] = ids[(size_t)c_par[w] * ids_ld + t];
-                    vf[w] = tok_lp[(size_t)c_par[w] * lp_ld + t];
-                }
-#pragma unroll
-            for (int w = 0; w < PS_MAX_W; ++w)
-                if (w < W) {
-                    ids[(size_t)(r0 + w) * ids_ld + t] = vi[w];
-                    tok_lp[(size_t)(r0 + w) * lp_ld + t] = vf[w];
-                }
-        }
-        int vh[PS_MAX_W];
-        for (int t = tid; t < pos; t += PS_THREADS) {
-#pragma unroll
-            for (int w = 0; w < PS_MAX_W; ++w)
-                if (w < W) vh[w] = hist[(size_t)c_par[w] * hist_ld + t];
-#pragma unroll
-            for (int w = 0; w < PS_MAX_W; ++w)
-                if (w < W) hist[(size_t)(r0 + w) * hist_ld + t] = vh[w];
-        }
-    }
+    move_rows<PS_MAX_W>(ids, ids_ld, c_par, r0, W, len, PS_THREADS);
+    move_rows<PS_MAX_W>(tok_lp, lp_ld, c_par, r0, W, len, PS_THREADS);
+    move_rows<PS_MAX_W>(hist, hist_ld, c_par, r0, W, pos, PS_THREADS);
     if (tid < W) {
         const int c = r0 + tid;
         ids[(size_t)c * ids_ld + len] = c_tok[tid];

@@ -128,11 +128,11 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 // v_mul_lo_u32 is quarter rate: at two per hash the hash was ~half of the attention kernels' VALU time (they are VALU-bound)
 // and a per-element hash cost more than the MFMA loop of a K = 512 GEMM.  Single-multiply mixers were tried and fail the
 // lag-correlation screen by hundreds of sigma (tests/test_host_cpu.py::test_dropout_rule_statistics holds the screen).
-__device__ __forceinline__ unsigned dropout_hash(unsigned key, unsigned quad) {
-    unsigned x = quad ^ key;
+__device__ __forceinline__ unsigned mix32(unsigned x) {                  // the lowbias32 mixer (beam.hip's beam_uniform chains three)
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
+__device__ __forceinline__ unsigned dropout_hash(unsigned key, unsigned quad) { return mix32(quad ^ key); }
 __device__ __forceinline__ bool dropout_keep(unsigned key, unsigned idx, unsigned thr8) {
     const unsigned h = dropout_hash(key, idx >> 2);
     return ((h >> (8u * (idx & 3u))) & 0xffu) >= thr8;

@@ -3,7 +3,7 @@
 // children of node n are edges child_off[n] .. child_off[n + 1), child_tok ascending, child_next the node an edge leads to, term[n] the
 // index of the phrase that ends at n or -1; node 0 is the root.  Every row keeps its node in node[r].  Plain loads and vector stores,
 // no atomics; nothing is read or written once *done is set.
-#include "common.h"
+#include "select_common.h"
 
 namespace {
 
@@ -20,8 +20,8 @@ __device__ __forceinline__ void node_edges(const int* __restrict__ child_off, in
     fan = fan < 0 ? 0 : fan;
 }
 
-// The pre-pass, between the lm_head GEMM and the chooser: one workgroup per row.  Pass A: the RAW row's (max, sum exp) -- a thread's
-// chain, a fixed xor tree, the waves in order (caption_logits_process_kernel's shape: bit-reproducible) -> raw_lse[r]; in the same pass
+// The pre-pass, between the lm_head GEMM and the chooser: one workgroup per row.  Pass A: the RAW row's log-sum-exp
+// (select_common.h's row_lse_partials / lse_waves_merge: bit-reproducible) -> raw_lse[r]; in the same pass
 // kept[r][i] = z[child_tok[off + i]] for the node's children and kept[r][fan] = z[eos] at a terminal node, all raw since nothing has
 // been written.  Barrier.  Pass B: -inf over columns [0, V), 16-byte stores; columns V .. ld are not touched.  Barrier.  Pass C: the
 // kept values back into their columns (thread i of pass A wrote kept[r][i] and reads it here itself).  Any fan-out works: no LDS bitmap,
@@ -48,30 +48,16 @@ __global__ __launch_bounds__(TRIE_THREADS) void caption_trie_mask_kernel(float* 
     const bool terminal = term[nd] >= 0;
     float* z = logits + (size_t)r * ld;
     float* kp = kept + (size_t)r * kept_ld;
-    float mx = -INFINITY, se = 0.f;
-    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
-    for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
-    }
-    for (int c = vend + tid; c < V; c += TRIE_THREADS) lse_add(mx, se, z[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
-    if ((tid & 63) == 0) {
-        rmx[tid >> 6] = mx;
-        rse[tid >> 6] = se;
-    }
+    float mx, se;
+    row_lse_partials<TRIE_THREADS>(z, V, mx, se, rmx, rse);
     for (int i = tid; i < fan; i += TRIE_THREADS) {
         const int t = child_tok[off + i];
         kp[i] = (t >= 0 && t < V) ? z[t] : -INFINITY;
     }
     if (tid == 0 && terminal) kp[fan] = z[eos];
     __syncthreads();                                    // every read of the raw row is done
-    if (tid == 0) {
-        for (int k = 1; k < TRIE_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
-        raw_lse[r] = mx + logf(se);
-    }
+    if (tid == 0) raw_lse[r] = lse_waves_merge<TRIE_THREADS>(mx, se, rmx, rse);
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
     const f32x4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) *reinterpret_cast<f32x4*>(z + c4) = ninf;
     for (int c = vend + tid; c < V; c += TRIE_THREADS) z[c] = -INFINITY;
@@ -136,31 +122,15 @@ __global__ __launch_bounds__(64 * TRIE_ADV_WAVES) void caption_trie_advance_kern
 // ---- Exact closed-set scoring (score_phrases): the trie is walked level by level, every node of a level a row, nothing
 // pruned.  The level tables are host-built (decoding.trie_levels) and static.
 
-// The RAW row's log-sum-exp alone, for the fp32-logits head: caption_trie_mask_kernel's pass A -- a thread's chain over its 16-byte
-// groups, a fixed xor tree, the waves in order -- and nothing else: one workgroup per row, bit-reproducible, the row is only read.
+// The RAW row's log-sum-exp alone, for the fp32-logits head: select_common.h's row_lse_partials / lse_waves_merge, as
+// caption_trie_mask_kernel's pass A, and nothing else: one workgroup per row, bit-reproducible, the row is only read.
 __global__ __launch_bounds__(TRIE_THREADS) void rows_lse_kernel(const float* __restrict__ logits, int ld, float* __restrict__ lse, int V) {
     __shared__ float rmx[TRIE_THREADS / 64], rse[TRIE_THREADS / 64];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const float* z = logits + (size_t)r * ld;
-    float mx = -INFINITY, se = 0.f;
-    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
-    for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
-    }
-    for (int c = vend + tid; c < V; c += TRIE_THREADS) lse_add(mx, se, z[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
-    if ((tid & 63) == 0) {
-        rmx[tid >> 6] = mx;
-        rse[tid >> 6] = se;
-    }
+    const int r = blockIdx.x;
+    float mx, se;
+    row_lse_partials<TRIE_THREADS>(logits + (size_t)r * ld, V, mx, se, rmx, rse);
     __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < TRIE_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
-        lse[r] = mx + logf(se);
-    }
+    if (threadIdx.x == 0) lse[r] = lse_waves_merge<TRIE_THREADS>(mx, se, rmx, rse);
 }
 
 // One level of the walk, after the level's step and its rows' LSE: one wave per (image b, entry j).  The first B * n_child waves are
@@ -238,6 +208,24 @@ __global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
 
 namespace {
 
+// Three checks every entry point of this file that takes the operand makes; `fn` names the caller in the message.
+int check_trie_tables(const char* fn, int nodes, int edges) {
+    I2T_REQUIRE(nodes >= 1 && edges >= 0, "%s: nodes = %d, edges = %d: a trie has a root", fn, nodes, edges);
+    return I2T_OK;
+}
+int check_eos_in_vocab(const char* fn, int eos, int V) {
+    I2T_REQUIRE(eos >= 0 && eos < V, "%s: eos = %d outside the vocabulary of %d", fn, eos, V);
+    return I2T_OK;
+}
+int check_logits_rows(const char* fn, int ld, int V) {                  // fp32 rows the kernels read in 16-byte groups
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "%s: ld = %d: logits rows hold V = %d columns and start on 16 bytes", fn, ld, V);
+    return I2T_OK;
+}
+#define TRIE_TRY(call)                    \
+    do {                                  \
+        if (int rc_ = (call)) return rc_; \
+    } while (0)
+
 // The checks and the launch the plain and the ragged entry point share; `fn` names the caller in every message.  plen null: the plain
 // kernel, which reads neither len_ptr nor N.
 int trie_mask_launch(const char* fn, void* stream, float* logits, int ld, const int* node, const int* child_off, const int* child_tok,
@@ -245,9 +233,9 @@ int trie_mask_launch(const char* fn, void* stream, float* logits, int ld, const 
                      const int* len_ptr, const int* plen, int N) {
     I2T_REQUIRE(logits && node && child_off && child_tok && term && done && raw_lse && kept, "%s: null pointer", fn);
     I2T_REQUIRE(R > 0 && V > 0, "%s: R = %d rows, V = %d", fn, R, V);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "%s: ld = %d: logits rows hold V = %d columns and start on 16 bytes", fn, ld, V);
-    I2T_REQUIRE(eos >= 0 && eos < V, "%s: eos = %d outside the vocabulary of %d", fn, eos, V);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "%s: nodes = %d, edges = %d: a trie has a root", fn, nodes, edges);
+    TRIE_TRY(check_logits_rows(fn, ld, V));
+    TRIE_TRY(check_eos_in_vocab(fn, eos, V));
+    TRIE_TRY(check_trie_tables(fn, nodes, edges));
     I2T_REQUIRE(kept_ld >= 1, "%s: kept_ld = %d: a row keeps at least the EOS logit", fn, kept_ld);
     I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(kept) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(child_off) && ALIGNED16(child_tok) &&
                     ALIGNED16(term),
@@ -270,9 +258,9 @@ int trie_advance_launch(const char* fn, void* stream, const int64_t* ids, int id
                     tok_lp,
                 "%s: null pointer", fn);
     I2T_REQUIRE(R > 0 && V > 0 && ids_ld > 0 && lp_ld > 0, "%s: R = %d rows, V = %d, ids_ld = %d, lp_ld = %d", fn, R, V, ids_ld, lp_ld);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "%s: ld = %d: logits rows hold V = %d columns and start on 16 bytes", fn, ld, V);
-    I2T_REQUIRE(eos >= 0 && eos < V, "%s: eos = %d outside the vocabulary of %d", fn, eos, V);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "%s: nodes = %d, edges = %d: a trie has a root", fn, nodes, edges);
+    TRIE_TRY(check_logits_rows(fn, ld, V));
+    TRIE_TRY(check_eos_in_vocab(fn, eos, V));
+    TRIE_TRY(check_trie_tables(fn, nodes, edges));
     I2T_REQUIRE(ALIGNED16(ids) && ALIGNED16(logits) && ALIGNED16(raw_lse) && ALIGNED16(node) && ALIGNED16(phrase_index) && ALIGNED16(child_off) &&
                     ALIGNED16(child_tok) && ALIGNED16(child_next) && ALIGNED16(term),
                 "%s: misaligned base pointer (16 bytes)", fn);
@@ -332,7 +320,7 @@ extern "C" int i2t_caption_trie_advance_ragged(void* stream, const int64_t* ids,
 extern "C" int i2t_rows_lse(void* stream, const float* logits, int ld, float* lse, int R, int V) {
     I2T_REQUIRE(logits && lse, "i2t_rows_lse: null pointer");
     I2T_REQUIRE(R > 0 && V > 0, "i2t_rows_lse: R = %d rows, V = %d", R, V);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_rows_lse: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    TRIE_TRY(check_logits_rows("i2t_rows_lse", ld, V));
     I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(lse), "i2t_rows_lse: misaligned base pointer (16 bytes)");
     hipLaunchKernelGGL(rows_lse_kernel, dim3(R), dim3(TRIE_THREADS), 0, (hipStream_t)stream, logits, ld, lse, V);
     I2T_CHECK_LAUNCH("i2t_rows_lse");
@@ -352,10 +340,10 @@ extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hi
     I2T_REQUIRE(B > 0 && W > 0 && V > 0 && ids_ld > 0 && lp_ld > 0 && (long)B * W < (1l << 31),
                 "i2t_trie_level_expand: B = %d images, W = %d rows each, V = %d, ids_ld = %d, lp_ld = %d", B, W, V, ids_ld, lp_ld);
     I2T_REQUIRE(n_child <= W && n_term <= W, "i2t_trie_level_expand: n_child = %d, n_term = %d exceed the W = %d rows of an image", n_child, n_term, W);
-    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_trie_level_expand: eos = %d outside the vocabulary of %d", eos, V);
+    TRIE_TRY(check_eos_in_vocab("i2t_trie_level_expand", eos, V));
     I2T_REQUIRE(path_in != path_out, "i2t_trie_level_expand: path_in and path_out are one buffer: they swap each level");
     if (logits) {
-        I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_trie_level_expand: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+        TRIE_TRY(check_logits_rows("i2t_trie_level_expand", ld, V));
     } else {
         I2T_REQUIRE(d > 0 && d % 8 == 0 && ld_hidden >= d && ld_w >= d && ld_hidden % 8 == 0 && ld_w % 8 == 0,
                     "i2t_trie_level_expand: d = %d must be a multiple of 8, hidden / head rows (ld %d / %d) 16-byte aligned", d, ld_hidden, ld_w);
@@ -381,15 +369,13 @@ extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hi
 // host's statements of the two kernels.  Plain loads and vector stores, no atomics.
 namespace {
 
-constexpr int TB_MAX_W = 8, TB_NONE = 0x7fffffff;
-// (total descending, edge ascending)
-__device__ __forceinline__ bool tb_better(float v, int e, float bv, int be) { return v > bv || (v == bv && e < be); }
+constexpr int TB_MAX_W = 8;
 
-// One workgroup per row, between the fp32 lm_head and the select kernel.  Pass A is rows_lse_kernel's, operation for operation, so
-// lse is that entry point's value on the same row.  Pass B gathers the node's children: thread i takes edges off + i, off + i + 256,
-// ..., total = path + (z[child_tok] - lse), and keeps its W best in registers; W rounds of a block arg-max over the threads' list
-// heads (the waves in order) give the row's W best, descending, the lower edge first on ties.  One pass over V plus a gather over the
-// fan-out -- no top-k over the vocabulary.  A dead row (node outside [0, nodes)) writes -1 / -inf and reads no logits.
+// One workgroup per row, between the fp32 lm_head and the select kernel.  Pass A is rows_lse_kernel's -- the same helpers of
+// select_common.h --, so lse is that entry point's value on the same row.  Pass B gathers the node's children: thread i takes edges
+// off + i, off + i + 256, ..., total = path + (z[child_tok] - lse), and keeps its W best in registers (topk_insert); W rounds of a
+// block arg-max over the threads' list heads (topk_round) give the row's W best, descending, the lower edge first on ties.
+// One pass over V plus a gather over the fan-out -- no top-k over the vocabulary.  A dead row (node outside [0, nodes)) writes -1 / -inf and reads no logits.
 __global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ node,
                                                                             const float* __restrict__ path, const int* __restrict__ child_off,
                                                                             const int* __restrict__ child_tok, const int* __restrict__ term,
@@ -399,7 +385,7 @@ __global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(cons
     __shared__ float rmx[TRIE_THREADS / 64], rse[TRIE_THREADS / 64], sh_v[TRIE_THREADS / 64], sh_lse;
     __shared__ int sh_e[TRIE_THREADS / 64], sh_win;
     if (ctrl[0]) return;                                // block-uniform, before any barrier
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.x, tid = threadIdx.x;
     const int nd = node[r];
     if (nd < 0 || nd >= nodes) {                        // block-uniform
         if (tid < W) {
@@ -410,25 +396,10 @@ __global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(cons
         return;
     }
     const float* z = logits + (size_t)r * ld;
-    float mx = -INFINITY, se = 0.f;
-    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
-    for (int c4 = tid * 4; c4 < vend; c4 += TRIE_THREADS * 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
-    }
-    for (int c = vend + tid; c < V; c += TRIE_THREADS) lse_add(mx, se, z[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
-    if ((tid & 63) == 0) {
-        rmx[tid >> 6] = mx;
-        rse[tid >> 6] = se;
-    }
+    float mx, se;
+    row_lse_partials<TRIE_THREADS>(z, V, mx, se, rmx, rse);
     __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < TRIE_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
-        sh_lse = mx + logf(se);
-    }
+    if (tid == 0) sh_lse = lse_waves_merge<TRIE_THREADS>(mx, se, rmx, rse);
     __syncthreads();
     const float lse = sh_lse, p = path[r];
     if (tid == 0) {
@@ -439,73 +410,22 @@ __global__ __launch_bounds__(TRIE_THREADS) void trie_beam_candidates_kernel(cons
     node_edges(child_off, nd, edges, edges, off, fan);
     float kv[TB_MAX_W];
     int ke[TB_MAX_W];
-#pragma unroll
-    for (int j = 0; j < TB_MAX_W; ++j) {
-        kv[j] = -INFINITY;
-        ke[j] = TB_NONE;
-    }
+    topk_clear(kv, ke);
     for (int i = tid; i < fan; i += TRIE_THREADS) {
         const int t = child_tok[off + i];
-        float cv = p + (((t >= 0 && t < V) ? z[t] : -INFINITY) - lse);
-        int ce = off + i;
-#pragma unroll
-        for (int j = 0; j < TB_MAX_W; ++j) {
-            if (j < W && tb_better(cv, ce, kv[j], ke[j])) {
-                const float tv = kv[j];
-                const int te = ke[j];
-                kv[j] = cv;
-                ke[j] = ce;
-                cv = tv;
-                ce = te;
-            }
-        }
+        topk_insert(kv, ke, W, p + (((t >= 0 && t < V) ? z[t] : -INFINITY) - lse), off + i);
     }
-    for (int j = 0; j < W; ++j) {                       // W rounds of a block arg-max over the threads' list heads
-        float bv = kv[0];
-        int be = ke[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oe = __shfl_xor(be, o, 64);
-            if (tb_better(ov, oe, bv, be)) {
-                bv = ov;
-                be = oe;
-            }
-        }
-        if (lane == 0) {
-            sh_v[wave] = bv;
-            sh_e[wave] = be;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < TRIE_THREADS / 64; ++w)
-                if (tb_better(sh_v[w], sh_e[w], bv, be)) {
-                    bv = sh_v[w];
-                    be = sh_e[w];
-                }
-            cand_edge[(size_t)r * W + j] = be == TB_NONE ? -1 : be;
-            cand_total[(size_t)r * W + j] = be == TB_NONE ? -INFINITY : bv;
-            sh_win = be;
-        }
-        __syncthreads();
-        const int win = sh_win;
-        if (win != TB_NONE && ke[0] == win) {           // the owner of the winning edge pops its head
-#pragma unroll
-            for (int t = 0; t < TB_MAX_W - 1; ++t) {
-                kv[t] = kv[t + 1];
-                ke[t] = ke[t + 1];
-            }
-            kv[TB_MAX_W - 1] = -INFINITY;
-            ke[TB_MAX_W - 1] = TB_NONE;
-        }
-        __syncthreads();
-    }
+    for (int j = 0; j < W; ++j)
+        topk_round<TRIE_THREADS>(kv, ke, sh_v, sh_e, &sh_win, [&](float bv, int be) {
+            cand_edge[(size_t)r * W + j] = be == TOPK_NONE ? -1 : be;
+            cand_total[(size_t)r * W + j] = be == TOPK_NONE ? -INFINITY : bv;
+        });
 }
 
 // One workgroup per image, after the candidates kernel.  Thread 0 does the bookkeeping in the replica's order: the rows' offers into
 // the pool (an entry held before a new one of equal score), the W best of the rows' sorted candidate lists by a W-way merge (the lower
 // row first on ties; within a row the list's order), the close test.  Then every thread moves history columns [0, pos) from the W
-// parents to the W children a column at a time through registers -- every parent column is read before a child row is written --,
+// parents to the W children (select_common.h's move_rows: every parent column is read before a child row is written),
 // and threads 0 .. W - 1 write the children's node, path, token and hist[child][pos] = parent.  A row without a child is dead: node
 // -1, path -inf, token eos, its own history row.  Every open image stores the same 1 into ctrl[1]: no atomic.
 // SETS (i2t_trie_beam_select_sets): image b has its own prompt length plen[b] (plen null: P) and its own longest phrase
@@ -619,15 +539,7 @@ __global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int*
         if (!cl) ctrl[1] = 1;
     }
     __syncthreads();
-    int vh[TB_MAX_W];
-    for (int c = tid; c < pos; c += TS_THREADS) {
-#pragma unroll
-        for (int w = 0; w < TB_MAX_W; ++w)
-            if (w < W) vh[w] = hist[(size_t)c_par[w] * hist_ld + c];
-#pragma unroll
-        for (int w = 0; w < TB_MAX_W; ++w)
-            if (w < W) hist[(size_t)(r0 + w) * hist_ld + c] = vh[w];
-    }
+    move_rows<TB_MAX_W>(hist, hist_ld, c_par, r0, W, pos, TS_THREADS);
     if (tid < W) {
         const int c = r0 + tid;
         node[c] = c_node[tid];
@@ -635,6 +547,43 @@ __global__ __launch_bounds__(TS_THREADS) void trie_beam_select_kernel(const int*
         ids[(size_t)c * ids_ld + len] = c_tok[tid];
         hist[(size_t)c * hist_ld + pos] = c_par[tid];
     }
+}
+
+// The checks and the launch i2t_trie_beam_select and i2t_trie_beam_select_sets share; `fn` names the caller in every message.
+// longest_of null: the plain kernel, one prompt length P and one longest phrase for every image, both held against ids_ld here.
+int trie_select_launch(const char* fn, void* stream, const int* cand_edge, const float* cand_total, const float* fin_total, int* node,
+                       float* path, const int* child_tok, const int* child_next, const int* term, int nodes, int edges, int eos, int64_t* ids,
+                       int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len, int* pool_n,
+                       int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P, int longest, float length_penalty,
+                       const int* plen, const int* longest_of) {
+    I2T_REQUIRE(cand_edge && cand_total && fin_total && node && path && child_tok && child_next && term && ids && hist && pool_phrase &&
+                    pool_sum && pool_score && pool_len && pool_n && closed && pos_ptr && len_ptr && ctrl,
+                "%s: null pointer", fn);
+    I2T_REQUIRE(B > 0 && (long)B * TB_MAX_W < (1l << 31), "%s: B = %d images", fn, B);
+    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "%s: W = %d rows per image (1 .. %d)", fn, W, TB_MAX_W);
+    if (longest_of) {
+        I2T_REQUIRE(P >= 1, "%s: P = %d (at least 1)", fn, P);
+        I2T_REQUIRE((long)P + 2 <= ids_ld && hist_ld >= 1, "%s: P + 2 = %ld columns exceed ids_ld = %d (hist_ld = %d)", fn, (long)P + 2, ids_ld,
+                    hist_ld);
+    } else {
+        I2T_REQUIRE(P >= 1 && longest >= 1, "%s: P = %d, longest = %d (each at least 1)", fn, P, longest);
+        I2T_REQUIRE((long)P + longest + 1 <= ids_ld && hist_ld >= 1, "%s: P + longest + 1 = %ld columns exceed ids_ld = %d (hist_ld = %d)", fn,
+                    (long)P + longest + 1, ids_ld, hist_ld);
+    }
+    TRIE_TRY(check_trie_tables(fn, nodes, edges));
+    I2T_REQUIRE(eos >= 0, "%s: eos = %d: a dead row takes it as its token", fn, eos);
+    // the exponent bits, not a comparison: no fast-math folding of a NaN test
+    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u, "%s: length_penalty must be finite", fn);
+    if (longest_of)
+        hipLaunchKernelGGL(trie_beam_select_kernel<true>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
+                           path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
+                           pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, 0, length_penalty, plen, longest_of);
+    else
+        hipLaunchKernelGGL(trie_beam_select_kernel<false>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
+                           path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
+                           pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, longest, length_penalty, nullptr, nullptr);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
 }
 
 }  // namespace
@@ -646,9 +595,9 @@ extern "C" int i2t_trie_beam_candidates(void* stream, const float* logits, int l
                 "i2t_trie_beam_candidates: null pointer");
     I2T_REQUIRE(R > 0 && V > 0, "i2t_trie_beam_candidates: R = %d rows, V = %d", R, V);
     I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_candidates: W = %d candidates per row (1 .. %d)", W, TB_MAX_W);
-    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_trie_beam_candidates: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
-    I2T_REQUIRE(eos >= 0 && eos < V, "i2t_trie_beam_candidates: eos = %d outside the vocabulary of %d", eos, V);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_candidates: nodes = %d, edges = %d: a trie has a root", nodes, edges);
+    TRIE_TRY(check_logits_rows("i2t_trie_beam_candidates", ld, V));
+    TRIE_TRY(check_eos_in_vocab("i2t_trie_beam_candidates", eos, V));
+    TRIE_TRY(check_trie_tables("i2t_trie_beam_candidates", nodes, edges));
     I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(node) && ALIGNED16(path) && ALIGNED16(child_off) && ALIGNED16(child_tok) && ALIGNED16(term) &&
                     ALIGNED16(cand_edge) && ALIGNED16(cand_total) && ALIGNED16(fin_total) && ALIGNED16(lse),
                 "i2t_trie_beam_candidates: misaligned base pointer (16 bytes)");
@@ -663,23 +612,9 @@ extern "C" int i2t_trie_beam_select(void* stream, const int* cand_edge, const fl
                                     int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score, int* pool_len,
                                     int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W, int P,
                                     int longest, float length_penalty) {
-    I2T_REQUIRE(cand_edge && cand_total && fin_total && node && path && child_tok && child_next && term && ids && hist && pool_phrase &&
-                    pool_sum && pool_score && pool_len && pool_n && closed && pos_ptr && len_ptr && ctrl,
-                "i2t_trie_beam_select: null pointer");
-    I2T_REQUIRE(B > 0 && (long)B * TB_MAX_W < (1l << 31), "i2t_trie_beam_select: B = %d images", B);
-    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_select: W = %d rows per image (1 .. %d)", W, TB_MAX_W);
-    I2T_REQUIRE(P >= 1 && longest >= 1, "i2t_trie_beam_select: P = %d, longest = %d (each at least 1)", P, longest);
-    I2T_REQUIRE((long)P + longest + 1 <= ids_ld && hist_ld >= 1,
-                "i2t_trie_beam_select: P + longest + 1 = %ld columns exceed ids_ld = %d (hist_ld = %d)", (long)P + longest + 1, ids_ld, hist_ld);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_select: nodes = %d, edges = %d: a trie has a root", nodes, edges);
-    I2T_REQUIRE(eos >= 0, "i2t_trie_beam_select: eos = %d: a dead row takes it as its token", eos);
-    // the exponent bits, not a comparison: no fast-math folding of a NaN test
-    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u, "i2t_trie_beam_select: length_penalty must be finite");
-    hipLaunchKernelGGL(trie_beam_select_kernel<false>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
-                       path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
-                       pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, longest, length_penalty, nullptr, nullptr);
-    I2T_CHECK_LAUNCH("i2t_trie_beam_select");
-    return I2T_OK;
+    return trie_select_launch("i2t_trie_beam_select", stream, cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, nodes,
+                              edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score, pool_len, pool_n, closed, pos_ptr, len_ptr,
+                              ctrl, B, W, P, longest, length_penalty, nullptr, nullptr);
 }
 
 // i2t_trie_beam_select with a prompt length and a longest phrase per image, both device tables.  The host cannot hold
@@ -689,23 +624,9 @@ extern "C" int i2t_trie_beam_select_sets(void* stream, const int* cand_edge, con
                                          int64_t* ids, int ids_ld, int* hist, int hist_ld, int* pool_phrase, float* pool_sum, float* pool_score,
                                          int* pool_len, int* pool_n, int* closed, const int* pos_ptr, const int* len_ptr, int* ctrl, int B, int W,
                                          int P, const int* plen, const int* longest_of, float length_penalty) {
-    I2T_REQUIRE(cand_edge && cand_total && fin_total && node && path && child_tok && child_next && term && ids && hist && pool_phrase &&
-                    pool_sum && pool_score && pool_len && pool_n && closed && pos_ptr && len_ptr && ctrl,
-                "i2t_trie_beam_select_sets: null pointer");
     I2T_REQUIRE(longest_of, "i2t_trie_beam_select_sets: null longest_of: every image names its set's longest phrase");
     I2T_REQUIRE(ALIGNED16(plen) && ALIGNED16(longest_of), "i2t_trie_beam_select_sets: misaligned plen or longest_of (16 bytes)");
-    I2T_REQUIRE(B > 0 && (long)B * TB_MAX_W < (1l << 31), "i2t_trie_beam_select_sets: B = %d images", B);
-    I2T_REQUIRE(W >= 1 && W <= TB_MAX_W, "i2t_trie_beam_select_sets: W = %d rows per image (1 .. %d)", W, TB_MAX_W);
-    I2T_REQUIRE(P >= 1, "i2t_trie_beam_select_sets: P = %d (at least 1)", P);
-    I2T_REQUIRE((long)P + 2 <= ids_ld && hist_ld >= 1, "i2t_trie_beam_select_sets: P + 2 = %ld columns exceed ids_ld = %d (hist_ld = %d)",
-                (long)P + 2, ids_ld, hist_ld);
-    I2T_REQUIRE(nodes >= 1 && edges >= 0, "i2t_trie_beam_select_sets: nodes = %d, edges = %d: a trie has a root", nodes, edges);
-    I2T_REQUIRE(eos >= 0, "i2t_trie_beam_select_sets: eos = %d: a dead row takes it as its token", eos);
-    I2T_REQUIRE((__builtin_bit_cast(unsigned, length_penalty) & 0x7f800000u) != 0x7f800000u,
-                "i2t_trie_beam_select_sets: length_penalty must be finite");
-    hipLaunchKernelGGL(trie_beam_select_kernel<true>, dim3(B), dim3(TS_THREADS), 0, (hipStream_t)stream, cand_edge, cand_total, fin_total, node,
-                       path, child_tok, child_next, term, nodes, edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score,
-                       pool_len, pool_n, closed, pos_ptr, len_ptr, ctrl, W, P, 0, length_penalty, plen, longest_of);
-    I2T_CHECK_LAUNCH("i2t_trie_beam_select_sets");
-    return I2T_OK;
+    return trie_select_launch("i2t_trie_beam_select_sets", stream, cand_edge, cand_total, fin_total, node, path, child_tok, child_next, term, nodes,
+                              edges, eos, ids, ids_ld, hist, hist_ld, pool_phrase, pool_sum, pool_score, pool_len, pool_n, closed, pos_ptr,
+                              len_ptr, ctrl, B, W, P, 0, length_penalty, plen, longest_of);
 }

@@ -1,6 +1,6 @@
 // Greedy-decode step kernels: everything position-dependent reads its position from DEVICE memory, so one captured
 // hipGraph replays unchanged for every generated token (static KV cache, no host round trip per token).
-#include "common.h"
+#include "select_common.h"
 
 namespace {
 
@@ -178,8 +178,8 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
 // gets token 0, torch.argmax's answer for a row of -inf, and margin 0.
 constexpr int BAN_THREADS = 1024;
 // LP (i2t_ngram_ban_argmax_lp, a caption step): the same choice, and tok_lp[b][len] = z[chosen] - logsumexp(z[b][:V]) over the RAW
-// row -- the ban does not enter -- from an online (max, sum exp) pass folded into the scan: per thread in its scan order, the
-// lanes by a fixed xor tree, the waves in order.  Nothing is written once *done is set.
+// row -- the ban does not enter -- from an online (max, sum exp) pass folded into the scan: per thread in its scan order, then
+// select_common.h's lse_wave_store and lse_waves_merge at 1024 threads.  Nothing is written once *done is set.
 template <bool F32, bool LP>
 __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const void* __restrict__ logits, int ld,
                                                                        int64_t* __restrict__ ids, int ids_ld,
@@ -249,14 +249,7 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
         }
     }
     const int w = tid >> 6;
-    if constexpr (LP) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
-        if ((tid & 63) == 0) {
-            rmx[w] = mx;
-            rse[w] = se;
-        }
-    }
+    if constexpr (LP) lse_wave_store(mx, se, rmx, rse);
     if ((tid & 63) == 0) {
         rv[w] = best;
         rv2[w] = second;
@@ -277,11 +270,10 @@ __global__ __launch_bounds__(BAN_THREADS) void ngram_ban_argmax_kernel(const voi
         row[len] = none ? 0 : bi;
         if (margin_out) margin_out[b] = none ? 0.f : best - second;
         if constexpr (LP) {
-            for (int k = 1; k < BAN_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
             const int tok = none ? 0 : bi;
             const float z = F32 ? reinterpret_cast<const float*>(logits)[(size_t)b * ld + tok]
                                 : bf16_to_f32(reinterpret_cast<const bf16_t*>(logits)[(size_t)b * ld + tok]);
-            tok_lp[(size_t)b * lp_ld + len] = z - (mx + logf(se));
+            tok_lp[(size_t)b * lp_ld + len] = z - lse_waves_merge<BAN_THREADS>(mx, se, rmx, rse);
         }
     }
 }
@@ -499,8 +491,8 @@ __global__ __launch_bounds__(FIN_THREADS) void caption_finish_kernel(int64_t* __
 
 // The logits processors of a caption step, a pre-pass over the step's fp32 logits row before the chooser: repetition
 // penalty over ids[r][0 .. len), suppressed ids, EOS below the minimum length -- transformers' RepetitionPenalty -> SuppressTokens ->
-// MinNewTokensLength order.  One workgroup per row.  Pass A: the RAW row's (max, sum exp), a thread's chain, a fixed xor tree, the
-// waves in order (ngram_ban_argmax_kernel's shape: bit-reproducible) -> raw_lse[r].  Pass B: saved[r][j] = z[ids[r][j]], all raw
+// MinNewTokensLength order.  One workgroup per row.  Pass A: the RAW row's log-sum-exp (select_common.h's row_lse_partials /
+// lse_waves_merge: bit-reproducible, the bits i2t_rows_lse gives for the row) -> raw_lse[r].  Pass B: saved[r][j] = z[ids[r][j]], all raw
 // since nothing has been written.  Barrier.  Pass C: z[ids[r][j]] = f(saved[r][j]); every occurrence of a token reads the same raw
 // value and stores the same result, so a token is penalised once however often it occurs, with no first-occurrence search.  Barrier.
 // Pass D: the suppress list and the min-length EOS, plain stores of -inf that read nothing.  An id outside [0, V) takes no part
@@ -520,29 +512,14 @@ __global__ __launch_bounds__(PROC_THREADS) void caption_logits_process_kernel(fl
     float* z = logits + (size_t)r * ld;
     const int64_t* row = ids + (size_t)r * ids_ld;
     float* sv = saved + (size_t)r * saved_ld;
-    float mx = -INFINITY, se = 0.f;
-    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
-    for (int c4 = tid * 4; c4 < vend; c4 += PROC_THREADS * 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lse_add(mx, se, q[e]);
-    }
-    for (int c = vend + tid; c < V; c += PROC_THREADS) lse_add(mx, se, z[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lse_merge(mx, se, __shfl_xor(mx, o, 64), __shfl_xor(se, o, 64));
-    if ((tid & 63) == 0) {
-        rmx[tid >> 6] = mx;
-        rse[tid >> 6] = se;
-    }
+    float mx, se;
+    row_lse_partials<PROC_THREADS>(z, V, mx, se, rmx, rse);
     for (int j = tid; j < len; j += PROC_THREADS) {
         const int64_t t = row[j];
         sv[j] = (t >= 0 && t < V) ? z[t] : 0.f;
     }
     __syncthreads();                                    // every read of the raw row is done
-    if (tid == 0) {
-        for (int k = 1; k < PROC_THREADS / 64; ++k) lse_merge(mx, se, rmx[k], rse[k]);
-        raw_lse[r] = mx + logf(se);
-    }
+    if (tid == 0) raw_lse[r] = lse_waves_merge<PROC_THREADS>(mx, se, rmx, rse);
     for (int j = tid; j < len; j += PROC_THREADS) {
         const int64_t t = row[j];
         if (t >= 0 && t < V) {
