@@ -194,6 +194,17 @@ class VisionEncoderDecoder(nn.Module):
             out, _ = self._engine.encode(images, False)
         return out
 
+    def preprocess_images(self, images, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), antialias: bool = True, size=None) -> torch.Tensor:
+        """Decoded uint8 images of any sizes (a [B, h, w, c] tensor or a sequence of [h, w, c] tensors, c in {1, 3}) -> the fp32
+        [B, 3, H, W] tensor ``encode`` / ``generate_captions`` / ``score`` take, on the model's device: the reference's
+        ``ToTensor -> Resize -> Normalize`` in one launch (image2text_amd/preprocess.py).  ``size=None``: the encoder's own input
+        resolution (the ``input`` spec of a from-scratch encoder, 224 x 224 for ``PretrainedViT``)."""
+        from ..preprocess import preprocess_images
+        if size is None:
+            spec = getattr(self.config.vision_encoder_config, 'input', None)
+            size = (spec.height, spec.width) if spec is not None else (224, 224)
+        return preprocess_images(images, size, mean=mean, std=std, antialias=antialias, device=next(self.parameters()).device)
+
     def forward(self, images: Optional[torch.FloatTensor], ids: torch.LongTensor,
                 attn_msk: Optional[torch.BoolTensor] = None,
                 encoder_output: Optional[torch.Tensor] = None) -> VisionEncoderDecoderModelOutput:

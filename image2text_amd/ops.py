@@ -1142,3 +1142,17 @@ def gemm_fp8(a8, sa, b8, sb, out, M, N, K, bias=None, residual=None, act=0):
     _k.i2t_gemm_fp8(a8, a8.stride(0), sa, b8, b8.stride(0), sb, out, out.stride(0), int(out.dtype == F32), M, N, K, bias, int(act), residual,
                     residual.stride(0) if residual is not None else 0)
     return out
+
+
+# ---- image preprocessing (csrc/preprocess.hip)
+def preprocess_images(data, offsets, shapes, out, a, b, max_side, antialias=True):
+    """data uint8 (packed images + 16 bytes of tail pad), offsets int64 [B], shapes int32 [B, 3] = (h, w, c) -> out f32 [B, 3, H, W] =
+    resize(image) * a[k] + b[k]; ``max_side``: the largest side in ``shapes``.  include/i2t.h::i2t_preprocess_images; the shapes and
+    offsets are the caller's to get right (preprocess.py::pack_images): the kernel writes NaN for an image they do not cover."""
+    B = offsets.numel()
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    assert out.dim() == 4 and out.shape[0] == B and out.shape[1] == 3 and out.is_contiguous()
+    assert tuple(shapes.shape) == (B, 3) and shapes.is_contiguous() and len(a) == 3 and len(b) == 3
+    _k.i2t_preprocess_images(data, data.numel(), offsets, shapes, B, int(max_side), out, out.shape[2], out.shape[3], float(a[0]), float(a[1]),
+                             float(a[2]), float(b[0]), float(b[1]), float(b[2]), int(bool(antialias)))
+    return out

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 16
+#define I2T_ABI_VERSION 17
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -885,6 +885,20 @@ int i2t_swiglu_bwd_fp8(void* stream, const void* dh, const void* gate_up, int ld
                        void* dgu_bf16);
 int i2t_gemm_fp8(void* stream, const void* A8, int lda, const float* sa, const void* B8, int ldb, const float* sb, void* C, int ldc,
                  int c_is_f32, int M, int N, int K, const float* bias, int act, const float* residual, int ldr);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Image preprocessing (csrc/preprocess.hip; replaces the reference's per-image host chain ToTensor -> Resize((H, W)) -> Normalize,
+ * trainer.py): B decoded uint8 images of different sizes -> out fp32 [B][3][H][W] in one launch and one pass over the source.
+ *   out[b][k] = resize(u_b[..., k]) * a_k + b_k,  a_k = 1 / (255 std_k), b_k = -mean_k / std_k (formed by the caller in fp64)
+ * resize = torch.nn.functional.interpolate(mode='bilinear', align_corners=False, antialias=antialias != 0) on the raw 0..255
+ * values: tap ranges and weights in fp64, rounded once to fp32; fp32 sums (width, then height); one fma per element.
+ *   data: packed bytes, 16-byte aligned; image b at byte offsets[b] as [h_b][w_b][c_b] rows, shapes int32 [B][3] = (h, w, c),
+ *     c = 1 (gray: replicated to the three output channels) or 3; every image ends at least 16 bytes before data + data_bytes
+ *     (rows are read with 16-byte loads aligned down)
+ *   max_side: the largest h or w in shapes (it sizes the LDS row buffers), 1..16384; H, W: 1..16384
+ * An image whose shape or offset breaks these bounds is not read; its outputs are NaN. */
+int i2t_preprocess_images(void* stream, const void* data, long data_bytes, const int64_t* offsets, const int* shapes, int B, int max_side,
+                          float* out, int H, int W, float a0, float a1, float a2, float b0, float b1, float b2, int antialias);
 
 #ifdef __cplusplus
 }
