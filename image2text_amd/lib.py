@@ -174,6 +174,7 @@ SIGNATURES = {
     'i2t_swiglu_bwd_fp8': [P, P, P, I, P, I, PF, I, I, P],
     'i2t_gemm_fp8': [P, P, I, PF, P, I, PF, P, I, I, I, I, I, PF, I, PF, I],
     'i2t_preprocess_images': [P, P, L, PL, PI, I, I, PF, I, I, F, F, F, F, F, F, I],
+    'i2t_preprocess_regions': [P, P, L, PL, PI, I, I, PI, I, PF, I, I, F, F, F, F, F, F, I],
     'i2t_set_deterministic': [I],
     'i2t_deterministic': [],
     'i2t_comm_available': [],
@@ -188,7 +189,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _lib = None
 
 

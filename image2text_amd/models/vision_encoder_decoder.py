@@ -194,16 +194,20 @@ class VisionEncoderDecoder(nn.Module):
             out, _ = self._engine.encode(images, False)
         return out
 
-    def preprocess_images(self, images, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), antialias: bool = True, size=None) -> torch.Tensor:
+    def preprocess_images(self, images, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), antialias: bool = True, size=None, boxes=None,
+                          box_index=None, flip=None) -> torch.Tensor:
         """Decoded uint8 images of any sizes (a [B, h, w, c] tensor or a sequence of [h, w, c] tensors, c in {1, 3}) -> the fp32
         [B, 3, H, W] tensor ``encode`` / ``generate_captions`` / ``score`` take, on the model's device: the reference's
         ``ToTensor -> Resize -> Normalize`` in one launch (image2text_amd/preprocess.py).  ``size=None``: the encoder's own input
-        resolution (the ``input`` spec of a from-scratch encoder, 224 x 224 for ``PretrainedViT``)."""
+        resolution (the ``input`` spec of a from-scratch encoder, 224 x 224 for ``PretrainedViT``).  ``boxes`` [R, 4] of (top, left,
+        height, width), ``box_index`` [R] and ``flip`` [R]: row r of the [R, 3, H, W] result is that box of image ``box_index[r]``,
+        mirrored where ``flip[r]`` -- regions, centre crops, random resized crops (``preprocess.center_boxes`` and its neighbours)."""
         from ..preprocess import preprocess_images
         if size is None:
             spec = getattr(self.config.vision_encoder_config, 'input', None)
             size = (spec.height, spec.width) if spec is not None else (224, 224)
-        return preprocess_images(images, size, mean=mean, std=std, antialias=antialias, device=next(self.parameters()).device)
+        return preprocess_images(images, size, mean=mean, std=std, antialias=antialias, device=next(self.parameters()).device, boxes=boxes,
+                                 box_index=box_index, flip=flip)
 
     def forward(self, images: Optional[torch.FloatTensor], ids: torch.LongTensor,
                 attn_msk: Optional[torch.BoolTensor] = None,

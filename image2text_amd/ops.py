@@ -1156,3 +1156,17 @@ def preprocess_images(data, offsets, shapes, out, a, b, max_side, antialias=True
     _k.i2t_preprocess_images(data, data.numel(), offsets, shapes, B, int(max_side), out, out.shape[2], out.shape[3], float(a[0]), float(a[1]),
                              float(a[2]), float(b[0]), float(b[1]), float(b[2]), int(bool(antialias)))
     return out
+
+
+def preprocess_regions(data, offsets, shapes, regions, out, a, b, max_side, antialias=True):
+    """``preprocess_images`` over boxes: regions int32 [R, 6] = (src, top, left, bh, bw, flip) on the device -> out f32 [R, 3, H, W], row r
+    the box of image src resized to H x W, mirrored when flip is 1.  include/i2t.h::i2t_preprocess_regions; the regions are the
+    caller's to get right (preprocess.py::preprocess_images): the kernel writes NaN for a region its arguments do not cover."""
+    B, R = offsets.numel(), regions.shape[0]
+    assert data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()
+    assert regions.dim() == 2 and regions.shape[1] == 6 and regions.is_contiguous()
+    assert out.dim() == 4 and out.shape[0] == R and out.shape[1] == 3 and out.is_contiguous()
+    assert tuple(shapes.shape) == (B, 3) and shapes.is_contiguous() and len(a) == 3 and len(b) == 3
+    _k.i2t_preprocess_regions(data, data.numel(), offsets, shapes, B, int(max_side), regions, R, out, out.shape[2], out.shape[3], float(a[0]),
+                              float(a[1]), float(a[2]), float(b[0]), float(b[1]), float(b[2]), int(bool(antialias)))
+    return out

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 17
+#define I2T_ABI_VERSION 18
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -899,6 +899,18 @@ int i2t_gemm_fp8(void* stream, const void* A8, int lda, const float* sa, const v
  * An image whose shape or offset breaks these bounds is not read; its outputs are NaN. */
 int i2t_preprocess_images(void* stream, const void* data, long data_bytes, const int64_t* offsets, const int* shapes, int B, int max_side,
                           float* out, int H, int W, float a0, float a1, float a2, float b0, float b1, float b2, int antialias);
+/* The same kernel body over R boxes of those images: output r resizes the box regions[r] of image src to H x W and
+ * mirrors it when flip is 1; R need not be B, an image may be named any number of times, the source is uploaded once.
+ *   regions: int32 [R][6] = (src, top, left, bh, bw, flip), rows [top, top + bh) and columns [left, left + bw) of image src,
+ *     0 <= src < B, the box inside the image, bh, bw >= 1, flip 0 or 1
+ *   out[r][k] = flip(resize(u_src[top : top + bh, left : left + bw, k])) * a_k + b_k: the axes run over the box (n = bw, bh), taps clamp
+ *     at the box's edges and no pixel outside it contributes; the flip is taken on the OUTPUT -- column x holds what column
+ *     W - 1 - x of the unflipped result holds, bit for bit.  With the full box and flip 0 this is i2t_preprocess_images, bit for bit.
+ * Only the rows and the byte span of a row that a workgroup's taps cover are read.  A region that breaks these bounds, or names an
+ * image that i2t_preprocess_images would not read, is not read; its outputs are NaN, the other regions are untouched. */
+int i2t_preprocess_regions(void* stream, const void* data, long data_bytes, const int64_t* offsets, const int* shapes, int B, int max_side,
+                           const int* regions, int R, float* out, int H, int W, float a0, float a1, float a2, float b0, float b1, float b2,
+                           int antialias);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,11 @@
   (c) the torch CPU pipeline, image by image, on 16 threads (the reference's ToTensor -> Resize -> Normalize)
 
     python tools/bench_preprocess.py [out.txt] [--images N]
+    python tools/bench_preprocess.py [out.txt] [--images N] --regions R
+
+With ``--regions R`` it measures boxes instead: R random-resized-crop boxes of each of N images (default 64), half of
+them flipped, as ONE launch over the batch uploaded once, against what a caller without boxes does -- slice every box on the host and
+hand the list of N R crops to preprocess_images, which joins and uploads every crop's pixels.
 
 Device times are events around a window of back-to-back calls after a warm-up, ROUNDS windows, median [min .. max].  The kernel's
 share of the HBM roof counts its own bytes (source bytes + 12 H W per image) against 6.29 TB/s, the measured copy rate of the card."""
@@ -68,8 +73,64 @@ def torch_chain(x_u8, mean, std):
     return (y - mean) / std
 
 
+def host_clock(fn, reps=3):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def regions_mode(n, per_image):
+    """R boxes per image in one launch against slicing on the host"""
+    say(f'device: {torch.cuda.get_device_name(0)}; {n} images x {per_image} boxes -> {SIZE[0]}x{SIZE[1]}, antialiased')
+    ims = flickr_like(n)
+    g = torch.Generator().manual_seed(2)
+    index = torch.arange(n).repeat_interleave(per_image)
+    boxes = pp.random_resized_crop_boxes([ims[i].shape for i in index.tolist()], generator=g)
+    flip = pp.random_flips(len(index), generator=g)
+    R = len(index)
+    src_bytes = sum(im.numel() for im in ims)
+    crop_bytes = int(sum(bh * bw * ims[i].shape[2] for i, (_, _, bh, bw) in zip(index.tolist(), boxes.tolist())))
+    out = torch.empty(R, 3, *SIZE, device=dev)
+    packed = pp.pack_images(ims, dev)
+    med, lo, hi = windows(lambda: pp.preprocess_images(packed, SIZE, MEAN, STD, out=out, boxes=boxes, box_index=index, flip=flip), WINDOW)
+    say(f'(r1) {R} boxes of the packed batch on the device, one launch (validation and the {24 * R} bytes of regions included): '
+        f'{med:.3f} [{lo:.3f} .. {hi:.3f}] ms = {R / med * 1e3:,.0f} outputs/s')
+    dt = host_clock(lambda: pp.preprocess_images(ims, SIZE, MEAN, STD, out=out, boxes=boxes, box_index=index, flip=flip))
+    say(f'(r2) the same from host tensors (join + one upload of {src_bytes / 1e6:.1f} MB + the launch), host clock: {dt * 1e3:.2f} ms = '
+        f'{R / dt:,.0f} outputs/s')
+    got = out.clone()
+
+    def sliced():
+        crops = [ims[i][t:t + bh, l:l + bw] for i, (t, l, bh, bw) in zip(index.tolist(), boxes.tolist())]
+        return pp.preprocess_images(crops, SIZE, MEAN, STD, out=out)
+
+    dt_s = host_clock(sliced)
+    say(f'(r3) slicing the boxes on the host and preprocess_images on the {R} crops (join + upload of {crop_bytes / 1e6:.1f} MB + the launch), '
+        f'host clock: {dt_s * 1e3:.2f} ms = {R / dt_s:,.0f} outputs/s ({dt_s / dt:.2f} x the time of (r2))')
+    want = torch.where(flip.to(dev)[:, None, None, None], torch.flip(out, [-1]), out)          # the parent has no flip: mirrored here
+    say(f'    the two results are {"bit-equal" if torch.equal(got, want) else "NOT bit-equal: max |diff| %.3e" % float((got - want).abs().max())}')
+
+
 def main():
     assert torch.cuda.is_available(), 'bench_preprocess.py measures on the MI355X; there is nothing to report without one'
+    if '--regions' in sys.argv:
+        i = sys.argv.index('--regions')
+        per_image = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        n = 64
+        if '--images' in sys.argv:
+            i = sys.argv.index('--images')
+            n = int(sys.argv[i + 1])
+            del sys.argv[i:i + 2]
+        regions_mode(n, per_image)
+        if len(sys.argv) > 1:
+            with open(sys.argv[1], 'w') as fh:
+                fh.write('\n'.join(lines) + '\n')
+        return
     n = int(sys.argv[sys.argv.index('--images') + 1]) if '--images' in sys.argv else 3072
     say(f'device: {torch.cuda.get_device_name(0)}; {n} images -> {SIZE[0]}x{SIZE[1]}, antialiased; {ROUNDS} windows, median [min .. max]')
     ims = flickr_like(n)
