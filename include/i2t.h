@@ -234,6 +234,8 @@ int i2t_attention_bwd_ex(void* stream, const void* q, long q_bs, int q_rs, const
  *   bwd: dwte[ids] += dx (atomics), dwpe[t+pos_offset] += sum_b dx[b][t]
  *   pos (device int[B*T], nullable): explicit position of every row for packed variable-length batches (then B*T is just
  *   the row count and the wpe gradient is accumulated with atomics).
+ *   ids outside [0, vocab) are CLAMPED, forward and backward: id < 0 reads / adds into row 0, id >= vocab row vocab - 1 (no table row
+ *   past the vocabulary is ever touched).  wpe NULL (fwd): the token rows alone; dwte / dwpe NULL (bwd): that gradient is skipped.
  * --------------------------------------------------------------------------------------------------------- */
 int i2t_embed_fwd(void* stream, const int64_t* ids, const float* wte, const float* wpe, float* x,
                   int B, int T, int d, int pos_offset, int vocab, const int* pos);
@@ -246,6 +248,10 @@ int i2t_embed_bwd(void* stream, const int64_t* ids, const float* dx, float* dwte
  *   fwd: lse[m] = logsumexp(logits[m]/T); loss += sum_m w[m]*(lse[m] - logits[m][label]/T)   (atomic into *loss)
  *   bwd: logits[m][:] <- bf16( gscale * w[m]/T * (softmax(logits[m]/T) - onehot) ), in place;  gscale read
  *        from device memory (*gscale_ptr) so the upstream gradient never needs a host sync.
+ *   DEAD rows: a row whose label is ignore_index, or any other label < 0 or >= V, is dead in every form below: lse[m] = 0, no loss
+ *   term, and its V gradient columns are written as zeros.  The pad columns [V, ld) are never written.
+ *   The logits must be FINITE: the streaming forms keep a running (max, sum) that starts at -inf, so a leading -inf logit makes
+ *   online_add evaluate exp(-inf - -inf) = NaN; +inf and NaN poison the row in every form.  The host does not scan them.
  * --------------------------------------------------------------------------------------------------------- */
 int i2t_ce_fwd(void* stream, const void* logits, int ld, const int64_t* labels, const float* w, float inv_temp,
                int64_t ignore_index, float* lse, float* loss, int M, int V);
@@ -329,6 +335,9 @@ int i2t_nchw_to_nhwc_bf16(void* stream, const void* src, void* dst, int B, int C
  *          f32 arena; also refreshes the bf16 shadow of every parameter.  lr/wd are per-element-range tables:
  *          seg_end[i] = exclusive end of segment i, seg_lr[i], seg_wd[i] (nseg small; device arrays).  A segment with
  *          seg_lr < 0 is FROZEN (requires_grad off, or in no parameter group): skipped entirely -- no state, no update, no traffic.
+ *          Every seg_end must be a MULTIPLE OF 4 (the arena aligns parameters to 8): a thread updates one float4 with the lr / wd
+ *          of the segment its first element lies in.  seg_lr == 0: p and its shadow keep their value (the decay factor is 1), the
+ *          moments advance.  p_bf16 NULL: no shadow.  The bias corrections 1 - beta^step are fp32 powf on the host (step >= 1).
  *   add_rows / cls concat helpers for the encoder token buffer.
  * --------------------------------------------------------------------------------------------------------- */
 int i2t_cast_f32_bf16(void* stream, const float* src, void* dst, long n);
