@@ -332,18 +332,54 @@ def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causa
         phrase_node_csr(trie)
     else:
         trie = phrase_trie(phrases, eos, vocab, 1 << 30)
+    _check_score_rest(int(P) + trie.longest + 1, window, causal, sparse, images_per_pass)
+    return trie
+
+
+def _check_score_rest(total: int, window: int, causal: bool, sparse: bool, images_per_pass):
+    """``check_phrase_score_args``' refusals behind the set, which ``check_phrase_set_score_args`` shares: the decoder, the window,
+    ``images_per_pass``"""
     if not causal:
         raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
                                   'state of the earlier ones --, so use rerank')
     if sparse:
         raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
                                   'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
-    total = int(P) + trie.longest + 1
     if total > window:
         raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
     if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
         raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
-    return trie
+
+
+class PhraseSetScores(NamedTuple):
+    """What ``score_phrases(phrase_sets=...)`` returns."""
+    logprob: torch.Tensor               # fp32 [B, Kmax], Kmax the phrases of the largest set: column k < K_s the raw log-likelihood of phrase k of
+                                        # the image's own set + EOS after its own prompt (``score``'s quantity), -inf in columns k >= K_s
+    best: torch.Tensor                  # int64 [B]: the argmax within the image's own set, the lowest index on ties (duplicates tie exactly)
+    lengths: torch.Tensor               # int32 [S, Kmax]: the tokens of phrase k of set s + 1 (the EOS), 0 in the padding
+
+
+def check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int,
+                                causal: bool = True, sparse: bool = False, images_per_pass=None):
+    """The refusals of ``score_phrases(phrase_sets=..., phrase_set_index=..., prompt_lengths=...)``, all before anything
+    runs (host only) -> (the S sets' ``PhraseTrie``, index int32 [B], plen int32 [B] or None).  ValueError, in this order:
+    ``prompt_lengths`` without ``phrase_sets``; ``check_phrase_sets``' own (``phrase_set_index`` without ``phrase_sets``, ``phrases`` given
+    too, a set ``phrase_trie`` refuses, an index that is not one set of ``phrase_sets`` per image); ``prompt_lengths``' own
+    (``check_ragged_caption_args``' texts).  Then ``check_phrase_score_args``' NotImplementedError for a non-causal decoder and for sparse
+    nano-mini blocks, and its ValueError for the window -- held against the largest p_b + longest phrase of b's set + 1 -- and for
+    ``images_per_pass`` < 1."""
+    if phrase_sets is None and phrase_set_index is None and prompt_lengths is not None:
+        raise ValueError('score_phrases(prompt_lengths=...) needs phrase_sets: one phrase list for all images is '
+                         'phrase_sets=[phrases], phrase_set_index=[0] * B')
+    sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
+    if isinstance(phrase_sets, torch.Tensor):
+        phrase_sets = phrase_sets.detach().cpu().tolist()
+    tries = tuple(phrase_trie(one, eos, vocab, 1 << 30) for one in phrase_sets)
+    plen = None if prompt_lengths is None else _prompt_lengths(prompt_lengths, B, P)
+    rows = np.full(B, int(P), dtype=np.int64) if plen is None else plen.astype(np.int64)
+    total = int((rows + sets.longest + 1).max()) if B else int(P)
+    _check_score_rest(total, window, causal, sparse, images_per_pass)
+    return tries, sets.index, plen
 
 
 class PhraseBeams(NamedTuple):

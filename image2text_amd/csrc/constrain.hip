@@ -143,6 +143,45 @@ __global__ __launch_bounds__(TRIE_THREADS) void rows_lse_kernel(const float* __r
 // out of the subtraction).  path_in and path_out are two buffers: no cell is read and written in one launch.  An entry whose parent row
 // or token lies outside its range (never from decoding.trie_levels) writes nothing, and so does a column outside the id rows.
 constexpr int EXPAND_WAVES = 4;
+
+// What one wave of a level-expand kernel computes for the token `tok` behind the node in row `pr`: path_in[pr] + (z - lse[pr]), z as
+// above.  Every lane returns the value.  trie_level_expand_kernel and trie_level_expand_sets_kernel both call it: one statement of the
+// arithmetic.
+__device__ __forceinline__ float expand_value(const bf16_t* __restrict__ hid, int ld_h, const bf16_t* __restrict__ Wh, int ldw, int d, float scale,
+                                              const float* __restrict__ logits, int ld, const float* __restrict__ lse,
+                                              const float* __restrict__ path_in, size_t pr, int tok, int lane) {
+    float z;
+    if (logits != nullptr) {
+        z = logits[pr * ld + tok];
+    } else {
+        const bf16_t* wr = Wh + (size_t)tok * ldw;
+        const bf16_t* hr = hid + pr * ld_h;
+        float acc = 0.f;
+        for (int k = 8 * lane; k < d; k += 8 * 64) {
+            const u32x4 wq = *reinterpret_cast<const u32x4*>(wr + k), hq = *reinterpret_cast<const u32x4*>(hr + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc += bf16lo(wq[e]) * bf16lo(hq[e]) + bf16hi(wq[e]) * bf16hi(hq[e]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        z = __fmul_rn(scale, acc);                           // its own rounding: never fused into the subtraction below
+    }
+    return path_in[pr] + (z - lse[pr]);
+}
+
+// The terminal part's stores: v into lp[i] for every phrase index i of term_phrase[term_off[j] .. term_off[j + 1]), the range clipped to
+// the n_term_phrases entries the table holds and an index outside [0, kmax) skipped.
+__device__ __forceinline__ void expand_terminal_store(const int* __restrict__ term_off, const int* __restrict__ term_phrase, int j,
+                                                      int n_term_phrases, float* __restrict__ lp, int kmax, float v, int lane) {
+    int lo = term_off[j], hi = term_off[j + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n_term_phrases ? n_term_phrases : hi;
+    for (int i = lo + lane; i < hi; i += 64) {
+        const int ph = term_phrase[i];
+        if (ph >= 0 && ph < kmax) lp[ph] = v;
+    }
+}
+
 __global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
     const bf16_t* __restrict__ hid, int ld_h, const bf16_t* __restrict__ Wh, int ldw, int d, float scale, const float* __restrict__ logits, int ld,
     const float* __restrict__ lse, const float* __restrict__ path_in, float* __restrict__ path_out, const int* __restrict__ child_parent,
@@ -168,23 +207,7 @@ __global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
     }
     if (p < 0 || p >= W || tok < 0 || tok >= V) return;
     const size_t pr = (size_t)b * W + p;
-    float z;
-    if (logits != nullptr) {
-        z = logits[pr * ld + tok];
-    } else {
-        const bf16_t* wr = Wh + (size_t)tok * ldw;
-        const bf16_t* hr = hid + pr * ld_h;
-        float acc = 0.f;
-        for (int k = 8 * lane; k < d; k += 8 * 64) {
-            const u32x4 wq = *reinterpret_cast<const u32x4*>(wr + k), hq = *reinterpret_cast<const u32x4*>(hr + k);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc += bf16lo(wq[e]) * bf16lo(hq[e]) + bf16hi(wq[e]) * bf16hi(hq[e]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        z = __fmul_rn(scale, acc);                           // its own rounding: never fused into the subtraction below
-    }
-    const float v = path_in[pr] + (z - lse[pr]);
+    const float v = expand_value(hid, ld_h, Wh, ldw, d, scale, logits, ld, lse, path_in, pr, tok, lane);
     if (child) {
         const int len = *len_ptr;
         if (len < 0 || len >= ids_ld) return;
@@ -195,13 +218,74 @@ __global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_kernel(
         }
         return;
     }
-    int lo = term_off[j], hi = term_off[j + 1];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > n_term_phrases ? n_term_phrases : hi;
-    for (int i = lo + lane; i < hi; i += 64) {
-        const int ph = term_phrase[i];
-        if (ph >= 0 && ph < lp_ld) logprob[(size_t)b * lp_ld + ph] = v;
+    expand_terminal_store(term_off, term_phrase, j, n_term_phrases, logprob + (size_t)b * lp_ld, lp_ld, v, lane);
+}
+
+// i2t_trie_level_expand_sets: one launch in which the images stand at different levels of different tries, or in a
+// forced prompt column, or behind their last level.  The level tables of every (set, level) lie end to end in child_parent / child_tok
+// [n_child_all], term_row [n_term_all], term_off [n_off_all] (a level's n_term + 1 offsets, which index term_phrase [n_term_phrases]
+// absolutely).  Image b's state is the 8 int32 of img + 8 b (IMG_* below), host-built per step.  One wave per (image, entry): the first
+// B * e_child waves are the child part, entry j of image b; the other B * e_term the terminal part.
+//   level < 0, forced token k >= 0 (child part, j < W): ids[b W + j][col] = k and path_out[b W + j] = path_in[b W + j] -- the swap stays
+//     valid; nothing is scored.  level < 0 and k < 0: the image is finished, nothing of it is read or written.
+//   level >= 0: entry j < n of the image's own table range does exactly what trie_level_expand_kernel does with it (expand_value, then
+//     the same stores), the terminal part into the image's own logprob row of kmax columns.
+// An entry outside its image's range, a range outside the tables, a column outside the id rows: nothing is written.
+constexpr int IMG_LEVEL = 0, IMG_FORCED = 1, IMG_CHILD_AT = 2, IMG_N_CHILD = 3, IMG_TERM_AT = 4, IMG_N_TERM = 5, IMG_OFF_AT = 6, IMG_COL = 7,
+              IMG_INTS = 8;
+__global__ __launch_bounds__(64 * EXPAND_WAVES) void trie_level_expand_sets_kernel(
+    const bf16_t* __restrict__ hid, int ld_h, const bf16_t* __restrict__ Wh, int ldw, int d, float scale, const float* __restrict__ logits, int ld,
+    const float* __restrict__ lse, const float* __restrict__ path_in, float* __restrict__ path_out, const int* __restrict__ child_parent,
+    const int* __restrict__ child_tok, int n_child_all, const int* __restrict__ term_row, int n_term_all, const int* __restrict__ term_off,
+    int n_off_all, const int* __restrict__ term_phrase, int n_term_phrases, const int* __restrict__ img, int e_child, int e_term,
+    int64_t* __restrict__ ids, int ids_ld, float* __restrict__ logprob, int lp_ld, int kmax, int eos, int B, int W, int V) {
+    const int lane = threadIdx.x & 63;
+    const long wv = (long)blockIdx.x * EXPAND_WAVES + (threadIdx.x >> 6);
+    const long n_exp = (long)B * e_child, total = n_exp + (long)B * e_term;
+    if (wv >= total) return;                                 // wave-uniform, as every return below
+    const bool child = wv < n_exp;
+    const int b = child ? (int)(wv / e_child) : (int)((wv - n_exp) / e_term);
+    const int j = child ? (int)(wv % e_child) : (int)((wv - n_exp) % e_term);
+    const int* st = img + (size_t)b * IMG_INTS;
+    const int col = st[IMG_COL];
+    if (st[IMG_LEVEL] < 0) {                                 // a forced column, or a finished image
+        const int k = st[IMG_FORCED];
+        if (!child || k < 0 || k >= V || j >= W || col < 0 || col >= ids_ld) return;
+        if (lane == 0) {
+            const size_t r = (size_t)b * W + j;
+            path_out[r] = path_in[r];
+            ids[r * ids_ld + col] = k;
+        }
+        return;
     }
+    int p, tok, at;
+    if (child) {
+        const int n = st[IMG_N_CHILD];
+        at = st[IMG_CHILD_AT];
+        if (j >= n || at < 0 || at > n_child_all - n) return;
+        p = child_parent[at + j];
+        tok = child_tok[at + j];
+    } else {
+        const int n = st[IMG_N_TERM], off = st[IMG_OFF_AT];
+        at = st[IMG_TERM_AT];
+        if (j >= n || at < 0 || at > n_term_all - n || off < 0 || off > n_off_all - n - 1) return;
+        p = term_row[at + j];
+        tok = eos;
+        at = off;
+    }
+    if (p < 0 || p >= W || tok < 0 || tok >= V) return;
+    const size_t pr = (size_t)b * W + p;
+    const float v = expand_value(hid, ld_h, Wh, ldw, d, scale, logits, ld, lse, path_in, pr, tok, lane);
+    if (child) {
+        if (col < 0 || col >= ids_ld) return;
+        if (lane == 0) {
+            const size_t c = (size_t)b * W + j;
+            path_out[c] = v;
+            ids[c * ids_ld + col] = tok;
+        }
+        return;
+    }
+    expand_terminal_store(term_off + at, term_phrase, j, n_term_phrases, logprob + (size_t)b * lp_ld, kmax, v, lane);
 }
 
 }  // namespace
@@ -327,6 +411,27 @@ extern "C" int i2t_rows_lse(void* stream, const float* logits, int ld, float* ls
     return I2T_OK;
 }
 
+namespace {
+
+// What i2t_trie_level_expand and i2t_trie_level_expand_sets both hold their EOS, their two path buffers and their z operands to, in
+// this order; `fn` names the caller in every message.
+int check_expand_operands(const char* fn, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
+                          const float* logits, int ld, const float* path_in, const float* path_out, int eos, int V) {
+    (void)hidden, (void)w_head;
+    TRIE_TRY(check_eos_in_vocab(fn, eos, V));
+    I2T_REQUIRE(path_in != path_out, "%s: path_in and path_out are one buffer: they swap each level", fn);
+    if (logits) {
+        TRIE_TRY(check_logits_rows(fn, ld, V));
+    } else {
+        I2T_REQUIRE(d > 0 && d % 8 == 0 && ld_hidden >= d && ld_w >= d && ld_hidden % 8 == 0 && ld_w % 8 == 0,
+                    "%s: d = %d must be a multiple of 8, hidden / head rows (ld %d / %d) 16-byte aligned", fn, d, ld_hidden, ld_w);
+        I2T_REQUIRE(scale == scale && scale - scale == 0.f, "%s: scale must be finite", fn);
+    }
+    return I2T_OK;
+}
+
+}  // namespace
+
 extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
                                      const float* logits, int ld, const float* lse, const float* path_in, float* path_out,
                                      const int* child_parent, const int* child_tok, int n_child, const int* term_row, const int* term_off,
@@ -340,15 +445,7 @@ extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hi
     I2T_REQUIRE(B > 0 && W > 0 && V > 0 && ids_ld > 0 && lp_ld > 0 && (long)B * W < (1l << 31),
                 "i2t_trie_level_expand: B = %d images, W = %d rows each, V = %d, ids_ld = %d, lp_ld = %d", B, W, V, ids_ld, lp_ld);
     I2T_REQUIRE(n_child <= W && n_term <= W, "i2t_trie_level_expand: n_child = %d, n_term = %d exceed the W = %d rows of an image", n_child, n_term, W);
-    TRIE_TRY(check_eos_in_vocab("i2t_trie_level_expand", eos, V));
-    I2T_REQUIRE(path_in != path_out, "i2t_trie_level_expand: path_in and path_out are one buffer: they swap each level");
-    if (logits) {
-        TRIE_TRY(check_logits_rows("i2t_trie_level_expand", ld, V));
-    } else {
-        I2T_REQUIRE(d > 0 && d % 8 == 0 && ld_hidden >= d && ld_w >= d && ld_hidden % 8 == 0 && ld_w % 8 == 0,
-                    "i2t_trie_level_expand: d = %d must be a multiple of 8, hidden / head rows (ld %d / %d) 16-byte aligned", d, ld_hidden, ld_w);
-        I2T_REQUIRE(scale == scale && scale - scale == 0.f, "i2t_trie_level_expand: scale must be finite");
-    }
+    TRIE_TRY(check_expand_operands("i2t_trie_level_expand", hidden, ld_hidden, w_head, ld_w, d, scale, logits, ld, path_in, path_out, eos, V));
     I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(hidden) && ALIGNED16(w_head) && ALIGNED16(lse) && ALIGNED16(path_in) && ALIGNED16(path_out) &&
                     ALIGNED16(child_parent) && ALIGNED16(child_tok) && ALIGNED16(term_row) && ALIGNED16(term_off) && ALIGNED16(term_phrase) &&
                     ALIGNED16(ids) && ALIGNED16(logprob),
@@ -361,6 +458,47 @@ extern "C" int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hi
                        path_out, child_parent, child_tok, n_child, term_row, term_off, term_phrase, n_term, n_term_phrases, ids, ids_ld, len_ptr,
                        logprob, lp_ld, eos, B, W, V);
     I2T_CHECK_LAUNCH("i2t_trie_level_expand");
+    return I2T_OK;
+}
+
+// i2t_trie_level_expand with the images of one launch at different levels of different tries.  The per-image state is
+// device memory, so its CONTENTS are the host's to check before upload (ops.trie_set_state); here: the operands, the sizes the kernel
+// clips every image's range to, and everything i2t_trie_level_expand refuses.
+extern "C" int i2t_trie_level_expand_sets(void* stream, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
+                                          const float* logits, int ld, const float* lse, const float* path_in, float* path_out,
+                                          const int* child_parent, const int* child_tok, int n_child_all, const int* term_row, int n_term_all,
+                                          const int* term_off, int n_off_all, const int* term_phrase, int n_term_phrases,
+                                          const int* image_state, int e_child, int e_term, int64_t* ids, int ids_ld, float* logprob, int lp_ld,
+                                          int kmax, int eos, int B, int W, int V) {
+    const char* fn = "i2t_trie_level_expand_sets";
+    I2T_REQUIRE(lse && path_in && path_out && ids && logprob && (logits || (hidden && w_head)), "%s: null pointer", fn);
+    I2T_REQUIRE(image_state, "%s: null image_state: every image names its level, its table ranges and its column", fn);
+    I2T_REQUIRE(n_child_all >= 0 && n_term_all >= 0 && n_off_all >= 0 && n_term_phrases >= 0,
+                "%s: n_child_all = %d, n_term_all = %d, n_off_all = %d, n_term_phrases = %d: none may be negative", fn, n_child_all, n_term_all,
+                n_off_all, n_term_phrases);
+    I2T_REQUIRE((n_child_all == 0 || (child_parent && child_tok)) && (n_term_all == 0 || (term_row && term_off && term_phrase)),
+                "%s: null pointer (a level table)", fn);
+    I2T_REQUIRE(n_term_all == 0 || n_off_all > n_term_all, "%s: n_off_all = %d offsets for n_term_all = %d terminal rows: every level has one more",
+                fn, n_off_all, n_term_all);
+    I2T_REQUIRE(B > 0 && W > 0 && V > 0 && ids_ld > 0 && lp_ld > 0 && (long)B * W < (1l << 31),
+                "%s: B = %d images, W = %d rows each, V = %d, ids_ld = %d, lp_ld = %d", fn, B, W, V, ids_ld, lp_ld);
+    I2T_REQUIRE(kmax >= 1 && kmax <= lp_ld, "%s: kmax = %d phrases per image (1 .. lp_ld = %d)", fn, kmax, lp_ld);
+    I2T_REQUIRE(e_child >= 0 && e_term >= 0 && e_child <= W && e_term <= W,
+                "%s: e_child = %d, e_term = %d entries per image (0 .. the W = %d rows of an image)", fn, e_child, e_term, W);
+    TRIE_TRY(check_expand_operands(fn, hidden, ld_hidden, w_head, ld_w, d, scale, logits, ld, path_in, path_out, eos, V));
+    I2T_REQUIRE(ALIGNED16(image_state), "%s: misaligned image_state (16 bytes)", fn);
+    I2T_REQUIRE(ALIGNED16(logits) && ALIGNED16(hidden) && ALIGNED16(w_head) && ALIGNED16(lse) && ALIGNED16(path_in) && ALIGNED16(path_out) &&
+                    ALIGNED16(child_parent) && ALIGNED16(child_tok) && ALIGNED16(term_row) && ALIGNED16(term_off) && ALIGNED16(term_phrase) &&
+                    ALIGNED16(ids) && ALIGNED16(logprob),
+                "%s: misaligned base pointer (16 bytes)", fn);
+    const long waves = (long)B * e_child + (long)B * e_term;
+    if (waves == 0) return I2T_OK;
+    I2T_REQUIRE((waves + EXPAND_WAVES - 1) / EXPAND_WAVES < (1l << 31), "%s: %ld waves exceed a grid", fn, waves);
+    hipLaunchKernelGGL(trie_level_expand_sets_kernel, dim3((unsigned)((waves + EXPAND_WAVES - 1) / EXPAND_WAVES)), dim3(64 * EXPAND_WAVES), 0,
+                       (hipStream_t)stream, (const bf16_t*)hidden, ld_hidden, (const bf16_t*)w_head, ld_w, d, scale, logits, ld, lse, path_in,
+                       path_out, child_parent, child_tok, n_child_all, term_row, n_term_all, term_off, n_off_all, term_phrase, n_term_phrases,
+                       image_state, e_child, e_term, ids, ids_ld, logprob, lp_ld, kmax, eos, B, W, V);
+    I2T_CHECK_LAUNCH(fn);
     return I2T_OK;
 }
 

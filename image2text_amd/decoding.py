@@ -33,18 +33,19 @@ import torch
 from . import ops
 from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
                            PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseBeams, PhraseScores, Processors, Sampling,
-                           PhraseSets, cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
+                           PhraseSets, PhraseSetScores, cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
                            check_phrase_caption_args, check_phrase_score_args, check_phrase_search_args, check_phrase_set_caption_args,
+                           check_phrase_set_score_args,
                            check_phrase_sets, check_ragged_caption_args, decode_window, phrase_beam_sets_graph_key, plan_captions, prefill_plan,
                            takes_long_cache, text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
                             beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
-                            phrase_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
+                            phrase_scores_host, phrase_set_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
                             trie_advance_ragged_host, trie_beam_candidates_host, trie_beam_select_host, trie_beam_select_sets_host,
                             trie_mask_host, trie_mask_ragged_host)
 from .engine import BF16, F32, HotPath
-from .phrase_trie import (PhraseForest, PhraseTrie, TrieLevel, TrieLevels, level_expand_tables, phrase_forest, phrase_node_csr, phrase_trie,
-                          trie_levels)
+from .phrase_trie import (PhraseForest, PhraseTrie, SetLevelTables, TrieLevel, TrieLevels, level_expand_tables, phrase_forest, phrase_node_csr,
+                          phrase_trie, set_level_tables, set_step_state, trie_levels)
 
 assert LONG_CHUNK_KEYS == ops.LONG_CHUNK_KEYS       # caption_plan.py loads no library: it keeps the figure, ops.py the kernels' copy
 
@@ -1135,7 +1136,8 @@ class TrieScoreDecoder(BeamDecoder):
                 else:                                           # head-major [R][H][slot][64]
                     dst.view(Bp, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(src.view(-1, dc.H, n_p, 64)[take].unsqueeze(1))
 
-    def _level_step(self, st, tables, t: int, eos: int, logprob):
+    def _level_lse(self, st):
+        """the level's step on all rows and the rows' LSE into st.lse -> the z operands of the expand kernel"""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, V, d = st.B, dc.V, dc.d
         head = a.W(eng.n_head)
@@ -1144,14 +1146,41 @@ class TrieScoreDecoder(BeamDecoder):
             self._final_norm(st)
             ops.gemm_lse(st.hid, head, st.stats, R, V, d)
             ops.lse_token_logprob(st.stats, st.hid, head, st.no_label, st.lse, st.no_lp, R, V, d, ignore_index=-100)
-            z = dict(hidden=st.hid, w_head=head, d=d)
-        else:
-            self._logits_head(st)
-            ops.rows_lse(st.logits, dc.Vp, st.lse, R, V)
-            z = dict(logits=st.logits, ld=dc.Vp)
+            return dict(hidden=st.hid, w_head=head, d=d)
+        self._logits_head(st)
+        ops.rows_lse(st.logits, dc.Vp, st.lse, R, V)
+        return dict(logits=st.logits, ld=dc.Vp)
+
+    def _level_step(self, st, tables, t: int, eos: int, logprob):
+        z = self._level_lse(st)
         ops.trie_level_expand(tables, st.lse, st.path[t & 1], st.path[(t + 1) & 1], st.ids, st.ids_ld, st.counters[1:2], logprob, eos,
-                              st.images, st.W, V, **z)
+                              st.images, st.W, self.eng.dec.V, **z)
         ops.advance(st.counters, 1)
+
+    def _sets_step(self, st, tables, state, k: int, eos: int, logprob):
+        """walk step k of ``score_sets``: _level_step with every image at its own level (``state``: ops.trie_set_state)"""
+        z = self._level_lse(st)
+        ops.trie_level_expand_sets(tables, state, st.lse, st.path[k & 1], st.path[(k + 1) & 1], st.ids, st.ids_ld, logprob, eos, st.W,
+                                   self.eng.dec.V, **z)
+        ops.advance(st.counters, 1)
+
+    def _score_state_for(self, B: int, W: int, total: int, images_per_pass: Optional[int]):
+        """-> (the decoder's own state for groups of Bp images of W rows and ``total`` id columns, Bp).  The walk reads ``total`` cache
+        slots however long the text window is, and W rows per image multiply every slot: a cache of that many slots (in whole 16s) --
+        or, past text_window on a decoder that takes the long cache, cache_plan's whole chunks."""
+        block, off, prefix, llama = self._cache_args()
+        clen, long = cache_plan(block, off, prefix, total, llama)
+        clen = clen if long else min(clen, prefix + -(-total // 16) * 16)
+        ids_ld = -(-total // 8) * 8
+        if images_per_pass is None:
+            images_per_pass = max(1, TRIE_SCORE_BYTES // (W * self.row_bytes(clen, ids_ld)))
+        Bp = min(int(images_per_pass), B)
+        st = self._score_state
+        if not self._reusable(st, Bp * W, total, lambda st: st.W == W and st.images == Bp and st.clen >= clen):
+            self._score_state = st = None                       # the old buffers go before the new ones are made
+            self._score_state = st = self._build_score(Bp, W, ids_ld, clen)
+        assert total <= st.tmax
+        return st, Bp
 
     @torch.no_grad()
     def score(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, images_per_pass: Optional[int] = None) -> PhraseScores:
@@ -1166,21 +1195,7 @@ class TrieScoreDecoder(BeamDecoder):
         levels = trie_levels(trie)
         W = levels.wmax
         total = P + trie.longest + 1
-        block, off, prefix, llama = self._cache_args()
-        # The walk reads prompt + longest phrase + 1 cache slots however long the text window is, and W rows per image multiply every
-        # slot: the state is this decoder's own, with a cache of that many slots (in whole 16s) -- or, past text_window on a decoder that
-        # takes the long cache, cache_plan's whole chunks
-        clen, long = cache_plan(block, off, prefix, total, llama)
-        clen = clen if long else min(clen, prefix + -(-total // 16) * 16)
-        ids_ld = -(-total // 8) * 8
-        if images_per_pass is None:
-            images_per_pass = max(1, TRIE_SCORE_BYTES // (W * self.row_bytes(clen, ids_ld)))
-        Bp = min(int(images_per_pass), B)
-        st = self._score_state
-        if not self._reusable(st, Bp * W, total, lambda st: st.W == W and st.images == Bp and st.clen >= clen):
-            self._score_state = st = None                       # the old buffers go before the new ones are made
-            self._score_state = st = self._build_score(Bp, W, ids_ld, clen)
-        assert total <= st.tmax
+        st, Bp = self._score_state_for(B, W, total, images_per_pass)
         # every level's tables, checked on the host and uploaded once per call
         tables = [ops.trie_level_tables(*level_expand_tables(trie, levels, t), W, dc.V, K, dev) for t in range(trie.longest + 1)]
         anc = [torch.from_numpy(lv.anc).to(dev) for lv in levels.levels]
@@ -1211,6 +1226,71 @@ class TrieScoreDecoder(BeamDecoder):
             depth[lv.nodes] = t
         lengths = torch.from_numpy((depth[trie.phrase_node] + 1).astype(np.int32)).to(dev)
         return PhraseScores(out, best, lengths)
+
+
+    @torch.no_grad()
+    def score_sets(self, images, prompt_ids: torch.Tensor, tries, index, eos: int, plen=None,
+                   images_per_pass: Optional[int] = None) -> PhraseSetScores:
+        """``phrase_set_scores_host`` for every image of the batch, on the device.  ``tries``, ``index``, ``plen``: what
+        ``check_phrase_set_score_args`` returned.  ``score``'s structure: the encoder once, groups of ``images_per_pass``, eager launches.
+        All rows share the step counter: min p_b - 1 prefill steps, then one walk step per id column up to the group's largest p_b +
+        longest phrase; in each the host says where every image stands (``set_step_state``) and uploads that and the images' history
+        tables -- ``TrieLevels.history`` of the image's own level and prompt length, the identity for a forced or finished image."""
+        eng = self.eng
+        dc = eng.dec
+        a = eng.prepare(False)
+        dev = a.device
+        prompt_ids = prompt_ids.to(dev)
+        B, P = prompt_ids.shape
+        index = np.asarray(index, dtype=np.int64)
+        plen = np.full(B, P, dtype=np.int64) if plen is None else np.asarray(plen, dtype=np.int64)
+        tabs = set_level_tables(tries)
+        W, K = tabs.wmax, tabs.kmax
+        longest = np.array([tries[s].longest for s in index.tolist()], dtype=np.int64)
+        pmin, pmax = int(plen.min()), int(plen.max())
+        total = int((plen + longest + 1).max())
+        st, Bp = self._score_state_for(B, W, total, images_per_pass)
+        tables = ops.trie_set_tables(tabs, W, dc.V, dev)        # checked on the host and uploaded once per call
+        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
+        keep = torch.arange(pmax, device=dev)[None, :] < torch.from_numpy(plen).to(dev)[:, None]
+        prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
+        prompt_host = prompt.cpu().numpy()
+        identity = np.arange(Bp * W, dtype=np.int32).reshape(Bp, W, 1).repeat(st.clen, axis=2)
+        histories = {}
+
+        def history(s, t, first):
+            if (s, t, first) not in histories:
+                histories[s, t, first] = tabs.levels[s].history(t, first, st.clen)
+            return histories[s, t, first]
+        out = torch.full((B, K), float('-inf'), dtype=F32, device=dev)
+        part = torch.zeros(Bp, (K + 3) // 4 * 4, dtype=F32, device=dev)
+        self.last_passes = 0
+        pre = self._encode_all(st, images, B)
+        for i in range(0, B, Bp):
+            n = min(Bp, B - i)
+            take_host = np.minimum(np.arange(i, i + Bp), B - 1)                 # a short last group is filled with its last image
+            take = torch.from_numpy(take_host).to(dev)
+            g_index, g_plen, g_prompt = index[take_host], plen[take_host], prompt_host[take_host]
+            self._load_group(st, pre, take)
+            self._reset(st, prompt[take].repeat_interleave(W, dim=0), pmax)
+            st.path[0].zero_()
+            part.fill_(float('-inf'))
+            for _ in range(pmin - 1):                           # prompt tokens every image has before its last: fill the cache only
+                self._step(st, False)
+            for k, col in enumerate(range(pmin, int((g_plen + longest[take_host]).max()) + 1)):
+                state = set_step_state(tabs, g_index, g_plen, g_prompt, col)
+                hist = identity.copy()
+                for b in np.flatnonzero(state[:, 0] >= 2).tolist():              # below level 2 a table is the identity
+                    s = int(g_index[b])
+                    h = history(s, int(state[b, 0]), st.prefix + int(g_plen[b]) - 1)
+                    hist[b, :h.shape[0]] = b * W + h
+                st.hist.copy_(torch.from_numpy(hist).view(Bp * W, st.clen))
+                self._sets_step(st, tables, ops.trie_set_state(tables, state, W, dc.V, st.ids_ld, dev), k, eos, part)
+            out[i:i + n] = part[:n, :K]
+            self.last_passes += 1
+        top = out.max(dim=1, keepdim=True).values
+        best = torch.where(out == top, torch.arange(K, device=dev)[None, :], torch.full((), K, device=dev)).min(dim=1).values
+        return PhraseSetScores(out, best, torch.from_numpy(tabs.lengths).to(dev))
 
 
 class PhraseBeamDecoder(BeamDecoder):

@@ -8,7 +8,7 @@ from typing import Optional
 import numpy as np
 
 from .caption_plan import BEAM_DEAD, LONG_CHUNK_KEYS
-from .phrase_trie import PhraseTrie, phrase_node_csr, trie_levels
+from .phrase_trie import PhraseTrie, phrase_node_csr, phrase_trie, set_level_tables, set_step_state, trie_levels
 
 
 def split_attention_host(q: np.ndarray, k: np.ndarray, v: np.ndarray, scale: float, chunk: int = LONG_CHUNK_KEYS) -> np.ndarray:
@@ -235,6 +235,61 @@ def phrase_scores_host(step_logits_fn, trie: PhraseTrie, eos: int, prompt=()):
     depth_of = {int(nd): t for t, lv in enumerate(levels.levels) for nd in lv.nodes.tolist()}
     lengths = np.array([depth_of[int(nd)] + 1 for nd in trie.phrase_node], dtype=np.int32)
     return SimpleNamespace(logprob=logprob, best=int(np.flatnonzero(logprob == logprob.max())[0]), lengths=lengths)
+
+
+def phrase_set_scores_host(step_logits_fn, sets, set_index, eos: int, prompts, prompt_lengths=None):
+    """The normative replica of ``score_phrases(phrase_sets=...)`` on the host: ``step_logits_fn(b, sequence)`` gives the
+    raw fp32 logits row [V] that follows a token sequence for image b (a list of ints: the image's prompt, then the path from its set's
+    root).  ``sets``: S phrase sets (token-id sequences, or the ``PhraseTrie`` of each); ``set_index`` [B]; ``prompts`` [B][>= p_b] with
+    ``prompt_lengths`` [B] (None: every row's whole length).  It walks as the device does: one global column counter from min p_b on,
+    every image forced, at its own level of its own set's tables (``set_level_tables`` / ``set_step_state``, the tables the kernel
+    reads) or finished; a child's path sum is path_in[parent] + (z[token] - lse) and a phrase that ends at a node gets path_in[node] +
+    (z[eos] - lse), in exactly this order in fp32 -- i2t_trie_level_expand_sets', which is i2t_trie_level_expand's: for S = 1 and equal
+    lengths the values are ``phrase_scores_host``'s bit for bit.
+    -> SimpleNamespace(logprob f32 [B, Kmax], -inf behind an image's own set; best int64 [B], the lowest index on ties; lengths int32
+    [S, Kmax], 0 in the padding; steps: the walk steps; states: every step's int32 [B, 8])."""
+    f32 = np.float32
+    tries = [s if isinstance(s, PhraseTrie) else phrase_trie(s, eos, 1 << 31, 1 << 30) for s in sets]
+    tabs = set_level_tables(tries)
+    set_index = [int(s) for s in np.asarray(set_index).reshape(-1)]
+    B, W = len(set_index), tabs.wmax
+    prompts = [[int(t) for t in np.asarray(p).reshape(-1)] for p in prompts]
+    plen = [len(p) for p in prompts] if prompt_lengths is None else [int(p) for p in np.asarray(prompt_lengths).reshape(-1)]
+    assert len(prompts) == B and len(plen) == B and all(1 <= plen[b] <= len(prompts[b]) for b in range(B))
+    logprob = np.full((B, tabs.kmax), -np.inf, dtype=f32)
+    path_in, path_out = np.zeros((B, W), dtype=f32), np.zeros((B, W), dtype=f32)
+    seqs = [[[]] + [None] * (W - 1) for _ in range(B)]
+    states = []
+    for col in range(min(plen), max(plen[b] + int(tries[set_index[b]].longest) for b in range(B)) + 1):
+        st = set_step_state(tabs, set_index, plen, prompts, col)
+        states.append(st)
+        for b in range(B):
+            level, forced, c_at, n_c, t_at, n_t, o_at, _ = (int(v) for v in st[b])
+            if level < 0:
+                if forced >= 0:
+                    path_out[b] = path_in[b]
+                continue
+            rows = {}
+
+            def row(p):
+                if p not in rows:
+                    z = np.asarray(step_logits_fn(b, prompts[b][:plen[b]] + seqs[b][p]), dtype=f32).reshape(-1)
+                    rows[p] = (z, _row_lse_host(z))
+                return rows[p]
+            nxt = [None] * W
+            for j in range(n_c):
+                p, tk = int(tabs.child_parent[c_at + j]), int(tabs.child_tok[c_at + j])
+                z, lse = row(p)
+                path_out[b, j], nxt[j] = f32(path_in[b, p] + f32(z[tk] - lse)), seqs[b][p] + [tk]
+            for j in range(n_t):
+                p = int(tabs.term_row[t_at + j])
+                z, lse = row(p)
+                for i in tabs.term_phrase[tabs.term_off[o_at + j]:tabs.term_off[o_at + j + 1]].tolist():
+                    logprob[b, i] = f32(path_in[b, p] + f32(z[eos] - lse))
+            seqs[b] = nxt
+        path_in, path_out = path_out, path_in
+    best = np.array([int(np.flatnonzero(r == r.max())[0]) for r in logprob], dtype=np.int64)
+    return SimpleNamespace(logprob=logprob, best=best, lengths=tabs.lengths, steps=len(states), states=states)
 
 
 def beam_pool_select_host(cand_tok, cand_lp, scores, ids, hist, tok_lp, pool_ids, pool_lp, pool_score, pool_sum, pool_len, pool_n, closed,

@@ -112,6 +112,8 @@ SIGNATURES = {
     'i2t_caption_trie_advance': [P, PL, I, PI, PI, PF, I, PF, PI, PI, PI, PI, I, I, I, PI, PI, PI, PF, I, I, I],
     'i2t_rows_lse': [P, PF, I, PF, I, I],
     'i2t_trie_level_expand': [P, P, I, P, I, I, F, PF, I, PF, PF, PF, PI, PI, I, PI, PI, PI, I, I, PL, I, PI, PF, I, I, I, I, I],
+    'i2t_trie_level_expand_sets': [P, P, I, P, I, I, F, PF, I, PF, PF, PF, PI, PI, I, PI, I, PI, I, PI, I, PI, I, I, PL, I, PF, I, I, I, I, I,
+                                   I],
     'i2t_trie_beam_candidates': [P, PF, I, PI, PF, PI, PI, PI, I, I, I, PI, PI, PF, PF, PF, I, I, I],
     'i2t_trie_beam_select': [P, PI, PF, PF, PI, PF, PI, PI, PI, I, I, I, PL, I, PI, I, PI, PF, PF, PI, PI, PI, PI, PI, PI, I, I, I, I, F],
     'i2t_caption_trie_mask_ragged': [P, PF, I, PI, PI, PI, PI, I, I, I, PI, PF, PF, I, PI, PI, I, I, I],
@@ -189,7 +191,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _lib = None
 
 

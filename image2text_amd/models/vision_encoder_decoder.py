@@ -386,7 +386,8 @@ class VisionEncoderDecoder(nn.Module):
         return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), None if plen is None else torch.from_numpy(plen).to(dev))
 
     @torch.no_grad()
-    def score_phrases(self, images, prompt_ids, phrases, eos_token_id, images_per_pass=None):
+    def score_phrases(self, images, prompt_ids, phrases=None, eos_token_id=None, images_per_pass=None, phrase_sets=None, phrase_set_index=None,
+                      prompt_lengths=None):
         """Exact closed-set scoring (no counterpart in the reference) -> ``decoding.PhraseScores(logprob [B, K], best [B],
         lengths [K])``: ``logprob[b, k]`` (fp32) is the raw log-likelihood of ``phrases[k]`` followed by ``eos_token_id`` after
         ``prompt_ids[b]`` for image b -- the sum of the raw log_softmax over the phrase's tokens and the EOS, the quantity ``score`` /
@@ -401,9 +402,28 @@ class VisionEncoderDecoder(nn.Module):
         the result.  Refusals, before anything runs (``caption_plan.check_phrase_score_args``): ValueError for everything
         ``generate_captions`` refuses about the set itself, prompt + longest phrase + 1 past the text window, ``images_per_pass`` < 1;
         NotImplementedError for a non-causal decoder and for sparse nano-mini blocks.  ``generate_captions``, ``score`` and ``rerank``
-        are untouched by this call: it keeps a decoder state of its own."""
-        from ..decoding import TrieScoreDecoder, caption_facts, check_phrase_score_args
+        are untouched by this call: it keeps a decoder state of its own.
+        ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths`` are ``search_phrases``' arguments of those names, with
+        the same meanings, dtypes and refusals: S phrase lists, image b answering from set ``phrase_set_index[b]`` (None: S == B, set b)
+        behind its own prompt ``prompt_ids[b, :p_b]`` (later columns are ignored; ``prompt_lengths`` None: every column).  The result is
+        then ``decoding.PhraseSetScores(logprob [B, Kmax], best [B], lengths [S, Kmax])``, Kmax the phrases of the largest set:
+        ``logprob[b, k]`` for k < K_s is the same quantity for phrase k of the image's OWN set behind its own prompt and ``-inf`` for
+        k >= K_s; ``best[b]`` the argmax within the image's own set, the lowest index on ties; ``lengths[s, k]`` the tokens of phrase k
+        of set s + 1, 0 in the padding.  One call, one walk: the images of a step stand at different levels of different tries, W = the
+        widest level of any set.  Refusals (``caption_plan.check_phrase_set_score_args``): ValueError for ``phrases`` together with
+        ``phrase_sets``, ``phrase_set_index`` or ``prompt_lengths`` without ``phrase_sets`` (one list for all images:
+        ``phrase_sets=[phrases], phrase_set_index=[0] * B``), the largest p_b + longest phrase of b's set + 1 past the text window,
+        ``images_per_pass`` < 1; the same NotImplementedErrors.  With the three at None the call is what it was, bit for bit."""
+        from ..decoding import TrieScoreDecoder, caption_facts, check_phrase_score_args, check_phrase_set_score_args
         facts = caption_facts(self)
+        if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
+            tries, index, plen = check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V,
+                                                             prompt_ids.shape[0], prompt_ids.shape[1], facts.cache_window, facts.causal,
+                                                             facts.sparse, images_per_pass)
+            return self._decoder('_trie_scorer', TrieScoreDecoder).score_sets(images, prompt_ids.to(next(self.parameters()).device), tries, index,
+                                                                              int(eos_token_id), plen, images_per_pass)
+        if phrases is None:
+            raise ValueError('score_phrases needs phrases or phrase_sets')
         trie = check_phrase_score_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, facts.causal, facts.sparse,
                                        images_per_pass)
         return self._decoder('_trie_scorer', TrieScoreDecoder).score(images, prompt_ids.to(next(self.parameters()).device), trie,

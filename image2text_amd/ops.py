@@ -924,6 +924,98 @@ def trie_level_expand(tables: TrieLevelTables, lse, path_in, path_out, ids, ids_
                              t.term_phrase, t.n_term, t.n_term_phrases, ids, ids_ld, len_ptr, logprob, logprob.stride(0), int(eos), B, W, V)
 
 
+class TrieSetTables:
+    """The level tables of every (set, level) of a score_phrases(phrase_sets=...) call on the device, end to end (int32, one allocation
+    each; trie_set_tables), with the sizes trie_level_expand_sets hands the kernel."""
+
+    def __init__(self, child_parent, child_tok, term_row, term_off, term_phrase, n_child_all, n_term_all, n_off_all, n_term_phrases, kmax):
+        self.child_parent, self.child_tok, self.term_row, self.term_off, self.term_phrase = child_parent, child_tok, term_row, term_off, term_phrase
+        self.n_child_all, self.n_term_all, self.n_off_all, self.n_term_phrases, self.kmax = n_child_all, n_term_all, n_off_all, n_term_phrases, kmax
+
+
+def trie_set_tables(tabs, W: int, V: int, device) -> TrieSetTables:
+    """``phrase_trie.set_level_tables``' arrays, checked BEFORE upload as trie_level_tables checks one level's, segment by segment:
+    I2TError for a segment outside its arrays or wider than W, a parent or terminal row outside [0, W), a token outside [0, V), a
+    segment's offsets that do not ascend inside term_phrase, a phrase index outside [0, kmax)."""
+    import numpy as np
+    arr = lambda a: np.asarray(a, dtype=np.int64).reshape(-1)
+    cp, ct, tr, to, tp = (arr(a) for a in (tabs.child_parent, tabs.child_tok, tabs.term_row, tabs.term_off, tabs.term_phrase))
+    seg = [arr(a) for a in (tabs.child_at, tabs.n_child, tabs.term_at, tabs.n_term, tabs.off_at)]
+    kmax = int(tabs.kmax)
+    bad = lambda a, hi: bool(a.size) and (int(a.min()) < 0 or int(a.max()) >= hi)
+    if cp.shape != ct.shape or len({a.shape for a in seg}) != 1 or kmax < 1:
+        raise _l.I2TError(f'trie_set_tables: {cp.shape[0]} parent rows for {ct.shape[0]} tokens, segment arrays of {[a.shape[0] for a in seg]}, kmax = {kmax}')
+    for g, (ca, nc, ta, nt, oa) in enumerate(zip(*(a.tolist() for a in seg))):
+        if min(ca, nc, ta, nt, oa) < 0 or ca + nc > cp.shape[0] or ta + nt > tr.shape[0] or oa + nt + 1 > to.shape[0]:
+            raise _l.I2TError(f'trie_set_tables: segment {g} lies outside its tables')
+        if nc > W or nt > W:
+            raise _l.I2TError(f'trie_set_tables: segment {g}: {nc} child rows, {nt} terminal rows exceed the W = {W} rows of an image')
+        off = to[oa:oa + nt + 1]
+        if int(off[0]) < 0 or int(off[-1]) > tp.shape[0] or bool((np.diff(off) < 0).any()):
+            raise _l.I2TError(f'trie_set_tables: segment {g}: term_off does not ascend inside the {tp.shape[0]} phrase indices')
+    if bad(cp, W):
+        raise _l.I2TError(f'trie_set_tables: a parent row outside [0, {W})')
+    if bad(tr, W):
+        raise _l.I2TError(f'trie_set_tables: a terminal row outside [0, {W})')
+    if bad(ct, V):
+        raise _l.I2TError(f'trie_set_tables: a token outside the vocabulary [0, {V})')
+    if bad(tp, kmax):
+        raise _l.I2TError(f'trie_set_tables: a phrase index outside [0, {kmax})')
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(np.concatenate((a, np.zeros(1, np.int64))).astype(np.int32))).to(device)
+    return TrieSetTables(up(cp), up(ct), up(tr), up(to), up(tp), int(cp.shape[0]), int(tr.shape[0]), int(to.shape[0]), int(tp.shape[0]), kmax)
+
+
+class TrieSetState:
+    """The per-image state of one trie_level_expand_sets launch on the device (int32 [B, 8]; trie_set_state) and the entries per image
+    its two parts need."""
+
+    def __init__(self, state, e_child, e_term, B):
+        self.state, self.e_child, self.e_term, self.B = state, e_child, e_term, B
+
+
+def trie_set_state(tables: TrieSetTables, state, W: int, V: int, ids_ld: int, device) -> TrieSetState:
+    """One step's per-image state (``phrase_trie.set_step_state``: int [B, 8] = level or -1, forced token or -1, child start and count,
+    terminal start and count, offset start, id column), checked BEFORE upload -- the entry point cannot read device memory --:
+    I2TError for a level below -1, a forced token outside [-1, V), a range of an image at a level outside the tables or wider than W,
+    a column outside [0, ids_ld)."""
+    import numpy as np
+    st = np.asarray(state, dtype=np.int64)
+    if st.ndim != 2 or st.shape[1] != 8 or st.shape[0] < 1:
+        raise _l.I2TError(f'trie_set_state: a state of shape {tuple(st.shape)}: 8 integers per image')
+    level, forced, ca, nc, ta, nt, oa, col = st.T
+    at = level >= 0
+    if bool((level < -1).any()):
+        raise _l.I2TError('trie_set_state: a level below -1')
+    if bool(((forced < -1) | (forced >= V))[~at].any()):
+        raise _l.I2TError(f'trie_set_state: a forced token outside [-1, {V})')
+    t = tables
+    if bool(((ca < 0) | (nc < 0) | (nc > W) | (ca + nc > t.n_child_all) | (ta < 0) | (nt < 0) | (nt > W) | (ta + nt > t.n_term_all) | (oa < 0)
+             | (oa + nt + 1 > t.n_off_all))[at].any()):
+        raise _l.I2TError(f"trie_set_state: an image's table ranges lie outside the tables or exceed the W = {W} rows of an image")
+    if bool(((col < 0) | (col >= ids_ld)).any()):
+        raise _l.I2TError(f'trie_set_state: an id column outside [0, {ids_ld})')
+    e_child = max(int(nc[at].max(initial=0)), W if bool((~at & (forced >= 0)).any()) else 0)
+    return TrieSetState(torch.from_numpy(np.ascontiguousarray(st.astype(np.int32))).to(device), e_child, int(nt[at].max(initial=0)), int(st.shape[0]))
+
+
+def trie_level_expand_sets(tables: TrieSetTables, state: TrieSetState, lse, path_in, path_out, ids, ids_ld, logprob, eos, W, V, *, hidden=None,
+                           w_head=None, d=0, scale=1.0, logits=None, ld=0):
+    """one step of score_phrases(phrase_sets=...)'s walk: trie_level_expand with every image at its own level of its own set's tables
+    (``tables``: trie_set_tables), in a forced prompt column or finished (``state``: trie_set_state); logprob [B, >= kmax]
+    (include/i2t.h::i2t_trie_level_expand_sets)"""
+    B = state.B
+    assert all(t.is_contiguous() and t.numel() >= B * W for t in (lse, path_in, path_out)) and ids.shape[0] >= B * W
+    assert logprob.dim() == 2 and logprob.stride(-1) == 1 and logprob.shape[0] >= B and logprob.shape[1] >= tables.kmax
+    assert logits is None or logits.shape[0] >= B * W
+    assert logits is not None or (hidden.dtype == BF16 and w_head.dtype == BF16 and hidden.stride(-1) == 1 and w_head.stride(-1) == 1
+                                  and hidden.shape[0] >= B * W and w_head.shape[0] >= V)
+    t = tables
+    _k.i2t_trie_level_expand_sets(hidden, 0 if hidden is None else hidden.stride(0), w_head, 0 if w_head is None else w_head.stride(0), int(d),
+                                  float(scale), logits, int(ld), lse, path_in, path_out, t.child_parent, t.child_tok, t.n_child_all, t.term_row,
+                                  t.n_term_all, t.term_off, t.n_off_all, t.term_phrase, t.n_term_phrases, state.state, state.e_child, state.e_term,
+                                  ids, ids_ld, logprob, logprob.stride(0), t.kmax, int(eos), B, W, V)
+
+
 def trie_beam_candidates(logits, ld, node, path, child_off, child_tok, term, eos, ctrl, cand_edge, cand_total, fin_total, R, W, V, lse=None):
     """the candidates of search_phrases' step on fp32 logits rows: per live row (node[r] a trie node) the W best children by
     path + (z[token] - lse) as edge indices and totals, and the total of ending here at a node that ends a phrase; lse (optional, f32

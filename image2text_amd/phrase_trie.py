@@ -1,5 +1,5 @@
-"""Phrase sets as token tries (DESIGN.md 4u, 4v): the CSR trie ``generate_captions(phrases=...)`` walks on the device and the per-depth
-tables ``score_phrases`` walks level by level.  Host only (numpy; torch only to accept tensors of ids); ``decoding`` re-exports every name."""
+"""Phrase sets as token tries (DESIGN.md 4u, 4v, 4ab): the CSR trie ``generate_captions(phrases=...)`` walks on the device and the per-depth
+tables ``score_phrases`` walks level by level, for one set or for a set per image.  Host only (numpy; torch only to accept tensors of ids); ``decoding`` re-exports every name."""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -245,3 +245,69 @@ def level_expand_tables(trie: PhraseTrie, levels: TrieLevels, t: int):
         term_phrase += idx[off[nd]:off[nd + 1]].tolist()
         term_off.append(len(term_phrase))
     return child_parent.astype(i32), child_tok.astype(i32), np.array(rows, dtype=i32), np.array(term_off, dtype=i32), np.array(term_phrase, dtype=i32)
+
+
+class SetLevelTables(NamedTuple):
+    """The ``level_expand_tables`` of S phrase sets laid end to end (``set_level_tables``): segment g = level_at[s] + t
+    holds level t of set s.  All arrays numpy int32."""
+    child_parent: np.ndarray            # [n_child_all]
+    child_tok: np.ndarray               # [n_child_all]
+    term_row: np.ndarray                # [n_term_all]
+    term_off: np.ndarray                # [n_term_all + segments]: a segment's n_term + 1 offsets, absolute into term_phrase
+    term_phrase: np.ndarray             # [the phrases of all sets]: a phrase's index WITHIN ITS SET
+    child_at: np.ndarray                # [segments]: where the segment's children start in child_parent / child_tok
+    n_child: np.ndarray                 # [segments]
+    term_at: np.ndarray                 # [segments]: where its terminal rows start in term_row
+    n_term: np.ndarray                  # [segments]
+    off_at: np.ndarray                  # [segments]: where its offsets start in term_off
+    level_at: np.ndarray                # [S + 1]: set s's levels are segments level_at[s] .. level_at[s + 1]
+    levels: tuple                       # S ``TrieLevels``
+    wmax: int                           # the widest level over all sets: the rows per image of the walk
+    kmax: int                           # the phrases of the largest set
+    lengths: np.ndarray                 # [S, kmax]: the tokens of phrase k of set s + 1, 0 in the padding
+
+
+def set_level_tables(tries) -> SetLevelTables:
+    """``tries``: S >= 1 ``PhraseTrie`` (with ``phrase_node``) -> every set's per-level tables end to end"""
+    i32 = np.int32
+    cp, ct, tr, to, tp = [], [], [], [], []
+    seg = {k: [] for k in ('child_at', 'n_child', 'term_at', 'n_term', 'off_at')}
+    level_at, all_levels = [0], []
+    n_c = n_t = n_o = n_p = 0
+    kmax = max(int(t.phrase_node.shape[0]) for t in tries)
+    lengths = np.zeros((len(tries), kmax), dtype=i32)
+    for s, trie in enumerate(tries):
+        levels = trie_levels(trie)
+        all_levels.append(levels)
+        depth = np.zeros(trie.nodes, dtype=i32)
+        for t, lv in enumerate(levels.levels):
+            depth[lv.nodes] = t
+            a, b, c, d, e = level_expand_tables(trie, levels, t)
+            for k, v in zip(seg, (n_c, a.shape[0], n_t, c.shape[0], n_o)):
+                seg[k].append(v)
+            cp.append(a), ct.append(b), tr.append(c), to.append(d.astype(np.int64) + n_p), tp.append(e)
+            n_c, n_t, n_o, n_p = n_c + a.shape[0], n_t + c.shape[0], n_o + d.shape[0], n_p + e.shape[0]
+        lengths[s, :trie.phrase_node.shape[0]] = depth[trie.phrase_node] + 1
+        level_at.append(level_at[-1] + len(levels.levels))
+    cat = lambda parts: np.concatenate(parts).astype(i32)
+    return SetLevelTables(cat(cp), cat(ct), cat(tr), cat(to), cat(tp), *(np.array(seg[k], dtype=i32) for k in seg), np.array(level_at, dtype=i32),
+                          tuple(all_levels), max(lv.wmax for lv in all_levels), kmax, lengths)
+
+
+def set_step_state(tabs: SetLevelTables, set_index, plen, prompts, col: int) -> np.ndarray:
+    """int32 [B, 8]: every image's state at the walk step that writes id column ``col`` (i2t_trie_level_expand_sets
+    reads it).  Image b, whose prompt is ``prompts[b, :plen[b]]`` and whose set is ``set_index[b]``, is FORCED while col < plen[b] (level
+    -1, the token prompts[b, col]), at level t = col - plen[b] of its set while t <= the set's longest phrase (the segment's ranges),
+    else FINISHED (level -1, token -1).  Columns: level, forced token, child start, children, terminal start, terminal rows, offset
+    start, ``col``."""
+    B = len(set_index)
+    st = np.zeros((B, 8), dtype=np.int32)
+    st[:, 0], st[:, 1], st[:, 7] = -1, -1, col
+    for b in range(B):
+        s, t = int(set_index[b]), col - int(plen[b])
+        if t < 0:
+            st[b, 1] = int(prompts[b][col])
+        elif t < len(tabs.levels[s].levels):
+            g = int(tabs.level_at[s]) + t
+            st[b, :7] = (t, -1, tabs.child_at[g], tabs.n_child[g], tabs.term_at[g], tabs.n_term[g], tabs.off_at[g])
+    return st

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 18
+#define I2T_ABI_VERSION 19
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -528,6 +528,29 @@ int i2t_trie_level_expand(void* stream, const void* hidden, int ld_hidden, const
                           const int* child_parent, const int* child_tok, int n_child, const int* term_row, const int* term_off,
                           const int* term_phrase, int n_term, int n_term_phrases, int64_t* ids, int ids_ld, const int* len_ptr,
                           float* logprob, int lp_ld, int eos, int B, int W, int V);
+/* i2t_trie_level_expand with a phrase set and a prompt length per image (score_phrases' phrase_sets; DESIGN.md 4ab, ABI 19): the
+ * images of one launch stand at different levels of different tries, in a forced prompt column, or behind their last level.  The level
+ * tables of every (set, level) lie end to end: child_parent / child_tok [n_child_all], term_row [n_term_all], term_off [n_off_all]
+ * (each level's n_term + 1 offsets; they index term_phrase [n_term_phrases] absolutely).  image_state int32 [B][8] (device memory,
+ * base on 16 bytes, host-built per step) holds per image: 0 the level, or -1; 1 the forced token, or -1; 2 / 3 where its level's
+ * children start in child_parent / child_tok and how many they are; 4 / 5 the same for term_row; 6 where its level's offsets start
+ * in term_off; 7 the id column it writes.  One wave per (image, entry), the child part over e_child and the terminal part over e_term
+ * entries per image (each 0 .. W).
+ *   level -1 with a forced token k in [0, V): ids[b W + j][column] = k and path_out[b W + j] = path_in[b W + j] for j < W (the child
+ *     part; e_child must reach W for such an image); nothing is scored.  Level -1 and token -1: the image is finished, nothing of it
+ *     is read or written.
+ *   level >= 0: entry j of the image's own ranges does what i2t_trie_level_expand does with entry j of its tables, the arithmetic
+ *     operation for operation (one device function); the terminal part writes logprob[b][i], i < kmax <= lp_ld.
+ * Refused before any launch: what i2t_trie_level_expand refuses; a null or misaligned image_state; negative table sizes, fewer
+ * offsets than terminal rows + 1; e_child or e_term outside 0 .. W; kmax outside 1 .. lp_ld.  What image_state HOLDS is device memory:
+ * the host checks it before upload, and the kernel writes nothing for an entry outside its image's range, a range outside the tables,
+ * a parent row outside [0, W), a token outside [0, V), a phrase index outside [0, kmax) or a column outside [0, ids_ld). */
+int i2t_trie_level_expand_sets(void* stream, const void* hidden, int ld_hidden, const void* w_head, int ld_w, int d, float scale,
+                               const float* logits, int ld, const float* lse, const float* path_in, float* path_out,
+                               const int* child_parent, const int* child_tok, int n_child_all, const int* term_row, int n_term_all,
+                               const int* term_off, int n_off_all, const int* term_phrase, int n_term_phrases, const int* image_state,
+                               int e_child, int e_term, int64_t* ids, int ids_ld, float* logprob, int lp_ld, int kmax, int eos, int B,
+                               int W, int V);
 /* Beam search over the phrase trie (search_phrases; DESIGN.md 4w, ABI 15): the N best phrases of a set, W <= 8 rows per image (row
  * b * W + w) whatever the size of the set; every row holds a trie node (node int32 [R], -1 or anything outside [0, nodes): a dead row) and
  * an fp32 path sum (path [R]).  The trie is the CSR trie above, `nodes` and `edges` what its arrays hold.  No atomics, fixed reduction
