@@ -7,7 +7,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from .phrase_trie import PhraseForest, PhraseTrie, phrase_forest, phrase_node_csr, phrase_trie
+from .phrase_trie import PhraseForest, PhraseTrie, phrase_forest, phrase_node_csr, phrase_trie, widest_level
 
 
 class Sampling(NamedTuple):
@@ -261,26 +261,93 @@ def check_phrase_sets(phrases, phrase_sets, phrase_set_index, B: int, eos, vocab
                       int(forest.widest[used].max()) if used.size else 1, int(forest.distinct[used].min()) if used.size else 0)
 
 
+class ClosedSet(NamedTuple):
+    """The phrases of a closed-set call, whichever way the caller named them (``closed_set``): ``phrases``, one set for all images -- a
+    forest of one whose root is node 0 --, or ``phrase_sets`` / ``phrase_set_index``, a set per image.  The drivers
+    take this record; only ``per_image`` decides which entry points, graph key and result type they use."""
+    trie: object                        # the ``PhraseTrie`` / ``PhraseForest`` whose arrays go to the device
+    roots: np.ndarray                   # int32 [B]: the node image b starts at
+    longest: np.ndarray                 # int32 [B]: the tokens of the longest phrase image b may answer
+    plen: Optional[np.ndarray]          # int32 [B] under ``prompt_lengths``, else None: every prompt fills all P columns
+    widest: Optional[int]               # the widest level over the sets in use; None for one set, which ``widest_level`` counts when asked
+    distinct: int                       # the distinct phrases of the set -- of the smallest set in use
+    tries: Optional[tuple]              # every set's own ``PhraseTrie``, which ``score_phrases`` walks; None where no one asked for them
+    index: np.ndarray                   # int32 [B]: image b answers from set index[b]
+    per_image: bool                     # the call came through ``phrase_sets``
+
+    @property
+    def sets(self) -> PhraseSets:
+        return PhraseSets(self.trie, self.index, self.roots, self.longest, self.widest, self.distinct)
+
+    def widest_level(self) -> int:
+        return widest_level(self.trie) if self.widest is None else self.widest
+
+
+def one_closed_set(trie: PhraseTrie, B: int) -> ClosedSet:
+    """a checked ``PhraseTrie`` as the record of a call on B images"""
+    none = np.zeros(B, dtype=np.int32)
+    return ClosedSet(trie, none, np.full(B, trie.longest, dtype=np.int32), None, None, int((trie.term >= 0).sum()), (trie,), none, False)
+
+
+def per_image_closed_set(sets: PhraseSets, plen=None, tries=None) -> ClosedSet:
+    """checked ``PhraseSets`` (and prompt lengths int32 [B], and the sets' own tries) as the record of a call"""
+    return ClosedSet(sets.forest, sets.roots, sets.longest, plen, sets.widest, sets.smallest, tries, sets.index, True)
+
+
+def held_phrase_trie(trie: PhraseTrie, eos, vocab: int, max_new_tokens: Optional[int] = None) -> PhraseTrie:
+    """A ``PhraseTrie`` that an earlier call built (the model hands its own to the decoder) is not built again, only held against this
+    call's ``eos`` and ``vocab`` -- and, in ``generate_captions`` alone, ``max_new_tokens`` -> the trie, or ValueError."""
+    if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
+            or bool((trie.child_tok == int(eos)).any()) or (max_new_tokens is not None and max_new_tokens < trie.longest + 1):
+        raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}' + (
+            '' if max_new_tokens is None else f', max_new_tokens = {max_new_tokens} against a longest phrase of {trie.longest} tokens'))
+    return trie
+
+
+def closed_set(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, max_new_tokens: Optional[int] = None,
+               tries: bool = False, per_image: Optional[bool] = None) -> ClosedSet:
+    """The phrase arguments of a call on ``prompt_ids`` [B, P], resolved (host only, ValueError).  With any of ``phrase_sets`` /
+    ``phrase_set_index`` / ``prompt_lengths`` (or ``per_image``, which overrides that test): ``check_phrase_sets``' refusals, then
+    ``prompt_lengths``' own (``check_ragged_caption_args``' texts); ``tries`` asks for every set's own trie.  Else ``phrases``, one set
+    for all images: ``phrase_trie``'s refusals, or ``held_phrase_trie``'s; ``max_new_tokens`` (``generate_captions``) is held against
+    this one set alone -- a caller with sets knows which are in use and checks those."""
+    if (phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None) if per_image is None else per_image:
+        sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
+        if tries:
+            each = phrase_sets.detach().cpu().tolist() if isinstance(phrase_sets, torch.Tensor) else phrase_sets
+            tries = tuple(phrase_trie(one, eos, vocab, 1 << 30) for one in each)
+        return per_image_closed_set(sets, None if prompt_lengths is None else _prompt_lengths(prompt_lengths, B, P), tries or None)
+    if isinstance(phrases, PhraseTrie):
+        return one_closed_set(held_phrase_trie(phrases, eos, vocab, max_new_tokens), B)
+    return one_closed_set(phrase_trie(phrases, eos, vocab, 1 << 30 if max_new_tokens is None else max_new_tokens), B)
+
+
+def _refuse_caption_combinations(name: str, processors_active, num_beams, causal: bool):
+    """what ``phrases`` / ``phrase_sets`` (``name``) do not combine with in ``generate_captions`` (NotImplementedError): an active logits
+    processor -- ``processors_active`` may be a callable, asked only here --, ``num_beams`` > 1, a non-causal decoder"""
+    if processors_active() if callable(processors_active) else processors_active:
+        raise NotImplementedError(f'{name} with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
+                                  'emitted, and a processor could leave a node without an allowed token')
+    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
+        raise NotImplementedError(f'{name} under num_beams > 1: the beam step has no trie state per hypothesis')
+    if not causal:
+        raise NotImplementedError(f'{name} run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
+                                  '(generate_by_recompute), which has no constrained step')
+
+
 def check_phrase_set_caption_args(phrases, phrase_sets, phrase_set_index, B: int, eos, vocab: int, max_new_tokens: int,
                                   processors_active=False, num_beams=1, causal: bool = True) -> PhraseSets:
     """``check_phrase_sets``, then ``max_new_tokens`` below the longest phrase of a set in use + 1 (ValueError), then what
     ``phrase_sets`` does not combine with in ``generate_captions`` (NotImplementedError, naming the reason): an active logits
     processor, ``num_beams`` > 1, a non-causal decoder.  ``prompt_lengths`` is NOT among them.  ``processors_active``
     may be a callable: it is asked only once the ValueErrors above have passed."""
-    sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
-    longest = int(sets.longest.max()) if B else 1
+    one = closed_set(phrases, phrase_sets, phrase_set_index, None, eos, vocab, B, 0, per_image=True)
+    longest = int(one.longest.max()) if B else 1
     if max_new_tokens < longest + 1:
         raise ValueError(f'max_new_tokens = {max_new_tokens} is below the longest phrase + 1 = {longest + 1} of the sets in use: every row '
                          f'ends with EOS')
-    if processors_active() if callable(processors_active) else processors_active:
-        raise NotImplementedError('phrase_sets with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
-                                  'emitted, and a processor could leave a node without an allowed token')
-    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
-        raise NotImplementedError('phrase_sets under num_beams > 1: the beam step has no trie state per hypothesis')
-    if not causal:
-        raise NotImplementedError('phrase_sets run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
-                                  '(generate_by_recompute), which has no constrained step')
-    return sets
+    _refuse_caption_combinations('phrase_sets', processors_active, num_beams, causal)
+    return one.sets
 
 
 def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, prompt_lengths=None, processors_active: bool = False,
@@ -289,26 +356,12 @@ def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, pro
     naming the reason: ``prompt_lengths``, an active logits processor, ``num_beams`` > 1, a non-causal decoder.  ``phrases`` may be a
     ``PhraseTrie`` that an earlier call of this function built (the model hands its own to the decoder): it is not built again, only
     held against this call's ``eos``, ``vocab`` and ``max_new_tokens``."""
-    if isinstance(phrases, PhraseTrie):
-        trie = phrases
-        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
-                or bool((trie.child_tok == int(eos)).any()) or max_new_tokens < trie.longest + 1:
-            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}, max_new_tokens = '
-                             f'{max_new_tokens} against a longest phrase of {trie.longest} tokens')
-    else:
-        trie = phrase_trie(phrases, eos, vocab, max_new_tokens)
+    one = closed_set(phrases, None, None, None, eos, vocab, 1, 0, max_new_tokens, per_image=False)
     if prompt_lengths is not None:
         raise NotImplementedError('phrases with prompt_lengths: a forced prompt column would have to hold the trie still, and the ragged '
                                   'finish rule has no such case')
-    if processors_active:
-        raise NotImplementedError('phrases with repetition_penalty / min_new_tokens / suppress_tokens: the phrase set says what may be '
-                                  'emitted, and a processor could leave a node without an allowed token')
-    if isinstance(num_beams, (int, np.integer)) and not isinstance(num_beams, bool) and num_beams > 1:
-        raise NotImplementedError('phrases under num_beams > 1: the beam step has no trie state per hypothesis')
-    if not causal:
-        raise NotImplementedError('phrases run inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
-                                  '(generate_by_recompute), which has no constrained step')
-    return trie
+    _refuse_caption_combinations('phrases', processors_active, num_beams, causal)
+    return one.trie
 
 
 class PhraseScores(NamedTuple):
@@ -316,39 +369,6 @@ class PhraseScores(NamedTuple):
     logprob: torch.Tensor               # fp32 [B, K]: the raw log-likelihood of phrase k + EOS after image b's prompt (``score``'s quantity)
     best: torch.Tensor                  # int64 [B]: the argmax over k, the lowest index on ties (duplicate phrases tie exactly)
     lengths: torch.Tensor               # int32 [K]: the tokens of each phrase + 1 (the EOS)
-
-
-def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
-                            images_per_pass=None) -> PhraseTrie:
-    """The refusals of ``score_phrases``, all before anything runs -> the trie.  ValueError: everything ``phrase_trie`` refuses about the
-    set (or a ``PhraseTrie`` built for another EOS / vocabulary, or one without ``phrase_node``), prompt + longest phrase + 1 past
-    the decode ``window`` (the text of every other call), ``images_per_pass`` < 1.  NotImplementedError, naming the reason: a
-    non-causal decoder, sparse nano-mini blocks."""
-    if isinstance(phrases, PhraseTrie):
-        trie = phrases
-        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
-                or bool((trie.child_tok == int(eos)).any()):
-            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
-        phrase_node_csr(trie)
-    else:
-        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
-    _check_score_rest(int(P) + trie.longest + 1, window, causal, sparse, images_per_pass)
-    return trie
-
-
-def _check_score_rest(total: int, window: int, causal: bool, sparse: bool, images_per_pass):
-    """``check_phrase_score_args``' refusals behind the set, which ``check_phrase_set_score_args`` shares: the decoder, the window,
-    ``images_per_pass``"""
-    if not causal:
-        raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
-                                  'state of the earlier ones --, so use rerank')
-    if sparse:
-        raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
-                                  'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
-    if total > window:
-        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
-    if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
-        raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
 
 
 class PhraseSetScores(NamedTuple):
@@ -359,27 +379,49 @@ class PhraseSetScores(NamedTuple):
     lengths: torch.Tensor               # int32 [S, Kmax]: the tokens of phrase k of set s + 1 (the EOS), 0 in the padding
 
 
-def check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int,
-                                causal: bool = True, sparse: bool = False, images_per_pass=None):
-    """The refusals of ``score_phrases(phrase_sets=..., phrase_set_index=..., prompt_lengths=...)``, all before anything
-    runs (host only) -> (the S sets' ``PhraseTrie``, index int32 [B], plen int32 [B] or None).  ValueError, in this order:
-    ``prompt_lengths`` without ``phrase_sets``; ``check_phrase_sets``' own (``phrase_set_index`` without ``phrase_sets``, ``phrases`` given
-    too, a set ``phrase_trie`` refuses, an index that is not one set of ``phrase_sets`` per image); ``prompt_lengths``' own
-    (``check_ragged_caption_args``' texts).  Then ``check_phrase_score_args``' NotImplementedError for a non-causal decoder and for sparse
-    nano-mini blocks, and its ValueError for the window -- held against the largest p_b + longest phrase of b's set + 1 -- and for
-    ``images_per_pass`` < 1."""
+def plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int, causal: bool = True,
+                       sparse: bool = False, images_per_pass=None, per_image: Optional[bool] = None) -> ClosedSet:
+    """The refusals of ``score_phrases`` on ``prompt_ids`` [B, P], all before anything runs (host only) -> the call's ``ClosedSet``, with
+    every set's own trie.  ValueError, in this order: ``prompt_lengths`` without ``phrase_sets``, or no phrases at all; ``closed_set``'s
+    (the set or sets, the index, then ``prompt_lengths``' own); a held ``PhraseTrie`` without ``phrase_node``.  Then NotImplementedError,
+    naming the reason, for a non-causal decoder and for sparse nano-mini blocks; then ValueError for the largest p_b + longest phrase of
+    b's set + 1 past the decode ``window`` (the text of every other call) and for ``images_per_pass`` < 1."""
     if phrase_sets is None and phrase_set_index is None and prompt_lengths is not None:
         raise ValueError('score_phrases(prompt_lengths=...) needs phrase_sets: one phrase list for all images is '
                          'phrase_sets=[phrases], phrase_set_index=[0] * B')
-    sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
-    if isinstance(phrase_sets, torch.Tensor):
-        phrase_sets = phrase_sets.detach().cpu().tolist()
-    tries = tuple(phrase_trie(one, eos, vocab, 1 << 30) for one in phrase_sets)
-    plen = None if prompt_lengths is None else _prompt_lengths(prompt_lengths, B, P)
-    rows = np.full(B, int(P), dtype=np.int64) if plen is None else plen.astype(np.int64)
-    total = int((rows + sets.longest + 1).max()) if B else int(P)
-    _check_score_rest(total, window, causal, sparse, images_per_pass)
-    return tries, sets.index, plen
+    if phrases is None and phrase_sets is None and phrase_set_index is None and not per_image:
+        raise ValueError('score_phrases needs phrases or phrase_sets')
+    one = closed_set(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab, B, P, tries=True, per_image=per_image)
+    if not one.per_image:
+        phrase_node_csr(one.trie)
+    rows = np.full(B, int(P), dtype=np.int64) if one.plen is None else one.plen.astype(np.int64)
+    total = int((rows + one.longest + 1).max()) if B else int(P)
+    if not causal:
+        raise NotImplementedError('score_phrases walks the trie on the KV cache; a non-causal decoder has none -- every new token changes the '
+                                  'state of the earlier ones --, so use rerank')
+    if sparse:
+        raise NotImplementedError('score_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, and '
+                                  'the static per-level history tables have not been run through its slot table (slot_pos); use rerank')
+    if total > window:
+        raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
+    if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
+        raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
+    return one
+
+
+def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
+                            images_per_pass=None) -> PhraseTrie:
+    """``plan_phrase_scores`` of ``phrases``, one set for all images, with its refusals in its order -> the trie"""
+    return plan_phrase_scores(phrases, None, None, None, eos, vocab, 1, P, window, causal, sparse, images_per_pass).trie
+
+
+def check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int,
+                                causal: bool = True, sparse: bool = False, images_per_pass=None):
+    """``plan_phrase_scores`` of ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths``, with its refusals in its
+    order -> (the S sets' ``PhraseTrie``, index int32 [B], plen int32 [B] or None)"""
+    one = plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab, B, P, window, causal, sparse, images_per_pass,
+                             per_image=True)
+    return one.tries, one.index, one.plen
 
 
 class PhraseBeams(NamedTuple):
@@ -391,73 +433,42 @@ class PhraseBeams(NamedTuple):
     exhaustive: bool                    # num_beams >= the widest trie level: nothing was pruned, the result is the exact top N of the set
 
 
-def trie_widest_level(trie: PhraseTrie) -> int:
-    """the largest number of nodes at one depth of the trie (the root's level counts: at least 1)"""
-    widest, level = 1, [0]
-    while level:
-        widest = max(widest, len(level))
-        level = [int(c) for nd in level for c in trie.children(nd)[1]]
-    return widest
+trie_widest_level = widest_level        # the largest number of nodes at one depth of a trie (the root's level counts: at least 1)
 
 
-def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_beams=4, num_return_sequences=1, length_penalty=0.0,
-                             poll_every=8, causal: bool = True, sparse: bool = False, phrase_sets=None, phrase_set_index=None,
-                             prompt_lengths=None, B: Optional[int] = None):
-    """The refusals of ``search_phrases``, all before anything runs (host only) -> (trie, W, N).  ValueError, in this order: everything
-    ``phrase_trie`` refuses about the set (or a ``PhraseTrie`` built for another EOS / vocabulary); ``num_beams`` outside
-    1 .. MAX_CAPTION_BEAMS; ``num_return_sequences`` outside 1 .. min(num_beams, distinct phrases); a non-finite ``length_penalty``;
-    prompt + longest phrase + 1 past the decode ``window`` (the text of every other call); a negative ``poll_every``.
-    NotImplementedError, naming the reason: a non-causal decoder, sparse nano-mini blocks.
-    With ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths`` (``B``: the images) -> (``PhraseSets``, W, N, plen int32
-    [B] or None): ``check_phrase_sets`` first, the same checks with N held against the smallest set in use and the window against the
-    longest prompt + the longest phrase in use + 1, and ``prompt_lengths``' own refusals (``check_ragged_caption_args``' texts) behind
-    ``num_return_sequences``'.  ``prompt_lengths`` with ``phrases=`` is refused (ValueError): the forced column is ``phrase_sets``' rule."""
-    if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
-        if phrase_sets is None and phrase_set_index is None:
+def plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int, num_beams=4,
+                       num_return_sequences=1, length_penalty=0.0, poll_every=8, causal: bool = True, sparse: bool = False):
+    """The refusals of ``search_phrases`` on ``prompt_ids`` [B, P], all before anything runs (host only) -> (the call's ``ClosedSet``, W,
+    N).  ValueError, in this order: ``prompt_lengths`` without ``phrase_sets`` (the forced column is ``phrase_sets``' rule), or no phrases
+    at all; ``closed_set``'s about the set or sets and the index; ``num_beams`` outside 1 .. MAX_CAPTION_BEAMS; ``num_return_sequences``
+    outside 1 .. min(num_beams, distinct phrases -- of the smallest set in use); a non-finite ``length_penalty``; ``prompt_lengths``' own
+    refusals (``check_ragged_caption_args``' texts), which stand behind those of N and the penalty; the longest prompt + the longest phrase in
+    use + 1 past the decode ``window`` (the text of every other call); a negative ``poll_every``.  NotImplementedError, naming the
+    reason: a non-causal decoder, sparse nano-mini blocks."""
+    if phrase_sets is None and phrase_set_index is None:
+        if prompt_lengths is not None:
             raise ValueError('search_phrases(prompt_lengths=...) needs phrase_sets: one answer list for all images is '
                              'phrase_sets=[answers], phrase_set_index=[0] * B')
-        assert B is not None
-        sets = check_phrase_sets(phrases, phrase_sets, phrase_set_index, B, eos, vocab)
-        W, N = _check_search_beams(num_beams, num_return_sequences, sets.smallest, length_penalty)
-        plen = None if prompt_lengths is None else _prompt_lengths(prompt_lengths, B, P)
-        total = (int(P) if plen is None else int(plen.max())) + int(sets.longest.max()) + 1
-        _check_search_rest(total, window, poll_every, causal, sparse)
-        return sets, W, N, plen
-    if phrases is None:
-        raise ValueError('search_phrases needs phrases or phrase_sets')
-    if isinstance(phrases, PhraseTrie):
-        trie = phrases
-        if eos is None or not 0 <= int(eos) < vocab or trie.edges < 1 or int(trie.child_tok.min()) < 0 or int(trie.child_tok.max()) >= vocab \
-                or bool((trie.child_tok == int(eos)).any()):
-            raise ValueError(f'a PhraseTrie built for another call: eos_token_id = {eos}, vocabulary {vocab}')
-    else:
-        trie = phrase_trie(phrases, eos, vocab, 1 << 30)
-    W, N = _check_search_beams(num_beams, num_return_sequences, int((trie.term >= 0).sum()), length_penalty)
-    _check_search_rest(int(P) + trie.longest + 1, window, poll_every, causal, sparse)
-    return trie, W, N
-
-
-def _check_search_beams(num_beams, num_return_sequences, distinct: int, length_penalty):
-    """``check_phrase_search_args``' refusals of W, N and the penalty -> (W, N); ``distinct``: the distinct phrases (of the smallest set)"""
+        if phrases is None:
+            raise ValueError('search_phrases needs phrases or phrase_sets')
+    one = closed_set(phrases, phrase_sets, phrase_set_index, None, eos, vocab, B, P)
     if isinstance(num_beams, bool) or int(num_beams) != num_beams or not 1 <= int(num_beams) <= MAX_CAPTION_BEAMS:
         raise ValueError(f'num_beams = {num_beams!r}: a whole number from 1 to {MAX_CAPTION_BEAMS} (the trie beam kernels keep at most '
                          f'{MAX_CAPTION_BEAMS} rows per image)')
     W = int(num_beams)
     N = num_return_sequences
-    if isinstance(N, bool) or int(N) != N or not 1 <= int(N) <= min(W, distinct):
-        raise ValueError(f'num_return_sequences = {N!r} with num_beams = {W} and {distinct} distinct phrases: from 1 to '
-                         f'{min(W, distinct)} phrases per image')
+    if isinstance(N, bool) or int(N) != N or not 1 <= int(N) <= min(W, one.distinct):
+        raise ValueError(f'num_return_sequences = {N!r} with num_beams = {W} and {one.distinct} distinct phrases: from 1 to '
+                         f'{min(W, one.distinct)} phrases per image')
     try:
         finite = bool(np.isfinite(float(length_penalty)))
     except (TypeError, ValueError):
         finite = False
     if not finite:
         raise ValueError(f'length_penalty = {length_penalty!r}: a finite number is needed')
-    return W, int(N)
-
-
-def _check_search_rest(total: int, window: int, poll_every, causal: bool, sparse: bool):
-    """``check_phrase_search_args``' refusals behind the penalty: the window, ``poll_every``, the decoder"""
+    if prompt_lengths is not None:
+        one = one._replace(plen=_prompt_lengths(prompt_lengths, B, P))
+    total = (int(P) if one.plen is None else int(one.plen.max())) + int(one.longest.max()) + 1
     if total > window:
         raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
     if isinstance(poll_every, bool) or int(poll_every) != poll_every or int(poll_every) < 0:
@@ -468,6 +479,18 @@ def _check_search_rest(total: int, window: int, poll_every, causal: bool, sparse
     if sparse:
         raise NotImplementedError('search_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, '
                                   'and the trie beam step has not been run through its slot table (slot_pos); use rerank')
+    return one, W, int(N)
+
+
+def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_beams=4, num_return_sequences=1, length_penalty=0.0,
+                             poll_every=8, causal: bool = True, sparse: bool = False, phrase_sets=None, phrase_set_index=None,
+                             prompt_lengths=None, B: Optional[int] = None):
+    """``plan_phrase_search`` under the name and with the results it had before ``ClosedSet``: (trie, W, N) of a call with ``phrases``,
+    (``PhraseSets``, W, N, plen int32 [B] or None) of one with ``phrase_sets`` / ``phrase_set_index`` / ``prompt_lengths`` (``B``: the
+    images).  New code calls ``plan_phrase_search``, which returns one shape."""
+    one, W, N = plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab, 1 if B is None else B, P, window,
+                                   num_beams, num_return_sequences, length_penalty, poll_every, causal, sparse)
+    return (one.sets, W, N, one.plen) if one.per_image else (one.trie, W, N)
 
 
 def check_caption_args(N: int, sampling: Optional[Sampling], eos, pad, poll_every: int, max_new_tokens: int, repetition_penalty: float = 1.0,

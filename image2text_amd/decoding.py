@@ -32,12 +32,13 @@ import torch
 
 from . import ops
 from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
-                           PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, GeneratedCaptions, PhraseBeams, PhraseScores, Processors, Sampling,
-                           PhraseSets, PhraseSetScores, cache_plan, caption_graph_key, caption_processors, check_beam_caption_args, check_caption_args,
-                           check_phrase_caption_args, check_phrase_score_args, check_phrase_search_args, check_phrase_set_caption_args,
-                           check_phrase_set_score_args,
-                           check_phrase_sets, check_ragged_caption_args, decode_window, phrase_beam_sets_graph_key, plan_captions, prefill_plan,
-                           takes_long_cache, text_window, trie_widest_level)
+                           PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, ClosedSet, GeneratedCaptions, PhraseBeams, PhraseScores,
+                           Processors, Sampling, PhraseSets, PhraseSetScores, cache_plan, caption_graph_key, caption_processors,
+                           check_beam_caption_args, check_caption_args, check_phrase_caption_args, check_phrase_score_args,
+                           check_phrase_search_args, check_phrase_set_caption_args, check_phrase_set_score_args, check_phrase_sets,
+                           check_ragged_caption_args, closed_set, decode_window, held_phrase_trie, one_closed_set, per_image_closed_set,
+                           phrase_beam_sets_graph_key, plan_captions, plan_phrase_scores, plan_phrase_search, prefill_plan, takes_long_cache,
+                           text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
                             beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
                             phrase_scores_host, phrase_set_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
@@ -1151,19 +1152,6 @@ class TrieScoreDecoder(BeamDecoder):
         ops.rows_lse(st.logits, dc.Vp, st.lse, R, V)
         return dict(logits=st.logits, ld=dc.Vp)
 
-    def _level_step(self, st, tables, t: int, eos: int, logprob):
-        z = self._level_lse(st)
-        ops.trie_level_expand(tables, st.lse, st.path[t & 1], st.path[(t + 1) & 1], st.ids, st.ids_ld, st.counters[1:2], logprob, eos,
-                              st.images, st.W, self.eng.dec.V, **z)
-        ops.advance(st.counters, 1)
-
-    def _sets_step(self, st, tables, state, k: int, eos: int, logprob):
-        """walk step k of ``score_sets``: _level_step with every image at its own level (``state``: ops.trie_set_state)"""
-        z = self._level_lse(st)
-        ops.trie_level_expand_sets(tables, state, st.lse, st.path[k & 1], st.path[(k + 1) & 1], st.ids, st.ids_ld, logprob, eos, st.W,
-                                   self.eng.dec.V, **z)
-        ops.advance(st.counters, 1)
-
     def _score_state_for(self, B: int, W: int, total: int, images_per_pass: Optional[int]):
         """-> (the decoder's own state for groups of Bp images of W rows and ``total`` id columns, Bp).  The walk reads ``total`` cache
         slots however long the text window is, and W rows per image multiply every slot: a cache of that many slots (in whole 16s) --
@@ -1182,79 +1170,33 @@ class TrieScoreDecoder(BeamDecoder):
         assert total <= st.tmax
         return st, Bp
 
-    @torch.no_grad()
-    def score(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, images_per_pass: Optional[int] = None) -> PhraseScores:
-        """``phrase_scores_host`` for every image of the batch, on the device.  ``trie``: what ``check_phrase_score_args`` returned."""
-        eng = self.eng
-        dc = eng.dec
-        a = eng.prepare(False)
-        dev = a.device
-        prompt_ids = prompt_ids.to(dev)
-        B, P = prompt_ids.shape
-        K = int(trie.phrase_node.shape[0])
-        levels = trie_levels(trie)
-        W = levels.wmax
-        total = P + trie.longest + 1
-        st, Bp = self._score_state_for(B, W, total, images_per_pass)
+    def _level_walk(self, st, trie: PhraseTrie, levels, P: int, eos: int):
+        """-> walk(i, part) of a call on one set for all images: levels t = 0 .. longest on every image of the group at once, the
+        columns in which level t's history table is not the identity written on the device"""
+        dev, dc, Bp, W = st.arena.device, self.eng.dec, st.images, st.W
         # every level's tables, checked on the host and uploaded once per call
-        tables = [ops.trie_level_tables(*level_expand_tables(trie, levels, t), W, dc.V, K, dev) for t in range(trie.longest + 1)]
+        tables = [ops.trie_level_tables(*level_expand_tables(trie, levels, t), W, dc.V, int(trie.phrase_node.shape[0]), dev)
+                  for t in range(trie.longest + 1)]
         anc = [torch.from_numpy(lv.anc).to(dev) for lv in levels.levels]
         first = st.prefix + P - 1                               # the cache slot of the level-0 step (TrieLevels.history)
-        out = torch.zeros(B, K, dtype=F32, device=dev)
-        part = torch.zeros(Bp, (K + 3) // 4 * 4, dtype=F32, device=dev)
-        self.last_passes = 0
-        pre = self._encode_all(st, images, B)
-        for i in range(0, B, Bp):
-            n = min(Bp, B - i)
-            take = torch.arange(i, i + Bp, device=dev).clamp(max=B - 1)         # a short last group is filled with its last image
-            self._load_group(st, pre, take)
-            self._reset(st, prompt_ids[take].repeat_interleave(W, dim=0), P)
-            st.path[0].zero_()
-            part.zero_()
-            for _ in range(P - 1):                              # prompt tokens before the last: fill the cache only
-                self._step(st, False)
+
+        def walk(i, part):
             for t in range(trie.longest + 1):
-                if t >= 2:                                      # the columns in which level t's table is not the identity
+                if t >= 2:
                     st.hist.view(Bp, W, st.clen)[:, :, first + 1:first + t] = st.row_base + anc[t][None, :, 1:t]
-                self._level_step(st, tables[t], t, eos, part)
-            out[i:i + n] = part[:n, :K]
-            self.last_passes += 1
-        top = out.max(dim=1, keepdim=True).values
-        best = torch.where(out == top, torch.arange(K, device=dev)[None, :], torch.full((), K, device=dev)).min(dim=1).values
-        depth = np.zeros(trie.nodes, dtype=np.int32)
-        for t, lv in enumerate(levels.levels):
-            depth[lv.nodes] = t
-        lengths = torch.from_numpy((depth[trie.phrase_node] + 1).astype(np.int32)).to(dev)
-        return PhraseScores(out, best, lengths)
+                z = self._level_lse(st)
+                ops.trie_level_expand(tables[t], st.lse, st.path[t & 1], st.path[(t + 1) & 1], st.ids, st.ids_ld, st.counters[1:2], part, eos,
+                                      Bp, W, dc.V, **z)
+                ops.advance(st.counters, 1)
+        return walk
 
-
-    @torch.no_grad()
-    def score_sets(self, images, prompt_ids: torch.Tensor, tries, index, eos: int, plen=None,
-                   images_per_pass: Optional[int] = None) -> PhraseSetScores:
-        """``phrase_set_scores_host`` for every image of the batch, on the device.  ``tries``, ``index``, ``plen``: what
-        ``check_phrase_set_score_args`` returned.  ``score``'s structure: the encoder once, groups of ``images_per_pass``, eager launches.
-        All rows share the step counter: min p_b - 1 prefill steps, then one walk step per id column up to the group's largest p_b +
-        longest phrase; in each the host says where every image stands (``set_step_state``) and uploads that and the images' history
-        tables -- ``TrieLevels.history`` of the image's own level and prompt length, the identity for a forced or finished image."""
-        eng = self.eng
-        dc = eng.dec
-        a = eng.prepare(False)
-        dev = a.device
-        prompt_ids = prompt_ids.to(dev)
-        B, P = prompt_ids.shape
-        index = np.asarray(index, dtype=np.int64)
-        plen = np.full(B, P, dtype=np.int64) if plen is None else np.asarray(plen, dtype=np.int64)
-        tabs = set_level_tables(tries)
-        W, K = tabs.wmax, tabs.kmax
-        longest = np.array([tries[s].longest for s in index.tolist()], dtype=np.int64)
-        pmin, pmax = int(plen.min()), int(plen.max())
-        total = int((plen + longest + 1).max())
-        st, Bp = self._score_state_for(B, W, total, images_per_pass)
+    def _sets_walk(self, st, one: ClosedSet, tabs, plen, prompt_host, eos: int):
+        """-> walk(i, part) of a call with a set and a prompt length per image: one step per id column from the shortest
+        prompt up to the group's largest p_b + longest phrase; in each the host says where every image stands (``set_step_state``) and
+        uploads that and the images' history tables -- ``TrieLevels.history`` of the image's own level and prompt length, the identity
+        for a forced or finished image"""
+        dev, dc, Bp, W = st.arena.device, self.eng.dec, st.images, st.W
         tables = ops.trie_set_tables(tabs, W, dc.V, dev)        # checked on the host and uploaded once per call
-        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
-        keep = torch.arange(pmax, device=dev)[None, :] < torch.from_numpy(plen).to(dev)[:, None]
-        prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
-        prompt_host = prompt.cpu().numpy()
         identity = np.arange(Bp * W, dtype=np.int32).reshape(Bp, W, 1).repeat(st.clen, axis=2)
         histories = {}
 
@@ -1262,35 +1204,76 @@ class TrieScoreDecoder(BeamDecoder):
             if (s, t, first) not in histories:
                 histories[s, t, first] = tabs.levels[s].history(t, first, st.clen)
             return histories[s, t, first]
-        out = torch.full((B, K), float('-inf'), dtype=F32, device=dev)
+
+        def walk(i, part):
+            take = np.minimum(np.arange(i, i + Bp), len(plen) - 1)              # the group's images, as the caller fills a short last one
+            g_index, g_plen, g_prompt = one.index[take], plen[take], prompt_host[take]
+            for k, col in enumerate(range(int(plen.min()), int((g_plen + one.longest[take]).max()) + 1)):
+                state = set_step_state(tabs, g_index, g_plen, g_prompt, col)
+                hist = identity.copy()
+                for b in np.flatnonzero(state[:, 0] >= 2).tolist():              # below level 2 a table is the identity
+                    h = history(int(g_index[b]), int(state[b, 0]), st.prefix + int(g_plen[b]) - 1)
+                    hist[b, :h.shape[0]] = b * W + h
+                st.hist.copy_(torch.from_numpy(hist).view(Bp * W, st.clen))
+                z = self._level_lse(st)
+                ops.trie_level_expand_sets(tables, ops.trie_set_state(tables, state, W, dc.V, st.ids_ld, dev), st.lse, st.path[k & 1],
+                                           st.path[(k + 1) & 1], st.ids, st.ids_ld, part, eos, W, dc.V, **z)
+                ops.advance(st.counters, 1)
+        return walk
+
+    @torch.no_grad()
+    def run(self, images, prompt_ids: torch.Tensor, one: ClosedSet, eos: int, images_per_pass: Optional[int] = None):
+        """``phrase_scores_host`` -- ``one.per_image``: ``phrase_set_scores_host`` -- for every image of the batch, on the
+        device -> ``PhraseScores`` / ``PhraseSetScores``.  ``one``: what ``plan_phrase_scores`` returned.  The encoder once, then groups
+        of ``images_per_pass`` images; all rows share the step counter: min p_b - 1 prefill steps, then the form's walk.  What the two
+        forms do not share is the walk, what a column no phrase writes holds (0 / -inf) and the prompt columns at or past p_b, which
+        only the per-image form has and drops here: nothing downstream sees what the caller left in them."""
+        dev = self.eng.prepare(False).device
+        prompt = prompt_ids.to(dev)
+        B, P = prompt.shape
+        per = one.per_image
+        plen = np.full(B, P, dtype=np.int32) if one.plen is None else np.asarray(one.plen, dtype=np.int32)
+        if per:
+            tabs = set_level_tables(one.tries)
+            W, K, lengths, fill = tabs.wmax, tabs.kmax, tabs.lengths, float('-inf')
+        else:
+            trie, = one.tries
+            levels = trie_levels(trie)
+            depth = np.zeros(trie.nodes, dtype=np.int32)
+            for t, lv in enumerate(levels.levels):
+                depth[lv.nodes] = t
+            W, K, lengths, fill = levels.wmax, int(trie.phrase_node.shape[0]), (depth[trie.phrase_node] + 1).astype(np.int32), 0.0
+        pmin, pmax = int(plen.min()), int(plen.max())
+        st, Bp = self._score_state_for(B, W, int((plen + one.longest + 1).max()), images_per_pass)
+        if per:
+            keep = torch.arange(pmax, device=dev)[None, :] < torch.from_numpy(plen).to(dev)[:, None]
+            prompt = torch.where(keep, prompt[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
+            walk = self._sets_walk(st, one, tabs, plen, prompt.cpu().numpy(), eos)
+        else:
+            walk = self._level_walk(st, trie, levels, P, eos)
+        out = torch.full((B, K), fill, dtype=F32, device=dev)
         part = torch.zeros(Bp, (K + 3) // 4 * 4, dtype=F32, device=dev)
         self.last_passes = 0
         pre = self._encode_all(st, images, B)
         for i in range(0, B, Bp):
             n = min(Bp, B - i)
-            take_host = np.minimum(np.arange(i, i + Bp), B - 1)                 # a short last group is filled with its last image
-            take = torch.from_numpy(take_host).to(dev)
-            g_index, g_plen, g_prompt = index[take_host], plen[take_host], prompt_host[take_host]
+            take = torch.arange(i, i + Bp, device=dev).clamp(max=B - 1)         # a short last group is filled with its last image
             self._load_group(st, pre, take)
             self._reset(st, prompt[take].repeat_interleave(W, dim=0), pmax)
             st.path[0].zero_()
-            part.fill_(float('-inf'))
+            part.fill_(fill)
             for _ in range(pmin - 1):                           # prompt tokens every image has before its last: fill the cache only
                 self._step(st, False)
-            for k, col in enumerate(range(pmin, int((g_plen + longest[take_host]).max()) + 1)):
-                state = set_step_state(tabs, g_index, g_plen, g_prompt, col)
-                hist = identity.copy()
-                for b in np.flatnonzero(state[:, 0] >= 2).tolist():              # below level 2 a table is the identity
-                    s = int(g_index[b])
-                    h = history(s, int(state[b, 0]), st.prefix + int(g_plen[b]) - 1)
-                    hist[b, :h.shape[0]] = b * W + h
-                st.hist.copy_(torch.from_numpy(hist).view(Bp * W, st.clen))
-                self._sets_step(st, tables, ops.trie_set_state(tables, state, W, dc.V, st.ids_ld, dev), k, eos, part)
+            walk(i, part)
             out[i:i + n] = part[:n, :K]
             self.last_passes += 1
         top = out.max(dim=1, keepdim=True).values
         best = torch.where(out == top, torch.arange(K, device=dev)[None, :], torch.full((), K, device=dev)).min(dim=1).values
-        return PhraseSetScores(out, best, torch.from_numpy(tabs.lengths).to(dev))
+        return (PhraseSetScores if per else PhraseScores)(out, best, torch.from_numpy(lengths).to(dev))
+
+    def score(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, images_per_pass: Optional[int] = None) -> PhraseScores:
+        """``run`` on one checked trie for all images"""
+        return self.run(images, prompt_ids, one_closed_set(trie, prompt_ids.shape[0]), eos, images_per_pass)
 
 
 class PhraseBeamDecoder(BeamDecoder):
@@ -1318,106 +1301,82 @@ class PhraseBeamDecoder(BeamDecoder):
         st.set_node_init = st.set_plen = st.set_longest = None      # phrase_sets: int32 [B, W] / [B] / [B], made at the first such call
         return st
 
-    def _phrase_beam_step(self, st, P: int, eos: int, longest: int, length_penalty: float):
+    def _phrase_beam_step(self, st, P: int, eos: int, longest: int, length_penalty: float, per_image: bool):
+        """``per_image``: P is the longest prompt, and every image's prompt length and longest phrase are read from
+        st.set_plen / st.set_longest in place of P and ``longest``"""
         dc = self.eng.dec
-        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
         off, tok, nxt, term = st.trie
         self._logits_head(st)
         ops.trie_beam_candidates(st.logits, dc.Vp, st.node, st.path, off, tok, term, eos, st.ctrl, st.cand_tok, st.cand_lp, st.fin_total,
                                  st.B, st.W, dc.V)
-        ops.trie_beam_select(st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist, st.pool_phrase,
-                             st.pool_sum, st.pool_score, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl, st.images, st.W, P,
-                             longest, length_penalty)
-        ops.beam_advance(st.counters, st.ctrl)
-
-    def _phrase_beam_sets_step(self, st, pmax: int, eos: int, length_penalty: float):
-        """_phrase_beam_step with every image's prompt length and longest phrase read from st.set_plen / st.set_longest"""
-        dc = self.eng.dec
-        pos_ptr, len_ptr = st.counters[0:1], st.counters[1:2]
-        off, tok, nxt, term = st.trie
-        self._logits_head(st)
-        ops.trie_beam_candidates(st.logits, dc.Vp, st.node, st.path, off, tok, term, eos, st.ctrl, st.cand_tok, st.cand_lp, st.fin_total,
-                                 st.B, st.W, dc.V)
-        ops.trie_beam_select_sets(st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist,
-                                  st.pool_phrase, st.pool_sum, st.pool_score, st.pool_len, st.pool_n, st.closed, pos_ptr, len_ptr, st.ctrl,
-                                  st.images, st.W, pmax, st.set_plen, st.set_longest, length_penalty)
+        shared = (st.cand_tok, st.cand_lp, st.fin_total, st.node, st.path, tok, nxt, term, eos, st.ids, st.hist, st.pool_phrase, st.pool_sum,
+                  st.pool_score, st.pool_len, st.pool_n, st.closed, st.counters[0:1], st.counters[1:2], st.ctrl, st.images, st.W, P)
+        if per_image:
+            ops.trie_beam_select_sets(*shared, st.set_plen, st.set_longest, length_penalty)
+        else:
+            ops.trie_beam_select(*shared, longest, length_penalty)
         ops.beam_advance(st.counters, st.ctrl)
 
     @torch.no_grad()
-    def search_sets(self, images, prompt_ids: torch.Tensor, sets: PhraseSets, eos: int, W: int, N: int, length_penalty: float = 0.0,
-                    poll_every: int = 8, use_graph: bool = True, each=None, plen=None) -> PhraseBeams:
-        """``search`` with a phrase set and (``plen`` int32 [B], or None) a prompt length per image: ``sets``, ``W``, ``N``,
-        ``plen``: what ``check_phrase_search_args`` returned.  Row 0 of image b starts at its set's root; Pmin - 1 prefill steps, then
-        Pmax - Pmin + max(longest) + 1 full steps in which an image whose prompt reaches past the column is held still by
-        i2t_trie_beam_select_sets.  The start nodes, prompt lengths and longest phrases are device tables filled per call: the graph
-        key is ('phrase_beam_sets', Pmax, W, eos, penalty)."""
+    def run(self, images, prompt_ids: torch.Tensor, one: ClosedSet, eos: int, W: int, N: int, length_penalty: float = 0.0,
+            poll_every: int = 8, use_graph: bool = True, each=None) -> PhraseBeams:
+        """``phrase_beam_search_host`` for every image of the batch, on the device.  ``one``, ``W``, ``N``: what ``plan_phrase_search``
+        returned -- nothing is checked again here.  ``each(i)`` runs after full step i.  One set for all images: row 0 of every image
+        starts at the root, P - 1 prefill steps, longest + 1 full steps; P, eos, the longest phrase and the penalty are kernel
+        arguments, so a captured step holds them (W is the state's).  ``one.per_image``: row 0 of image b starts at its
+        set's root; Pmin - 1 prefill steps, then Pmax - Pmin + max(longest) + 1 full steps in which an image whose prompt reaches past
+        the column is held still by i2t_trie_beam_select_sets.  The start nodes, prompt lengths and longest phrases are then device
+        tables filled per call: the graph key is ('phrase_beam_sets', Pmax, W, eos, penalty)."""
         eng = self.eng
         dc = eng.dec
         a = eng.prepare(False)
         dev = a.device
-        prompt_ids = prompt_ids.to(dev)
+        prompt = prompt_ids = prompt_ids.to(dev)
         B, P = prompt_ids.shape
-        plen = np.full(B, P, dtype=np.int32) if plen is None else np.asarray(plen, dtype=np.int32)
-        pmin, pmax = int(plen.min()), int(plen.max())
-        longest, length_penalty = int(sets.longest.max()), float(length_penalty)
+        per = one.per_image
+        plen = np.full(B, P, dtype=np.int32) if one.plen is None else np.asarray(one.plen, dtype=np.int32)
+        pmin, pmax = (int(plen.min()), int(plen.max())) if per else (P, P)
+        longest, length_penalty = int(one.longest.max()), float(length_penalty)
         R, total = B * W, pmax + longest + 1
         st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
                              lambda st: st.W == W)
-        self._upload_trie(st, sets.forest, ('phrase_beam', 'phrase_beam_sets'))
-        if st.set_node_init is None:        # persistent: the captured steps bake the two tables' pointers
-            i32 = dict(dtype=torch.int32, device=dev)
-            st.set_node_init, st.set_plen, st.set_longest = torch.full((B, W), -1, **i32), torch.ones(B, **i32), torch.ones(B, **i32)
-        st.set_node_init[:, 0] = torch.from_numpy(sets.roots).to(dev)
-        st.set_plen.copy_(torch.from_numpy(plen))
-        st.set_longest.copy_(torch.from_numpy(sets.longest))
+        self._upload_trie(st, one.trie, ('phrase_beam', 'phrase_beam_sets'))
+        node_init = st.node_init
+        if per:
+            if st.set_node_init is None:    # persistent: the captured steps bake the two tables' pointers
+                i32 = dict(dtype=torch.int32, device=dev)
+                st.set_node_init, st.set_plen, st.set_longest = torch.full((B, W), -1, **i32), torch.ones(B, **i32), torch.ones(B, **i32)
+            node_init = st.set_node_init
+            node_init[:, 0] = torch.from_numpy(one.roots).to(dev)
+            st.set_plen.copy_(torch.from_numpy(plen))
+            st.set_longest.copy_(torch.from_numpy(one.longest))
         self._prepare_inputs(st, images, B, W)
-        # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
-        keep = torch.arange(pmax, device=dev)[None, :] < st.set_plen[:, None]
-        prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
+        if per:                             # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
+            keep = torch.arange(pmax, device=dev)[None, :] < st.set_plen[:, None]
+            prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
         prompt_rows = prompt.repeat_interleave(W, dim=0)
 
         def reset():
             self._reset(st, prompt_rows, pmax)
-            st.node.copy_(st.set_node_init.view(-1))
+            st.node.copy_(node_init.view(-1))
             st.path.zero_()
             st.pool_phrase.fill_(-1)
             self._reset_pool(st)
-        key = phrase_beam_sets_graph_key(pmax, W, eos, length_penalty)
-        self.last_replays = self._replay(st, key, lambda: self._phrase_beam_sets_step(st, pmax, int(eos), length_penalty), reset, pmin - 1,
-                                         pmax - pmin + longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
+        key = phrase_beam_sets_graph_key(pmax, W, eos, length_penalty) if per else ('phrase_beam', P, W, int(eos), longest, length_penalty)
+        self.last_replays = self._replay(st, key, lambda: self._phrase_beam_step(st, pmax, int(eos), longest, length_penalty, per), reset,
+                                         pmin - 1, pmax - pmin + longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
         return PhraseBeams(st.pool_phrase[:, :N].long(), st.pool_sum[:, :N].clone(), st.pool_score[:, :N].clone(), st.pool_len[:, :N].clone(),
-                           W >= sets.widest)
+                           W >= one.widest_level())
 
-    @torch.no_grad()
     def search(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float = 0.0,
                poll_every: int = 8, use_graph: bool = True, each=None) -> PhraseBeams:
-        """``phrase_beam_search_host`` for every image of the batch, on the device.  ``trie``, ``W``, ``N``: what
-        ``check_phrase_search_args`` returned -- nothing is checked again here.  ``each(i)`` runs after full step i."""
-        eng = self.eng
-        dc = eng.dec
-        a = eng.prepare(False)
-        prompt_ids = prompt_ids.to(a.device)
-        B, P = prompt_ids.shape
-        longest, length_penalty = int(trie.longest), float(length_penalty)
-        R, total = B * W, P + longest + 1
-        st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
-                             lambda st: st.W == W)
-        self._upload_trie(st, trie, ('phrase_beam', 'phrase_beam_sets'))
-        self._prepare_inputs(st, images, B, W)
-        prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
+        """``run`` on one checked trie for all images"""
+        return self.run(images, prompt_ids, one_closed_set(trie, prompt_ids.shape[0]), eos, W, N, length_penalty, poll_every, use_graph, each)
 
-        def reset():
-            self._reset(st, prompt_rows, P)
-            st.node.copy_(st.node_init.view(-1))
-            st.path.zero_()
-            st.pool_phrase.fill_(-1)
-            self._reset_pool(st)
-        # P, eos, longest and the penalty are kernel arguments: a captured step holds them (W is the state's)
-        key = ('phrase_beam', P, W, int(eos), longest, length_penalty)
-        self.last_replays = self._replay(st, key, lambda: self._phrase_beam_step(st, P, int(eos), longest, length_penalty), reset, P - 1,
-                                         longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
-        return PhraseBeams(st.pool_phrase[:, :N].long(), st.pool_sum[:, :N].clone(), st.pool_score[:, :N].clone(), st.pool_len[:, :N].clone(),
-                           W >= trie_widest_level(trie))
+    def search_sets(self, images, prompt_ids: torch.Tensor, sets: PhraseSets, eos: int, W: int, N: int, length_penalty: float = 0.0,
+                    poll_every: int = 8, use_graph: bool = True, each=None, plen=None) -> PhraseBeams:
+        """``run`` on checked ``PhraseSets`` and (``plen`` int32 [B], or None) a prompt length per image"""
+        return self.run(images, prompt_ids, per_image_closed_set(sets, plen), eos, W, N, length_penalty, poll_every, use_graph, each)
 
 
 def caption_facts(model) -> CaptionFacts:

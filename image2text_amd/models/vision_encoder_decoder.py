@@ -414,20 +414,12 @@ class VisionEncoderDecoder(nn.Module):
         ``phrase_sets``, ``phrase_set_index`` or ``prompt_lengths`` without ``phrase_sets`` (one list for all images:
         ``phrase_sets=[phrases], phrase_set_index=[0] * B``), the largest p_b + longest phrase of b's set + 1 past the text window,
         ``images_per_pass`` < 1; the same NotImplementedErrors.  With the three at None the call is what it was, bit for bit."""
-        from ..decoding import TrieScoreDecoder, caption_facts, check_phrase_score_args, check_phrase_set_score_args
+        from ..decoding import TrieScoreDecoder, caption_facts, plan_phrase_scores
         facts = caption_facts(self)
-        if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
-            tries, index, plen = check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V,
-                                                             prompt_ids.shape[0], prompt_ids.shape[1], facts.cache_window, facts.causal,
-                                                             facts.sparse, images_per_pass)
-            return self._decoder('_trie_scorer', TrieScoreDecoder).score_sets(images, prompt_ids.to(next(self.parameters()).device), tries, index,
-                                                                              int(eos_token_id), plen, images_per_pass)
-        if phrases is None:
-            raise ValueError('score_phrases needs phrases or phrase_sets')
-        trie = check_phrase_score_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, facts.causal, facts.sparse,
-                                       images_per_pass)
-        return self._decoder('_trie_scorer', TrieScoreDecoder).score(images, prompt_ids.to(next(self.parameters()).device), trie,
-                                                                     int(eos_token_id), images_per_pass)
+        one = plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V, *prompt_ids.shape,
+                                 facts.cache_window, facts.causal, facts.sparse, images_per_pass)
+        return self._decoder('_trie_scorer', TrieScoreDecoder).run(images, prompt_ids.to(next(self.parameters()).device), one,
+                                                                   int(eos_token_id), images_per_pass)
 
     @torch.no_grad()
     def search_phrases(self, images, prompt_ids, phrases=None, eos_token_id=None, num_beams=4, num_return_sequences=1, length_penalty=0.0,
@@ -453,19 +445,12 @@ class VisionEncoderDecoder(nn.Module):
         then indexes into the image's own set; N is at most W and at most the distinct phrases of the smallest set in use;
         ``exhaustive`` says W >= the widest level of every set in use.  ``prompt_lengths`` needs ``phrase_sets`` (one list for all
         images: ``phrase_sets=[answers], phrase_set_index=[0] * B``); ``phrases`` together with ``phrase_sets`` is a ValueError."""
-        from ..decoding import PhraseBeamDecoder, caption_facts, check_phrase_search_args
+        from ..decoding import PhraseBeamDecoder, caption_facts, plan_phrase_search
         facts = caption_facts(self)
-        if phrase_sets is not None or phrase_set_index is not None or prompt_lengths is not None:
-            sets, W, N, plen = check_phrase_search_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, num_beams,
-                                                        num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse,
-                                                        phrase_sets, phrase_set_index, prompt_lengths, prompt_ids.shape[0])
-            return self._decoder('_phrase_searcher', PhraseBeamDecoder).search_sets(
-                images, prompt_ids.to(next(self.parameters()).device), sets, int(eos_token_id), W, N, float(length_penalty), int(poll_every),
-                plen=plen)
-        trie, W, N = check_phrase_search_args(phrases, eos_token_id, facts.V, prompt_ids.shape[1], facts.cache_window, num_beams,
-                                              num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse)
-        return self._decoder('_phrase_searcher', PhraseBeamDecoder).search(images, prompt_ids.to(next(self.parameters()).device), trie,
-                                                                           int(eos_token_id), W, N, float(length_penalty), int(poll_every))
+        one, W, N = plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V, *prompt_ids.shape,
+                                       facts.cache_window, num_beams, num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse)
+        return self._decoder('_phrase_searcher', PhraseBeamDecoder).run(images, prompt_ids.to(next(self.parameters()).device), one,
+                                                                        int(eos_token_id), W, N, float(length_penalty), int(poll_every))
 
     @torch.no_grad()
     def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:

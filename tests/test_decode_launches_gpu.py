@@ -16,7 +16,7 @@ import torch
 from conftest import GOLDEN
 from image2text_amd import ops
 from image2text_amd.decoding import (BeamDecoder, BeamSpec, CaptionBeamDecoder, CaptionDecoder, GreedyDecoder, PhraseBeamDecoder, Sampling,
-                                     phrase_trie)
+                                     check_phrase_sets, phrase_trie)
 from image2text_amd.synth import synthetic_batch, tiny_config
 from test_generate_captions_gpu import _ved
 
@@ -76,6 +76,7 @@ def calls(m, images, prompt):
     ngrams = tuple(int(n) for n in m.config.no_repeat_n_grams)
     cap = dict(eos=EOS, pad=V - 1, poll_every=0, use_graph=False)
     captions = lambda **kw: CaptionDecoder(m).generate_captions(images, prompt, kw.pop('new', NEW), **cap, **kw)
+    sets = dict(phrase_sets=[PHRASES, PHRASES[:2]], phrase_set_index=[0, 1])
     return [
         ('generate greedy', lambda: GreedyDecoder(m).generate(images, prompt, NEW, use_graph=False)),
         ('generate sampled', lambda: GreedyDecoder(m).generate(images, prompt, NEW, use_graph=False, sampling=SAMPLED)),
@@ -88,6 +89,14 @@ def calls(m, images, prompt):
         ('captions num_beams=2', lambda: CaptionBeamDecoder(m).generate_captions(images, prompt, NEW, 2, **cap)),
         ('score_phrases', lambda: m.score_phrases(images, prompt, PHRASES, EOS)),
         ('search_phrases W=2', lambda: PhraseBeamDecoder(m).search(images, prompt, trie, EOS, 2, 2, poll_every=0, use_graph=False)),
+        # a phrase set per image, with every prompt column in use and with prompts of 2 and 3 tokens
+        ('captions phrase_sets', lambda: captions(new=3, **sets)),
+        ('captions phrase_sets prompt_lengths', lambda: captions(new=3, prompt_lengths=[2, 3], **sets)),
+        ('score_phrases phrase_sets', lambda: m.score_phrases(images, prompt, None, EOS, **sets)),
+        ('score_phrases phrase_sets prompt_lengths', lambda: m.score_phrases(images, prompt, None, EOS, prompt_lengths=[2, 3], **sets)),
+        ('search_phrases phrase_sets W=2', lambda: PhraseBeamDecoder(m).search_sets(
+            images, prompt, check_phrase_sets(None, sets['phrase_sets'], sets['phrase_set_index'], B, EOS, V), EOS, 2, 1, poll_every=0,
+            use_graph=False, plen=[2, 3])),
     ]
 
 
