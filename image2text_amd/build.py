@@ -8,7 +8,7 @@ LIB = os.path.join(CSRC, 'libi2t_hip.so')
 SOURCES = ['abi.cpp', 'comm.cpp', 'gemm.hip', 'norm.hip', 'attention.hip', 'elementwise.hip', 'conv.hip', 'conv_mfma.hip', 'decode.hip', 'constrain.hip', 'sample.hip', 'beam.hip',
            'attention_g.hip', 'family.hip', 'grouped.hip', 'llama.hip', 'lora.hip', 'vit.hip', 'fp8.hip', 'preprocess.hip']
 # every header a source may include: _stale and _build both read this list, so a library is rebuilt whenever one of them changes
-HEADERS = [os.path.join(CSRC, h) for h in ('common.h', 'select_common.h', 'attention_common.h', 'attention_route.h', 'gemm_route.h')] + [
+HEADERS = [os.path.join(CSRC, h) for h in ('common.h', 'select_common.h', 'attention_common.h', 'attention_route.h', 'gemm_route.h', 'conv_route.h')] + [
     os.path.join(CSRC, '..', '..', 'include', 'i2t.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast']
 # per-file additions.  attention: keep MFMA accumulators in VGPRs -- the softmax rescales them every key tile, and the

@@ -25,6 +25,12 @@ void i2t_set_error(const char* fmt, ...);
             return I2T_EINVAL;                                   \
         }                                                        \
     } while (0)
+// a refusal that was decided elsewhere (conv_route.h: the text without the entry point's name; "" = accepted)
+inline int i2t_refused(const char* who, const char* why) {
+    if (!why[0]) return I2T_OK;
+    i2t_set_error("%s: %s", who, why);
+    return I2T_EINVAL;
+}
 #define I2T_CHECK_LAUNCH(name)                                                       \
     do {                                                                             \
         hipError_t e_ = hipGetLastError();                                           \

@@ -11,10 +11,11 @@
 //   backward-weight: a thread owns a (cin, ky, kx) tap and all COUT accumulators, the dY values of a pixel are
 //                    wave-uniform (scalar loads), one atomic per weight per workgroup at the end.
 #include "common.h"
+#include "conv_route.h"
 
 namespace {
 
-constexpr int TILE = 32;
+using namespace i2t;              // conv_route.h: TILE -- the number the routes read too
 constexpr int CI_CHUNK = 4;
 constexpr int KMAX = 8;
 
@@ -181,100 +182,74 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(const bf16_t* __re
     }
 }
 
-template <int COUT_T, bool IN_F32, bool IN_GELU, bool DGELU>
-int launch_direct(hipStream_t s, const void* x, const float* wr, const float* bias, bf16_t* y, const bf16_t* pre, int B,
-                  int Cin, int Cout, int H, int W, int k, int pad_before) {
-    const int groups = (Cout + COUT_T - 1) / COUT_T;
-    dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B * groups);
-    if (k == 6)
-        hipLaunchKernelGGL((conv_direct_kernel<COUT_T, 6, IN_F32, IN_GELU, DGELU>), grid, dim3(256), 0, s, x, wr, bias, y, pre,
-                           Cin, Cout, H, W, pad_before, groups);
-    else if (k == 4)
-        hipLaunchKernelGGL((conv_direct_kernel<COUT_T, 4, IN_F32, IN_GELU, DGELU>), grid, dim3(256), 0, s, x, wr, bias, y, pre,
-                           Cin, Cout, H, W, pad_before, groups);
-    else {
-        i2t_set_error("conv: kernel size %d unsupported (4 or 6)", k);
-        return I2T_EINVAL;
-    }
-    return I2T_OK;
-}
-
-template <bool IN_F32, bool IN_GELU, bool DGELU>
-int dispatch_cout(hipStream_t s, const void* x, const float* wr, const float* bias, bf16_t* y, const bf16_t* pre, int B,
-                  int Cin, int Cout, int H, int W, int k, int pad_before) {
-    if (Cout <= 4) return launch_direct<4, IN_F32, IN_GELU, DGELU>(s, x, wr, bias, y, pre, B, Cin, Cout, H, W, k, pad_before);
-    if (Cout <= 8) return launch_direct<8, IN_F32, IN_GELU, DGELU>(s, x, wr, bias, y, pre, B, Cin, Cout, H, W, k, pad_before);
-    return launch_direct<16, IN_F32, IN_GELU, DGELU>(s, x, wr, bias, y, pre, B, Cin, Cout, H, W, k, pad_before);
-}
-
 }  // namespace
+
+// Host side.  Each entry point describes its call (i2t::ConvCall), runs conv_check, asks conv_route.h and launches what the route says;
+// a refused call has issued nothing.
+
+// repack the weights into the workspace, then the convolution (forward, or backward-data with the roles swapped) on them
+static void conv_direct_launch(hipStream_t s, const ConvCall& c, const ConvDirectRoute& r, const void* src, const float* w, float* w_ws,
+                               const float* bias, void* dst, const void* pre) {
+    hipLaunchKernelGGL(repack_weights_kernel, dim3(32), dim3(256), 0, s, w, w_ws, c.Cout, c.Cin, c.k, r.flip);
+    first_index<CONV_DIRECT_CANDIDATES>([&](auto I) {
+        constexpr ConvDirectTargs t = conv_direct_candidate(decltype(I)::value);
+        if constexpr (conv_direct_instantiated(t)) {
+            if (!same(t, r.t)) return false;
+            hipLaunchKernelGGL((conv_direct_kernel<t.COUT_T, t.K, t.IN_F32, t.IN_GELU, t.DGELU>), dim3(r.grid.x, r.grid.y, r.grid.z), dim3(r.block), 0, s, src,
+                               w_ws, bias, (bf16_t*)dst, (const bf16_t*)pre, r.cin, r.cout, c.H, c.W, r.pad_before, r.groups);
+            return true;
+        }
+        return false;
+    });
+}
 
 extern "C" int i2t_conv_fwd(void* stream, const void* x, int in_is_f32, int in_gelu, const float* w, const float* bias,
                             void* y, float* w_ws, int B, int Cin, int Cout, int H, int W, int k) {
-    I2T_REQUIRE(x && w && y && w_ws && B > 0 && Cin > 0 && Cout > 0, "i2t_conv_fwd: bad args");
-    I2T_REQUIRE(k == 4 || k == 6, "i2t_conv_fwd: kernel size %d unsupported (4 or 6)", k);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(repack_weights_kernel, dim3(32), dim3(256), 0, s, w, w_ws, Cout, Cin, k, 0);
-    const int pad = (k - 1) / 2;
-    int rc;
-    if (in_is_f32 && !in_gelu) rc = dispatch_cout<true, false, false>(s, x, w_ws, bias, (bf16_t*)y, nullptr, B, Cin, Cout, H, W, k, pad);
-    else if (!in_is_f32 && in_gelu) rc = dispatch_cout<false, true, false>(s, x, w_ws, bias, (bf16_t*)y, nullptr, B, Cin, Cout, H, W, k, pad);
-    else if (!in_is_f32 && !in_gelu) rc = dispatch_cout<false, false, false>(s, x, w_ws, bias, (bf16_t*)y, nullptr, B, Cin, Cout, H, W, k, pad);
-    else rc = dispatch_cout<true, true, false>(s, x, w_ws, bias, (bf16_t*)y, nullptr, B, Cin, Cout, H, W, k, pad);
-    if (rc != I2T_OK) return rc;
-    I2T_CHECK_LAUNCH("i2t_conv_fwd");
+    const char* who = "i2t_conv_fwd";
+    const ConvCall c{ConvOp::Fwd, in_is_f32 ? SRC_NCHW_F32 : SRC_NCHW_BF16, 0, in_gelu != 0, false, true, B, Cin, Cout, H, W, k, false};
+    if (int rc = i2t_refused(who, conv_check(c, x && w && y && w_ws).refused)) return rc;
+    const ConvDirectRoute r = conv_direct_route(c);
+    if (int rc = i2t_refused(who, r.refused)) return rc;
+    conv_direct_launch((hipStream_t)stream, c, r, x, w, w_ws, bias, y, nullptr);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }
 
 extern "C" int i2t_conv_bwd_data(void* stream, const void* dy, const float* w, const void* x_pre, int in_gelu, void* dx,
                                  float* w_ws, int B, int Cin, int Cout, int H, int W, int k) {
-    I2T_REQUIRE(dy && w && dx && w_ws && B > 0, "i2t_conv_bwd_data: bad args");
-    I2T_REQUIRE(!in_gelu || x_pre, "i2t_conv_bwd_data: in_gelu needs the stored pre-activation");
-    I2T_REQUIRE(k == 4 || k == 6, "i2t_conv_bwd_data: kernel size %d unsupported (4 or 6)", k);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(repack_weights_kernel, dim3(32), dim3(256), 0, s, w, w_ws, Cout, Cin, k, 1);
-    const int pad = k - 1 - (k - 1) / 2;   // mirrored padding
-    int rc;
-    // roles swap: the "input" is dY with Cout channels, the "output" is dX with Cin channels
-    if (in_gelu) rc = dispatch_cout<false, false, true>(s, dy, w_ws, nullptr, (bf16_t*)dx, (const bf16_t*)x_pre, B, Cout, Cin, H, W, k, pad);
-    else rc = dispatch_cout<false, false, false>(s, dy, w_ws, nullptr, (bf16_t*)dx, nullptr, B, Cout, Cin, H, W, k, pad);
-    if (rc != I2T_OK) return rc;
-    I2T_CHECK_LAUNCH("i2t_conv_bwd_data");
+    const char* who = "i2t_conv_bwd_data";
+    const ConvCall c{ConvOp::BwdData, 0, SRC_NCHW_BF16, in_gelu != 0, x_pre != nullptr, true, B, Cin, Cout, H, W, k, false};
+    if (int rc = i2t_refused(who, conv_check(c, dy && w && dx && w_ws).refused)) return rc;
+    const ConvDirectRoute r = conv_direct_route(c);
+    if (int rc = i2t_refused(who, r.refused)) return rc;
+    // the "input" is dY with Cout channels, the "output" is dX with Cin channels
+    conv_direct_launch((hipStream_t)stream, c, r, dy, w, w_ws, nullptr, dx, r.t.DGELU ? x_pre : nullptr);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }
 
-#define BWD_W_CASE(CO, KK)                                                                                              \
-    if (Cout == CO && k == KK) {                                                                                        \
-        if (in_is_f32 && !in_gelu)                                                                                      \
-            hipLaunchKernelGGL((conv_bwd_weight_kernel<CO, KK, true, false>), g1, dim3(256), 0, s, (const bf16_t*)dy, x, dw, \
-                               db, Cin, H, W, pad, bx, by, bz);                                                         \
-        else if (!in_is_f32 && in_gelu)                                                                                 \
-            hipLaunchKernelGGL((conv_bwd_weight_kernel<CO, KK, false, true>), g1, dim3(256), 0, s, (const bf16_t*)dy, x, dw, \
-                               db, Cin, H, W, pad, bx, by, bz);                                                         \
-        else                                                                                                            \
-            hipLaunchKernelGGL((conv_bwd_weight_kernel<CO, KK, false, false>), g1, dim3(256), 0, s, (const bf16_t*)dy, x, dw, \
-                               db, Cin, H, W, pad, bx, by, bz);                                                         \
-        launched = true;                                                                                                \
-    }
-
 extern "C" int i2t_conv_bwd_weight(void* stream, const void* dy, const void* x, int in_is_f32, int in_gelu, float* dw,
                                    float* db, int B, int Cin, int Cout, int H, int W, int k) {
-    I2T_REQUIRE(dy && x && dw && B > 0, "i2t_conv_bwd_weight: bad args");
-    I2T_REQUIRE(!(in_is_f32 && in_gelu), "i2t_conv_bwd_weight: f32+gelu input combination unsupported");
+    const char* who = "i2t_conv_bwd_weight";
+    const ConvCall c{ConvOp::BwdWeight, in_is_f32 ? SRC_NCHW_F32 : SRC_NCHW_BF16, SRC_NCHW_BF16, in_gelu != 0, false, false, B, Cin, Cout, H, W, k, false};
+    if (int rc = i2t_refused(who, conv_check(c, dy && x && dw).refused)) return rc;
+    const ConvDirectBwdWeightRoute r = conv_direct_bwd_weight_route(c, i2t_det());
+    if (int rc = i2t_refused(who, r.refused)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
-    const int pad = (k - 1) / 2;
-    bool launched = false;
-    // deterministic mode: the workgroups' atomics onto dw / db land in (image, tile row, tile column) order -- one launch each
-    const bool det = i2t_det();
-    const dim3 g1 = det ? dim3(1, 1, 1) : grid;
-    for (int bz = 0; bz < (det ? (int)grid.z : 1); ++bz)
-        for (int by = 0; by < (det ? (int)grid.y : 1); ++by)
-            for (int bx = 0; bx < (det ? (int)grid.x : 1); ++bx) {
-                BWD_W_CASE(4, 6) BWD_W_CASE(8, 6) BWD_W_CASE(16, 6) BWD_W_CASE(32, 6)
-                BWD_W_CASE(4, 4) BWD_W_CASE(8, 4) BWD_W_CASE(16, 4) BWD_W_CASE(32, 4)
-            }
-    I2T_REQUIRE(launched, "i2t_conv_bwd_weight: Cout=%d k=%d unsupported (Cout in {4,8,16,32}, k in {4,6})", Cout, k);
-    I2T_CHECK_LAUNCH("i2t_conv_bwd_weight");
+    first_index<CONV_DIRECT_BWD_WEIGHT_CANDIDATES>([&](auto I) {
+        constexpr ConvDirectBwdWeightTargs t = conv_direct_bwd_weight_candidate(decltype(I)::value);
+        if constexpr (conv_direct_bwd_weight_instantiated(t)) {
+            if (!same(t, r.t)) return false;
+            // (deterministic mode: the workgroups' atomics onto dw / db land in (image, tile row, tile column) order, one launch each)
+            for (int bz = 0; bz < r.serial.z; ++bz)
+                for (int by = 0; by < r.serial.y; ++by)
+                    for (int bx = 0; bx < r.serial.x; ++bx)
+                        hipLaunchKernelGGL((conv_bwd_weight_kernel<t.COUT, t.K, t.IN_F32, t.IN_GELU>), dim3(r.grid.x, r.grid.y, r.grid.z), dim3(r.block), 0, s,
+                                           (const bf16_t*)dy, x, dw, db, Cin, H, W, r.pad_before, bx, by, bz);
+            return true;
+        }
+        return false;
+    });
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }

@@ -17,26 +17,24 @@
 //       (ds_read_b64_tr_b16, any 4-row set); a workgroup sweeps a row of 14 tiles keeping dW in registers, then adds
 //       its partial with contiguous float atomics into a [co][tap][ci] scratch that a tiny kernel folds into dW.
 #include "common.h"
+#include "conv_route.h"
 #include <utility>
 
 namespace {
+
+using namespace i2t;              // conv_route.h: TS, KS, NTAP, pad8, SRC_* -- the numbers the routes read too
 
 template <int N, class F, int... Is>
 __device__ __forceinline__ void static_for_impl_c(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 template <int N, class F>
 __device__ __forceinline__ void static_for_c(F&& f) { static_for_impl_c<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
 
-constexpr int TS = 16;            // output tile edge
-constexpr int KS = 6;             // kernel size
 constexpr int PW = TS + KS - 1;   // 21: patch edge
-constexpr int NTAP = KS * KS;
 #ifdef I2T_CONV_NOGELU          // timing experiment (tools/build_variant.sh): the staging GELU left out -- WRONG results, prices its VALU share
 #define CONV_GELU(x) (x)
 #else
 #define CONV_GELU(x) gelu_tanh(x)
 #endif
-
-enum { SRC_NCHW_F32 = 0, SRC_NCHW_BF16 = 1, SRC_NHWC_BF16 = 2 };
 
 // wr[co][tap][ci_p] (bf16, zero padded) from w[Cout][Cin][6][6] (f32).
 //   flip = 0: forward            co = output channel of w, ci = input channel of w
@@ -570,8 +568,6 @@ __global__ void conv_fold_dw_kernel(const float* __restrict__ scratch, float* __
     }
 }
 
-int pad8(int c) { return c <= 8 ? 8 : (c <= 16 ? 16 : 32); }
-
 // dst[b][y][x][c] = src[b][c][y][x] (bf16): one workgroup per (64-pixel run of a row, b); coalesced both ways through LDS.
 // The projector's dX GEMM produces the last conv layer's gradient as flat NCHW patches; both backward kernels of that layer
 // are ~3x faster on channels-last input (16-byte staging instead of 2-byte scatter), so it is transposed once.
@@ -621,138 +617,87 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const bf16_t* __restr
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef CONV_NCHW_GRP
-#define CONV_NCHW_GRP 4
-#endif
-#define LAUNCH_CONV(CP_, NT_, SRC_, G_, D_, N_)                                                                                             \
-    hipLaunchKernelGGL((conv_mfma_kernel<CP_, NT_, SRC_, G_, D_, N_, (CP_ == 32 || (N_ && CP_ == 16) ? 8 : 4), ((N_ && CP_ >= 16) ? CONV_NCHW_GRP : 1)>), grid,         \
-                       dim3((CP_ == 32 || (N_ && CP_ == 16)) ? 512 : 256), 0, s, src,                                                  \
-                       (const bf16_t*)wr, bias, (bf16_t*)dst, (const bf16_t*)pre, Cin, Cout, H, W, pad_before, tiles_x)
+// Host side.  Each entry point describes its call (i2t::ConvCall), runs conv_check, asks conv_route.h and launches what the route says;
+// a refused call has issued nothing.  One launcher per kernel template: it walks the candidate template arguments and names the
+// instantiation the route asks for -- only members of the instantiated set are compiled.
 
-static int conv_mfma_dispatch(hipStream_t s, const void* src, int src_layout, int in_gelu, const void* wr, const float* bias,
-                              void* dst, int dst_nchw, const void* pre, int B, int Cin, int Cout, int H, int W,
-                              int pad_before) {
-    const int tiles_x = (W + TS - 1) / TS, tiles_y = (H + TS - 1) / TS;
-    dim3 grid(tiles_y, B);
-    const int cp = pad8(Cin), nt = Cout <= 16 ? 1 : 2;
-    const bool dg = pre != nullptr;
-    // the combinations the feature extractor uses (forward: f32 NCHW image | NHWC+GELU; backward-data: NCHW | NHWC dY)
-    if (src_layout == SRC_NCHW_F32 && cp == 8 && !in_gelu && !dg && !dst_nchw) { if (nt == 1) LAUNCH_CONV(8, 1, SRC_NCHW_F32, false, false, false); else LAUNCH_CONV(8, 2, SRC_NCHW_F32, false, false, false); }
-    else if (src_layout == SRC_NCHW_F32 && cp == 8 && !in_gelu && !dg && dst_nchw) { if (nt == 1) LAUNCH_CONV(8, 1, SRC_NCHW_F32, false, false, true); else LAUNCH_CONV(8, 2, SRC_NCHW_F32, false, false, true); }
-    else if (src_layout == SRC_NHWC_BF16 && in_gelu && !dg && !dst_nchw) {
-        if (cp == 8 && nt == 1) LAUNCH_CONV(8, 1, SRC_NHWC_BF16, true, false, false);
-        else if (cp == 8) LAUNCH_CONV(8, 2, SRC_NHWC_BF16, true, false, false);
-        else if (cp == 16 && nt == 1) LAUNCH_CONV(16, 1, SRC_NHWC_BF16, true, false, false);
-        else if (cp == 16) LAUNCH_CONV(16, 2, SRC_NHWC_BF16, true, false, false);
-        else if (nt == 1) LAUNCH_CONV(32, 1, SRC_NHWC_BF16, true, false, false);
-        else LAUNCH_CONV(32, 2, SRC_NHWC_BF16, true, false, false);
-    } else if (src_layout == SRC_NHWC_BF16 && in_gelu && !dg && dst_nchw) {
-        if (cp == 8 && nt == 1) LAUNCH_CONV(8, 1, SRC_NHWC_BF16, true, false, true);
-        else if (cp == 8) LAUNCH_CONV(8, 2, SRC_NHWC_BF16, true, false, true);
-        else if (cp == 16 && nt == 1) LAUNCH_CONV(16, 1, SRC_NHWC_BF16, true, false, true);
-        else if (cp == 16) LAUNCH_CONV(16, 2, SRC_NHWC_BF16, true, false, true);
-        else if (nt == 1) LAUNCH_CONV(32, 1, SRC_NHWC_BF16, true, false, true);
-        else LAUNCH_CONV(32, 2, SRC_NHWC_BF16, true, false, true);
-    } else if (dg && !in_gelu && !dst_nchw && (src_layout == SRC_NCHW_BF16 || src_layout == SRC_NHWC_BF16)) {
-        if (nt != 1) { i2t_set_error("conv6 bwd-data: Cin=%d > 16 unsupported", Cout); return I2T_EINVAL; }
-        if (src_layout == SRC_NCHW_BF16) {
-            if (cp == 8) LAUNCH_CONV(8, 1, SRC_NCHW_BF16, false, true, false);
-            else if (cp == 16) LAUNCH_CONV(16, 1, SRC_NCHW_BF16, false, true, false);
-            else LAUNCH_CONV(32, 1, SRC_NCHW_BF16, false, true, false);
-        } else {
-            if (cp == 8) LAUNCH_CONV(8, 1, SRC_NHWC_BF16, false, true, false);
-            else if (cp == 16) LAUNCH_CONV(16, 1, SRC_NHWC_BF16, false, true, false);
-            else LAUNCH_CONV(32, 1, SRC_NHWC_BF16, false, true, false);
+// repack the weights into the workspace, then the convolution (forward, or backward-data with the roles swapped) on them
+static void conv6_launch(hipStream_t s, const ConvCall& c, const Conv6Route& r, const void* src, const float* w, void* w_ws, const float* bias,
+                         void* dst, const void* pre) {
+    hipLaunchKernelGGL(conv_repack_kernel, dim3(64), dim3(256), 0, s, w, (bf16_t*)w_ws, c.Cout, c.Cin, r.rows_p, r.red_p, r.flip);
+    first_index<CONV6_CANDIDATES>([&](auto I) {
+        constexpr Conv6Targs t = conv6_candidate(decltype(I)::value);
+        if constexpr (conv6_instantiated(t)) {
+            if (!same(t, r.t)) return false;
+            hipLaunchKernelGGL((conv_mfma_kernel<t.CP, t.NT, t.SRC, t.IN_GELU, t.DGELU, t.DST_NCHW, t.NW, t.GRP>), dim3(r.grid.x, r.grid.y), dim3(r.block), 0, s,
+                               src, (const bf16_t*)w_ws, bias, (bf16_t*)dst, (const bf16_t*)pre, r.cin, r.cout, c.H, c.W, r.pad_before, r.tiles_x);
+            return true;
         }
-    } else {
-        i2t_set_error("conv6 mfma: unsupported layout combination (src=%d gelu=%d dgelu=%d nchw_out=%d)", src_layout, in_gelu, (int)dg, dst_nchw);
-        return I2T_EINVAL;
-    }
-    return I2T_OK;
+        return false;
+    });
 }
 
 extern "C" int i2t_nchw_to_nhwc_bf16(void* stream, const void* src, void* dst, int B, int C, int H, int W) {
-    I2T_REQUIRE(src && dst && B > 0 && C > 0 && C <= 32 && H > 0 && W > 0, "i2t_nchw_to_nhwc_bf16: bad args (C <= 32)");
-    if (C == 32 && W % 8 == 0 && ALIGNED16(src) && ALIGNED16(dst)) {
-        hipLaunchKernelGGL(nchw_to_nhwc32_kernel, dim3((W + 63) / 64, H, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src,
-                           (bf16_t*)dst, H, W);
-        I2T_CHECK_LAUNCH("i2t_nchw_to_nhwc_bf16");
-        return I2T_OK;
-    }
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((W + 63) / 64, H, B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src,
-                       (bf16_t*)dst, C, H, W);
-    I2T_CHECK_LAUNCH("i2t_nchw_to_nhwc_bf16");
+    const char* who = "i2t_nchw_to_nhwc_bf16";
+    const ConvCall c{ConvOp::Fwd, SRC_NCHW_BF16, 0, false, false, false, B, C, C, H, W, 0, ALIGNED16(src) && ALIGNED16(dst)};
+    if (int rc = i2t_refused(who, conv_check(c, src && dst).refused)) return rc;
+    const TransposeRoute r = nchw_to_nhwc_route(c);
+    if (int rc = i2t_refused(who, r.refused)) return rc;
+    const dim3 grid(r.grid.x, r.grid.y, r.grid.z);
+    if (r.c32) hipLaunchKernelGGL(nchw_to_nhwc32_kernel, grid, dim3(r.block), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst, H, W);
+    else hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(r.block), 0, (hipStream_t)stream, (const bf16_t*)src, (bf16_t*)dst, C, H, W);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }
 
 extern "C" int i2t_conv6_fwd(void* stream, const void* x, int x_layout, int in_gelu, const float* w, const float* bias,
                              void* y, int y_nchw, void* w_ws, int B, int Cin, int Cout, int H, int W) {
-    I2T_REQUIRE(x && w && y && w_ws && B > 0 && Cin > 0 && Cout > 0 && Cin <= 32 && Cout <= 32, "i2t_conv6_fwd: bad args");
-    I2T_REQUIRE(x_layout != SRC_NHWC_BF16 || Cin == pad8(Cin), "i2t_conv6_fwd: NHWC input needs 8/16/32 channels");
-    I2T_REQUIRE(y_nchw || Cout % 8 == 0, "i2t_conv6_fwd: NHWC output needs Cout %% 8 == 0");
-    hipStream_t s = (hipStream_t)stream;
-    const int cp = pad8(Cin), cop = Cout <= 16 ? 16 : 32;
-    hipLaunchKernelGGL(conv_repack_kernel, dim3(64), dim3(256), 0, s, w, (bf16_t*)w_ws, Cout, Cin, cop, cp, 0);
-    int rc = conv_mfma_dispatch(s, x, x_layout, in_gelu, w_ws, bias, y, y_nchw, nullptr, B, Cin, Cout, H, W, (KS - 1) / 2);
-    if (rc != I2T_OK) return rc;
-    I2T_CHECK_LAUNCH("i2t_conv6_fwd");
+    const char* who = "i2t_conv6_fwd";
+    const ConvCall c{ConvOp::Fwd, x_layout, 0, in_gelu != 0, false, y_nchw != 0, B, Cin, Cout, H, W, KS, false};
+    if (int rc = i2t_refused(who, conv_check(c, x && w && y && w_ws).refused)) return rc;
+    const Conv6Route r = conv6_route(c);
+    if (int rc = i2t_refused(who, r.refused)) return rc;
+    conv6_launch((hipStream_t)stream, c, r, x, w, w_ws, bias, y, nullptr);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }
 
 extern "C" int i2t_conv6_bwd_data(void* stream, const void* dy, int dy_layout, const float* w, const void* x_pre, void* dx,
                                   void* w_ws, int B, int Cin, int Cout, int H, int W) {
-    I2T_REQUIRE(dy && w && x_pre && dx && w_ws && B > 0 && Cin % 8 == 0 && Cin <= 16 && Cout <= 32, "i2t_conv6_bwd_data: bad args");
-    I2T_REQUIRE(dy_layout == SRC_NCHW_BF16 || (dy_layout == SRC_NHWC_BF16 && Cout == pad8(Cout)), "i2t_conv6_bwd_data: dy layout");
-    hipStream_t s = (hipStream_t)stream;
-    const int cp = pad8(Cout);                 // reduction channels = Cout of the forward conv
-    hipLaunchKernelGGL(conv_repack_kernel, dim3(64), dim3(256), 0, s, w, (bf16_t*)w_ws, Cout, Cin, 16, cp, 1);
-    // roles swapped: "Cin" of the kernel = Cout, "Cout" of the kernel = Cin; mirrored padding (3 before)
-    int rc = conv_mfma_dispatch(s, dy, dy_layout, 0, w_ws, nullptr, dx, 0, x_pre, B, Cout, Cin, H, W, KS - 1 - (KS - 1) / 2);
-    if (rc != I2T_OK) return rc;
-    I2T_CHECK_LAUNCH("i2t_conv6_bwd_data");
+    const char* who = "i2t_conv6_bwd_data";
+    const ConvCall c{ConvOp::BwdData, 0, dy_layout, false, x_pre != nullptr, false, B, Cin, Cout, H, W, KS, false};
+    if (int rc = i2t_refused(who, conv_check(c, dy && w && dx && w_ws).refused)) return rc;
+    const Conv6Route r = conv6_route(c);
+    if (int rc = i2t_refused(who, r.refused)) return rc;
+    conv6_launch((hipStream_t)stream, c, r, dy, w, w_ws, nullptr, dx, x_pre);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }
 
-#define LAUNCH_BW(CP_, COP_, DS_, AS_, G_)                                                                              \
-    for (int bz = 0; bz < (det ? B : 1); ++bz)                                                                         \
-        for (int by = 0; by < (det ? tiles_y : 1); ++by)                                                               \
-            hipLaunchKernelGGL((conv_mfma_bwd_weight_kernel<CP_, COP_, DS_, AS_, G_>), (det ? dim3(1, 1) : grid), dim3(256), 0, s, dy, x, \
-                               scratch, db, Cin, Cout, H, W, (KS - 1) / 2, tiles_x, by, bz)
-
 extern "C" int i2t_conv6_bwd_weight(void* stream, const void* dy, int dy_layout, const void* x, int x_layout, int in_gelu,
                                     float* dw, float* db, float* scratch, int B, int Cin, int Cout, int H, int W) {
-    I2T_REQUIRE(dy && x && dw && scratch && B > 0 && Cin <= 16 && Cout <= 32, "i2t_conv6_bwd_weight: bad args");
-    I2T_REQUIRE(dy_layout != SRC_NHWC_BF16 || Cout % 8 == 0, "i2t_conv6_bwd_weight: NHWC dy needs Cout %% 8 == 0");
+    const char* who = "i2t_conv6_bwd_weight";
+    const ConvCall c{ConvOp::BwdWeight, x_layout, dy_layout, in_gelu != 0, false, false, B, Cin, Cout, H, W, KS, false};
+    if (int rc = i2t_refused(who, conv_check(c, dy && x && dw && scratch).refused)) return rc;
+    const Conv6BwdWeightRoute r = conv6_bwd_weight_route(c, i2t_det());
+    if (int rc = i2t_refused(who, r.refused)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int cp = pad8(Cin), cop = Cout <= 16 ? 16 : 32;
-    hipError_t e = hipMemsetAsync(scratch, 0, sizeof(float) * (size_t)cop * NTAP * cp, s);
-    if (e != hipSuccess) { i2t_set_error("i2t_conv6_bwd_weight: memset: %s", hipGetErrorString(e)); return I2T_EHIP; }
-    const int tiles_x = (W + TS - 1) / TS, tiles_y = (H + TS - 1) / TS;
-    dim3 grid(tiles_y, B);
-    const bool det = i2t_det();      // deterministic mode: the scratch / db atomics land in (image, tile row) order, one launch each
-    bool ok = true;
-    if (x_layout == SRC_NCHW_F32 && !in_gelu && cp == 8) {
-        if (dy_layout == SRC_NHWC_BF16 && cop == 16) LAUNCH_BW(8, 16, SRC_NHWC_BF16, SRC_NCHW_F32, false);
-        else if (dy_layout == SRC_NHWC_BF16) LAUNCH_BW(8, 32, SRC_NHWC_BF16, SRC_NCHW_F32, false);
-        else if (cop == 16) LAUNCH_BW(8, 16, SRC_NCHW_BF16, SRC_NCHW_F32, false);
-        else LAUNCH_BW(8, 32, SRC_NCHW_BF16, SRC_NCHW_F32, false);
-    } else if (x_layout == SRC_NHWC_BF16 && in_gelu && Cin == cp) {
-        if (cp == 8) {
-            if (dy_layout == SRC_NHWC_BF16 && cop == 16) LAUNCH_BW(8, 16, SRC_NHWC_BF16, SRC_NHWC_BF16, true);
-            else if (dy_layout == SRC_NHWC_BF16) LAUNCH_BW(8, 32, SRC_NHWC_BF16, SRC_NHWC_BF16, true);
-            else if (cop == 16) LAUNCH_BW(8, 16, SRC_NCHW_BF16, SRC_NHWC_BF16, true);
-            else LAUNCH_BW(8, 32, SRC_NCHW_BF16, SRC_NHWC_BF16, true);
-        } else {
-            if (dy_layout == SRC_NHWC_BF16 && cop == 16) LAUNCH_BW(16, 16, SRC_NHWC_BF16, SRC_NHWC_BF16, true);
-            else if (dy_layout == SRC_NHWC_BF16) LAUNCH_BW(16, 32, SRC_NHWC_BF16, SRC_NHWC_BF16, true);
-            else if (cop == 16) LAUNCH_BW(16, 16, SRC_NCHW_BF16, SRC_NHWC_BF16, true);
-            else LAUNCH_BW(16, 32, SRC_NCHW_BF16, SRC_NHWC_BF16, true);
+    hipError_t e = hipMemsetAsync(scratch, 0, r.scratch_bytes, s);
+    if (e != hipSuccess) { i2t_set_error("%s: memset: %s", who, hipGetErrorString(e)); return I2T_EHIP; }
+    first_index<CONV6_BWD_WEIGHT_CANDIDATES>([&](auto I) {
+        constexpr Conv6BwdWeightTargs t = conv6_bwd_weight_candidate(decltype(I)::value);
+        if constexpr (conv6_bwd_weight_instantiated(t)) {
+            if (!same(t, r.t)) return false;
+            // (deterministic mode: the scratch / db atomics land in (image, tile row) order, one launch each)
+            for (int bz = 0; bz < r.serial.y; ++bz)
+                for (int by = 0; by < r.serial.x; ++by)
+                    hipLaunchKernelGGL((conv_mfma_bwd_weight_kernel<t.CP, t.COP, t.DY_SRC, t.ACT_SRC, t.ACT_GELU>), dim3(r.grid.x, r.grid.y), dim3(r.block), 0, s,
+                                       dy, x, scratch, db, Cin, Cout, H, W, r.pad_before, r.tiles_x, by, bz);
+            return true;
         }
-    } else {
-        ok = false;
-    }
-    I2T_REQUIRE(ok, "i2t_conv6_bwd_weight: unsupported layout combination (x_layout=%d gelu=%d Cin=%d)", x_layout, in_gelu, Cin);
-    hipLaunchKernelGGL(conv_fold_dw_kernel, dim3(32), dim3(256), 0, s, scratch, dw, Cout, Cin, cp);
-    I2T_CHECK_LAUNCH("i2t_conv6_bwd_weight");
+        return false;
+    });
+    hipLaunchKernelGGL(conv_fold_dw_kernel, dim3(32), dim3(256), 0, s, scratch, dw, Cout, Cin, r.t.CP);
+    I2T_CHECK_LAUNCH(who);
     return I2T_OK;
 }

@@ -376,8 +376,7 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
             chans = [ecfg.input.n_channels] + gates + [ecfg.n_channels]
             self.conv = [(f'{self.ep}feature_extractor.model.{2 * i}', chans[i], chans[i + 1]) for i in range(len(chans) - 1)]
             # MFMA (channels-last) convolutions when the kernel is 6x6 and every intermediate width is 8/16/32 channels
-            self.conv_mfma = (ecfg.feature_extractor_kernel_size[0] == 6 and all(c in (8, 16, 32) for c in chans[1:-1])
-                              and chans[0] <= 8 and chans[-1] <= 32 and all(c <= 16 for c in chans[:-1]))
+            self.conv_mfma = ops.conv_stack_takes_mfma(chans, ecfg.feature_extractor_kernel_size[0])
             # non-causal encoder: its output reads only the CLS rows, so the last block runs on those rows (block_fwd_cls);
             # I2T_FULL_LAST_BLOCK=1 keeps the full-row form (A/B runs)
             self.cls_only_last = ((not self.enc.causal) and self.enc.L >= 1 and os.environ.get('I2T_FULL_LAST_BLOCK') != '1'
@@ -445,7 +444,7 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
                 self.arena.skip_grad = self.vit_skip_grad()
             self._ws = torch.zeros(4, dtype=F32, device=dev)
             self._conv_ws_pool = {}
-            self._conv_scratch = torch.empty(32 * 36 * 16, dtype=F32, device=dev)
+            self._conv_scratch = torch.empty(ops.CONV6_SCRATCH_FLOATS, dtype=F32, device=dev)
             self._logits_cache.clear()
             self._moe_cache.clear()
             self._sub_cache.clear()
@@ -486,7 +485,8 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         key = torch.cuda.current_stream(self.arena.device).cuda_stream
         ws = self._conv_ws_pool.get(key)
         if ws is None:
-            n = max(32 * 36 * 32, max(self.arena.entries[f'{n}.weight'][1] for n, _, _ in self.conv))
+            # (fp32 elements: the generic path repacks a layer's weights as fp32, the MFMA path as bf16)
+            n = max(ops.CONV6_WS_ELEMS, max(self.arena.entries[f'{n}.weight'][1] for n, _, _ in self.conv))
             ws = self._conv_ws_pool[key] = torch.empty(n, dtype=F32, device=self.arena.device)
         return ws
 
@@ -882,7 +882,11 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
                          f'{self.ep}projector.bias' if a.G(f'{self.ep}projector.bias') is not None else None, dx_out=dflat)
         dy = dflat.view(B, self.conv[-1][2], ctx.Hh, ctx.Ww)
         dy_layout = ops.LAYOUT_NCHW_BF16
-        if self.conv_mfma and self.conv[-1][2] % 8 == 0:       # one coalesced transpose beats two 2-byte-scatter stagings
+        # one coalesced transpose beats two 2-byte-scatter stagings, where the kernels take the result: the weight gradient reads an NHWC
+        # dY of any multiple of 8 channels, the data gradient (a stack of two or more layers) only of 8 / 16 / 32 -- a deeper stack that
+        # ends in 24 channels keeps its dY NCHW (transposed, i2t_conv6_bwd_data refused it: "dy layout")
+        c_last = self.conv[-1][2]
+        if self.conv_mfma and c_last % 8 == 0 and (len(self.conv) == 1 or c_last in (8, 16, 32)):
             dyt = self._empty(B, ctx.Hh, ctx.Ww, self.conv[-1][2], dtype=BF16)
             ops.nchw_to_nhwc(dy, dyt, B, self.conv[-1][2], ctx.Hh, ctx.Ww)
             dy, dy_layout = dyt, ops.LAYOUT_NHWC_BF16

@@ -306,6 +306,15 @@ def attention_bwd_takes_q_seq(Tq: int, Tk: int, drop) -> bool:
     return 64 <= Tq <= 288 and Tk <= 288 and (drop is None or Tk % 4 == 0)
 
 
+def conv_stack_takes_mfma(chans, k: int) -> bool:
+    """whether the engine runs a ConvMLP stack of these channel widths (image, gates ..., output) on the 6x6 MFMA entry points: the
+    kernel is 6x6, every intermediate width is 8 / 16 / 32 channels, the image has at most 8, the output at most 32 and every layer's
+    input at most 16.  csrc/conv_route.h accepts every call encode / encode_backward then make (tests/test_conv_route_cpu.py holds
+    the two together); any other stack takes the generic conv_* path."""
+    return (k == 6 and all(c in (8, 16, 32) for c in chans[1:-1]) and chans[0] <= 8 and chans[-1] <= 32
+            and all(c <= 16 for c in chans[:-1]))
+
+
 def gq_attention_fwd(q, k, v, o, lse, B, H, Hkv, hd, Tq, Tk, causal, drop=None, cu_q=None, cu_k=None, total_q=0, split=0):
     """Grouped-query attention (include/i2t.h::i2t_gq_attention_fwd): H query heads of width hd on Hkv shared key/value heads."""
     qb, qr = _bs_rs(q); kb, kr = _bs_rs(k); vb, vr = _bs_rs(v); ob, orr = _bs_rs(o)
@@ -622,6 +631,10 @@ def conv_bwd_weight(dy, x, in_gelu, dw, db, B, Cin, Cout, H, W, k):
 
 
 LAYOUT_NCHW_F32, LAYOUT_NCHW_BF16, LAYOUT_NHWC_BF16 = 0, 1, 2
+# The workspaces of the conv6_* calls, at the largest instantiation (csrc/conv_route.h: ws_elems, scratch_bytes; held to it by
+# tests/test_conv_route_cpu.py): the repacked weights, 32 rows x 36 taps x 32 channels, and the dW scratch, 32 x 36 x 16 floats
+CONV6_WS_ELEMS = 32 * 36 * 32
+CONV6_SCRATCH_FLOATS = 32 * 36 * 16
 
 
 def conv6_fwd(x, x_layout, in_gelu, w, bias, y, y_nchw, w_ws, B, Cin, Cout, H, W):

@@ -23,8 +23,9 @@ from test_row_kernels_gpu import TINY, _gelu_tanh64, bf16_round
 
 F32, F64 = torch.float32, torch.float64
 E8, U32, U24 = 2.0 ** -8, 2.0 ** -23, 2.0 ** -24
-TS, KS, GRP = 16, 6, 4                                      # csrc/conv_mfma.hip: tile edge, kernel size, NCHW store group
-TILE = 32                                                   # csrc/conv.hip: tile edge
+# csrc/conv_route.h: TS, KS, NCHW_GRP (the MFMA kernels' tile edge, kernel size, NCHW store group) and TILE (the generic path's tile edge)
+TS, KS, GRP = 16, 6, 4
+TILE = 32
 NCHW_F32, NCHW_BF16, NHWC_BF16 = 0, 1, 2                    # include/i2t.h layouts
 II_MAX = 0.25                                               # condition (ii): median(bound) <= rms(ref) / (4 sqrt n)
 
@@ -244,9 +245,9 @@ def _src(layout):
 
 
 def route(c):
-    """the kernel instantiation a case launches: conv_mfma_dispatch, the LAUNCH_BW selection and i2t_nchw_to_nhwc_bf16 restated.
-    The staging of an fp32 image is a run-time choice inside one instantiation (pixel chunks for <= 4 channels, planar otherwise):
-    it is part of the route."""
+    """the kernel instantiation a case launches: csrc/conv_route.h (conv6_route, conv6_bwd_weight_route) restated;
+    tests/test_conv_route_cpu.py holds the two together for every case.  The staging of an fp32 image is a run-time choice inside
+    one instantiation (pixel chunks for <= 4 channels, planar otherwise): the /chunks | /planar suffix notes it, the header does not."""
     b = lambda v: 'true' if v else 'false'
     if c.op == 'fwd':
         cp, nt = pad8(c.Cin), 1 if c.Cout <= 16 else 2
@@ -266,8 +267,9 @@ def transpose_route(C, W, aligned):
 
 
 def all_routes():
-    """every instantiation i2t_conv6_fwd / i2t_conv6_bwd_data / i2t_conv6_bwd_weight / i2t_nchw_to_nhwc_bf16 can launch, written out
-    from the launch lines of csrc/conv_mfma.hip"""
+    """every instantiation i2t_conv6_fwd / i2t_conv6_bwd_data / i2t_conv6_bwd_weight / i2t_nchw_to_nhwc_bf16 can launch: the set the
+    *_instantiated predicates of csrc/conv_route.h state (tests/test_conv_route_cpu.py compares the two), each image kernel once
+    per staging form"""
     r = set()
     for nt, nchw, sub in itertools.product((1, 2), ('false', 'true'), ('/chunks', '/planar')):
         r.add(f'conv_mfma_kernel<8, {nt}, SRC_NCHW_F32, false, false, {nchw}>{sub}')

@@ -77,7 +77,8 @@ def guarded(t, dtype, row, shift=0):
 @pytest.fixture(scope='module')
 def ws():
     """weight workspace and backward-weight scratch, sized as engine.py sizes them, inside guards"""
-    return Out((32 * 36 * 32,), F32, 64), Out((32 * 36 * 16,), F32, 64)
+    from image2text_amd import ops as _ops
+    return Out((_ops.CONV6_WS_ELEMS,), F32, 64), Out((_ops.CONV6_SCRATCH_FLOATS,), F32, 64)
 
 
 def lay(t, layout):
@@ -272,6 +273,8 @@ def test_conv6_refusals(ops, ws):
     dw = torch.full((40 * 40 * 36,), SENT, device=dev())
     db = torch.full((40,), SENT, device=dev())
     w_ws, scr = ws[0].v, ws[1].v
+    w_ws.fill_(SENT)                                        # a refused call issues nothing: no repack, no memset
+    scr.fill_(SENT)
     refused(lambda: ops.conv6_fwd(xb, 2, True, w, None, y, False, w_ws, B, 12, 16, H, W), 'NHWC input needs')
     refused(lambda: ops.conv6_fwd(xb, 2, True, w, None, y, False, w_ws, B, 24, 16, H, W), 'NHWC input needs')
     refused(lambda: ops.conv6_fwd(xb, 2, True, w, None, y, False, w_ws, B, 16, 12, H, W), 'NHWC output needs')
@@ -297,8 +300,12 @@ def test_conv6_refusals(ops, ws):
     refused(lambda: ops.conv_bwd_weight(xb, x32, False, dw, db, B, 3, 16, H, W, 5), 'unsupported')                               # generic: k
     refused(lambda: ops.conv_fwd(x32, False, w, None, y, w_ws, B, 3, 16, H, W, 5), 'kernel size 5 unsupported')
     refused(lambda: ops.conv_bwd_data(xb, w, None, False, y, w_ws, B, 3, 16, H, W, 3), 'kernel size 3 unsupported')
+    for h, wd in ((0, W), (H, 0)):                                                                                               # an empty image
+        refused(lambda: ops.conv6_fwd(x32, 0, False, w, None, y, True, w_ws, B, 3, 16, h, wd), 'i2t_conv6_fwd: bad args')
+        refused(lambda: ops.conv6_bwd_weight(xb, 2, xb, 2, True, dw, db, scr, B, 16, 32, h, wd), 'i2t_conv6_bwd_weight: bad args')
+        refused(lambda: ops.conv_fwd(x32, False, w, None, y, w_ws, B, 3, 16, h, wd, 6), 'i2t_conv_fwd: bad args')
     done(*ws)
-    for t in (y, dw, db):
+    for t in (y, dw, db, w_ws, scr):
         assert bool((t == SENT).all())
 
 
