@@ -138,12 +138,61 @@ class GeneratedCaptions(_CaptionFields):
     phrase_index: Optional[torch.Tensor] = None     # int32 [B, N] under ``phrases``: the index into ``phrases`` of the
                                                     # phrase the row emitted; None in every other mode
 
-    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None):
+    image_index: Optional[torch.Tensor] = None      # int32 [Q] under ``image_index``: the image query q was asked of -- every
+                                                    # "B" above is then Q, the queries; None without the argument
+
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None, image_index=None):
         self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
         self.prompt_lengths = prompt_lengths
         self.beam_scores = beam_scores
         self.phrase_index = phrase_index
+        self.image_index = image_index
         return self
+
+
+def check_image_index(image_index, Q: int, images: Optional[int] = None) -> Optional[np.ndarray]:
+    """What ``image_index`` refuses about itself (host only, ValueError, read before anything moves to the device) -> the
+    table, int32 [Q], or None without the argument: query q is ``prompt_ids[q]`` asked of image ``image_index[q]``.  ``Q``: the rows of
+    ``prompt_ids``; ``images``: the images of the call (None: a caller that does not know them checks no range and no count).  In this
+    order: a non-integer dtype; a shape other than (Q,); a value outside [0, images).  Without the argument, Q != images: row b of
+    ``prompt_ids`` is then asked of image b.  Before this check the drivers sized everything by Q and never compared it with the
+    images (DESIGN.md 4ac says what each call then did): with fewer prompts than images the cross K/V GEMM took the first Q images'
+    encoder rows and the others were dropped without a word; with more it ran over Q * S rows of an operand that holds images * S."""
+    if image_index is None:
+        if images is not None and int(images) != Q:
+            raise ValueError(f'{Q} prompts for {int(images)} images: without image_index row b of prompt_ids is asked of image b, so there is one '
+                             f'prompt per image; image_index (one image per prompt, shape ({Q},), values in [0, {int(images)})) asks several '
+                             f'prompts of one image')
+        return None
+    if isinstance(image_index, torch.Tensor):
+        if image_index.is_floating_point() or image_index.is_complex() or image_index.dtype == torch.bool:
+            raise ValueError(f'image_index of dtype {image_index.dtype}: integers are needed')
+        index = image_index.detach().cpu().numpy()
+    else:
+        index = np.asarray(image_index)
+        if index.dtype == np.bool_ or (index.size and not np.issubdtype(index.dtype, np.integer)):
+            raise ValueError(f'image_index of type {index.dtype}: integers are needed')
+    if index.shape != (Q,):
+        raise ValueError(f'image_index of shape {tuple(index.shape)} for prompt_ids of {Q} rows: one image per prompt, shape ({Q},)')
+    if images is not None and Q and (int(index.min()) < 0 or int(index.max()) >= int(images)):
+        bad = int(np.flatnonzero((index < 0) | (index >= int(images)))[0])
+        raise ValueError(f'image_index[{bad}] = {int(index[bad])} is outside the {int(images)} images: [0, {int(images)})')
+    if images is None and Q and int(index.min()) < 0:
+        raise ValueError(f'image_index[{int(index.argmin())}] = {int(index.min())}: an image index cannot be negative')
+    return index.astype(np.int32)
+
+
+def row_images(image_index: Optional[np.ndarray], per: int) -> Optional[np.ndarray]:
+    """The row -> image table of a call whose R = Q * ``per`` rows are query-major -- (query, n) or (query, w) --, int32 [R]: what the
+    drivers upload into st.mem_index; None without ``image_index``"""
+    return None if image_index is None else np.repeat(np.asarray(image_index, dtype=np.int32), int(per))
+
+
+def refuse_image_index_prefill(image_index, prompt_prefill: str, causal: bool = True):
+    """``image_index`` with ``prompt_prefill='pass'`` (NotImplementedError; a non-causal decoder has no cache and ignores the mode)"""
+    if image_index is not None and prompt_prefill == 'pass' and causal:
+        raise NotImplementedError("image_index with prompt_prefill='pass': the prefill pass is one causal sequence per IMAGE, and a prompt per "
+                                  "query needs that pass per query over gathered encoder outputs, which is not built; use 'steps'")
 
 
 class Processors(NamedTuple):
@@ -274,6 +323,7 @@ class ClosedSet(NamedTuple):
     tries: Optional[tuple]              # every set's own ``PhraseTrie``, which ``score_phrases`` walks; None where no one asked for them
     index: np.ndarray                   # int32 [B]: image b answers from set index[b]
     per_image: bool                     # the call came through ``phrase_sets``
+    image_index: Optional[np.ndarray] = None    # int32 [Q] under ``image_index``: every "B" above is then Q, the queries
 
     @property
     def sets(self) -> PhraseSets:
@@ -364,28 +414,48 @@ def check_phrase_caption_args(phrases, eos, vocab: int, max_new_tokens: int, pro
     return one.trie
 
 
-class PhraseScores(NamedTuple):
-    """What ``score_phrases`` returns."""
+class _PhraseScoreFields(NamedTuple):
     logprob: torch.Tensor               # fp32 [B, K]: the raw log-likelihood of phrase k + EOS after image b's prompt (``score``'s quantity)
     best: torch.Tensor                  # int64 [B]: the argmax over k, the lowest index on ties (duplicate phrases tie exactly)
     lengths: torch.Tensor               # int32 [K]: the tokens of each phrase + 1 (the EOS)
 
 
-class PhraseSetScores(NamedTuple):
-    """What ``score_phrases(phrase_sets=...)`` returns."""
+class _ImageIndexed:
+    """``image_index`` (int32 [Q], or None without the argument) as an attribute BESIDE a result tuple, the optional last
+    argument of its constructor -- ``GeneratedCaptions.prompt_lengths``' way: the tuple unpacks as before and ``_fields`` names what it named."""
+    image_index: Optional[torch.Tensor] = None
+
+    def __new__(cls, *fields, image_index=None):
+        self = super().__new__(cls, *fields)
+        self.image_index = image_index
+        return self
+
+
+class PhraseScores(_ImageIndexed, _PhraseScoreFields):
+    """What ``score_phrases`` returns; with ``image_index`` every B is Q, the queries, and the attribute ``image_index`` holds the table."""
+
+
+class _PhraseSetScoreFields(NamedTuple):
     logprob: torch.Tensor               # fp32 [B, Kmax], Kmax the phrases of the largest set: column k < K_s the raw log-likelihood of phrase k of
                                         # the image's own set + EOS after its own prompt (``score``'s quantity), -inf in columns k >= K_s
     best: torch.Tensor                  # int64 [B]: the argmax within the image's own set, the lowest index on ties (duplicates tie exactly)
     lengths: torch.Tensor               # int32 [S, Kmax]: the tokens of phrase k of set s + 1 (the EOS), 0 in the padding
 
 
+class PhraseSetScores(_ImageIndexed, _PhraseSetScoreFields):
+    """What ``score_phrases(phrase_sets=...)`` returns; ``image_index`` as in ``PhraseScores``."""
+
+
 def plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int, causal: bool = True,
-                       sparse: bool = False, images_per_pass=None, per_image: Optional[bool] = None) -> ClosedSet:
+                       sparse: bool = False, images_per_pass=None, per_image: Optional[bool] = None, image_index=None,
+                       images: Optional[int] = None) -> ClosedSet:
     """The refusals of ``score_phrases`` on ``prompt_ids`` [B, P], all before anything runs (host only) -> the call's ``ClosedSet``, with
     every set's own trie.  ValueError, in this order: ``prompt_lengths`` without ``phrase_sets``, or no phrases at all; ``closed_set``'s
     (the set or sets, the index, then ``prompt_lengths``' own); a held ``PhraseTrie`` without ``phrase_node``.  Then NotImplementedError,
     naming the reason, for a non-causal decoder and for sparse nano-mini blocks; then ValueError for the largest p_b + longest phrase of
-    b's set + 1 past the decode ``window`` (the text of every other call) and for ``images_per_pass`` < 1."""
+    b's set + 1 past the decode ``window`` (the text of every other call) and for ``images_per_pass`` < 1.  ``image_index`` / ``images``
+    (DESIGN.md 4ac): ``check_image_index``' refusals come first; B is then Q, the queries, and the record carries the table."""
+    index = check_image_index(image_index, B, images)
     if phrase_sets is None and phrase_set_index is None and prompt_lengths is not None:
         raise ValueError('score_phrases(prompt_lengths=...) needs phrase_sets: one phrase list for all images is '
                          'phrase_sets=[phrases], phrase_set_index=[0] * B')
@@ -406,7 +476,7 @@ def plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, e
         raise ValueError(f'prompt + new tokens ({total}) exceed the text window ({window})')
     if images_per_pass is not None and (isinstance(images_per_pass, bool) or int(images_per_pass) != images_per_pass or int(images_per_pass) < 1):
         raise ValueError(f'images_per_pass = {images_per_pass!r}: a whole number of images, at least 1')
-    return one
+    return one if index is None else one._replace(image_index=index)
 
 
 def check_phrase_score_args(phrases, eos, vocab: int, P: int, window: int, causal: bool = True, sparse: bool = False,
@@ -424,8 +494,7 @@ def check_phrase_set_score_args(phrases, phrase_sets, phrase_set_index, prompt_l
     return one.tries, one.index, one.plen
 
 
-class PhraseBeams(NamedTuple):
-    """What ``search_phrases`` returns: the N best phrases of the set per image, best first."""
+class _PhraseBeamFields(NamedTuple):
     phrase_index: torch.Tensor          # int64 [B, N]: the index into ``phrases``; among duplicates the one the trie's ``term`` holds (the lowest)
     logprob: torch.Tensor               # fp32 [B, N]: the raw log-likelihood of phrase + EOS after image b's prompt (``score``'s quantity)
     scores: torch.Tensor                # fp32 [B, N]: logprob / (tokens + 1) ** length_penalty, the sort key; at penalty 0.0 it equals logprob
@@ -433,18 +502,26 @@ class PhraseBeams(NamedTuple):
     exhaustive: bool                    # num_beams >= the widest trie level: nothing was pruned, the result is the exact top N of the set
 
 
+class PhraseBeams(_ImageIndexed, _PhraseBeamFields):
+    """What ``search_phrases`` returns: the N best phrases of the set per image, best first; ``image_index`` as in
+    ``PhraseScores``."""
+
+
 trie_widest_level = widest_level        # the largest number of nodes at one depth of a trie (the root's level counts: at least 1)
 
 
 def plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos, vocab: int, B: int, P: int, window: int, num_beams=4,
-                       num_return_sequences=1, length_penalty=0.0, poll_every=8, causal: bool = True, sparse: bool = False):
+                       num_return_sequences=1, length_penalty=0.0, poll_every=8, causal: bool = True, sparse: bool = False, image_index=None,
+                       images: Optional[int] = None):
     """The refusals of ``search_phrases`` on ``prompt_ids`` [B, P], all before anything runs (host only) -> (the call's ``ClosedSet``, W,
     N).  ValueError, in this order: ``prompt_lengths`` without ``phrase_sets`` (the forced column is ``phrase_sets``' rule), or no phrases
     at all; ``closed_set``'s about the set or sets and the index; ``num_beams`` outside 1 .. MAX_CAPTION_BEAMS; ``num_return_sequences``
     outside 1 .. min(num_beams, distinct phrases -- of the smallest set in use); a non-finite ``length_penalty``; ``prompt_lengths``' own
     refusals (``check_ragged_caption_args``' texts), which stand behind those of N and the penalty; the longest prompt + the longest phrase in
     use + 1 past the decode ``window`` (the text of every other call); a negative ``poll_every``.  NotImplementedError, naming the
-    reason: a non-causal decoder, sparse nano-mini blocks."""
+    reason: a non-causal decoder, sparse nano-mini blocks.  ``image_index`` / ``images``: ``check_image_index``' refusals
+    come first; B is then Q, the queries, and the record carries the table."""
+    index = check_image_index(image_index, B, images)
     if phrase_sets is None and phrase_set_index is None:
         if prompt_lengths is not None:
             raise ValueError('search_phrases(prompt_lengths=...) needs phrase_sets: one answer list for all images is '
@@ -479,7 +556,7 @@ def plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, e
     if sparse:
         raise NotImplementedError('search_phrases on sparse nano-mini decoder blocks: a sparse layer caches the positions it keeps by slot, '
                                   'and the trie beam step has not been run through its slot table (slot_pos); use rerank')
-    return one, W, int(N)
+    return (one if index is None else one._replace(image_index=index)), W, int(N)
 
 
 def check_phrase_search_args(phrases, eos, vocab: int, P: int, window: int, num_beams=4, num_return_sequences=1, length_penalty=0.0,
@@ -626,20 +703,35 @@ class CaptionPlan(NamedTuple):
     length_penalty: float
     early_stopping: bool
     sets: Optional[PhraseSets] = None   # ``phrase_sets``: the forest, every image's set, root and longest phrase; None: no sets
+    image_index: Optional[np.ndarray] = None    # int32 [Q] under ``image_index``: every "per image" above is then per query
+
+    @property
+    def rows_per_query(self) -> int:
+        return self.W if self.mode == 'beam' else self.N
+
+    @property
+    def row_images(self) -> Optional[np.ndarray]:
+        """the row -> image table of the call's R = Q * rows_per_query rows (query-major), int32 [R]; None without ``image_index``"""
+        return row_images(self.image_index, self.rows_per_query)
 
 
 def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                   temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None, prompt_prefill='steps',
                   repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1, length_penalty=1.0, early_stopping=False,
-                  phrases=None, phrase_sets=None, phrase_set_index=None, *, sampling=...) -> CaptionPlan:
+                  phrases=None, phrase_sets=None, phrase_set_index=None, *, sampling=..., image_index=None,
+                  images: Optional[int] = None) -> CaptionPlan:
     """The one place that says what ``generate_captions(...)`` on ``prompt_ids`` [B, P] means, or refuses it: the arguments are the model
     method's (``sampling``: the decoders' keyword methods hand their ``Sampling`` or None in place of the four sampling arguments).
     Refusals come in this order, the first that applies wins: ``phrase_sets`` / ``phrase_set_index``
     (``check_phrase_set_caption_args``: its ValueErrors, then the logits processors' own, then its NotImplementedErrors); ``phrases``
     (``check_phrase_caption_args``, behind the logits processors' own ValueErrors); the beam arguments (``check_beam_caption_args``); under num_beams = W > 1 the text window, then 2 W > V; else
     ``check_caption_args`` / ``check_ragged_caption_args``; an active processor on a non-causal decoder; ``prefill_plan``'s; the text
-    window.  At W = 1 only ``num_beams``, ``length_penalty`` and ``early_stopping`` are looked at among the beam arguments."""
+    window.  At W = 1 only ``num_beams``, ``length_penalty`` and ``early_stopping`` are looked at among the beam arguments.
+    ``image_index`` / ``images`` (``images``: the images of the call, None: unknown): ``check_image_index``' ValueErrors
+    come before everything above -- B is then Q, the queries, in all of it --, and its one NotImplementedError,
+    ``prompt_prefill='pass'``, after everything above; the plan carries the table."""
     eos, pad, formed = eos_token_id, pad_token_id, []
+    index = check_image_index(image_index, B, images)
 
     def processors():                   # caption_processors, entered once, by the first check that reaches it: its refusals keep their place
         if not formed:
@@ -664,7 +756,7 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
         if W * 2 > facts.V:
             raise ValueError(f'num_beams = {W} needs 2 * num_beams candidates per row: the vocabulary holds {facts.V} tokens')
         return CaptionPlan('beam', N, W, None, eos, int((0 if eos is None else eos) if pad is None else pad), poll_every, max_new_tokens, None,
-                           P, P, prompt_prefill, 0, (facts.prefix, 1), None, None, float(length_penalty), bool(early_stopping))
+                           P, P, prompt_prefill, 0, (facts.prefix, 1), None, None, float(length_penalty), bool(early_stopping), None, index)
     if sampling is ...:
         sampling = None if (top_k == 1 and nucleus_p is None) else Sampling(temperature, top_k, nucleus_p, seed)
     if prompt_lengths is None:
@@ -680,7 +772,8 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
     m, start = prefill_plan(prompt_prefill, pmin, facts.prefix, facts.fam, facts.causal)
     if pmax + max_new_tokens > facts.window:
         raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({facts.window})')
+    refuse_image_index_prefill(index, prompt_prefill, facts.causal)
     return CaptionPlan('cache' if facts.causal else 'recompute', N, 1, sampling, eos, (0 if eos is None else eos) if pad is None else pad,
                        poll_every, max_new_tokens, plen, pmin, pmax, prompt_prefill, m, start, proc, trie, float(length_penalty),
-                       bool(early_stopping), sets)
+                       bool(early_stopping), sets, index)
 

@@ -49,13 +49,13 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
 // b / rows_per_mem for every key, the per-image cross-attention memory) through the LDS copy hs[] of the table row; the
 // new token still lands in row b.  The table row is all that HIST changes -- same loads, same lanes, same reduction order:
 // with an identity table the output is bit-equal.  HIST = false reads neither hs[] (no LDS for it) nor the last three arguments.
+// The body is one device function, decode_attention_body: the kernel below hands it the key count n and `base`, the cache row its base
+// pointers kb / vb address -- row b itself, or (HIST) row 0 -- and mem_decode_attention_kernel (i2t_mem_decode_attention: a memory
+// stored once per image, row b over memory row mem_index[b]) the row its table names, with HIST = false and no append.
 template <int WPB, bool HIST>         // waves (= heads) per workgroup: 49 152 one-wave workgroups per launch were dispatch-rate bound
-__global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs,
-                                                                    bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
-                                                                    long cache_bs, int cache_rs, long cache_hs, bf16_t* __restrict__ o,
-                                                                    int o_rs, const int* __restrict__ pos_ptr, int n_keys_fixed,
-                                                                    int append_dm, const int* __restrict__ hist, int hist_ld,
-                                                                    int rows_per_mem) {
+__device__ __forceinline__ void decode_attention_body(const bf16_t* __restrict__ q, int q_rs, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                      long cache_bs, int cache_rs, long cache_hs, bf16_t* __restrict__ o, int o_rs, const int n,
+                                                      int append_dm, const int* __restrict__ hist, int hist_ld, int rows_per_mem, const int base) {
     __shared__ float qs_[WPB][64], kn_[WPB][64], vn_[WPB][64];
     __shared__ float ps_[WPB][DECODE_MAX_KEYS];
     __shared__ int hs[HIST ? DECODE_MAX_KEYS : 1];
@@ -65,13 +65,12 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
     float* vn = vn_[wv];
     float* ps = ps_[wv];
     const int h = blockIdx.x * WPB + wv, b = blockIdx.y, lane = threadIdx.x & 63;
-    const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
     const bf16_t* qrow = q + (size_t)b * q_rs + h * 64 + lane;
     qs[lane] = bf16_to_f32(qrow[0]);
-    // the cache row kb / vb address is row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
+    // the cache row kb / vb address is `base`: row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
     const int own = HIST ? b : 0;
-    bf16_t* kb = kc + (size_t)(b - own) * cache_bs + (size_t)h * cache_hs;      // cache_hs = 64: token-major rows [t][H][64];
-    bf16_t* vb = vc + (size_t)(b - own) * cache_bs + (size_t)h * cache_hs;      // cache_hs = tmax * 64 (cache_rs = 64): head-major [H][t][64]
+    bf16_t* kb = kc + (size_t)base * cache_bs + (size_t)h * cache_hs;           // cache_hs = 64: token-major rows [t][H][64];
+    bf16_t* vb = vc + (size_t)base * cache_bs + (size_t)h * cache_hs;           // cache_hs = tmax * 64 (cache_rs = 64): head-major [H][t][64]
     const int n_cached = append_dm > 0 ? n - 1 : n;          // keys read back from the cache
     if constexpr (HIST)
         for (int t = threadIdx.x; t < n_cached; t += 64 * WPB) hs[t] = hist ? hist[(size_t)b * hist_ld + t] : b / rows_per_mem;
@@ -172,6 +171,32 @@ __global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t
                           pack_bf16x2(acc[4] * inv, acc[5] * inv), pack_bf16x2(acc[6] * inv, acc[7] * inv)};
         *reinterpret_cast<u32x4*>(o + (size_t)b * o_rs + h * 64 + c * 8) = pk;
     }
+}
+
+template <int WPB, bool HIST>
+__global__ __launch_bounds__(64 * WPB) void decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs,
+                                                                    bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                                    long cache_bs, int cache_rs, long cache_hs, bf16_t* __restrict__ o,
+                                                                    int o_rs, const int* __restrict__ pos_ptr, int n_keys_fixed,
+                                                                    int append_dm, const int* __restrict__ hist, int hist_ld,
+                                                                    int rows_per_mem) {
+    decode_attention_body<WPB, HIST>(q, q_rs, kc, vc, cache_bs, cache_rs, cache_hs, o, o_rs, pos_ptr ? (*pos_ptr + 1) : n_keys_fixed, append_dm,
+                                     hist, hist_ld, rows_per_mem, HIST ? 0 : (int)blockIdx.y);
+}
+
+// i2t_mem_decode_attention: cross-attention of R rows over a memory stored once per image, [n_mem][n_keys][H 64] (token-major: heads 64
+// apart, keys mem_rs apart).  Row b = blockIdx.y attends to the n_keys keys of memory row mem_index[b]: ONE wave-uniform word per
+// workgroup, loaded once and folded into the base pointers -- no table in LDS, nothing per key (the HIST form fills hs[t] = b /
+// rows_per_mem for every key and reads it back per load).  Everything else is decode_attention_body<WPB, false> without append: the
+// same loads, lanes and reduction order, so the output is bit-equal to decode_attention_kernel<WPB, false> on the gathered memory.
+// The values of mem_index are NOT checked here: the host validates them (0 <= mem_index[r] < n_mem) before it uploads the table.
+template <int WPB>
+__global__ __launch_bounds__(64 * WPB) void mem_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ kmem,
+                                                                        const bf16_t* __restrict__ vmem, long mem_bs, int mem_rs,
+                                                                        bf16_t* __restrict__ o, int o_rs, int n_keys,
+                                                                        const int* __restrict__ mem_index) {
+    decode_attention_body<WPB, false>(q, q_rs, const_cast<bf16_t*>(kmem), const_cast<bf16_t*>(vmem), mem_bs, mem_rs, 64, o, o_rs, n_keys, 0,
+                                      nullptr, 0, 1, mem_index[blockIdx.y]);
 }
 
 // HF NoRepeatNGramLogitsProcessor + argmax for one caption per workgroup.  A row with no finite allowed column (all banned)
@@ -683,6 +708,29 @@ extern "C" int i2t_beam_decode_attention(void* stream, const void* q, int q_rs, 
                                          const int* hist, int hist_ld, int rows_per_mem, int R, int H) {
     return decode_attention("i2t_beam_decode_attention", true, stream, q, q_rs, kcache, vcache, cache_bs, cache_rs, cache_hs, o, o_rs,
                             pos_ptr, n_keys_fixed, append_dm, hist, hist_ld, rows_per_mem, R, H);
+}
+
+// Cross-attention of R rows over a memory stored once per image: row r attends to the n_keys keys of memory row mem_index[r] (head h
+// of memory row m starts at kmem + m * mem_bs + h * 64, its keys mem_rs apart).  No append, no position, no history table.  The
+// VALUES of mem_index are the caller's to check -- 0 <= mem_index[r] < n_mem, validated on the host before the table is uploaded --:
+// the kernel does not scan them, and n_mem is here for the checks below only.
+extern "C" int i2t_mem_decode_attention(void* stream, const void* q, int q_rs, const void* kmem, const void* vmem, long mem_bs, int mem_rs,
+                                        void* o, int o_rs, int n_keys, const int* mem_index, int n_mem, int R, int H) {
+    const char* fn = "i2t_mem_decode_attention";
+    I2T_REQUIRE(q && kmem && vmem && o, "%s: null operand", fn);
+    I2T_REQUIRE(mem_index, "%s: mem_index is required (one memory row per query row)", fn);
+    I2T_REQUIRE(R > 0 && H > 0, "%s: R = %d rows, H = %d heads", fn, R, H);
+    I2T_REQUIRE(n_keys >= 1 && n_keys <= DECODE_MAX_KEYS, "%s: n_keys = %d: key count out of range (1 .. %d)", fn, n_keys, DECODE_MAX_KEYS);
+    I2T_REQUIRE(n_mem >= 1, "%s: n_mem = %d: at least one memory row", fn, n_mem);
+    I2T_REQUIRE(mem_rs >= 64 * H && mem_rs % 8 == 0 && mem_bs >= (long)n_keys * mem_rs && mem_bs % 8 == 0 && ALIGNED16(kmem) && ALIGNED16(vmem),
+                "%s: memory misaligned or rows too short (mem_bs = %ld, mem_rs = %d for %d keys of %d heads of 64)", fn, mem_bs, mem_rs, n_keys, H);
+    I2T_REQUIRE(q_rs >= 64 * H && o_rs >= 64 * H && o_rs % 8 == 0 && ALIGNED16(o), "%s: output rows must be 16-byte aligned and hold H * 64 columns", fn);
+    const bool w4 = H % 4 == 0;
+    hipLaunchKernelGGL(w4 ? mem_decode_attention_kernel<4> : mem_decode_attention_kernel<1>, w4 ? dim3(H / 4, R) : dim3(H, R),
+                       dim3(w4 ? 256 : 64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs, (const bf16_t*)kmem, (const bf16_t*)vmem, mem_bs, mem_rs,
+                       (bf16_t*)o, o_rs, n_keys, mem_index);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
 }
 
 extern "C" int i2t_ngram_ban_argmax(void* stream, const void* logits, int ld, int logits_is_f32, int64_t* ids, int ids_ld,

@@ -272,24 +272,25 @@ __global__ __launch_bounds__(256) void moe_unpack_dw2_kernel(const float* __rest
 // slot_pos (sparse layers, nullable): slot s holds the layer's s-th kept text position, so its row is hist[b][slot_pos[s]].  The
 // table row is all that HIST changes: with an identity table the output is bit-equal.  HIST = false reads neither hs[] (no LDS
 // for it) nor the last four arguments.
+// The body is one device function, gq_decode_attention_body: the kernel below hands it the key count n and `base`, the cache row its
+// base pointers kb / vb address -- row b itself, or (HIST) row 0 -- and gq_mem_decode_attention_kernel (i2t_mem_gq_decode_attention: a
+// memory stored once per image, row b over memory row mem_index[b]) the row its table names, with HIST = false and no append.
 template <int HD, bool HIST>
-__global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
-                                                                 const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
-                                                                 bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
-                                                                 bf16_t* __restrict__ o, int o_rs, const int* __restrict__ pos_ptr,
-                                                                 int n_keys_fixed, int G, float scale, const int* __restrict__ hist,
-                                                                 int hist_ld, const int* __restrict__ slot_pos, int rows_per_mem) {
+__device__ __forceinline__ void gq_decode_attention_body(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
+                                                         const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
+                                                         bf16_t* __restrict__ vc, long cache_bs, int cache_rs, bf16_t* __restrict__ o, int o_rs,
+                                                         const int n, int G, float scale, const int* __restrict__ hist, int hist_ld,
+                                                         const int* __restrict__ slot_pos, int rows_per_mem, const int base) {
     constexpr int LPK = HD / 8, KPP = 64 / LPK;             // lanes per key, keys per pass
     __shared__ float qs[HD], kn[HD], vn[HD];
     __shared__ float ps[DECODE_MAX_KEYS];
     __shared__ int hs[HIST ? DECODE_MAX_KEYS : 1];
     const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x, hk = h / G;
     const bool append = k_new != nullptr;
-    const int n = pos_ptr ? (*pos_ptr + 1) : n_keys_fixed;
-    // the cache row kb / vb address is row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
+    // the cache row kb / vb address is `base`: row b itself, or (HIST) row 0, where every key adds its own row and the new token adds `own`
     const int own = HIST ? b : 0;
-    bf16_t* kb = kc + (size_t)(b - own) * cache_bs + hk * HD;
-    bf16_t* vb = vc + (size_t)(b - own) * cache_bs + hk * HD;
+    bf16_t* kb = kc + (size_t)base * cache_bs + hk * HD;
+    bf16_t* vb = vc + (size_t)base * cache_bs + hk * HD;
     if constexpr (HIST)
         for (int t = lane; t < (append ? n - 1 : n); t += 64)
             hs[t] = hist ? hist[(size_t)b * hist_ld + (slot_pos ? slot_pos[t] : t)] : b / rows_per_mem;
@@ -378,6 +379,32 @@ __global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* _
                           pack_bf16x2(acc[4] * inv, acc[5] * inv), pack_bf16x2(acc[6] * inv, acc[7] * inv)};
         *reinterpret_cast<u32x4*>(o + (size_t)b * o_rs + h * HD + c * 8) = pk;
     }
+}
+
+template <int HD, bool HIST>
+__global__ __launch_bounds__(64) void gq_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ k_new,
+                                                                 const bf16_t* __restrict__ v_new, int kv_rs, bf16_t* __restrict__ kc,
+                                                                 bf16_t* __restrict__ vc, long cache_bs, int cache_rs,
+                                                                 bf16_t* __restrict__ o, int o_rs, const int* __restrict__ pos_ptr,
+                                                                 int n_keys_fixed, int G, float scale, const int* __restrict__ hist,
+                                                                 int hist_ld, const int* __restrict__ slot_pos, int rows_per_mem) {
+    gq_decode_attention_body<HD, HIST>(q, q_rs, k_new, v_new, kv_rs, kc, vc, cache_bs, cache_rs, o, o_rs,
+                                       pos_ptr ? (*pos_ptr + 1) : n_keys_fixed, G, scale, hist, hist_ld, slot_pos, rows_per_mem,
+                                       HIST ? 0 : (int)blockIdx.y);
+}
+
+// i2t_mem_gq_decode_attention: cross-attention of R rows over a memory stored once per image, [n_mem][n_keys][Hkv HD] (row-major: keys
+// mem_rs apart).  Row b = blockIdx.y attends to the n_keys keys of memory row mem_index[b]: ONE wave-uniform word per workgroup, loaded
+// once and folded into the base pointers -- no table in LDS, nothing per key.  Everything else is gq_decode_attention_body<HD, false>
+// without append: the same loads, lanes and reduction order, so the output is bit-equal to gq_decode_attention_kernel<HD, false> on
+// the gathered memory.  The values of mem_index are NOT checked here: the host validates them before it uploads the table.
+template <int HD>
+__global__ __launch_bounds__(64) void gq_mem_decode_attention_kernel(const bf16_t* __restrict__ q, int q_rs, const bf16_t* __restrict__ kmem,
+                                                                     const bf16_t* __restrict__ vmem, long mem_bs, int mem_rs,
+                                                                     bf16_t* __restrict__ o, int o_rs, int n_keys, int G, float scale,
+                                                                     const int* __restrict__ mem_index) {
+    gq_decode_attention_body<HD, false>(q, q_rs, nullptr, nullptr, 0, const_cast<bf16_t*>(kmem), const_cast<bf16_t*>(vmem), mem_bs, mem_rs, o,
+                                        o_rs, n_keys, G, scale, nullptr, 0, nullptr, 1, mem_index[blockIdx.y]);
 }
 
 // ---------------------------------------------------------------------------------------- decode step, split over the keys
@@ -734,6 +761,32 @@ extern "C" int i2t_beam_gq_decode_attention_long(void* stream, const void* q, in
                                                  int H, int Hkv, int hd, float* ws, long ws_floats) {
     return gq_decode_attention("i2t_beam_gq_decode_attention_long", true, true, stream, q, q_rs, k_new, v_new, kv_rs, kcache, vcache, cache_bs,
                                cache_rs, out, out_rs, pos_ptr, n_keys_fixed, max_keys, hist, hist_ld, nullptr, 1, R, H, Hkv, hd, ws, ws_floats);
+}
+
+// i2t_mem_decode_attention (decode.hip) for heads of width hd over Hkv key/value heads: row r attends to the n_keys keys of memory row
+// mem_index[r] (key/value head g of memory row m starts at kmem + m * mem_bs + g * hd, its keys mem_rs apart).  The VALUES of
+// mem_index are the caller's to check -- 0 <= mem_index[r] < n_mem, validated on the host before the table is uploaded --: the kernel
+// does not scan them, and n_mem is here for the checks below only.
+extern "C" int i2t_mem_gq_decode_attention(void* stream, const void* q, int q_rs, const void* kmem, const void* vmem, long mem_bs, int mem_rs,
+                                           void* out, int out_rs, int n_keys, const int* mem_index, int n_mem, int R, int H, int Hkv, int hd) {
+    const char* fn = "i2t_mem_gq_decode_attention";
+    I2T_REQUIRE(q && kmem && vmem && out, "%s: null operand", fn);
+    I2T_REQUIRE(mem_index, "%s: mem_index is required (one memory row per query row)", fn);
+    I2T_REQUIRE(R > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "%s: R = %d rows, H = %d heads over Hkv = %d", fn, R, H, Hkv);
+    I2T_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 128, "%s: head_dim %d (16, 32, 64 or 128)", fn, hd);
+    I2T_REQUIRE(n_keys >= 1 && n_keys <= DECODE_MAX_KEYS, "%s: n_keys = %d: key count out of range (1 .. %d)", fn, n_keys, DECODE_MAX_KEYS);
+    I2T_REQUIRE(n_mem >= 1, "%s: n_mem = %d: at least one memory row", fn, n_mem);
+    I2T_REQUIRE(mem_rs >= Hkv * hd && mem_rs % 8 == 0 && mem_bs >= (long)n_keys * mem_rs && mem_bs % 8 == 0 && out_rs >= H * hd && out_rs % 8 == 0 &&
+                    q_rs >= H * hd && ALIGNED16(kmem) && ALIGNED16(vmem) && ALIGNED16(out),
+                "%s: memory / output rows must be 16-byte aligned and hold their heads (mem_bs = %ld, mem_rs = %d, out_rs = %d)", fn, mem_bs, mem_rs,
+                out_rs);
+    const float scale = 1.0f / sqrtf((float)hd);
+    const auto kernel = hd == 16 ? gq_mem_decode_attention_kernel<16> : hd == 32 ? gq_mem_decode_attention_kernel<32>
+                      : hd == 64 ? gq_mem_decode_attention_kernel<64> : gq_mem_decode_attention_kernel<128>;
+    hipLaunchKernelGGL(kernel, dim3(H, R), dim3(64), 0, (hipStream_t)stream, (const bf16_t*)q, q_rs, (const bf16_t*)kmem, (const bf16_t*)vmem, mem_bs,
+                       mem_rs, (bf16_t*)out, out_rs, n_keys, H / Hkv, scale, mem_index);
+    I2T_CHECK_LAUNCH(fn);
+    return I2T_OK;
 }
 
 extern "C" int i2t_sparse_step_setup(void* stream, const int* pos_ptr, const int* rank, const int* member, int* lpos, int* lmem, int L,

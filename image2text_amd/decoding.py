@@ -37,7 +37,7 @@ from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LON
                            check_beam_caption_args, check_caption_args, check_phrase_caption_args, check_phrase_score_args,
                            check_phrase_search_args, check_phrase_set_caption_args, check_phrase_set_score_args, check_phrase_sets,
                            check_ragged_caption_args, closed_set, decode_window, held_phrase_trie, one_closed_set, per_image_closed_set,
-                           phrase_beam_sets_graph_key, plan_captions, plan_phrase_scores, plan_phrase_search, prefill_plan, takes_long_cache,
+                           phrase_beam_sets_graph_key, plan_captions, plan_phrase_scores, plan_phrase_search, prefill_plan, row_images, takes_long_cache,
                            text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
                             beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
@@ -66,6 +66,7 @@ class GreedyDecoder:
         self.eng: HotPath = model._engine
         self._state = None
         self._long_state = None             # the state of calls past text_window (cache_plan): classic calls never run on it
+        self._state_mem = self._long_state_mem = None       # the two under ``image_index``: a call without it never runs on them
 
     # ------------------------------------------------------------------------------------------------ buffers
     def _cache_args(self):
@@ -75,26 +76,31 @@ class GreedyDecoder:
         return (dc.block, ncls if self.model.config.use_soft_prompting else 0, min(ncls, dc.block) if dc.prefixed else 0,
                 takes_long_cache(dc.llama))
 
-    def _state_for(self, rows: int, total: int, build, extra=None):
+    def _state_for(self, rows: int, total: int, build, extra=None, mem=None):
         """The cached state that serves a call over ``rows`` rows and ``total`` id columns, (re)built by ``build(clen)`` -- clen None: the
         classic window's -- when the cached one does not (_reusable).  A call that fits text_window runs on self._state, whatever ran
         before; one past it (takes_long_cache) on self._long_state, rebuilt when it holds fewer cache slots than the call needs.  A call
-        past decode_window is cache_plan's ValueError."""
+        past decode_window is cache_plan's ValueError.  ``mem`` = (memory rows, indexed) of a caller that knows them: an
+        ``image_index`` call runs on states of its own (self._state_mem / self._long_state_mem) -- its steps launch other cross-attention
+        kernels and its graphs bake st.mem_index --, rebuilt when the number of images differs; a call without it never sees them."""
         block, off, prefix, llama = self._cache_args()
         clen, long = cache_plan(block, off, prefix, total, llama)
-        slot = '_long_state' if long else '_state'
+        slot = ('_long_state' if long else '_state') + ('_mem' if mem is not None and mem[1] else '')
         st = getattr(self, slot)
-        if not self._reusable(st, rows, total, lambda st: (not long or st.clen >= clen) and (extra is None or extra(st))):
+        if not self._reusable(st, rows, total, lambda st: (not long or st.clen >= clen) and (extra is None or extra(st)) and
+                              (mem is None or (st.mem_rows == mem[0] and (st.mem_index is not None) == mem[1]))):
             setattr(self, slot, None)                           # the old buffers go before the new ones are made
             st = build(clen if long else None)
             setattr(self, slot, st)
         assert total <= st.tmax
         return st
 
-    def _build(self, B: int, ids_ld: int, mem_rows: Optional[int] = None, clen: Optional[int] = None):
+    def _build(self, B: int, ids_ld: int, mem_rows: Optional[int] = None, clen: Optional[int] = None, indexed: bool = False):
         """Buffers of a step over B rows; the cross-attention memory holds ``mem_rows`` (default B) rows -- the images, when the B
         rows are beams of them (BeamDecoder).  ``clen``: the cache slots per row of a long state (cache_plan), whose self-attention
-        runs the split-key kernels over st.attn_ws; None: the classic window."""
+        runs the split-key kernels over st.attn_ws; None: the classic window.  ``indexed`` (``image_index``): the rows
+        reach the ``mem_rows`` memory rows through the table st.mem_index, int32 [B], persistent because captured graphs bake its
+        pointer; its contents are written per call (_set_mem_index)."""
         eng, a = self.eng, self.eng.arena
         dc = eng.dec
         dev = a.device
@@ -140,6 +146,8 @@ class GreedyDecoder:
         st.hist = st.hist_init = None       # beam search: int32 [B][clen] history table (BeamDecoder), None: row b's keys are row b's
         st.ctrl = None                      # int32 [done, unfinished]: the modes that stop early (_reset clears it, _replay polls it)
         st.mem_div = 1                      # rows per cross-attention memory row
+        st.mem_rows = mem_rows or B         # the cross-attention memory's rows
+        st.mem_index = torch.zeros(B, dtype=torch.int32, device=dev) if indexed else None      # row -> memory row; None: row // st.mem_div
         if dc.fam is not None:
             self._build_family(st, e)
         if dc.advpos:
@@ -415,6 +423,12 @@ class GreedyDecoder:
         kernel; None: 64, the dense model's).  Under beam search the st.mem_div rows of an image share its memory row."""
         B, d, H = st.B, self.eng.dec.d, self.eng.dec.H
         kv, S = st.cross_kv[l]
+        if st.mem_index is not None:        # ``image_index`` (DESIGN.md 4ac): row r over memory row st.mem_index[r], checked on the host
+            if gq_hd is None:
+                ops.mem_decode_attention(st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, S, st.mem_index, st.mem_rows, B, H)
+            else:
+                ops.mem_gq_decode_attention(st.q, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, S, st.mem_index, st.mem_rows, B, H, H, gq_hd)
+            return
         kw = {} if st.mem_div == 1 else dict(rows_per_mem=st.mem_div)
         if gq_hd is None:
             args = (st.q, d, kv, kv.view(-1)[d:], S * 2 * d, 2 * d, st.ao, d, None, S, B, H)
@@ -517,11 +531,23 @@ class GreedyDecoder:
                 break
         return replays
 
-    def _prepare_inputs(self, st, images, B: int, W: int = 1, prefill=None):
+    def _set_mem_index(self, st, rows, per: int):
+        """The row -> image table of a call (``CaptionPlan.row_images`` / ``caption_plan.row_images``: int32 [R] on the host, its values
+        checked by ``check_image_index``; None: nothing to do) into st.mem_index, its one upload -> (the table as int64 on the device,
+        for _prepare_inputs' gather; ``image_index`` int32 [Q] as the results carry it, every ``per``-th word of the table)"""
+        if rows is None:
+            return None, None
+        assert rows.shape == (st.B,) and rows.min() >= 0 and rows.max() < st.mem_rows      # no out-of-range row ever reaches the device
+        st.mem_index.copy_(torch.from_numpy(rows))
+        return st.mem_index.long(), st.mem_index[::per].clone()
+
+    def _prepare_inputs(self, st, images, B: int, W: int = 1, prefill=None, index=None):
         """Everything a step reads besides the ids: the encoder output of the B images, the per-layer cross K/V (B rows), the
         soft-prompt rows' K/V at the head of the cache (copied to the W rows b * W .. b * W + W - 1 of every image) and the packed
         expert weights.  ``prefill`` = (prompt [B, >= m], m >= 1) under prompt_prefill='pass': the first m prompt columns' K/V go into
-        the cache too, from one pass that also covers the soft-prompt rows (_prefill_pass)."""
+        the cache too, from one pass that also covers the soft-prompt rows (_prefill_pass).  ``index`` (``image_index``, DESIGN.md 4ac:
+        int64 [R] on the device, row -> image): the encoder, the cross K/V and the soft-prompt pass still run over the B images, once;
+        the soft-prompt K/V then reach the R rows through a gather, row r taking image index[r]'s (W is not read)."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         # encoder + per-layer cross K/V (once per image)
         # (in slices of ENC_CHUNK images -- 4096: +1.4 % captions/s over 1024 -- every image is independent in the encoder, and its activations -- ~20 MB per
@@ -555,8 +581,13 @@ class GreedyDecoder:
 
                 def take_kv(l, sv):
                     qkv = sv.qkv.view(B, n_p, -1)
-                    st.kc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(qkv[..., ls.H * ls.hd:(ls.H + ls.Hkv) * ls.hd].unsqueeze(1))
-                    st.vc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(qkv[..., (ls.H + ls.Hkv) * ls.hd:].unsqueeze(1))
+                    kq, vq = qkv[..., ls.H * ls.hd:(ls.H + ls.Hkv) * ls.hd], qkv[..., (ls.H + ls.Hkv) * ls.hd:]
+                    if index is not None:
+                        st.kc[l][:, :n_p].copy_(kq.index_select(0, index))
+                        st.vc[l][:, :n_p].copy_(vq.index_select(0, index))
+                        return
+                    st.kc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(kq.unsqueeze(1))
+                    st.vc[l].view(B, W, st.clen, -1)[:, :, :n_p].copy_(vq.unsqueeze(1))
                 eng._layer_sink = take_kv
             try:
                 _, _, pctx = eng.decode_segment(B, n_p, eng._mem_bf16(enc_out) if eng.cross_inputs else None, S, True,
@@ -565,6 +596,10 @@ class GreedyDecoder:
                 eng._layer_sink = None
             for l in range(dc.L if dc.llama is None else 0):
                 qkv = pctx.saves[l].qkv.view(B, n_p, 3, dc.H, 64)
+                if index is not None:
+                    st.kc[l].view(-1, dc.H, st.clen, 64)[:, :, :n_p].copy_(qkv[:, :, 1].transpose(1, 2).index_select(0, index))
+                    st.vc[l].view(-1, dc.H, st.clen, 64)[:, :, :n_p].copy_(qkv[:, :, 2].transpose(1, 2).index_select(0, index))
+                    continue
                 st.kc[l].view(B, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(qkv[:, :, 1].transpose(1, 2).unsqueeze(1))
                 st.vc[l].view(B, W, dc.H, st.clen, 64)[:, :, :, :n_p].copy_(qkv[:, :, 2].transpose(1, 2).unsqueeze(1))
             del pctx
@@ -662,10 +697,11 @@ class BeamDecoder(GreedyDecoder):
     (rows_per_mem = W); the prompt is prefilled for all R rows under the identity table.  Once every beam of every caption holds
     EOS the remaining replays do nothing, so the host launches them all and reads the final length once."""
 
-    def _build_beam(self, B: int, spec: BeamSpec, ids_ld: int, record: bool, clen: Optional[int] = None):
+    def _build_beam(self, B: int, spec: BeamSpec, ids_ld: int, record: bool, clen: Optional[int] = None, mem=None):
+        """``mem`` = (images, True) under ``image_index``: B is then the queries"""
         W, E = spec.beam_width, spec.expansion
         R = B * W
-        st = self._build(R, ids_ld, mem_rows=B, clen=clen)
+        st = self._build(R, ids_ld, mem_rows=B if mem is None else mem[0], clen=clen, indexed=mem is not None and mem[1])
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         st.W, st.images = W, B
@@ -772,9 +808,10 @@ class CaptionDecoder(GreedyDecoder):
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
     last_prefill_steps = 0              # prefill replays the last call launched: Pmin - 1, or 0 under prompt_prefill='pass'
 
-    def _build_captions(self, B: int, N: int, ids_ld: int, clen: Optional[int] = None):
+    def _build_captions(self, B: int, N: int, ids_ld: int, clen: Optional[int] = None, mem=None):
+        """``mem`` = (images, True) under ``image_index``: B is then the queries"""
         R = B * N
-        st = self._build(R, ids_ld, mem_rows=B, clen=clen)
+        st = self._build(R, ids_ld, mem_rows=B if mem is None else mem[0], clen=clen, indexed=mem is not None and mem[1])
         dev = st.arena.device
         i32 = dict(dtype=torch.int32, device=dev)
         st.N, st.images = N, B
@@ -881,7 +918,7 @@ class CaptionDecoder(GreedyDecoder):
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
                           use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps', repetition_penalty: float = 1.0,
                           min_new_tokens: int = 0, suppress_tokens=None, phrases=None, each=None, phrase_sets=None,
-                          phrase_set_index=None) -> GeneratedCaptions:
+                          phrase_set_index=None, image_index=None) -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
         None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
@@ -902,17 +939,21 @@ class CaptionDecoder(GreedyDecoder):
         plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
                              poll_every=poll_every, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
                              repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
-                             phrases=phrases, phrase_sets=phrase_sets, phrase_set_index=phrase_set_index, sampling=sampling)
+                             phrases=phrases, phrase_sets=phrase_sets, phrase_set_index=phrase_set_index, sampling=sampling,
+                             image_index=image_index, images=len(images))
         return self.run(images, prompt_ids, plan, use_graph, each)
 
     @torch.no_grad()
     def run(self, images, prompt_ids: torch.Tensor, plan: CaptionPlan, use_graph: bool = True, each=None) -> GeneratedCaptions:
-        """A 'cache' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here."""
+        """A 'cache' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here.  Under
+        ``plan.image_index`` B is Q, the queries -- rows are (query, n), and everything below is per query -- except in
+        what runs once per IMAGE: the encoder, the cross K/V and the soft-prompt pass (_prepare_inputs over ``mem[0]`` images)."""
         if plan.mode != 'cache':
             raise ValueError('CaptionDecoder needs a causal decoder')
         eng = self.eng
         dc = eng.dec
         B = prompt_ids.shape[0]
+        mem = (B, False) if plan.image_index is None else (len(images), True)
         N, sampling, eos, pad, poll_every, max_new_tokens = plan.N, plan.sampling, plan.eos, plan.pad, plan.poll_every, plan.max_new
         plen, pmin, pmax, proc, trie, m, start = plan.plen, plan.pmin, plan.pmax, plan.proc, plan.trie, plan.m, plan.start
         sets = plan.sets
@@ -924,7 +965,8 @@ class CaptionDecoder(GreedyDecoder):
             m = 0
         a = eng.prepare(False)
         R, total = B * N, pmax + max_new_tokens
-        st = self._state_for(R, total, lambda clen: self._build_captions(B, N, max(total, dc.block), clen), lambda st: st.N == N)
+        st = self._state_for(R, total, lambda clen: self._build_captions(B, N, max(total, dc.block), clen, mem), lambda st: st.N == N, mem)
+        row_index, index_dev = self._set_mem_index(st, plan.row_images, N)
         prompt = prompt_ids[:, :pmax].to(a.device)
         plen_dev = forced = None
         if ragged:
@@ -943,9 +985,9 @@ class CaptionDecoder(GreedyDecoder):
                 ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
                 self.last_replays = self.last_prefill_steps = 0
                 zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
-                return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev)
+                return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev, image_index=index_dev)
             forced = (st.rag_prompt, st.rag_plen, max_new_tokens)
-        self._prepare_inputs(st, images, B, N, prefill=(prompt, m) if m else None)
+        self._prepare_inputs(st, images, mem[0], N, prefill=(prompt, m) if m else None, index=row_index)
         # 'pass': the first step is at slot prefix + m, column 1 + m; st.counters_init stays what 'steps' calls on this state start from
         start = torch.tensor(start, dtype=torch.int32, device=a.device) if m else st.counters_init
         if sampling is not None:
@@ -982,7 +1024,7 @@ class CaptionDecoder(GreedyDecoder):
         ids = st.ids[:, :L].reshape(B, N, L).clone()
         tok_lp = st.tok_lp[:, pmin:L].reshape(B, N, L - pmin).clone()
         return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev,
-                                 phrase_index=None if trie is None else st.phrase_index.view(B, N).clone())
+                                 phrase_index=None if trie is None else st.phrase_index.view(B, N).clone(), image_index=index_dev)
 
 
 class CaptionBeamDecoder(BeamDecoder):
@@ -994,9 +1036,9 @@ class CaptionBeamDecoder(BeamDecoder):
 
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
 
-    def _build_caption_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None):
+    def _build_caption_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None, mem=None):
         spec = BeamSpec(W, 2 * W, 0.0, None, 0.0, None, 0.0, tuple(int(n) for n in self.model.config.no_repeat_n_grams))
-        st = self._build_beam(B, spec, ids_ld, False, clen)
+        st = self._build_beam(B, spec, ids_ld, False, clen, mem)
         dev = st.arena.device
         st.tok_lp = torch.zeros(B * W, ids_ld, dtype=F32, device=dev)
         self._build_pool(st, B, W, ids_ld)
@@ -1018,16 +1060,19 @@ class CaptionBeamDecoder(BeamDecoder):
     @torch.no_grad()
     def generate_captions(self, images, prompt_ids: torch.Tensor, max_new_tokens: int, num_beams: int, eos: Optional[int] = None,
                           pad: Optional[int] = None, num_return_sequences: int = 1, length_penalty: float = 1.0,
-                          early_stopping: bool = False, poll_every: int = 8, use_graph: bool = True, each=None) -> GeneratedCaptions:
+                          early_stopping: bool = False, poll_every: int = 8, use_graph: bool = True, each=None,
+                          image_index=None) -> GeneratedCaptions:
         """``beam_search_host`` for every image of the batch, on the device -> GeneratedCaptions with ``beam_scores``.  ``each(i)`` runs
         after full step i (tests read the step's buffers there)."""
         plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
-                             poll_every=poll_every, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+                             poll_every=poll_every, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
+                             image_index=image_index, images=len(images))
         return self.run(images, prompt_ids, plan, use_graph, each)
 
     @torch.no_grad()
     def run(self, images, prompt_ids: torch.Tensor, plan: CaptionPlan, use_graph: bool = True, each=None) -> GeneratedCaptions:
-        """A 'beam' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here."""
+        """A 'beam' plan (``plan_captions``) on ``prompt_ids`` [B, P]: nothing is checked or derived again here.  Under
+        ``plan.image_index`` B is Q, the queries: rows are (query, w), the pools are the queries'."""
         assert plan.mode == 'beam', plan.mode
         eng = self.eng
         dc = eng.dec
@@ -1037,14 +1082,17 @@ class CaptionBeamDecoder(BeamDecoder):
         prompt_ids = prompt_ids.to(a.device)
         B, P = prompt_ids.shape
         R, total = B * W, P + max_new_tokens
+        mem = (B, False) if plan.image_index is None else (len(images), True)
         if max_new_tokens == 0:             # nothing to emit: the prompts, N times, at score 0
             self.last_replays = 0
             zero = torch.zeros(B, N, 0, dtype=F32, device=a.device)
             return GeneratedCaptions(prompt_ids[:, None].expand(B, N, P).clone(), torch.full((B, N), P, dtype=torch.int32, device=a.device),
-                                     zero, zero.sum(dim=-1), None, torch.zeros(B, N, dtype=F32, device=a.device))
-        st = self._state_for(R, total, lambda clen: self._build_caption_beam(B, W, max(total, dc.block), clen),
-                             lambda st: st.W == W)
-        self._prepare_inputs(st, images, B, W)
+                                     zero, zero.sum(dim=-1), None, torch.zeros(B, N, dtype=F32, device=a.device),
+                                     image_index=None if plan.image_index is None else torch.from_numpy(plan.image_index).to(a.device))
+        st = self._state_for(R, total, lambda clen: self._build_caption_beam(B, W, max(total, dc.block), clen, mem),
+                             lambda st: st.W == W, mem)
+        row_index, index_dev = self._set_mem_index(st, plan.row_images, W)
+        self._prepare_inputs(st, images, mem[0], W, index=row_index)
         prompt_rows = prompt_ids.repeat_interleave(W, dim=0)
 
         def reset():
@@ -1063,7 +1111,7 @@ class CaptionBeamDecoder(BeamDecoder):
         L = int(lengths.max().item())                           # the final host sync
         tok_lp = st.pool_lp[:, :N, P:L].contiguous()
         return GeneratedCaptions(st.pool_ids[:, :N, :L].contiguous(), lengths, tok_lp, tok_lp.sum(dim=-1), None,
-                                 st.pool_score[:, :N].contiguous())
+                                 st.pool_score[:, :N].contiguous(), image_index=index_dev)
 
 
 TRIE_SCORE_BYTES = int(os.environ.get('I2T_TRIE_SCORE_BYTES', str(8 << 30)))      # the per-pass state budget images_per_pass is derived from
@@ -1125,7 +1173,9 @@ class TrieScoreDecoder(BeamDecoder):
         return pre
 
     def _load_group(self, st, pre, take):
-        """the cross K/V of images ``take`` [st.images] and their soft-prompt K/V into the head of every row's cache"""
+        """the cross K/V of images ``take`` [st.images] and their soft-prompt K/V into the head of every row's cache.  Under
+        ``image_index`` ``take`` names the images of the group's QUERIES: an image asked twice in a pass has its K/V
+        there twice -- the pass keeps rows_per_mem = W and its kernels"""
         dc = self.eng.dec
         Bp, W, n_p = st.images, st.W, st.prefix
         for l, (kv, _) in st.cross_kv.items():
@@ -1224,7 +1274,8 @@ class TrieScoreDecoder(BeamDecoder):
     @torch.no_grad()
     def run(self, images, prompt_ids: torch.Tensor, one: ClosedSet, eos: int, images_per_pass: Optional[int] = None):
         """``phrase_scores_host`` -- ``one.per_image``: ``phrase_set_scores_host`` -- for every image of the batch, on the
-        device -> ``PhraseScores`` / ``PhraseSetScores``.  ``one``: what ``plan_phrase_scores`` returned.  The encoder once, then groups
+        device -> ``PhraseScores`` / ``PhraseSetScores``.  ``one``: what ``plan_phrase_scores`` returned; under ``one.image_index``
+         B below is Q, the queries, the groups are groups of queries, and only _encode_all runs over the images.  The encoder once, then groups
         of ``images_per_pass`` images; all rows share the step counter: min p_b - 1 prefill steps, then the form's walk.  What the two
         forms do not share is the walk, what a column no phrase writes holds (0 / -inf) and the prompt columns at or past p_b, which
         only the per-image form has and drops here: nothing downstream sees what the caller left in them."""
@@ -1254,11 +1305,12 @@ class TrieScoreDecoder(BeamDecoder):
         out = torch.full((B, K), fill, dtype=F32, device=dev)
         part = torch.zeros(Bp, (K + 3) // 4 * 4, dtype=F32, device=dev)
         self.last_passes = 0
-        pre = self._encode_all(st, images, B)
+        index_dev = None if one.image_index is None else torch.from_numpy(one.image_index).to(dev)
+        pre = self._encode_all(st, images, B if index_dev is None else len(images))
         for i in range(0, B, Bp):
             n = min(Bp, B - i)
             take = torch.arange(i, i + Bp, device=dev).clamp(max=B - 1)         # a short last group is filled with its last image
-            self._load_group(st, pre, take)
+            self._load_group(st, pre, take if index_dev is None else index_dev.long()[take])
             self._reset(st, prompt[take].repeat_interleave(W, dim=0), pmax)
             st.path[0].zero_()
             part.fill_(fill)
@@ -1269,7 +1321,7 @@ class TrieScoreDecoder(BeamDecoder):
             self.last_passes += 1
         top = out.max(dim=1, keepdim=True).values
         best = torch.where(out == top, torch.arange(K, device=dev)[None, :], torch.full((), K, device=dev)).min(dim=1).values
-        return (PhraseSetScores if per else PhraseScores)(out, best, torch.from_numpy(lengths).to(dev))
+        return (PhraseSetScores if per else PhraseScores)(out, best, torch.from_numpy(lengths).to(dev), image_index=index_dev)
 
     def score(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, images_per_pass: Optional[int] = None) -> PhraseScores:
         """``run`` on one checked trie for all images"""
@@ -1287,8 +1339,8 @@ class PhraseBeamDecoder(BeamDecoder):
 
     last_replays = 0                    # full-step replays the last call launched (tests, tools)
 
-    def _build_phrase_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None):
-        st = self._build_beam(B, BeamSpec(W, W, 0.0, None, 0.0, None, 0.0, ()), ids_ld, False, clen)       # cand_tok / cand_lp: [R, W]
+    def _build_phrase_beam(self, B: int, W: int, ids_ld: int, clen: Optional[int] = None, mem=None):
+        st = self._build_beam(B, BeamSpec(W, W, 0.0, None, 0.0, None, 0.0, ()), ids_ld, False, clen, mem)  # cand_tok / cand_lp: [R, W]
         dev = st.arena.device
         i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=F32, device=dev)
         R = B * W
@@ -1326,7 +1378,8 @@ class PhraseBeamDecoder(BeamDecoder):
         arguments, so a captured step holds them (W is the state's).  ``one.per_image``: row 0 of image b starts at its
         set's root; Pmin - 1 prefill steps, then Pmax - Pmin + max(longest) + 1 full steps in which an image whose prompt reaches past
         the column is held still by i2t_trie_beam_select_sets.  The start nodes, prompt lengths and longest phrases are then device
-        tables filled per call: the graph key is ('phrase_beam_sets', Pmax, W, eos, penalty)."""
+        tables filled per call: the graph key is ('phrase_beam_sets', Pmax, W, eos, penalty).  Under ``one.image_index`` B
+        is Q, the queries: rows are (query, w), the pools are the queries'."""
         eng = self.eng
         dc = eng.dec
         a = eng.prepare(False)
@@ -1338,8 +1391,9 @@ class PhraseBeamDecoder(BeamDecoder):
         pmin, pmax = (int(plen.min()), int(plen.max())) if per else (P, P)
         longest, length_penalty = int(one.longest.max()), float(length_penalty)
         R, total = B * W, pmax + longest + 1
-        st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen),
-                             lambda st: st.W == W)
+        mem = (B, False) if one.image_index is None else (len(images), True)
+        st = self._state_for(R, total, lambda clen: self._build_phrase_beam(B, W, max(total, dc.block), clen, mem),
+                             lambda st: st.W == W, mem)
         self._upload_trie(st, one.trie, ('phrase_beam', 'phrase_beam_sets'))
         node_init = st.node_init
         if per:
@@ -1350,7 +1404,8 @@ class PhraseBeamDecoder(BeamDecoder):
             node_init[:, 0] = torch.from_numpy(one.roots).to(dev)
             st.set_plen.copy_(torch.from_numpy(plen))
             st.set_longest.copy_(torch.from_numpy(one.longest))
-        self._prepare_inputs(st, images, B, W)
+        row_index, index_dev = self._set_mem_index(st, row_images(one.image_index, W), W)
+        self._prepare_inputs(st, images, mem[0], W, index=row_index)
         if per:                             # columns at or past p_b are dropped here: nothing downstream sees what the caller left in them
             keep = torch.arange(pmax, device=dev)[None, :] < st.set_plen[:, None]
             prompt = torch.where(keep, prompt_ids[:, :pmax], torch.zeros((), dtype=torch.long, device=dev))
@@ -1366,7 +1421,7 @@ class PhraseBeamDecoder(BeamDecoder):
         self.last_replays = self._replay(st, key, lambda: self._phrase_beam_step(st, pmax, int(eos), longest, length_penalty, per), reset,
                                          pmin - 1, pmax - pmin + longest + 1, use_graph, each=each, poll_every=poll_every, prefill_first=True)
         return PhraseBeams(st.pool_phrase[:, :N].long(), st.pool_sum[:, :N].clone(), st.pool_score[:, :N].clone(), st.pool_len[:, :N].clone(),
-                           W >= one.widest_level())
+                           W >= one.widest_level(), image_index=index_dev)
 
     def search(self, images, prompt_ids: torch.Tensor, trie: PhraseTrie, eos: int, W: int, N: int, length_penalty: float = 0.0,
                poll_every: int = 8, use_graph: bool = True, each=None) -> PhraseBeams:

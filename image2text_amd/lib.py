@@ -140,6 +140,8 @@ SIGNATURES = {
     'i2t_beam_advance': [P, PI, PI],
     'i2t_beam_decode_attention': [P, P, I, P, P, L, I, L, P, I, PI, I, I, PI, I, I, I, I],
     'i2t_beam_gq_decode_attention': [P, P, I, P, P, I, P, P, L, I, P, I, PI, I, I, PI, I, PI, I, I, I, I, I],
+    'i2t_mem_decode_attention': [P, P, I, P, P, L, I, P, I, I, PI, I, I, I],
+    'i2t_mem_gq_decode_attention': [P, P, I, P, P, L, I, P, I, I, PI, I, I, I, I, I],
     'i2t_sparse_step_setup': [P, PI, PI, PI, PI, PI, I, I],
     'i2t_select_rows': [P, PI, PF, PF, PF, L],
     'i2t_grouped_gemm': [P, I, P, I, P, I, L, P, I, L, I, PF, L, I, P, P, I, PF, I, I, PI, I, I, PI, I, I, I],
@@ -191,7 +193,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _lib = None
 
 

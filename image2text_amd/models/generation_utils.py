@@ -166,12 +166,18 @@ def rerank_labels(ids: torch.Tensor, eos: Optional[int], prompt_len: int = 1, ig
 
 
 @torch.no_grad()
-def rerank(model, images, candidates: torch.Tensor, eos: Optional[int] = None, prompt_len: int = 1, temperature: float = 1.0):
+def rerank(model, images, candidates: torch.Tensor, eos: Optional[int] = None, prompt_len: int = 1, temperature: float = 1.0, image_index=None):
     """Order W candidate captions per image by their log-likelihood (an addition: the reference has no such call).
     candidates (B, W, L) -> (order (B, W): candidate indices, best first; logprob (B, W): sum of log p(token | image, predecessors)
-    over each candidate's tokens after the prompt, up to and including its first ``eos``).  The encoder runs once per image."""
+    over each candidate's tokens after the prompt, up to and including its first ``eos``).  The encoder runs once per image.
+    ``image_index`` (ints [Q] in [0, images)): candidates is (Q, W, L), and row q's candidates are scored against image
+    image_index[q] -- the encoder still runs once per image, its output gathered per row; ``caption_plan.check_image_index``' refusals."""
+    from ..caption_plan import check_image_index
     B, W, L = candidates.shape
-    enc = model.encode(images)                                                  # (B, n_cls, d), once
+    index = check_image_index(image_index, B, len(images) if image_index is not None else None)
+    enc = model.encode(images)                                                  # (images, n_cls, d), once
+    if index is not None:
+        enc = enc.index_select(0, torch.from_numpy(index).to(enc.device).long())
     enc = enc.unsqueeze(1).expand(B, W, *enc.shape[1:]).reshape(B * W, *enc.shape[1:]).contiguous()
     flat = candidates.to(enc.device).reshape(B * W, L)
     scores = model.score(None, flat, labels=rerank_labels(flat, eos, prompt_len), encoder_output=enc, temperature=temperature)

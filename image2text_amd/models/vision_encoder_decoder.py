@@ -260,7 +260,7 @@ class VisionEncoderDecoder(nn.Module):
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
                           prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1,
-                          length_penalty=1.0, early_stopping=False, phrases=None, phrase_sets=None, phrase_set_index=None):
+                          length_penalty=1.0, early_stopping=False, phrases=None, phrase_sets=None, phrase_set_index=None, image_index=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -350,14 +350,27 @@ class VisionEncoderDecoder(nn.Module):
         ``phrases`` given too, ``phrase_set_index`` without ``phrase_sets``, what ``phrases`` refuses about a set (behind
         'phrase_sets[s]: '), an index of the wrong length or outside [0, S), None with S != B, ``max_new_tokens`` below the longest
         phrase of a set in use + 1; NotImplementedError with an active logits processor, ``num_beams`` > 1 or a non-causal decoder.
-        Without the two arguments the call is the one before they existed, launch for launch."""
+        Without the two arguments the call is the one before they existed, launch for launch.
+        ``image_index`` asks several prompts of one image in ONE call: ``images`` is [B, 3, H, W], ``prompt_ids`` [Q, P],
+        and query q is ``prompt_ids[q]`` asked of image ``image_index[q]`` (an int sequence or tensor [Q] with values in [0, B)).
+        Everything above that is "per image" is then per QUERY and has length Q -- ``prompt_lengths``, ``phrase_set_index`` (None: S == Q),
+        ``ids [Q, N, L]`` and every other result tensor --, and the result carries ``image_index`` (int32 [Q]; None without the
+        argument).  The encoder, the cross-attention K/V and the soft-prompt rows' pass run over the B images, ONCE, where
+        ``images[image_index]`` pays them per query; an image no query names is still encoded.  The decode steps are the same launches
+        over the same Q * N rows, except the cross-attention, which reads its memory row through the table
+        (``i2t_mem_decode_attention`` / ``i2t_mem_gq_decode_attention``) and is bit-equal to the plain kernel on the gathered memory.
+        Refusals, before anything runs (``caption_plan.check_image_index``): ValueError for a non-integer dtype, a length other than Q,
+        a value outside [0, B), and -- without the argument -- for Q != B, which was silently mishandled before;
+        NotImplementedError with ``prompt_prefill='pass'`` (that pass is one sequence per image).  A NON-causal decoder has no cache:
+        it runs the path above on ``images[image_index]``.  None (the default) is the call without the argument, launch for launch."""
         import numpy as np
         from ..decoding import CaptionBeamDecoder, CaptionDecoder, GeneratedCaptions, caption_facts, generate_by_recompute, plan_captions
         from ..decoding_host import apply_finish_rule_ragged
         B, P = prompt_ids.shape
         plan = plan_captions(caption_facts(self), B, P, max_new_tokens, eos_token_id, pad_token_id, num_return_sequences, temperature, top_k,
                              nucleus_p, seed, poll_every, prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens,
-                             num_beams, length_penalty, early_stopping, phrases, phrase_sets, phrase_set_index)
+                             num_beams, length_penalty, early_stopping, phrases, phrase_sets, phrase_set_index, image_index=image_index,
+                             images=len(images))
         dev = next(self.parameters()).device
         prompt_ids = prompt_ids.to(dev)
         if plan.mode == 'beam':
@@ -365,6 +378,8 @@ class VisionEncoderDecoder(nn.Module):
         if plan.mode == 'cache':
             return self._decoder('_captioner', CaptionDecoder).run(images, prompt_ids, plan)
         N, sampling, plen, pmin, pmax = plan.N, plan.sampling, plan.plen, plan.pmin, plan.pmax
+        index_dev = None if plan.image_index is None else torch.from_numpy(plan.image_index).to(dev)
+        images = images if index_dev is None else images.to(dev)[index_dev.long()]          # no cache, nothing to share: one image per query
         # no cache: generate_by_recompute once per distinct prompt length over the rows of that length, the host rule, then score
         images_rep = images.repeat_interleave(N, dim=0) if N > 1 else images
         prompt_rep = prompt_ids.repeat_interleave(N, dim=0)
@@ -383,7 +398,8 @@ class VisionEncoderDecoder(nn.Module):
         labels[(col >= lengths[:, None] - 1) | (col < torch.from_numpy(rows).to(dev)[:, None] - 1)] = -100
         lp = self.score(images_rep, ids, labels=labels).token_logprobs[:, pmin - 1:L - 1] if L > pmin else torch.zeros(B * N, 0, device=dev)
         lp = lp.reshape(B, N, L - pmin).contiguous()
-        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), None if plen is None else torch.from_numpy(plen).to(dev))
+        return GeneratedCaptions(ids.view(B, N, L), lengths.view(B, N), lp, lp.sum(dim=-1), None if plen is None else torch.from_numpy(plen).to(dev),
+                                 image_index=index_dev)
 
     @torch.no_grad()
     def score_phrases(self, images, prompt_ids, phrases=None, eos_token_id=None, images_per_pass=None, phrase_sets=None, phrase_set_index=None,
@@ -413,17 +429,34 @@ class VisionEncoderDecoder(nn.Module):
         widest level of any set.  Refusals (``caption_plan.check_phrase_set_score_args``): ValueError for ``phrases`` together with
         ``phrase_sets``, ``phrase_set_index`` or ``prompt_lengths`` without ``phrase_sets`` (one list for all images:
         ``phrase_sets=[phrases], phrase_set_index=[0] * B``), the largest p_b + longest phrase of b's set + 1 past the text window,
-        ``images_per_pass`` < 1; the same NotImplementedErrors.  With the three at None the call is what it was, bit for bit."""
+        ``images_per_pass`` < 1; the same NotImplementedErrors.  With the three at None the call is what it was, bit for bit.
+        Several prompts per image (``image_index``) go through ``score_phrases_indexed``: this method's parameter list is
+        held as it stands by tests/test_phrase_set_scores_host_cpu.py, so the table is a positional argument of a method of its own.
+        Here row b of ``prompt_ids`` is asked of image b, and a ``prompt_ids`` with another number of rows than ``images`` is a ValueError."""
+        return self.score_phrases_indexed(images, prompt_ids, None, phrases, eos_token_id, images_per_pass, phrase_sets, phrase_set_index,
+                                          prompt_lengths)
+
+    @torch.no_grad()
+    def score_phrases_indexed(self, images, prompt_ids, image_index, phrases=None, eos_token_id=None, images_per_pass=None, phrase_sets=None,
+                              phrase_set_index=None, prompt_lengths=None):
+        """``score_phrases`` with several prompts per image: ``image_index`` is ``generate_captions``' argument of that
+        name, with its meaning and refusals -- ``prompt_ids`` is [Q, P], query q is asked of image ``image_index[q]`` --, every other
+        argument is ``score_phrases``' own, and everything "per image" there is per query: ``logprob [Q, K]``, ``best [Q]``,
+        ``prompt_lengths`` and ``phrase_set_index`` of length Q (None: S == Q), ``images_per_pass`` counting queries; the result carries
+        ``image_index``.  The encoder, the cross K/V projections and the soft-prompt pass run once per IMAGE; a pass copies them per
+        query, so an image asked twice in one pass has its K/V there twice.  An image no query names is still encoded.
+        ``image_index=None`` is ``score_phrases``, bit for bit."""
         from ..decoding import TrieScoreDecoder, caption_facts, plan_phrase_scores
         facts = caption_facts(self)
         one = plan_phrase_scores(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V, *prompt_ids.shape,
-                                 facts.cache_window, facts.causal, facts.sparse, images_per_pass)
+                                 facts.cache_window, facts.causal, facts.sparse, images_per_pass, image_index=image_index,
+                                 images=len(images))
         return self._decoder('_trie_scorer', TrieScoreDecoder).run(images, prompt_ids.to(next(self.parameters()).device), one,
                                                                    int(eos_token_id), images_per_pass)
 
     @torch.no_grad()
     def search_phrases(self, images, prompt_ids, phrases=None, eos_token_id=None, num_beams=4, num_return_sequences=1, length_penalty=0.0,
-                       poll_every=8, phrase_sets=None, phrase_set_index=None, prompt_lengths=None):
+                       poll_every=8, phrase_sets=None, phrase_set_index=None, prompt_lengths=None, image_index=None):
         """The N best phrases of a closed set by beam search on the set's token trie (no counterpart in the reference) ->
         ``decoding.PhraseBeams(phrase_index [B, N], logprob [B, N], scores [B, N], lengths [B, N], exhaustive)``, best first.
         ``phrases`` is what ``generate_captions`` and ``score_phrases`` take: K >= 1 token-id sequences (or the ``PhraseTrie`` built of
@@ -444,11 +477,16 @@ class VisionEncoderDecoder(nn.Module):
         phrase set and a prompt of its own length per image (``prompt_ids[b, :p_b]``; later columns are ignored).  ``phrase_index``
         then indexes into the image's own set; N is at most W and at most the distinct phrases of the smallest set in use;
         ``exhaustive`` says W >= the widest level of every set in use.  ``prompt_lengths`` needs ``phrase_sets`` (one list for all
-        images: ``phrase_sets=[answers], phrase_set_index=[0] * B``); ``phrases`` together with ``phrase_sets`` is a ValueError."""
+        images: ``phrase_sets=[answers], phrase_set_index=[0] * B``); ``phrases`` together with ``phrase_sets`` is a ValueError.
+        ``image_index`` is ``generate_captions``' argument of that name, with its meaning and refusals: ``prompt_ids`` is
+        [Q, P], query q is asked of image ``image_index[q]``, every result is [Q, N], ``prompt_lengths`` and ``phrase_set_index`` have
+        length Q, and the result carries ``image_index``.  The encoder, the cross K/V and the soft-prompt pass run once per IMAGE; an
+        image no query names is still encoded."""
         from ..decoding import PhraseBeamDecoder, caption_facts, plan_phrase_search
         facts = caption_facts(self)
         one, W, N = plan_phrase_search(phrases, phrase_sets, phrase_set_index, prompt_lengths, eos_token_id, facts.V, *prompt_ids.shape,
-                                       facts.cache_window, num_beams, num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse)
+                                       facts.cache_window, num_beams, num_return_sequences, length_penalty, poll_every, facts.causal, facts.sparse,
+                                       image_index=image_index, images=len(images))
         return self._decoder('_phrase_searcher', PhraseBeamDecoder).run(images, prompt_ids.to(next(self.parameters()).device), one,
                                                                         int(eos_token_id), W, N, float(length_penalty), int(poll_every))
 

@@ -401,6 +401,28 @@ def beam_gq_decode_attention(q, k_new, v_new, kcache, vcache, cache_bs, cache_rs
     return out
 
 
+def _mem_index(mem_index, R):
+    """the row -> memory-row table of the two calls below: int32 [>= R], contiguous.  Its VALUES are the caller's to check against
+    n_mem before the upload (caption_plan.check_image_index): the kernels do not scan them."""
+    assert mem_index is None or (mem_index.dim() == 1 and mem_index.is_contiguous() and mem_index.numel() >= R), \
+        f'mem_index: one contiguous int32 word per row ({R} rows)'
+    return mem_index
+
+
+def mem_decode_attention(q, q_rs, kmem, vmem, mem_bs, mem_rs, o, o_rs, n_keys, mem_index, n_mem, R, H):
+    """Cross-attention of R rows over a memory stored once per image: row r attends to the n_keys keys of memory row mem_index[r], heads
+    of 64 in decode_attention's token-major layout (include/i2t.h::i2t_mem_decode_attention)."""
+    _k.i2t_mem_decode_attention(q, q_rs, kmem, vmem, mem_bs, mem_rs, o, o_rs, n_keys, _mem_index(mem_index, R), n_mem, R, H)
+
+
+def mem_gq_decode_attention(q, kmem, vmem, mem_bs, mem_rs, out, n_keys, mem_index, n_mem, R, H, Hkv, hd):
+    """mem_decode_attention for Hkv key/value heads of width hd under H query heads (include/i2t.h::i2t_mem_gq_decode_attention); q /
+    out are row-major 2-D views."""
+    _k.i2t_mem_gq_decode_attention(q, 0 if q is None else q.stride(0), kmem, vmem, mem_bs, mem_rs, out, 0 if out is None else out.stride(0), n_keys,
+                                   _mem_index(mem_index, R), n_mem, R, H, Hkv, hd)
+    return out
+
+
 # the host's copy of csrc/common.h::LONG_CHUNK_KEYS, the keys per wave of the split-key decode attention
 # (tests/test_long_decode_host_cpu.py reads the header against it)
 LONG_CHUNK_KEYS = 256

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 19
+#define I2T_ABI_VERSION 20
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -747,6 +747,21 @@ int i2t_beam_gq_decode_attention(void* stream, const void* q, int q_rs, const vo
                                  void* vcache, long cache_bs, int cache_rs, void* out, int out_rs, const int* pos_ptr, int n_keys_fixed,
                                  int max_keys, const int* hist, int hist_ld, const int* slot_pos, int rows_per_mem, int R, int H,
                                  int Hkv, int hd);
+/* Cross-attention over a memory stored once per image, with a row -> memory-row table (``image_index`` of the decoding calls; DESIGN.md
+ * 4ac, ABI 20): row r of the R query rows attends to the n_keys keys of memory row mem_index[r] (int32 [R] on the device).  kmem / vmem:
+ * [n_mem][n_keys] rows mem_rs apart, memory rows mem_bs apart; mem_decode_attention: H heads of 64, head h at column h * 64
+ * (i2t_decode_attention's token-major layout, cache_hs = 64); mem_gq_decode_attention: Hkv key/value heads of width hd (16, 32, 64,
+ * 128) under H query heads (i2t_gq_decode_attention's layout).  No append, no position pointer, no history table, no slot_pos.  The
+ * table word is wave-uniform: it is loaded once per workgroup and folded into the base pointers; loads, lanes and reduction order are
+ * those of i2t_decode_attention / i2t_gq_decode_attention, so the output is bit-equal to theirs on the gathered memory, and with
+ * mem_index[r] = r / W to the beam forms' with rows_per_mem = W.  THE VALUES OF mem_index ARE NOT CHECKED: the caller validates
+ * 0 <= mem_index[r] < n_mem on the host before it uploads the table (caption_plan.check_image_index); the kernels do not scan it, and
+ * n_mem only takes part in the checks.  I2T_EINVAL with a message, before anything is launched: a null operand, a null mem_index,
+ * n_keys outside 1 .. 1024, n_mem < 1, rows that are not 16-byte aligned or too short for their heads, a head width outside the list. */
+int i2t_mem_decode_attention(void* stream, const void* q, int q_rs, const void* kmem, const void* vmem, long mem_bs, int mem_rs, void* o,
+                             int o_rs, int n_keys, const int* mem_index, int n_mem, int R, int H);
+int i2t_mem_gq_decode_attention(void* stream, const void* q, int q_rs, const void* kmem, const void* vmem, long mem_bs, int mem_rs, void* out,
+                                int out_rs, int n_keys, const int* mem_index, int n_mem, int R, int H, int Hkv, int hd);
 /* Sparse blocks in the decode step: a layer's cache holds only its kept positions, so the token at text position *pos_ptr uses
  * slot rank[l][pos] (= kept positions before it) and runs the block only when member[l][pos]; both tables int [L][tmax] on the
  * device.  setup writes lpos[l] / lmem[l] for the current position; i2t_select_rows picks the block's or the null connector's
