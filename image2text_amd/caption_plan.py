@@ -141,12 +141,20 @@ class GeneratedCaptions(_CaptionFields):
     image_index: Optional[torch.Tensor] = None      # int32 [Q] under ``image_index``: the image query q was asked of -- every
                                                     # "B" above is then Q, the queries; None without the argument
 
-    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None, image_index=None):
+    # under ``top_logprobs`` = K > 0, all three aligned by column as ``token_logprobs`` is; None without the argument.  A cell
+    # no step wrote -- a row's prompt columns under ``prompt_lengths``, columns past its end -- holds -1 / 0.0 / 0.0.
+    top_tokens: Optional[torch.Tensor] = None       # int32 [B, N, L - Pmin, K]: the K best tokens of the step's raw row, (z descending, id ascending)
+    top_logprobs: Optional[torch.Tensor] = None     # fp32 [B, N, L - Pmin, K]: their log-probs, ``token_logprobs``' quantity at those tokens
+    token_entropy: Optional[torch.Tensor] = None    # fp32 [B, N, L - Pmin]: the entropy of the step's raw distribution, in nats
+
+    def __new__(cls, ids, lengths, token_logprobs, logprob, prompt_lengths=None, beam_scores=None, phrase_index=None, image_index=None,
+                top_tokens=None, top_logprobs=None, token_entropy=None):
         self = super().__new__(cls, ids, lengths, token_logprobs, logprob)
         self.prompt_lengths = prompt_lengths
         self.beam_scores = beam_scores
         self.phrase_index = phrase_index
         self.image_index = image_index
+        self.top_tokens, self.top_logprobs, self.token_entropy = top_tokens, top_logprobs, token_entropy
         return self
 
 
@@ -243,20 +251,42 @@ def caption_processors(repetition_penalty: float, min_new_tokens: int, suppress_
     return Processors(theta, float(inv), min_new, tuple(suppress))
 
 
+MAX_TOP_LOGPROBS = 8                # i2t_caption_top_logprobs keeps a thread's K best in 8 register pairs (csrc/decode.hip::TOPLP_MAXK)
+
+
+def check_top_logprobs(top_logprobs, vocab: int) -> int:
+    """The refusals of ``top_logprobs`` about itself (host only, ValueError) -> K, 0 for the call without the argument.
+    In this order: not a whole number (a bool is not one); outside 0 .. MAX_TOP_LOGPROBS; more alternatives than the vocabulary holds."""
+    K = top_logprobs
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f'top_logprobs = {K!r}: a whole number of alternatives per step, from 0 (none) to {MAX_TOP_LOGPROBS}')
+    if not 0 <= int(K) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f'top_logprobs = {int(K)}: from 0 (none) to {MAX_TOP_LOGPROBS} alternatives per step (the kernel keeps a thread\'s best in '
+                         f'{MAX_TOP_LOGPROBS} register pairs)')
+    if int(K) > vocab:
+        raise ValueError(f'top_logprobs = {int(K)} alternatives of a vocabulary of {vocab} tokens')
+    return int(K)
+
+
 def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False,
-                      sets: bool = False):
+                      sets: bool = False, top_logprobs: int = 0):
     """The graph key of a ``generate_captions`` full step: everything a captured step holds as a kernel argument.  (head, eos, pad), or
     ('ragged', head, eos, pad, max_new) under ``prompt_lengths`` -- and with active processors ('proc', theta, min_new, n_suppress, P,
     ...that key): an inactive call never sees a 'proc' key.  ``P``: the prompt length the min-length count starts from (0 when ragged:
     the count then reads the device's table).  ``trie`` (a ``phrases`` call): ('trie', eos, ...that key) -- the trie's
     contents live in device buffers the step only points at, so they are no part of it; a call without phrases never sees a 'trie' key.
     ``sets`` (a ``phrase_sets`` call): ('trie_sets', eos, ...the ragged or plain key) -- the forest, the start nodes and the
-    prompt lengths are device tables; a call without ``phrase_sets`` never sees a 'trie_sets' key."""
+    prompt lengths are device tables; a call without ``phrase_sets`` never sees a 'trie_sets' key.  ``top_logprobs`` = K > 0 (DESIGN.md
+    4ad): (...that key, whichever of the above it is, 'top_logprobs', K) -- K is a kernel argument and the step points at the three result
+    buffers; the pair stands at the END, so the key still starts with the tag of every other buffer the step points at (_drop_graphs);
+    K = 0 leaves every key above as it is."""
     key = (head, eos, pad) if ragged_max_new is None else ('ragged', head, eos, pad, ragged_max_new)
     key = key if proc is None else ('proc',) + proc.key() + (0 if ragged_max_new is not None else int(P),) + key
     if sets:
-        return ('trie_sets', eos) + key
-    return ('trie', eos) + key if trie else key
+        key = ('trie_sets', eos) + key
+    elif trie:
+        key = ('trie', eos) + key
+    return tuple(key) + ('top_logprobs', int(top_logprobs)) if top_logprobs else key
 
 
 def phrase_beam_sets_graph_key(pmax: int, W: int, eos: int, length_penalty: float):
@@ -704,6 +734,7 @@ class CaptionPlan(NamedTuple):
     early_stopping: bool
     sets: Optional[PhraseSets] = None   # ``phrase_sets``: the forest, every image's set, root and longest phrase; None: no sets
     image_index: Optional[np.ndarray] = None    # int32 [Q] under ``image_index``: every "per image" above is then per query
+    top_logprobs: int = 0               # K alternatives and the entropy per step; 0: the call without the argument
 
     @property
     def rows_per_query(self) -> int:
@@ -719,7 +750,7 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
                   temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None, prompt_prefill='steps',
                   repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                   phrases=None, phrase_sets=None, phrase_set_index=None, *, sampling=..., image_index=None,
-                  images: Optional[int] = None) -> CaptionPlan:
+                  images: Optional[int] = None, top_logprobs=0) -> CaptionPlan:
     """The one place that says what ``generate_captions(...)`` on ``prompt_ids`` [B, P] means, or refuses it: the arguments are the model
     method's (``sampling``: the decoders' keyword methods hand their ``Sampling`` or None in place of the four sampling arguments).
     Refusals come in this order, the first that applies wins: ``phrase_sets`` / ``phrase_set_index``
@@ -729,9 +760,14 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
     window.  At W = 1 only ``num_beams``, ``length_penalty`` and ``early_stopping`` are looked at among the beam arguments.
     ``image_index`` / ``images`` (``images``: the images of the call, None: unknown): ``check_image_index``' ValueErrors
     come before everything above -- B is then Q, the queries, in all of it --, and its one NotImplementedError,
-    ``prompt_prefill='pass'``, after everything above; the plan carries the table."""
+    ``prompt_prefill='pass'``, after everything above; the plan carries the table.
+    ``top_logprobs`` = K: ``check_top_logprobs``' ValueErrors come right behind ``check_image_index``' and before everything
+    else; with K > 0 a NotImplementedError under num_beams > 1 right behind the beam arguments' own refusals (before the beam window), and
+    one on a non-causal decoder behind the processors' refusal there (before ``prefill_plan``'s).  Every K > 0 plan is a 'cache' plan; K = 0
+    is the call without the argument."""
     eos, pad, formed = eos_token_id, pad_token_id, []
     index = check_image_index(image_index, B, images)
+    K = check_top_logprobs(top_logprobs, facts.V)
 
     def processors():                   # caption_processors, entered once, by the first check that reaches it: its refusals keep their place
         if not formed:
@@ -750,6 +786,9 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
                                 nucleus_p=nucleus_p, seed=seed, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
                                 max_new_tokens=max_new_tokens, eos=eos, pad=pad, poll_every=poll_every, causal=facts.causal, **procs)
     N = int(num_return_sequences)
+    if W > 1 and K:
+        raise NotImplementedError('top_logprobs under num_beams > 1: the beam step\'s quantity is the row AFTER the n-gram ban, and its rows are '
+                                  'reordered between steps, so no column of the result would belong to one hypothesis')
     if W > 1:
         if P + max_new_tokens > facts.window:
             raise ValueError(f'prompt + new tokens ({P + max_new_tokens}) exceed the text window ({facts.window})')
@@ -769,11 +808,14 @@ def plan_captions(facts: CaptionFacts, B: int, P: int, max_new_tokens=128, eos_t
     if not facts.causal and proc is not None:
         raise NotImplementedError('repetition_penalty / min_new_tokens / suppress_tokens run inside the KV-cache caption step; a non-causal '
                                   'decoder generates by re-evaluation (generate_by_recompute), which has no processed step')
+    if not facts.causal and K:
+        raise NotImplementedError('top_logprobs runs inside the KV-cache caption step; a non-causal decoder generates by re-evaluation '
+                                  '(generate_by_recompute), whose loop has no such step')
     m, start = prefill_plan(prompt_prefill, pmin, facts.prefix, facts.fam, facts.causal)
     if pmax + max_new_tokens > facts.window:
         raise ValueError(f'prompt + new tokens ({pmax + max_new_tokens}) exceed the text window ({facts.window})')
     refuse_image_index_prefill(index, prompt_prefill, facts.causal)
     return CaptionPlan('cache' if facts.causal else 'recompute', N, 1, sampling, eos, (0 if eos is None else eos) if pad is None else pad,
                        poll_every, max_new_tokens, plen, pmin, pmax, prompt_prefill, m, start, proc, trie, float(length_penalty),
-                       bool(early_stopping), sets, index)
+                       bool(early_stopping), sets, index, K)
 

@@ -591,6 +591,79 @@ __global__ __launch_bounds__(64 * RAWLP_WAVES) void caption_raw_logprob_kernel(c
     }
 }
 
+// The alternatives of a caption step (generate_captions' top_logprobs), right behind the lm_head GEMM and before anything
+// writes the row: for column len = *len_ptr of row r, the K best columns of the RAW fp32 row by (z descending, id ascending), their
+// log-probs z - lse(z), and the row's entropy -sum p log p.  One workgroup per row at rows_lse_kernel's thread count, two passes over the
+// row (the second an L2 read).  Pass A: select_common.h's row_lse_partials / lse_waves_merge -- the bits i2t_rows_lse gives for the row --,
+// broadcast through LDS.  Pass B, each thread over the same columns in the same order: the entropy term p (lse - z), p = exp(z - lse)
+// (a -inf column has p = 0 and adds nothing), and the thread's K best in a sorted register list (topk_insert), a candidate first held
+// against the list's last live slot: a thread sees V / 256 columns and almost none enter.  Then K topk_round's give the row's K best in
+// order, thread 0 storing each as it is found; the entropy goes a thread's chain -> a fixed xor tree -> the waves in order.  No atomics:
+// two launches give the same bits.  Nothing is read or written once *done is set, for a finished row, for a row whose column is still
+// inside its prompt (plen, int32 [R / N], or null: no row is) or for a column outside the outputs; else exactly column len of the row's
+// three outputs is written.  Columns [V, ld) are never read.  decoding_host.top_logprobs_host is the host's statement.
+constexpr int TOPLP_THREADS = 256;                      // = TRIE_THREADS of constrain.hip's rows_lse_kernel: the lse's bits depend on it
+constexpr int TOPLP_MAXK = 8;
+__global__ __launch_bounds__(TOPLP_THREADS) void caption_top_logprobs_kernel(const float* __restrict__ logits, int ld, const int* __restrict__ len_ptr,
+                                                                             const int* __restrict__ plen, int N, const int* __restrict__ finished,
+                                                                             const int* __restrict__ done, int* __restrict__ top_tok,
+                                                                             float* __restrict__ top_lp, float* __restrict__ entropy, int out_ld,
+                                                                             int K, int V) {
+    constexpr int WAVES = TOPLP_THREADS / 64;
+    __shared__ float rmx[WAVES], rse[WAVES], sh_v[WAVES], sh_h[WAVES], sh_lse;
+    __shared__ int sh_i[WAVES], sh_win;
+    if (*done) return;                                  // block-uniform, as every return before the first barrier
+    const int r = blockIdx.x, tid = threadIdx.x, len = *len_ptr;
+    if (len < 0 || len >= out_ld || finished[r]) return;
+    if (plen && len < plen[r / N]) return;              // a forced column
+    const float* z = logits + (size_t)r * ld;
+    float mx, se;
+    row_lse_partials<TOPLP_THREADS>(z, V, mx, se, rmx, rse);
+    __syncthreads();
+    if (tid == 0) sh_lse = lse_waves_merge<TOPLP_THREADS>(mx, se, rmx, rse);
+    __syncthreads();
+    const float lse = sh_lse;
+    float kv[TOPLP_MAXK], lastv = -INFINITY, h = 0.f;
+    int ki[TOPLP_MAXK], lasti = TOPK_NONE;              // (lastv, lasti): a copy of list slot K - 1, so no register is indexed by K
+    topk_clear(kv, ki);
+    auto offer = [&](float v, int c) {
+        if (v > -INFINITY) {
+            const float dlt = lse - v;
+            h += __expf(-dlt) * dlt;
+        }
+        if (better(v, c, lastv, lasti)) {
+            topk_insert(kv, ki, K, v, c);
+#pragma unroll
+            for (int j = 0; j < TOPLP_MAXK; ++j)
+                if (j == K - 1) {
+                    lastv = kv[j];
+                    lasti = ki[j];
+                }
+        }
+    };
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
+    for (int c4 = tid * 4; c4 < vend; c4 += TOPLP_THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) offer(q[e], c4 + e);
+    }
+    for (int c = vend + tid; c < V; c += TOPLP_THREADS) offer(z[c], c);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o, 64);
+    if ((tid & 63) == 0) sh_h[tid >> 6] = h;            // read by thread 0 behind the rounds' barriers (K >= 1)
+    const size_t cell = (size_t)r * out_ld + len;
+#pragma unroll 1
+    for (int j = 0; j < K; ++j)
+        topk_round<TOPLP_THREADS>(kv, ki, sh_v, sh_i, &sh_win, [&](float bv, int bi) {
+            top_tok[cell * K + j] = bi == TOPK_NONE ? -1 : bi;      // (K <= V: every round finds a column)
+            top_lp[cell * K + j] = bv - lse;
+        });
+    if (tid == 0) {
+        for (int w = 1; w < WAVES; ++w) h += sh_h[w];
+        entropy[cell] = h;
+    }
+}
+
 __global__ void advance_kernel(int* counters, int n, int delta) {
     if ((int)threadIdx.x < n) counters[threadIdx.x] += delta;
 }
@@ -848,6 +921,21 @@ extern "C" int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids
     hipLaunchKernelGGL(caption_raw_logprob_kernel, dim3((R + RAWLP_WAVES - 1) / RAWLP_WAVES), dim3(64 * RAWLP_WAVES), 0, (hipStream_t)stream, ids,
                        ids_ld, len_ptr, raw_lse, saved, saved_ld, logits, ld, done, tok_lp, lp_ld, R, V);
     I2T_CHECK_LAUNCH("i2t_caption_raw_logprob");
+    return I2T_OK;
+}
+
+extern "C" int i2t_caption_top_logprobs(void* stream, const float* logits, int ld, const int* len_ptr, const int* plen, int N,
+                                        const int* finished, const int* done, int* top_tok, float* top_lp, float* entropy, int out_ld, int K,
+                                        int R, int V) {
+    I2T_REQUIRE(logits && len_ptr && finished && done && top_tok && top_lp && entropy, "i2t_caption_top_logprobs: null pointer");
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_caption_top_logprobs: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    I2T_REQUIRE(ALIGNED16(logits), "i2t_caption_top_logprobs: misaligned base pointer (16 bytes)");
+    I2T_REQUIRE(K >= 1 && K <= TOPLP_MAXK, "i2t_caption_top_logprobs: K = %d: from 1 to %d alternatives", K, TOPLP_MAXK);
+    I2T_REQUIRE(K <= V, "i2t_caption_top_logprobs: K = %d alternatives of a vocabulary of %d", K, V);
+    I2T_REQUIRE(out_ld > 0 && N > 0 && R > 0, "i2t_caption_top_logprobs: out_ld = %d, N = %d, R = %d: all positive", out_ld, N, R);
+    hipLaunchKernelGGL(caption_top_logprobs_kernel, dim3(R), dim3(TOPLP_THREADS), 0, (hipStream_t)stream, logits, ld, len_ptr, plen, N, finished,
+                       done, top_tok, top_lp, entropy, out_ld, K, V);
+    I2T_CHECK_LAUNCH("i2t_caption_top_logprobs");
     return I2T_OK;
 }
 

@@ -31,19 +31,19 @@ import numpy as np
 import torch
 
 from . import ops
-from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS,
+from .caption_plan import (BEAM_DEAD, DECODE_LONG_MAX_KEYS, DECODE_MAX_KEYS, LONG_CHUNK_KEYS, LONG_HEAD_DIMS, MAX_CAPTION_BEAMS, MAX_TOP_LOGPROBS,
                            PROMPT_PREFILL_MODES, BeamSpec, CaptionFacts, CaptionPlan, ClosedSet, GeneratedCaptions, PhraseBeams, PhraseScores,
                            Processors, Sampling, PhraseSets, PhraseSetScores, cache_plan, caption_graph_key, caption_processors,
                            check_beam_caption_args, check_caption_args, check_phrase_caption_args, check_phrase_score_args,
                            check_phrase_search_args, check_phrase_set_caption_args, check_phrase_set_score_args, check_phrase_sets,
-                           check_ragged_caption_args, closed_set, decode_window, held_phrase_trie, one_closed_set, per_image_closed_set,
+                           check_ragged_caption_args, check_top_logprobs, closed_set, decode_window, held_phrase_trie, one_closed_set, per_image_closed_set,
                            phrase_beam_sets_graph_key, plan_captions, plan_phrase_scores, plan_phrase_search, prefill_plan, row_images, takes_long_cache,
                            text_window, trie_widest_level)
 from .decoding_host import (_finish_rows, apply_finish_rule, apply_finish_rule_ragged, banned_log_softmax_host, beam_advance_host,
                             beam_pool_select_host, beam_search_host, constrained_decode_host, kv_prefill_host, phrase_beam_search_host,
                             phrase_scores_host, phrase_set_scores_host, process_logits_host, slot_positions, split_attention_host, trie_advance_host,
                             trie_advance_ragged_host, trie_beam_candidates_host, trie_beam_select_host, trie_beam_select_sets_host,
-                            trie_mask_host, trie_mask_ragged_host)
+                            top_logprobs_host, trie_mask_host, trie_mask_ragged_host)
 from .engine import BF16, F32, HotPath
 from .phrase_trie import (PhraseForest, PhraseTrie, SetLevelTables, TrieLevel, TrieLevels, level_expand_tables, phrase_forest, phrase_node_csr,
                           phrase_trie, set_level_tables, set_step_state, trie_levels)
@@ -460,9 +460,12 @@ class GreedyDecoder:
     @staticmethod
     def _drop_graphs(st, tag):
         """Forget the captured steps that hold a buffer about to be replaced: those whose key is a tuple that starts with ``tag`` (or with
-        one of a tuple of tags), or -- tag None -- ``generate``'s sampling steps, every key but None / 'greedy' / 'greedy_top2'."""
+        one of a tuple of tags) or -- tag 'top_logprobs' alone -- ends with ``caption_graph_key``'s ('top_logprobs', K), or -- tag None --
+        ``generate``'s sampling steps, every key but None / 'greedy' / 'greedy_top2'."""
         tags = tag if isinstance(tag, tuple) else (tag,)
-        stale = (lambda k: k not in (None, 'greedy', 'greedy_top2')) if tag is None else (lambda k: isinstance(k, tuple) and k[:1] and k[0] in tags)
+        ends = 'top_logprobs' in tags                       # the one tag that stands at a key's end, and only when it is asked for
+        tagged = lambda k: isinstance(k, tuple) and k[:1] and (k[0] in tags or (ends and k[-2:-1] == ('top_logprobs',)))
+        stale = (lambda k: k not in (None, 'greedy', 'greedy_top2')) if tag is None else tagged
         st.graphs = {k: g for k, g in st.graphs.items() if not stale(k)}
 
     def _upload_trie(self, st, trie, tag, fanout: bool = False):
@@ -823,7 +826,25 @@ class CaptionDecoder(GreedyDecoder):
         st.raw_lse = st.saved = st.suppress = None              # logits processors: f32 [R] / f32 [R, ids_ld] / int32 list, made at the first active call
         st.node = st.phrase_index = st.kept = st.trie = None    # phrases: int32 [R] / int32 [R] / f32 [R, fan-out + 1] / the four trie arrays (and raw_lse)
         st.node_init = None                                     # phrase_sets: int32 [R], every row's start node, made at the first such call
+        st.top_tok = st.top_lp = st.entropy = None              # top_logprobs: int32 / f32 [R, ids_ld, K] and f32 [R, ids_ld], made at the first such call
         return st
+
+    def _top_logprobs_state(self, st, K: int):
+        """The result buffers of a ``top_logprobs`` step, persistent because captured steps bake their pointers: st.top_tok
+        and st.top_lp (R * ids_ld * K * 4 bytes each) and st.entropy (R * ids_ld * 4 bytes), regrown -- together with the graphs tagged
+        'top_logprobs' -- only when a call asks for a larger K than they were made for.  -> (top_tok, top_lp) as this call's [R, ids_ld,
+        K]: the kernel takes K as the cells' width, so a smaller K is a view of the head of the same storage, and a step captured for
+        it points at the same base.  reset() fills the views with the values of a cell no step writes."""
+        if st.top_tok is None or st.top_tok.shape[2] < K:
+            dev = st.arena.device
+            st.top_tok = st.top_lp = None                       # the old buffers go before the new ones are made
+            st.top_tok = torch.full((st.B, st.ids_ld, K), -1, dtype=torch.int32, device=dev)
+            st.top_lp = torch.zeros(st.B, st.ids_ld, K, dtype=F32, device=dev)
+            if st.entropy is None:
+                st.entropy = torch.zeros(st.B, st.ids_ld, dtype=F32, device=dev)
+            self._drop_graphs(st, 'top_logprobs')        # (the tag stands at the END of a key: caption_graph_key)
+        n = st.B * st.ids_ld * K
+        return st.top_tok.view(-1)[:n].view(st.B, st.ids_ld, K), st.top_lp.view(-1)[:n].view(st.B, st.ids_ld, K)
 
     def _processor_state(self, st, proc: Processors):
         """The buffers of an active-processor step, persistent because captured steps bake their pointers: st.raw_lse,
@@ -859,7 +880,7 @@ class CaptionDecoder(GreedyDecoder):
             st.node_init.copy_(torch.from_numpy(np.repeat(np.asarray(roots, dtype=np.int32), st.N)))
 
     def _caption_step(self, st, sampling: Optional[Sampling], top2: bool, eos: Optional[int], pad: int, forced=None, proc=None,
-                      trie: bool = False):
+                      trie: bool = False, top=None):
         """The launches of a full step.  ``forced``: None, or (prompt, plen, max_new) of a ``prompt_lengths`` call -- the finish rule is
         then i2t_caption_finish_ragged; the choosers run as they are, on every row, and what they wrote at a forced column is replaced
         after them.  ``proc``: None, or (Processors, P) of a call with active logits processors (never with ``top2``):
@@ -867,7 +888,9 @@ class CaptionDecoder(GreedyDecoder):
         ``trie`` (a ``phrases`` or ``phrase_sets`` call; never with ``top2`` or ``proc``): i2t_caption_trie_mask before
         the chooser, which then runs without n-gram sizes -- the phrase set says what may be emitted --, i2t_caption_trie_advance after it.
         Together with ``forced`` (``phrase_sets`` under ``prompt_lengths``) the pair is i2t_caption_trie_mask_ragged /
-        i2t_caption_trie_advance_ragged, which hold a row's trie state still while its column is forced."""
+        i2t_caption_trie_advance_ragged, which hold a row's trie state still while its column is forced.  ``top``: None, or (top_tok,
+        top_lp, K) of a ``top_logprobs`` call (never with ``top2``): i2t_caption_top_logprobs right behind the GEMM, where
+        the row is still raw -- before the processors and the trie mask, which write it."""
         eng, a, dc = self.eng, self.eng.arena, self.eng.dec
         R, d = st.B, dc.d
         len_ptr, done = st.counters[1:2], st.ctrl[0:1]
@@ -880,6 +903,9 @@ class CaptionDecoder(GreedyDecoder):
                                      st.tok_lp)
         else:
             self._logits_head(st)
+            if top is not None:
+                ops.caption_top_logprobs(st.logits, dc.Vp, len_ptr, None if forced is None else forced[1], st.N, st.finished, done, top[0], top[1],
+                                         st.entropy, top[2], R, dc.V)
             if proc is not None:
                 pr, P = proc
                 ops.caption_logits_process(st.logits, dc.Vp, st.ids, st.ids_ld, len_ptr, None if forced is None else forced[1], P, st.N,
@@ -918,7 +944,7 @@ class CaptionDecoder(GreedyDecoder):
                           num_return_sequences: int = 1, sampling: Optional[Sampling] = None, poll_every: int = 8,
                           use_graph: bool = True, prompt_lengths=None, prompt_prefill: str = 'steps', repetition_penalty: float = 1.0,
                           min_new_tokens: int = 0, suppress_tokens=None, phrases=None, each=None, phrase_sets=None,
-                          phrase_set_index=None, image_index=None) -> GeneratedCaptions:
+                          phrase_set_index=None, top_logprobs: int = 0, image_index=None) -> GeneratedCaptions:
         """Row (b, n) is prompt_ids[b] and up to max_new_tokens emitted tokens.  With ``prompt_lengths`` it is prompt_ids[b, :p_b]: all
         rows share the step's column counter, and a row whose prompt reaches past the column is forced on the device (DESIGN.md 4p);
         None is the case Pmin = Pmax = P, which needs no forcing table.  ``prompt_prefill`` (``prefill_plan``): 'steps'
@@ -934,13 +960,16 @@ class CaptionDecoder(GreedyDecoder):
         over the allowed tokens only, without the n-gram ban -- and i2t_caption_trie_advance after it, under graph keys of their own;
         the result carries ``phrase_index``.  None: the call is the one without the argument.  ``phrase_sets`` / ``phrase_set_index``
         (``check_phrase_set_caption_args``): a phrase set per image -- the sets as one forest in the trie's buffers, every
-        row starting at its set's root --, with or without ``prompt_lengths``; graph keys ('trie_sets', ...).  ``each(i)`` runs after full
-        step i (tests read the step's buffers there)."""
+        row starting at its set's root --, with or without ``prompt_lengths``; graph keys ('trie_sets', ...).  ``top_logprobs`` = K
+        (``check_top_logprobs``): the K best tokens of every step's RAW row with their log-probs, and the row's entropy --
+        i2t_caption_top_logprobs between the GEMM and whatever writes the row, on the fp32-logits head whatever the decoder's width, under
+        graph keys (..., 'top_logprobs', K); the result carries ``top_tokens`` / ``top_logprobs`` / ``token_entropy``.  0: the call without
+        the argument.  ``each(i)`` runs after full step i (tests read the step's buffers there)."""
         plan = plan_captions(caption_facts(self.model), *prompt_ids.shape, max_new_tokens, eos, pad, num_return_sequences,
                              poll_every=poll_every, prompt_lengths=prompt_lengths, prompt_prefill=prompt_prefill,
                              repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, suppress_tokens=suppress_tokens,
                              phrases=phrases, phrase_sets=phrase_sets, phrase_set_index=phrase_set_index, sampling=sampling,
-                             image_index=image_index, images=len(images))
+                             image_index=image_index, images=len(images), top_logprobs=top_logprobs)
         return self.run(images, prompt_ids, plan, use_graph, each)
 
     @torch.no_grad()
@@ -956,7 +985,7 @@ class CaptionDecoder(GreedyDecoder):
         mem = (B, False) if plan.image_index is None else (len(images), True)
         N, sampling, eos, pad, poll_every, max_new_tokens = plan.N, plan.sampling, plan.eos, plan.pad, plan.poll_every, plan.max_new
         plen, pmin, pmax, proc, trie, m, start = plan.plen, plan.pmin, plan.pmax, plan.proc, plan.trie, plan.m, plan.start
-        sets = plan.sets
+        sets, K = plan.sets, plan.top_logprobs
         if sets is not None:                # the forest stands where the trie stands: the step's launches differ only under prompt_lengths
             trie = sets.forest
         ragged = plen is not None
@@ -985,7 +1014,10 @@ class CaptionDecoder(GreedyDecoder):
                 ids = torch.where(keep, prompt, torch.full((), pad, dtype=torch.long, device=a.device)).repeat_interleave(N, dim=0)
                 self.last_replays = self.last_prefill_steps = 0
                 zero = torch.zeros(B, N, pmax - pmin, dtype=F32, device=a.device)
-                return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev, image_index=index_dev)
+                none = {} if not K else dict(top_tokens=torch.full((B, N, pmax - pmin, K), -1, dtype=torch.int32, device=a.device),
+                                             top_logprobs=torch.zeros(B, N, pmax - pmin, K, dtype=F32, device=a.device), token_entropy=zero.clone())
+                return GeneratedCaptions(ids.view(B, N, pmax), len_rows.view(B, N).clone(), zero, zero.sum(dim=-1), plen_dev, image_index=index_dev,
+                                         **none)
             forced = (st.rag_prompt, st.rag_plen, max_new_tokens)
         self._prepare_inputs(st, images, mem[0], N, prefill=(prompt, m) if m else None, index=row_index)
         # 'pass': the first step is at slot prefix + m, column 1 + m; st.counters_init stays what 'steps' calls on this state start from
@@ -996,11 +1028,12 @@ class CaptionDecoder(GreedyDecoder):
             self._processor_state(st, proc)
         if trie is not None:
             self._trie_state(st, trie, None if sets is None else sets.roots)
-        top2, head = self._greedy_head(st, sampling, logits=proc is not None or trie is not None, lse=True)
+        top = None if not K else self._top_logprobs_state(st, K) + (K,)
+        top2, head = self._greedy_head(st, sampling, logits=proc is not None or trie is not None or top is not None, lse=True)
         # eos, pad and max_new_tokens are kernel arguments: a captured step holds them ('ragged': never an equal-length step's key), and
         # so are the processors' scalars ('proc': never an inactive call's key); 'trie': never a key of a call without phrases
-        # 'trie_sets': never a key of a call without phrase_sets
-        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax, trie is not None, sets is not None)
+        # 'trie_sets': never a key of a call without phrase_sets; 'top_logprobs': never a key of a call without K
+        full_key = caption_graph_key(head, eos, pad, max_new_tokens if ragged else None, proc, pmax, trie is not None, sets is not None, K)
         prompt_rows = prompt.repeat_interleave(N, dim=0) if N > 1 else prompt
 
         def reset():
@@ -1012,19 +1045,26 @@ class CaptionDecoder(GreedyDecoder):
             if trie is not None:                                # every row at the root (of its set), no phrase named yet
                 st.node.zero_() if sets is None else st.node.copy_(st.node_init)
                 st.phrase_index.fill_(-1)
+            if top is not None:                                 # what a cell no step writes holds
+                top[0].fill_(-1)
+                top[1].zero_()
+                st.entropy.zero_()
         # Pmin - 1 columns every row holds a prompt token in, then the longest prompt's row emits its last token in the last full step
         # ('pass': those columns' K/V are in the cache already, n_prefill = 0)
         self.last_prefill_steps = n_prefill
         self.last_replays = self._replay(st, full_key, lambda: self._caption_step(st, sampling, top2, eos, pad, forced, None if proc is None else (proc, pmax),
-                                                                                  trie is not None),
+                                                                                  trie is not None, top),
                                          reset, n_prefill,
                                          pmax - pmin + max_new_tokens, use_graph, each=each, poll_every=poll_every if eos is not None else 0)
         lengths = st.lengths.clone()
         L = int(lengths.max().item()) if max_new_tokens else pmax       # the final host sync
         ids = st.ids[:, :L].reshape(B, N, L).clone()
         tok_lp = st.tok_lp[:, pmin:L].reshape(B, N, L - pmin).clone()
+        cut = lambda t: t[:, pmin:L].reshape((B, N, L - pmin) + tuple(t.shape[2:])).clone()
         return GeneratedCaptions(ids, lengths.view(B, N), tok_lp, tok_lp.sum(dim=-1), plen_dev,
-                                 phrase_index=None if trie is None else st.phrase_index.view(B, N).clone(), image_index=index_dev)
+                                 phrase_index=None if trie is None else st.phrase_index.view(B, N).clone(), image_index=index_dev,
+                                 top_tokens=None if top is None else cut(top[0]), top_logprobs=None if top is None else cut(top[1]),
+                                 token_entropy=None if top is None else cut(st.entropy))
 
 
 class CaptionBeamDecoder(BeamDecoder):

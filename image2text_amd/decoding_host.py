@@ -51,6 +51,31 @@ def kv_prefill_host(src: np.ndarray, k_off: int, v_off: int, src_T: int, src_t0:
                     vcache[at:at + hd] = row[v_off + h * hd:v_off + (h + 1) * hd]
 
 
+def top_logprobs_host(logits: np.ndarray, K: int):
+    """What i2t_caption_top_logprobs computes for every row of ``logits`` [R, V] (the raw rows, any float dtype; read as given and
+    evaluated in fp64) -> (tokens int32 [R, K], logprobs fp64 [R, K], entropy fp64 [R]); DESIGN.md 4ad.  The normative statement of two
+    rules.  The TIE rule: column j of ``tokens`` is the j-th column of the row under the order (z descending, id ascending) -- equal
+    logits, the -inf ones among them, go by ascending id.  The -INF rule: a column that holds -inf has probability 0; it adds 0 to the
+    entropy, and if the list reaches it (fewer than K finite columns) its log-prob is -inf.  logprobs = z - lse(z) with lse over the
+    finite columns; entropy = sum over the finite columns of p (lse - z), p = exp(z - lse).  A row without a finite column has no
+    distribution: it is refused."""
+    z = np.asarray(logits).astype(np.float64)
+    assert z.ndim == 2 and 1 <= int(K) <= z.shape[1] and not np.isnan(z).any() and not (z == np.inf).any()
+    R, V = z.shape
+    tok, lp, ent = np.zeros((R, K), dtype=np.int32), np.zeros((R, K), dtype=np.float64), np.zeros(R, dtype=np.float64)
+    for r in range(R):
+        row = z[r]
+        order = np.lexsort((np.arange(V), -row))             # the last key is the primary one: -z ascending, then the id
+        fin = row[np.isfinite(row)]
+        assert fin.size, f'row {r} holds no finite logit'
+        m = fin.max()
+        lse = m + np.log(np.exp(fin - m).sum())
+        tok[r] = order[:K]
+        lp[r] = row[order[:K]] - lse
+        ent[r] = (np.exp(fin - lse) * (lse - fin)).sum()
+    return tok, lp, ent
+
+
 def slot_positions(member: np.ndarray) -> np.ndarray:
     """int32 [L][slots] from a sparse decoder's membership table (int [L][tmax], 1 where layer l keeps text position p): row l lists
     the text positions layer l keeps, in order, zero-padded -- the position whose K/V sit at each cache slot (slot = rank of the

@@ -260,7 +260,8 @@ class VisionEncoderDecoder(nn.Module):
     def generate_captions(self, images, prompt_ids, max_new_tokens=128, eos_token_id=None, pad_token_id=None, num_return_sequences=1,
                           temperature=1.0, top_k=None, nucleus_p=None, seed=None, poll_every=8, prompt_lengths=None,
                           prompt_prefill='steps', repetition_penalty=1.0, min_new_tokens=0, suppress_tokens=None, num_beams=1,
-                          length_penalty=1.0, early_stopping=False, phrases=None, phrase_sets=None, phrase_set_index=None, image_index=None):
+                          length_penalty=1.0, early_stopping=False, phrases=None, phrase_sets=None, phrase_set_index=None, top_logprobs=0,
+                          image_index=None):
         """``generate`` that stops at EOS, draws ``num_return_sequences`` captions per image and keeps the model's confidence (no
         counterpart in the reference) -> ``decoding.GeneratedCaptions(ids [B, N, L], lengths [B, N], token_logprobs [B, N, L - P],
         logprob [B, N])``, rows batch-major; ``ids`` is what ``generation_utils.rerank`` takes.
@@ -362,7 +363,26 @@ class VisionEncoderDecoder(nn.Module):
         Refusals, before anything runs (``caption_plan.check_image_index``): ValueError for a non-integer dtype, a length other than Q,
         a value outside [0, B), and -- without the argument -- for Q != B, which was silently mishandled before;
         NotImplementedError with ``prompt_prefill='pass'`` (that pass is one sequence per image).  A NON-causal decoder has no cache:
-        it runs the path above on ``images[image_index]``.  None (the default) is the call without the argument, launch for launch."""
+        it runs the path above on ``images[image_index]``.  None (the default) is the call without the argument, launch for launch.
+        ``top_logprobs`` = K, 1 <= K <= 8, keeps what else the model could have said at every step: the result carries
+        ``top_tokens`` (int32 [B, N, L - Pmin, K]), ``top_logprobs`` (fp32, same shape) and ``token_entropy`` (fp32 [B, N, L - Pmin]),
+        attributes beside the tuple, aligned by column exactly as ``token_logprobs`` is (under ``image_index`` B is Q); all three are None
+        without the argument.  Everything is taken from the step's RAW fp32 logits row z over the whole vocabulary [0, V) -- before the
+        logits processors, the trie mask of ``phrases`` / ``phrase_sets``, temperature, n-gram ban, top-k and nucleus: the distribution
+        ``token_logprobs`` is defined on in every non-beam mode.  ``top_tokens[..., j]`` is the j-th best column by (z descending, id
+        ascending), exact; ``top_logprobs[..., j]`` = z[id] - lse(z); ``token_entropy`` = -sum_c p_c log p_c with p_c = exp(z_c - lse(z)),
+        in nats.  A column that holds -inf contributes 0 to the entropy, and its log-prob in the list, if it gets there, is -inf
+        (``decoding_host.top_logprobs_host`` is the normative statement of both rules).  Cells that no step writes -- a row's prompt
+        columns under ``prompt_lengths``, columns past a row's end -- hold exactly -1 / 0.0 / 0.0; the column in which a row emits its EOS
+        IS written.  Every KV-cache mode works: greedy and sampled, ``num_return_sequences``, ``prompt_lengths``, both
+        ``prompt_prefill`` settings, active logits processors, ``phrases`` / ``phrase_sets`` (the alternatives are then the UNCONSTRAINED
+        model's, which is the point), ``image_index``, the long Llama-family cache.  With K > 0 the step takes the fp32-logits head
+        whatever the decoder's width, as with the processors -- a d % 128 == 0 decoder gives up the segment-maxima head's saving
+         --, and one launch (``i2t_caption_top_logprobs``) joins the step.  Refusals, before anything runs
+        (``caption_plan.plan_captions``): ValueError for a K that is not a whole number, K < 0 or K > 8, K > V; NotImplementedError with
+        ``num_beams`` > 1 (the beam step's quantity is post-ban and its rows are reordered) and on a non-causal decoder (its
+        re-evaluation loop has no such step).  0 (the default) is the call without the argument, launch for launch and graph key for
+        graph key."""
         import numpy as np
         from ..decoding import CaptionBeamDecoder, CaptionDecoder, GeneratedCaptions, caption_facts, generate_by_recompute, plan_captions
         from ..decoding_host import apply_finish_rule_ragged
@@ -370,7 +390,7 @@ class VisionEncoderDecoder(nn.Module):
         plan = plan_captions(caption_facts(self), B, P, max_new_tokens, eos_token_id, pad_token_id, num_return_sequences, temperature, top_k,
                              nucleus_p, seed, poll_every, prompt_lengths, prompt_prefill, repetition_penalty, min_new_tokens, suppress_tokens,
                              num_beams, length_penalty, early_stopping, phrases, phrase_sets, phrase_set_index, image_index=image_index,
-                             images=len(images))
+                             images=len(images), top_logprobs=top_logprobs)
         dev = next(self.parameters()).device
         prompt_ids = prompt_ids.to(dev)
         if plan.mode == 'beam':

@@ -842,6 +842,18 @@ def caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, logits, ld, done, 
     _k.i2t_caption_raw_logprob(ids, ids_ld, len_ptr, raw_lse, saved, saved.stride(0), logits, ld, done, tok_lp, tok_lp.stride(0), R, V)
 
 
+def caption_top_logprobs(logits, ld, len_ptr, plen, N, finished, done, top_tok, top_lp, entropy, K, R, V):
+    """the alternatives of a caption step on RAW fp32 logits rows, which are only read: column *len_ptr of top_tok (int32 [R, out_ld, K]:
+    the K best columns by (z descending, id ascending)), top_lp (f32, same shape: z - the row's rows_lse value) and entropy (f32 [R,
+    out_ld]); nothing for a finished row, a row in a forced column (plen int32 [R / N], or None: no row is), a column outside the
+    outputs, or once *done (include/i2t.h::i2t_caption_top_logprobs)"""
+    assert top_tok.dim() == 3 and top_tok.is_contiguous() and top_lp.is_contiguous() and top_tok.shape == top_lp.shape
+    assert top_tok.shape[0] >= R and top_tok.shape[2] == K and entropy.is_contiguous() and tuple(entropy.shape) == tuple(top_tok.shape[:2])
+    assert finished.is_contiguous() and finished.numel() >= R
+    assert plen is None or (plen.is_contiguous() and (N < 1 or plen.numel() >= -(-R // N)))
+    _k.i2t_caption_top_logprobs(logits, ld, len_ptr, plen, int(N), finished, done, top_tok, top_lp, entropy, top_tok.shape[1], int(K), R, V)
+
+
 def _trie_args(child_off, child_tok, term, child_next=None):
     """the shared checks of the trie kernels: int32 CSR arrays on the device -> (nodes, edges) the arrays hold"""
     arrays = (child_off, child_tok, term) + (() if child_next is None else (child_next,))

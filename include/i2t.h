@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 20
+#define I2T_ABI_VERSION 21
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -486,6 +486,17 @@ int i2t_caption_logits_process(void* stream, float* logits, int ld, const int64_
                                const int* done, float* raw_lse, float* saved, int saved_ld, int R, int V);
 int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids_ld, const int* len_ptr, const float* raw_lse, const float* saved,
                             int saved_ld, const float* logits, int ld, const int* done, float* tok_lp, int lp_ld, int R, int V);
+/* The alternatives of a caption step (generate_captions' top_logprobs; DESIGN.md 4ad, ABI 21), after the lm_head GEMM and before
+ * anything writes the row.  Per row r of logits f32 [R][ld] (ld >= V, ld % 4 == 0, base on 16 bytes), one workgroup, with len =
+ * *len_ptr: top_tok[r][len][j] (int32 [R][out_ld][K]) = the j-th best column of the RAW row z over [0, V) by (z descending, id
+ * ascending), exact; top_lp[r][len][j] (f32, same shape) = z[that column] - lse, lse = log sum_c exp(z[c]) with i2t_rows_lse's bits
+ * for the row and ONE fp32 subtraction (-inf for a column that holds -inf); entropy[r][len] (f32 [R][out_ld]) = sum_c p_c (lse - z[c]),
+ * p_c = exp(z[c] - lse), a -inf column adding 0, reduced in a fixed order (no atomics: bit-reproducible).  1 <= K <= 8, K <= V.
+ * Returns at once if *done; writes nothing for a row with finished[r], for a row whose column is still inside its prompt (plen int32
+ * [R / N], device memory, non-null and len < plen[r / N]) and when len >= out_ld; else exactly column len of the row's three outputs.
+ * Columns [V, ld) are never read.  The row is only read. */
+int i2t_caption_top_logprobs(void* stream, const float* logits, int ld, const int* len_ptr, const int* plen, int N, const int* finished,
+                             const int* done, int* top_tok, float* top_lp, float* entropy, int out_ld, int K, int R, int V);
 /* Closed-set decoding (generate_captions' phrases; DESIGN.md 4u, ABI 13): every row emits one phrase of a set and then EOS.  The set is
  * a flat CSR trie in device memory, all int32: the children of node n are edges child_off[n] .. child_off[n + 1) (child_off [nodes + 1]),
  * child_tok [edges] ascending within a node, child_next [edges] the node an edge leads to, term [nodes] the index of the phrase that
