@@ -2,6 +2,7 @@
 the window and cache planners, the refusals of ``generate_captions`` / ``score_phrases`` / ``search_phrases`` and -- composing them -- ``plan_captions``, the
 one function that resolves a ``generate_captions`` call into a ``CaptionPlan``; the result tuples and the graph key beside them.  numpy,
 and torch only to accept tensors; no device, engine or library.  ``decoding`` re-exports every name."""
+import math
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -266,6 +267,23 @@ def check_top_logprobs(top_logprobs, vocab: int) -> int:
     if int(K) > vocab:
         raise ValueError(f'top_logprobs = {int(K)} alternatives of a vocabulary of {vocab} tokens')
     return int(K)
+
+
+def check_score_top_logprobs(top_logprobs, temperature, vocab: int) -> int:
+    """The refusals of ``score(..., top_logprobs=K)`` (host only, ValueError) -> K, 0 for the call without the argument:
+    ``check_top_logprobs``' about K itself, then -- with K > 0 only, the call without the argument keeps taking what it took -- a
+    temperature that is not a finite positive number: the kernel scales the row by fp32(1 / temperature) and refuses anything else."""
+    K = check_top_logprobs(top_logprobs, vocab)
+    if K:
+        try:
+            t = float(temperature)
+        except (TypeError, ValueError):
+            t = float('nan')
+        # (fp32's range: the smallest subnormal and the largest finite number)
+        if not (math.isfinite(t) and t > 0 and 2.0 ** -149 <= 1.0 / t <= (2.0 - 2.0 ** -23) * 2.0 ** 127):
+            raise ValueError(f'temperature = {temperature!r} with top_logprobs = {K}: a finite positive number whose reciprocal is one in fp32 '
+                             f'(the rows are scaled by fp32(1 / temperature))')
+    return K
 
 
 def caption_graph_key(head, eos, pad, ragged_max_new: Optional[int] = None, proc: Optional[Processors] = None, P: int = 0, trie: bool = False,

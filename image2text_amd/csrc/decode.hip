@@ -664,6 +664,90 @@ __global__ __launch_bounds__(TOPLP_THREADS) void caption_top_logprobs_kernel(con
     }
 }
 
+// The same for a caption that is GIVEN (VisionEncoderDecoder.score's top_logprobs), behind the fp32 lm_head GEMM of a chunk
+// of teacher-forced rows: for every row r, on v = z * scale (mul_rounded: one fp32 rounding per column, the same number wherever it is
+// used), the K best columns by (v descending, id ascending), their log-probs v - lse(v), the entropy, the row's lse, and for the row's
+// label y the log-prob v_y - lse and the RANK: the number of columns strictly ahead of y in that order.  The kernel above with the
+// label's two outputs added and no step state: one workgroup per row, pass A the shared fixed-order lse on the scaled row (at scale 1
+// the bits i2t_rows_lse gives), pass B over the same columns in the same order with the entropy term, the thread's sorted K-list and an
+// integer count of better(v_c, c, v_y, y) -- v_y is loaded once before the pass; integer sums are order-free --, then K topk_round's
+// and thread 0's stores.  The list entry at the label's rank and the label's log-prob are the same subtraction on the same two numbers:
+// the same bits.  A label that is ignore_index or outside [0, V) gives rank -1 and logprob 0 and counts nothing; every row gets the
+// other outputs.  No atomics.  Columns [V, ld) are never read.  decoding_host.score_top_logprobs_host is the host's statement.
+__global__ __launch_bounds__(TOPLP_THREADS) void score_top_logprobs_kernel(const float* __restrict__ logits, int ld, float scale,
+                                                                           const int64_t* __restrict__ labels, int64_t ignore_index,
+                                                                           int* __restrict__ top_tok, float* __restrict__ top_lp,
+                                                                           float* __restrict__ entropy, int* __restrict__ rank,
+                                                                           float* __restrict__ lse_out, float* __restrict__ logprob, int K, int V) {
+    constexpr int WAVES = TOPLP_THREADS / 64;
+    __shared__ float rmx[WAVES], rse[WAVES], sh_v[WAVES], sh_h[WAVES], sh_lse;
+    __shared__ int sh_i[WAVES], sh_n[WAVES], sh_win;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float* z = logits + (size_t)r * ld;
+    const int64_t lab = labels[r];
+    const bool live = lab != ignore_index && lab >= 0 && lab < V;       // block-uniform
+    const int y = live ? (int)lab : 0;
+    const float vy = live ? mul_rounded(z[y], scale) : 0.f;
+    float mx, se;
+    row_lse_partials_scaled<TOPLP_THREADS>(z, V, scale, mx, se, rmx, rse);
+    __syncthreads();
+    if (tid == 0) sh_lse = lse_waves_merge<TOPLP_THREADS>(mx, se, rmx, rse);
+    __syncthreads();
+    const float lse = sh_lse;
+    float kv[TOPLP_MAXK], lastv = -INFINITY, h = 0.f;
+    int ki[TOPLP_MAXK], lasti = TOPK_NONE, ahead = 0;   // (lastv, lasti): a copy of list slot K - 1, so no register is indexed by K
+    topk_clear(kv, ki);
+    auto offer = [&](float zc, int c) {
+        const float v = mul_rounded(zc, scale);
+        if (v > -INFINITY) {
+            const float dlt = lse - v;
+            h += __expf(-dlt) * dlt;
+        }
+        ahead += live && better(v, c, vy, y);
+        if (better(v, c, lastv, lasti)) {
+            topk_insert(kv, ki, K, v, c);
+#pragma unroll
+            for (int j = 0; j < TOPLP_MAXK; ++j)
+                if (j == K - 1) {
+                    lastv = kv[j];
+                    lasti = ki[j];
+                }
+        }
+    };
+    const int vend = V & ~3;                            // (ld % 4 == 0 and a 16-byte base: the entry point's checks)
+    for (int c4 = tid * 4; c4 < vend; c4 += TOPLP_THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) offer(q[e], c4 + e);
+    }
+    for (int c = vend + tid; c < V; c += TOPLP_THREADS) offer(z[c], c);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        h += __shfl_xor(h, o, 64);
+        ahead += __shfl_xor(ahead, o, 64);
+    }
+    if ((tid & 63) == 0) {                              // read by thread 0 behind the rounds' barriers (K >= 1)
+        sh_h[tid >> 6] = h;
+        sh_n[tid >> 6] = ahead;
+    }
+#pragma unroll 1
+    for (int j = 0; j < K; ++j)
+        topk_round<TOPLP_THREADS>(kv, ki, sh_v, sh_i, &sh_win, [&](float bv, int bi) {
+            top_tok[(size_t)r * K + j] = bi == TOPK_NONE ? -1 : bi;     // (K <= V: every round finds a column)
+            top_lp[(size_t)r * K + j] = bv - lse;
+        });
+    if (tid == 0) {
+        for (int w = 1; w < WAVES; ++w) {
+            h += sh_h[w];
+            ahead += sh_n[w];
+        }
+        entropy[r] = h;
+        lse_out[r] = lse;
+        rank[r] = live ? ahead : -1;
+        logprob[r] = live ? vy - lse : 0.f;
+    }
+}
+
 __global__ void advance_kernel(int* counters, int n, int delta) {
     if ((int)threadIdx.x < n) counters[threadIdx.x] += delta;
 }
@@ -936,6 +1020,21 @@ extern "C" int i2t_caption_top_logprobs(void* stream, const float* logits, int l
     hipLaunchKernelGGL(caption_top_logprobs_kernel, dim3(R), dim3(TOPLP_THREADS), 0, (hipStream_t)stream, logits, ld, len_ptr, plen, N, finished,
                        done, top_tok, top_lp, entropy, out_ld, K, V);
     I2T_CHECK_LAUNCH("i2t_caption_top_logprobs");
+    return I2T_OK;
+}
+
+extern "C" int i2t_score_top_logprobs(void* stream, const float* logits, int ld, float scale, const int64_t* labels, int64_t ignore_index,
+                                      int* top_tok, float* top_lp, float* entropy, int* rank, float* lse, float* logprob, int K, int R, int V) {
+    I2T_REQUIRE(logits && labels && top_tok && top_lp && entropy && rank && lse && logprob, "i2t_score_top_logprobs: null pointer");
+    I2T_REQUIRE(ld >= V && ld % 4 == 0, "i2t_score_top_logprobs: ld = %d: logits rows hold V = %d columns and start on 16 bytes", ld, V);
+    I2T_REQUIRE(ALIGNED16(logits), "i2t_score_top_logprobs: misaligned base pointer (16 bytes)");
+    I2T_REQUIRE(K >= 1 && K <= TOPLP_MAXK, "i2t_score_top_logprobs: K = %d: from 1 to %d alternatives", K, TOPLP_MAXK);
+    I2T_REQUIRE(K <= V, "i2t_score_top_logprobs: K = %d alternatives of a vocabulary of %d", K, V);
+    I2T_REQUIRE(R > 0, "i2t_score_top_logprobs: R = %d rows", R);
+    I2T_REQUIRE(scale > 0.f && scale < INFINITY, "i2t_score_top_logprobs: scale = %g: finite and positive", (double)scale);
+    hipLaunchKernelGGL(score_top_logprobs_kernel, dim3(R), dim3(TOPLP_THREADS), 0, (hipStream_t)stream, logits, ld, scale, labels, ignore_index,
+                       top_tok, top_lp, entropy, rank, lse, logprob, K, V);
+    I2T_CHECK_LAUNCH("i2t_score_top_logprobs");
     return I2T_OK;
 }
 

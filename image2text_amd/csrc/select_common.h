@@ -32,6 +32,27 @@ __device__ __forceinline__ void row_lse_partials(const float* z, int V, float& m
     for (int c = vend + tid; c < V; c += THREADS) lse_add(mx, se, z[c]);
     lse_wave_store(mx, se, rmx, rse);
 }
+// a * b rounded to fp32 ON ITS OWN: the build contracts a plain product into the fma of whatever addition consumes it, and a value that
+// is compared, listed and subtracted from in several places must be one number in all of them.  A constrained multiply is never fused.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp exceptions(strict)
+    return a * b;
+}
+// Part one on the SCALED row v = mul_rounded(z, scale): the same columns, chain and tree.  At scale == 1.0f v is z, so the partials
+// are row_lse_partials' bits.
+template <int THREADS>
+__device__ __forceinline__ void row_lse_partials_scaled(const float* z, int V, float scale, float& mx, float& se, float* rmx, float* rse) {
+    const int tid = threadIdx.x, vend = V & ~3;
+    mx = -INFINITY;
+    se = 0.f;
+    for (int c4 = tid * 4; c4 < vend; c4 += THREADS * 4) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(z + c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lse_add(mx, se, mul_rounded(q[e], scale));
+    }
+    for (int c = vend + tid; c < V; c += THREADS) lse_add(mx, se, mul_rounded(z[c], scale));
+    lse_wave_store(mx, se, rmx, rse);
+}
 // Part two, thread 0 after the barrier: its own wave's pair, then waves 1 .. THREADS / 64 - 1 in order.
 template <int THREADS>
 __device__ __forceinline__ float lse_waves_merge(float mx, float se, const float* rmx, const float* rse) {

@@ -76,6 +76,37 @@ def top_logprobs_host(logits: np.ndarray, K: int):
     return tok, lp, ent
 
 
+def score_top_logprobs_host(logits: np.ndarray, labels, K: int, scale: float = 1.0, ignore_index: int = -100):
+    """What i2t_score_top_logprobs computes for every row of ``logits`` [R, V] with ``labels`` [R] -> (tokens int32 [R, K],
+    logprobs fp64 [R, K], entropy fp64 [R], rank int32 [R], lse fp64 [R], label_logprob fp64 [R]).  The row the kernel works on is
+    v = np.float32(z) * np.float32(scale), formed in fp32: the kernel's one rounding per column, so the order and the ties are the
+    kernel's; everything after that is evaluated in fp64 by ``top_logprobs_host``'s TIE rule and -INF rule.  rank[r] = the number of
+    columns c with v[c] > v[y] or (v[c] == v[y] and c < y), y = labels[r]: the label's place in the order the tokens are listed in (0:
+    the arg-max), so rank < K puts y at tokens[r, rank]; a label on a -inf column has log-prob -inf and stands behind every finite
+    column and the -inf columns of lower id.  A label equal to ``ignore_index`` or outside [0, V): rank -1, label_logprob 0.0."""
+    z = np.asarray(logits)
+    assert z.ndim == 2 and np.isfinite(np.float32(scale)) and np.float32(scale) > 0
+    v = z.astype(np.float32) * np.float32(scale)
+    assert v.dtype == np.float32
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    R, V = v.shape
+    assert labels.shape == (R,)
+    tok, lp, ent = top_logprobs_host(v, K)
+    v64 = v.astype(np.float64)
+    rank, lse, lab_lp = np.full(R, -1, dtype=np.int32), np.zeros(R, dtype=np.float64), np.zeros(R, dtype=np.float64)
+    ids = np.arange(V)
+    for r in range(R):
+        fin = v64[r][np.isfinite(v64[r])]
+        m = fin.max()
+        lse[r] = m + np.log(np.exp(fin - m).sum())
+        y = int(labels[r])
+        if y == ignore_index or not 0 <= y < V:
+            continue
+        rank[r] = int(((v[r] > v[r, y]) | ((v[r] == v[r, y]) & (ids < y))).sum())
+        lab_lp[r] = v64[r, y] - lse[r]
+    return tok, lp, ent, rank, lse, lab_lp
+
+
 def slot_positions(member: np.ndarray) -> np.ndarray:
     """int32 [L][slots] from a sparse decoder's membership table (int [L][tmax], 1 where layer l keeps text position p): row l lists
     the text positions layer l keeps, in order, zero-padded -- the position whose K/V sit at each cache slot (slot = rank of the

@@ -1061,7 +1061,7 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
         ops.gemm(hb, self.arena.W(self.n_head), buf, M, self.dec.V, self.dec.d)
         return buf
 
-    SCORE_WS_BYTES = 256 << 20      # cap of the scoring workspace (segment statistics, or the fallback's bf16 logits chunk)
+    SCORE_WS_BYTES = 256 << 20      # cap of the scoring workspace (segment statistics, the fallback's bf16 logits chunk, token_top_logprobs' fp32 one)
 
     def _score_ws(self, kind: str, rows: int, cols: int, dtype):
         """cached [rows, cols] scratch of token_logprobs (grown, never shrunk; dropped with the arena)"""
@@ -1114,6 +1114,36 @@ class HotPath(FamilyBlocks, LlamaBlocks, LoraAdapters, ViTEncoder):
             z = buf[:n].gather(1, col[r0:r0 + n, None])[:, 0].float() * inv_temp
             logprob[r0:r0 + n] = torch.where(live[r0:r0 + n], z - lse[r0:r0 + n], torch.zeros_like(z))
         return logprob, lse
+
+    def token_top_logprobs(self, hb: torch.Tensor, labels: torch.Tensor, M: int, K: int, inv_temp: float = 1.0, ignore_index: int = -100,
+                           each=None):
+        """token_logprobs with what else every row could have said: on v = fp32(z . inv_temp), z = the RAW fp32 logits
+        hb . W_head^T of a row -> (logprob f32 [M], lse f32 [M], top_tok int32 [M, K], top_lp f32 [M, K], entropy f32 [M], rank int32
+        [M]), all six from one pass over the same fp32 rows (ops.score_top_logprobs).  Every decoder width takes this one form, the
+        fp32 lm_head the decode step's ``_logits_head`` runs followed by the kernel: the rows are walked in chunks whose fp32 logits
+        scratch [chunk, Vp] stays within SCORE_WS_BYTES -- a multiple of 256 rows where that many fit, whatever fits (at least one
+        row) where they do not --, so nothing V-wide outlives a chunk.  ``each(r0, n, logits)``, when given, is called behind the
+        kernel of every chunk with the chunk's first row, its rows and the scratch that holds them (the tests' hook)."""
+        a, dc = self.arena, self.dec
+        W = a.W(self.n_head)
+        labels = labels.to(device=a.device, dtype=torch.long).contiguous().view(-1)
+        assert labels.numel() == M and hb.shape[0] >= M and hb.dtype == BF16 and 1 <= K <= min(8, dc.V)
+        logprob, lse, entropy = self._empty(M), self._empty(M), self._empty(M)
+        rank = self._empty(M, dtype=torch.int32)
+        top_tok, top_lp = self._empty(M, K, dtype=torch.int32), self._empty(M, K)
+        if M == 0:
+            return logprob, lse, top_tok, top_lp, entropy, rank
+        chunk = self.SCORE_WS_BYTES // (dc.Vp * 4)
+        chunk = chunk // 256 * 256 if chunk >= 256 else max(1, chunk)
+        buf = self._score_ws('logits32', min(chunk, M), dc.Vp, F32)         # (pad columns zero and never written or read)
+        for r0 in range(0, M, chunk):
+            n = min(chunk, M - r0)
+            ops.gemm(hb[r0:r0 + n], W, buf[:n], n, dc.V, dc.d)
+            ops.score_top_logprobs(buf[:n], dc.Vp, labels[r0:r0 + n], top_tok[r0:r0 + n], top_lp[r0:r0 + n], entropy[r0:r0 + n],
+                                   rank[r0:r0 + n], lse[r0:r0 + n], logprob[r0:r0 + n], K, n, dc.V, scale=inv_temp, ignore_index=ignore_index)
+            if each is not None:
+                each(r0, n, buf[:n])
+        return logprob, lse, top_tok, top_lp, entropy, rank
 
     @staticmethod
     def _lockstep(*gens):

@@ -109,6 +109,7 @@ SIGNATURES = {
     'i2t_caption_logits_process': [P, PF, I, PL, I, PI, PI, I, I, PI, I, I, I, F, F, PI, PF, PF, I, I, I],
     'i2t_caption_raw_logprob': [P, PL, I, PI, PF, PF, I, PF, I, PI, PF, I, I, I],
     'i2t_caption_top_logprobs': [P, PF, I, PI, PI, I, PI, PI, PI, PF, PF, I, I, I, I],
+    'i2t_score_top_logprobs': [P, PF, I, F, PL, I64, PI, PF, PF, PI, PF, PF, I, I, I],
     'i2t_caption_trie_mask': [P, PF, I, PI, PI, PI, PI, I, I, I, PI, PF, PF, I, I, I],
     'i2t_caption_trie_advance': [P, PL, I, PI, PI, PF, I, PF, PI, PI, PI, PI, I, I, I, PI, PI, PI, PF, I, I, I],
     'i2t_rows_lse': [P, PF, I, PF, I, I],
@@ -194,7 +195,7 @@ SIGNATURES = {
     'i2t_graph_destroy': [P],
 }
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lib = None
 
 

@@ -511,12 +511,29 @@ class VisionEncoderDecoder(nn.Module):
                                                                         int(eos_token_id), W, N, float(length_penalty), int(poll_every))
 
     @torch.no_grad()
-    def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100) -> CaptionScores:
+    def score(self, images, ids, labels=None, temperature=1.0, encoder_output=None, ignore_index=-100, *, top_logprobs=0) -> CaptionScores:
         """Log-likelihood of given captions (no counterpart in the reference): ``token_logprobs[b, t]`` is
         ``log_softmax(self(images, ids).logits[b, t].float() / temperature)[labels[b, t]]`` and 0 where ``labels[b, t]`` is
         ``ignore_index`` (or no token id); ``labels=None`` scores every token given its predecessors (``next_token_labels``).
         Same decoder calls and block-size crop as ``forward``; the encoder runs once, or not at all when ``encoder_output`` is given.
-        The logits are not materialised when the decoder width allows (``HotPath.token_logprobs``)."""
+        The logits are not materialised when the decoder width allows (``HotPath.token_logprobs``).
+        ``top_logprobs`` = K, 1 <= K <= 8, adds the teacher-forced diagnostics of every position, as attributes beside
+        the three tuple fields (all None without the argument), on the position's row v = fp32(z . fp32(1 / temperature)), z its raw
+        fp32 logits: ``top_tokens`` (int32 [B, T, K]) the K best columns by (v descending, id ascending), exact; ``top_logprobs`` (fp32
+        [B, T, K]) = v[token] - lse(v); ``token_entropy`` (fp32 [B, T]) = -sum p log p of softmax(v), in nats; ``label_rank`` (int32
+        [B, T]) the number of columns strictly ahead of the label in that order -- 0: the label is the arg-max, so ``label_rank < k``
+        is top-k token accuracy --, -1 where the label is ignored.  Every position gets the first three, whatever its label;
+        ``label_rank`` and ``token_logprobs`` follow the label rule above.  With K > 0 ``token_logprobs``, ``lse`` and ``logprob`` come
+        from the same pass over the same fp32 rows: where ``label_rank[b, t] < K``, ``top_tokens[b, t, rank]`` is the label and
+        ``top_logprobs[b, t, rank]`` and ``token_logprobs[b, t]`` are the same bits.  They are CLOSE to, not bit-equal with, the values
+        of the call without the argument, which come from bf16 logits or from segment statistics.  Nothing V-wide outlives a chunk of
+        rows (``HotPath.token_top_logprobs``): the fp32-logits head on every decoder width -- a d % 128 == 0 decoder gives up the
+        segment-statistics head --, then ``i2t_score_top_logprobs``.  Refusals, before anything is launched
+        (``caption_plan.check_score_top_logprobs``): ValueError for a K that is not a whole number, K outside 0 .. 8, K > V, and --
+        with K > 0 -- a temperature that is not finite and positive.  0 (the default) is the call without the argument, launch for
+        launch.  ``decoding_host.score_top_logprobs_host`` is the normative statement."""
+        from ..caption_plan import check_score_top_logprobs
+        K = check_score_top_logprobs(top_logprobs, temperature, self._engine.dec.V)
         dev = next(self.parameters()).device
         ids = ids.to(dev)
         labels = next_token_labels(ids, ignore_index) if labels is None else labels.to(dev)
@@ -538,6 +555,12 @@ class VisionEncoderDecoder(nn.Module):
         else:
             _, hb, _ = eng.decode_segment(B, T, mem, ncls, False, ids=ids[:, :T], pos_offset=off)
         T = hb.shape[0] // B
+        if K:
+            lp, lse, tok, tlp, ent, rank = eng.token_top_logprobs(hb, labels[:, :T].contiguous().view(B * T), B * T, K, 1.0 / temperature,
+                                                                  ignore_index)
+            lp = lp.view(B, T)
+            return CaptionScores(lp, lse.view(B, T), lp.sum(dim=1), top_tokens=tok.view(B, T, K), top_logprobs=tlp.view(B, T, K),
+                                 token_entropy=ent.view(B, T), label_rank=rank.view(B, T))
         lp, lse = eng.token_logprobs(hb, labels[:, :T].contiguous().view(B * T), B * T, 1.0 / temperature, ignore_index)
         lp = lp.view(B, T)
         return CaptionScores(token_logprobs=lp, lse=lse.view(B, T), logprob=lp.sum(dim=1))

@@ -854,6 +854,19 @@ def caption_top_logprobs(logits, ld, len_ptr, plen, N, finished, done, top_tok, 
     _k.i2t_caption_top_logprobs(logits, ld, len_ptr, plen, int(N), finished, done, top_tok, top_lp, entropy, top_tok.shape[1], int(K), R, V)
 
 
+def score_top_logprobs(logits, ld, labels, top_tok, top_lp, entropy, rank, lse, logprob, K, R, V, scale=1.0, ignore_index=-100):
+    """the alternatives, entropy, lse and label rank / log-prob of R teacher-forced fp32 logits rows, which are only read, on v = z * scale
+    (one fp32 rounding per column): top_tok (int32 [R, K]: the K best columns by (v descending, id ascending)), top_lp (f32 [R, K]: v -
+    lse), entropy / lse / logprob (f32 [R]) and rank (int32 [R]: columns strictly ahead of labels[r], -1 and logprob 0 for an ignored
+    or out-of-range label) (include/i2t.h::i2t_score_top_logprobs)"""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) == ld and logits.shape[0] >= R
+    assert top_tok.dim() == 2 and top_tok.is_contiguous() and top_lp.is_contiguous() and top_tok.shape == top_lp.shape
+    assert top_tok.shape[0] >= R and top_tok.shape[1] == K and labels.is_contiguous() and labels.numel() >= R
+    for t in (entropy, rank, lse, logprob):
+        assert t.is_contiguous() and t.numel() >= R
+    _k.i2t_score_top_logprobs(logits, ld, float(scale), labels, int(ignore_index), top_tok, top_lp, entropy, rank, lse, logprob, int(K), R, V)
+
+
 def _trie_args(child_off, child_tok, term, child_next=None):
     """the shared checks of the trie kernels: int32 CSR arrays on the device -> (nodes, edges) the arrays hold"""
     arrays = (child_off, child_tok, term) + (() if child_next is None else (child_next,))

@@ -27,7 +27,7 @@ extern "C" {
 #define I2T_EINVAL (-1)   /* bad argument (shape/alignment/unsupported size) */
 #define I2T_EHIP (-2)     /* a HIP runtime call failed */
 
-#define I2T_ABI_VERSION 21
+#define I2T_ABI_VERSION 22
 
 int i2t_abi_version(void);
 /* copies the last error message of the calling thread into buf (NUL-terminated); returns its length */
@@ -497,6 +497,19 @@ int i2t_caption_raw_logprob(void* stream, const int64_t* ids, int ids_ld, const 
  * Columns [V, ld) are never read.  The row is only read. */
 int i2t_caption_top_logprobs(void* stream, const float* logits, int ld, const int* len_ptr, const int* plen, int N, const int* finished,
                              const int* done, int* top_tok, float* top_lp, float* entropy, int out_ld, int K, int R, int V);
+/* The same for captions that are GIVEN (VisionEncoderDecoder.score's top_logprobs; DESIGN.md 4ae, ABI 22), behind the fp32 lm_head GEMM
+ * of a chunk of teacher-forced rows.  Per row r of logits f32 [R][ld] (ld >= V, ld % 4 == 0, base on 16 bytes), one workgroup, on
+ * v[c] = fp32(z[c] * scale), ONE rounded fp32 multiply per column (scale finite and positive; at scale 1 v is z): top_tok[r][j] (int32
+ * [R][K]) = the j-th best column over [0, V) by (v descending, id ascending), exact; top_lp[r][j] (f32 [R][K]) = v[that column] -
+ * lse[r] in ONE fp32 subtraction (-inf for a column that holds -inf); lse[r] = log sum_c exp(v[c]) in i2t_rows_lse's order -- at
+ * scale 1 its bits for the row --; entropy[r] = sum_c p_c (lse - v[c]), p_c = exp(v[c] - lse), a -inf column adding 0, reduced in a
+ * fixed order.  With y = labels[r] (int64 [R], device memory): rank[r] (int32) = the number of columns strictly ahead of y in that
+ * order -- 0: y is the arg-max; where rank[r] < K, top_tok[r][rank[r]] == y -- and logprob[r] = v[y] - lse[r], the same bits as
+ * top_lp[r][rank[r]] there, -inf where column y holds -inf.  y == ignore_index or outside [0, V): rank -1, logprob 0.0; the row's
+ * other outputs are written all the same.  1 <= K <= 8, K <= V, R > 0.  No atomics: two launches give the same bits.  Columns
+ * [V, ld) are never read.  The rows are only read; a refused call writes nothing. */
+int i2t_score_top_logprobs(void* stream, const float* logits, int ld, float scale, const int64_t* labels, int64_t ignore_index, int* top_tok,
+                           float* top_lp, float* entropy, int* rank, float* lse, float* logprob, int K, int R, int V);
 /* Closed-set decoding (generate_captions' phrases; DESIGN.md 4u, ABI 13): every row emits one phrase of a set and then EOS.  The set is
  * a flat CSR trie in device memory, all int32: the children of node n are edges child_off[n] .. child_off[n + 1) (child_off [nodes + 1]),
  * child_tok [edges] ascending within a node, child_next [edges] the node an edge leads to, term [nodes] the index of the phrase that
